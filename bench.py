@@ -39,6 +39,10 @@ kernel does, where a traffic figure comes from, the CPU sample in words — goes
                         "bf16" = bf16 logits on bf16 observations; each with an MFMA roofline object for the MLP launch.
   cpu_baseline        — the oracle (CPU restatement of the reference path, torch CPU) timed on this host's cores on a
                         bounded sample of the same workload (rank 0, N=1 only). A reported baseline, not a target.
+
+``--dump-outputs DIR`` also writes what the last timed iteration computed — parameters, losses, rollout buffers, final
+environment state — as DIR/<name>.npy (float32, finite, seeded samples of the large arrays, 64 MB at most). The inputs
+depend on the arguments alone, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -101,7 +105,7 @@ def parse():
     ap.add_argument("--edges", type=int, default=10000)
     ap.add_argument("--agents", type=int, default=16384)
     ap.add_argument("--envs", type=int, default=32768,
-                    help="vectorised environments per GPU (32 768: 150 GB of the 288; 16 384 until round 5: -6 % env-steps/s)")
+                    help="vectorised environments per GPU (32 768: 150 GB of the 288; 16 384 until round 5: -6 %% env-steps/s)")
     ap.add_argument("--rollout-steps", type=int, default=256)
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--sub-batch", type=int, default=32)
@@ -135,7 +139,13 @@ def parse():
                     help="do not bracket the frame kernels with HIP events (PMC / kernel-trace passes)")
     ap.add_argument("--details", type=str, default=os.path.join("gpurun_out", "bench_details.json"),
                     help="sidecar file with every descriptive field (relative to the repo root; '' = stderr only)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed PPO iteration computed as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of the larger arrays; rank 0's outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_network(edges):
@@ -357,6 +367,47 @@ def time_iterations(trainer, steps, L, T, prof, device, run=None):
     return frames, elapsed, mine, (list(ms_all), list(ms_late), list(nfr))
 
 
+DUMP_BYTES = 64 << 20            # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20            # elements kept of an array larger than this (a seeded sample of flat positions)
+
+
+def dump_sample(a, k=None, seed=0):
+    """``a`` flattened, as float32 on the host: whole if it has at most ``k`` elements, else ``k`` flat positions drawn
+    with a fixed seed (sorted). The positions depend on the element count alone, so two builds sample the same ones."""
+    k = DUMP_SAMPLE if k is None else k
+    flat = a.view(-1)                # (no silent copy of a multi-GB array)
+    if flat.numel() > k:
+        idx = torch.randint(flat.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+        flat = flat.index_select(0, idx.to(flat.device))
+    return flat.to("cpu", torch.float32).numpy()
+
+
+def dump_outputs(path, trainer, engine):
+    """What the last ``train_iteration`` left its caller: the parameters after the update and its losses, the rollout
+    buffers (rewards, log-probs, critic values, clock times, count and action bytes, leg histogram) and the environments'
+    state and agent tables after the last frame. -> {name: elements written}
+
+    Every file holds finite numbers. An action in which some node drew no out-edge (its uniform at or above the node's
+    fp32 cumulative probability) is infeasible, and its log-probability is -inf as in the reference's
+    GraphDistribution.log_prob (src/reinforcement_learning.py:82-93): ``log_prob_infeasible`` is 1 for those frames and
+    ``log_prob`` holds 0 there."""
+    import numpy as np
+    infeasible = torch.isneginf(trainer.logp)
+    out = {"params": trainer.flat.flat, "losses": trainer.last["losses"], "reward": trainer.reward,
+           "log_prob": trainer.logp.masked_fill(infeasible, 0.0), "log_prob_infeasible": infeasible,
+           "values": trainer.values, "times": trainer.times, "counts": trainer.counts,
+           "choice": trainer.choice, "leg": trainer.leg, "state": engine.x, "agents": engine.agents}
+    arrays = {k: dump_sample(v) for k, v in out.items() if v is not None}
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    assert not bad, f"--dump-outputs: non-finite values in {bad}"
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {k: a.size for k, a in arrays.items()}
+
+
 def pmc_record(cfg):
     """The committed PMC record of a workload, or None: the config must match AND the record must have been taken on the
     very frame-kernel sources this run executes (sha256 of csrc/fused.hip + fused_common.h) — a kernel edit without a fresh
@@ -576,6 +627,9 @@ def main():
     for _ in range(args.warmup):
         trainer.train_iteration()
     frames, elapsed, elapsed_rank, prof_main = time_iterations(trainer, args.steps, L, T, prof, device)
+    if args.dump_outputs and rank == 0:      # before anything below runs the trainer again
+        sizes = dump_outputs(args.dump_outputs, trainer, engine)
+        print(f"bench.py: outputs of the last timed step in {args.dump_outputs}: {sizes}", file=sys.stderr)
     per_rank = dist_utils.gather_floats([setup_s, elapsed_rank], device)     # [rank][setup_seconds, timed_seconds]
     # data-parallel evidence (outside the timed region): after `steps` averaged-gradient Adam steps every replica must still
     # hold rank 0's parameter bits

@@ -23,6 +23,11 @@ def _worker(rank, world, port, q):
             sys.path.insert(0, p)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
+    # CPU ranks also on a GPU host: init_from_env would bind every rank to a device, and torch.distributed's barrier asks
+    # the runtime for an accelerator; either query opens the GPU, and eight processes holding one GPU are more than a
+    # shared machine allows
+    torch.cuda.is_available = lambda: False
+    torch._C._get_accelerator = lambda *a, **k: torch.device("cpu")
     from tarl_hip import dist_utils
     r, w, _ = dist_utils.init_from_env(backend="gloo")
     assert (r, w) == (rank, world) and dist_utils.world() == (rank, world)

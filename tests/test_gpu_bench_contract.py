@@ -12,13 +12,14 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_line_contract():
+def test_bench_line_contract(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     det = os.path.join("gpurun_out", "bench_details_contract_test.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
                           "--envs", "512", "--cpu-seconds", "1", "--congested-steps", "1", "--policy-envs", "128",
                           "--policy-steps", "1", "--update-epochs", "2", "--update-sub-batch", "256", "--update-steps", "1",
-                          "--config5-envs", "0", "--details", det], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--config5-envs", "0", "--details", det, "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -65,6 +66,17 @@ def test_bench_line_contract():
     det_d = json.load(open(os.path.join(ROOT, det)))
     assert "what" in det_d["roofline"] and det_d["roofline"]["compulsory_bytes_per_launch"] > 0
     assert "stages" in det_d["update_path"] and "sample" in det_d["cpu_baseline"] and "note" in det_d["state_dependent_policy"]
+    # --dump-outputs: the last timed step's outputs, float32, within 64 MB; the (T, B) buffers whole, the large ones sampled
+    import numpy as np
+    dump = {p.stem: np.load(p) for p in (tmp_path / "dump").iterdir()}
+    assert set(dump) == {"params", "losses", "reward", "log_prob", "log_prob_infeasible", "values", "times", "counts", "choice",
+                         "leg", "state", "agents"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dump.values())
+    assert (dump["log_prob"] <= 0).all() and set(np.unique(dump["log_prob_infeasible"])) <= {0.0, 1.0}
+    assert (dump["log_prob"][dump["log_prob_infeasible"] == 1] == 0).all()          # (an infeasible action's -inf, as a mask)
+    assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+    assert dump["reward"].size == dump["log_prob"].size == 256 * 512 and dump["counts"].size == dump["state"].size == 1 << 20
+    assert dump["losses"].size == 6 and (dump["reward"] <= 0).all()
 
 
 def test_bench_starts_its_own_ranks():

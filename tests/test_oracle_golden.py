@@ -1,6 +1,6 @@
 """CPU: pin the oracle (oracle/*.py) to the golden vectors produced by the reference's own source
 (oracle/make_golden.py) and to the integer facts of the reference's tests. Integer state bit-exact; fp32 <= 1e-4
-(in practice bit-exact too, same torch CPU kernels)."""
+(in practice bit-exact too, same torch CPU kernels — except where those kernels round by host, see ``near``)."""
 import math
 
 import pytest
@@ -14,6 +14,23 @@ def eq(a, b):
     if not torch.is_tensor(b):
         b = torch.as_tensor(b, dtype=a.dtype).reshape(a.shape)
     return torch.equal(a, b)
+
+
+def near(a, b, ulps):
+    """fp32 results of torch CPU kernels whose rounding depends on the host: exp / log (MKL's vector math) and the GEMMs
+    take a code path chosen by the CPU's vendor and ISA, and GEMMs split their sums by thread count. Bit-exact on the host
+    the fixtures were recorded on (AVX-512 Intel); elsewhere within ``ulps`` fp32 epsilons of the array's largest
+    magnitude. Infinities must match exactly."""
+    if not torch.is_tensor(b):
+        b = torch.as_tensor(b, dtype=a.dtype).reshape(a.shape)
+    a = a.detach()
+    fin = torch.isfinite(b)
+    if a.shape != b.shape or not torch.equal(torch.isfinite(a), fin) or not torch.equal(a[~fin], b[~fin]):
+        return False
+    if not fin.any():
+        return True
+    tol = ulps * torch.finfo(torch.float32).eps * float(b[fin].abs().max())
+    return bool(((a[fin] - b[fin]).abs() <= tol).all())
 
 
 @pytest.mark.parametrize("name", ["core_hom", "core_het", "core_noconst"])
@@ -92,22 +109,22 @@ def test_graphdist(name):
     ei = g["edge_index"]
     d = dist.GraphDist(g["logits"], ei)
     assert d.nb_nodes == g["nb_nodes"]
-    assert eq(d.proba, g["proba"]) and eq(d.cumsum, g["cumsum_sorted"])
-    assert eq(d.entropy(), g["entropy"]) and eq(d.mode, g["mode"])
+    assert near(d.proba, g["proba"], 4) and near(d.cumsum, g["cumsum_sorted"], 16)     # (global prefix sum, then rebased)
+    assert near(d.entropy(), g["entropy"], 4) and eq(d.mode, g["mode"])
     for k in range(4):
         a = d.sample(g[f"u{k}"])
         assert a.dtype == torch.int64 and eq(a, g[f"a{k}"])            # int64 one-hot, bit-exact
-        assert eq(d.log_prob(a), g[f"lp{k}"])
+        assert near(d.log_prob(a), g[f"lp{k}"], 4)
     assert d.log_prob(g["bad"]).item() == -math.inf and float(g["lp_bad"]) == -math.inf
     lb = g["logits_b"].clone().requires_grad_(True)
     db = dist.GraphDist(lb, ei)
     lp, ent = db.log_prob(g["acts_b"]), db.entropy()
-    assert torch.allclose(lp, g["lp_b"], atol=1e-6, rtol=0) and torch.allclose(ent, g["ent_b"], atol=1e-6, rtol=0)
+    assert near(lp, g["lp_b"], 4) and near(ent, g["ent_b"], 4)
     (lp * g["w_b"]).sum().backward(retain_graph=True)
-    assert torch.allclose(lb.grad, g["grad_lp_b"], atol=1e-6, rtol=0)
+    assert near(lb.grad, g["grad_lp_b"], 4)
     lb.grad = None
     (ent * g["w_b"]).sum().backward()
-    assert torch.allclose(lb.grad, g["grad_ent_b"], atol=1e-6, rtol=0)
+    assert near(lb.grad, g["grad_ent_b"], 4)
 
 
 @pytest.mark.parametrize("name", ["env_hom", "env_het"])
@@ -133,7 +150,7 @@ def test_env_rollout_bit_exact(name):
         d = dist.GraphDist(logits, ei)
         a = d.sample(g["u_sample"][s])
         assert eq(a, g["action"][s]), f"action differs at step {s}"
-        assert torch.allclose(d.log_prob(a), g["log_prob"][s], atol=1e-6, rtol=0)
+        assert near(d.log_prob(a), g["log_prob"][s], 4)
         out = sim.env_step(x, ag, ei, ea, adj, a, t, Nmax, uniform=g["u_dir"][s], congestion_constant=cc)
         t = out["time"]
         assert eq(x, g["x"][s]), f"state differs at step {s}"
@@ -284,7 +301,7 @@ def test_edge_mlp_oracle_matches_reference_module():
         ws = [g[f"{tag}__{k}"].clone().requires_grad_(True) for k in ("0__weight", "0__bias", "2__weight", "2__bias",
                                                                         "4__weight", "4__bias")]
         logits = nets.edge_mlp_logits(x16, g["edge_index"], g["edge_attr"].expand(3, -1, -1), *ws)
-        assert torch.equal(logits, g[f"{tag}__logits"])
+        assert near(logits, g[f"{tag}__logits"], 8)
         (logits * g["coef"]).sum().backward()
         for w_, k in zip(ws, ("0__weight", "0__bias", "2__weight", "2__bias", "4__weight", "4__bias")):
-            assert torch.allclose(w_.grad, g[f"{tag}__grad__{k}"], rtol=1e-6, atol=1e-3)
+            assert near(w_.grad, g[f"{tag}__grad__{k}"], 16)
