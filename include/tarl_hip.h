@@ -586,6 +586,30 @@ int tarl_select_next_hop(float* x, int64_t B, int64_t x_bstride, int64_t ldx, in
                          const float* agent_features, int64_t num_agents, int64_t a_bstride, const int64_t* next_hop,
                          int64_t nh_bstride, tarl_stream stream);
 
+/* ---- per-origin shortest-path trees (MSA on large graphs) ------------------------------------------------------------------
+ * The all-or-nothing step of run_msa (src/algorithms/user_equilibrium_msa.py:117-131) needs one shortest-path tree per
+ * distinct origin of the demand, not an all-pairs table: O(E) work and O(N) state per tree (csrc/msa.hip).
+ *   weights: float64 [E] in ORIGINAL edge order (run_msa passes cost[edge_index[1]]), non-negative (+inf allowed).
+ *   dist[v] = the minimum over paths s -> v of the left-to-right fp64 sum ((0 + w1) + w2) + ... — the reference's
+ *   Dijkstra (nx.shortest_path, src/algorithms/user_equilibrium_msa.py:121) bit for bit; +inf when unreachable.
+ *   Tie rule of pred: among the TIGHT in-edges (fl(dist[u] + w) == dist[v]) take the fewest hops from s over tight edges,
+ *   then the smallest predecessor node id. Independent of scheduling; hops strictly increase, so the tree is acyclic.
+ *   scratch: tarl_msa_scratch_bytes(plan, num_sources) bytes of device memory (O(min(num_sources, 1024) x N)); -1 on a
+ *   bad argument. Graphs up to N = 327 680 nodes (the LDS bitmaps). Source / OD ids live on the device: an
+ *   out-of-range id writes nothing.
+ * tarl_sssp_f64: dist_out float64 [num_sources][N], pred_out int32 [num_sources][N] (-1 for the source itself and for
+ *   unreachable nodes); either may be NULL (then only the range check runs).
+ * tarl_msa_assign_sssp == src/algorithms/user_equilibrium_msa.py:117-131 for OD pairs SORTED BY ORIGIN: the pairs of
+ *   origins[j] are od_dest / od_volume [od_ptr[j], od_ptr[j+1]) (od_ptr int64 [num_origins + 1]); each walks d -> o along
+ *   the tree and adds its volume to aux_flow[v] (double, ACCUMULATED) for every node v != o of the path with is_road[v] != 0,
+ *   the semantics of tarl_msa_assign. */
+int64_t tarl_msa_scratch_bytes(const tarl_plan* plan, int64_t num_sources);
+int tarl_sssp_f64(const tarl_plan* plan, const double* weights, const int64_t* sources, int64_t num_sources, void* scratch,
+                  int64_t scratch_bytes, double* dist_out, int32_t* pred_out, tarl_stream stream);
+int tarl_msa_assign_sssp(const tarl_plan* plan, const double* weights, const int64_t* origins, int64_t num_origins,
+                         const int64_t* od_ptr, const int64_t* od_dest, const double* od_volume, const uint8_t* is_road,
+                         void* scratch, int64_t scratch_bytes, double* aux_flow, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

@@ -158,14 +158,13 @@ class Runner:
             sim.compute_node_metrics(str(out_dir))
             sim.plot_leg_histogram(str(out_dir))
             sim.plot_road_optimality(str(out_dir))
-            if sim.graph.x.size(0) <= 4096:          # all-pairs table per MSA iteration: keep it to mid-size graphs
-                from .algorithms.user_equilibrium_msa import run_msa
-                expected = run_msa(sim.graph, agent)
-                out_dir.mkdir(parents=True, exist_ok=True)
-                with open(out_dir / "msa_expected_flows.csv", "w") as f:
-                    f.write("road,expected_hourly_flow\n")
-                    f.writelines(f"{r},{v}\n" for r, v in expected.items())
-                sim.plot_daily_counts(expected, str(out_dir))
+            from .algorithms.user_equilibrium_msa import run_msa
+            expected = run_msa(sim.graph, agent)         # all-pairs table on mid-size graphs, per-origin trees above
+            out_dir.mkdir(parents=True, exist_ok=True)
+            with open(out_dir / "msa_expected_flows.csv", "w") as f:
+                f.write("road,expected_hourly_flow\n")
+                f.writelines(f"{r},{v}\n" for r, v in expected.items())
+            sim.plot_daily_counts(expected, str(out_dir))
             import matplotlib.pyplot as plt
             plt.close("all")
         except Exception as exc:  # noqa: BLE001 - analysis output must not fail the run

@@ -258,6 +258,54 @@ def msa_assign(next_hop, od_origin, od_dest, od_volume, is_road, aux_flow):
                                  od_origin.numel(), is_road.data_ptr(), aux_flow.data_ptr(), _lib.current_stream()))
 
 
+def _tree_args(plan: Plan, weights, sources, name):
+    _contig(weights, torch.float64, "weights")
+    _contig(sources, torch.int64, name)
+    if weights.dim() != 1 or weights.numel() != plan.num_edges:
+        raise ValueError(f"weights must be ({plan.num_edges},) float64 in original edge order, got {tuple(weights.shape)}")
+    if sources.dim() != 1:
+        raise ValueError(f"{name} must be 1-D")
+    L = _lib.load()
+    S = sources.numel()
+    need = int(L.tarl_msa_scratch_bytes(plan.handle, S))
+    scratch = torch.empty(need, dtype=torch.uint8, device=weights.device) if need > 0 else None
+    return L, S, need, scratch
+
+
+def shortest_path_trees(plan: Plan, weights, sources, *, want_dist=True, want_pred=True):
+    """One shortest-path tree per source (tarl_sssp_f64): ``weights`` (E,) float64 in original edge order, ``sources``
+    (S,) int64 -> (dist float64 (S, N) | None, pred int32 (S, N) | None). dist is Dijkstra's left-to-right fp64 sum (+inf:
+    unreachable); pred[v] = the smallest-id tight in-neighbour among those fewest tight hops from the source (-1 for
+    the source and unreachable nodes). Rows of out-of-range sources are left as allocated (uninitialised)."""
+    if not (want_dist or want_pred):
+        raise ValueError("no output requested")
+    L, S, need, scratch = _tree_args(plan, weights, sources, "sources")
+    N = plan.num_nodes
+    d = torch.empty((S, N), dtype=torch.float64, device=weights.device) if want_dist else None
+    p = torch.empty((S, N), dtype=torch.int32, device=weights.device) if want_pred else None
+    _lib.check(L.tarl_sssp_f64(plan.handle, weights.data_ptr(), sources.data_ptr(), S, _lib.ptr(scratch), need,
+                               _lib.ptr(d), _lib.ptr(p), _lib.current_stream()))
+    return d, p
+
+
+def msa_assign_trees(plan: Plan, weights, origins, od_ptr, od_dest, od_volume, is_road, aux_flow):
+    """All-or-nothing assignment along per-origin trees (tarl_msa_assign_sssp): the OD pairs sorted by origin, those of
+    ``origins[j]`` at ``[od_ptr[j], od_ptr[j+1])``; aux_flow (N,) float64 += volume of every pair on the road nodes of
+    its path (origin excluded). Same semantics as :func:`msa_assign` on the all-pairs table."""
+    L, S, need, scratch = _tree_args(plan, weights, origins, "origins")
+    for t, dt, nm in ((od_ptr, torch.int64, "od_ptr"), (od_dest, torch.int64, "od_dest"),
+                      (od_volume, torch.float64, "od_volume"), (is_road, torch.uint8, "is_road"),
+                      (aux_flow, torch.float64, "aux_flow")):
+        _contig(t, dt, nm)
+    if od_ptr.numel() != S + 1 or od_volume.numel() != od_dest.numel():
+        raise ValueError("od_ptr must have num_origins + 1 entries and od_volume one per od_dest")
+    if is_road.numel() != plan.num_nodes or aux_flow.numel() != plan.num_nodes:
+        raise ValueError("is_road and aux_flow need one entry per node")
+    _lib.check(L.tarl_msa_assign_sssp(plan.handle, weights.data_ptr(), origins.data_ptr(), S, od_ptr.data_ptr(),
+                                      od_dest.data_ptr(), od_volume.data_ptr(), is_road.data_ptr(), _lib.ptr(scratch),
+                                      need, aux_flow.data_ptr(), _lib.current_stream()))
+
+
 def select_next_hop(x, Nmax, agent_features, next_hop):
     """x[b, i, SELECTED_ROAD] = next_hop[b, i, DESTINATION[head agent of i]] (src/agents/base.py:572-580)."""
     L = _lib.load()
