@@ -546,6 +546,47 @@ int tarl_fused_rollout_policy(const tarl_plan* plan, const tarl_fused* f, int64_
                               void* dist_scratch, int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward,
                               uint8_t* counts, int32_t metrics_envs, float* dtt_node, uint8_t* events, int32_t* leg,
                               tarl_stream stream);
+/* ---- the shortest-path prior head of MPNNPolicyNet (policy_head = "embedding_dijkstra"; csrc/prior.hip) -------------------
+ * The live forward of the reference computes a Dijkstra prior and leaves its addition commented out
+ * (src/agents/mpnn_agent.py:180-190, compute_dijkstra_logits :81-113). This head adds it, weighted:
+ *   logit[m][e] = emb[ROAD_INDEX(v)] + prior_weight * ((-dist[v][dest(u)]) - time_travel(v)),   u = src(e), v = dst(e),
+ *   time_travel(v) = max(FF, FF * (MAXN + 10 - MAX_FLOW * FF / 3600) / (MAXN + 10 - NUMBER_OF_AGENT)) of road v (:181-184),
+ *   dest(u) = (long) DESTINATION of u's head agent (:186-187; the head rule of tarl_policy_obs16 / tarl_fused_obs16).
+ * fp32 in the reference's operation order; prior_weight = 1 is the reference's literal sum. ROAD_INDEX outside
+ * [0, num_embeddings) contributes 0 (tarl_policy_edge_logits_fwd). dist [dist_n][dist_n] fp32 = MPNNPolicyNet.dist_matrix
+ * (tarl_apsp on the free-flow weights), dist_n must equal the plan's N; prior_weight finite and >= 0.
+ * Unreachable (dist = +inf, or dest outside [0, N)): the prior term is the finite sentinel -1e20 instead of -inf — such a
+ * candidate has probability exactly 0 next to a reachable one, and a node whose every candidate is unreachable (NaN in the
+ * reference) draws uniformly among its out-edges. No inf / NaN is emitted. Gradients w.r.t. emb: tarl_policy_edge_logits_bwd.
+ * tarl_policy_prior_logits: from observations obs16 [M][N][16] (tarl_policy_obs16 layout, 16-byte aligned) -> logits [M][E].
+ * tarl_fused_prior_logits: from the fused engine's packed state (count byte and head agent of every road) and the static
+ *   columns of x -> logits [B][E], no observation written (the rollout's hot path). Same values as the observation path. */
+int tarl_policy_prior_logits(const tarl_plan* plan, const float* obs16, int64_t M, const float* emb,
+                             int64_t num_embeddings, const float* dist, int64_t dist_n, float prior_weight, float* logits,
+                             tarl_stream stream);
+int tarl_fused_prior_logits(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B, int64_t x_bstride,
+                            int64_t ldx, int32_t Nmax, const float* agent_features, int64_t num_agents, int64_t a_bstride,
+                            const float* emb, int64_t num_embeddings, const float* dist, int64_t dist_n, float prior_weight,
+                            float* logits, tarl_stream stream);
+/* tarl_fused_rollout_prior: tarl_fused_rollout_policy with the prior head — T frames in one foreign call, per frame
+ *   [tarl_fused_obs16_rows of the kept environments] -> tarl_fused_prior_logits -> tarl_graphdist_rollout (temperature;
+ *   policy counter policy_counter0 + t; writes the action into tarl_fused.sel8) -> tarl_fused_frame with that action (Direction,
+ *   rows, insert; noise counter counter0 + t) -> the count bytes, with the same results as those calls made one by one.
+ *   keep_ptr_host / keep_env / keep_slot / obs_keep: as tarl_fused_rollout_policy (fp32 observations of the pre-drawn
+ *   minibatch frames: what the PPO update needs to recompute the prior exactly). Scratch (device): logits_scratch fp32
+ *   [B][E], dist_scratch (tarl_graphdist_rollout_scratch_bytes), ins_scratch int32 [B][2A]. Outputs, frame-major, nullable:
+ *   choice8 uint8 [T][B][N] (ENV-MAJOR rank bytes, bit 7: nothing drawn), log_prob / reward fp32 [T][B], counts uint8
+ *   [T][N][B] (env-minor, after frame t). The per-step logs of tarl_fused_rollout (leg, dtt_node, events) are not produced. */
+int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                             const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
+                             float* agent_features, int64_t num_agents, int64_t a_bstride, const float* edge_attr,
+                             const float* log_edge_attr, float log_eps, int use_cong, const float* emb,
+                             int64_t num_embeddings, const float* dist, int64_t dist_n, float prior_weight,
+                             float temperature, uint64_t policy_seed, uint64_t policy_counter0, uint64_t seed,
+                             uint64_t counter0, const int64_t* keep_ptr_host, const int32_t* keep_env,
+                             const int32_t* keep_slot, float* obs_keep, float* logits_scratch, void* dist_scratch,
+                             int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                             tarl_stream stream);
 /* the action / count bytes of a rollout back in the formats of the unfused entry points: choice_eid int32 [rows][N] =
  *   chosen edge id (-1: none), counts_f fp32 [rows][N], for `rows` (frame, environment) pairs given as flat indices
  *   idx int64 [rows] = t * B + b (NULL: all T * B pairs in order). env_minor != 0: the buffers are [T][N][B], else

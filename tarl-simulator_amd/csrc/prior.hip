@@ -1,0 +1,222 @@
+// prior.hip — the shortest-path prior head of MPNNPolicyNet (policy_head = "embedding_dijkstra"):
+//
+//     logit[e] = W_emb[ROAD_INDEX(v)] + prior_weight * ((-dist[v][dest(u)]) - time_travel(v)),   u = src(e), v = dst(e)
+//     time_travel(v) = max(FF, FF * (MAXN + 10 - MAX_FLOW * FF / 3600) / (MAXN + 10 - NUMBER_OF_AGENT))   (of road v)
+//
+// The reference computes every term (src/agents/mpnn_agent.py:180-187, compute_dijkstra_logits :81-113) and leaves the sum
+// commented out (:188); this is that sum with a weight on the prior. fp32, the reference's operation order (the library is
+// built with -ffp-contract=off). dest(u) = (long) DESTINATION of u's head agent, read exactly as the observation kernels read
+// it (tarl_policy_obs16 / tarl_fused_obs16: an empty FIFO's head id, and an id outside [0, A), read agent 0).
+// dist = the free-flow all-pairs table [N][N] of MPNNPolicyNet.dist_matrix (tarl_apsp), +inf where unreachable.
+//
+// Unreachable pairs. A candidate whose destination cannot be reached from v (dist = +inf, or a destination id outside
+// [0, N)) gets the prior PRIOR_UNREACHABLE = -1e20 instead of prior_weight * (-inf): the segment softmax subtracts the node's
+// maximum, so next to any reachable candidate its probability is exp(-1e20 + O(1e12)) = 0 exactly (the reference's value);
+// when every candidate of a node is unreachable (the reference's softmax is NaN there) all of them carry W_emb + -1e20,
+// which rounds to -1e20 for |W_emb| < 2^43 — the node draws uniformly among its out-edges. No inf or NaN is ever emitted
+// (the logits stay finite after division by a temperature >= 1e-18), so probabilities, samples, log-probs, entropies and
+// their gradients stay finite. The logit depends on W_emb with derivative 1 on every edge, reachable or not, which is what
+// tarl_policy_edge_logits_bwd propagates.
+//
+// Two producers of the same numbers:
+//   * tarl_policy_prior_logits: from observations obs16 [M][N][16] (the tarl_policy_obs16 layout) — the module forward and
+//     the PPO update. One thread per (sample, edge), original edge order: coalesced logits stores.
+//   * tarl_fused_prior_logits: from the fused engine's packed state (count byte + head id of hdp) and the static columns, no
+//     observation written — the rollout's hot path. A workgroup owns 64 environments x 64 CSR positions: lanes run along
+//     the environments, so the packed words are read as contiguous 512-byte runs, the source/target road of a position is
+//     wave-uniform, and the table row dist[v] is one row for the whole wave (the table is stored [candidate][destination]:
+//     the 64 lanes gather inside one row of N floats instead of touching 64 rows). The [64 env][64 edge] tile is turned
+//     through LDS and leaves as 256-byte runs of each environment's logits row.
+// tarl_fused_rollout_prior queues, per frame, prior logits -> tarl_graphdist_rollout_at -> tarl_fused_frame (Direction, rows,
+// insert; SELECTED_ROAD set by the sampler) -> count bytes, in one foreign call.
+#include <math.h>
+
+#include "fused_common.h"
+
+#define PRIOR_UNREACHABLE (-1e20f)
+#define PR_BLOCK 256
+#define PR_TE 64      // environments per fused tile (one per lane)
+#define PR_TK 64      // CSR positions per fused tile
+
+__device__ __forceinline__ float prior_logit(float em, float d, float ff, float maxn, float maxflow, float na, float w) {
+  if (!(d <= 3.4028234663852886e38f)) return em + PRIOR_UNREACHABLE;     // +inf (unreachable) or NaN
+  const float crit = maxflow * ff / 3600.0f;                             // critical_number (:182)
+  const float tc = ff * (maxn + 10.0f - crit) / (maxn + 10.0f - na);     // time_congestion (:183)
+  const float tt = (ff != ff || tc != tc) ? NAN : fmaxf(ff, tc);         // torch.max over the stack (:184)
+  return em + w * ((-d) - tt);                                           // logits + logits_dijkstra (:113, :188)
+}
+
+__device__ __forceinline__ float emb_of(const float* __restrict__ emb, int64_t M, float road) {
+  const long long idx = (long long)road;
+  return (idx >= 0 && idx < M) ? emb[idx] : 0.0f;        // tarl_policy_edge_logits_fwd's rule
+}
+
+__device__ __forceinline__ float dist_of(const float* __restrict__ dist, int64_t N, int64_t v, float dest_f) {
+  const long long d = (long long)dest_f;                   // agent_destination.to(torch.long) (:186)
+  return (d >= 0 && d < N) ? dist[v * N + d] : INFINITY;
+}
+
+// ---- from observations ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PR_BLOCK) void k_prior_obs(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
+                                                        const float* __restrict__ obs, int64_t M, int64_t N, int64_t E,
+                                                        const float* __restrict__ emb, int64_t num_emb,
+                                                        const float* __restrict__ dist, float w,
+                                                        float* __restrict__ logits) {
+  const int64_t gid = (int64_t)blockIdx.x * PR_BLOCK + threadIdx.x;
+  if (gid >= M * E) return;
+  const int64_t m = gid / E, e = gid - m * E;
+  const float* ou = obs + (m * N + src[e]) * 16;
+  const int64_t v = dst[e];
+  const float4* ov = reinterpret_cast<const float4*>(obs + (m * N + v) * 16);
+  const float4 a = ov[0], c = ov[1];     // {MAXN, NUMBER_OF_AGENT, FF, LENGTH}, {MAX_FLOW, SELECTED_ROAD, ROAD_INDEX, ORIGIN}
+  logits[gid] = prior_logit(emb_of(emb, num_emb, c.z), dist_of(dist, N, v, ou[8]), a.z, a.x, c.x, a.y, w);
+}
+
+extern "C" int tarl_policy_prior_logits(const tarl_plan* plan, const float* obs16, int64_t M, const float* emb,
+                                        int64_t num_embeddings, const float* dist, int64_t dist_n, float prior_weight,
+                                        float* logits, tarl_stream stream) {
+  TARL_REQUIRE(plan && obs16 && emb && dist && logits, "null argument");
+  TARL_REQUIRE(M >= 1 && num_embeddings >= 1, "bad sizes");
+  TARL_REQUIRE(dist_n == plan->N, "distance table is not N x N for this plan");
+  TARL_REQUIRE(prior_weight >= 0.0f && prior_weight <= 3.0e38f, "prior_weight must be finite and >= 0");
+  TARL_REQUIRE(((uintptr_t)obs16) % 16 == 0, "obs16 must be 16-byte aligned");
+  if (plan->E == 0) return TARL_OK;
+  hipLaunchKernelGGL(k_prior_obs, dim3((unsigned)ceil_div(M * plan->E, PR_BLOCK)), dim3(PR_BLOCK), 0, (hipStream_t)stream,
+                     plan->src, plan->dst, obs16, M, plan->N, plan->E, emb, num_embeddings, dist, prior_weight, logits);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+// ---- from the packed state -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PR_BLOCK) void k_prior_fused(const int32_t* __restrict__ src, const int32_t* __restrict__ out_dst,
+                                                          const int32_t* __restrict__ out_eid, int64_t B, int64_t N,
+                                                          int64_t E, const uint2* __restrict__ hdp,
+                                                          const float4* __restrict__ st0, const float* __restrict__ x0,
+                                                          int64_t ldx, int col_maxflow, const float* __restrict__ ag,
+                                                          int64_t A, int64_t a_bstride, const float* __restrict__ emb,
+                                                          int64_t num_emb, const float* __restrict__ dist, float w,
+                                                          float* __restrict__ logits) {
+  __shared__ float tile[PR_TE][PR_TK + 1];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t b0 = (int64_t)blockIdx.x * PR_TE, k0 = (int64_t)blockIdx.y * PR_TK;
+  const int64_t b = b0 + lane;
+  for (int kk = wv; kk < PR_TK; kk += PR_BLOCK / 64) {     // one CSR position per wave step: u, v wave-uniform
+    const int64_t k = k0 + kk;
+    if (k >= E) break;
+    const int64_t e = out_eid[k], u = src[e], v = out_dst[k];
+    float l = 0.0f;
+    if (b < B) {
+      const uint32_t hu = hdp[u * B + b].x, hv = hdp[v * B + b].x;
+      const long long head = (long long)(hu >> 8);
+      const float dest = ag[b * a_bstride + ((head >= 0 && head < A) ? head : 0) * AG_COLS + AG_DEST];
+      const float4 st = st0[v];    // {MAXN, FF, ROAD_INDEX, congestion_constant}
+      l = prior_logit(emb_of(emb, num_emb, st.z), dist_of(dist, N, v, dest), st.y, st.x, x0[v * ldx + col_maxflow],
+                      (float)(hv & HD_CNT), w);
+    }
+    tile[lane][kk] = l;
+  }
+  __syncthreads();
+  const int64_t k = k0 + lane;
+  if (k >= E) return;
+  const int64_t e = out_eid[k];
+  for (int r = wv; r < PR_TE; r += PR_BLOCK / 64) {
+    const int64_t bb = b0 + r;
+    if (bb < B) logits[bb * E + e] = tile[r][lane];
+  }
+}
+
+static int check_prior_state(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, const float* x,
+                             const float* agent_features, int64_t A, const float* emb, int64_t num_embeddings,
+                             const float* dist, int64_t dist_n, float prior_weight) {
+  TARL_REQUIRE(plan && f && x && agent_features && emb && dist, "null argument");
+  TARL_REQUIRE(B >= 1 && A >= 1 && num_embeddings >= 1, "bad sizes");
+  TARL_REQUIRE(dist_n == plan->N, "distance table is not N x N for this plan");
+  TARL_REQUIRE(prior_weight >= 0.0f && prior_weight <= 3.0e38f, "prior_weight must be finite and >= 0");
+  TARL_REQUIRE(ceil_div(plan->E, PR_TK) < 65536 && ceil_div(B, PR_TE) < 65536, "too many tiles for one grid dimension");
+  return tarl_check_fused_core(plan, f, B, Nmax);
+}
+
+static int launch_prior_fused(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, const float* x,
+                              int64_t ldx, const float* agent_features, int64_t A, int64_t a_bstride, const float* emb,
+                              int64_t num_embeddings, const float* dist, float prior_weight, float* logits,
+                              hipStream_t s) {
+  const FusedBufs fb = tarl_to_bufs(f);
+  const Layout L{Nmax, ldx, 0};
+  hipLaunchKernelGGL(k_prior_fused, dim3((unsigned)ceil_div(B, PR_TE), (unsigned)ceil_div(plan->E, PR_TK)), dim3(PR_BLOCK),
+                     0, s, plan->src, plan->out_dst, plan->out_eid, B, plan->N, plan->E, fb.hdp, fb.st0, x, ldx,
+                     L.col_maxflow(), agent_features, A, a_bstride, emb, num_embeddings, dist, prior_weight, logits);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+extern "C" int tarl_fused_prior_logits(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B,
+                                       int64_t x_bstride, int64_t ldx, int32_t Nmax, const float* agent_features,
+                                       int64_t num_agents, int64_t a_bstride, const float* emb, int64_t num_embeddings,
+                                       const float* dist, int64_t dist_n, float prior_weight, float* logits,
+                                       tarl_stream stream) {
+  (void)x_bstride;    // the static columns of environment 0 speak for all
+  TARL_REQUIRE(logits, "null argument");
+  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, num_agents, emb, num_embeddings, dist, dist_n,
+                             prior_weight);
+  if (rc) return rc;
+  if (plan->E == 0) return TARL_OK;
+  return launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, num_agents, a_bstride, emb, num_embeddings, dist,
+                            prior_weight, logits, (hipStream_t)stream);
+}
+
+// the count bytes of the rollout buffers (NUMBER_OF_AGENT after the frame, env-minor [N][B]) from the packed state
+__global__ __launch_bounds__(PR_BLOCK) void k_counts8(const uint2* __restrict__ hdp, int64_t n, uint8_t* __restrict__ counts) {
+  const int64_t gid = (int64_t)blockIdx.x * PR_BLOCK + threadIdx.x;
+  if (gid < n) counts[gid] = (uint8_t)(hdp[gid].x & HD_CNT);
+}
+
+// observation row env[j] of the current frame -> obs_keep[slot[j]] for the kept (frame, environment) pairs, then the frame
+extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                        const float* times_host, float prev_time, const float* x, int64_t x_bstride,
+                                        int64_t ldx, float* agent_features, int64_t A, int64_t a_bstride,
+                                        const float* edge_attr, const float* log_edge_attr, float log_eps, int use_cong,
+                                        const float* emb, int64_t num_embeddings, const float* dist, int64_t dist_n,
+                                        float prior_weight, float temperature, uint64_t policy_seed,
+                                        uint64_t policy_counter0, uint64_t seed, uint64_t counter0,
+                                        const int64_t* keep_ptr_host, const int32_t* keep_env, const int32_t* keep_slot,
+                                        float* obs_keep, float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
+                                        uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                                        tarl_stream stream) {
+  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, A, emb, num_embeddings, dist, dist_n, prior_weight);
+  if (rc) return rc;
+  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
+  TARL_REQUIRE(logits_scratch && dist_scratch && ins_scratch, "logits / sampler / insert scratch missing");
+  TARL_REQUIRE(!keep_ptr_host || (keep_env && keep_slot && obs_keep), "keep list without its arrays");
+  TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t N = plan->N, NB = N * B;
+  const FusedBufs fb = tarl_to_bufs(f);
+  for (int64_t t = 0; t < T; ++t) {
+    if (keep_ptr_host && keep_ptr_host[t + 1] > keep_ptr_host[t]) {
+      const int64_t lo = keep_ptr_host[t], n = keep_ptr_host[t + 1] - lo;
+      rc = tarl_fused_obs16_rows(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, keep_env + lo,
+                                 keep_slot + lo, n, obs_keep, stream);
+      if (rc) return rc;
+    }
+    if (plan->E > 0) {
+      rc = launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, A, a_bstride, emb, num_embeddings, dist, prior_weight,
+                              logits_scratch, s);
+      if (rc) return rc;
+    }
+    rc = tarl_graphdist_rollout_at(plan, logits_scratch, B, temperature, nullptr, policy_seed, policy_counter0 + (uint64_t)t,
+                                   dist_scratch, nullptr, choice8 ? choice8 + t * NB : nullptr, f->sel8,
+                                   log_prob ? log_prob + t * B : nullptr, f->env_base, stream);
+    if (rc) return rc;
+    rc = tarl_fused_frame(plan, f, B, Nmax, nullptr, nullptr, nullptr, nullptr, 0, 0, agent_features, A, a_bstride, edge_attr,
+                          log_edge_attr, log_eps, use_cong, times_host[t], t > 0 ? times_host[t - 1] : prev_time, nullptr,
+                          seed, counter0 + (uint64_t)t, nullptr, nullptr, nullptr, ins_scratch, nullptr, nullptr, nullptr,
+                          reward ? reward + t * B : nullptr, nullptr, stream);
+    if (rc) return rc;
+    if (counts) {
+      hipLaunchKernelGGL(k_counts8, dim3((unsigned)ceil_div(NB, PR_BLOCK)), dim3(PR_BLOCK), 0, s, fb.hdp, NB, counts + t * NB);
+      TARL_LAUNCH_CHECK();
+    }
+  }
+  return TARL_OK;
+}

@@ -4,7 +4,8 @@ Same constructors, ``forward`` signatures and state-dict keys (``nodes_embedding
 ``edge_mlp_test.{0,2}.*``, ``final_mlp.{0,2,4}.*``). Live actor: logits[e] = W_emb[ROAD_INDEX(dst(e))]
 (``tarl_policy_edge_logits_fwd/bwd``); live critic: MLP(cat(NUMBER_OF_AGENT per node, time)) on fp32 MFMA
 (``tarl_critic_mlp_fwd/bwd``). What the reference computes and discards after the logits (Dijkstra prior, travel
-time, norm — :181-190) is not evaluated; the all-pairs Dijkstra matrix of its constructor is built lazily on request.
+time, norm — :181-190) is not evaluated by the default head; ``policy_head = "embedding_dijkstra"`` adds the prior
+(``tarl_policy_prior_logits``). The all-pairs Dijkstra matrix of its constructor is built lazily on request.
 """
 from __future__ import annotations
 
@@ -28,6 +29,23 @@ class _EdgeLogits(torch.autograd.Function):
         from tarl_hip import ops
         g = ops.policy_edge_logits_bwd(ctx.plan, ctx.nf, grad_logits.contiguous(), int(torch.Size(ctx.shape).numel()))
         return g.view(ctx.shape), None, None
+
+
+class _PriorLogits(torch.autograd.Function):
+    """The embedding plus the weighted shortest-path prior (tarl_policy_prior_logits); the prior has no parameters, so the
+    embedding receives the logits' gradient through tarl_policy_edge_logits_bwd (ROAD_INDEX = observation column 6)."""
+
+    @staticmethod
+    def forward(ctx, emb_weight, obs16, plan, table, prior_weight):
+        from tarl_hip import ops
+        ctx.plan, ctx.obs, ctx.shape = plan, obs16, emb_weight.shape
+        return ops.policy_prior_logits(plan, obs16, emb_weight.detach().reshape(-1).contiguous(), table, prior_weight)
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        from tarl_hip import ops
+        g = ops.policy_edge_logits_bwd(ctx.plan, ctx.obs, grad_logits.contiguous(), int(torch.Size(ctx.shape).numel()))
+        return g.view(ctx.shape), None, None, None, None
 
 
 class _EdgeMlp(torch.autograd.Function):
@@ -55,8 +73,12 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
     # road, src/agents/mpnn_agent.py:215-217). "edge_mlp" / "edge_mlp_fp32" / "edge_mlp_bf16": the per-edge MLP the reference
     # keeps as parameters and spells out in its commented lines (:227-231), on fp32 / bf16 MFMA — a state-dependent policy
     # (this module's forward runs the fp32 MFMA kernel for the first two; the names differ in the ROLLOUT kernel the trainer
-    # picks: fp32 accuracy on the bf16 pipe / exact fp32 products / bf16).
+    # picks: fp32 accuracy on the bf16 pipe / exact fp32 products / bf16). "embedding_dijkstra": the embedding plus
+    # ``prior_weight`` times the shortest-path prior the reference computes and leaves commented out (:180-190):
+    # -dist[dst(e), DESTINATION of the head agent of src(e)] - time_travel(dst(e)), dist = ``dist_matrix`` (state-dependent,
+    # no parameters of its own; prior_weight = 1 is the reference's literal sum).
     policy_head = "embedding"
+    prior_weight = 1.0
 
     def __init__(self, edge_index, num_nodes, free_flow_time_travel, device):
         Agents.__init__(self, device=device)
@@ -109,6 +131,11 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
         """node_features (N,7) or (B,N,7) -> logits (E,) or (B,E)."""
         require_cuda(node_features, "node_features")
         plan = cached_plan(self.edge_index, self.num_nodes)
+        if self.policy_head == "embedding_dijkstra":
+            from tarl_hip import ops
+            obs16 = ops.policy_obs16(node_features, agent_index, self.agent_features.to(node_features.device))
+            logits = _PriorLogits.apply(self.nodes_embedding.weight, obs16, plan, self.dist_matrix, float(self.prior_weight))
+            return logits if node_features.dim() == 3 else logits.view(-1)
         if self.policy_head != "embedding":
             from tarl_hip import ops
             from .._compat import cached_edge_const

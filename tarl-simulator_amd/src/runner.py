@@ -26,6 +26,7 @@ class RunnerArgs:
     steps: int = None          # README / BASELINE use --steps; the reference CLI lacks it
     num_envs: int = 1
     policy_head: str = "embedding"
+    prior_weight: float = 1.0      # policy_head "embedding_dijkstra": weight of the shortest-path prior
 
 
 class Runner:
@@ -80,6 +81,7 @@ class Runner:
             free_flow = g.x[:, h.FREE_FLOW_TIME_TRAVEL][g.edge_index[1]]
             self.policy_net = MPNNPolicyNet(g.edge_index, g.x.size(0), free_flow, device=str(self.device))
             self.policy_net.policy_head = a.policy_head
+            self.policy_net.prior_weight = float(a.prior_weight)
             self.policy_net.load(a.scenario)
             self.value_net = MPNNValueNetSimple(g.edge_index, g.x.size(0), device=str(self.device))
             self.value_net.load(a.scenario)

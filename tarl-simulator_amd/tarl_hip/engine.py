@@ -234,6 +234,37 @@ class SimEngine:
             self.check_flags()
         return times
 
+    def rollout_prior(self, T, emb, table, *, prior_weight=1.0, temperature, policy_seed, policy_counter0, choice8, log_prob,
+                      reward, counts, keep=None, obs_keep=None, check=True):
+        """``T`` frames under the shortest-path prior head (``emb``: flat embedding, ``table``: (N, N) free-flow distances) in
+        one foreign call: per frame prior logits from the packed state -> GraphDistribution sample + log-prob -> the
+        simulation frame. Buffers as :meth:`rollout_policy` (``choice8`` (T,B,N), ``counts`` (T+1,N,B)). Returns the list of
+        clock values."""
+        if self._packed_stale:
+            self.resync()
+        if counts.dtype != torch.uint8 or tuple(counts.shape) != (T + 1, self.N, self.B) or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous uint8 {(T + 1, self.N, self.B)} tensor")
+        times = []
+        t_clock = self.time
+        for _ in range(T):
+            times.append(float(t_clock))
+            t_clock += self.timestep
+        self._x_stale = True
+        ops.fused_rollout_prior(self.plan, self.fs, self._x, self.agents, self.ec, emb, table, times,
+                                prior_weight=prior_weight, use_cong=self.cc is not None, temperature=temperature,
+                                policy_seed=policy_seed, policy_counter0=policy_counter0, seed=self.seed,
+                                counter0=self.noise_counter + 1, scratch=self.ins_scratch, prev_time=self._last_step_time,
+                                keep=keep, obs_keep=obs_keep, choice8=choice8, log_prob=log_prob, reward=reward,
+                                counts=counts[1:])
+        self.sample_counter += T
+        self.noise_counter += T
+        self._last_step_time = times[-1]
+        self.time = t_clock
+        times.append(float(self.time))
+        if check:
+            self.check_flags()
+        return times
+
     def decode_rollout(self, env_minor, *, choice=None, counts=None):
         """The rollout's byte buffers in the formats of the unfused entry points, ENV-MAJOR: ``choice`` (T,N,B) / (T,B,N)
         uint8 -> (T,B,N) int32 edge ids (-1: none); ``counts`` (T',N,B) / (T',B,N) uint8 -> (T',B,N) fp32."""

@@ -86,6 +86,12 @@ SIGNATURES = {
     "tarl_fused_rollout_policy": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p,
                                             _f32, C.c_int] + [_p] * 6 + [C.c_int, _f32, _u64, _u64, _u64, _u64] +
                                   [_p] * 12 + [_i32, _p, _p, _p, _p]),
+    "tarl_policy_prior_logits": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _f32, _p, _p]),
+    "tarl_fused_prior_logits": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _f32, _p,
+                                          _p]),
+    "tarl_fused_rollout_prior": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p,
+                                           _f32, C.c_int, _p, _i64, _p, _i64, _f32, _f32, _u64, _u64, _u64, _u64] +
+                                 [_p] * 11 + [_p]),
     "tarl_rollout_gather": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_int, _p, _i64, _p, _p, _p]),
     "tarl_rollout_env_supported": (C.c_int, [_p]),
     "tarl_rollout_env_scratch_bytes": (_i64, [_p]),

@@ -1054,6 +1054,90 @@ def fused_rollout_policy(plan: Plan, fs: FusedState, x, agent_features, ec: Edge
         _lib.ptr(leg), _lib.current_stream()))
 
 
+# ---- shortest-path prior head (policy_head = "embedding_dijkstra", csrc/prior.hip) ------------------------------------------
+def _prior_args(plan: Plan, emb, table, prior_weight):
+    _contig(emb, torch.float32, "emb")
+    _contig(table, torch.float32, "prior_table")
+    N = plan.num_nodes
+    if tuple(table.shape) != (N, N):
+        raise ValueError(f"prior_table must be the ({N}, {N}) all-pairs distance table of the plan's graph")
+    w = float(prior_weight)
+    if not (0.0 <= w < float("inf")):
+        raise ValueError("prior_weight must be finite and >= 0")
+    return w
+
+
+def policy_prior_logits(plan: Plan, obs16, emb, table, prior_weight=1.0):
+    """logit[m, e] = emb[ROAD_INDEX(dst)] + prior_weight * ((-table[dst, dest(src)]) - time_travel(dst)) from observations
+    ``obs16`` (M, N, 16) (the :func:`policy_obs16` layout) -> (M, E). ``table``: (N, N) fp32 free-flow distances
+    (MPNNPolicyNet.dist_matrix). Unreachable candidates carry the finite sentinel -1e20 (see include/tarl_hip.h)."""
+    L = _lib.load()
+    w = _prior_args(plan, emb, table, prior_weight)
+    _contig(obs16, torch.float32, "obs16")
+    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (plan.num_nodes, 16):
+        raise ValueError(f"obs16 must be (M, {plan.num_nodes}, 16)")
+    M = obs16.size(0)
+    logits = torch.empty((M, plan.num_edges), dtype=torch.float32, device=obs16.device)
+    _lib.check(L.tarl_policy_prior_logits(plan.handle, obs16.data_ptr(), M, emb.data_ptr(), emb.numel(), table.data_ptr(),
+                                          table.size(0), w, logits.data_ptr(), _lib.current_stream()))
+    return logits
+
+
+def fused_prior_logits(plan: Plan, fs, x, Nmax, agent_features, emb, table, prior_weight=1.0, out=None):
+    """The same logits from the packed state of the fused engine: (B, E), no observation materialised."""
+    L = _lib.load()
+    w = _prior_args(plan, emb, table, prior_weight)
+    B, N, bs, ldx = _state(x, Nmax)
+    A, abs_ = _agents(agent_features, B)
+    logits = out if out is not None else torch.empty((B, plan.num_edges), dtype=torch.float32, device=x.device)
+    _contig(logits, torch.float32, "logits")
+    if tuple(logits.shape) != (B, plan.num_edges):
+        raise ValueError(f"logits must be ({B}, {plan.num_edges})")
+    _lib.check(L.tarl_fused_prior_logits(plan.handle, fs.ref, x.data_ptr(), B, bs, ldx, Nmax, agent_features.data_ptr(), A,
+                                         abs_, emb.data_ptr(), emb.numel(), table.data_ptr(), table.size(0), w,
+                                         logits.data_ptr(), _lib.current_stream()))
+    return logits
+
+
+def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeConst, emb, table, times, *, prior_weight,
+                        use_cong, temperature, policy_seed, policy_counter0, seed, counter0, scratch, prev_time=None,
+                        keep=None, obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None):
+    """``T = len(times)`` frames under the prior head in one foreign call (tarl_fused_rollout_prior). ``keep`` /
+    ``obs_keep`` / ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
+    L = _lib.load()
+    w = _prior_args(plan, emb, table, prior_weight)
+    T, B, N = len(times), fs.B, fs.N
+    A, abs_ = _agents(agent_features, B)
+    _, _, bs, ldx = _state(x, fs.Nmax)
+    _contig(scratch, torch.int32, "scratch")
+    _check_rollout_outputs(T, B, N, True, 0, None, counts, log_prob, None, reward, None, None, None)
+    _check_rollout_outputs(T, B, N, False, 0, choice8, None, None, None, None, None, None, None)
+    dev = fs.sel8.device
+    if getattr(fs, "prior_logits_scratch", None) is None:
+        fs.prior_logits_scratch = torch.empty((B, plan.num_edges), dtype=torch.float32, device=dev)
+        fs.prior_dist_scratch = torch.empty((int(L.tarl_graphdist_rollout_scratch_bytes(plan.handle, B)) + 7) // 8,
+                                            dtype=torch.float64, device=dev)
+    kptr = kenv = kslot = None
+    if keep is not None:
+        ptr, kenv, kslot = keep
+        if len(ptr) != T + 1 or ptr[0] != 0 or any(b < a for a, b in zip(ptr, ptr[1:])):
+            raise ValueError("keep pointer list must be T + 1 non-decreasing offsets starting at 0")
+        _contig(kenv, torch.int32, "keep env")
+        _contig(kslot, torch.int32, "keep slot")
+        _contig(obs_keep, torch.float32, "obs_keep")
+        if kenv.numel() < ptr[-1] or kslot.numel() < ptr[-1] or obs_keep.shape[1:] != (N, 16):
+            raise ValueError("keep arrays shorter than the pointer list, or obs_keep not (K, N, 16)")
+        kptr = (C.c_int64 * (T + 1))(*[int(v) for v in ptr])
+    tarr = (C.c_float * T)(*[float(t) for t in times])
+    _lib.check(L.tarl_fused_rollout_prior(
+        plan.handle, fs.ref, B, fs.Nmax, T, tarr, float(times[0] - 1 if prev_time is None else prev_time), x.data_ptr(),
+        bs, ldx, agent_features.data_ptr(), A, abs_, ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
+        1 if use_cong else 0, emb.data_ptr(), emb.numel(), table.data_ptr(), table.size(0), w, float(temperature),
+        int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot),
+        _lib.ptr(obs_keep), fs.prior_logits_scratch.data_ptr(), fs.prior_dist_scratch.data_ptr(), scratch.data_ptr(),
+        _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), _lib.current_stream()))
+
+
 def rollout_gather(plan: Plan, T, B, env_minor, idx=None, *, choice=None, counts=None):
     """Rollout bytes -> (choice_eid int32 (rows, N) | None, counts_f fp32 (rows, N) | None) for the (frame, env) pairs
     ``idx`` (int64 flat indices t * B + b; None = all ``T * B`` in order). ``choice`` / ``counts``: the uint8 buffers

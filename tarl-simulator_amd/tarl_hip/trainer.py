@@ -63,7 +63,8 @@ class VecPPOTrainer:
     def __init__(self, engine, emb_param, critic_params, *, rollout_steps, num_epochs=1, sub_batch_size=32, lr=1e-3,
                  gamma=0.99, lmbda=0.95, clip_epsilon=0.2, entropy_coef=0.01, critic_coef=1.0, temperature=1.0,
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
-                 policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None):
+                 policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
+                 prior_weight=1.0):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -78,7 +79,12 @@ class VecPPOTrainer:
         # ``policy_bf16``: rollout logits on the bf16 MFMA path (the update always runs in fp32). ``policy_precision``
         # ("fp32" | "bf16" | "x3") names the rollout kernel outright; the default for a non-bf16 policy is "x3": logits
         # within a few fp32 ulp of the fp32 MFMA kernel's (the north star's 1e-4 contract) at 2.7x its matrix rate.
+        # "embedding_dijkstra" = the embedding plus ``prior_weight`` times the shortest-path prior of the reference
+        # (src/agents/mpnn_agent.py:180-190, csrc/prior.hip): state-DEPENDENT like the MLP head, but without parameters of
+        # its own; ``prior_table`` (N, N) = MPNNPolicyNet.dist_matrix. Gradients reach the embedding alone.
         self.policy = policy
+        self.prior_table = prior_table
+        self.prior_weight = float(prior_weight)
         self.policy_precision = policy_precision or ("bf16" if policy_bf16 else "x3")
         if self.policy_precision not in ops.EDGE_MLP_PRECISIONS:
             raise ValueError(f"policy_precision must be one of {ops.EDGE_MLP_PRECISIONS}")
@@ -90,12 +96,19 @@ class VecPPOTrainer:
             ids = {id(p) for p in extra_params}
             if not all(id(p) in ids for p in self.edge_mlp_params):
                 raise ValueError("edge_mlp_params must be part of extra_params (the optimiser's flat buffer)")
+        elif policy == "embedding_dijkstra":
+            if engine.fs is None or prior_table is None:
+                raise ValueError("policy='embedding_dijkstra' needs the fused engine and the (N, N) prior_table")
+            if tuple(prior_table.shape) != (engine.N, engine.N):
+                raise ValueError(f"prior_table must be ({engine.N}, {engine.N})")
         elif policy != "embedding":
-            raise ValueError("policy must be 'embedding' or 'edge_mlp'")
+            raise ValueError("policy must be 'embedding', 'edge_mlp' or 'embedding_dijkstra'")
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
         self.lazy_log_prob = bool(lazy_log_prob)
+        if self.lazy_log_prob and policy == "embedding_dijkstra":
+            raise ValueError("lazy_log_prob re-evaluates the state-independent embedding head only")
         self.T = int(rollout_steps)
         self.num_epochs = int(num_epochs)
         self.M = int(sub_batch_size)
@@ -121,6 +134,8 @@ class VecPPOTrainer:
             mode = "unfused"
         elif policy == "edge_mlp":
             mode = "frames+policy"      # per-frame policy evaluation in front of the four-launch frame
+        elif policy == "embedding_dijkstra":
+            mode = "frames+prior"       # per-frame prior logits in front of the frame (pre-drawn minibatch frames, too)
         elif mode == "auto":
             mode = "env" if (engine.env_rollout_supported and engine.B * engine.N <= 800_000) else "frames"
         elif mode == "env" and not engine.env_rollout_supported:
@@ -128,13 +143,13 @@ class VecPPOTrainer:
         self.rollout = mode
         self.layout_tag = ops.FUSED_LAYOUT
         # rollout buffers, written directly by the kernels: ENV-MINOR ([frame][node][env]) for "frames"
-        self.env_minor = mode in ("frames", "frames+policy")
+        self.env_minor = mode in ("frames", "frames+policy", "frames+prior")
         shp = (lambda t: (t, N, B)) if self.env_minor else (lambda t: (t, B, N))
         # fused rollouts write one BYTE per (frame, node, env): the count and the rank of the chosen out-edge
-        byte = mode in ("frames", "env", "frames+policy")
+        byte = mode in ("frames", "env", "frames+policy", "frames+prior")
         self.counts = torch.zeros(shp(self.T + 1), dtype=torch.uint8 if byte else torch.float32, device=dev)
         # "frames+policy": the per-frame sampler (one workgroup per environment) writes its rank bytes env-major
-        self.choice = torch.zeros((self.T, B, N) if mode == "frames+policy" else shp(self.T),
+        self.choice = torch.zeros((self.T, B, N) if mode in ("frames+policy", "frames+prior") else shp(self.T),
                                   dtype=torch.uint8 if byte else torch.int32, device=dev)
         # per-step logs of SimulatorEnv._step, accumulated on the device by the rollout kernels: the leg histogram's
         # (departed, arrived) per frame for every environment, delta_travel_time / pop + withdraw masks per node for the
@@ -186,6 +201,38 @@ class VecPPOTrainer:
         queued by one foreign call per episode segment (tarl_fused_rollout_policy). Nothing is hoisted. The update only
         ever reads the observations of its minibatch frames, and those frames are a random draw that does not depend on
         the data: the draw is made up front and only their observations are kept."""
+        w = self._edge_mlp()
+        m = self.metrics_envs
+
+        def run(sl, seg, pseed, counter0, keep):
+            return self.eng.rollout_policy(seg, w, precision=self.policy_precision, temperature=self.temperature,
+                                           policy_seed=pseed, policy_counter0=counter0, choice8=self.choice[sl],
+                                           log_prob=self.logp[sl], reward=self.reward[sl],
+                                           counts=self.counts[sl.start:sl.stop + 1], keep=keep, obs_keep=self.obs_mb,
+                                           metrics_envs=m, dtt_node=self.dtt_node[sl] if m else None,
+                                           events=self.events[sl] if m else None, leg=self.leg[sl], check=False)
+        return self._collect_state_dependent(run)
+
+    @torch.no_grad()
+    def _collect_prior(self):
+        """T frames with the shortest-path prior head: per frame prior logits from the packed state (no observation
+        written) -> GraphDistribution sample + log_prob -> the simulation frame, one foreign call per episode segment
+        (tarl_fused_rollout_prior). Minibatch frames are drawn up front as for the MLP head; their observations are kept
+        so that the update recomputes exactly the rollout's logits. (The per-step logs leg / dtt_node / events stay
+        zero on this path.)"""
+        emb = self._emb()
+
+        def run(sl, seg, pseed, counter0, keep):
+            return self.eng.rollout_prior(seg, emb, self.prior_table, prior_weight=self.prior_weight,
+                                          temperature=self.temperature, policy_seed=pseed, policy_counter0=counter0,
+                                          choice8=self.choice[sl], log_prob=self.logp[sl], reward=self.reward[sl],
+                                          counts=self.counts[sl.start:sl.stop + 1], keep=keep, obs_keep=self.obs_mb,
+                                          check=False)
+        return self._collect_state_dependent(run)
+
+    def _collect_state_dependent(self, run):
+        """The collector loop of the state-dependent heads: ``run(slice, frames, policy_seed, policy_counter0, keep)``
+        queues one episode segment and returns its clock values."""
         from .engine import EPISODE_END
         eng = self.eng
         T, B, N = self.T, eng.B, eng.N
@@ -203,9 +250,7 @@ class VecPPOTrainer:
         keep_env = (flat[order] % B).to(torch.int32).pin_memory().to(eng.device, non_blocking=True)
         keep_slot = order.to(torch.int32).pin_memory().to(eng.device, non_blocking=True)
         self.obs_mb = torch.empty((flat.numel(), N, 16), dtype=torch.float32, device=eng.device)
-        w = self._edge_mlp()
         pseed = self.seed ^ 0x5DEECE66D
-        m = self.metrics_envs
         host_times, done, pos, t0 = [], [False] * T, 0, 0
         while t0 < T:
             # frames until the episode ends (clock past 7 h) or the batch is full: one foreign call
@@ -222,13 +267,7 @@ class VecPPOTrainer:
                     pos += 1
                 rel.append(pos - seg_lo)
             keep = (rel, keep_env[seg_lo:pos], keep_slot[seg_lo:pos]) if pos > seg_lo else None
-            sl = slice(t0, t0 + seg)
-            times = eng.rollout_policy(seg, w, precision=self.policy_precision, temperature=self.temperature, policy_seed=pseed,
-                                       policy_counter0=self.sample_counter + 1, choice8=self.choice[sl],
-                                       log_prob=self.logp[sl], reward=self.reward[sl],
-                                       counts=self.counts[t0:t0 + seg + 1], keep=keep, obs_keep=self.obs_mb,
-                                       metrics_envs=m, dtt_node=self.dtt_node[sl] if m else None,
-                                       events=self.events[sl] if m else None, leg=self.leg[sl], check=False)
+            times = run(slice(t0, t0 + seg), seg, pseed, self.sample_counter + 1, keep)
             host_times += times[:-1]
             self.sample_counter += seg
             t0 += seg
@@ -258,6 +297,8 @@ class VecPPOTrainer:
         from .engine import EPISODE_END
         if self.policy == "edge_mlp":
             return self._collect_edge_mlp()
+        if self.policy == "embedding_dijkstra":
+            return self._collect_prior()
         eng = self.eng
         eng.reset()
         emb = self._emb()
@@ -372,7 +413,8 @@ class VecPPOTrainer:
         eng = self.eng
         T, B, N, E = self.T, eng.B, eng.N, eng.E
         M = min(self.M, T * B)
-        if self.policy == "edge_mlp":       # the draw was made before the rollout (its observations were kept)
+        state_dep = self.policy in ("edge_mlp", "embedding_dijkstra")
+        if state_dep:       # the draw was made before the rollout (its observations were kept)
             k = self._epoch
             idx = self._mb_idx[k]
             M = idx.numel()
@@ -386,7 +428,7 @@ class VecPPOTrainer:
             M = idx.numel()
         st = self.stage
         with st("minibatch_gather"):
-            if self.policy == "edge_mlp":
+            if state_dep:
                 _, counts_mb = ops.rollout_gather(eng.plan, T, B, True, idx, counts=self.counts[:T])     # env-minor bytes
                 choice_mb, _ = ops.rollout_gather(eng.plan, T, B, False, idx, choice=self.choice)        # env-major bytes
             elif self.rollout == "unfused":
@@ -410,6 +452,8 @@ class VecPPOTrainer:
             if self.policy == "edge_mlp":
                 wmlp = self._edge_mlp()
                 logits = ops.policy_edge_mlp(eng.plan, obs_mb, eng.ec, wmlp)          # fp32 MFMA
+            elif self.policy == "embedding_dijkstra":      # the rollout's logits, recomputed from the kept observations
+                logits = ops.policy_prior_logits(eng.plan, obs_mb, self._emb(), self.prior_table, self.prior_weight)
             else:
                 logits = ops.policy_edge_logits(eng.plan, nf, self._emb())
         with st("graphdist_fwd"):
@@ -435,8 +479,9 @@ class VecPPOTrainer:
                 gm = [self.flat.grad_view(p) for p in self.edge_mlp_params]
                 ops.policy_edge_mlp_bwd(eng.plan, obs_mb, eng.ec, wmlp, g_logits,
                                         (gm[0], gm[1], gm[2], gm[3], gm[4].view(-1), gm[5]))
-            else:
-                g_emb = ops.policy_edge_logits_bwd(eng.plan, nf, g_logits, self.emb_param.numel())
+            else:       # the prior has no parameters: the embedding receives the logits' gradient as is
+                g_emb = ops.policy_edge_logits_bwd(eng.plan, obs_mb if self.policy == "embedding_dijkstra" else nf,
+                                                   g_logits, self.emb_param.numel())
                 self.flat.grad_view(self.emb_param).add_(g_emb.view_as(self.emb_param))
         gw = [self.flat.grad_view(p) for p in self.critic_params]
         with st("critic_bwd"):
