@@ -8,6 +8,8 @@ launch — every environment follows exactly the reference's
 """
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 
 from . import ops
@@ -175,7 +177,9 @@ class SimEngine:
         """True when one environment's hot records fit a CU's LDS (tarl_rollout_env)."""
         return self.fs is not None and ops.rollout_env_supported(self.plan)
 
-    def _rollout(self, fn, env_minor, T, choice, log_prob, reward, counts, metrics_envs, dtt_node, events, leg, check):
+    def _rollout(self, T, counts, env_minor, check, queue, **outputs):
+        """Bookkeeping of the multi-frame calls: ``queue(times, ..., **outputs)`` enqueues the ``T`` frames from the clock
+        values, the previous frame's clock, the engine's noise counters and ``counts[1:]``. Returns the clock values."""
         if self._packed_stale:
             self.resync()
         shp = (T + 1, self.N, self.B) if env_minor else (T + 1, self.B, self.N)
@@ -187,11 +191,8 @@ class SimEngine:
             times.append(float(t_clock))
             t_clock += self.timestep
         self._x_stale = True
-        self._times_dev = fn(self.plan, self.fs, self.tables, self.agents, self.ec, times, use_cong=self.cc is not None,
-                             prev_time=self._last_step_time, policy_seed=self.seed ^ 0x5DEECE66D,
-                             policy_counter0=self.sample_counter + 1, seed=self.seed, counter0=self.noise_counter + 1,
-                             scratch=self.ins_scratch, choice=choice, log_prob=log_prob, reward=reward,
-                             counts=counts[1:], metrics_envs=metrics_envs, dtt_node=dtt_node, events=events, leg=leg)
+        self._times_dev = queue(times, use_cong=self.cc is not None, prev_time=self._last_step_time, seed=self.seed,
+                                counter0=self.noise_counter + 1, scratch=self.ins_scratch, counts=counts[1:], **outputs)
         self.sample_counter += T
         self.noise_counter += T
         self._last_step_time = times[-1]
@@ -209,30 +210,11 @@ class SimEngine:
         (ENV-MAJOR rank bytes), ``counts`` (T+1,N,B) uint8 (counts[t + 1] = after frame t), ``log_prob`` / ``reward`` (T,B).
         Frame t draws its action with Philox counter ``policy_counter0 + t``. ``precision`` of the rollout's logits: "fp32"
         (fp32 MFMA), "bf16" (= ``bf16=True``) or "x3" (fp32-accurate on the bf16 pipe). Returns the list of clock values."""
-        if self._packed_stale:
-            self.resync()
-        if counts.dtype != torch.uint8 or tuple(counts.shape) != (T + 1, self.N, self.B) or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous uint8 {(T + 1, self.N, self.B)} tensor")
-        times = []
-        t_clock = self.time
-        for _ in range(T):
-            times.append(float(t_clock))
-            t_clock += self.timestep
-        self._x_stale = True
-        ops.fused_rollout_policy(self.plan, self.fs, self._x, self.agents, self.ec, weights, times,
-                                 use_cong=self.cc is not None, bf16=bf16, temperature=temperature, policy_seed=policy_seed,
-                                 policy_counter0=policy_counter0, seed=self.seed, counter0=self.noise_counter + 1,
-                                 scratch=self.ins_scratch, prev_time=self._last_step_time, keep=keep, obs_keep=obs_keep,
-                                 choice8=choice8, log_prob=log_prob, reward=reward, counts=counts[1:],
-                                 metrics_envs=metrics_envs, dtt_node=dtt_node, events=events, leg=leg, precision=precision)
-        self.sample_counter += T
-        self.noise_counter += T
-        self._last_step_time = times[-1]
-        self.time = t_clock
-        times.append(float(self.time))
-        if check:
-            self.check_flags()
-        return times
+        return self._rollout(T, counts, True, check,
+                             partial(ops.fused_rollout_policy, self.plan, self.fs, self._x, self.agents, self.ec, weights),
+                             bf16=bf16, temperature=temperature, policy_seed=policy_seed, policy_counter0=policy_counter0,
+                             keep=keep, obs_keep=obs_keep, choice8=choice8, log_prob=log_prob, reward=reward,
+                             metrics_envs=metrics_envs, dtt_node=dtt_node, events=events, leg=leg, precision=precision)
 
     def rollout_prior(self, T, emb, table, *, prior_weight=1.0, temperature, policy_seed, policy_counter0, choice8, log_prob,
                       reward, counts, keep=None, obs_keep=None, check=True):
@@ -240,30 +222,11 @@ class SimEngine:
         one foreign call: per frame prior logits from the packed state -> GraphDistribution sample + log-prob -> the
         simulation frame. Buffers as :meth:`rollout_policy` (``choice8`` (T,B,N), ``counts`` (T+1,N,B)). Returns the list of
         clock values."""
-        if self._packed_stale:
-            self.resync()
-        if counts.dtype != torch.uint8 or tuple(counts.shape) != (T + 1, self.N, self.B) or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous uint8 {(T + 1, self.N, self.B)} tensor")
-        times = []
-        t_clock = self.time
-        for _ in range(T):
-            times.append(float(t_clock))
-            t_clock += self.timestep
-        self._x_stale = True
-        ops.fused_rollout_prior(self.plan, self.fs, self._x, self.agents, self.ec, emb, table, times,
-                                prior_weight=prior_weight, use_cong=self.cc is not None, temperature=temperature,
-                                policy_seed=policy_seed, policy_counter0=policy_counter0, seed=self.seed,
-                                counter0=self.noise_counter + 1, scratch=self.ins_scratch, prev_time=self._last_step_time,
-                                keep=keep, obs_keep=obs_keep, choice8=choice8, log_prob=log_prob, reward=reward,
-                                counts=counts[1:])
-        self.sample_counter += T
-        self.noise_counter += T
-        self._last_step_time = times[-1]
-        self.time = t_clock
-        times.append(float(self.time))
-        if check:
-            self.check_flags()
-        return times
+        return self._rollout(T, counts, True, check,
+                             partial(ops.fused_rollout_prior, self.plan, self.fs, self._x, self.agents, self.ec, emb, table),
+                             prior_weight=prior_weight, temperature=temperature, policy_seed=policy_seed,
+                             policy_counter0=policy_counter0, keep=keep, obs_keep=obs_keep, choice8=choice8,
+                             log_prob=log_prob, reward=reward)
 
     def decode_rollout(self, env_minor, *, choice=None, counts=None):
         """The rollout's byte buffers in the formats of the unfused entry points, ENV-MAJOR: ``choice`` (T,N,B) / (T,B,N)
@@ -283,8 +246,10 @@ class SimEngine:
         """Same frames as :meth:`rollout_fused` through ``tarl_rollout_env`` (one workgroup per environment, LDS-resident
         records, a single launch); the buffers are ENV-MAJOR: ``choice`` (T,B,N) uint8, ``counts`` (T+1,B,N) uint8 with
         counts[t + 1] = the counts after frame t; ``log_prob`` (T,B) or None; ``reward`` (T,B)."""
-        return self._rollout(ops.rollout_env, False, T, choice, log_prob, reward, counts, metrics_envs, dtt_node, events,
-                             leg, check)
+        queue = partial(ops.rollout_env, self.plan, self.fs, self.tables, self.agents, self.ec)
+        return self._rollout(T, counts, False, check, queue, policy_seed=self.seed ^ 0x5DEECE66D,
+                             policy_counter0=self.sample_counter + 1, choice=choice, log_prob=log_prob, reward=reward,
+                             metrics_envs=metrics_envs, dtt_node=dtt_node, events=events, leg=leg)
 
     def rollout_fused(self, T, *, choice, log_prob, reward, counts, metrics_envs=0, dtt_node=None, events=None, leg=None,
                       check=True):
@@ -294,5 +259,7 @@ class SimEngine:
         first ``metrics_envs`` environments ``dtt_node`` (T,N,m) fp32 / ``events`` (T,N,m) uint8. Same as T calls of
         :meth:`frame_fused` with the per-frame Python overhead removed. ``check``: read the device status word afterwards
         (one synchronisation) and raise on a domain exit. Returns the list of clock values."""
-        return self._rollout(ops.fused_rollout, True, T, choice, log_prob, reward, counts, metrics_envs, dtt_node, events,
-                             leg, check)
+        queue = partial(ops.fused_rollout, self.plan, self.fs, self.tables, self.agents, self.ec)
+        return self._rollout(T, counts, True, check, queue, policy_seed=self.seed ^ 0x5DEECE66D,
+                             policy_counter0=self.sample_counter + 1, choice=choice, log_prob=log_prob, reward=reward,
+                             metrics_envs=metrics_envs, dtt_node=dtt_node, events=events, leg=leg)

@@ -974,6 +974,40 @@ def _check_rollout_outputs(T, B, N, env_minor, m_env, choice, counts, log_prob, 
             raise ValueError(f"{name} must be a contiguous cuda {dt} tensor of shape {shp}")
 
 
+def _rollout_args(fs: FusedState, agent_features, times, scratch, prev_time):
+    """Common preamble of the multi-frame wrappers -> (library, T, A, a_bstride, prev_time), ``prev_time`` defaulting to
+    ``times[0] - 1``."""
+    A, abs_ = _agents(agent_features, fs.B)
+    _contig(scratch, torch.int32, "scratch")
+    return _lib.load(), len(times), A, abs_, float(times[0] - 1 if prev_time is None else prev_time)
+
+
+def _keep_args(keep, obs_keep, T, N):
+    """``keep`` = (ptr, env, slot) of the state-dependent rollouts (see :func:`fused_rollout_policy`) -> the C arguments
+    (int64 pointer array, env, slot); Nones without ``keep``."""
+    if keep is None:
+        return None, None, None
+    ptr, kenv, kslot = keep
+    if len(ptr) != T + 1 or ptr[0] != 0 or any(b < a for a, b in zip(ptr, ptr[1:])):
+        raise ValueError("keep pointer list must be T + 1 non-decreasing offsets starting at 0")
+    _contig(kenv, torch.int32, "keep env")
+    _contig(kslot, torch.int32, "keep slot")
+    _contig(obs_keep, torch.float32, "obs_keep")
+    if kenv.numel() < ptr[-1] or kslot.numel() < ptr[-1] or obs_keep.shape[1:] != (N, 16):
+        raise ValueError("keep arrays shorter than the pointer list, or obs_keep not (K, N, 16)")
+    return (C.c_int64 * (T + 1))(*[int(v) for v in ptr]), kenv, kslot
+
+
+def _sampler_scratch(L, plan: Plan, fs: FusedState):
+    """The per-frame sampler's (B, E) fp32 logits and tarl_graphdist_rollout scratch, one pair per FusedState shared by
+    the state-dependent heads."""
+    if getattr(fs, "logits_scratch", None) is None:
+        fs.logits_scratch = torch.empty((fs.B, plan.num_edges), dtype=torch.float32, device=fs.sel8.device)
+        fs.dist_scratch = torch.empty((int(L.tarl_graphdist_rollout_scratch_bytes(plan.handle, fs.B)) + 7) // 8,
+                                      dtype=torch.float64, device=fs.sel8.device)
+    return fs.logits_scratch.data_ptr(), fs.dist_scratch.data_ptr()
+
+
 def fused_rollout(plan: Plan, fs: FusedState, tables: PolicyTables, agent_features, ec: EdgeConst, times, *, use_cong,
                   policy_seed, policy_counter0, seed, counter0, scratch, prev_time=None, choice=None, log_prob=None,
                   entropy=None, reward=None, counts=None, metrics_envs=0, dtt_node=None, events=None, leg=None):
@@ -982,22 +1016,18 @@ def fused_rollout(plan: Plan, fs: FusedState, tables: PolicyTables, agent_featur
     / ``reward`` (T,B) fp32, ``leg`` (T,B,2) int32, ``dtt_node`` (T,N,metrics_envs) fp32, ``events`` (T,N,metrics_envs)
     uint8 — all optional, contiguous device tensors. Frame t uses policy counter ``policy_counter0 + t`` and noise counter
     ``counter0 + t``."""
-    L = _lib.load()
-    T, B, N = len(times), fs.B, fs.N
-    A, abs_ = _agents(agent_features, B)
-    _contig(scratch, torch.int32, "scratch")
-    _check_rollout_outputs(T, B, N, True, metrics_envs, choice, counts, log_prob, entropy, reward, dtt_node, events, leg)
+    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
+    _check_rollout_outputs(T, fs.B, fs.N, True, metrics_envs, choice, counts, log_prob, entropy, reward, dtt_node, events, leg)
     if getattr(fs, "acc_scratch", None) is None:     # double buffers of the merged insert + choice launch
         fs.acc_scratch = torch.zeros_like(fs.acc_lp)
     if choice is None and getattr(fs, "sel_scratch", None) is None:
         fs.sel_scratch = torch.empty_like(fs.sel8)
-    need = int(L.tarl_fused_rollout_scratch_ints(plan.handle, T, B))
+    need = int(L.tarl_fused_rollout_scratch_ints(plan.handle, T, fs.B))
     if getattr(fs, "choice_scratch", None) is None or fs.choice_scratch.numel() < need:
         # unresolved-draw list + packed policy records + per-(frame, env) log-prob accumulators of the side stream
         fs.choice_scratch = torch.zeros(need, dtype=torch.int32, device=fs.sel8.device)
     tarr = (C.c_float * T)(*[float(t) for t in times])
-    _lib.check(L.tarl_fused_rollout(plan.handle, fs.ref, B, fs.Nmax, T, tarr,
-                                    float(times[0] - 1 if prev_time is None else prev_time), tables.thresholds.data_ptr(),
+    _lib.check(L.tarl_fused_rollout(plan.handle, fs.ref, fs.B, fs.Nmax, T, tarr, prev, tables.thresholds.data_ptr(),
                                     tables.log_probs.data_ptr(), tables.entropy.data_ptr(), int(policy_seed),
                                     int(policy_counter0), agent_features.data_ptr(), A, abs_, ec.edge_attr.data_ptr(),
                                     ec.log_edge_attr.data_ptr(), ec.log_eps, 1 if use_cong else 0, int(seed),
@@ -1018,38 +1048,23 @@ def fused_rollout_policy(plan: Plan, fs: FusedState, x, agent_features, ec: Edge
     observations (frame t, environment env[j]) for ptr[t] <= j < ptr[t + 1] are copied to ``obs_keep[slot[j]]``
     ((K, N, 16) fp32). ``choice8`` (T, B, N) uint8 ENV-MAJOR rank bytes; ``counts`` (T, N, B) uint8 env-minor; the
     other outputs as :func:`fused_rollout`."""
-    L = _lib.load()
-    T, B, N = len(times), fs.B, fs.N
-    A, abs_ = _agents(agent_features, B)
+    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
+    B, N = fs.B, fs.N
     _, _, bs, ldx = _state(x, fs.Nmax)
-    _contig(scratch, torch.int32, "scratch")
     _check_rollout_outputs(T, B, N, True, metrics_envs, None, counts, log_prob, None, reward, dtt_node, events, leg)
     _check_rollout_outputs(T, B, N, False, metrics_envs, choice8, None, None, None, None, None, None, None)
-    dev = fs.sel8.device
     if getattr(fs, "obs_scratch", None) is None:
-        fs.obs_scratch = torch.empty((B, N, 16), dtype=torch.float32, device=dev)
-        fs.logits_scratch = torch.empty((B, plan.num_edges), dtype=torch.float32, device=dev)
-        fs.dist_scratch = torch.empty((int(L.tarl_graphdist_rollout_scratch_bytes(plan.handle, B)) + 7) // 8,
-                                      dtype=torch.float64, device=dev)
-    kptr = kenv = kslot = None
-    if keep is not None:
-        ptr, kenv, kslot = keep
-        if len(ptr) != T + 1 or ptr[0] != 0 or any(b < a for a, b in zip(ptr, ptr[1:])):
-            raise ValueError("keep pointer list must be T + 1 non-decreasing offsets starting at 0")
-        _contig(kenv, torch.int32, "keep env")
-        _contig(kslot, torch.int32, "keep slot")
-        _contig(obs_keep, torch.float32, "obs_keep")
-        if kenv.numel() < ptr[-1] or kslot.numel() < ptr[-1] or obs_keep.shape[1:] != (N, 16):
-            raise ValueError("keep arrays shorter than the pointer list, or obs_keep not (K, N, 16)")
-        kptr = (C.c_int64 * (T + 1))(*[int(v) for v in ptr])
+        fs.obs_scratch = torch.empty((B, N, 16), dtype=torch.float32, device=fs.sel8.device)
+    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
+    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
     tarr = (C.c_float * T)(*[float(t) for t in times])
     _lib.check(L.tarl_fused_rollout_policy(
-        plan.handle, fs.ref, B, fs.Nmax, T, tarr, float(times[0] - 1 if prev_time is None else prev_time), x.data_ptr(),
-        bs, ldx, agent_features.data_ptr(), A, abs_, ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
+        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
+        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
         1 if use_cong else 0, *w.ptrs(), {"fp32": 0, "bf16": 1, "x3": 2}[_edge_mlp_precision(bf16, precision)],
         float(temperature), int(policy_seed), int(policy_counter0),
         int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot), _lib.ptr(obs_keep), fs.obs_scratch.data_ptr(),
-        fs.logits_scratch.data_ptr(), fs.dist_scratch.data_ptr(), scratch.data_ptr(), _lib.ptr(choice8),
+        logits_scratch, dist_scratch, scratch.data_ptr(), _lib.ptr(choice8),
         _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), int(metrics_envs), _lib.ptr(dtt_node), _lib.ptr(events),
         _lib.ptr(leg), _lib.current_stream()))
 
@@ -1104,37 +1119,21 @@ def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeC
                         keep=None, obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None):
     """``T = len(times)`` frames under the prior head in one foreign call (tarl_fused_rollout_prior). ``keep`` /
     ``obs_keep`` / ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
-    L = _lib.load()
     w = _prior_args(plan, emb, table, prior_weight)
-    T, B, N = len(times), fs.B, fs.N
-    A, abs_ = _agents(agent_features, B)
+    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
+    B, N = fs.B, fs.N
     _, _, bs, ldx = _state(x, fs.Nmax)
-    _contig(scratch, torch.int32, "scratch")
     _check_rollout_outputs(T, B, N, True, 0, None, counts, log_prob, None, reward, None, None, None)
     _check_rollout_outputs(T, B, N, False, 0, choice8, None, None, None, None, None, None, None)
-    dev = fs.sel8.device
-    if getattr(fs, "prior_logits_scratch", None) is None:
-        fs.prior_logits_scratch = torch.empty((B, plan.num_edges), dtype=torch.float32, device=dev)
-        fs.prior_dist_scratch = torch.empty((int(L.tarl_graphdist_rollout_scratch_bytes(plan.handle, B)) + 7) // 8,
-                                            dtype=torch.float64, device=dev)
-    kptr = kenv = kslot = None
-    if keep is not None:
-        ptr, kenv, kslot = keep
-        if len(ptr) != T + 1 or ptr[0] != 0 or any(b < a for a, b in zip(ptr, ptr[1:])):
-            raise ValueError("keep pointer list must be T + 1 non-decreasing offsets starting at 0")
-        _contig(kenv, torch.int32, "keep env")
-        _contig(kslot, torch.int32, "keep slot")
-        _contig(obs_keep, torch.float32, "obs_keep")
-        if kenv.numel() < ptr[-1] or kslot.numel() < ptr[-1] or obs_keep.shape[1:] != (N, 16):
-            raise ValueError("keep arrays shorter than the pointer list, or obs_keep not (K, N, 16)")
-        kptr = (C.c_int64 * (T + 1))(*[int(v) for v in ptr])
+    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
+    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
     tarr = (C.c_float * T)(*[float(t) for t in times])
     _lib.check(L.tarl_fused_rollout_prior(
-        plan.handle, fs.ref, B, fs.Nmax, T, tarr, float(times[0] - 1 if prev_time is None else prev_time), x.data_ptr(),
-        bs, ldx, agent_features.data_ptr(), A, abs_, ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
+        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
+        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
         1 if use_cong else 0, emb.data_ptr(), emb.numel(), table.data_ptr(), table.size(0), w, float(temperature),
         int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot),
-        _lib.ptr(obs_keep), fs.prior_logits_scratch.data_ptr(), fs.prior_dist_scratch.data_ptr(), scratch.data_ptr(),
+        _lib.ptr(obs_keep), logits_scratch, dist_scratch, scratch.data_ptr(),
         _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), _lib.current_stream()))
 
 
@@ -1229,17 +1228,13 @@ def rollout_env(plan: Plan, fs: FusedState, tables: PolicyTables, agent_features
     """Same contract as :func:`fused_rollout` through ``tarl_rollout_env`` (one workgroup per environment, LDS-resident
     records, one launch for all frames); the per-node buffers are ENV-MAJOR: ``choice`` / ``counts`` (T, B, N),
     ``dtt_node`` / ``events`` (T, metrics_envs, N)."""
-    L = _lib.load()
-    T, B, N = len(times), fs.B, fs.N
-    A, abs_ = _agents(agent_features, B)
-    _contig(scratch, torch.int32, "scratch")
-    _check_rollout_outputs(T, B, N, False, metrics_envs, choice, counts, log_prob, entropy, reward, dtt_node, events, leg)
+    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
+    _check_rollout_outputs(T, fs.B, fs.N, False, metrics_envs, choice, counts, log_prob, entropy, reward, dtt_node, events, leg)
     tdev = torch.tensor([float(t) for t in times], dtype=torch.float32).to(fs.sel.device, non_blocking=True)
     if getattr(fs, "env_scratch", None) is None:
         fs.env_scratch = torch.empty(int(L.tarl_rollout_env_scratch_bytes(plan.handle)), dtype=torch.uint8,
                                      device=fs.sel.device)
-    _lib.check(L.tarl_rollout_env(plan.handle, fs.ref, B, fs.Nmax, T, tdev.data_ptr(),
-                                  float(times[0] - 1 if prev_time is None else prev_time), tables.thresholds.data_ptr(),
+    _lib.check(L.tarl_rollout_env(plan.handle, fs.ref, fs.B, fs.Nmax, T, tdev.data_ptr(), prev, tables.thresholds.data_ptr(),
                                   tables.log_probs.data_ptr(), tables.entropy.data_ptr(), int(policy_seed),
                                   int(policy_counter0), agent_features.data_ptr(), A, abs_, ec.edge_attr.data_ptr(),
                                   ec.log_edge_attr.data_ptr(), ec.log_eps, 1 if use_cong else 0, int(seed),

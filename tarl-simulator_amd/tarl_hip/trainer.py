@@ -13,9 +13,14 @@ Multi-GPU: one process per GPU, each with its own environments and minibatch; gr
 """
 from __future__ import annotations
 
+import os
+from bisect import bisect_left
+
+import numpy as np
 import torch
 
 from . import dist_utils, ops
+from .engine import EPISODE_END
 from .flatparams import FlatParams
 
 
@@ -103,11 +108,13 @@ class VecPPOTrainer:
                 raise ValueError(f"prior_table must be ({engine.N}, {engine.N})")
         elif policy != "embedding":
             raise ValueError("policy must be 'embedding', 'edge_mlp' or 'embedding_dijkstra'")
+        # the state-dependent heads evaluate their logits in front of every frame and draw the minibatch frames up front
+        self.state_dep = policy != "embedding"
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
         self.lazy_log_prob = bool(lazy_log_prob)
-        if self.lazy_log_prob and policy == "embedding_dijkstra":
+        if self.lazy_log_prob and self.state_dep:
             raise ValueError("lazy_log_prob re-evaluates the state-independent embedding head only")
         self.T = int(rollout_steps)
         self.num_epochs = int(num_epochs)
@@ -128,28 +135,25 @@ class VecPPOTrainer:
         # 8192; N = 1024, B = 1024: frames 1.24x; N = 2500: env +19 % at B = 256, frames +13 % at B = 512. One environment
         # keeps one CU busy for the whole frame; the four-launch path spreads the same work over the chip but needs
         # enough environments to fill its lanes and hide four dependent launches.
-        import os
         mode = rollout or os.environ.get("TARL_ROLLOUT", "auto")
         if engine.fs is None:
             mode = "unfused"
-        elif policy == "edge_mlp":
-            mode = "frames+policy"      # per-frame policy evaluation in front of the four-launch frame
-        elif policy == "embedding_dijkstra":
-            mode = "frames+prior"       # per-frame prior logits in front of the frame (pre-drawn minibatch frames, too)
+        elif self.state_dep:    # per-frame policy evaluation in front of the four-launch frame
+            mode = "frames+policy" if policy == "edge_mlp" else "frames+prior"
         elif mode == "auto":
             mode = "env" if (engine.env_rollout_supported and engine.B * engine.N <= 800_000) else "frames"
         elif mode == "env" and not engine.env_rollout_supported:
             raise ValueError("rollout='env' needs a graph whose hot records fit the LDS (tarl_rollout_env_supported)")
         self.rollout = mode
         self.layout_tag = ops.FUSED_LAYOUT
-        # rollout buffers, written directly by the kernels: ENV-MINOR ([frame][node][env]) for "frames"
-        self.env_minor = mode in ("frames", "frames+policy", "frames+prior")
+        # rollout buffers, written directly by the kernels: ENV-MINOR ([frame][node][env]) for the "frames" family
+        self.env_minor = mode.startswith("frames")
         shp = (lambda t: (t, N, B)) if self.env_minor else (lambda t: (t, B, N))
         # fused rollouts write one BYTE per (frame, node, env): the count and the rank of the chosen out-edge
-        byte = mode in ("frames", "env", "frames+policy", "frames+prior")
+        byte = mode != "unfused"
         self.counts = torch.zeros(shp(self.T + 1), dtype=torch.uint8 if byte else torch.float32, device=dev)
-        # "frames+policy": the per-frame sampler (one workgroup per environment) writes its rank bytes env-major
-        self.choice = torch.zeros((self.T, B, N) if mode in ("frames+policy", "frames+prior") else shp(self.T),
+        # state-dependent heads: the per-frame sampler (one workgroup per environment) writes its rank bytes env-major
+        self.choice = torch.zeros((self.T, B, N) if self.state_dep else shp(self.T),
                                   dtype=torch.uint8 if byte else torch.int32, device=dev)
         # per-step logs of SimulatorEnv._step, accumulated on the device by the rollout kernels: the leg histogram's
         # (departed, arrived) per frame for every environment, delta_travel_time / pop + withdraw masks per node for the
@@ -172,7 +176,6 @@ class VecPPOTrainer:
         # shuffled buffer). Drawn on the HOST in O(M) (numpy's Floyd sampler) and copied behind the launches already queued:
         # a device randperm of T * B = 4.2 M keys is seven radix-sort passes + key generation per optimiser step (0.3 ms and a
         # dozen launches per iteration in profiles/r03_default_kernel_stats.csv) for 32 indices
-        import numpy as np
         self.np_rng = np.random.Generator(np.random.Philox(key=int(seed) + 7919 * off))
         self.seed = int(seed) + off
         self.sample_counter = 0
@@ -193,100 +196,6 @@ class VecPPOTrainer:
     def _edge_mlp(self):
         return ops.EdgeMlpWeights(*(p.data for p in self.edge_mlp_params))
 
-    # -- HOT LOOP A, state-dependent policy --------------------------------------------------------------------------------
-    @torch.no_grad()
-    def _collect_edge_mlp(self):
-        """T frames with the per-edge MLP policy: per frame observation (from the packed state) -> edge MLP on MFMA ->
-        GraphDistribution sample + log_prob (one launch) -> the three-launch simulation frame with that action, all
-        queued by one foreign call per episode segment (tarl_fused_rollout_policy). Nothing is hoisted. The update only
-        ever reads the observations of its minibatch frames, and those frames are a random draw that does not depend on
-        the data: the draw is made up front and only their observations are kept."""
-        w = self._edge_mlp()
-        m = self.metrics_envs
-
-        def run(sl, seg, pseed, counter0, keep):
-            return self.eng.rollout_policy(seg, w, precision=self.policy_precision, temperature=self.temperature,
-                                           policy_seed=pseed, policy_counter0=counter0, choice8=self.choice[sl],
-                                           log_prob=self.logp[sl], reward=self.reward[sl],
-                                           counts=self.counts[sl.start:sl.stop + 1], keep=keep, obs_keep=self.obs_mb,
-                                           metrics_envs=m, dtt_node=self.dtt_node[sl] if m else None,
-                                           events=self.events[sl] if m else None, leg=self.leg[sl], check=False)
-        return self._collect_state_dependent(run)
-
-    @torch.no_grad()
-    def _collect_prior(self):
-        """T frames with the shortest-path prior head: per frame prior logits from the packed state (no observation
-        written) -> GraphDistribution sample + log_prob -> the simulation frame, one foreign call per episode segment
-        (tarl_fused_rollout_prior). Minibatch frames are drawn up front as for the MLP head; their observations are kept
-        so that the update recomputes exactly the rollout's logits. (The per-step logs leg / dtt_node / events stay
-        zero on this path.)"""
-        emb = self._emb()
-
-        def run(sl, seg, pseed, counter0, keep):
-            return self.eng.rollout_prior(seg, emb, self.prior_table, prior_weight=self.prior_weight,
-                                          temperature=self.temperature, policy_seed=pseed, policy_counter0=counter0,
-                                          choice8=self.choice[sl], log_prob=self.logp[sl], reward=self.reward[sl],
-                                          counts=self.counts[sl.start:sl.stop + 1], keep=keep, obs_keep=self.obs_mb,
-                                          check=False)
-        return self._collect_state_dependent(run)
-
-    def _collect_state_dependent(self, run):
-        """The collector loop of the state-dependent heads: ``run(slice, frames, policy_seed, policy_counter0, keep)``
-        queues one episode segment and returns its clock values."""
-        from .engine import EPISODE_END
-        eng = self.eng
-        T, B, N = self.T, eng.B, eng.N
-        eng.reset()
-        self.counts[0].zero_()
-        M = min(self.M, T * B)
-        if self.obs_idx is not None:                    # test hook: these frames instead of a random draw
-            host = [self.obs_idx.cpu()]
-        else:
-            host = [self.draw_frames(T * B, M, device=False) for _ in range(self.num_epochs)]
-        self._mb_idx = [h.pin_memory().to(eng.device, non_blocking=True) for h in host]
-        flat = torch.cat(host)      # (the frame list stays on the host: no device round trip before the rollout)
-        order = torch.argsort(flat, stable=True)
-        t_sorted = torch.div(flat[order], B, rounding_mode="floor").tolist()
-        keep_env = (flat[order] % B).to(torch.int32).pin_memory().to(eng.device, non_blocking=True)
-        keep_slot = order.to(torch.int32).pin_memory().to(eng.device, non_blocking=True)
-        self.obs_mb = torch.empty((flat.numel(), N, 16), dtype=torch.float32, device=eng.device)
-        pseed = self.seed ^ 0x5DEECE66D
-        host_times, done, pos, t0 = [], [False] * T, 0, 0
-        while t0 < T:
-            # frames until the episode ends (clock past 7 h) or the batch is full: one foreign call
-            seg, clock = 0, float(eng.time)
-            while t0 + seg < T:
-                seg += 1
-                clock += eng.timestep
-                if clock > EPISODE_END:
-                    break
-            seg_lo = pos                     # the kept (frame, environment) pairs are sorted by frame
-            rel = [0]
-            for t in range(t0, t0 + seg):
-                while pos < len(t_sorted) and t_sorted[pos] == t:
-                    pos += 1
-                rel.append(pos - seg_lo)
-            keep = (rel, keep_env[seg_lo:pos], keep_slot[seg_lo:pos]) if pos > seg_lo else None
-            times = run(slice(t0, t0 + seg), seg, pseed, self.sample_counter + 1, keep)
-            host_times += times[:-1]
-            self.sample_counter += seg
-            t0 += seg
-            if eng.time > EPISODE_END:
-                done[t0 - 1] = True
-                if t0 < T:
-                    eng.reset()
-                    self.counts[t0].zero_()
-        host_times.append(float(eng.time))
-        self.times.copy_(torch.tensor(host_times, dtype=torch.float32))
-        self.done_frames = torch.tensor(done, dtype=torch.bool)
-        self.done_mask = (self.done_frames.to(eng.device, torch.uint8).view(T, 1).expand(T, B).contiguous()
-                          if any(done) else None)
-        self._flag_host.copy_(eng.fs.flags, non_blocking=True)      # polled at the next collect / checked at the end
-        self._flag_event = torch.cuda.Event()
-        self._flag_event.record()
-        self._epoch = 0
-        return T * B
-
     # -- HOT LOOP A -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def collect(self):
@@ -294,43 +203,24 @@ class VecPPOTrainer:
         An episode that ends inside the batch (clock past 7 h: ``done = terminated``, src/reinforcement_learning.py:273-276)
         is followed by a reset, like the collector's auto-reset: the rollout is split at that frame, the reset observation
         becomes the next frame's observation and ``done_frames`` marks the frame for GAE."""
-        from .engine import EPISODE_END
-        if self.policy == "edge_mlp":
-            return self._collect_edge_mlp()
-        if self.policy == "embedding_dijkstra":
-            return self._collect_prior()
         eng = self.eng
         eng.reset()
-        emb = self._emb()
         T = self.T
         host_times, done = [], [False] * T
         if eng.fs is not None:
-            # fused path: every output lands directly in the rollout buffers (no copies)
+            # fused path: every output lands directly in the rollout buffers (no copies), one foreign call per segment
             self.counts[0].zero_()
-            eng.prepare_policy(emb, self.temperature)      # once per parameter update, not per frame
-            # sample_log_prob is only ever read for the <= sub_batch_size frames of each minibatch: keep the behaviour
-            # policy's parameters and evaluate it (exactly, with the unfused kernel) for those frames at update time
-            self.emb_rollout = emb.clone()
-            self.poll_flags()
-            run = eng.rollout_env if self.rollout == "env" else eng.rollout_fused
-            t = 0
-            while t < T:
-                # frames until the episode ends (the frame whose step pushes the clock past EPISODE_END is the last)
-                left = (EPISODE_END - eng.time) // eng.timestep + 1
-                n = int(min(T - t, max(1, left)))
-                sl = slice(t, t + n)
-                host_times += run(n, choice=self.choice[sl], log_prob=None if self.lazy_log_prob else self.logp[sl],
-                                  reward=self.reward[sl], counts=self.counts[t:t + n + 1],
-                                  metrics_envs=self.metrics_envs,
-                                  dtt_node=None if self.dtt_node is None else self.dtt_node[sl],
-                                  events=None if self.events is None else self.events[sl], leg=self.leg[sl],
-                                  check=False)[:-1]
-                t += n
-                if eng.time > EPISODE_END:
-                    done[t - 1] = True
-                    if t < T:
-                        eng.reset()
-                        self.counts[t].zero_()         # the reset observation is frame t's observation
+            if self.state_dep:
+                self._draw_minibatch_frames()
+            else:
+                emb = self._emb()
+                eng.prepare_policy(emb, self.temperature)      # once per parameter update, not per frame
+                # sample_log_prob is only ever read for the <= sub_batch_size frames of each minibatch: keep the behaviour
+                # policy's parameters and evaluate it (exactly, with the unfused kernel) for those frames at update time
+                self.emb_rollout = emb.clone()
+                self.poll_flags()
+            for sl in self._segments(done):
+                host_times += self._queue(sl)[:-1]
             host_times.append(float(eng.time))
             # the device status word travels to pinned host memory behind the rollout; it is looked at when it has
             # arrived (no stall of the launch pipeline) and by check_flags() at the caller's synchronisation points
@@ -338,6 +228,7 @@ class VecPPOTrainer:
             self._flag_event = torch.cuda.Event()
             self._flag_event.record()
         else:
+            emb = self._emb()
             for t in range(T):
                 self.counts[t].copy_(eng.counts)
                 host_times.append(float(eng.time))
@@ -364,6 +255,68 @@ class VecPPOTrainer:
                           if any(done) else None)
         return T * eng.B
 
+    def _segments(self, done):
+        """The batch's frames as episode segments (slices), each queued by one foreign call: frames until the episode ends
+        (the frame whose step pushes the clock past EPISODE_END is the last) or the batch is full. After an episode end
+        the engine is reset, the reset observation becomes the next frame's and ``done`` marks the frame."""
+        eng, T, t = self.eng, self.T, 0
+        while t < T:
+            n = int(min(T - t, max(1, (EPISODE_END - eng.time) // eng.timestep + 1)))
+            yield slice(t, t + n)
+            t += n
+            if eng.time > EPISODE_END:
+                done[t - 1] = True
+                if t < T:
+                    eng.reset()
+                    self.counts[t].zero_()
+
+    def _draw_minibatch_frames(self):
+        """State-dependent heads: the update only ever reads the observations of its minibatch frames, and those frames are
+        a random draw that does not depend on the data. The draw is made up front and the rollout keeps only their
+        observations, so that the update recomputes exactly the rollout's logits."""
+        eng = self.eng
+        T, B, N = self.T, eng.B, eng.N
+        if self.obs_idx is not None:                    # test hook: these frames instead of a random draw
+            host = [self.obs_idx.cpu()]
+        else:
+            host = [self.draw_frames(T * B, min(self.M, T * B), device=False) for _ in range(self.num_epochs)]
+        self._mb_idx = [h.pin_memory().to(eng.device, non_blocking=True) for h in host]
+        self._epoch = 0
+        flat = torch.cat(host)      # (the frame list stays on the host: no device round trip before the rollout)
+        order = torch.argsort(flat, stable=True)
+        self._keep = (torch.div(flat[order], B, rounding_mode="floor").tolist(),        # frames, sorted
+                      (flat[order] % B).to(torch.int32).pin_memory().to(eng.device, non_blocking=True),
+                      order.to(torch.int32).pin_memory().to(eng.device, non_blocking=True))
+        self.obs_mb = torch.empty((flat.numel(), N, 16), dtype=torch.float32, device=eng.device)
+
+    def _queue(self, sl):
+        """Frames ``sl`` (one episode segment) in one foreign call; returns the clock values. The embedding head draws from
+        its tables (tarl_rollout_env / tarl_fused_rollout); the state-dependent heads evaluate their logits from the packed
+        state per frame (tarl_fused_rollout_policy: observation -> edge MLP; tarl_fused_rollout_prior: shortest-path
+        prior, without the per-step logs leg / dtt_node / events) -> GraphDistribution sample + log_prob -> the frame."""
+        eng, n = self.eng, sl.stop - sl.start
+        counts = self.counts[sl.start:sl.stop + 1]
+        logs = dict(metrics_envs=self.metrics_envs, dtt_node=None if self.dtt_node is None else self.dtt_node[sl],
+                    events=None if self.events is None else self.events[sl], leg=self.leg[sl])
+        if not self.state_dep:
+            run = eng.rollout_env if self.rollout == "env" else eng.rollout_fused
+            return run(n, choice=self.choice[sl], log_prob=None if self.lazy_log_prob else self.logp[sl],
+                       reward=self.reward[sl], counts=counts, check=False, **logs)
+        # the kept (frame, environment) pairs of this segment with their offsets per frame
+        t_sorted, keep_env, keep_slot = self._keep
+        lo, hi = bisect_left(t_sorted, sl.start), bisect_left(t_sorted, sl.stop)
+        keep = ([bisect_left(t_sorted, t) - lo for t in range(sl.start, sl.stop + 1)], keep_env[lo:hi],
+                keep_slot[lo:hi]) if hi > lo else None
+        kw = dict(temperature=self.temperature, policy_seed=self.seed ^ 0x5DEECE66D, policy_counter0=self.sample_counter + 1,
+                  choice8=self.choice[sl], log_prob=self.logp[sl], reward=self.reward[sl], counts=counts, keep=keep,
+                  obs_keep=self.obs_mb, check=False)
+        if self.policy == "edge_mlp":
+            times = eng.rollout_policy(n, self._edge_mlp(), precision=self.policy_precision, **logs, **kw)
+        else:
+            times = eng.rollout_prior(n, self._emb(), self.prior_table, prior_weight=self.prior_weight, **kw)
+        self.sample_counter += n
+        return times
+
     def draw_frames(self, n, M, device=True):
         """M distinct flat frame indices t * B + b out of n, uniform, int64 (host draw; device=True: asynchronous copy)."""
         idx = torch.from_numpy(self.np_rng.choice(n, size=M, replace=False, shuffle=True).astype("int64"))
@@ -382,6 +335,27 @@ class VecPPOTrainer:
         self.eng.check_flags()
 
     # -- HOT LOOP B -------------------------------------------------------------------------------------------------------
+    def _actor_logits(self, obs):
+        """The policy head's logits (M, E) for the minibatch observations ``obs``, fp32, current parameters (the prior
+        head's equal the rollout's, recomputed from the kept observations)."""
+        eng = self.eng
+        if self.policy == "edge_mlp":
+            return ops.policy_edge_mlp(eng.plan, obs, eng.ec, self._edge_mlp())          # fp32 MFMA
+        if self.policy == "embedding_dijkstra":
+            return ops.policy_prior_logits(eng.plan, obs, self._emb(), self.prior_table, self.prior_weight)
+        return ops.policy_edge_logits(eng.plan, obs, self._emb())
+
+    def _actor_logits_bwd(self, obs, g_logits):
+        """Backward of :meth:`_actor_logits`: the parameter gradients land in the flat gradient buffer."""
+        eng = self.eng
+        if self.policy == "edge_mlp":
+            gm = [self.flat.grad_view(p) for p in self.edge_mlp_params]
+            ops.policy_edge_mlp_bwd(eng.plan, obs, eng.ec, self._edge_mlp(), g_logits,
+                                    (gm[0], gm[1], gm[2], gm[3], gm[4].view(-1), gm[5]))
+        else:       # the prior has no parameters: the embedding receives the logits' gradient as is
+            g_emb = ops.policy_edge_logits_bwd(eng.plan, obs, g_logits, self.emb_param.numel())
+            self.flat.grad_view(self.emb_param).add_(g_emb.view_as(self.emb_param))
+
     def advantages(self):
         """GAE(gamma, lmbda, average_gae=True) with the current critic over all (T+1)*B observations."""
         eng = self.eng
@@ -411,24 +385,20 @@ class VecPPOTrainer:
     def minibatch_step(self, adv, target, idx=None):
         """One minibatch + one Adam step. ``idx`` (test hook): flat frame indices t * B + b instead of a random draw."""
         eng = self.eng
-        T, B, N, E = self.T, eng.B, eng.N, eng.E
-        M = min(self.M, T * B)
-        state_dep = self.policy in ("edge_mlp", "embedding_dijkstra")
-        if state_dep:       # the draw was made before the rollout (its observations were kept)
-            k = self._epoch
-            idx = self._mb_idx[k]
-            M = idx.numel()
-            off = sum(i.numel() for i in self._mb_idx[:k])
-            obs_mb = self.obs_mb[off:off + M]
+        T, B, N = self.T, eng.B, eng.N
+        if self.state_dep:       # the draw was made before the rollout (its observations were kept)
+            idx = self._mb_idx[self._epoch]
+            off = sum(i.numel() for i in self._mb_idx[:self._epoch])
+            obs = self.obs_mb[off:off + idx.numel()]
             self._epoch += 1
-        elif idx is None:
-            idx = self.draw_frames(T * B, M)
         else:
-            idx = idx.to(eng.device)
-            M = idx.numel()
+            idx = self.draw_frames(T * B, min(self.M, T * B)) if idx is None else idx.to(eng.device)
+            # the live policy reads only the static ROAD_INDEX column: one observation broadcast over the minibatch
+            obs = eng.static_node_features[:1].expand(idx.numel(), N, 7)
+        M = idx.numel()
         st = self.stage
         with st("minibatch_gather"):
-            if state_dep:
+            if self.state_dep:
                 _, counts_mb = ops.rollout_gather(eng.plan, T, B, True, idx, counts=self.counts[:T])     # env-minor bytes
                 choice_mb, _ = ops.rollout_gather(eng.plan, T, B, False, idx, choice=self.choice)        # env-major bytes
             elif self.rollout == "unfused":
@@ -437,9 +407,8 @@ class VecPPOTrainer:
             else:   # one launch: the sampled frames' action bytes -> edge ids, count bytes -> fp32 rows
                 choice_mb, counts_mb = ops.rollout_gather(eng.plan, T, B, self.env_minor, idx, choice=self.choice,
                                                           counts=self.counts[:T])
-            nf = eng.static_node_features[:1].expand(M, N, 7)
             if eng.fs is not None and self.lazy_log_prob:   # behaviour log-prob of the sampled frames, rollout-time parameters
-                p_old = ops.graphdist_softmax(eng.plan, ops.policy_edge_logits(eng.plan, nf, self.emb_rollout),
+                p_old = ops.graphdist_softmax(eng.plan, ops.policy_edge_logits(eng.plan, obs, self.emb_rollout),
                                               self.temperature)
                 lp_old, _ = ops.graphdist_logprob_entropy(eng.plan, p_old, choice=choice_mb, want_entropy=False)
             else:
@@ -447,15 +416,8 @@ class VecPPOTrainer:
             adv_mb = adv.view(-1).index_select(0, idx)
             tgt_mb = target.view(-1).index_select(0, idx)
             time_mb = self.times[:T].index_select(0, torch.div(idx, B, rounding_mode="floor"))
-        # actor forward (the live policy reads only the static ROAD_INDEX column: broadcast one observation over M rows)
         with st("actor_logits_fwd"):
-            if self.policy == "edge_mlp":
-                wmlp = self._edge_mlp()
-                logits = ops.policy_edge_mlp(eng.plan, obs_mb, eng.ec, wmlp)          # fp32 MFMA
-            elif self.policy == "embedding_dijkstra":      # the rollout's logits, recomputed from the kept observations
-                logits = ops.policy_prior_logits(eng.plan, obs_mb, self._emb(), self.prior_table, self.prior_weight)
-            else:
-                logits = ops.policy_edge_logits(eng.plan, nf, self._emb())
+            logits = self._actor_logits(obs)
         with st("graphdist_fwd"):
             proba = ops.graphdist_softmax(eng.plan, logits, self.temperature)
             lp_new, ent = ops.graphdist_logprob_entropy(eng.plan, proba, choice=choice_mb)
@@ -475,14 +437,7 @@ class VecPPOTrainer:
             g_logits = ops.graphdist_logprob_entropy_bwd(eng.plan, proba, self.temperature, choice=choice_mb,
                                                          grad_log_prob=g_lp, grad_entropy=g_ent, log_prob_fwd=lp_new)
         with st("actor_logits_bwd"):
-            if self.policy == "edge_mlp":
-                gm = [self.flat.grad_view(p) for p in self.edge_mlp_params]
-                ops.policy_edge_mlp_bwd(eng.plan, obs_mb, eng.ec, wmlp, g_logits,
-                                        (gm[0], gm[1], gm[2], gm[3], gm[4].view(-1), gm[5]))
-            else:       # the prior has no parameters: the embedding receives the logits' gradient as is
-                g_emb = ops.policy_edge_logits_bwd(eng.plan, obs_mb if self.policy == "embedding_dijkstra" else nf,
-                                                   g_logits, self.emb_param.numel())
-                self.flat.grad_view(self.emb_param).add_(g_emb.view_as(self.emb_param))
+            self._actor_logits_bwd(obs, g_logits)
         gw = [self.flat.grad_view(p) for p in self.critic_params]
         with st("critic_bwd"):
             ops.critic_backward(cw, counts_mb, time_mb, 1, h1, h2, g_val,

@@ -130,3 +130,16 @@ def test_trainer_and_dispatch_know_the_head():
     assert MPNNPolicyNet.policy_head == "embedding" and MPNNPolicyNet.prior_weight == 1.0
     src = inspect.getsource(__import__("src.rl.ppo_trainer", fromlist=["ppo_train"]).ppo_train)
     assert "embedding_dijkstra" in src and "prior_table" in src
+
+
+def test_trainer_refuses_lazy_log_prob_for_state_dependent_heads():
+    """lazy_log_prob re-evaluates the embedding head's tables at update time: both state-dependent heads refuse it up
+    front (checked before the engine is touched, so a stand-in engine suffices)."""
+    import types
+    from tarl_hip.trainer import VecPPOTrainer
+    eng = types.SimpleNamespace(fs=object(), N=4)
+    mlp = [torch.zeros(1) for _ in range(6)]
+    for kw in (dict(policy="edge_mlp", edge_mlp_params=mlp, extra_params=mlp),
+               dict(policy="embedding_dijkstra", prior_table=torch.zeros(4, 4))):
+        with pytest.raises(ValueError, match="lazy_log_prob"):
+            VecPPOTrainer(eng, torch.zeros(4, 1), [], rollout_steps=4, lazy_log_prob=True, **kw)
