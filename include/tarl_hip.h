@@ -587,6 +587,52 @@ int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t
                              const int32_t* keep_slot, float* obs_keep, float* logits_scratch, void* dist_scratch,
                              int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
                              tarl_stream stream);
+/* ---- the graph-transformer head of MPNNPolicyNet (policy_head = "graph_transformer"; csrc/gt_policy.hip) ------------------
+ * The edge output (raw=True) of GraphTransformerNet (src/transformer/model.py:140-178) as MLAgents builds it
+ * (src/agents/transformer_agent.py:30-39: hidden 16, 4 heads, gate=True, 2 GTConv layers; node input 16 = obs16), in
+ * evaluation mode: BatchNorm on running_mean / running_var (eps 1e-5), dropout = identity. GTConv: src/transformer/gt_conv.py:144-232
+ * (attention softmax over the in-edges of the target as torch_geometric.utils.softmax: max subtracted, + 1e-16).
+ * w: host array of TARL_GT_NUM_TENSORS device pointers, fp32 nn.Linear layouts: the TARL_GT_NUM_PARAMS trainable tensors that
+ *   reach the logits, in this order (state-dict names of GraphTransformerNet):
+ *     node_emb.weight, pe_emb.weight, edge_emb.weight,
+ *     gt_layers.0.{WQ.weight, WK.weight, WV.weight, n_gate.weight, n_gate.bias, WO.weight, WO.bias, norm1.weight,
+ *       norm1.bias, ffn.mlp.0.weight, ffn.mlp.0.bias, ffn.mlp.3.weight, ffn.mlp.3.bias, norm2.weight, norm2.bias},
+ *     gt_layers.L.{WE.weight, WE.bias, WOe.weight, WOe.bias, norm1e.weight, norm1e.bias, ffn_e.mlp.0.weight,
+ *       ffn_e.mlp.0.bias, ffn_e.mlp.3.weight, ffn_e.mlp.3.bias, norm2e.weight, norm2e.bias} for L = 0, then
+ *     gt_layers.1.{WQ.weight, WK.weight}, the same twelve for L = 1, edge_linear.weight, edge_linear.bias;
+ *   then the running statistics: gt_layers.0.{norm1, norm2, norm1e, norm2e}.{running_mean, running_var},
+ *   gt_layers.1.{norm1e, norm2e}.{running_mean, running_var}. The rest of the module (gt_layers.1's node side, e_gate,
+ *   mu_mlp, log_var_mlp) does not reach the logits (gt_conv.py:218-222 overwrites the e_gate product).
+ * pe [N][16]: the positional encoding (Laplacian eigenvectors, transformer_agent.py:153-200), 16-byte aligned;
+ * obs16 [M][N][16] as tarl_policy_obs16; edge_attr [E] (edge_dim_in = 1); logits [M][E], original edge order.
+ * tarl_policy_gt_fwd: scratch fp32 of at least tarl_policy_gt_fwd_scratch_floats(plan, M), 16-byte aligned.
+ * tarl_policy_gt_bwd ACCUMULATES (+=) the gradients of sum(grad_logits * logits) into grads (host array of
+ *   TARL_GT_NUM_PARAMS device pointers, same order and shapes as w), the forward recomputed inside; scratch: at least
+ *   tarl_policy_gt_bwd_scratch_floats(plan, M) floats. Deterministic: no atomics, per-node sums over in- / out-edges in
+ *   CSC / CSR order, weight gradients summed over fixed chunks of items, then the chunks in order. */
+#define TARL_GT_NUM_PARAMS 46
+#define TARL_GT_NUM_TENSORS 58
+int64_t tarl_policy_gt_fwd_scratch_floats(const tarl_plan* plan, int64_t M);
+int tarl_policy_gt_fwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* edge_attr, const float* pe,
+                       const float* const* w, float* scratch, int64_t scratch_floats, float* logits, tarl_stream stream);
+int64_t tarl_policy_gt_bwd_scratch_floats(const tarl_plan* plan, int64_t M);
+int tarl_policy_gt_bwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* edge_attr, const float* pe,
+                       const float* const* w, const float* grad_logits, float* scratch, int64_t scratch_floats,
+                       float* const* grads, tarl_stream stream);
+/* tarl_fused_rollout_gt: tarl_fused_rollout_prior with the graph-transformer head — T frames in one foreign call, per frame
+ *   [tarl_fused_obs16_rows of the kept environments] -> tarl_fused_obs16 (obs_scratch fp32 [B][N][16]) -> the forward above
+ *   (gt_scratch: tarl_policy_gt_fwd_scratch_floats(plan, B) floats; the state-independent terms once per call) ->
+ *   tarl_graphdist_rollout (temperature; policy counter policy_counter0 + t; writes tarl_fused.sel8) -> tarl_fused_frame
+ *   (noise counter counter0 + t) -> the count bytes. Other arguments and outputs as tarl_fused_rollout_prior. */
+int tarl_fused_rollout_gt(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                          const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
+                          float* agent_features, int64_t num_agents, int64_t a_bstride, const float* edge_attr,
+                          const float* log_edge_attr, float log_eps, int use_cong, const float* pe, const float* const* w,
+                          float temperature, uint64_t policy_seed, uint64_t policy_counter0, uint64_t seed,
+                          uint64_t counter0, const int64_t* keep_ptr_host, const int32_t* keep_env,
+                          const int32_t* keep_slot, float* obs_keep, float* obs_scratch, float* gt_scratch,
+                          int64_t gt_scratch_floats, float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
+                          uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts, tarl_stream stream);
 /* the action / count bytes of a rollout back in the formats of the unfused entry points: choice_eid int32 [rows][N] =
  *   chosen edge id (-1: none), counts_f fp32 [rows][N], for `rows` (frame, environment) pairs given as flat indices
  *   idx int64 [rows] = t * B + b (NULL: all T * B pairs in order). env_minor != 0: the buffers are [T][N][B], else

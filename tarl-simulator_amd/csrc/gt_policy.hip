@@ -1,0 +1,820 @@
+// gt_policy.hip — the graph-transformer policy head of MPNNPolicyNet (policy_head = "graph_transformer"): the edge output of
+// the reference's GraphTransformerNet (src/transformer/model.py:140-178, raw=True) as MLAgents builds it
+// (src/agents/transformer_agent.py:30-39: 16 -> 16 hidden, 4 heads of d_k = 4, gate=True, two GTConv layers), in evaluation
+// mode (BatchNorm on its running statistics, dropout = identity). Edge e = (u -> v), PyG source_to_target: i = v, j = u.
+//
+//   x0 = node_emb(obs16) + pe_emb(pe)              e0 = edge_emb(edge_attr)                       (model.py:160-164)
+//   per layer (gt_conv.py:144-232):  Q, K, V = WQ x, WK x, WV x;  G = n_gate x + b
+//     q_e = Q_v * K_u / 2 (per channel);  eij = WE(e) * q_e;  score_e,h = sum_{d in h} Q_v K_u / 2
+//     alpha = softmax of the scores over the in-edges of v (PyG 2.5: group max subtracted, + 1e-16 in the denominator)
+//     x' = BN2(y + FFN(y)),  y = BN1(WO(sum_u alpha V_u sigmoid(G_u)) + x)
+//     e' = BN2e(z + FFN_e(z)), z = BN1e(WOe(eij) + e)                 FFN = Linear -> ReLU -> (Dropout) -> Linear
+//   logits = edge_linear(e2)                                                                          (model.py:174-178)
+//
+// Only what reaches the logits is computed: the e_gate product is overwritten before use (gt_conv.py:218-222), and in the
+// last layer WV, n_gate, WO, norm1, ffn and norm2 feed x2 alone (-> pool / value output). Those parameters receive no
+// gradient here. fp32 on the vector ALU, one thread per (sample, node) or (sample, edge); the weights are wave-uniform
+// (scalar loads from a pointer table passed by value).
+//
+// Passes (forward):  hoist (state-independent: P = pe_emb(pe) per node, e0 and E1 = WE1 e0 + b per edge) ->
+//   node pass A (x0; Q1, K1, V1 * sigmoid(G1)) -> node pass B (segment softmax over the CSC in-edges, WO, BN, FFN, BN -> x1;
+//   Q2, K2) -> edge pass C (both edge layers, edge_linear -> logits [M][E] in original edge order).
+// Backward (forward recomputed inside): A, B and C store their activations in per-item records; C runs the edge chain
+// backwards; node pass D walks the in- and out-edges (CSC / CSR order) for the gradients of Q2 / K2 and runs the node layer
+// backwards to the attention; pass E walks them again for Q1 / K1 / V / G and x0. Weight gradients: every one is a sum over
+// items (sample, node) or (sample, edge) of products of two recorded vectors — stage 1 sums fixed chunks of items per output
+// in item order, stage 2 adds the chunk partials in chunk order into the caller's buffers. No atomics: bit-reproducible.
+#include <math.h>
+
+#include "fused_common.h"
+
+#define GT_BLOCK 256
+#define GT_CHUNK 1024      // items per stage-1 partial sum of the weight gradients
+
+// ---- the pointer table: trainable parameters in kernel order (GT_NP), then the BatchNorm running statistics -------------
+enum {
+  P_NODE_EMB = 0, P_PE_EMB, P_EDGE_EMB,
+  // gt_layers.0
+  P0_WQ, P0_WK, P0_WV, P0_NG_W, P0_NG_B, P0_WO_W, P0_WO_B, P0_N1_W, P0_N1_B, P0_F0_W, P0_F0_B, P0_F3_W, P0_F3_B, P0_N2_W,
+  P0_N2_B,
+  P0_WE_W, P0_WE_B, P0_WOE_W, P0_WOE_B, P0_N1E_W, P0_N1E_B, P0_FE0_W, P0_FE0_B, P0_FE3_W, P0_FE3_B, P0_N2E_W, P0_N2E_B,
+  // gt_layers.1 (only what reaches the logits)
+  P1_WQ, P1_WK,
+  P1_WE_W, P1_WE_B, P1_WOE_W, P1_WOE_B, P1_N1E_W, P1_N1E_B, P1_FE0_W, P1_FE0_B, P1_FE3_W, P1_FE3_B, P1_N2E_W, P1_N2E_B,
+  P_LIN_W, P_LIN_B,
+  GT_NP_,
+  // running_mean / running_var
+  R0_N1_M = GT_NP_, R0_N1_V, R0_N2_M, R0_N2_V, R0_N1E_M, R0_N1E_V, R0_N2E_M, R0_N2E_V, R1_N1E_M, R1_N1E_V, R1_N2E_M,
+  R1_N2E_V,
+  GT_NW_
+};
+static_assert(GT_NP_ == TARL_GT_NUM_PARAMS, "parameter table out of step with the header");
+static_assert(GT_NW_ == TARL_GT_NUM_TENSORS, "tensor table out of step with the header");
+
+struct GtW {
+  const float* p[GT_NW_];
+};
+
+// first parameter index of each edge layer's block (WE_W .. N2E_B) and its running statistics
+__host__ __device__ constexpr int edge_par(int L) { return L == 0 ? P0_WE_W : P1_WE_W; }
+__host__ __device__ constexpr int edge_run(int L) { return L == 0 ? R0_N1E_M : R1_N1E_M; }
+
+// ---- record layouts --------------------------------------------------------------------------------------------------------
+// node record (sample, node): 16-float slots; the forward keeps the first NF_SLOTS, the backward all NB_SLOTS
+enum {
+  NQ1 = 0, NK1, NVG1, NQ2, NK2, NX0, NF_SLOTS,
+  NV1 = NF_SLOTS, NSG, NAGG, NTH1, NY, NH, NR, NSH2, NX1, NOBS, NPE,
+  NGQ2, NGK2, NGX1, NGS, NGH, NGY, NGT, NGAGG, NGQ1, NGK1, NGV, NGG, NGX0, NB_SLOTS
+};
+// edge record (sample, edge), backward only: 18 slots per layer, then the edge attribute and the logit's gradient
+enum { EIN = 0, EE, EQ, EIJ, ETH, EZ, EH, ER, ESH, EOUT, EGE, EGT, EGZ, EGH, EGS, EGOUT, EGIN, EGQ, E_LAYER_SLOTS };
+enum { E_ATTR = 2 * E_LAYER_SLOTS, E_GLOGIT, E_SLOTS };
+// hoisted per-edge / per-node constants: [E][32] = {e0, E1}, then [N][16] = P
+#define HOIST_E 32
+
+__device__ __forceinline__ void ld16(const float* __restrict__ p, float* v) {
+  const float4* q = reinterpret_cast<const float4*>(p);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 t = q[i];
+    v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+  }
+}
+__device__ __forceinline__ void st16(float* __restrict__ p, const float* v) {
+  float4* q = reinterpret_cast<float4*>(p);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+}
+// y = W x (+ b), W [16][16] row-major (nn.Linear), ascending input index
+__device__ __forceinline__ void lin16(const float* __restrict__ W, const float* __restrict__ b, const float* x, float* y) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    float a = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) a += W[i * 16 + j] * x[j];
+    y[i] = b ? a + b[i] : a;
+  }
+}
+// y (+)= W^T g
+__device__ __forceinline__ void lin16t(const float* __restrict__ W, const float* g, float* y, bool acc) {
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    float a = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a += W[i * 16 + j] * g[i];
+    y[j] = acc ? y[j] + a : a;
+  }
+}
+// evaluation-mode BatchNorm1d: out = (x - mean) / sqrt(var + 1e-5) * w + b; xh = the normalised input
+__device__ __forceinline__ void bn16(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ rm,
+                                     const float* __restrict__ rv, const float* x, float* xh, float* out) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    xh[i] = (x[i] - rm[i]) / sqrtf(rv[i] + 1e-5f);
+    out[i] = xh[i] * w[i] + b[i];
+  }
+}
+// gradient through it: g_in = g_out * w / sqrt(var + 1e-5)
+__device__ __forceinline__ void bn16_bwd(const float* __restrict__ w, const float* __restrict__ rv, const float* g, float* gi) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gi[i] = g[i] * w[i] / sqrtf(rv[i] + 1e-5f);
+}
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// ---- hoist -------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_hoist(GtW W, const float* __restrict__ edge_attr,
+                                                       const float* __restrict__ pe, int64_t N, int64_t E,
+                                                       float* __restrict__ hoist) {
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid < E) {
+    const float a = edge_attr[gid];
+    float e0[16], e1[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) e0[i] = W.p[P_EDGE_EMB][i] * a;
+    lin16(W.p[P0_WE_W], W.p[P0_WE_B], e0, e1);
+    st16(hoist + gid * HOIST_E, e0);
+    st16(hoist + gid * HOIST_E + 16, e1);
+  } else if (gid < E + N) {
+    const int64_t n = gid - E;
+    float p[16], q[16];
+    ld16(pe + n * 16, p);
+    lin16(W.p[P_PE_EMB], nullptr, p, q);
+    st16(hoist + E * HOIST_E + n * 16, q);
+  }
+}
+
+// ---- node pass A: x0, Q1, K1, V1 * sigmoid(G1) -------------------------------------------------------------------------------
+template <bool BWD>
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeA(GtW W, const float* __restrict__ obs, const float* __restrict__ pe,
+                                                       const float* __restrict__ P, int64_t MN, int64_t N,
+                                                       float* __restrict__ nrec) {
+  constexpr int NS = (BWD ? NB_SLOTS : NF_SLOTS) * 16;
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid >= MN) return;
+  const int64_t n = gid % N;
+  float o[16], x0[16], p[16], t[16], g[16];
+  ld16(obs + gid * 16, o);
+  ld16(P + n * 16, p);
+  lin16(W.p[P_NODE_EMB], nullptr, o, x0);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) x0[i] = x0[i] + p[i];
+  float* r = nrec + gid * NS;
+  lin16(W.p[P0_WQ], nullptr, x0, t);
+  st16(r + NQ1 * 16, t);
+  lin16(W.p[P0_WK], nullptr, x0, t);
+  st16(r + NK1 * 16, t);
+  st16(r + NX0 * 16, x0);
+  lin16(W.p[P0_WV], nullptr, x0, t);
+  lin16(W.p[P0_NG_W], W.p[P0_NG_B], x0, g);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) g[i] = sigmoidf_(g[i]);
+  if (BWD) {
+    st16(r + NV1 * 16, t);
+    st16(r + NSG * 16, g);
+    st16(r + NOBS * 16, o);
+    ld16(pe + n * 16, p);
+    st16(r + NPE * 16, p);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) t[i] = t[i] * g[i];
+  st16(r + NVG1 * 16, t);
+}
+
+// attention score of in-edge (u -> v) for head h: sum_{d in h} Q_v[d] K_u[d] / 2
+__device__ __forceinline__ void scores4(const float* q, const float* __restrict__ ku, float* s) {
+  float k[16];
+  ld16(ku, k);
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    float a = 0.0f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) a += q[4 * h + d] * k[4 * h + d];
+    s[h] = a / 2.0f;
+  }
+}
+
+// ---- node pass B: segment softmax + aggregation, WO, BN1, FFN, BN2 -> x1; Q2, K2 ------------------------------------------------
+template <bool BWD>
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeB(GtW W, const int32_t* __restrict__ in_ptr,
+                                                       const int32_t* __restrict__ in_src, const int32_t* __restrict__ in_eid,
+                                                       int64_t MN, int64_t N, int64_t E, float* __restrict__ nrec,
+                                                       float* __restrict__ alpha) {
+  constexpr int NS = (BWD ? NB_SLOTS : NF_SLOTS) * 16;
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid >= MN) return;
+  const int64_t m = gid / N, v = gid - m * N;
+  float* r = nrec + gid * NS;
+  const float* base = nrec + m * N * NS;
+  float q[16], s[4], mx[4], den[4], agg[16];
+  ld16(r + NQ1 * 16, q);
+  const int k0 = in_ptr[v], k1 = in_ptr[v + 1];
+#pragma unroll
+  for (int h = 0; h < 4; ++h) { mx[h] = -INFINITY; den[h] = 0.0f; }
+  for (int k = k0; k < k1; ++k) {
+    scores4(q, base + (int64_t)in_src[k] * NS + NK1 * 16, s);
+#pragma unroll
+    for (int h = 0; h < 4; ++h) mx[h] = fmaxf(mx[h], s[h]);
+  }
+  for (int k = k0; k < k1; ++k) {
+    scores4(q, base + (int64_t)in_src[k] * NS + NK1 * 16, s);
+#pragma unroll
+    for (int h = 0; h < 4; ++h) den[h] += expf(s[h] - mx[h]);
+  }
+#pragma unroll
+  for (int h = 0; h < 4; ++h) den[h] = den[h] + 1e-16f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) agg[i] = 0.0f;
+  for (int k = k0; k < k1; ++k) {
+    const int64_t u = in_src[k];
+    scores4(q, base + u * NS + NK1 * 16, s);
+    float vg[16];
+    ld16(base + u * NS + NVG1 * 16, vg);
+    float a[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) a[h] = expf(s[h] - mx[h]) / den[h];
+    if (BWD) *reinterpret_cast<float4*>(alpha + (m * E + in_eid[k]) * 4) = make_float4(a[0], a[1], a[2], a[3]);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) agg[i] += a[i >> 2] * vg[i];
+  }
+  float x0[16], t[16], th[16], y[16], hh[16], rr[16], f[16], sh[16], x1[16];
+  ld16(r + NX0 * 16, x0);
+  lin16(W.p[P0_WO_W], W.p[P0_WO_B], agg, t);           // WO(out) + x_ (gt_conv.py:183)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) t[i] = t[i] + x0[i];
+  bn16(W.p[P0_N1_W], W.p[P0_N1_B], W.p[R0_N1_M], W.p[R0_N1_V], t, th, y);
+  lin16(W.p[P0_F0_W], W.p[P0_F0_B], y, hh);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) rr[i] = fmaxf(hh[i], 0.0f);
+  lin16(W.p[P0_F3_W], W.p[P0_F3_B], rr, f);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) f[i] = y[i] + f[i];    // norm2(ffn_in + out) (gt_conv.py:192)
+  bn16(W.p[P0_N2_W], W.p[P0_N2_B], W.p[R0_N2_M], W.p[R0_N2_V], f, sh, x1);
+  lin16(W.p[P1_WQ], nullptr, x1, t);
+  st16(r + NQ2 * 16, t);
+  lin16(W.p[P1_WK], nullptr, x1, t);
+  st16(r + NK2 * 16, t);
+  if (BWD) {
+    st16(r + NAGG * 16, agg);
+    st16(r + NTH1 * 16, th);
+    st16(r + NY * 16, y);
+    st16(r + NH * 16, hh);
+    st16(r + NR * 16, rr);
+    st16(r + NSH2 * 16, sh);
+    st16(r + NX1 * 16, x1);
+  }
+}
+
+// ---- one edge layer -------------------------------------------------------------------------------------------------------------
+// forward: ein = e, Ee = WE e + b; qv / ku = Q of the target, K of the source -> eout; rec (nullable) = the layer's record
+template <int L>
+__device__ __forceinline__ void edge_layer_fwd(const GtW& W, const float* ein, const float* Ee, const float* qv,
+                                               const float* ku, float* eout, float* rec) {
+  constexpr int P = edge_par(L), R = edge_run(L);
+  float q[16], eij[16], t[16], th[16], z[16], h[16], r[16], s[16], sh[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    q[i] = (qv[i] * ku[i]) / 2.0f;                     // (Q_i * K_j) / sqrt(d_k) (gt_conv.py:214)
+    eij[i] = Ee[i] * q[i];                             // E * qijk (:218)
+  }
+  lin16(W.p[P + 2], W.p[P + 3], eij, t);               // WOe(out_eij) + edge_attr_ (:205)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) t[i] = t[i] + ein[i];
+  bn16(W.p[P + 4], W.p[P + 5], W.p[R + 0], W.p[R + 1], t, th, z);
+  lin16(W.p[P + 6], W.p[P + 7], z, h);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) r[i] = fmaxf(h[i], 0.0f);
+  lin16(W.p[P + 8], W.p[P + 9], r, s);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) s[i] = z[i] + s[i];
+  bn16(W.p[P + 10], W.p[P + 11], W.p[R + 2], W.p[R + 3], s, sh, eout);
+  if (rec) {
+    st16(rec + EIN * 16, ein);
+    st16(rec + EE * 16, Ee);
+    st16(rec + EQ * 16, q);
+    st16(rec + EIJ * 16, eij);
+    st16(rec + ETH * 16, th);
+    st16(rec + EZ * 16, z);
+    st16(rec + EH * 16, h);
+    st16(rec + ER * 16, r);
+    st16(rec + ESH * 16, sh);
+    st16(rec + EOUT * 16, eout);
+  }
+}
+
+// backward of the layer from its record: geout -> gin (gradient of the layer's input edge features); gq -> the record
+template <int L>
+__device__ __forceinline__ void edge_layer_bwd(const GtW& W, float* rec, const float* geout, float* gin) {
+  constexpr int P = edge_par(L), R = edge_run(L);
+  float gs[16], gh[16], gz[16], gt[16], geij[16], v[16], w[16];
+  bn16_bwd(W.p[P + 10], W.p[R + 3], geout, gs);
+  lin16t(W.p[P + 8], gs, gh, false);
+  ld16(rec + EH * 16, v);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gh[i] = v[i] > 0.0f ? gh[i] : 0.0f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gz[i] = gs[i];
+  lin16t(W.p[P + 6], gh, gz, true);
+  bn16_bwd(W.p[P + 4], W.p[R + 1], gz, gt);
+  lin16t(W.p[P + 2], gt, geij, false);
+  ld16(rec + EQ * 16, v);
+  ld16(rec + EE * 16, w);
+  float gE[16], gq[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    gE[i] = geij[i] * v[i];
+    gq[i] = geij[i] * w[i];
+    gin[i] = gt[i];
+  }
+  lin16t(W.p[P + 0], gE, gin, true);
+  st16(rec + EGOUT * 16, geout);
+  st16(rec + EGS * 16, gs);
+  st16(rec + EGH * 16, gh);
+  st16(rec + EGZ * 16, gz);
+  st16(rec + EGT * 16, gt);
+  st16(rec + EGE * 16, gE);
+  st16(rec + EGQ * 16, gq);
+  st16(rec + EGIN * 16, gin);
+}
+
+// ---- edge pass C: both edge layers and edge_linear (forward: logits; backward: the records and the edge chain's gradients) ----
+template <bool BWD>
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_edge(GtW W, const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
+                                                      const float* __restrict__ edge_attr, const float* __restrict__ hoist,
+                                                      const float* __restrict__ nrec, int64_t M, int64_t N, int64_t E,
+                                                      float* __restrict__ logits, const float* __restrict__ grad_logits,
+                                                      float* __restrict__ erec) {
+  constexpr int NS = (BWD ? NB_SLOTS : NF_SLOTS) * 16;
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid >= M * E) return;
+  const int64_t m = gid / E, e = gid - m * E;
+  const float* nu = nrec + (m * N + src[e]) * NS;
+  const float* nv = nrec + (m * N + dst[e]) * NS;
+  float* rec = BWD ? erec + gid * (E_SLOTS * 16) : nullptr;
+  float e0[16], Ee[16], qv[16], ku[16], e1[16], e2[16];
+  ld16(hoist + e * HOIST_E, e0);
+  ld16(hoist + e * HOIST_E + 16, Ee);
+  ld16(nv + NQ1 * 16, qv);
+  ld16(nu + NK1 * 16, ku);
+  edge_layer_fwd<0>(W, e0, Ee, qv, ku, e1, rec);
+  lin16(W.p[P1_WE_W], W.p[P1_WE_B], e1, Ee);
+  ld16(nv + NQ2 * 16, qv);
+  ld16(nu + NK2 * 16, ku);
+  edge_layer_fwd<1>(W, e1, Ee, qv, ku, e2, BWD ? rec + E_LAYER_SLOTS * 16 : nullptr);
+  if (!BWD) {
+    float a = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) a += W.p[P_LIN_W][j] * e2[j];
+    logits[gid] = a + W.p[P_LIN_B][0];
+    return;
+  }
+  const float g = grad_logits[gid];
+  float v[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) v[i] = 0.0f;
+  v[0] = g;
+  st16(rec + E_GLOGIT * 16, v);
+  v[0] = edge_attr[e];
+  st16(rec + E_ATTR * 16, v);
+  float ge[16], gin[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) ge[i] = g * W.p[P_LIN_W][i];
+  edge_layer_bwd<1>(W, rec + E_LAYER_SLOTS * 16, ge, gin);
+  edge_layer_bwd<0>(W, rec, gin, ge);
+}
+
+// ---- node pass D: gradients of Q2 / K2 (walks of the in- and out-edges), node layer backwards, attention scores' gradients ------
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeD(GtW W, const int32_t* __restrict__ in_ptr,
+                                                       const int32_t* __restrict__ in_src, const int32_t* __restrict__ in_eid,
+                                                       const int32_t* __restrict__ out_ptr,
+                                                       const int32_t* __restrict__ out_dst,
+                                                       const int32_t* __restrict__ out_eid, int64_t MN, int64_t N, int64_t E,
+                                                       float* __restrict__ nrec, const float* __restrict__ erec,
+                                                       const float* __restrict__ alpha, float* __restrict__ gscore) {
+  constexpr int NS = NB_SLOTS * 16, ES = E_SLOTS * 16;
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid >= MN) return;
+  const int64_t m = gid / N, n = gid - m * N;
+  float* r = nrec + gid * NS;
+  const float* base = nrec + m * N * NS;
+  const float* eb = erec + m * E * ES;
+  float gQ[16], gK[16], a[16], b[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { gQ[i] = 0.0f; gK[i] = 0.0f; }
+  for (int k = in_ptr[n]; k < in_ptr[n + 1]; ++k) {        // n is the target: d q / d Q_v = K_u / 2
+    ld16(eb + (int64_t)in_eid[k] * ES + (E_LAYER_SLOTS + EGQ) * 16, a);
+    ld16(base + (int64_t)in_src[k] * NS + NK2 * 16, b);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gQ[i] += a[i] * b[i] / 2.0f;
+  }
+  for (int k = out_ptr[n]; k < out_ptr[n + 1]; ++k) {      // n is the source: d q / d K_u = Q_v / 2
+    ld16(eb + (int64_t)out_eid[k] * ES + (E_LAYER_SLOTS + EGQ) * 16, a);
+    ld16(base + (int64_t)out_dst[k] * NS + NQ2 * 16, b);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gK[i] += a[i] * b[i] / 2.0f;
+  }
+  float gx1[16], gs[16], gh[16], gy[16], gt[16], gagg[16];
+  lin16t(W.p[P1_WQ], gQ, gx1, false);
+  lin16t(W.p[P1_WK], gK, gx1, true);
+  bn16_bwd(W.p[P0_N2_W], W.p[R0_N2_V], gx1, gs);
+  lin16t(W.p[P0_F3_W], gs, gh, false);
+  ld16(r + NH * 16, a);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gh[i] = a[i] > 0.0f ? gh[i] : 0.0f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gy[i] = gs[i];
+  lin16t(W.p[P0_F0_W], gh, gy, true);
+  bn16_bwd(W.p[P0_N1_W], W.p[R0_N1_V], gy, gt);
+  lin16t(W.p[P0_WO_W], gt, gagg, false);
+  st16(r + NGQ2 * 16, gQ);
+  st16(r + NGK2 * 16, gK);
+  st16(r + NGX1 * 16, gx1);
+  st16(r + NGS * 16, gs);
+  st16(r + NGH * 16, gh);
+  st16(r + NGY * 16, gy);
+  st16(r + NGT * 16, gt);
+  st16(r + NGAGG * 16, gagg);
+  // softmax backward per head: g_score = alpha * (g_alpha - sum_k alpha_k g_alpha_k), g_alpha = <g_agg, V_u sigma(G_u)>_head
+  float dot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int k = in_ptr[n]; k < in_ptr[n + 1]; ++k) {
+      const int64_t eid = in_eid[k];
+      ld16(base + (int64_t)in_src[k] * NS + NVG1 * 16, b);
+      const float4 al = *reinterpret_cast<const float4*>(alpha + (m * E + eid) * 4);
+      const float av[4] = {al.x, al.y, al.z, al.w};
+      float ga[4];
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        float s = 0.0f;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) s += gagg[4 * h + d] * b[4 * h + d];
+        ga[h] = s;
+      }
+      if (pass == 0) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) dot[h] += av[h] * ga[h];
+      } else {
+        *reinterpret_cast<float4*>(gscore + (m * E + eid) * 4) =
+            make_float4(av[0] * (ga[0] - dot[0]), av[1] * (ga[1] - dot[1]), av[2] * (ga[2] - dot[2]), av[3] * (ga[3] - dot[3]));
+      }
+    }
+  }
+}
+
+// ---- node pass E: gradients of Q1 / K1 / V1 / G1 and x0 ------------------------------------------------------------------------------
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeE(GtW W, const int32_t* __restrict__ in_ptr,
+                                                       const int32_t* __restrict__ in_src, const int32_t* __restrict__ in_eid,
+                                                       const int32_t* __restrict__ out_ptr,
+                                                       const int32_t* __restrict__ out_dst,
+                                                       const int32_t* __restrict__ out_eid, int64_t MN, int64_t N, int64_t E,
+                                                       float* __restrict__ nrec, const float* __restrict__ erec,
+                                                       const float* __restrict__ alpha, const float* __restrict__ gscore) {
+  constexpr int NS = NB_SLOTS * 16, ES = E_SLOTS * 16;
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid >= MN) return;
+  const int64_t m = gid / N, n = gid - m * N;
+  float* r = nrec + gid * NS;
+  const float* base = nrec + m * N * NS;
+  const float* eb = erec + m * E * ES;
+  float gQ[16], gK[16], gVG[16], a[16], b[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { gQ[i] = 0.0f; gK[i] = 0.0f; gVG[i] = 0.0f; }
+  for (int k = in_ptr[n]; k < in_ptr[n + 1]; ++k) {
+    const int64_t eid = in_eid[k];
+    ld16(eb + eid * ES + EGQ * 16, a);
+    const float4 gsc = *reinterpret_cast<const float4*>(gscore + (m * E + eid) * 4);
+    const float gv[4] = {gsc.x, gsc.y, gsc.z, gsc.w};
+    ld16(base + (int64_t)in_src[k] * NS + NK1 * 16, b);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gQ[i] += (a[i] + gv[i >> 2]) * b[i] / 2.0f;
+  }
+  for (int k = out_ptr[n]; k < out_ptr[n + 1]; ++k) {
+    const int64_t eid = out_eid[k], v = out_dst[k];
+    ld16(eb + eid * ES + EGQ * 16, a);
+    const float4 gsc = *reinterpret_cast<const float4*>(gscore + (m * E + eid) * 4);
+    const float gv[4] = {gsc.x, gsc.y, gsc.z, gsc.w};
+    ld16(base + v * NS + NQ1 * 16, b);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gK[i] += (a[i] + gv[i >> 2]) * b[i] / 2.0f;
+    const float4 al = *reinterpret_cast<const float4*>(alpha + (m * E + eid) * 4);
+    const float av[4] = {al.x, al.y, al.z, al.w};
+    ld16(base + v * NS + NGAGG * 16, b);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gVG[i] += av[i >> 2] * b[i];
+  }
+  float V[16], sg[16], gV[16], gG[16], gx0[16];
+  ld16(r + NV1 * 16, V);
+  ld16(r + NSG * 16, sg);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    gV[i] = gVG[i] * sg[i];
+    gG[i] = gVG[i] * V[i] * (sg[i] * (1.0f - sg[i]));
+  }
+  ld16(r + NGT * 16, gx0);                 // the residual of WO(out) + x_
+  lin16t(W.p[P0_WQ], gQ, gx0, true);
+  lin16t(W.p[P0_WK], gK, gx0, true);
+  lin16t(W.p[P0_WV], gV, gx0, true);
+  lin16t(W.p[P0_NG_W], gG, gx0, true);
+  st16(r + NGQ1 * 16, gQ);
+  st16(r + NGK1 * 16, gK);
+  st16(r + NGV * 16, gV);
+  st16(r + NGG * 16, gG);
+  st16(r + NGX0 * 16, gx0);
+}
+
+// ---- weight gradients: sum over items of g[i] * a[j] (outer), g[i] (bias) or g[i] * a[i] (BatchNorm weight) ------------------------
+enum { T_OUTER = 0, T_BIAS, T_DIAG };
+struct GtTerm {
+  int16_t param, edge, g, a, kind, rows, cols;
+  int32_t off;    // offset of the parameter's outputs in the partial-sum rows
+};
+#define GT_NTERMS GT_NP_
+struct GtTerms {
+  GtTerm t[GT_NTERMS];
+};
+struct GtG {
+  float* p[GT_NP_];
+};
+
+static GtTerms make_terms(int* nout) {
+  GtTerms T{};
+  int k = 0, off = 0;
+  auto add = [&](int param, int edge, int g, int a, int kind, int rows, int cols) {
+    T.t[k] = GtTerm{(int16_t)param, (int16_t)edge, (int16_t)g, (int16_t)a, (int16_t)kind, (int16_t)rows, (int16_t)cols, off};
+    off += rows * cols;
+    ++k;
+  };
+  add(P_NODE_EMB, 0, NGX0, NOBS, T_OUTER, 16, 16);
+  add(P_PE_EMB, 0, NGX0, NPE, T_OUTER, 16, 16);
+  add(P_EDGE_EMB, 1, EGIN, E_ATTR, T_OUTER, 16, 1);
+  add(P0_WQ, 0, NGQ1, NX0, T_OUTER, 16, 16);
+  add(P0_WK, 0, NGK1, NX0, T_OUTER, 16, 16);
+  add(P0_WV, 0, NGV, NX0, T_OUTER, 16, 16);
+  add(P0_NG_W, 0, NGG, NX0, T_OUTER, 16, 16);
+  add(P0_NG_B, 0, NGG, 0, T_BIAS, 16, 1);
+  add(P0_WO_W, 0, NGT, NAGG, T_OUTER, 16, 16);
+  add(P0_WO_B, 0, NGT, 0, T_BIAS, 16, 1);
+  add(P0_N1_W, 0, NGY, NTH1, T_DIAG, 16, 1);
+  add(P0_N1_B, 0, NGY, 0, T_BIAS, 16, 1);
+  add(P0_F0_W, 0, NGH, NY, T_OUTER, 16, 16);
+  add(P0_F0_B, 0, NGH, 0, T_BIAS, 16, 1);
+  add(P0_F3_W, 0, NGS, NR, T_OUTER, 16, 16);
+  add(P0_F3_B, 0, NGS, 0, T_BIAS, 16, 1);
+  add(P0_N2_W, 0, NGX1, NSH2, T_DIAG, 16, 1);
+  add(P0_N2_B, 0, NGX1, 0, T_BIAS, 16, 1);
+  for (int L = 0; L < 2; ++L) {
+    const int P = edge_par(L), o = L * E_LAYER_SLOTS;
+    add(P + 0, 1, o + EGE, o + EIN, T_OUTER, 16, 16);
+    add(P + 1, 1, o + EGE, 0, T_BIAS, 16, 1);
+    add(P + 2, 1, o + EGT, o + EIJ, T_OUTER, 16, 16);
+    add(P + 3, 1, o + EGT, 0, T_BIAS, 16, 1);
+    add(P + 4, 1, o + EGZ, o + ETH, T_DIAG, 16, 1);
+    add(P + 5, 1, o + EGZ, 0, T_BIAS, 16, 1);
+    add(P + 6, 1, o + EGH, o + EZ, T_OUTER, 16, 16);
+    add(P + 7, 1, o + EGH, 0, T_BIAS, 16, 1);
+    add(P + 8, 1, o + EGS, o + ER, T_OUTER, 16, 16);
+    add(P + 9, 1, o + EGS, 0, T_BIAS, 16, 1);
+    add(P + 10, 1, o + EGOUT, o + ESH, T_DIAG, 16, 1);
+    add(P + 11, 1, o + EGOUT, 0, T_BIAS, 16, 1);
+    if (L == 0) {
+      add(P1_WQ, 0, NGQ2, NX1, T_OUTER, 16, 16);
+      add(P1_WK, 0, NGK2, NX1, T_OUTER, 16, 16);
+    }
+  }
+  add(P_LIN_W, 1, E_GLOGIT, E_LAYER_SLOTS + EOUT, T_OUTER, 1, 16);
+  add(P_LIN_B, 1, E_GLOGIT, 0, T_BIAS, 1, 1);
+  *nout = off;
+  return T;
+}
+
+// stage 1: block (term, chunk), one thread per output, items of the chunk in ascending order
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_wgrad1(GtTerms T, const float* __restrict__ nrec,
+                                                        const float* __restrict__ erec, int64_t n_node, int64_t n_edge,
+                                                        int nout, float* __restrict__ partial) {
+  const GtTerm& t = T.t[blockIdx.x];
+  const int64_t items = t.edge ? n_edge : n_node;
+  const int64_t i0 = (int64_t)blockIdx.y * GT_CHUNK;
+  const int o = threadIdx.x;
+  if (i0 >= items || o >= t.rows * t.cols) return;
+  const int64_t stride = t.edge ? E_SLOTS * 16 : NB_SLOTS * 16;
+  const float* S = t.edge ? erec : nrec;
+  const int gi = t.g * 16 + (t.kind == T_OUTER ? o / t.cols : o);
+  const int ai = t.a * 16 + (t.kind == T_OUTER ? o % t.cols : o);
+  const int64_t i1 = i0 + GT_CHUNK < items ? i0 + GT_CHUNK : items;
+  float acc = 0.0f;
+  if (t.kind == T_BIAS) {
+    for (int64_t it = i0; it < i1; ++it) acc += S[it * stride + gi];
+  } else {
+    for (int64_t it = i0; it < i1; ++it) acc += S[it * stride + gi] * S[it * stride + ai];
+  }
+  partial[(int64_t)blockIdx.y * nout + t.off + o] = acc;
+}
+
+// stage 2: the chunk partials in chunk order, added to the caller's gradient
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_wgrad2(GtTerms T, GtG G, int64_t n_node, int64_t n_edge, int nout,
+                                                        const float* __restrict__ partial) {
+  const GtTerm& t = T.t[blockIdx.x];
+  const int o = threadIdx.x;
+  if (o >= t.rows * t.cols) return;
+  const int64_t chunks = ((t.edge ? n_edge : n_node) + GT_CHUNK - 1) / GT_CHUNK;
+  float acc = 0.0f;
+  for (int64_t c = 0; c < chunks; ++c) acc += partial[c * nout + t.off + o];
+  G.p[t.param][o] += acc;
+}
+
+// ---- entry points --------------------------------------------------------------------------------------------------------------------
+static int gt_nout() {
+  static int n = -1;
+  if (n < 0) make_terms(&n);
+  return n;
+}
+static int64_t hoist_floats(const tarl_plan* plan) { return plan->E * HOIST_E + plan->N * 16; }
+
+extern "C" int64_t tarl_policy_gt_fwd_scratch_floats(const tarl_plan* plan, int64_t M) {
+  if (!plan || M < 0) return -1;
+  return hoist_floats(plan) + M * plan->N * NF_SLOTS * 16;
+}
+
+extern "C" int64_t tarl_policy_gt_bwd_scratch_floats(const tarl_plan* plan, int64_t M) {
+  if (!plan || M < 0) return -1;
+  const int64_t chunks = ceil_div(M * (plan->E > plan->N ? plan->E : plan->N), GT_CHUNK);
+  return hoist_floats(plan) + M * plan->N * NB_SLOTS * 16 + M * plan->E * (E_SLOTS * 16 + 8) + chunks * gt_nout();
+}
+
+static int gt_check(const tarl_plan* plan, const float* obs16, int64_t M, const float* edge_attr, const float* pe,
+                    const float* const* w, GtW* W) {
+  TARL_REQUIRE(plan && obs16 && edge_attr && pe && w, "null argument");
+  TARL_REQUIRE(M >= 1, "bad sample count");
+  TARL_REQUIRE(((uintptr_t)obs16) % 16 == 0 && ((uintptr_t)pe) % 16 == 0, "obs16 / pe must be 16-byte aligned");
+  for (int i = 0; i < GT_NW_; ++i) {
+    TARL_REQUIRE(w[i] != nullptr, "parameter pointer is null");
+    W->p[i] = w[i];
+  }
+  return TARL_OK;
+}
+
+static int launch_hoist(const tarl_plan* plan, const GtW& W, const float* edge_attr, const float* pe, float* hoist,
+                        hipStream_t s) {
+  const int64_t n = plan->E + plan->N;
+  if (n == 0) return TARL_OK;
+  hipLaunchKernelGGL(k_gt_hoist, dim3((unsigned)ceil_div(n, GT_BLOCK)), dim3(GT_BLOCK), 0, s, W, edge_attr, pe, plan->N,
+                     plan->E, hoist);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+// node passes A, B and the edge pass of the forward (hoist already in scratch)
+static int launch_fwd(const tarl_plan* plan, const GtW& W, const float* obs16, const float* pe, int64_t M,
+                      const float* edge_attr, float* scratch, float* logits, hipStream_t s) {
+  const int64_t N = plan->N, E = plan->E, MN = M * N;
+  const float* hoist = scratch;
+  float* nrec = scratch + hoist_floats(plan);
+  const unsigned gn = (unsigned)ceil_div(MN, GT_BLOCK);
+  hipLaunchKernelGGL(k_gt_nodeA<false>, dim3(gn), dim3(GT_BLOCK), 0, s, W, obs16, pe, hoist + E * HOIST_E, MN, N, nrec);
+  TARL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_gt_nodeB<false>, dim3(gn), dim3(GT_BLOCK), 0, s, W, plan->in_ptr, plan->in_src, plan->in_eid, MN, N,
+                     E, nrec, (float*)nullptr);
+  TARL_LAUNCH_CHECK();
+  if (E == 0) return TARL_OK;
+  hipLaunchKernelGGL(k_gt_edge<false>, dim3((unsigned)ceil_div(M * E, GT_BLOCK)), dim3(GT_BLOCK), 0, s, W, plan->src,
+                     plan->dst, edge_attr, hoist, (const float*)nrec, M, N, E, logits, (const float*)nullptr,
+                     (float*)nullptr);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+extern "C" int tarl_policy_gt_fwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* edge_attr,
+                                  const float* pe, const float* const* w, float* scratch, int64_t scratch_floats,
+                                  float* logits, tarl_stream stream) {
+  GtW W;
+  int rc = gt_check(plan, obs16, M, edge_attr, pe, w, &W);
+  if (rc) return rc;
+  TARL_REQUIRE(logits && scratch, "null logits / scratch");
+  TARL_REQUIRE(((uintptr_t)scratch) % 16 == 0, "scratch must be 16-byte aligned");
+  TARL_REQUIRE(scratch_floats >= tarl_policy_gt_fwd_scratch_floats(plan, M), "scratch smaller than tarl_policy_gt_fwd_scratch_floats");
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)stream;
+  rc = launch_hoist(plan, W, edge_attr, pe, scratch, s);
+  if (rc) return rc;
+  return launch_fwd(plan, W, obs16, pe, M, edge_attr, scratch, logits, s);
+}
+
+extern "C" int tarl_policy_gt_bwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* edge_attr,
+                                  const float* pe, const float* const* w, const float* grad_logits, float* scratch,
+                                  int64_t scratch_floats, float* const* grads, tarl_stream stream) {
+  GtW W;
+  int rc = gt_check(plan, obs16, M, edge_attr, pe, w, &W);
+  if (rc) return rc;
+  TARL_REQUIRE(grad_logits && scratch && grads, "null grad_logits / scratch / grads");
+  TARL_REQUIRE(((uintptr_t)scratch) % 16 == 0, "scratch must be 16-byte aligned");
+  TARL_REQUIRE(scratch_floats >= tarl_policy_gt_bwd_scratch_floats(plan, M), "scratch smaller than tarl_policy_gt_bwd_scratch_floats");
+  GtG G;
+  for (int i = 0; i < GT_NP_; ++i) {
+    TARL_REQUIRE(grads[i] != nullptr, "gradient pointer is null");
+    G.p[i] = grads[i];
+  }
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t N = plan->N, E = plan->E, MN = M * N, ME = M * E;
+  float* hoist = scratch;
+  float* nrec = hoist + hoist_floats(plan);
+  float* erec = nrec + MN * NB_SLOTS * 16;
+  float* alpha = erec + ME * E_SLOTS * 16;
+  float* gscore = alpha + ME * 4;
+  float* partial = gscore + ME * 4;
+  rc = launch_hoist(plan, W, edge_attr, pe, hoist, s);
+  if (rc) return rc;
+  const unsigned gn = (unsigned)ceil_div(MN, GT_BLOCK);
+  hipLaunchKernelGGL(k_gt_nodeA<true>, dim3(gn), dim3(GT_BLOCK), 0, s, W, obs16, pe, (const float*)(hoist + E * HOIST_E), MN,
+                     N, nrec);
+  TARL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_gt_nodeB<true>, dim3(gn), dim3(GT_BLOCK), 0, s, W, plan->in_ptr, plan->in_src, plan->in_eid, MN, N,
+                     E, nrec, alpha);
+  TARL_LAUNCH_CHECK();
+  if (E > 0) {
+    hipLaunchKernelGGL(k_gt_edge<true>, dim3((unsigned)ceil_div(ME, GT_BLOCK)), dim3(GT_BLOCK), 0, s, W, plan->src,
+                       plan->dst, edge_attr, (const float*)hoist, (const float*)nrec, M, N, E, (float*)nullptr, grad_logits,
+                       erec);
+    TARL_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_gt_nodeD, dim3(gn), dim3(GT_BLOCK), 0, s, W, plan->in_ptr, plan->in_src, plan->in_eid, plan->out_ptr,
+                     plan->out_dst, plan->out_eid, MN, N, E, nrec, (const float*)erec, (const float*)alpha, gscore);
+  TARL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_gt_nodeE, dim3(gn), dim3(GT_BLOCK), 0, s, W, plan->in_ptr, plan->in_src, plan->in_eid, plan->out_ptr,
+                     plan->out_dst, plan->out_eid, MN, N, E, nrec, (const float*)erec, (const float*)alpha,
+                     (const float*)gscore);
+  TARL_LAUNCH_CHECK();
+  int nout = 0;
+  const GtTerms T = make_terms(&nout);
+  const int64_t chunks = ceil_div(MN > ME ? MN : ME, GT_CHUNK);
+  TARL_REQUIRE(chunks < 65536, "too many gradient chunks for one grid dimension");
+  hipLaunchKernelGGL(k_gt_wgrad1, dim3(GT_NTERMS, (unsigned)chunks), dim3(GT_BLOCK), 0, s, T, (const float*)nrec,
+                     (const float*)erec, MN, ME, nout, partial);
+  TARL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_gt_wgrad2, dim3(GT_NTERMS), dim3(GT_BLOCK), 0, s, T, G, MN, ME, nout, (const float*)partial);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+// the count bytes of the rollout buffers (NUMBER_OF_AGENT after the frame, env-minor [N][B]) from the packed state
+__global__ __launch_bounds__(GT_BLOCK) void k_gt_counts8(const uint2* __restrict__ hdp, int64_t n, uint8_t* __restrict__ counts) {
+  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+  if (gid < n) counts[gid] = (uint8_t)(hdp[gid].x & HD_CNT);
+}
+
+extern "C" int tarl_fused_rollout_gt(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                     const float* times_host, float prev_time, const float* x, int64_t x_bstride,
+                                     int64_t ldx, float* agent_features, int64_t A, int64_t a_bstride,
+                                     const float* edge_attr, const float* log_edge_attr, float log_eps, int use_cong,
+                                     const float* pe, const float* const* w, float temperature, uint64_t policy_seed,
+                                     uint64_t policy_counter0, uint64_t seed, uint64_t counter0,
+                                     const int64_t* keep_ptr_host, const int32_t* keep_env, const int32_t* keep_slot,
+                                     float* obs_keep, float* obs_scratch, float* gt_scratch, int64_t gt_scratch_floats,
+                                     float* logits_scratch, void* dist_scratch, int32_t* ins_scratch, uint8_t* choice8,
+                                     float* log_prob, float* reward, uint8_t* counts, tarl_stream stream) {
+  int rc = tarl_check_fused_core(plan, f, B, Nmax);
+  if (rc) return rc;
+  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
+  TARL_REQUIRE(x && agent_features && obs_scratch && gt_scratch && logits_scratch && dist_scratch && ins_scratch,
+               "state / observation / logits / sampler / insert scratch missing");
+  TARL_REQUIRE(!keep_ptr_host || (keep_env && keep_slot && obs_keep), "keep list without its arrays");
+  TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
+  TARL_REQUIRE(((uintptr_t)obs_scratch) % 16 == 0 && ((uintptr_t)gt_scratch) % 16 == 0, "scratch must be 16-byte aligned");
+  TARL_REQUIRE(gt_scratch_floats >= tarl_policy_gt_fwd_scratch_floats(plan, B),
+               "gt_scratch smaller than tarl_policy_gt_fwd_scratch_floats(plan, B)");
+  GtW W;
+  rc = gt_check(plan, obs_scratch, B, edge_attr, pe, w, &W);
+  if (rc) return rc;
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t N = plan->N, NB = N * B;
+  const FusedBufs fb = tarl_to_bufs(f);
+  rc = launch_hoist(plan, W, edge_attr, pe, gt_scratch, s);     // the state-independent terms, once per call
+  if (rc) return rc;
+  for (int64_t t = 0; t < T; ++t) {
+    if (keep_ptr_host && keep_ptr_host[t + 1] > keep_ptr_host[t]) {
+      const int64_t lo = keep_ptr_host[t], n = keep_ptr_host[t + 1] - lo;
+      rc = tarl_fused_obs16_rows(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, keep_env + lo,
+                                 keep_slot + lo, n, obs_keep, stream);
+      if (rc) return rc;
+    }
+    rc = tarl_fused_obs16(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, obs_scratch, stream);
+    if (rc) return rc;
+    rc = launch_fwd(plan, W, obs_scratch, pe, B, edge_attr, gt_scratch, logits_scratch, s);
+    if (rc) return rc;
+    rc = tarl_graphdist_rollout_at(plan, logits_scratch, B, temperature, nullptr, policy_seed, policy_counter0 + (uint64_t)t,
+                                   dist_scratch, nullptr, choice8 ? choice8 + t * NB : nullptr, f->sel8,
+                                   log_prob ? log_prob + t * B : nullptr, f->env_base, stream);
+    if (rc) return rc;
+    rc = tarl_fused_frame(plan, f, B, Nmax, nullptr, nullptr, nullptr, nullptr, 0, 0, agent_features, A, a_bstride, edge_attr,
+                          log_edge_attr, log_eps, use_cong, times_host[t], t > 0 ? times_host[t - 1] : prev_time, nullptr,
+                          seed, counter0 + (uint64_t)t, nullptr, nullptr, nullptr, ins_scratch, nullptr, nullptr, nullptr,
+                          reward ? reward + t * B : nullptr, nullptr, stream);
+    if (rc) return rc;
+    if (counts) {
+      hipLaunchKernelGGL(k_gt_counts8, dim3((unsigned)ceil_div(NB, GT_BLOCK)), dim3(GT_BLOCK), 0, s, fb.hdp, NB,
+                         counts + t * NB);
+      TARL_LAUNCH_CHECK();
+    }
+  }
+  return TARL_OK;
+}

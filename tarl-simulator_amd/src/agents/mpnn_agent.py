@@ -77,6 +77,9 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
     # ``prior_weight`` times the shortest-path prior the reference computes and leaves commented out (:180-190):
     # -dist[dst(e), DESTINATION of the head agent of src(e)] - time_travel(dst(e)), dist = ``dist_matrix`` (state-dependent,
     # no parameters of its own; prior_weight = 1 is the reference's literal sum).
+    # "graph_transformer": the reference's GraphTransformerNet edge output (src/transformer/model.py, as MLAgents builds it),
+    # evaluation-mode BatchNorm; its ``transformer`` submodule and ``gt_pe`` buffer exist only after
+    # :meth:`use_graph_transformer`, so the other heads' state dicts do not change.
     policy_head = "embedding"
     prior_weight = 1.0
 
@@ -127,10 +130,32 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
         logits = -self.dist_matrix[head, agent_destination.to(head.device)] - time_travel
         return logits.view(rep, -1) if rep > 1 else logits.view(-1)
 
+    def use_graph_transformer(self, pe: torch.Tensor):
+        """Switch to the graph-transformer head: creates ``transformer`` (GraphTransformerNet(16, 1, 16, hidden 16, gate,
+        2 layers, 4 heads, dropout 0.1), evaluation mode) and the positional-encoding buffer ``gt_pe`` (N, 16)."""
+        from ..transformer import GraphTransformerNet
+        if tuple(pe.shape) != (self.num_nodes, 16):
+            raise ValueError(f"pe must be ({self.num_nodes}, 16)")
+        self.policy_head = "graph_transformer"
+        if getattr(self, "transformer", None) is None:
+            self.transformer = GraphTransformerNet(16, 1, 16, 16, gate=True, num_gt_layers=2, num_heads=4, dropout=0.1)
+        self.register_buffer("gt_pe", pe.detach().to(torch.float32).contiguous())
+        self.transformer.eval()
+        self.to(self.device)
+        return self
+
     def forward(self, node_features: torch.Tensor, edge_features: torch.Tensor, agent_index: torch.Tensor):
         """node_features (N,7) or (B,N,7) -> logits (E,) or (B,E)."""
         require_cuda(node_features, "node_features")
         plan = cached_plan(self.edge_index, self.num_nodes)
+        if self.policy_head == "graph_transformer":
+            from tarl_hip import ops
+            from .._compat import cached_edge_const
+            ea = edge_features if edge_features.dim() <= 2 else edge_features[0]
+            ec = cached_edge_const(ea.reshape(-1, 1), node_features.device)
+            obs16 = ops.policy_obs16(node_features, agent_index, self.agent_features.to(node_features.device))
+            logits = self.transformer.edge_logits(obs16, plan, ec, self.gt_pe)
+            return logits if node_features.dim() == 3 else logits.view(-1)
         if self.policy_head == "embedding_dijkstra":
             from tarl_hip import ops
             obs16 = ops.policy_obs16(node_features, agent_index, self.agent_features.to(node_features.device))

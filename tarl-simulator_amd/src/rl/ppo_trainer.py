@@ -94,11 +94,13 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             [l[0].weight, l[0].bias, l[2].weight, l[2].bias, l[4].weight, l[4].bias],
                             rollout_steps=frames_per_batch, num_epochs=num_epochs, sub_batch_size=sub_batch_size,
                             extra_params=dormant, seed=seed,
-                            policy=head if head in ("embedding", "embedding_dijkstra") else "edge_mlp",
+                            policy=head if head in ("embedding", "embedding_dijkstra", "graph_transformer") else "edge_mlp",
                             edge_mlp_params=[m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias],
                             policy_precision={"edge_mlp_bf16": "bf16", "edge_mlp_fp32": "fp32"}.get(head, "x3"),
                             prior_table=policy_net.dist_matrix if head == "embedding_dijkstra" else None,
-                            prior_weight=getattr(policy_net, "prior_weight", 1.0))
+                            prior_weight=getattr(policy_net, "prior_weight", 1.0),
+                            gt_params=policy_net.transformer.kernel_tensors() if head == "graph_transformer" else None,
+                            gt_pe=getattr(policy_net, "gt_pe", None))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)

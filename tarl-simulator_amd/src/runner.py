@@ -82,6 +82,14 @@ class Runner:
             self.policy_net = MPNNPolicyNet(g.edge_index, g.x.size(0), free_flow, device=str(self.device))
             self.policy_net.policy_head = a.policy_head
             self.policy_net.prior_weight = float(a.prior_weight)
+            if a.policy_head == "graph_transformer":
+                from .transformer import cached_laplacian_pe
+                # on the road graph (MLAgents: edge_index_routes, num_roads); the SRC / DEST rows stay zero
+                roads = int(getattr(g, "num_roads", None) or g.x.size(0))
+                routes = getattr(g, "edge_index_routes", None)
+                cache = None if a.scenario.startswith("synthetic") else str(Path("save") / a.scenario)
+                self.policy_net.use_graph_transformer(
+                    cached_laplacian_pe(g.edge_index if routes is None else routes, roads, g.x.size(0), cache))
             self.policy_net.load(a.scenario)
             self.value_net = MPNNValueNetSimple(g.edge_index, g.x.size(0), device=str(self.device))
             self.value_net.load(a.scenario)

@@ -228,6 +228,16 @@ class SimEngine:
                              policy_counter0=policy_counter0, keep=keep, obs_keep=obs_keep, choice8=choice8,
                              log_prob=log_prob, reward=reward)
 
+    def rollout_gt(self, T, pe, weights, *, temperature, policy_seed, policy_counter0, choice8, log_prob, reward, counts,
+                   keep=None, obs_keep=None, check=True):
+        """``T`` frames under the graph-transformer head (``pe``: (N, 16) positional encoding, ``weights``: ops.GtWeights) in
+        one foreign call: per frame observation -> transformer logits -> GraphDistribution sample + log-prob -> the
+        simulation frame. Buffers as :meth:`rollout_policy`. Returns the list of clock values."""
+        return self._rollout(T, counts, True, check,
+                             partial(ops.fused_rollout_gt, self.plan, self.fs, self._x, self.agents, self.ec, pe, weights),
+                             temperature=temperature, policy_seed=policy_seed, policy_counter0=policy_counter0, keep=keep,
+                             obs_keep=obs_keep, choice8=choice8, log_prob=log_prob, reward=reward)
+
     def decode_rollout(self, env_minor, *, choice=None, counts=None):
         """The rollout's byte buffers in the formats of the unfused entry points, ENV-MAJOR: ``choice`` (T,N,B) / (T,B,N)
         uint8 -> (T,B,N) int32 edge ids (-1: none); ``counts`` (T',N,B) / (T',B,N) uint8 -> (T',B,N) fp32."""

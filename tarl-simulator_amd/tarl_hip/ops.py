@@ -1137,6 +1137,125 @@ def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeC
         _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), _lib.current_stream()))
 
 
+# ---- graph-transformer head (policy_head = "graph_transformer", csrc/gt_policy.hip) ------------------------------------------
+# state-dict keys of GraphTransformerNet in the kernels' order: the trainable tensors that reach the logits, then the
+# BatchNorm running statistics (include/tarl_hip.h)
+_GT_EDGE = ("WE.weight", "WE.bias", "WOe.weight", "WOe.bias", "norm1e.weight", "norm1e.bias", "ffn_e.mlp.0.weight",
+            "ffn_e.mlp.0.bias", "ffn_e.mlp.3.weight", "ffn_e.mlp.3.bias", "norm2e.weight", "norm2e.bias")
+GT_PARAM_KEYS = (("node_emb.weight", "pe_emb.weight", "edge_emb.weight")
+                 + tuple("gt_layers.0." + k for k in ("WQ.weight", "WK.weight", "WV.weight", "n_gate.weight", "n_gate.bias",
+                                                      "WO.weight", "WO.bias", "norm1.weight", "norm1.bias",
+                                                      "ffn.mlp.0.weight", "ffn.mlp.0.bias", "ffn.mlp.3.weight",
+                                                      "ffn.mlp.3.bias", "norm2.weight", "norm2.bias") + _GT_EDGE)
+                 + tuple("gt_layers.1." + k for k in ("WQ.weight", "WK.weight") + _GT_EDGE)
+                 + ("edge_linear.weight", "edge_linear.bias"))
+GT_BUFFER_KEYS = tuple(f"gt_layers.{L}.{n}.{s}" for L, norms in ((0, ("norm1", "norm2", "norm1e", "norm2e")),
+                                                                 (1, ("norm1e", "norm2e")))
+                       for n in norms for s in ("running_mean", "running_var"))
+
+
+class GtWeights:
+    """The graph-transformer head's tensors in kernel order (``GT_PARAM_KEYS`` then ``GT_BUFFER_KEYS``), fp32 device tensors
+    (contiguous views, no copies); ``tensors`` maps each key to its tensor, e.g. a ``GraphTransformerNet.state_dict()``."""
+
+    def __init__(self, tensors):
+        self.params = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_PARAM_KEYS]
+        self.buffers = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_BUFFER_KEYS]
+        self.table = _ptr_array(self.params + self.buffers)
+
+
+def _gt_args(plan: Plan, obs16, ec: EdgeConst, pe):
+    _contig(obs16, torch.float32, "obs16")
+    _contig(pe, torch.float32, "pe")
+    N = plan.num_nodes
+    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (N, 16):
+        raise ValueError(f"obs16 must be (M, {N}, 16)")
+    if tuple(pe.shape) != (N, 16):
+        raise ValueError(f"pe must be ({N}, 16)")
+    return obs16.size(0)
+
+
+def policy_gt_logits(plan: Plan, obs16, ec: EdgeConst, pe, w: GtWeights, out=None):
+    """The graph-transformer head's logits (M, E) from observations ``obs16`` (M, N, 16) (the :func:`policy_obs16` layout),
+    the edge attribute of ``ec`` and the positional encoding ``pe`` (N, 16); evaluation-mode BatchNorm / dropout."""
+    L = _lib.load()
+    M = _gt_args(plan, obs16, ec, pe)
+    logits = out if out is not None else torch.empty((M, plan.num_edges), dtype=torch.float32, device=obs16.device)
+    n = int(L.tarl_policy_gt_fwd_scratch_floats(plan.handle, M))
+    scratch = torch.empty(n, dtype=torch.float32, device=obs16.device)
+    _lib.check(L.tarl_policy_gt_fwd(plan.handle, obs16.data_ptr(), M, ec.edge_attr.data_ptr(), pe.data_ptr(), w.table,
+                                    scratch.data_ptr(), n, logits.data_ptr(), _lib.current_stream()))
+    return logits
+
+
+GT_CHUNK_ITEMS = 1024          # items per stage-1 partial sum of the backward's weight gradients (csrc/gt_policy.hip)
+
+
+def gt_bwd_max_samples(plan: Plan) -> int:
+    """The largest sample count one tarl_policy_gt_bwd call takes: its weight-gradient grid has one row of blocks per
+    1 024 (sample, edge) or (sample, node) items, at most 65 535 rows."""
+    return 65535 * GT_CHUNK_ITEMS // max(plan.num_edges, plan.num_nodes, 1)
+
+
+def gt_bwd_scratch_bytes(plan: Plan, M: int) -> int:
+    """Device scratch of one tarl_policy_gt_bwd call over ``M`` samples (activation records of every node and edge)."""
+    return 4 * int(_lib.load().tarl_policy_gt_bwd_scratch_floats(plan.handle, int(M)))
+
+
+def policy_gt_bwd(plan: Plan, obs16, ec: EdgeConst, pe, w: GtWeights, grad_logits, grads, scratch=None):
+    """Accumulates the gradients of sum(grad_logits * logits) into ``grads``: one fp32 contiguous tensor per
+    ``GT_PARAM_KEYS`` entry, shaped like the parameter. Deterministic (no atomics). ``scratch``: an fp32 device tensor of
+    at least ``gt_bwd_scratch_bytes(plan, M) / 4`` elements to reuse across calls (allocated per call when None)."""
+    L = _lib.load()
+    M = _gt_args(plan, obs16, ec, pe)
+    gl = _contig(grad_logits, torch.float32, "grad_logits")
+    if gl.numel() != M * plan.num_edges:
+        raise ValueError("grad_logits must be (M, E)")
+    gs = [_contig(g, torch.float32, "grad") for g in grads]
+    if len(gs) != len(GT_PARAM_KEYS) or any(g.shape != p.shape for g, p in zip(gs, w.params)):
+        raise ValueError("grads must match GT_PARAM_KEYS in number and shapes")
+    if M > gt_bwd_max_samples(plan):
+        raise ValueError(f"the graph-transformer backward takes at most {gt_bwd_max_samples(plan)} samples on this graph")
+    n = int(L.tarl_policy_gt_bwd_scratch_floats(plan.handle, M))
+    if scratch is None:
+        scratch = torch.empty(n, dtype=torch.float32, device=obs16.device)
+    else:
+        _contig(scratch, torch.float32, "scratch")
+        n = scratch.numel()
+    _lib.check(L.tarl_policy_gt_bwd(plan.handle, obs16.data_ptr(), M, ec.edge_attr.data_ptr(), pe.data_ptr(), w.table,
+                                    gl.data_ptr(), scratch.data_ptr(), n, _ptr_array(gs), _lib.current_stream()))
+
+
+def fused_rollout_gt(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeConst, pe, w: GtWeights, times, *, use_cong,
+                     temperature, policy_seed, policy_counter0, seed, counter0, scratch, prev_time=None, keep=None,
+                     obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None):
+    """``T = len(times)`` frames under the graph-transformer head in one foreign call (tarl_fused_rollout_gt). ``keep`` /
+    ``obs_keep`` / ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
+    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
+    B, N = fs.B, fs.N
+    _, _, bs, ldx = _state(x, fs.Nmax)
+    _contig(pe, torch.float32, "pe")
+    if tuple(pe.shape) != (N, 16):
+        raise ValueError(f"pe must be ({N}, 16)")
+    _check_rollout_outputs(T, B, N, True, 0, None, counts, log_prob, None, reward, None, None, None)
+    _check_rollout_outputs(T, B, N, False, 0, choice8, None, None, None, None, None, None, None)
+    if getattr(fs, "obs_scratch", None) is None:
+        fs.obs_scratch = torch.empty((B, N, 16), dtype=torch.float32, device=fs.sel8.device)
+    n = int(L.tarl_policy_gt_fwd_scratch_floats(plan.handle, B))
+    if getattr(fs, "gt_scratch", None) is None or fs.gt_scratch.numel() < n:
+        fs.gt_scratch = torch.empty(n, dtype=torch.float32, device=fs.sel8.device)
+    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
+    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
+    tarr = (C.c_float * T)(*[float(t) for t in times])
+    _lib.check(L.tarl_fused_rollout_gt(
+        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
+        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps, 1 if use_cong else 0, pe.data_ptr(), w.table,
+        float(temperature), int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv),
+        _lib.ptr(kslot), _lib.ptr(obs_keep), fs.obs_scratch.data_ptr(), fs.gt_scratch.data_ptr(), fs.gt_scratch.numel(),
+        logits_scratch, dist_scratch, scratch.data_ptr(), _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward),
+        _lib.ptr(counts), _lib.current_stream()))
+
+
 def rollout_gather(plan: Plan, T, B, env_minor, idx=None, *, choice=None, counts=None):
     """Rollout bytes -> (choice_eid int32 (rows, N) | None, counts_f fp32 (rows, N) | None) for the (frame, env) pairs
     ``idx`` (int64 flat indices t * B + b; None = all ``T * B`` in order). ``choice`` / ``counts``: the uint8 buffers

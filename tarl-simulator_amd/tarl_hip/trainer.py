@@ -69,7 +69,7 @@ class VecPPOTrainer:
                  gamma=0.99, lmbda=0.95, clip_epsilon=0.2, entropy_coef=0.01, critic_coef=1.0, temperature=1.0,
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
-                 prior_weight=1.0):
+                 prior_weight=1.0, gt_params=None, gt_pe=None):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -87,6 +87,9 @@ class VecPPOTrainer:
         # "embedding_dijkstra" = the embedding plus ``prior_weight`` times the shortest-path prior of the reference
         # (src/agents/mpnn_agent.py:180-190, csrc/prior.hip): state-DEPENDENT like the MLP head, but without parameters of
         # its own; ``prior_table`` (N, N) = MPNNPolicyNet.dist_matrix. Gradients reach the embedding alone.
+        # "graph_transformer" = the reference's GraphTransformerNet edge output (csrc/gt_policy.hip), evaluation-mode
+        # BatchNorm: ``gt_params`` maps the state-dict keys of ops.GT_PARAM_KEYS + GT_BUFFER_KEYS to the module's tensors
+        # (the parameters must also be in ``extra_params``), ``gt_pe`` (N, 16) is its positional encoding.
         self.policy = policy
         self.prior_table = prior_table
         self.prior_weight = float(prior_weight)
@@ -106,8 +109,25 @@ class VecPPOTrainer:
                 raise ValueError("policy='embedding_dijkstra' needs the fused engine and the (N, N) prior_table")
             if tuple(prior_table.shape) != (engine.N, engine.N):
                 raise ValueError(f"prior_table must be ({engine.N}, {engine.N})")
+        elif policy == "graph_transformer":
+            if engine.fs is None or gt_params is None or gt_pe is None:
+                raise ValueError("policy='graph_transformer' needs the fused engine, gt_params and the (N, 16) gt_pe")
+            ids = {id(p) for p in extra_params}
+            if not all(id(gt_params[k]) in ids for k in ops.GT_PARAM_KEYS):
+                raise ValueError("the graph-transformer parameters must be part of extra_params (the optimiser's flat buffer)")
+            # the backward keeps every node's and edge's activations of the minibatch (~2 KB per node and per edge and
+            # sample): refuse a sub-batch it cannot take here rather than inside the library
+            m = min(int(sub_batch_size), int(rollout_steps) * engine.B)
+            need, cap = ops.gt_bwd_scratch_bytes(engine.plan, m), ops.gt_bwd_max_samples(engine.plan)
+            free = torch.cuda.mem_get_info(engine.device)[0]
+            if m > cap or need > free // 2:
+                raise ValueError(f"sub_batch_size {m} is too large for the graph-transformer backward on this graph: it "
+                                 f"takes at most {cap} samples and needs {need / 2**20:.0f} MiB of scratch "
+                                 f"({free / 2**20:.0f} MiB free); use a smaller sub_batch_size")
         elif policy != "embedding":
-            raise ValueError("policy must be 'embedding', 'edge_mlp' or 'embedding_dijkstra'")
+            raise ValueError("policy must be 'embedding', 'edge_mlp', 'embedding_dijkstra' or 'graph_transformer'")
+        self.gt_params = dict(gt_params) if gt_params is not None else None
+        self.gt_pe = gt_pe
         # the state-dependent heads evaluate their logits in front of every frame and draw the minibatch frames up front
         self.state_dep = policy != "embedding"
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
@@ -139,7 +159,7 @@ class VecPPOTrainer:
         if engine.fs is None:
             mode = "unfused"
         elif self.state_dep:    # per-frame policy evaluation in front of the four-launch frame
-            mode = "frames+policy" if policy == "edge_mlp" else "frames+prior"
+            mode = {"edge_mlp": "frames+policy", "graph_transformer": "frames+gt"}.get(policy, "frames+prior")
         elif mode == "auto":
             mode = "env" if (engine.env_rollout_supported and engine.B * engine.N <= 800_000) else "frames"
         elif mode == "env" and not engine.env_rollout_supported:
@@ -195,6 +215,9 @@ class VecPPOTrainer:
 
     def _edge_mlp(self):
         return ops.EdgeMlpWeights(*(p.data for p in self.edge_mlp_params))
+
+    def _gt(self):
+        return ops.GtWeights(self.gt_params)
 
     # -- HOT LOOP A -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -312,6 +335,8 @@ class VecPPOTrainer:
                   obs_keep=self.obs_mb, check=False)
         if self.policy == "edge_mlp":
             times = eng.rollout_policy(n, self._edge_mlp(), precision=self.policy_precision, **logs, **kw)
+        elif self.policy == "graph_transformer":
+            times = eng.rollout_gt(n, self.gt_pe, self._gt(), **kw)
         else:
             times = eng.rollout_prior(n, self._emb(), self.prior_table, prior_weight=self.prior_weight, **kw)
         self.sample_counter += n
@@ -341,6 +366,8 @@ class VecPPOTrainer:
         eng = self.eng
         if self.policy == "edge_mlp":
             return ops.policy_edge_mlp(eng.plan, obs, eng.ec, self._edge_mlp())          # fp32 MFMA
+        if self.policy == "graph_transformer":
+            return ops.policy_gt_logits(eng.plan, obs, eng.ec, self.gt_pe, self._gt())
         if self.policy == "embedding_dijkstra":
             return ops.policy_prior_logits(eng.plan, obs, self._emb(), self.prior_table, self.prior_weight)
         return ops.policy_edge_logits(eng.plan, obs, self._emb())
@@ -352,6 +379,12 @@ class VecPPOTrainer:
             gm = [self.flat.grad_view(p) for p in self.edge_mlp_params]
             ops.policy_edge_mlp_bwd(eng.plan, obs, eng.ec, self._edge_mlp(), g_logits,
                                     (gm[0], gm[1], gm[2], gm[3], gm[4].view(-1), gm[5]))
+        elif self.policy == "graph_transformer":
+            need = ops.gt_bwd_scratch_bytes(eng.plan, obs.size(0)) // 4
+            if getattr(self, "_gt_scratch", None) is None or self._gt_scratch.numel() < need:
+                self._gt_scratch = torch.empty(need, dtype=torch.float32, device=eng.device)     # once per trainer
+            ops.policy_gt_bwd(eng.plan, obs, eng.ec, self.gt_pe, self._gt(), g_logits,
+                              [self.flat.grad_view(self.gt_params[k]) for k in ops.GT_PARAM_KEYS], scratch=self._gt_scratch)
         else:       # the prior has no parameters: the embedding receives the logits' gradient as is
             g_emb = ops.policy_edge_logits_bwd(eng.plan, obs, g_logits, self.emb_param.numel())
             self.flat.grad_view(self.emb_param).add_(g_emb.view_as(self.emb_param))
