@@ -633,6 +633,36 @@ int tarl_fused_rollout_gt(const tarl_plan* plan, const tarl_fused* f, int64_t B,
                           const int32_t* keep_slot, float* obs_keep, float* obs_scratch, float* gt_scratch,
                           int64_t gt_scratch_floats, float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
                           uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts, tarl_stream stream);
+/* ---- the graph-transformer critic (value_head = "graph_transformer"; csrc/gt_value.hip) -------------------------------------
+ * ValueNet(MLAgents) (src/agents/transformer_agent.py:257-323): value = mu_mlp(sum over all N nodes of x2) of a second
+ * GraphTransformerNet (model.py:174-178, raw=True; hidden 16, 4 heads, gate=True, 2 GTConv layers; node input 16 = obs16),
+ * evaluation mode as the policy head above. The node path never reads edge features (the score is (Q_i K_j).sum / sqrt(d_k),
+ * gt_conv.py:222): edge_emb, WE, WOe, ffn_e, norm1e / norm2e, e_gate, edge_linear and log_var_mlp do not reach the value.
+ * w: host array of TARL_GTV_NUM_TENSORS device pointers, fp32 nn.Linear layouts: the TARL_GTV_NUM_PARAMS trainable tensors
+ *   that reach the value, in this order (state-dict names of GraphTransformerNet):
+ *     node_emb.weight, pe_emb.weight,
+ *     gt_layers.L.{WQ.weight, WK.weight, WV.weight, n_gate.weight, n_gate.bias, WO.weight, WO.bias, norm1.weight,
+ *       norm1.bias, ffn.mlp.0.weight, ffn.mlp.0.bias, ffn.mlp.3.weight, ffn.mlp.3.bias, norm2.weight, norm2.bias} for L = 0, 1,
+ *     mu_mlp.mlp.0.weight, mu_mlp.mlp.0.bias, mu_mlp.mlp.2.weight, mu_mlp.mlp.2.bias;
+ *   then the running statistics gt_layers.L.{norm1, norm2}.{running_mean, running_var} for L = 0, 1.
+ * pe [N][16]: the positional encoding; obs16 [M][N][16] as tarl_policy_obs16 (16-byte aligned); value [M].
+ * tarl_value_gt_fwd: scratch fp32 of at least tarl_value_gt_fwd_scratch_floats(plan, M), 16-byte aligned.
+ * tarl_value_gt_bwd ACCUMULATES (+=) the gradients of sum(grad_value * value) into grads (host array of TARL_GTV_NUM_PARAMS
+ *   device pointers, same order and shapes as w), the forward recomputed inside; scratch: at least
+ *   tarl_value_gt_bwd_scratch_floats(plan, M) floats; M at most tarl_value_gt_bwd_max_samples(plan) (one row of the weight
+ *   gradients' grid per 1 024 (sample, node) items). Deterministic: no atomics, the node sum of the pooling in a fixed
+ *   order, per-node sums over in- / out-edges in CSC / CSR order, weight gradients summed over fixed chunks of items, then
+ *   the chunks in order. */
+#define TARL_GTV_NUM_PARAMS 36
+#define TARL_GTV_NUM_TENSORS 44
+int64_t tarl_value_gt_fwd_scratch_floats(const tarl_plan* plan, int64_t M);
+int tarl_value_gt_fwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* pe, const float* const* w,
+                      float* scratch, int64_t scratch_floats, float* value, tarl_stream stream);
+int64_t tarl_value_gt_bwd_max_samples(const tarl_plan* plan);
+int64_t tarl_value_gt_bwd_scratch_floats(const tarl_plan* plan, int64_t M);
+int tarl_value_gt_bwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* pe, const float* const* w,
+                      const float* grad_value, float* scratch, int64_t scratch_floats, float* const* grads,
+                      tarl_stream stream);
 /* the action / count bytes of a rollout back in the formats of the unfused entry points: choice_eid int32 [rows][N] =
  *   chosen edge id (-1: none), counts_f fp32 [rows][N], for `rows` (frame, environment) pairs given as flat indices
  *   idx int64 [rows] = t * B + b (NULL: all T * B pairs in order). env_minor != 0: the buffers are [T][N][B], else

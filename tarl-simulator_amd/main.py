@@ -1,7 +1,7 @@
 """Command line of the MI355X build. The flag set is the reference CLI's contract (main.py of the reference: --algo,
 --scenario, --mode, --timestep_size, --start-end-time, --epochs, --rollout-steps, --seed, --device, --output-dir,
 --profile, --torch-compile) plus ``--steps`` (used by the reference's README but missing from its parser) and
-``--num-envs`` (vectorised environments per GPU) and ``--policy-head``."""
+``--num-envs`` (vectorised environments per GPU), ``--policy-head`` and ``--value-head``."""
 import argparse
 import os
 import sys
@@ -44,6 +44,10 @@ OPTIONS = (
                                 "BatchNorm, Laplacian positional encoding)")),
     ("--prior-weight", dict(type=float, default=1.0,
                             help="embedding_dijkstra: weight of the shortest-path prior (1.0 = the reference's plain sum)")),
+    ("--value-head", dict(choices=("simple", "graph_transformer"), default="simple",
+                          help="mpnn+ppo critic: the reference runner's MPNNValueNetSimple (per-road counts and the clock), "
+                               "or graph_transformer: the reference's ValueNet, a second GraphTransformerNet on the policy's "
+                               "observation, node output summed and read by mu_mlp (needs a state-dependent policy head)")),
 )
 
 

@@ -76,7 +76,10 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
 
     rank, world = dist_utils.world()
     policy_net = unwrap(policy_module, "MPNNPolicyNet")
-    value_net = unwrap(value_module, "MPNNValueNetSimple")
+    try:
+        value_net, value_head = unwrap(value_module, "MPNNValueNetSimple"), "simple"
+    except TypeError:
+        value_net, value_head = unwrap(value_module, "ValueNet"), "graph_transformer"
     sim = env.simulator
     g = sim.graph
     agents = sim.agent.agent_features
@@ -86,12 +89,18 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                        congestion_constant=getattr(g, "congestion_constant", None), num_envs=num_envs,
                        device=g.x.device, timestep=sim.timestep, seed=seed + 7919 * rank,
                        fused=ops.fused_path_supported(g.edge_index, sim.Nmax))   # same decision on every rank
-    l = value_net.final_mlp
     dormant = [p for n, p in policy_net.named_parameters() if not n.startswith("nodes_embedding")]
+    if value_head == "simple":
+        l = value_net.final_mlp
+        critic = [l[0].weight, l[0].bias, l[2].weight, l[2].bias, l[4].weight, l[4].bias]
+        critic_kw = {}
+    else:       # every parameter of the critic's network goes to the optimiser, as loss_module.parameters() does
+        critic = list(value_net.transformer.parameters())
+        critic_kw = dict(value="graph_transformer", gt_value_params=value_net.kernel_tensors(), gt_value_pe=value_net.gt_pe)
     head = getattr(policy_net, "policy_head", "embedding")
     m = policy_net.edge_mlp
     trainer = VecPPOTrainer(engine, policy_net.nodes_embedding.weight,
-                            [l[0].weight, l[0].bias, l[2].weight, l[2].bias, l[4].weight, l[4].bias],
+                            critic,
                             rollout_steps=frames_per_batch, num_epochs=num_epochs, sub_batch_size=sub_batch_size,
                             extra_params=dormant, seed=seed,
                             policy=head if head in ("embedding", "embedding_dijkstra", "graph_transformer") else "edge_mlp",
@@ -100,7 +109,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             prior_table=policy_net.dist_matrix if head == "embedding_dijkstra" else None,
                             prior_weight=getattr(policy_net, "prior_weight", 1.0),
                             gt_params=policy_net.transformer.kernel_tensors() if head == "graph_transformer" else None,
-                            gt_pe=getattr(policy_net, "gt_pe", None))
+                            gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw)
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)

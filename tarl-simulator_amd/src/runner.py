@@ -27,6 +27,15 @@ class RunnerArgs:
     num_envs: int = 1
     policy_head: str = "embedding"
     prior_weight: float = 1.0      # policy_head "embedding_dijkstra": weight of the shortest-path prior
+    value_head: str = "simple"     # "graph_transformer": ValueNet (src/agents/transformer_agent.py)
+
+    def __post_init__(self):
+        if self.value_head not in ("simple", "graph_transformer"):
+            raise ValueError("value_head must be 'simple' or 'graph_transformer'")
+        if self.value_head == "graph_transformer" and self.policy_head == "embedding":
+            raise ValueError("value_head 'graph_transformer' reads the observation of every frame, which the 'embedding' "
+                             "head's rollout does not build: use a state-dependent policy head (edge_mlp*, "
+                             "embedding_dijkstra or graph_transformer)")
 
 
 class Runner:
@@ -82,16 +91,23 @@ class Runner:
             self.policy_net = MPNNPolicyNet(g.edge_index, g.x.size(0), free_flow, device=str(self.device))
             self.policy_net.policy_head = a.policy_head
             self.policy_net.prior_weight = float(a.prior_weight)
-            if a.policy_head == "graph_transformer":
+            pe = None
+            if "graph_transformer" in (a.policy_head, a.value_head):
                 from .transformer import cached_laplacian_pe
                 # on the road graph (MLAgents: edge_index_routes, num_roads); the SRC / DEST rows stay zero
                 roads = int(getattr(g, "num_roads", None) or g.x.size(0))
                 routes = getattr(g, "edge_index_routes", None)
                 cache = None if a.scenario.startswith("synthetic") else str(Path("save") / a.scenario)
-                self.policy_net.use_graph_transformer(
-                    cached_laplacian_pe(g.edge_index if routes is None else routes, roads, g.x.size(0), cache))
+                pe = cached_laplacian_pe(g.edge_index if routes is None else routes, roads, g.x.size(0), cache)
+            if a.policy_head == "graph_transformer":
+                self.policy_net.use_graph_transformer(pe)
             self.policy_net.load(a.scenario)
-            self.value_net = MPNNValueNetSimple(g.edge_index, g.x.size(0), device=str(self.device))
+            if a.value_head == "graph_transformer":
+                from .agents.transformer_agent import ValueNet
+                # the same encoding as the policy's (ValueNet is an MLAgents: compute_encodings on the same road graph)
+                self.value_net = ValueNet(g.edge_index, g.x.size(0), str(self.device), pe)
+            else:
+                self.value_net = MPNNValueNetSimple(g.edge_index, g.x.size(0), device=str(self.device))
             self.value_net.load(a.scenario)
             self.env.simulator.agent = self.policy_net     # the policy IS the population store used by the env
         else:

@@ -99,6 +99,15 @@ class SimEngine:
         policy reads ROAD_INDEX alone) — avoids an export of the packed state."""
         return self._x[:, :, 3 * self.Nmax:]
 
+    def obs16(self, out=None):
+        """(B, N, 16) fp32 observation of the current state from the packed state (tarl_fused_obs16): what the next frame of
+        a state-dependent rollout reads (fused engine only)."""
+        if self.fs is None:
+            raise ValueError("obs16 needs the fused engine")
+        if self._packed_stale:
+            self.resync()
+        return ops.fused_obs16(self.plan, self.fs, self._x, self.Nmax, self.agents, out=out)
+
     def refresh_counts(self):
         self.counts.copy_(self.x[:, :, 3 * self.Nmax + 1])
         return self.counts

@@ -99,6 +99,11 @@ SIGNATURES = {
     "tarl_fused_rollout_gt": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _f32,
                                         C.c_int, _p, _p, _f32, _u64, _u64, _u64, _u64] + [_p] * 6 + [_i64] +
                               [_p] * 8),
+    "tarl_value_gt_fwd_scratch_floats": (_i64, [_p, _i64]),
+    "tarl_value_gt_fwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _p, _p]),
+    "tarl_value_gt_bwd_max_samples": (_i64, [_p]),
+    "tarl_value_gt_bwd_scratch_floats": (_i64, [_p, _i64]),
+    "tarl_value_gt_bwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p]),
     "tarl_rollout_gather": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_int, _p, _i64, _p, _p, _p]),
     "tarl_rollout_env_supported": (C.c_int, [_p]),
     "tarl_rollout_env_scratch_bytes": (_i64, [_p]),

@@ -1256,6 +1256,102 @@ def fused_rollout_gt(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeCons
         _lib.ptr(counts), _lib.current_stream()))
 
 
+# ---- graph-transformer critic (value_head = "graph_transformer", csrc/gt_value.hip) -------------------------------------------
+# state-dict keys of the critic's GraphTransformerNet in the kernels' order: the trainable tensors that reach the value, then
+# the BatchNorm running statistics (include/tarl_hip.h). The edge side (edge_emb, WE, WOe, ffn_e, norm1e / norm2e, e_gate,
+# edge_linear, log_var_mlp) never reaches the node output.
+_GTV_NODE = ("WQ.weight", "WK.weight", "WV.weight", "n_gate.weight", "n_gate.bias", "WO.weight", "WO.bias", "norm1.weight",
+             "norm1.bias", "ffn.mlp.0.weight", "ffn.mlp.0.bias", "ffn.mlp.3.weight", "ffn.mlp.3.bias", "norm2.weight",
+             "norm2.bias")
+GT_VALUE_PARAM_KEYS = (("node_emb.weight", "pe_emb.weight")
+                       + tuple(f"gt_layers.{L}.{k}" for L in (0, 1) for k in _GTV_NODE)
+                       + ("mu_mlp.mlp.0.weight", "mu_mlp.mlp.0.bias", "mu_mlp.mlp.2.weight", "mu_mlp.mlp.2.bias"))
+GT_VALUE_BUFFER_KEYS = tuple(f"gt_layers.{L}.{n}.{s}" for L in (0, 1) for n in ("norm1", "norm2")
+                             for s in ("running_mean", "running_var"))
+
+
+class GtValueWeights:
+    """The graph-transformer critic's tensors in kernel order (``GT_VALUE_PARAM_KEYS`` then ``GT_VALUE_BUFFER_KEYS``), fp32
+    device tensors (contiguous views, no copies); ``tensors`` maps each key to its tensor."""
+
+    def __init__(self, tensors):
+        self.params = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_VALUE_PARAM_KEYS]
+        self.buffers = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_VALUE_BUFFER_KEYS]
+        self.table = _ptr_array(self.params + self.buffers)
+
+
+def _gtv_args(plan: Plan, obs16, pe):
+    _contig(obs16, torch.float32, "obs16")
+    _contig(pe, torch.float32, "pe")
+    N = plan.num_nodes
+    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (N, 16) or obs16.size(0) < 1:
+        raise ValueError(f"obs16 must be (M, {N}, 16) with M >= 1")
+    if tuple(pe.shape) != (N, 16):
+        raise ValueError(f"pe must be ({N}, 16)")
+    return obs16.size(0)
+
+
+def value_gt_fwd_scratch_bytes(plan: Plan, M: int) -> int:
+    """Device scratch of one tarl_value_gt_fwd call over ``M`` samples."""
+    return 4 * int(_lib.load().tarl_value_gt_fwd_scratch_floats(plan.handle, int(M)))
+
+
+def value_gt_bwd_max_samples(plan: Plan) -> int:
+    """The largest sample count one tarl_value_gt_bwd call takes (its weight-gradient grid has one row of blocks per
+    1 024 (sample, node) items, at most 65 535 rows)."""
+    return int(_lib.load().tarl_value_gt_bwd_max_samples(plan.handle))
+
+
+def value_gt_bwd_scratch_bytes(plan: Plan, M: int) -> int:
+    """Device scratch of one tarl_value_gt_bwd call over ``M`` samples (activation records of every node and edge)."""
+    return 4 * int(_lib.load().tarl_value_gt_bwd_scratch_floats(plan.handle, int(M)))
+
+
+def _scratch(scratch, n, device):
+    if scratch is None:
+        return torch.empty(n, dtype=torch.float32, device=device)
+    _contig(scratch, torch.float32, "scratch")
+    if scratch.numel() < n:
+        raise ValueError(f"scratch holds {scratch.numel()} floats, the call needs {n}")
+    return scratch
+
+
+def value_gt_forward(plan: Plan, obs16, pe, w: GtValueWeights, out=None, scratch=None):
+    """The graph-transformer critic's value (M,) from observations ``obs16`` (M, N, 16) (the :func:`policy_obs16` layout)
+    and the positional encoding ``pe`` (N, 16); evaluation-mode BatchNorm / dropout. ``scratch``: an fp32 device tensor of
+    at least ``value_gt_fwd_scratch_bytes(plan, M) / 4`` elements to reuse (allocated per call when None)."""
+    L = _lib.load()
+    M = _gtv_args(plan, obs16, pe)
+    value = out if out is not None else torch.empty(M, dtype=torch.float32, device=obs16.device)
+    _contig(value, torch.float32, "value")
+    if value.numel() != M:
+        raise ValueError("value must hold M elements")
+    scratch = _scratch(scratch, int(L.tarl_value_gt_fwd_scratch_floats(plan.handle, M)), obs16.device)
+    _lib.check(L.tarl_value_gt_fwd(plan.handle, obs16.data_ptr(), M, pe.data_ptr(), w.table, scratch.data_ptr(),
+                                   scratch.numel(), value.data_ptr(), _lib.current_stream()))
+    return value
+
+
+def value_gt_backward(plan: Plan, obs16, pe, w: GtValueWeights, grad_value, grads, scratch=None):
+    """Accumulates the gradients of sum(grad_value * value) into ``grads``: one fp32 contiguous tensor per
+    ``GT_VALUE_PARAM_KEYS`` entry, shaped like the parameter. Deterministic (no atomics). ``scratch``: an fp32 device tensor
+    of at least ``value_gt_bwd_scratch_bytes(plan, M) / 4`` elements to reuse (allocated per call when None)."""
+    L = _lib.load()
+    M = _gtv_args(plan, obs16, pe)
+    gv = _contig(grad_value, torch.float32, "grad_value")
+    if gv.numel() != M:
+        raise ValueError("grad_value must hold M elements")
+    gs = [_contig(g, torch.float32, "grad") for g in grads]
+    if len(gs) != len(GT_VALUE_PARAM_KEYS) or any(g.shape != p.shape for g, p in zip(gs, w.params)):
+        raise ValueError("grads must match GT_VALUE_PARAM_KEYS in number and shapes")
+    cap = value_gt_bwd_max_samples(plan)
+    if M > cap:
+        raise ValueError(f"the graph-transformer critic's backward takes at most {cap} samples on this graph")
+    scratch = _scratch(scratch, int(L.tarl_value_gt_bwd_scratch_floats(plan.handle, M)), obs16.device)
+    _lib.check(L.tarl_value_gt_bwd(plan.handle, obs16.data_ptr(), M, pe.data_ptr(), w.table, gv.data_ptr(),
+                                   scratch.data_ptr(), scratch.numel(), _ptr_array(gs), _lib.current_stream()))
+
+
 def rollout_gather(plan: Plan, T, B, env_minor, idx=None, *, choice=None, counts=None):
     """Rollout bytes -> (choice_eid int32 (rows, N) | None, counts_f fp32 (rows, N) | None) for the (frame, env) pairs
     ``idx`` (int64 flat indices t * B + b; None = all ``T * B`` in order). ``choice`` / ``counts``: the uint8 buffers

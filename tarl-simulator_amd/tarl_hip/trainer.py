@@ -69,12 +69,18 @@ class VecPPOTrainer:
                  gamma=0.99, lmbda=0.95, clip_epsilon=0.2, entropy_coef=0.01, critic_coef=1.0, temperature=1.0,
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
-                 prior_weight=1.0, gt_params=None, gt_pe=None):
+                 prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
         edge MLPs) — they sit in the flat buffer so that the optimiser covers ``loss_module.parameters()`` like the
-        reference's does."""
+        reference's does.
+        ``value``: "simple" = MPNNValueNetSimple over the count bytes and the clock (``critic_params`` as above);
+        "graph_transformer" = ValueNet (src/agents/transformer_agent.py, csrc/gt_value.hip) on the policy's observation:
+        ``critic_params`` = every parameter of its GraphTransformerNet, ``gt_value_params`` maps the state-dict keys of
+        ops.GT_VALUE_PARAM_KEYS + GT_VALUE_BUFFER_KEYS to its tensors, ``gt_value_pe`` (N, 16) is its positional encoding.
+        It needs a state-dependent policy head (the rollout builds the observation of every frame) and keeps all (T + 1) * B
+        observations (``obs_all``, fp32 (T+1, B, N, 16)) for GAE's all-frames critic pass."""
         self.eng = engine
         # policy: "embedding" = the reference's live head (logit = embedding of the target road: state-independent, its
         # distribution is tabulated once per update); "edge_mlp" = the per-edge MLP head it carries as parameters
@@ -128,6 +134,13 @@ class VecPPOTrainer:
             raise ValueError("policy must be 'embedding', 'edge_mlp', 'embedding_dijkstra' or 'graph_transformer'")
         self.gt_params = dict(gt_params) if gt_params is not None else None
         self.gt_pe = gt_pe
+        self.value = value
+        self.gt_value_params = dict(gt_value_params) if gt_value_params is not None else None
+        self.gt_value_pe = gt_value_pe
+        if value == "graph_transformer":
+            self._check_gt_value(engine, policy, critic_params, extra_params, rollout_steps, sub_batch_size)
+        elif value != "simple":
+            raise ValueError("value must be 'simple' or 'graph_transformer'")
         # the state-dependent heads evaluate their logits in front of every frame and draw the minibatch frames up front
         self.state_dep = policy != "embedding"
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
@@ -190,6 +203,10 @@ class VecPPOTrainer:
         self.reward = torch.zeros((self.T, B), dtype=torch.float32, device=dev)
         self.times = torch.zeros(self.T + 1, dtype=torch.float32, device=dev)
         self.values = torch.zeros((self.T + 1, B), dtype=torch.float32, device=dev)
+        # graph-transformer critic: the observation of every frame 0..T of every environment (frames 0..T-1 written by the
+        # rollout's keep path, frame T from the final state), and one forward / one backward scratch reused across calls
+        self.obs_all = (torch.empty((self.T + 1, B, N, 16), dtype=torch.float32, device=dev)
+                        if value == "graph_transformer" else None)
         # every rank draws its own minibatches / action noise; rank_offset=False (test hook) makes replicas identical
         off = self.rank if rank_offset else 0
         # minibatch draw: M distinct frames out of T * B (the reference's SamplerWithoutReplacement hands out sub-batches of a
@@ -205,6 +222,41 @@ class VecPPOTrainer:
         self.obs_idx = None
         self.stage = NoStageTimer()          # bench.py swaps in a StageTimer for its update_path object
 
+    GTV_FWD_CHUNK_BYTES = 1 << 30      # scratch of one all-frames critic call: the store is evaluated in chunks of rows
+
+    def _gtv_sizes(self, plan, B, T, m):
+        """(rows per all-frames forward call, forward scratch bytes, backward scratch bytes, store bytes per row)."""
+        per = ops.value_gt_fwd_scratch_bytes(plan, 2) - ops.value_gt_fwd_scratch_bytes(plan, 1)
+        chunk = max(1, min((T + 1) * B, (self.GTV_FWD_CHUNK_BYTES - ops.value_gt_fwd_scratch_bytes(plan, 0)) // per))
+        return chunk, ops.value_gt_fwd_scratch_bytes(plan, chunk), ops.value_gt_bwd_scratch_bytes(plan, m), plan.num_nodes * 64
+
+    def _check_gt_value(self, engine, policy, critic_params, extra_params, rollout_steps, sub_batch_size):
+        """Refusals of value="graph_transformer", each naming its limit."""
+        if policy == "embedding":
+            raise ValueError("value='graph_transformer' needs a state-dependent policy head (edge_mlp, embedding_dijkstra "
+                             "or graph_transformer): the embedding head's rollout builds no observation")
+        if engine.fs is None or self.gt_value_params is None or self.gt_value_pe is None:
+            raise ValueError("value='graph_transformer' needs the fused engine, gt_value_params and the (N, 16) gt_value_pe")
+        ids = {id(p) for p in list(critic_params) + list(extra_params)}
+        if not all(id(self.gt_value_params[k]) in ids for k in ops.GT_VALUE_PARAM_KEYS):
+            raise ValueError("the graph-transformer critic's parameters must be part of critic_params or extra_params (the "
+                             "optimiser's flat buffer)")
+        T, B = int(rollout_steps), engine.B
+        m = min(int(sub_batch_size), T * B)
+        cap = ops.value_gt_bwd_max_samples(engine.plan)
+        if m > cap:
+            raise ValueError(f"sub_batch_size {m} is too large for the graph-transformer critic's backward on this graph: it "
+                             f"takes at most {cap} samples")
+        _, fwd, bwd, row = self._gtv_sizes(engine.plan, B, T, m)
+        budget = torch.cuda.mem_get_info(engine.device)[0] // 2
+        need = (T + 1) * B * row + fwd + bwd
+        if need > budget:
+            fit = max(0, (budget - fwd - bwd) // row)
+            raise ValueError(f"the graph-transformer critic's observation store of (T + 1) * B = {(T + 1) * B} frames "
+                             f"({(T + 1) * B * row / 2**30:.1f} GiB) plus its scratch ({(fwd + bwd) / 2**30:.2f} GiB) exceeds "
+                             f"half the free device memory ({budget / 2**30:.1f} GiB): at most (T + 1) * B = {fit} frames fit "
+                             f"(T = {max(0, fit // B - 1)} at B = {B})")
+
     # -- views of the live parameters -----------------------------------------------------------------------------------
     def _emb(self):
         return self.emb_param.data.reshape(-1)
@@ -218,6 +270,9 @@ class VecPPOTrainer:
 
     def _gt(self):
         return ops.GtWeights(self.gt_params)
+
+    def _gt_value(self):
+        return ops.GtValueWeights(self.gt_value_params)
 
     # -- HOT LOOP A -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -245,6 +300,8 @@ class VecPPOTrainer:
             for sl in self._segments(done):
                 host_times += self._queue(sl)[:-1]
             host_times.append(float(eng.time))
+            if self.obs_all is not None:      # frame T: the final state (an episode end at T - 1 is not followed by a reset)
+                eng.obs16(out=self.obs_all[T])
             # the device status word travels to pinned host memory behind the rollout; it is looked at when it has
             # arrived (no stall of the launch pipeline) and by check_flags() at the caller's synchronisation points
             self._flag_host.copy_(eng.fs.flags, non_blocking=True)
@@ -307,6 +364,14 @@ class VecPPOTrainer:
         self._epoch = 0
         flat = torch.cat(host)      # (the frame list stays on the host: no device round trip before the rollout)
         order = torch.argsort(flat, stable=True)
+        if self.obs_all is not None:
+            # the graph-transformer critic keeps every (frame, environment) observation: row t * B + b of the store; the
+            # minibatches read their rows from it
+            self._keep = ([t for t in range(T) for _ in range(B)],
+                          torch.arange(B, dtype=torch.int32, device=eng.device).repeat(T),
+                          torch.arange(T * B, dtype=torch.int32, device=eng.device))
+            self.obs_mb = self.obs_all.view((T + 1) * B, N, 16)
+            return
         self._keep = (torch.div(flat[order], B, rounding_mode="floor").tolist(),        # frames, sorted
                       (flat[order] % B).to(torch.int32).pin_memory().to(eng.device, non_blocking=True),
                       order.to(torch.int32).pin_memory().to(eng.device, non_blocking=True))
@@ -393,9 +458,11 @@ class VecPPOTrainer:
         """GAE(gamma, lmbda, average_gae=True) with the current critic over all (T+1)*B observations."""
         eng = self.eng
         T, B, N = self.T, eng.B, eng.N
-        cw = self._critic()
+        cw = None if self.obs_all is not None else self._critic()
         with self.stage("critic_all_frames"):
-            if self.env_minor and B % 128 == 0:
+            if self.obs_all is not None:
+                v = self._gt_value_all_frames()
+            elif self.env_minor and B % 128 == 0:
                 v = ops.critic_forward_slabs(cw, self.counts, self.times)           # reads [frame][node][env] bytes as is
             elif self.env_minor and self.counts.dtype == torch.uint8:    # odd batch sizes: the count bytes as fp32 rows first
                 _, rows = ops.rollout_gather(eng.plan, T + 1, B, True, counts=self.counts)
@@ -415,6 +482,20 @@ class VecPPOTrainer:
             ops.advantage_normalize_(adv, stats)
         return adv, target
 
+    def _gt_value_all_frames(self):
+        """The graph-transformer critic over all (T + 1) * B stored observations, in chunks of rows -> (T + 1) * B values."""
+        eng = self.eng
+        rows = self.obs_all.view(-1, eng.N, 16)
+        chunk, fwd, _, _ = self._gtv_sizes(eng.plan, eng.B, self.T, 1)
+        if getattr(self, "_gtv_fwd_scratch", None) is None:
+            self._gtv_fwd_scratch = torch.empty(fwd // 4, dtype=torch.float32, device=eng.device)     # once per trainer
+        v = torch.empty(rows.size(0), dtype=torch.float32, device=eng.device)
+        w = self._gt_value()
+        for lo in range(0, rows.size(0), chunk):
+            hi = min(lo + chunk, rows.size(0))
+            ops.value_gt_forward(eng.plan, rows[lo:hi], self.gt_value_pe, w, out=v[lo:hi], scratch=self._gtv_fwd_scratch)
+        return v
+
     def minibatch_step(self, adv, target, idx=None):
         """One minibatch + one Adam step. ``idx`` (test hook): flat frame indices t * B + b instead of a random draw."""
         eng = self.eng
@@ -422,7 +503,10 @@ class VecPPOTrainer:
         if self.state_dep:       # the draw was made before the rollout (its observations were kept)
             idx = self._mb_idx[self._epoch]
             off = sum(i.numel() for i in self._mb_idx[:self._epoch])
-            obs = self.obs_mb[off:off + idx.numel()]
+            if self.obs_all is not None:         # rows t * B + b of the observation store (the same values)
+                obs = self.obs_mb.index_select(0, idx)
+            else:
+                obs = self.obs_mb[off:off + idx.numel()]
             self._epoch += 1
         else:
             idx = self.draw_frames(T * B, min(self.M, T * B)) if idx is None else idx.to(eng.device)
@@ -432,7 +516,8 @@ class VecPPOTrainer:
         st = self.stage
         with st("minibatch_gather"):
             if self.state_dep:
-                _, counts_mb = ops.rollout_gather(eng.plan, T, B, True, idx, counts=self.counts[:T])     # env-minor bytes
+                counts_mb = None if self.obs_all is not None else \
+                    ops.rollout_gather(eng.plan, T, B, True, idx, counts=self.counts[:T])[1]            # env-minor bytes
                 choice_mb, _ = ops.rollout_gather(eng.plan, T, B, False, idx, choice=self.choice)        # env-major bytes
             elif self.rollout == "unfused":
                 counts_mb = self.counts[:T].view(T * B, N).index_select(0, idx)
@@ -454,11 +539,15 @@ class VecPPOTrainer:
         with st("graphdist_fwd"):
             proba = ops.graphdist_softmax(eng.plan, logits, self.temperature)
             lp_new, ent = ops.graphdist_logprob_entropy(eng.plan, proba, choice=choice_mb)
-        cw = self._critic()
+        gtv = self.obs_all is not None
+        cw = self._gt_value() if gtv else self._critic()
         with st("critic_fwd"):
-            # split-K while the minibatch is far from filling the chip with 128-row MFMA tiles (M = 4 096: 32 workgroups walking
-            # all N columns alone took 743 us, bench.py's update_path; spread over the columns: see DESIGN §4.7)
-            value, h1, h2 = ops.critic_forward(cw, counts_mb, time_mb, 1, keep_hidden=True, split_k=M <= 16384)
+            if gtv:
+                value = ops.value_gt_forward(eng.plan, obs, self.gt_value_pe, cw)
+            else:
+                # split-K while the minibatch is far from filling the chip with 128-row MFMA tiles (M = 4 096: 32 workgroups
+                # walking all N columns alone took 743 us, bench.py's update_path; spread over the columns: see DESIGN §4.7)
+                value, h1, h2 = ops.critic_forward(cw, counts_mb, time_mb, 1, keep_hidden=True, split_k=M <= 16384)
         scale = 1.0 / self.world
         with st("ppo_loss"):
             out, g_lp, g_ent, g_val = ops.ppo_loss(lp_new, lp_old, adv_mb, value, tgt_mb, ent,
@@ -471,10 +560,18 @@ class VecPPOTrainer:
                                                          grad_log_prob=g_lp, grad_entropy=g_ent, log_prob_fwd=lp_new)
         with st("actor_logits_bwd"):
             self._actor_logits_bwd(obs, g_logits)
-        gw = [self.flat.grad_view(p) for p in self.critic_params]
         with st("critic_bwd"):
-            ops.critic_backward(cw, counts_mb, time_mb, 1, h1, h2, g_val,
-                                (gw[0], gw[1], gw[2], gw[3], gw[4].view(-1), gw[5]))
+            if gtv:
+                need = ops.value_gt_bwd_scratch_bytes(eng.plan, M) // 4
+                if getattr(self, "_gtv_bwd_scratch", None) is None or self._gtv_bwd_scratch.numel() < need:
+                    self._gtv_bwd_scratch = torch.empty(need, dtype=torch.float32, device=eng.device)    # once per trainer
+                ops.value_gt_backward(eng.plan, obs, self.gt_value_pe, cw, g_val,
+                                      [self.flat.grad_view(self.gt_value_params[k]) for k in ops.GT_VALUE_PARAM_KEYS],
+                                      scratch=self._gtv_bwd_scratch)
+            else:
+                gw = [self.flat.grad_view(p) for p in self.critic_params]
+                ops.critic_backward(cw, counts_mb, time_mb, 1, h1, h2, g_val,
+                                    (gw[0], gw[1], gw[2], gw[3], gw[4].view(-1), gw[5]))
         with st("grad_allreduce"):
             self.flat.allreduce_grads()               # ONE all-reduce of the fused gradient buffer (RCCL over xGMI)
         self.last_grad = self.flat.grad.clone() if getattr(self, "keep_grad", False) else None
