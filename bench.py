@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — PPO env-steps/sec (+ MPNN message-pass edges/sec) of the MPNN+PPO routing hot path on N MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-      bench.py --gpus N --steps K --warmup W
+      bench.py --gpus N --steps K --warmup W [--full]
 
 A *step* is one PPO iteration of the reference's ``ppo_train`` (src/rl/ppo_trainer.py:129-145) for every environment
 of a rank: a rollout of T frames (policy logits -> GraphDistribution sample/log_prob -> env step: choice,
@@ -29,6 +29,10 @@ kernel does, where a traffic figure comes from, the CPU sample in words — goes
                         read / write requests per launch (TCC_EA0_RDREQ / WRREQ).
   roofline_direction  — the same for k_fused_direction (DirectionMPNN.message + aggregate, the scatter kernel the
                         north star names); roofline_insert — the insert launch (latency-bound).
+A plain run stops there: it sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints the line (the three
+roofline objects come from HIP events on those timed steps). Every object below takes runs of its own and comes only with
+``--full``:
+  value_rollout_only  — the collector loop alone (rollout without the update): one warm-up, then min(K, 3) timed iterations.
   config5             — BASELINE config 5 (100k route edges, 262 144 agents) at ``--config5-envs`` environments: one or two
                         PPO iterations, its own three roofline objects, and the bf16 per-edge MLP line at that size.
   update_path         — the same iteration with ``--update-epochs`` x ``--update-sub-batch`` (the update at a size where
@@ -114,18 +118,20 @@ def parse():
                     help="seconds after the episode start within which ALL agents depart (0 = the whole 61-minute episode, "
                          "BASELINE's workload; e.g. 600 = the congested regime: the network fills up inside the rollout)")
     ap.add_argument("--congested-window", type=int, default=600,
-                    help="also time --congested-steps iterations with every agent departing within this many seconds "
-                         "(0 = skip); reported under congested_regime")
+                    help="--full: also time --congested-steps iterations with every agent departing within this many "
+                         "seconds (0 = skip); reported under congested_regime")
     ap.add_argument("--congested-steps", type=int, default=2)
     ap.add_argument("--update-epochs", type=int, default=8,
-                    help="update_path object: epochs per iteration (0 = skip); with --update-sub-batch frames per minibatch")
+                    help="--full: update_path object, epochs per iteration (0 = skip); with --update-sub-batch frames per "
+                         "minibatch")
     ap.add_argument("--update-sub-batch", type=int, default=4096)
     ap.add_argument("--update-steps", type=int, default=2)
     ap.add_argument("--config5-envs", type=int, default=2048,
-                    help="environments per GPU of the config5 object (BASELINE config 5: 100k edges, 262 144 agents; 0 = skip)")
+                    help="--full: environments per GPU of the config5 object (BASELINE config 5: 100k edges, 262 144 agents; "
+                         "0 = skip)")
     ap.add_argument("--config5-steps", type=int, default=2)
     ap.add_argument("--policy-envs", type=int, default=4096,
-                    help="environments per GPU of the state-dependent-policy lines (policy_head=edge_mlp; 0 = skip)")
+                    help="--full: environments per GPU of the state-dependent-policy lines (policy_head=edge_mlp; 0 = skip)")
     ap.add_argument("--policy-steps", type=int, default=2)
     ap.add_argument("--policy-temperature", type=float, default=2000.0,
                     help="GraphDistribution temperature of the state-dependent-policy lines: the head reads raw features "
@@ -134,11 +140,14 @@ def parse():
     ap.add_argument("--metrics-envs", type=int, default=1,
                     help="environments that keep the per-node logs of SimulatorEnv._step (delta_travel_time, pop / withdraw "
                          "masks); the per-frame leg histogram is kept for all of them")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="do not bracket the frame kernels with HIP events (PMC / kernel-trace passes)")
     ap.add_argument("--details", type=str, default=os.path.join("gpurun_out", "bench_details.json"),
                     help="sidecar file with every descriptive field (relative to the repo root; '' = stderr only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure value_rollout_only, update_path, congested_regime, config5, "
+                         "state_dependent_policy and cpu_baseline (a plain run only times the --steps iterations)")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed PPO iteration computed as DIR/<name>.npy "
                          "(float32; a fixed, seeded sample of the larger arrays; rank 0's outputs)")
@@ -634,12 +643,19 @@ def main():
     # data-parallel evidence (outside the timed region): after `steps` averaged-gradient Adam steps every replica must still
     # hold rank 0's parameter bits
     replica_diff = dist_utils.replica_max_abs_diff(trainer.flat.flat)
+    # the measurements from here to the line's assembly run with --full only: the headline figure needs none of them
     # rollout-only figure (BASELINE.md §3 / SURVEY §8d: "rollout + update, and rollout-only"): the collector loop alone
-    ro_frames, ro_elapsed, _, _ = time_iterations(trainer, min(args.steps, 3), L, T, False, device, run=trainer.collect)
+    ro_frames = ro_elapsed = None
+    if args.full:
+        # a warm-up of its own: --dump-outputs and the host work since the timed steps leave the device idle, and at a small
+        # --envs the first collect after that idle time runs far below the steady rate
+        trainer.collect()
+        ro_frames, ro_elapsed, _, _ = time_iterations(trainer, min(args.steps, 3), L, T, False, device, run=trainer.collect)
 
     # ---- the update at a size where its kernels exist -----------------------------------------------------------------------------
     upd = upd_detail = None
-    if args.update_epochs > 0 and not args.departure_window and world == 1:      # (N = 1 only: a multi-rank run times the headline)
+    # (N = 1 only: a multi-rank run times the headline)
+    if args.full and args.update_epochs > 0 and not args.departure_window and world == 1:
         upd, upd_detail = update_path(args, trainer, engine, world, L, T, device)
 
     # ---- the congested regime: every agent departs within --congested-window seconds -----------------------------------------------
@@ -647,7 +663,7 @@ def main():
     # a filling network. Here the FIFOs fill up, most rows pop / withdraw / enqueue in every frame. Same engine, same kernels,
     # populations re-drawn and re-packed.
     congested = cong_detail = None
-    if args.congested_window > 0 and not args.departure_window:
+    if args.full and args.congested_window > 0 and not args.departure_window:
         from tarl_hip import synth
         engine.agents.copy_(synth.population_batch(args.agents, engine.N, B, seed=args.seed + 1000 * rank + 17,
                                                    device=device, t1=synth.EPISODE_START + args.congested_window))
@@ -673,7 +689,7 @@ def main():
 
     # ---- BASELINE config 5: 100k route edges, 262 144 agents ("HBM-bound scatter stress") --------------------------------------------
     c5 = c5_detail = None
-    if args.config5_envs > 0 and world == 1 and not args.departure_window and (E, args.agents) == (10000, 16384):
+    if args.full and args.config5_envs > 0 and world == 1 and not args.departure_window and (E, args.agents) == (10000, 16384):
         from tarl_hip import synth
         B5, A5 = args.config5_envs, 262144
         net5 = synth.torus_network(25, 250)
@@ -706,7 +722,7 @@ def main():
 
     # ---- the state-dependent policy at config 4 -------------------------------------------------------------------------------------
     pol = pol_detail = None
-    if args.policy_envs > 0:
+    if args.full and args.policy_envs > 0:
         # "fp32": rollout logits on the fp32 matrix pipe (exact fp32 products); "fp32_x3": the same 1e-4 contract on the bf16
         # pipe — operands split into exact bf16 pieces, k_edge_mlp_fwd_x3 (the trainer's default for an fp32 policy);
         # "bf16": bf16 logits on bf16 observations (BASELINE config 5's "bf16 MPNN features")
@@ -734,15 +750,17 @@ def main():
             "replica_param_max_abs_diff": replica_diff,
         }
         out = dict(head, **rl)
-        out["config5"], out["update_path"], out["congested_regime"], out["state_dependent_policy"] = c5, upd, congested, pol
-        out["value_rollout_only"] = ro_frames * world / ro_elapsed if ro_elapsed > 0 else None
         details = dict(head, **rd)
-        details.update(config5=c5_detail, update_path=upd_detail, congested_regime=cong_detail, state_dependent_policy=pol_detail,
-                       value_rollout_only=out["value_rollout_only"], layout=layout_tag,
+        if args.full:
+            out["config5"], out["update_path"], out["congested_regime"], out["state_dependent_policy"] = c5, upd, congested, pol
+            out["value_rollout_only"] = ro_frames * world / ro_elapsed if ro_elapsed > 0 else None
+            details.update(config5=c5_detail, update_path=upd_detail, congested_regime=cong_detail,
+                           state_dependent_policy=pol_detail, value_rollout_only=out["value_rollout_only"])
+        details.update(layout=layout_tag,
                        env_steps_per_step=B * T, msgpass_edges_per_sec=value * E, epochs=args.epochs, sub_batch=args.sub_batch,
                        roads=n_roads, setup_seconds=setup_s,
                        parallelism=f"dp{world}: rollouts sharded, one gradient all-reduce per optimiser step")
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             cb = cpu_baseline(args, net)
             details["cpu_baseline"] = cb
             out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample", "value_rollout_only",

@@ -1,4 +1,5 @@
-"""GPU: bench.py's one JSON line carries the contract's keys, and the roofline objects are fractions of peak.
+"""GPU: bench.py's one JSON line carries the contract's keys, and the roofline objects are fractions of peak; a plain run
+(without --full) carries the headline alone.
 (A reduced size and a short CPU sample keep this quick; the driver's run uses the defaults.)"""
 import json
 import os
@@ -15,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_line_contract(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     det = os.path.join("gpurun_out", "bench_details_contract_test.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                           "--envs", "512", "--cpu-seconds", "1", "--congested-steps", "1", "--policy-envs", "128",
                           "--policy-steps", "1", "--update-epochs", "2", "--update-sub-batch", "256", "--update-steps", "1",
                           "--config5-envs", "0", "--details", det, "--dump-outputs", str(tmp_path / "dump")],
@@ -77,6 +78,28 @@ def test_bench_line_contract(tmp_path):
     assert sum(a.nbytes for a in dump.values()) <= 64 << 20
     assert dump["reward"].size == dump["log_prob"].size == 256 * 512 and dump["counts"].size == dump["state"].size == 1 << 20
     assert dump["losses"].size == 6 and (dump["reward"] <= 0).all()
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """Without --full the bench sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline
+    and its three roofline objects (HIP events on the timed steps), none of the objects that take runs of their own."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--envs", "512", "--details", "", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k, v in (("metric", "ppo_env_steps_per_sec"), ("unit", "env-steps/s"), ("n_gpus", 1), ("steps", 2), ("warmup", 1),
+                 ("higher_is_better", True), ("dtype", "f32")):
+        assert d[k] == v, (k, d[k])
+    assert abs(d["value"] - 512 * 256 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-4
+    assert {"roofline", "roofline_direction", "roofline_insert", "msgpass_pair_edges_per_sec"} <= set(d)
+    assert not set(d) & {"config5", "update_path", "congested_regime", "state_dependent_policy", "value_rollout_only",
+                         "cpu_baseline"}
+    assert {p.stem for p in (tmp_path / "dump").iterdir()} == {"params", "losses", "reward", "log_prob", "log_prob_infeasible",
+                                                               "values", "times", "counts", "choice", "leg", "state", "agents"}
 
 
 def test_bench_starts_its_own_ranks():

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 REPS=2
 if [ "$1" = "-r" ]; then REPS=$2; shift 2; fi
 TREE=${1:-tmp_ab/prev_tree}
-Q="--steps 2 --warmup 1 --cpu-seconds 0 --policy-envs 0 --config5-envs 0 --congested-window 0 --update-steps 2"
+Q="--steps 2 --warmup 1 --full --cpu-seconds 0 --policy-envs 0 --config5-envs 0 --congested-window 0 --update-steps 2"
 show() { python3 -c "
 import json,sys
 d=json.load(open(sys.argv[1])); u=d['update_path']

@@ -11,7 +11,7 @@ SETS=("SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY"
 i=0
 for s in "${SETS[@]}"; do
   i=$((i + 1))
-  rocprofv3 --pmc $s --kernel-trace --output-format csv -d $O/p$i -o run -- python3 bench.py --steps 1 --warmup 0 --cpu-seconds 0 --policy-envs 0 --config5-envs 0 --congested-window 0 --update-steps 1 --update-epochs 2 --no-kernel-timing --details '' > $O/p$i.log 2>&1 || { echo "pass $i FAILED"; tail -5 $O/p$i.log; exit 1; }
+  rocprofv3 --pmc $s --kernel-trace --output-format csv -d $O/p$i -o run -- python3 bench.py --steps 1 --warmup 0 --full --cpu-seconds 0 --policy-envs 0 --config5-envs 0 --congested-window 0 --update-steps 1 --update-epochs 2 --no-kernel-timing --details '' > $O/p$i.log 2>&1 || { echo "pass $i FAILED"; tail -5 $O/p$i.log; exit 1; }
   rm -f $O/p$i/run_kernel_trace.csv
 done
 python3 tools/pmc_reduce.py $O/p* --last 2 --kernels k_critic_fwd_slab_u8x3 | tee $O/counters.txt

@@ -25,9 +25,9 @@ if [[ $PARTS == *stats* ]]; then
     if ! eval rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -o run -- python3 bench.py $OFF --no-kernel-timing "$@" > $O/prof_$name.log 2>&1; then
       echo "[r05_final] kernel trace $name FAILED"; tail -3 $O/prof_$name.log; rc=1; fi
   done
-  if ! rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_policy -o run -- python3 bench.py --cpu-seconds 0 --congested-window 0 --config5-envs 0 --update-epochs 0 --details '' --steps 1 --policy-steps 2 --no-kernel-timing > $O/prof_policy.log 2>&1; then
+  if ! rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_policy -o run -- python3 bench.py --full --cpu-seconds 0 --congested-window 0 --config5-envs 0 --update-epochs 0 --details '' --steps 1 --policy-steps 2 --no-kernel-timing > $O/prof_policy.log 2>&1; then
     echo "[r05_final] kernel trace policy FAILED"; rc=1; fi
-  if ! rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_update -o run -- python3 bench.py --cpu-seconds 0 --congested-window 0 --config5-envs 0 --policy-envs 0 --details '' --steps 1 --no-kernel-timing > $O/prof_update.log 2>&1; then
+  if ! rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_update -o run -- python3 bench.py --full --cpu-seconds 0 --congested-window 0 --config5-envs 0 --policy-envs 0 --details '' --steps 1 --no-kernel-timing > $O/prof_update.log 2>&1; then
     echo "[r05_final] kernel trace update FAILED"; rc=1; fi
   rm -f $O/*/run_kernel_trace.csv
   echo "[r05_final] kernel stats done"
@@ -52,7 +52,7 @@ fi
 if [[ $PARTS == *bench* ]]; then
   # 4. the default bench line last, against the traffic records just measured (copied into this run's profiles/)
   for f in pmc_traffic pmc_traffic_congested pmc_traffic_c5; do [ -s $O/pmc/$f.json ] && cp $O/pmc/$f.json profiles/r05_$f.json; done
-  run bench_default python bench.py --details $O/bench_default_details.json
+  run bench_default python bench.py --full --details $O/bench_default_details.json
   python tools/bench_brief.py < $O/bench_default.json.log | sed "s/^/default /"
 fi
 ls $O
