@@ -727,6 +727,34 @@ int tarl_msa_assign_sssp(const tarl_plan* plan, const double* weights, const int
                          const int64_t* od_ptr, const int64_t* od_dest, const double* od_volume, const uint8_t* is_road,
                          void* scratch, int64_t scratch_bytes, double* aux_flow, tarl_stream stream);
 
+/* ---- per-destination shortest-path trees (the dijkstra agent on large graphs) ------------------------------------------------
+ * DijkstraAgents.choice (src/agents/base.py:519-584) only reads next_hop[u][dest] for the destination of each row's head
+ * agent: one reverse shortest-path tree per distinct destination replaces the N x N table of tarl_apsp (csrc/dest_trees.hip).
+ * tarl_dest_trees == nx.all_pairs_dijkstra_path + the next-hop extraction of src/agents/base.py:556-570, restricted to
+ *   the columns dests[0 .. num_dests):
+ *   weights: fp32 [E] in ORIGINAL edge order (what tarl_edge_travel_time writes), non-negative (+inf allowed).
+ *   dist_out float64 [num_dests][N]: dist[j][u] = the minimum over paths u -> dests[j] of the fp64 sum w1 + (w2 + (...));
+ *   0 at the destination, +inf when unreachable. networkx sums left to right from u; both orders are exact, and the
+ *   distances equal networkx's bit for bit, while on every path the exponent span of the weights (in bits) plus
+ *   ceil(log2 hops) stays at or below 28.
+ *   next_hop_out int32 [num_dests][N]: the successor of u on a TIGHT out-edge (fl(w(u,v) + dist[v]) == dist[u]); tie rule:
+ *   the fewest hops to the destination over tight edges, then the smallest successor id. The destination itself holds
+ *   its own id, unreachable nodes -1 (tarl_apsp's conventions). Either output may be NULL, not both.
+ *   scratch: tarl_dest_trees_scratch_bytes(plan, num_dests) bytes of device memory (O(min(num_dests, 1024) x N)); -1 on a
+ *   bad argument. Graphs up to N = 327 680 nodes (the LDS bitmaps). dests int64 [num_dests] live on the device: an
+ *   out-of-range id writes nothing for its slot.
+ * tarl_select_next_hop_dest == src/agents/base.py:572-580 on that table: SELECTED_ROAD[i] =
+ *   next_hop[dest_slot[DESTINATION[head agent of i]]][i] for every row i, with tarl_select_next_hop's rules (rows with an
+ *   empty FIFO read agent 0; an out-of-range head or destination leaves the row untouched). dest_slot int32 [num_nodes]:
+ *   the row of next_hop [num_dests][num_nodes] holding each destination's tree, -1 = none (the row is left untouched).
+ *   One table is shared by the B environments. */
+int64_t tarl_dest_trees_scratch_bytes(const tarl_plan* plan, int64_t num_dests);
+int tarl_dest_trees(const tarl_plan* plan, const float* weights, const int64_t* dests, int64_t num_dests, void* scratch,
+                    int64_t scratch_bytes, int32_t* next_hop_out, double* dist_out, tarl_stream stream);
+int tarl_select_next_hop_dest(float* x, int64_t B, int64_t x_bstride, int64_t ldx, int32_t Nmax, int64_t num_nodes,
+                              const float* agent_features, int64_t num_agents, int64_t a_bstride, const int32_t* dest_slot,
+                              const int32_t* next_hop, int64_t num_dests, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

@@ -1,7 +1,7 @@
 """Command line of the MI355X build. The flag set is the reference CLI's contract (main.py of the reference: --algo,
 --scenario, --mode, --timestep_size, --start-end-time, --epochs, --rollout-steps, --seed, --device, --output-dir,
 --profile, --torch-compile) plus ``--steps`` (used by the reference's README but missing from its parser) and
-``--num-envs`` (vectorised environments per GPU), ``--policy-head`` and ``--value-head``."""
+``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head`` and ``--dijkstra-method``."""
 import argparse
 import os
 import sys
@@ -11,6 +11,7 @@ import sys
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from src.agents.base import DijkstraAgents  # noqa: E402
 from src.runner import Runner, RunnerArgs  # noqa: E402
 
 ALGOS = ("dijkstra", "random", "mpnn", "mpnn+ppo")
@@ -44,6 +45,10 @@ OPTIONS = (
                                 "BatchNorm, Laplacian positional encoding)")),
     ("--prior-weight", dict(type=float, default=1.0,
                             help="embedding_dijkstra: weight of the shortest-path prior (1.0 = the reference's plain sum)")),
+    ("--dijkstra-method", dict(choices=DijkstraAgents.METHODS, default="all_pairs",
+                               help="dijkstra: next-hop table from all-pairs shortest paths (N x N), or one reverse "
+                                    "shortest-path tree per distinct agent destination ([D][N], for large networks), or "
+                                    "auto: all_pairs up to 4 096 nodes, per_destination above")),
     ("--value-head", dict(choices=("simple", "graph_transformer"), default="simple",
                           help="mpnn+ppo critic: the reference runner's MPNNValueNetSimple (per-road counts and the clock), "
                                "or graph_transformer: the reference's ValueNet, a second GraphTransformerNet on the policy's "

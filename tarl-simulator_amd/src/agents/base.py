@@ -12,6 +12,7 @@ import os
 import torch
 
 from .._compat import cached_plan, cached_routing_plan, require_cuda
+from ..algorithms.user_equilibrium_msa import ALL_PAIRS_MAX_NODES
 from ..feature_helpers import AgentFeatureHelpers, FeatureHelpers
 
 
@@ -114,26 +115,75 @@ class Agents(AgentFeatureHelpers):
 
 
 class DijkstraAgents(Agents):
-    """Shortest-path routing (reference: src/agents/base.py:519-584): every ``refresh_rate`` calls the all-pairs next-hop
-    table is rebuilt from the current travel times, and every row selects the next hop towards its head agent's
-    destination. The table comes from ``tarl_apsp`` — one wave per source node, networkx's tie order — instead of
-    ``nx.all_pairs_dijkstra_path`` on the host."""
+    """Shortest-path routing (reference: src/agents/base.py:519-584): every ``refresh_rate`` calls the next-hop table is
+    rebuilt from the current travel times, and every row selects the next hop towards its head agent's destination.
 
-    def __init__(self, device):
+    ``method`` picks the table:
+
+    * ``"all_pairs"`` (default): the N x N table of ``tarl_apsp`` — one wave per source node, networkx's tie order —
+      instead of ``nx.all_pairs_dijkstra_path`` on the host, kept in ``next_hop_tensor``.
+    * ``"per_destination"``: one reverse shortest-path tree per distinct DESTINATION of the agent table
+      (``tarl_dest_trees``): O(E) work per tree and a [D][N] int32 table in ``dest_next_hop`` (row ``dest_slot[d]`` leads
+      to ``d``); ``next_hop_tensor`` stays None. Ties go to the fewest hops, then the smallest next node: the same routes
+      as all_pairs wherever the shortest path is unique.
+    * ``"auto"``: all_pairs up to ``ALL_PAIRS_MAX_NODES`` nodes, per_destination above.
+    """
+
+    METHODS = ("all_pairs", "per_destination", "auto")
+
+    def __init__(self, device, method: str = "all_pairs"):
         super().__init__(device)
+        if method not in self.METHODS:
+            raise ValueError(f"method must be one of {self.METHODS}, got {method!r}")
+        self.method = method
         self.count = 0
         self.refresh_rate = 10
         self.next_hop_tensor = None
+        self.dest_next_hop = None      # per_destination: int32 [D][N]
+        self.destinations = None       # per_destination: int64 [D], the tree roots
+        self.dest_slot = None          # per_destination: int32 [N], row of dest_next_hop per destination, -1 = none
+        self._dest_table = None        # the agent table the destination set was built from
+        self._weights = None           # per_destination: the travel times of the last refresh
+
+    def resolve_method(self, num_nodes: int) -> str:
+        if self.method != "auto":
+            return self.method
+        return "all_pairs" if num_nodes <= ALL_PAIRS_MAX_NODES else "per_destination"
+
+    def _build_destinations(self, num_nodes: int):
+        """Every distinct DESTINATION of the agent table, dummy row 0 included (empty rows read agent 0)."""
+        d = torch.unique(self.agent_features[..., self.DESTINATION].reshape(-1).to(torch.int64))
+        d = d[(d >= 0) & (d < num_nodes)].contiguous()
+        slot = torch.full((num_nodes,), -1, dtype=torch.int32, device=d.device)
+        slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=d.device)
+        if self._dest_table is None:
+            print(f"Dijkstra routing: per-destination trees ({d.numel()} destinations, {num_nodes} nodes)")
+        self.destinations, self.dest_slot, self._dest_table = d, slot, self.agent_features
 
     @torch.no_grad()
     def choice(self, graph, h: FeatureHelpers):
         from tarl_hip import ops
         x = graph.x
         require_cuda(x, "graph.x")
-        if self.count % self.refresh_rate == 0:
-            plan = cached_plan(graph.edge_index, x.size(0))
-            w = ops.edge_travel_time(plan, x, h.Nmax, graph.congestion_constant)
-            self.next_hop_tensor = ops.all_pairs_shortest_paths(plan, w)[0][0]
-        ops.select_next_hop(x, h.Nmax, self.agent_features, self.next_hop_tensor)
+        N = x.size(-2)
+        method = self.resolve_method(N)
+        refresh = self.count % self.refresh_rate == 0
+        stale = method == "per_destination" and self._dest_table is not self.agent_features
+        if refresh or stale:
+            plan = cached_plan(graph.edge_index, N)
+            if refresh:
+                w = ops.edge_travel_time(plan, x, h.Nmax, graph.congestion_constant)
+                if method == "all_pairs":
+                    self.next_hop_tensor = ops.all_pairs_shortest_paths(plan, w)[0][0]
+                else:
+                    self._weights = w[0].contiguous()       # environment 0's weights, as the all-pairs table's [0]
+            if method == "per_destination":
+                if stale:                                   # a replaced agent table: new roots, the same weights
+                    self._build_destinations(N)
+                self.dest_next_hop = ops.destination_trees(plan, self._weights, self.destinations)[0]
+        if method == "all_pairs":
+            ops.select_next_hop(x, h.Nmax, self.agent_features, self.next_hop_tensor)
+        else:
+            ops.select_next_hop_dest(x, h.Nmax, self.agent_features, self.dest_slot, self.dest_next_hop)
         self.count += 1
         return graph

@@ -1,6 +1,6 @@
 """Runner / RunnerArgs — CLI-facing orchestration (reference: src/runner.py). ``mpnn`` and ``mpnn+ppo`` run on the HIP
 path; ``random`` and ``dijkstra`` run the classical loop on the same kernels (``dijkstra``: all-pairs next-hop table by
-``tarl_apsp`` instead of networkx)."""
+``tarl_apsp`` instead of networkx, or per-destination trees by ``tarl_dest_trees``, ``dijkstra_method``)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -28,8 +28,12 @@ class RunnerArgs:
     policy_head: str = "embedding"
     prior_weight: float = 1.0      # policy_head "embedding_dijkstra": weight of the shortest-path prior
     value_head: str = "simple"     # "graph_transformer": ValueNet (src/agents/transformer_agent.py)
+    dijkstra_method: str = "all_pairs"   # DijkstraAgents: "all_pairs", "per_destination" or "auto"
 
     def __post_init__(self):
+        from .agents.base import DijkstraAgents
+        if self.dijkstra_method not in DijkstraAgents.METHODS:
+            raise ValueError(f"dijkstra_method must be one of {DijkstraAgents.METHODS}, got {self.dijkstra_method!r}")
         if self.value_head not in ("simple", "graph_transformer"):
             raise ValueError("value_head must be 'simple' or 'graph_transformer'")
         if self.value_head == "graph_transformer" and self.policy_head == "embedding":
@@ -78,7 +82,11 @@ class Runner:
         if a.algo in {"dijkstra", "random"}:
             self.simulator = TransportationSimulator(str(self.device), torch_compile=a.torch_compile)
             self.simulator.load_network(scenario=a.scenario)
-            self.agent = self.simulator.agent = (DijkstraAgents if a.algo == "dijkstra" else Agents)(str(self.device))
+            if a.algo == "dijkstra":
+                self.agent = DijkstraAgents(str(self.device), method=a.dijkstra_method)
+            else:
+                self.agent = Agents(str(self.device))
+            self.simulator.agent = self.agent
             self.agent.load(scenario=a.scenario)
             self.simulator.config_parameters(timestep_size=a.timestep_size, start_time=a.start_end_time[0])
             self.agent.set_time(a.start_end_time[0])

@@ -317,6 +317,49 @@ def select_next_hop(x, Nmax, agent_features, next_hop):
                                       nh.data_ptr(), 0 if nh.size(0) == 1 else N * N, _lib.current_stream()))
 
 
+def destination_trees(plan: Plan, weights, dests, *, want_next_hop=True, want_dist=False):
+    """One reverse shortest-path tree per destination (tarl_dest_trees): ``weights`` (E,) fp32 in original edge order
+    (what :func:`edge_travel_time` writes), ``dests`` (D,) int64 -> (next_hop int32 (D, N) | None, dist float64 (D, N) |
+    None). dist[j, u] is the fp64 sum w1 + (w2 + (...)) of the shortest path u -> dests[j] (+inf: unreachable);
+    next_hop[j, u] = the successor of u on a tight out-edge, the fewest tight hops to the destination first, then the
+    smallest id (the destination itself on its own column, -1: unreachable). Rows of out-of-range destinations are left
+    as allocated (uninitialised)."""
+    if not (want_next_hop or want_dist):
+        raise ValueError("no output requested")
+    _contig(weights, torch.float32, "weights")
+    _contig(dests, torch.int64, "dests")
+    if weights.dim() != 1 or weights.numel() != plan.num_edges:
+        raise ValueError(f"weights must be ({plan.num_edges},) float32 in original edge order, got {tuple(weights.shape)}")
+    if dests.dim() != 1:
+        raise ValueError("dests must be 1-D")
+    L = _lib.load()
+    D, N = dests.numel(), plan.num_nodes
+    need = int(L.tarl_dest_trees_scratch_bytes(plan.handle, D))
+    scratch = torch.empty(need, dtype=torch.uint8, device=weights.device) if need > 0 else None
+    nh = torch.empty((D, N), dtype=torch.int32, device=weights.device) if want_next_hop else None
+    d = torch.empty((D, N), dtype=torch.float64, device=weights.device) if want_dist else None
+    _lib.check(L.tarl_dest_trees(plan.handle, weights.data_ptr(), dests.data_ptr(), D, _lib.ptr(scratch), need,
+                                 _lib.ptr(nh), _lib.ptr(d), _lib.current_stream()))
+    return nh, d
+
+
+def select_next_hop_dest(x, Nmax, agent_features, dest_slot, next_hop):
+    """x[b, i, SELECTED_ROAD] = next_hop[dest_slot[DESTINATION[head agent of i]], i] (tarl_select_next_hop_dest): the
+    (D, N) int32 table of :func:`destination_trees`, shared by the environments; ``dest_slot`` (N,) int32 is the table
+    row of each destination, -1 = no tree (the row keeps its selection)."""
+    L = _lib.load()
+    B, N, bs, ldx = _state(x, Nmax)
+    A, abs_ = _agents(agent_features, B)
+    _contig(dest_slot, torch.int32, "dest_slot")
+    _contig(next_hop, torch.int32, "next_hop")
+    if dest_slot.dim() != 1 or dest_slot.numel() != N or next_hop.dim() != 2 or next_hop.size(1) != N:
+        raise ValueError(f"dest_slot must be ({N},) and next_hop (D, {N}), got {tuple(dest_slot.shape)} and "
+                         f"{tuple(next_hop.shape)}")
+    _lib.check(L.tarl_select_next_hop_dest(x.data_ptr(), B, bs, ldx, Nmax, N, agent_features.data_ptr(), A, abs_,
+                                           dest_slot.data_ptr(), next_hop.data_ptr(), next_hop.size(0),
+                                           _lib.current_stream()))
+
+
 def reset_state(x, Nmax, agent_features=None):
     L = _lib.load()
     B, N, bs, ldx = _state(x, Nmax)
