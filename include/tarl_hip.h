@@ -587,6 +587,42 @@ int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t
                              const int32_t* keep_slot, float* obs_keep, float* logits_scratch, void* dist_scratch,
                              int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
                              tarl_stream stream);
+/* ---- the same prior from a per-destination table (MPNNPolicyNet.prior_method = "per_destination") -------------------------
+ * The prior only reads dist[v][dest] for destinations some agent has: the N x N table of tarl_apsp is replaced by a
+ * candidate-major [N][num_dests] fp32 table with one column per destination (csrc/dest_trees.hip, csrc/prior.hip).
+ * tarl_prior_dest_table: table[u][j] = the fp32 rounding of tarl_dest_trees' fp64 distance u -> dests[j] (the distance
+ *   phase alone: no next hops, no fp64 [num_dests][N] output); +inf where unreachable, 0 at the destination itself, a column
+ *   of +inf for an out-of-range dests[j]. weights fp32 [E] in original edge order (the free-flow weights for the prior),
+ *   dests int64 [num_dests] on the device. Where tarl_dest_trees' 28-bit condition holds on every path, each column equals
+ *   tarl_apsp's dist[:, dests[j]] bit for bit. scratch: tarl_prior_dest_table_scratch_bytes(plan, num_dests) bytes of
+ *   device memory (O(min(num_dests, 1024) x N)); -1 on a bad argument. Graphs up to N = 655 360 nodes.
+ * tarl_policy_prior_logits_dest / tarl_fused_prior_logits_dest / tarl_fused_rollout_prior_dest: tarl_policy_prior_logits /
+ *   tarl_fused_prior_logits / tarl_fused_rollout_prior with dist[v][dest] read as table[v][dest_slot[dest]]. table fp32
+ *   [N][num_dests] (num_dests >= 1), dest_slot int32 [N]: the column of each destination, -1 = none. A destination outside
+ *   [0, N), or one whose slot is -1 or outside [0, num_dests), is unreachable: its candidates get the sentinel -1e20, as
+ *   an unreachable pair does. Every other argument, rule and output as the all-pairs entry points; on the same distances
+ *   the logits, draws, log-probs and frames are bit-identical. */
+int64_t tarl_prior_dest_table_scratch_bytes(const tarl_plan* plan, int64_t num_dests);
+int tarl_prior_dest_table(const tarl_plan* plan, const float* weights, const int64_t* dests, int64_t num_dests,
+                          void* scratch, int64_t scratch_bytes, float* table, tarl_stream stream);
+int tarl_policy_prior_logits_dest(const tarl_plan* plan, const float* obs16, int64_t M, const float* emb,
+                                  int64_t num_embeddings, const float* table, int64_t num_dests, const int32_t* dest_slot,
+                                  float prior_weight, float* logits, tarl_stream stream);
+int tarl_fused_prior_logits_dest(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B, int64_t x_bstride,
+                                 int64_t ldx, int32_t Nmax, const float* agent_features, int64_t num_agents,
+                                 int64_t a_bstride, const float* emb, int64_t num_embeddings, const float* table,
+                                 int64_t num_dests, const int32_t* dest_slot, float prior_weight, float* logits,
+                                 tarl_stream stream);
+int tarl_fused_rollout_prior_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                  const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
+                                  float* agent_features, int64_t num_agents, int64_t a_bstride, const float* edge_attr,
+                                  const float* log_edge_attr, float log_eps, int use_cong, const float* emb,
+                                  int64_t num_embeddings, const float* table, int64_t num_dests, const int32_t* dest_slot,
+                                  float prior_weight, float temperature, uint64_t policy_seed, uint64_t policy_counter0,
+                                  uint64_t seed, uint64_t counter0, const int64_t* keep_ptr_host, const int32_t* keep_env,
+                                  const int32_t* keep_slot, float* obs_keep, float* logits_scratch, void* dist_scratch,
+                                  int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                                  tarl_stream stream);
 /* ---- the graph-transformer head of MPNNPolicyNet (policy_head = "graph_transformer"; csrc/gt_policy.hip) ------------------
  * The edge output (raw=True) of GraphTransformerNet (src/transformer/model.py:140-178) as MLAgents builds it
  * (src/agents/transformer_agent.py:30-39: hidden 16, 4 heads, gate=True, 2 GTConv layers; node input 16 = obs16), in

@@ -21,6 +21,10 @@
 // weights (largest over smallest, in bits) plus ceil(log2 hops) stays at or below 28 (24-bit fp32 significands in a 53-bit
 // fp64 one). Beyond that only the last bit may differ, and with it the tie choice.
 // Scratch is O(workgroups x N), never O(destinations x N).
+//
+// k_prior_dest_table runs phase 1 alone for the shortest-path prior head (prior.hip) and writes the fp32 rounding of each
+// distance straight into the destination's column of a candidate-major [N][D] table: no next hops, no fp64 [D][N] output.
+// The column stores are scattered (stride 4 D bytes); they cost little next to the relaxation rounds.
 #include "tarl_common.h"
 
 #define DT_BLOCK 256
@@ -30,6 +34,74 @@
 static inline int64_t dt_row_bytes(int64_t N) { return (12 * N + 255) / 256 * 256; }
 
 __device__ __forceinline__ bool dt_bit(const uint32_t* bm, int32_t v) { return (bm[v >> 5] >> (v & 31)) & 1u; }
+
+// ---- phase 1, shared by k_dest_trees and k_prior_dest_table ------------------------------------------------------------
+// dist [N] (the workgroup's scratch row) <- the fp64 distances of every node to d; F and C are W-word LDS bitmaps (C is left
+// all zero). With VISITED, V is cleared and gets {d}. Ends on a barrier.
+template <bool VISITED>
+__device__ __forceinline__ void dt_distances(const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
+                                             const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
+                                             const int32_t* __restrict__ out_eid, const float* __restrict__ w, int64_t N,
+                                             int32_t d, double* dist, uint32_t* F, uint32_t* C, uint32_t* V) {
+  const int tid = threadIdx.x;
+  const int32_t W = (int32_t)((N + 31) >> 5);
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  for (int64_t v = tid; v < N; v += DT_BLOCK) dist[v] = INF;
+  for (int32_t i = tid; i < W; i += DT_BLOCK) {
+    F[i] = 0u;
+    C[i] = 0u;
+    if (VISITED) V[i] = 0u;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    dist[d] = 0.0;
+    F[d >> 5] = 1u << (d & 31);
+    if (VISITED) V[d >> 5] = 1u << (d & 31);
+  }
+  __syncthreads();
+
+  // at most N rounds: only reachable with negative weights, which the contract excludes
+  for (int64_t round = 0; round < N; ++round) {
+    for (int32_t i = tid; i < W; i += DT_BLOCK) {
+      uint32_t m = F[i];
+      while (m) {
+        const int32_t v = (i << 5) + __builtin_ctz(m);
+        m &= m - 1u;
+        const int32_t k1 = in_ptr[v + 1];
+        for (int32_t k = in_ptr[v]; k < k1; ++k) {
+          const int32_t u = in_src[k];
+          atomicOr(&C[u >> 5], 1u << (u & 31));
+        }
+      }
+    }
+    __syncthreads();
+    int any = 0;
+    for (int32_t i = tid; i < W; i += DT_BLOCK) {
+      uint32_t c = C[i];
+      uint32_t nf = 0u;
+      if (c) C[i] = 0u;
+      while (c) {
+        const int b = __builtin_ctz(c);
+        c &= c - 1u;
+        const int32_t u = (i << 5) + b;
+        const double old = dist[u];
+        double best = old;
+        const int32_t k1 = out_ptr[u + 1];
+        for (int32_t k = out_ptr[u]; k < k1; ++k) {
+          const double du = (double)w[out_eid[k]] + dist[out_dst[k]];
+          if (du < best) best = du;
+        }
+        if (best < old) {
+          dist[u] = best;
+          nf |= 1u << b;
+        }
+      }
+      F[i] = nf;
+      any |= (nf != 0u);
+    }
+    if (!__syncthreads_or(any)) break;
+  }
+}
 
 __global__ __launch_bounds__(DT_BLOCK) void k_dest_trees(
     const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src, const int32_t* __restrict__ out_ptr,
@@ -51,61 +123,9 @@ __global__ __launch_bounds__(DT_BLOCK) void k_dest_trees(
     const int64_t d64 = dests[j];
     if (d64 < 0 || d64 >= N) continue;      // uniform: an out-of-range destination writes nothing
     const int32_t d = (int32_t)d64;
-    for (int64_t v = tid; v < N; v += DT_BLOCK) dist[v] = INF;
-    for (int32_t i = tid; i < W; i += DT_BLOCK) {
-      F[i] = 0u;
-      C[i] = 0u;
-      V[i] = 0u;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      dist[d] = 0.0;
-      F[d >> 5] = 1u << (d & 31);
-      V[d >> 5] = 1u << (d & 31);
-    }
-    __syncthreads();
 
-    // ---- 1. distances (at most N rounds: only reachable with negative weights, which the contract excludes) ----
-    for (int64_t round = 0; round < N; ++round) {
-      for (int32_t i = tid; i < W; i += DT_BLOCK) {
-        uint32_t m = F[i];
-        while (m) {
-          const int32_t v = (i << 5) + __builtin_ctz(m);
-          m &= m - 1u;
-          const int32_t k1 = in_ptr[v + 1];
-          for (int32_t k = in_ptr[v]; k < k1; ++k) {
-            const int32_t u = in_src[k];
-            atomicOr(&C[u >> 5], 1u << (u & 31));
-          }
-        }
-      }
-      __syncthreads();
-      int any = 0;
-      for (int32_t i = tid; i < W; i += DT_BLOCK) {
-        uint32_t c = C[i];
-        uint32_t nf = 0u;
-        if (c) C[i] = 0u;
-        while (c) {
-          const int b = __builtin_ctz(c);
-          c &= c - 1u;
-          const int32_t u = (i << 5) + b;
-          const double old = dist[u];
-          double best = old;
-          const int32_t k1 = out_ptr[u + 1];
-          for (int32_t k = out_ptr[u]; k < k1; ++k) {
-            const double du = (double)w[out_eid[k]] + dist[out_dst[k]];
-            if (du < best) best = du;
-          }
-          if (best < old) {
-            dist[u] = best;
-            nf |= 1u << b;
-          }
-        }
-        F[i] = nf;
-        any |= (nf != 0u);
-      }
-      if (!__syncthreads_or(any)) break;
-    }
+    // ---- 1. distances ----
+    dt_distances<true>(in_ptr, in_src, out_ptr, out_dst, out_eid, w, N, d, dist, F, C, V);
 
     // ---- 2. next hops: BFS levels backwards over the tight edges; F = {d}, V = {d} ----
     if (next_hop_out) {
@@ -192,6 +212,30 @@ __global__ __launch_bounds__(DT_BLOCK) void k_select_next_hop_dest(float* __rest
   xi[L.col_sel()] = (float)next_hop[(int64_t)slot * N + i];
 }
 
+// ---- the prior head's distance table: table[u][j] = (float) dist(u -> dests[j]), candidate-major ----------------------------
+// One workgroup per destination as k_dest_trees, phase 1 only (two LDS bitmaps, an fp64 scratch row of N). +inf where
+// unreachable, 0 at the destination; an out-of-range destination gets a column of +inf.
+__global__ __launch_bounds__(DT_BLOCK) void k_prior_dest_table(
+    const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src, const int32_t* __restrict__ out_ptr,
+    const int32_t* __restrict__ out_dst, const int32_t* __restrict__ out_eid, const float* __restrict__ w, int64_t N,
+    const int64_t* __restrict__ dests, int64_t D, uint8_t* __restrict__ scratch, int64_t row_bytes,
+    float* __restrict__ table) {
+  extern __shared__ uint32_t dt_lds[];
+  const int tid = threadIdx.x;
+  const int32_t W = (int32_t)((N + 31) >> 5);
+  double* dist = (double*)(scratch + (int64_t)blockIdx.x * row_bytes);
+  for (int64_t j = blockIdx.x; j < D; j += gridDim.x) {
+    const int64_t d64 = dests[j];
+    if (d64 < 0 || d64 >= N) {               // uniform
+      for (int64_t u = tid; u < N; u += DT_BLOCK) table[u * D + j] = __int_as_float(0x7F800000);
+      continue;
+    }
+    dt_distances<false>(in_ptr, in_src, out_ptr, out_dst, out_eid, w, N, (int32_t)d64, dist, dt_lds, dt_lds + W, nullptr);
+    for (int64_t u = tid; u < N; u += DT_BLOCK) table[u * D + j] = (float)dist[u];
+    __syncthreads();   // the next destination re-initialises the row other threads may still be reading
+  }
+}
+
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------
 extern "C" int64_t tarl_dest_trees_scratch_bytes(const tarl_plan* plan, int64_t num_dests) {
   if (!plan || num_dests < 0) return -1;
@@ -233,6 +277,35 @@ extern "C" int tarl_select_next_hop_dest(float* x, int64_t B, int64_t x_bstride,
   hipLaunchKernelGGL(k_select_next_hop_dest, dim3((unsigned)ceil_div(B * num_nodes, DT_BLOCK)), dim3(DT_BLOCK), 0,
                      (hipStream_t)stream, x, L, B, num_nodes, agent_features, num_agents, a_bstride, dest_slot, next_hop,
                      num_dests);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+static inline int64_t pt_row_bytes(int64_t N) { return (8 * N + 255) / 256 * 256; }
+
+extern "C" int64_t tarl_prior_dest_table_scratch_bytes(const tarl_plan* plan, int64_t num_dests) {
+  if (!plan || num_dests < 0) return -1;
+  const int64_t wg = num_dests < DT_MAX_WG ? num_dests : DT_MAX_WG;
+  return wg * pt_row_bytes(plan->N);
+}
+
+extern "C" int tarl_prior_dest_table(const tarl_plan* plan, const float* weights, const int64_t* dests, int64_t num_dests,
+                                     void* scratch, int64_t scratch_bytes, float* table, tarl_stream stream) {
+  TARL_REQUIRE(plan && weights && dests && table, "null argument");
+  TARL_REQUIRE(num_dests >= 0, "bad sizes");
+  const int64_t N = plan->N;
+  const int64_t lds = 8 * ((N + 31) / 32);
+  TARL_REQUIRE(lds <= DT_LDS_MAX, "graph too large for the per-destination trees (N > 655360)");
+  if (num_dests == 0 || N == 0) return TARL_OK;
+  const int64_t need = tarl_prior_dest_table_scratch_bytes(plan, num_dests);
+  TARL_REQUIRE(scratch && scratch_bytes >= need, "scratch too small (tarl_prior_dest_table_scratch_bytes)");
+  const int64_t wg = num_dests < DT_MAX_WG ? num_dests : DT_MAX_WG;
+  if (lds > 64 * 1024)
+    TARL_CHECK_HIP(hipFuncSetAttribute((const void*)k_prior_dest_table, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds));
+  hipLaunchKernelGGL(k_prior_dest_table, dim3((unsigned)wg), dim3(DT_BLOCK), (size_t)lds, (hipStream_t)stream, plan->in_ptr,
+                     plan->in_src, plan->out_ptr, plan->out_dst, plan->out_eid, weights, N, dests, num_dests,
+                     (uint8_t*)scratch, pt_row_bytes(N), table);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
 }

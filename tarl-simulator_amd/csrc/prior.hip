@@ -29,6 +29,11 @@
 //     through LDS and leaves as 256-byte runs of each environment's logits row.
 // tarl_fused_rollout_prior queues, per frame, prior logits -> tarl_graphdist_rollout_at -> tarl_fused_frame (Direction, rows,
 // insert; SELECTED_ROAD set by the sampler) -> count bytes, in one foreign call.
+//
+// The *_dest entry points read the same distances from the per-destination table of tarl_prior_dest_table instead:
+// table [N][D] fp32 (candidate-major like dist, one column per destination) and dest_slot int32 [N] (the column of each
+// destination, -1 = none). A destination outside [0, N) or without a column is unreachable (the sentinel). The kernels are
+// the same templates; only the table lookup differs (PriorAllPairs / PriorPerDest).
 #include <math.h>
 
 #include "fused_common.h"
@@ -51,16 +56,34 @@ __device__ __forceinline__ float emb_of(const float* __restrict__ emb, int64_t M
   return (idx >= 0 && idx < M) ? emb[idx] : 0.0f;        // tarl_policy_edge_logits_fwd's rule
 }
 
-__device__ __forceinline__ float dist_of(const float* __restrict__ dist, int64_t N, int64_t v, float dest_f) {
-  const long long d = (long long)dest_f;                   // agent_destination.to(torch.long) (:186)
-  return (d >= 0 && d < N) ? dist[v * N + d] : INFINITY;
-}
+// dist[v][dest]: the N x N all-pairs table
+struct PriorAllPairs {
+  const float* __restrict__ dist;
+  int64_t N;
+  __device__ __forceinline__ float operator()(int64_t v, float dest_f) const {
+    const long long d = (long long)dest_f;                 // agent_destination.to(torch.long) (:186)
+    return (d >= 0 && d < N) ? dist[v * N + d] : INFINITY;
+  }
+};
+
+// table[v][slot[dest]]: the [N][D] per-destination table; no column -> unreachable
+struct PriorPerDest {
+  const float* __restrict__ table;
+  const int32_t* __restrict__ slot;
+  int64_t N, D;
+  __device__ __forceinline__ float operator()(int64_t v, float dest_f) const {
+    const long long d = (long long)dest_f;
+    if (d < 0 || d >= N) return INFINITY;
+    const int32_t s = slot[d];
+    return (s >= 0 && s < D) ? table[v * D + s] : INFINITY;
+  }
+};
 
 // ---- from observations ---------------------------------------------------------------------------------------------------
+template <class Tab>
 __global__ __launch_bounds__(PR_BLOCK) void k_prior_obs(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                         const float* __restrict__ obs, int64_t M, int64_t N, int64_t E,
-                                                        const float* __restrict__ emb, int64_t num_emb,
-                                                        const float* __restrict__ dist, float w,
+                                                        const float* __restrict__ emb, int64_t num_emb, Tab tab, float w,
                                                         float* __restrict__ logits) {
   const int64_t gid = (int64_t)blockIdx.x * PR_BLOCK + threadIdx.x;
   if (gid >= M * E) return;
@@ -69,33 +92,63 @@ __global__ __launch_bounds__(PR_BLOCK) void k_prior_obs(const int32_t* __restric
   const int64_t v = dst[e];
   const float4* ov = reinterpret_cast<const float4*>(obs + (m * N + v) * 16);
   const float4 a = ov[0], c = ov[1];     // {MAXN, NUMBER_OF_AGENT, FF, LENGTH}, {MAX_FLOW, SELECTED_ROAD, ROAD_INDEX, ORIGIN}
-  logits[gid] = prior_logit(emb_of(emb, num_emb, c.z), dist_of(dist, N, v, ou[8]), a.z, a.x, c.x, a.y, w);
+  logits[gid] = prior_logit(emb_of(emb, num_emb, c.z), tab(v, ou[8]), a.z, a.x, c.x, a.y, w);
+}
+
+template <class Tab>
+static int prior_obs(const tarl_plan* plan, const float* obs16, int64_t M, const float* emb, int64_t num_embeddings, Tab tab,
+                     float prior_weight, float* logits, tarl_stream stream) {
+  TARL_REQUIRE(plan && obs16 && emb && logits, "null argument");
+  TARL_REQUIRE(M >= 1 && num_embeddings >= 1, "bad sizes");
+  TARL_REQUIRE(prior_weight >= 0.0f && prior_weight <= 3.0e38f, "prior_weight must be finite and >= 0");
+  TARL_REQUIRE(((uintptr_t)obs16) % 16 == 0, "obs16 must be 16-byte aligned");
+  if (plan->E == 0) return TARL_OK;
+  hipLaunchKernelGGL(k_prior_obs<Tab>, dim3((unsigned)ceil_div(M * plan->E, PR_BLOCK)), dim3(PR_BLOCK), 0,
+                     (hipStream_t)stream, plan->src, plan->dst, obs16, M, plan->N, plan->E, emb, num_embeddings, tab,
+                     prior_weight, logits);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+static int check_all_pairs(const tarl_plan* plan, const float* dist, int64_t dist_n) {
+  TARL_REQUIRE(plan && dist, "null argument");
+  TARL_REQUIRE(dist_n == plan->N, "distance table is not N x N for this plan");
+  return TARL_OK;
+}
+
+static int check_per_dest(const tarl_plan* plan, const float* table, int64_t num_dests, const int32_t* dest_slot) {
+  TARL_REQUIRE(plan && table && dest_slot, "null argument");
+  TARL_REQUIRE(num_dests >= 1, "the per-destination table needs at least one column");
+  return TARL_OK;
 }
 
 extern "C" int tarl_policy_prior_logits(const tarl_plan* plan, const float* obs16, int64_t M, const float* emb,
                                         int64_t num_embeddings, const float* dist, int64_t dist_n, float prior_weight,
                                         float* logits, tarl_stream stream) {
-  TARL_REQUIRE(plan && obs16 && emb && dist && logits, "null argument");
-  TARL_REQUIRE(M >= 1 && num_embeddings >= 1, "bad sizes");
-  TARL_REQUIRE(dist_n == plan->N, "distance table is not N x N for this plan");
-  TARL_REQUIRE(prior_weight >= 0.0f && prior_weight <= 3.0e38f, "prior_weight must be finite and >= 0");
-  TARL_REQUIRE(((uintptr_t)obs16) % 16 == 0, "obs16 must be 16-byte aligned");
-  if (plan->E == 0) return TARL_OK;
-  hipLaunchKernelGGL(k_prior_obs, dim3((unsigned)ceil_div(M * plan->E, PR_BLOCK)), dim3(PR_BLOCK), 0, (hipStream_t)stream,
-                     plan->src, plan->dst, obs16, M, plan->N, plan->E, emb, num_embeddings, dist, prior_weight, logits);
-  TARL_LAUNCH_CHECK();
-  return TARL_OK;
+  int rc = check_all_pairs(plan, dist, dist_n);
+  if (rc) return rc;
+  return prior_obs(plan, obs16, M, emb, num_embeddings, PriorAllPairs{dist, plan->N}, prior_weight, logits, stream);
+}
+
+extern "C" int tarl_policy_prior_logits_dest(const tarl_plan* plan, const float* obs16, int64_t M, const float* emb,
+                                             int64_t num_embeddings, const float* table, int64_t num_dests,
+                                             const int32_t* dest_slot, float prior_weight, float* logits,
+                                             tarl_stream stream) {
+  int rc = check_per_dest(plan, table, num_dests, dest_slot);
+  if (rc) return rc;
+  return prior_obs(plan, obs16, M, emb, num_embeddings, PriorPerDest{table, dest_slot, plan->N, num_dests}, prior_weight,
+                   logits, stream);
 }
 
 // ---- from the packed state -------------------------------------------------------------------------------------------------
+template <class Tab>
 __global__ __launch_bounds__(PR_BLOCK) void k_prior_fused(const int32_t* __restrict__ src, const int32_t* __restrict__ out_dst,
                                                           const int32_t* __restrict__ out_eid, int64_t B, int64_t N,
                                                           int64_t E, const uint2* __restrict__ hdp,
                                                           const float4* __restrict__ st0, const float* __restrict__ x0,
                                                           int64_t ldx, int col_maxflow, const float* __restrict__ ag,
                                                           int64_t A, int64_t a_bstride, const float* __restrict__ emb,
-                                                          int64_t num_emb, const float* __restrict__ dist, float w,
-                                                          float* __restrict__ logits) {
+                                                          int64_t num_emb, Tab tab, float w, float* __restrict__ logits) {
   __shared__ float tile[PR_TE][PR_TK + 1];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t b0 = (int64_t)blockIdx.x * PR_TE, k0 = (int64_t)blockIdx.y * PR_TK;
@@ -110,7 +163,7 @@ __global__ __launch_bounds__(PR_BLOCK) void k_prior_fused(const int32_t* __restr
       const long long head = (long long)(hu >> 8);
       const float dest = ag[b * a_bstride + ((head >= 0 && head < A) ? head : 0) * AG_COLS + AG_DEST];
       const float4 st = st0[v];    // {MAXN, FF, ROAD_INDEX, congestion_constant}
-      l = prior_logit(emb_of(emb, num_emb, st.z), dist_of(dist, N, v, dest), st.y, st.x, x0[v * ldx + col_maxflow],
+      l = prior_logit(emb_of(emb, num_emb, st.z), tab(v, dest), st.y, st.x, x0[v * ldx + col_maxflow],
                       (float)(hv & HD_CNT), w);
     }
     tile[lane][kk] = l;
@@ -127,26 +180,37 @@ __global__ __launch_bounds__(PR_BLOCK) void k_prior_fused(const int32_t* __restr
 
 static int check_prior_state(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, const float* x,
                              const float* agent_features, int64_t A, const float* emb, int64_t num_embeddings,
-                             const float* dist, int64_t dist_n, float prior_weight) {
-  TARL_REQUIRE(plan && f && x && agent_features && emb && dist, "null argument");
+                             float prior_weight) {
+  TARL_REQUIRE(plan && f && x && agent_features && emb, "null argument");
   TARL_REQUIRE(B >= 1 && A >= 1 && num_embeddings >= 1, "bad sizes");
-  TARL_REQUIRE(dist_n == plan->N, "distance table is not N x N for this plan");
   TARL_REQUIRE(prior_weight >= 0.0f && prior_weight <= 3.0e38f, "prior_weight must be finite and >= 0");
   TARL_REQUIRE(ceil_div(plan->E, PR_TK) < 65536 && ceil_div(B, PR_TE) < 65536, "too many tiles for one grid dimension");
   return tarl_check_fused_core(plan, f, B, Nmax);
 }
 
+template <class Tab>
 static int launch_prior_fused(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, const float* x,
                               int64_t ldx, const float* agent_features, int64_t A, int64_t a_bstride, const float* emb,
-                              int64_t num_embeddings, const float* dist, float prior_weight, float* logits,
-                              hipStream_t s) {
+                              int64_t num_embeddings, Tab tab, float prior_weight, float* logits, hipStream_t s) {
   const FusedBufs fb = tarl_to_bufs(f);
   const Layout L{Nmax, ldx, 0};
-  hipLaunchKernelGGL(k_prior_fused, dim3((unsigned)ceil_div(B, PR_TE), (unsigned)ceil_div(plan->E, PR_TK)), dim3(PR_BLOCK),
-                     0, s, plan->src, plan->out_dst, plan->out_eid, B, plan->N, plan->E, fb.hdp, fb.st0, x, ldx,
-                     L.col_maxflow(), agent_features, A, a_bstride, emb, num_embeddings, dist, prior_weight, logits);
+  hipLaunchKernelGGL(k_prior_fused<Tab>, dim3((unsigned)ceil_div(B, PR_TE), (unsigned)ceil_div(plan->E, PR_TK)),
+                     dim3(PR_BLOCK), 0, s, plan->src, plan->out_dst, plan->out_eid, B, plan->N, plan->E, fb.hdp, fb.st0, x,
+                     ldx, L.col_maxflow(), agent_features, A, a_bstride, emb, num_embeddings, tab, prior_weight, logits);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
+}
+
+template <class Tab>
+static int fused_prior(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B, int64_t ldx, int32_t Nmax,
+                       const float* agent_features, int64_t num_agents, int64_t a_bstride, const float* emb,
+                       int64_t num_embeddings, Tab tab, float prior_weight, float* logits, tarl_stream stream) {
+  TARL_REQUIRE(logits, "null argument");
+  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, num_agents, emb, num_embeddings, prior_weight);
+  if (rc) return rc;
+  if (plan->E == 0) return TARL_OK;
+  return launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, num_agents, a_bstride, emb, num_embeddings, tab,
+                            prior_weight, logits, (hipStream_t)stream);
 }
 
 extern "C" int tarl_fused_prior_logits(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B,
@@ -155,13 +219,23 @@ extern "C" int tarl_fused_prior_logits(const tarl_plan* plan, const tarl_fused* 
                                        const float* dist, int64_t dist_n, float prior_weight, float* logits,
                                        tarl_stream stream) {
   (void)x_bstride;    // the static columns of environment 0 speak for all
-  TARL_REQUIRE(logits, "null argument");
-  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, num_agents, emb, num_embeddings, dist, dist_n,
-                             prior_weight);
+  int rc = check_all_pairs(plan, dist, dist_n);
   if (rc) return rc;
-  if (plan->E == 0) return TARL_OK;
-  return launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, num_agents, a_bstride, emb, num_embeddings, dist,
-                            prior_weight, logits, (hipStream_t)stream);
+  return fused_prior(plan, f, x, B, ldx, Nmax, agent_features, num_agents, a_bstride, emb, num_embeddings,
+                     PriorAllPairs{dist, plan->N}, prior_weight, logits, stream);
+}
+
+extern "C" int tarl_fused_prior_logits_dest(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B,
+                                            int64_t x_bstride, int64_t ldx, int32_t Nmax, const float* agent_features,
+                                            int64_t num_agents, int64_t a_bstride, const float* emb,
+                                            int64_t num_embeddings, const float* table, int64_t num_dests,
+                                            const int32_t* dest_slot, float prior_weight, float* logits,
+                                            tarl_stream stream) {
+  (void)x_bstride;
+  int rc = check_per_dest(plan, table, num_dests, dest_slot);
+  if (rc) return rc;
+  return fused_prior(plan, f, x, B, ldx, Nmax, agent_features, num_agents, a_bstride, emb, num_embeddings,
+                     PriorPerDest{table, dest_slot, plan->N, num_dests}, prior_weight, logits, stream);
 }
 
 // the count bytes of the rollout buffers (NUMBER_OF_AGENT after the frame, env-minor [N][B]) from the packed state
@@ -171,18 +245,17 @@ __global__ __launch_bounds__(PR_BLOCK) void k_counts8(const uint2* __restrict__ 
 }
 
 // observation row env[j] of the current frame -> obs_keep[slot[j]] for the kept (frame, environment) pairs, then the frame
-extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
-                                        const float* times_host, float prev_time, const float* x, int64_t x_bstride,
-                                        int64_t ldx, float* agent_features, int64_t A, int64_t a_bstride,
-                                        const float* edge_attr, const float* log_edge_attr, float log_eps, int use_cong,
-                                        const float* emb, int64_t num_embeddings, const float* dist, int64_t dist_n,
-                                        float prior_weight, float temperature, uint64_t policy_seed,
-                                        uint64_t policy_counter0, uint64_t seed, uint64_t counter0,
-                                        const int64_t* keep_ptr_host, const int32_t* keep_env, const int32_t* keep_slot,
-                                        float* obs_keep, float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
-                                        uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
-                                        tarl_stream stream) {
-  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, A, emb, num_embeddings, dist, dist_n, prior_weight);
+template <class Tab>
+static int rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                         const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
+                         float* agent_features, int64_t A, int64_t a_bstride, const float* edge_attr,
+                         const float* log_edge_attr, float log_eps, int use_cong, const float* emb, int64_t num_embeddings,
+                         Tab tab, float prior_weight, float temperature, uint64_t policy_seed, uint64_t policy_counter0,
+                         uint64_t seed, uint64_t counter0, const int64_t* keep_ptr_host, const int32_t* keep_env,
+                         const int32_t* keep_slot, float* obs_keep, float* logits_scratch, void* dist_scratch,
+                         int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                         tarl_stream stream) {
+  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, A, emb, num_embeddings, prior_weight);
   if (rc) return rc;
   TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
   TARL_REQUIRE(logits_scratch && dist_scratch && ins_scratch, "logits / sampler / insert scratch missing");
@@ -200,7 +273,7 @@ extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused*
       if (rc) return rc;
     }
     if (plan->E > 0) {
-      rc = launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, A, a_bstride, emb, num_embeddings, dist, prior_weight,
+      rc = launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, A, a_bstride, emb, num_embeddings, tab, prior_weight,
                               logits_scratch, s);
       if (rc) return rc;
     }
@@ -219,4 +292,44 @@ extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused*
     }
   }
   return TARL_OK;
+}
+
+extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                        const float* times_host, float prev_time, const float* x, int64_t x_bstride,
+                                        int64_t ldx, float* agent_features, int64_t A, int64_t a_bstride,
+                                        const float* edge_attr, const float* log_edge_attr, float log_eps, int use_cong,
+                                        const float* emb, int64_t num_embeddings, const float* dist, int64_t dist_n,
+                                        float prior_weight, float temperature, uint64_t policy_seed,
+                                        uint64_t policy_counter0, uint64_t seed, uint64_t counter0,
+                                        const int64_t* keep_ptr_host, const int32_t* keep_env, const int32_t* keep_slot,
+                                        float* obs_keep, float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
+                                        uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                                        tarl_stream stream) {
+  int rc = check_all_pairs(plan, dist, dist_n);
+  if (rc) return rc;
+  return rollout_prior(plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A, a_bstride, edge_attr,
+                       log_edge_attr, log_eps, use_cong, emb, num_embeddings, PriorAllPairs{dist, plan->N}, prior_weight,
+                       temperature, policy_seed, policy_counter0, seed, counter0, keep_ptr_host, keep_env, keep_slot,
+                       obs_keep, logits_scratch, dist_scratch, ins_scratch, choice8, log_prob, reward, counts, stream);
+}
+
+extern "C" int tarl_fused_rollout_prior_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                             const float* times_host, float prev_time, const float* x, int64_t x_bstride,
+                                             int64_t ldx, float* agent_features, int64_t A, int64_t a_bstride,
+                                             const float* edge_attr, const float* log_edge_attr, float log_eps,
+                                             int use_cong, const float* emb, int64_t num_embeddings, const float* table,
+                                             int64_t num_dests, const int32_t* dest_slot, float prior_weight,
+                                             float temperature, uint64_t policy_seed, uint64_t policy_counter0,
+                                             uint64_t seed, uint64_t counter0, const int64_t* keep_ptr_host,
+                                             const int32_t* keep_env, const int32_t* keep_slot, float* obs_keep,
+                                             float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
+                                             uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                                             tarl_stream stream) {
+  int rc = check_per_dest(plan, table, num_dests, dest_slot);
+  if (rc) return rc;
+  return rollout_prior(plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A, a_bstride, edge_attr,
+                       log_edge_attr, log_eps, use_cong, emb, num_embeddings,
+                       PriorPerDest{table, dest_slot, plan->N, num_dests}, prior_weight, temperature, policy_seed,
+                       policy_counter0, seed, counter0, keep_ptr_host, keep_env, keep_slot, obs_keep, logits_scratch,
+                       dist_scratch, ins_scratch, choice8, log_prob, reward, counts, stream);
 }

@@ -1,7 +1,8 @@
 """Command line of the MI355X build. The flag set is the reference CLI's contract (main.py of the reference: --algo,
 --scenario, --mode, --timestep_size, --start-end-time, --epochs, --rollout-steps, --seed, --device, --output-dir,
 --profile, --torch-compile) plus ``--steps`` (used by the reference's README but missing from its parser) and
-``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head`` and ``--dijkstra-method``."""
+``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method`` and
+``--dijkstra-method``."""
 import argparse
 import os
 import sys
@@ -45,6 +46,10 @@ OPTIONS = (
                                 "BatchNorm, Laplacian positional encoding)")),
     ("--prior-weight", dict(type=float, default=1.0,
                             help="embedding_dijkstra: weight of the shortest-path prior (1.0 = the reference's plain sum)")),
+    ("--prior-method", dict(choices=("all_pairs", "per_destination", "auto"), default="all_pairs",
+                            help="embedding_dijkstra: free-flow distances from the all-pairs table (N x N), or one column "
+                                 "per distinct agent destination ([N][D], for large networks), or auto: all_pairs up to "
+                                 "4 096 nodes, per_destination above")),
     ("--dijkstra-method", dict(choices=DijkstraAgents.METHODS, default="all_pairs",
                                help="dijkstra: next-hop table from all-pairs shortest paths (N x N), or one reverse "
                                     "shortest-path tree per distinct agent destination ([D][N], for large networks), or "

@@ -16,6 +16,20 @@ from ..algorithms.user_equilibrium_msa import ALL_PAIRS_MAX_NODES
 from ..feature_helpers import AgentFeatureHelpers, FeatureHelpers
 
 
+_DESTINATION = AgentFeatureHelpers._COLUMNS.index("DESTINATION")
+
+
+def destination_set(agent_features: torch.Tensor, num_nodes: int):
+    """The roots of the per-destination tables: every distinct DESTINATION of ``agent_features`` ((A, F), or (B, A, F) for
+    B environments), dummy row 0 included (empty rows read agent 0), ids outside [0, num_nodes) dropped. -> (dests int64
+    (D,), dest_slot int32 (num_nodes,): the table row / column of each destination, -1 = none)."""
+    d = torch.unique(agent_features[..., _DESTINATION].reshape(-1).to(torch.int64))
+    d = d[(d >= 0) & (d < num_nodes)].contiguous()
+    slot = torch.full((num_nodes,), -1, dtype=torch.int32, device=d.device)
+    slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=d.device)
+    return d, slot
+
+
 class Agents(AgentFeatureHelpers):
     def __init__(self, device):
         super().__init__()
@@ -152,10 +166,7 @@ class DijkstraAgents(Agents):
 
     def _build_destinations(self, num_nodes: int):
         """Every distinct DESTINATION of the agent table, dummy row 0 included (empty rows read agent 0)."""
-        d = torch.unique(self.agent_features[..., self.DESTINATION].reshape(-1).to(torch.int64))
-        d = d[(d >= 0) & (d < num_nodes)].contiguous()
-        slot = torch.full((num_nodes,), -1, dtype=torch.int32, device=d.device)
-        slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=d.device)
+        d, slot = destination_set(self.agent_features, num_nodes)
         if self._dest_table is None:
             print(f"Dijkstra routing: per-destination trees ({d.numel()} destinations, {num_nodes} nodes)")
         self.destinations, self.dest_slot, self._dest_table = d, slot, self.agent_features

@@ -5,7 +5,8 @@ Same constructors, ``forward`` signatures and state-dict keys (``nodes_embedding
 (``tarl_policy_edge_logits_fwd/bwd``); live critic: MLP(cat(NUMBER_OF_AGENT per node, time)) on fp32 MFMA
 (``tarl_critic_mlp_fwd/bwd``). What the reference computes and discards after the logits (Dijkstra prior, travel
 time, norm — :181-190) is not evaluated by the default head; ``policy_head = "embedding_dijkstra"`` adds the prior
-(``tarl_policy_prior_logits``). The all-pairs Dijkstra matrix of its constructor is built lazily on request.
+(``tarl_policy_prior_logits``). The all-pairs Dijkstra matrix of its constructor is built lazily on request;
+``prior_method = "per_destination"`` replaces it by one column per destination of the agent table.
 """
 from __future__ import annotations
 
@@ -13,8 +14,9 @@ import torch
 import torch.nn as nn
 
 from .._compat import MessagePassingBase, cached_plan, require_cuda
+from ..algorithms.user_equilibrium_msa import ALL_PAIRS_MAX_NODES
 from ..feature_helpers import ObservationFeatureHelpers
-from .base import Agents
+from .base import Agents, destination_set
 
 
 class _EdgeLogits(torch.autograd.Function):
@@ -36,16 +38,17 @@ class _PriorLogits(torch.autograd.Function):
     embedding receives the logits' gradient through tarl_policy_edge_logits_bwd (ROAD_INDEX = observation column 6)."""
 
     @staticmethod
-    def forward(ctx, emb_weight, obs16, plan, table, prior_weight):
+    def forward(ctx, emb_weight, obs16, plan, table, prior_weight, dest_slot):
         from tarl_hip import ops
         ctx.plan, ctx.obs, ctx.shape = plan, obs16, emb_weight.shape
-        return ops.policy_prior_logits(plan, obs16, emb_weight.detach().reshape(-1).contiguous(), table, prior_weight)
+        return ops.policy_prior_logits(plan, obs16, emb_weight.detach().reshape(-1).contiguous(), table, prior_weight,
+                                       dest_slot=dest_slot)
 
     @staticmethod
     def backward(ctx, grad_logits):
         from tarl_hip import ops
         g = ops.policy_edge_logits_bwd(ctx.plan, ctx.obs, grad_logits.contiguous(), int(torch.Size(ctx.shape).numel()))
-        return g.view(ctx.shape), None, None, None, None
+        return g.view(ctx.shape), None, None, None, None, None
 
 
 class _EdgeMlp(torch.autograd.Function):
@@ -80,8 +83,14 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
     # "graph_transformer": the reference's GraphTransformerNet edge output (src/transformer/model.py, as MLAgents builds it),
     # evaluation-mode BatchNorm; its ``transformer`` submodule and ``gt_pe`` buffer exist only after
     # :meth:`use_graph_transformer`, so the other heads' state dicts do not change.
+    # Where the prior's distances come from: "all_pairs" = ``dist_matrix`` (N x N, tarl_apsp); "per_destination" = one
+    # column per distinct DESTINATION of the agent table, (N, D) fp32 (tarl_prior_dest_table; ``dist_matrix`` is never
+    # built); "auto" = all_pairs up to ALL_PAIRS_MAX_NODES nodes, per_destination above. The same logits either way
+    # wherever tarl_dest_trees' exactness condition holds.
     policy_head = "embedding"
     prior_weight = 1.0
+    prior_method = "all_pairs"
+    PRIOR_METHODS = ("all_pairs", "per_destination", "auto")
 
     def __init__(self, edge_index, num_nodes, free_flow_time_travel, device):
         Agents.__init__(self, device=device)
@@ -93,6 +102,7 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
         self.dim_edge_features = 1
         self._free_flow = free_flow_time_travel
         self._dist_matrix = None
+        self._prior_dest = None         # per_destination: (table (N, D), dest_slot (N,), the agent table it covers)
         self.nodes_embedding = nn.Embedding(num_nodes, 1)
         self.edge_mlp_test = nn.Sequential(nn.Linear(2 * self.dim_node_features, 16), nn.ReLU(), nn.Linear(16, 1))
         self.edge_mlp = nn.Sequential(nn.Linear(2 * self.dim_node_features + self.dim_edge_features, 64), nn.ReLU(),
@@ -121,13 +131,48 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
         require_cuda(w, "free_flow_travel")
         self._dist_matrix = ops.all_pairs_shortest_paths(plan, w, want_next_hop=False, want_dist=True)[1][0]
 
+    def resolve_prior_method(self) -> str:
+        if self.prior_method not in self.PRIOR_METHODS:
+            raise ValueError(f"prior_method must be one of {self.PRIOR_METHODS}, got {self.prior_method!r}")
+        if self.prior_method != "auto":
+            return self.prior_method
+        return "all_pairs" if self.num_nodes <= ALL_PAIRS_MAX_NODES else "per_destination"
+
+    def free_flow_weights(self) -> torch.Tensor:
+        """The prior's edge weights: free-flow travel times, fp32 (E,) on the module's device."""
+        w = self._free_flow.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+        require_cuda(w, "free_flow_travel")
+        return w
+
+    def prior_tables(self):
+        """-> (table, dest_slot) the prior head reads: (``dist_matrix``, None) under all_pairs; else the (N, D) table over
+        the destinations of ``agent_features`` and its column map (src.agents.base.destination_set), rebuilt when the agent
+        table is replaced."""
+        if self.resolve_prior_method() == "all_pairs":
+            return self.dist_matrix, None
+        if self.agent_features is None:
+            raise RuntimeError("the per-destination prior needs agent_features (its destinations are the table's columns)")
+        if self._prior_dest is None or self._prior_dest[2] is not self.agent_features:
+            from tarl_hip import ops
+            dests, slot = destination_set(self.agent_features.to(self.device), self.num_nodes)
+            table = ops.prior_dest_table(cached_plan(self.edge_index, self.num_nodes), self.free_flow_weights(), dests)
+            self._prior_dest = (table, slot, self.agent_features)
+        return self._prior_dest[0], self._prior_dest[1]
+
     def compute_dijkstra_logits(self, agent_destination: torch.Tensor, time_travel: torch.Tensor) -> torch.Tensor:
         """Shortest-path prior (src/agents/mpnn_agent.py:81-113; dormant in the live forward):
-        logits[e] = -dist[dst(e), destination[e]] - time_travel[e]; a destination vector of k * E entries is batched."""
+        logits[e] = -dist[dst(e), destination[e]] - time_travel[e]; a destination vector of k * E entries is batched.
+        Under per_destination every destination must have a column (be a DESTINATION of ``agent_features``)."""
         E = self.edge_index.size(1)
         rep = agent_destination.size(0) // E
-        head = self.edge_index[1].to(self.dist_matrix.device).repeat(rep)
-        logits = -self.dist_matrix[head, agent_destination.to(head.device)] - time_travel
+        table, slot = self.prior_tables()
+        head = self.edge_index[1].to(table.device).repeat(rep)
+        col = agent_destination.to(head.device)
+        if slot is not None:
+            col = slot[col].long()
+            if bool((col < 0).any()):
+                raise ValueError("a destination without a per-destination column (not a DESTINATION of agent_features)")
+        logits = -table[head, col] - time_travel
         return logits.view(rep, -1) if rep > 1 else logits.view(-1)
 
     def use_graph_transformer(self, pe: torch.Tensor):
@@ -159,7 +204,8 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
         if self.policy_head == "embedding_dijkstra":
             from tarl_hip import ops
             obs16 = ops.policy_obs16(node_features, agent_index, self.agent_features.to(node_features.device))
-            logits = _PriorLogits.apply(self.nodes_embedding.weight, obs16, plan, self.dist_matrix, float(self.prior_weight))
+            table, slot = self.prior_tables()
+            logits = _PriorLogits.apply(self.nodes_embedding.weight, obs16, plan, table, float(self.prior_weight), slot)
             return logits if node_features.dim() == 3 else logits.view(-1)
         if self.policy_head != "embedding":
             from tarl_hip import ops

@@ -19,6 +19,7 @@ import time
 
 import torch
 
+from ..agents.base import destination_set
 from .modules import unwrap
 
 
@@ -99,6 +100,13 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
         critic_kw = dict(value="graph_transformer", gt_value_params=value_net.kernel_tensors(), gt_value_pe=value_net.gt_pe)
     head = getattr(policy_net, "policy_head", "embedding")
     m = policy_net.edge_mlp
+    prior_kw = {}
+    if head == "embedding_dijkstra":
+        if policy_net.resolve_prior_method() == "all_pairs":
+            prior_kw = dict(prior_table=policy_net.dist_matrix)
+        else:       # one column per destination of every environment's agent table
+            prior_kw = dict(prior_free_flow=policy_net.free_flow_weights(),
+                            prior_dests=destination_set(engine.agents, engine.N))
     trainer = VecPPOTrainer(engine, policy_net.nodes_embedding.weight,
                             critic,
                             rollout_steps=frames_per_batch, num_epochs=num_epochs, sub_batch_size=sub_batch_size,
@@ -106,8 +114,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             policy=head if head in ("embedding", "embedding_dijkstra", "graph_transformer") else "edge_mlp",
                             edge_mlp_params=[m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias],
                             policy_precision={"edge_mlp_bf16": "bf16", "edge_mlp_fp32": "fp32"}.get(head, "x3"),
-                            prior_table=policy_net.dist_matrix if head == "embedding_dijkstra" else None,
-                            prior_weight=getattr(policy_net, "prior_weight", 1.0),
+                            prior_weight=getattr(policy_net, "prior_weight", 1.0), **prior_kw,
                             gt_params=policy_net.transformer.kernel_tensors() if head == "graph_transformer" else None,
                             gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw)
     log = writer = None

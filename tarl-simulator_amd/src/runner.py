@@ -27,6 +27,7 @@ class RunnerArgs:
     num_envs: int = 1
     policy_head: str = "embedding"
     prior_weight: float = 1.0      # policy_head "embedding_dijkstra": weight of the shortest-path prior
+    prior_method: str = "all_pairs"   # its distances: "all_pairs", "per_destination" or "auto" (MPNNPolicyNet.prior_method)
     value_head: str = "simple"     # "graph_transformer": ValueNet (src/agents/transformer_agent.py)
     dijkstra_method: str = "all_pairs"   # DijkstraAgents: "all_pairs", "per_destination" or "auto"
 
@@ -34,6 +35,9 @@ class RunnerArgs:
         from .agents.base import DijkstraAgents
         if self.dijkstra_method not in DijkstraAgents.METHODS:
             raise ValueError(f"dijkstra_method must be one of {DijkstraAgents.METHODS}, got {self.dijkstra_method!r}")
+        from .agents.mpnn_agent import MPNNPolicyNet
+        if self.prior_method not in MPNNPolicyNet.PRIOR_METHODS:
+            raise ValueError(f"prior_method must be one of {MPNNPolicyNet.PRIOR_METHODS}, got {self.prior_method!r}")
         if self.value_head not in ("simple", "graph_transformer"):
             raise ValueError("value_head must be 'simple' or 'graph_transformer'")
         if self.value_head == "graph_transformer" and self.policy_head == "embedding":
@@ -99,6 +103,7 @@ class Runner:
             self.policy_net = MPNNPolicyNet(g.edge_index, g.x.size(0), free_flow, device=str(self.device))
             self.policy_net.policy_head = a.policy_head
             self.policy_net.prior_weight = float(a.prior_weight)
+            self.policy_net.prior_method = a.prior_method
             pe = None
             if "graph_transformer" in (a.policy_head, a.value_head):
                 from .transformer import cached_laplacian_pe

@@ -226,16 +226,16 @@ class SimEngine:
                              metrics_envs=metrics_envs, dtt_node=dtt_node, events=events, leg=leg, precision=precision)
 
     def rollout_prior(self, T, emb, table, *, prior_weight=1.0, temperature, policy_seed, policy_counter0, choice8, log_prob,
-                      reward, counts, keep=None, obs_keep=None, check=True):
-        """``T`` frames under the shortest-path prior head (``emb``: flat embedding, ``table``: (N, N) free-flow distances) in
-        one foreign call: per frame prior logits from the packed state -> GraphDistribution sample + log-prob -> the
-        simulation frame. Buffers as :meth:`rollout_policy` (``choice8`` (T,B,N), ``counts`` (T+1,N,B)). Returns the list of
-        clock values."""
+                      reward, counts, keep=None, obs_keep=None, check=True, dest_slot=None):
+        """``T`` frames under the shortest-path prior head (``emb``: flat embedding, ``table``: (N, N) free-flow distances,
+        or with ``dest_slot`` the (N, D) per-destination table) in one foreign call: per frame prior logits from the packed
+        state -> GraphDistribution sample + log-prob -> the simulation frame. Buffers as :meth:`rollout_policy` (``choice8``
+        (T,B,N), ``counts`` (T+1,N,B)). Returns the list of clock values."""
         return self._rollout(T, counts, True, check,
                              partial(ops.fused_rollout_prior, self.plan, self.fs, self._x, self.agents, self.ec, emb, table),
                              prior_weight=prior_weight, temperature=temperature, policy_seed=policy_seed,
                              policy_counter0=policy_counter0, keep=keep, obs_keep=obs_keep, choice8=choice8,
-                             log_prob=log_prob, reward=reward)
+                             log_prob=log_prob, reward=reward, dest_slot=dest_slot)
 
     def rollout_gt(self, T, pe, weights, *, temperature, policy_seed, policy_counter0, choice8, log_prob, reward, counts,
                    keep=None, obs_keep=None, check=True):

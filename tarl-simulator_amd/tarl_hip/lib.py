@@ -92,6 +92,14 @@ SIGNATURES = {
     "tarl_fused_rollout_prior": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p,
                                            _f32, C.c_int, _p, _i64, _p, _i64, _f32, _f32, _u64, _u64, _u64, _u64] +
                                  [_p] * 11 + [_p]),
+    "tarl_prior_dest_table_scratch_bytes": (_i64, [_p, _i64]),
+    "tarl_prior_dest_table": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "tarl_policy_prior_logits_dest": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _f32, _p, _p]),
+    "tarl_fused_prior_logits_dest": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p,
+                                               _f32, _p, _p]),
+    "tarl_fused_rollout_prior_dest": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p,
+                                                _f32, C.c_int, _p, _i64, _p, _i64, _p, _f32, _f32, _u64, _u64, _u64, _u64] +
+                                      [_p] * 11 + [_p]),
     "tarl_policy_gt_fwd_scratch_floats": (_i64, [_p, _i64]),
     "tarl_policy_gt_fwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p]),
     "tarl_policy_gt_bwd_scratch_floats": (_i64, [_p, _i64]),

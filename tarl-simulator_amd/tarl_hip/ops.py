@@ -1113,56 +1113,96 @@ def fused_rollout_policy(plan: Plan, fs: FusedState, x, agent_features, ec: Edge
 
 
 # ---- shortest-path prior head (policy_head = "embedding_dijkstra", csrc/prior.hip) ------------------------------------------
-def _prior_args(plan: Plan, emb, table, prior_weight):
+def prior_dest_table_bytes(plan: Plan, num_dests: int):
+    """-> (table bytes, scratch bytes) of :func:`prior_dest_table` for ``num_dests`` destinations."""
+    L = _lib.load()
+    return 4 * plan.num_nodes * int(num_dests), int(L.tarl_prior_dest_table_scratch_bytes(plan.handle, int(num_dests)))
+
+
+def prior_dest_table(plan: Plan, weights, dests):
+    """The per-destination distance table of the prior head (tarl_prior_dest_table): ``weights`` (E,) fp32 in original edge
+    order, ``dests`` (D,) int64 -> fp32 (N, D), table[u, j] = the fp32 rounding of the fp64 shortest-path distance
+    u -> dests[j] (+inf: unreachable, 0 at the destination). Column j equals the all-pairs ``dist[:, dests[j]]`` wherever
+    :func:`destination_trees`' exactness condition holds."""
+    _contig(weights, torch.float32, "weights")
+    _contig(dests, torch.int64, "dests")
+    if weights.dim() != 1 or weights.numel() != plan.num_edges:
+        raise ValueError(f"weights must be ({plan.num_edges},) float32 in original edge order, got {tuple(weights.shape)}")
+    if dests.dim() != 1:
+        raise ValueError("dests must be 1-D")
+    L = _lib.load()
+    D, N = dests.numel(), plan.num_nodes
+    _, need = prior_dest_table_bytes(plan, D)
+    scratch = torch.empty(need, dtype=torch.uint8, device=weights.device) if need > 0 else None
+    table = torch.empty((N, D), dtype=torch.float32, device=weights.device)
+    _lib.check(L.tarl_prior_dest_table(plan.handle, weights.data_ptr(), dests.data_ptr(), D, _lib.ptr(scratch), need,
+                                       table.data_ptr(), _lib.current_stream()))
+    return table
+
+
+def _prior_args(plan: Plan, emb, table, prior_weight, dest_slot):
+    """-> (weight, the table's trailing C arguments, the entry-point suffix). ``dest_slot`` None: ``table`` is the (N, N)
+    all-pairs table; else ``table`` is the (N, D) per-destination table and ``dest_slot`` (N,) int32 its column map."""
     _contig(emb, torch.float32, "emb")
     _contig(table, torch.float32, "prior_table")
     N = plan.num_nodes
-    if tuple(table.shape) != (N, N):
-        raise ValueError(f"prior_table must be the ({N}, {N}) all-pairs distance table of the plan's graph")
     w = float(prior_weight)
     if not (0.0 <= w < float("inf")):
         raise ValueError("prior_weight must be finite and >= 0")
-    return w
+    if dest_slot is None:
+        if tuple(table.shape) != (N, N):
+            raise ValueError(f"prior_table must be the ({N}, {N}) all-pairs distance table of the plan's graph")
+        return w, (table.data_ptr(), table.size(0)), ""
+    _contig(dest_slot, torch.int32, "dest_slot")
+    if table.dim() != 2 or table.size(0) != N or table.size(1) < 1 or tuple(dest_slot.shape) != (N,):
+        raise ValueError(f"a per-destination prior_table must be ({N}, D >= 1) with a ({N},) dest_slot, got "
+                         f"{tuple(table.shape)} and {tuple(dest_slot.shape)}")
+    return w, (table.data_ptr(), table.size(1), dest_slot.data_ptr()), "_dest"
 
 
-def policy_prior_logits(plan: Plan, obs16, emb, table, prior_weight=1.0):
+def policy_prior_logits(plan: Plan, obs16, emb, table, prior_weight=1.0, dest_slot=None):
     """logit[m, e] = emb[ROAD_INDEX(dst)] + prior_weight * ((-table[dst, dest(src)]) - time_travel(dst)) from observations
     ``obs16`` (M, N, 16) (the :func:`policy_obs16` layout) -> (M, E). ``table``: (N, N) fp32 free-flow distances
-    (MPNNPolicyNet.dist_matrix). Unreachable candidates carry the finite sentinel -1e20 (see include/tarl_hip.h)."""
+    (MPNNPolicyNet.dist_matrix), or with ``dest_slot`` the (N, D) table of :func:`prior_dest_table`, read as
+    table[dst, dest_slot[dest]] (tarl_policy_prior_logits_dest). Unreachable candidates, and destinations without a column,
+    carry the finite sentinel -1e20 (see include/tarl_hip.h)."""
     L = _lib.load()
-    w = _prior_args(plan, emb, table, prior_weight)
+    w, targs, sfx = _prior_args(plan, emb, table, prior_weight, dest_slot)
     _contig(obs16, torch.float32, "obs16")
     if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (plan.num_nodes, 16):
         raise ValueError(f"obs16 must be (M, {plan.num_nodes}, 16)")
     M = obs16.size(0)
     logits = torch.empty((M, plan.num_edges), dtype=torch.float32, device=obs16.device)
-    _lib.check(L.tarl_policy_prior_logits(plan.handle, obs16.data_ptr(), M, emb.data_ptr(), emb.numel(), table.data_ptr(),
-                                          table.size(0), w, logits.data_ptr(), _lib.current_stream()))
+    fn = getattr(L, "tarl_policy_prior_logits" + sfx)
+    _lib.check(fn(plan.handle, obs16.data_ptr(), M, emb.data_ptr(), emb.numel(), *targs, w, logits.data_ptr(),
+                  _lib.current_stream()))
     return logits
 
 
-def fused_prior_logits(plan: Plan, fs, x, Nmax, agent_features, emb, table, prior_weight=1.0, out=None):
-    """The same logits from the packed state of the fused engine: (B, E), no observation materialised."""
+def fused_prior_logits(plan: Plan, fs, x, Nmax, agent_features, emb, table, prior_weight=1.0, out=None, dest_slot=None):
+    """The same logits from the packed state of the fused engine: (B, E), no observation materialised (``dest_slot``: as
+    :func:`policy_prior_logits`)."""
     L = _lib.load()
-    w = _prior_args(plan, emb, table, prior_weight)
+    w, targs, sfx = _prior_args(plan, emb, table, prior_weight, dest_slot)
     B, N, bs, ldx = _state(x, Nmax)
     A, abs_ = _agents(agent_features, B)
     logits = out if out is not None else torch.empty((B, plan.num_edges), dtype=torch.float32, device=x.device)
     _contig(logits, torch.float32, "logits")
     if tuple(logits.shape) != (B, plan.num_edges):
         raise ValueError(f"logits must be ({B}, {plan.num_edges})")
-    _lib.check(L.tarl_fused_prior_logits(plan.handle, fs.ref, x.data_ptr(), B, bs, ldx, Nmax, agent_features.data_ptr(), A,
-                                         abs_, emb.data_ptr(), emb.numel(), table.data_ptr(), table.size(0), w,
-                                         logits.data_ptr(), _lib.current_stream()))
+    fn = getattr(L, "tarl_fused_prior_logits" + sfx)
+    _lib.check(fn(plan.handle, fs.ref, x.data_ptr(), B, bs, ldx, Nmax, agent_features.data_ptr(), A, abs_, emb.data_ptr(),
+                  emb.numel(), *targs, w, logits.data_ptr(), _lib.current_stream()))
     return logits
 
 
 def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeConst, emb, table, times, *, prior_weight,
                         use_cong, temperature, policy_seed, policy_counter0, seed, counter0, scratch, prev_time=None,
-                        keep=None, obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None):
-    """``T = len(times)`` frames under the prior head in one foreign call (tarl_fused_rollout_prior). ``keep`` /
-    ``obs_keep`` / ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
-    w = _prior_args(plan, emb, table, prior_weight)
+                        keep=None, obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None, dest_slot=None):
+    """``T = len(times)`` frames under the prior head in one foreign call (tarl_fused_rollout_prior, or
+    tarl_fused_rollout_prior_dest with ``dest_slot``: as :func:`policy_prior_logits`). ``keep`` / ``obs_keep`` /
+    ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
+    w, targs, sfx = _prior_args(plan, emb, table, prior_weight, dest_slot)
     L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
     B, N = fs.B, fs.N
     _, _, bs, ldx = _state(x, fs.Nmax)
@@ -1171,10 +1211,10 @@ def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeC
     logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
     kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
     tarr = (C.c_float * T)(*[float(t) for t in times])
-    _lib.check(L.tarl_fused_rollout_prior(
+    _lib.check(getattr(L, "tarl_fused_rollout_prior" + sfx)(
         plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
         ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
-        1 if use_cong else 0, emb.data_ptr(), emb.numel(), table.data_ptr(), table.size(0), w, float(temperature),
+        1 if use_cong else 0, emb.data_ptr(), emb.numel(), *targs, w, float(temperature),
         int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot),
         _lib.ptr(obs_keep), logits_scratch, dist_scratch, scratch.data_ptr(),
         _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), _lib.current_stream()))

@@ -69,7 +69,8 @@ class VecPPOTrainer:
                  gamma=0.99, lmbda=0.95, clip_epsilon=0.2, entropy_coef=0.01, critic_coef=1.0, temperature=1.0,
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
-                 prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None):
+                 prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
+                 prior_free_flow=None, prior_dests=None):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -92,12 +93,16 @@ class VecPPOTrainer:
         # within a few fp32 ulp of the fp32 MFMA kernel's (the north star's 1e-4 contract) at 2.7x its matrix rate.
         # "embedding_dijkstra" = the embedding plus ``prior_weight`` times the shortest-path prior of the reference
         # (src/agents/mpnn_agent.py:180-190, csrc/prior.hip): state-DEPENDENT like the MLP head, but without parameters of
-        # its own; ``prior_table`` (N, N) = MPNNPolicyNet.dist_matrix. Gradients reach the embedding alone.
+        # its own; ``prior_table`` (N, N) = MPNNPolicyNet.dist_matrix. Gradients reach the embedding alone. Per-destination
+        # prior instead (MPNNPolicyNet.prior_method): no ``prior_table``, but ``prior_free_flow`` (E,) fp32 free-flow
+        # weights and ``prior_dests`` = (dests, dest_slot) of src.agents.base.destination_set over the agent tables of all B
+        # environments; the trainer builds the (N, D) table (ops.prior_dest_table) after checking that it fits.
         # "graph_transformer" = the reference's GraphTransformerNet edge output (csrc/gt_policy.hip), evaluation-mode
         # BatchNorm: ``gt_params`` maps the state-dict keys of ops.GT_PARAM_KEYS + GT_BUFFER_KEYS to the module's tensors
         # (the parameters must also be in ``extra_params``), ``gt_pe`` (N, 16) is its positional encoding.
         self.policy = policy
         self.prior_table = prior_table
+        self.prior_dest_slot = None
         self.prior_weight = float(prior_weight)
         self.policy_precision = policy_precision or ("bf16" if policy_bf16 else "x3")
         if self.policy_precision not in ops.EDGE_MLP_PRECISIONS:
@@ -111,9 +116,12 @@ class VecPPOTrainer:
             if not all(id(p) in ids for p in self.edge_mlp_params):
                 raise ValueError("edge_mlp_params must be part of extra_params (the optimiser's flat buffer)")
         elif policy == "embedding_dijkstra":
-            if engine.fs is None or prior_table is None:
-                raise ValueError("policy='embedding_dijkstra' needs the fused engine and the (N, N) prior_table")
-            if tuple(prior_table.shape) != (engine.N, engine.N):
+            if engine.fs is not None and prior_table is None and prior_free_flow is not None and prior_dests is not None:
+                self.prior_table, self.prior_dest_slot = self._build_prior_dest(engine, prior_free_flow, *prior_dests)
+            elif engine.fs is None or prior_table is None:
+                raise ValueError("policy='embedding_dijkstra' needs the fused engine and the (N, N) prior_table, or "
+                                 "prior_free_flow and prior_dests for the per-destination table")
+            elif tuple(prior_table.shape) != (engine.N, engine.N):
                 raise ValueError(f"prior_table must be ({engine.N}, {engine.N})")
         elif policy == "graph_transformer":
             if engine.fs is None or gt_params is None or gt_pe is None:
@@ -229,6 +237,25 @@ class VecPPOTrainer:
         per = ops.value_gt_fwd_scratch_bytes(plan, 2) - ops.value_gt_fwd_scratch_bytes(plan, 1)
         chunk = max(1, min((T + 1) * B, (self.GTV_FWD_CHUNK_BYTES - ops.value_gt_fwd_scratch_bytes(plan, 0)) // per))
         return chunk, ops.value_gt_fwd_scratch_bytes(plan, chunk), ops.value_gt_bwd_scratch_bytes(plan, m), plan.num_nodes * 64
+
+    @staticmethod
+    def _build_prior_dest(engine, free_flow, dests, dest_slot):
+        """The per-destination prior table (N, D) and its column map, refused when the destination set misses a destination
+        of some environment's agent table or when table and scratch take more than half of the free device memory."""
+        N = engine.N
+        ad = engine.agents[..., 1].reshape(-1).to(torch.int64)        # DESTINATION of every agent of every environment
+        ad = ad[(ad >= 0) & (ad < N)]
+        if tuple(dest_slot.shape) != (N,) or bool((dest_slot.to(engine.device)[ad] < 0).any()):
+            raise ValueError("prior_dests must cover the destinations of all environments' agent tables "
+                             "(src.agents.base.destination_set(engine.agents, N))")
+        table_bytes, scratch_bytes = ops.prior_dest_table_bytes(engine.plan, dests.numel())
+        free = torch.cuda.mem_get_info(engine.device)[0]
+        if table_bytes + scratch_bytes > free // 2:
+            raise ValueError(f"the per-destination prior table ({N} x {dests.numel()} fp32, {table_bytes / 2**20:.0f} MiB) "
+                             f"and its scratch ({scratch_bytes / 2**20:.0f} MiB) need more than half of the free device "
+                             f"memory ({free / 2**20:.0f} MiB free)")
+        w = free_flow.detach().to(engine.device, torch.float32).contiguous()
+        return ops.prior_dest_table(engine.plan, w, dests.to(engine.device)), dest_slot.to(engine.device).contiguous()
 
     def _check_gt_value(self, engine, policy, critic_params, extra_params, rollout_steps, sub_batch_size):
         """Refusals of value="graph_transformer", each naming its limit."""
@@ -403,7 +430,8 @@ class VecPPOTrainer:
         elif self.policy == "graph_transformer":
             times = eng.rollout_gt(n, self.gt_pe, self._gt(), **kw)
         else:
-            times = eng.rollout_prior(n, self._emb(), self.prior_table, prior_weight=self.prior_weight, **kw)
+            times = eng.rollout_prior(n, self._emb(), self.prior_table, prior_weight=self.prior_weight,
+                                      dest_slot=self.prior_dest_slot, **kw)
         self.sample_counter += n
         return times
 
@@ -434,7 +462,8 @@ class VecPPOTrainer:
         if self.policy == "graph_transformer":
             return ops.policy_gt_logits(eng.plan, obs, eng.ec, self.gt_pe, self._gt())
         if self.policy == "embedding_dijkstra":
-            return ops.policy_prior_logits(eng.plan, obs, self._emb(), self.prior_table, self.prior_weight)
+            return ops.policy_prior_logits(eng.plan, obs, self._emb(), self.prior_table, self.prior_weight,
+                                           dest_slot=self.prior_dest_slot)
         return ops.policy_edge_logits(eng.plan, obs, self._emb())
 
     def _actor_logits_bwd(self, obs, g_logits):
