@@ -763,6 +763,42 @@ int tarl_msa_assign_sssp(const tarl_plan* plan, const double* weights, const int
                          const int64_t* od_ptr, const int64_t* od_dest, const double* od_volume, const uint8_t* is_road,
                          void* scratch, int64_t scratch_bytes, double* aux_flow, tarl_stream stream);
 
+/* ---- equilibrium metrics: assignment with its gap, and the step between two assignments (src/algorithms/equilibrium.py) ------
+ * Model of run_msa: entering road node v costs t_v(f) = ff_v (1 + 0.15 (f_v / max(cap_v, 1e-8))^4), other nodes cost 0. The
+ * system optimum is the same problem on the marginal cost m_v(f) = d(f t_v)/df = ff_v (1 + 0.75 (f_v / cap_v)^4).
+ * tarl_msa_assign_sssp_gap == tarl_msa_assign_sssp plus, out of the same launch and the same scratch row,
+ *   sptt_part[j] = the sum over the OD pairs of origins[j], in pair order, of fl(volume * dist[dest]) for reachable
+ *   destinations (the demand's shortest-path travel time at `weights`), and unrouted_part[j] = the volume of its pairs no
+ *   path serves. float64 [num_origins], one thread each, no atomics: two calls give the same bits. Entries of out-of-range
+ *   origins are not written (zero the arrays first).
+ * tarl_msa_assign_gap == tarl_msa_assign that also reads node_cost float64 [num_nodes] and writes pair_cost float64
+ *   [num_pairs]: ((0 + cost[v1]) + cost[v2]) + ... over the nodes entered on the walk (Dijkstra's own sum along that path),
+ *   +inf for a pair without a path or with an id out of range. (tarl_apsp_f64's dist is fp32: not usable for this.)
+ * tarl_bpr_step: everything between two all-or-nothing assignments, one launch, nothing read back by the host.
+ *   flow f, aon_flow y, target_prev, free_flow, capacity float64 [num_nodes]; is_road uint8 [num_nodes]. cost = t (UE) or
+ *   m (SO), H_v = d cost_v / df at f_v. iteration <= 1 (the first load; f is not a feasible flow yet): s = y, lambda = 1.
+ *   Otherwise (i) the target: s = y for MSA and FW; for CFW s = a * target_prev + (1 - a) * y, a = Nn / Dn,
+ *   Nn = sum (target_prev - f) H (y - f), Dn = sum (target_prev - f) H (y - target_prev); a = 0 when Dn == 0 or a is not
+ *   positive, at most 0.99. (ii) the step: msa_step for MSA; else 1 when g(1) <= 0, else the root of
+ *   g(l) = sum (s - f) cost(f + l (s - f)) on [0, 1] by bisection from [0, 1] (g < 0: the lower half is dropped) until the
+ *   midpoint equals an end, at most 60 halvings; lambda = the last midpoint. (iii) in place f <- f + lambda (s - f),
+ *   target_prev <- s; cost_out [num_nodes] = cost at the new f (0 off the roads: what the next assignment reads);
+ *   record float64 [8] = {a, lambda, sum f t(f), sum f cost(f), g(0), g(1), halvings done, iteration}, sums at the new f.
+ *   TARL_BPR_EVAL changes nothing and only writes cost_out and record[2], [3] for the f handed in (aon_flow and
+ *   target_prev may be NULL). Every sum is a fixed-shape reduction inside one workgroup: same inputs, same bits. */
+enum { TARL_BPR_UE = 0, TARL_BPR_SO = 1 };
+enum { TARL_BPR_MSA = 0, TARL_BPR_FW = 1, TARL_BPR_CFW = 2, TARL_BPR_EVAL = 3 };
+int tarl_msa_assign_sssp_gap(const tarl_plan* plan, const double* weights, const int64_t* origins, int64_t num_origins,
+                             const int64_t* od_ptr, const int64_t* od_dest, const double* od_volume,
+                             const uint8_t* is_road, void* scratch, int64_t scratch_bytes, double* aux_flow,
+                             double* sptt_part, double* unrouted_part, tarl_stream stream);
+int tarl_msa_assign_gap(const int64_t* next_hop, int64_t num_nodes, const int64_t* od_origin, const int64_t* od_dest,
+                        const double* od_volume, int64_t num_pairs, const uint8_t* is_road, const double* node_cost,
+                        double* aux_flow, double* pair_cost, tarl_stream stream);
+int tarl_bpr_step(double* flow, const double* aon_flow, double* target_prev, const double* free_flow,
+                  const double* capacity, const uint8_t* is_road, int64_t num_nodes, int objective, int rule,
+                  double msa_step, int64_t iteration, double* cost_out, double* record, tarl_stream stream);
+
 /* ---- per-destination shortest-path trees (the dijkstra agent on large graphs) ------------------------------------------------
  * DijkstraAgents.choice (src/agents/base.py:519-584) only reads next_hop[u][dest] for the destination of each row's head
  * agent: one reverse shortest-path tree per distinct destination replaces the N x N table of tarl_apsp (csrc/dest_trees.hip).

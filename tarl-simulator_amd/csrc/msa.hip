@@ -15,6 +15,8 @@
 //      along the tree, so zero-weight cycles cannot close one; the rule does not depend on scheduling.
 //   3. (assignment only) the OD pairs of the source (sorted by origin, od_ptr offsets) walk d -> o along pred and add the
 //      pair's volume to every road node of path[1:] (d included, o not), fp64 atomics into aux_flow as k_msa_assign does.
+//      With sptt_part / unrouted_part (tarl_msa_assign_sssp_gap) one thread also sums volume x dist[d] over the origin's
+//      pairs, in pair order, while the distances are still in the scratch row: the gap costs no second pass.
 // Scratch is O(workgroups x N), never O(sources x N).
 #include "tarl_common.h"
 
@@ -32,7 +34,7 @@ __global__ __launch_bounds__(MSA_BLOCK) void k_msa_trees(
     const int64_t* __restrict__ sources, int64_t S, uint8_t* __restrict__ scratch, int64_t row_bytes,
     double* __restrict__ dist_out, int32_t* __restrict__ pred_out, const int64_t* __restrict__ od_ptr,
     const int64_t* __restrict__ od_dest, const double* __restrict__ od_vol, const uint8_t* __restrict__ is_road,
-    double* __restrict__ aux_flow) {
+    double* __restrict__ aux_flow, double* __restrict__ sptt_part, double* __restrict__ unrouted_part) {
   extern __shared__ uint32_t msa_lds[];
   const int tid = threadIdx.x;
   const int32_t W = (int32_t)((N + 31) >> 5);
@@ -180,6 +182,21 @@ __global__ __launch_bounds__(MSA_BLOCK) void k_msa_trees(
             if (node < 0 || node >= N) break;
           }
         }
+        // the demand's shortest-path travel time out of the same scratch row: one thread, pair order, no atomics (the
+        // last thread: it has a walk of its own only when the origin has 256 pairs or more)
+        if (sptt_part && tid == MSA_BLOCK - 1) {
+          double sp = 0.0, un = 0.0;
+          for (int64_t p = p0; p < p1; ++p) {
+            const int64_t d = od_dest[p];
+            const double vol = od_vol[p];
+            if (d < 0 || d >= N || !(vol > 0.0)) continue;
+            const double dd = dist[d];
+            if (dd < INF) sp += vol * dd;
+            else un += vol;
+          }
+          sptt_part[j] = sp;
+          unrouted_part[j] = un;
+        }
       }
     }
     __syncthreads();   // the next source re-initialises the row other threads may still be reading
@@ -196,7 +213,7 @@ extern "C" int64_t tarl_msa_scratch_bytes(const tarl_plan* plan, int64_t num_sou
 static int msa_launch(const tarl_plan* plan, const double* weights, const int64_t* sources, int64_t S, void* scratch,
                       int64_t scratch_bytes, double* dist_out, int32_t* pred_out, const int64_t* od_ptr,
                       const int64_t* od_dest, const double* od_vol, const uint8_t* is_road, double* aux_flow,
-                      tarl_stream stream) {
+                      double* sptt_part, double* unrouted_part, tarl_stream stream) {
   TARL_REQUIRE(plan && weights && sources, "null argument");
   TARL_REQUIRE(S >= 0, "bad sizes");
   const int64_t N = plan->N;
@@ -211,7 +228,7 @@ static int msa_launch(const tarl_plan* plan, const double* weights, const int64_
   hipLaunchKernelGGL(k_msa_trees, dim3((unsigned)wg), dim3(MSA_BLOCK), (size_t)lds, (hipStream_t)stream, plan->in_ptr,
                      plan->in_src, plan->in_eid, plan->out_ptr, plan->out_dst, weights, N, sources, S,
                      (uint8_t*)scratch, msa_row_bytes(N), dist_out, pred_out, od_ptr, od_dest, od_vol, is_road,
-                     aux_flow);
+                     aux_flow, sptt_part, unrouted_part);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
 }
@@ -220,7 +237,7 @@ extern "C" int tarl_sssp_f64(const tarl_plan* plan, const double* weights, const
                              void* scratch, int64_t scratch_bytes, double* dist_out, int32_t* pred_out,
                              tarl_stream stream) {
   return msa_launch(plan, weights, sources, num_sources, scratch, scratch_bytes, dist_out, pred_out, nullptr, nullptr,
-                    nullptr, nullptr, nullptr, stream);
+                    nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int tarl_msa_assign_sssp(const tarl_plan* plan, const double* weights, const int64_t* origins,
@@ -229,5 +246,17 @@ extern "C" int tarl_msa_assign_sssp(const tarl_plan* plan, const double* weights
                                     int64_t scratch_bytes, double* aux_flow, tarl_stream stream) {
   TARL_REQUIRE(od_ptr && od_dest && od_volume && is_road && aux_flow, "null argument");
   return msa_launch(plan, weights, origins, num_origins, scratch, scratch_bytes, nullptr, nullptr, od_ptr, od_dest,
-                    od_volume, is_road, aux_flow, stream);
+                    od_volume, is_road, aux_flow, nullptr, nullptr, stream);
+}
+
+// tarl_msa_assign_sssp that also returns, per origin, the shortest-path travel time of its demand and the volume no path
+// serves. Entries of out-of-range origins (and of origins with an inconsistent od_ptr range) are not written.
+extern "C" int tarl_msa_assign_sssp_gap(const tarl_plan* plan, const double* weights, const int64_t* origins,
+                                        int64_t num_origins, const int64_t* od_ptr, const int64_t* od_dest,
+                                        const double* od_volume, const uint8_t* is_road, void* scratch,
+                                        int64_t scratch_bytes, double* aux_flow, double* sptt_part,
+                                        double* unrouted_part, tarl_stream stream) {
+  TARL_REQUIRE(od_ptr && od_dest && od_volume && is_road && aux_flow && sptt_part && unrouted_part, "null argument");
+  return msa_launch(plan, weights, origins, num_origins, scratch, scratch_bytes, nullptr, nullptr, od_ptr, od_dest,
+                    od_volume, is_road, aux_flow, sptt_part, unrouted_part, stream);
 }

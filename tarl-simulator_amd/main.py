@@ -1,8 +1,8 @@
 """Command line of the MI355X build. The flag set is the reference CLI's contract (main.py of the reference: --algo,
 --scenario, --mode, --timestep_size, --start-end-time, --epochs, --rollout-steps, --seed, --device, --output-dir,
 --profile, --torch-compile) plus ``--steps`` (used by the reference's README but missing from its parser) and
-``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method`` and
-``--dijkstra-method``."""
+``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method``,
+``--dijkstra-method`` and ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``)."""
 import argparse
 import os
 import sys
@@ -58,6 +58,14 @@ OPTIONS = (
                           help="mpnn+ppo critic: the reference runner's MPNNValueNetSimple (per-road counts and the clock), "
                                "or graph_transformer: the reference's ValueNet, a second GraphTransformerNet on the policy's "
                                "observation, node output summed and read by mu_mlp (needs a state-dependent policy head)")),
+    ("--equilibrium-metrics", dict(action="store_true",
+                                   help="eval: also solve the user equilibrium and the system optimum of the static BPR "
+                                        "model behind the MSA flows; print TSTT, both relative gaps and the Price of "
+                                        "Anarchy with its interval, write equilibrium_metrics.json and "
+                                        "equilibrium_flows.csv")),
+    ("--equilibrium-gap", dict(type=float, default=1e-4, help="--equilibrium-metrics: relative-gap target")),
+    ("--equilibrium-max-iter", dict(type=int, default=500,
+                                    help="--equilibrium-metrics: iteration limit per problem (conjugate Frank-Wolfe)")),
 )
 
 

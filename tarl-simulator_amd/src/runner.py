@@ -30,6 +30,9 @@ class RunnerArgs:
     prior_method: str = "all_pairs"   # its distances: "all_pairs", "per_destination" or "auto" (MPNNPolicyNet.prior_method)
     value_head: str = "simple"     # "graph_transformer": ValueNet (src/agents/transformer_agent.py)
     dijkstra_method: str = "all_pairs"   # DijkstraAgents: "all_pairs", "per_destination" or "auto"
+    equilibrium_metrics: bool = False    # eval: TSTT at UE and SO, both relative gaps, Price of Anarchy (algorithms/equilibrium.py)
+    equilibrium_gap: float = 1e-4        # its relative-gap target
+    equilibrium_max_iter: int = 500      # and its iteration limit per problem
 
     def __post_init__(self):
         from .agents.base import DijkstraAgents
@@ -204,8 +207,41 @@ class Runner:
                 f.write("road,expected_hourly_flow\n")
                 f.writelines(f"{r},{v}\n" for r, v in expected.items())
             sim.plot_daily_counts(expected, str(out_dir))
+            if a.equilibrium_metrics:
+                self._equilibrium_metrics(sim.graph, agent, expected, out_dir)
             import matplotlib.pyplot as plt
             plt.close("all")
         except Exception as exc:  # noqa: BLE001 - analysis output must not fail the run
             print(f"metric tables / figures skipped: {exc}")
         return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg}
+
+    def _equilibrium_metrics(self, graph, agent, msa_flows, out_dir):
+        """--equilibrium-metrics: solve the user equilibrium and the system optimum of run_msa's static model, print the
+        block below the summary and write equilibrium_metrics.json / equilibrium_flows.csv beside msa_expected_flows.csv.
+        A Price of Anarchy is only ever shown with both gaps and its interval."""
+        import json
+        from .algorithms.equilibrium import assignment_gap, equilibrium_report
+        a = self.args
+        rep = equilibrium_report(graph, agent, gap_tol=a.equilibrium_gap, max_iter=a.equilibrium_max_iter)
+        msa = assignment_gap(graph, agent, msa_flows, objective="ue")
+        ue, so = rep["ue"], rep["so"]
+        lo, hi = rep["price_of_anarchy_interval"]
+        print("\n=== Equilibrium Metrics (static BPR model of the MSA step) ===")
+        for label, r in (("User equilibrium:", ue), ("System optimum:", so)):
+            state = "converged" if r["converged"] else "NOT converged"
+            print(f"{label:25} TSTT {r['tstt']:.6g} s, relative gap {r['relative_gap']:.3e} after {r['iterations']} "
+                  f"{r['solver']} iterations ({state} to {a.equilibrium_gap:g})")
+        print(f"{'Price of Anarchy:':25} {rep['price_of_anarchy']:.6f} in [{lo:.6f}, {hi:.6f}] "
+              f"(gaps: UE {ue['relative_gap']:.3e}, SO {so['relative_gap']:.3e}; lower bound on the optimal TSTT "
+              f"{rep['tstt_lower_bound']:.6g} s)")
+        print(f"{'MSA flows (run_msa):':25} TSTT {msa.tstt:.6g} s, relative gap {msa.relative_gap:.3e}")
+        print(f"{'Unrouted volume:':25} {rep['unrouted_volume']:.0f} of {ue['routed_volume'] + ue['unrouted_volume']:.0f} trips")
+        doc = {k: rep[k] for k in ("ue", "so", "price_of_anarchy", "price_of_anarchy_interval", "relative_gap_ue",
+                                   "relative_gap_so", "tstt_ue", "tstt_so", "tstt_lower_bound", "unrouted_volume")}
+        doc["msa"] = msa.scalars()
+        doc["gap_tol"], doc["max_iter"] = a.equilibrium_gap, a.equilibrium_max_iter
+        with open(out_dir / "equilibrium_metrics.json", "w") as f:
+            json.dump(doc, f, indent=1)
+        with open(out_dir / "equilibrium_flows.csv", "w") as f:
+            f.write("road,ue_flow,so_flow\n")
+            f.writelines(f"{r},{v},{rep['so_flows'][r]}\n" for r, v in rep["ue_flows"].items())

@@ -126,6 +126,9 @@ SIGNATURES = {
     "tarl_msa_scratch_bytes": (_i64, [_p, _i64]),
     "tarl_sssp_f64": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p]),
     "tarl_msa_assign_sssp": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "tarl_msa_assign_sssp_gap": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "tarl_msa_assign_gap": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "tarl_bpr_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, C.c_int, _f64, _i64, _p, _p, _p]),
     "tarl_dest_trees_scratch_bytes": (_i64, [_p, _i64]),
     "tarl_dest_trees": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p]),
     "tarl_select_next_hop_dest": (C.c_int, _STATE + [_i64, _p, _i64, _i64, _p, _p, _i64, _p]),

@@ -306,6 +306,125 @@ def msa_assign_trees(plan: Plan, weights, origins, od_ptr, od_dest, od_volume, i
                                       need, aux_flow.data_ptr(), _lib.current_stream()))
 
 
+# ---- equilibrium metrics (csrc/equilibrium.hip, csrc/msa.hip) -----------------------------------------------------------------
+BPR_OBJECTIVES = {"ue": 0, "so": 1}                      # TARL_BPR_UE / TARL_BPR_SO
+BPR_RULES = {"msa": 0, "fw": 1, "cfw": 2, "eval": 3}     # TARL_BPR_MSA / FW / CFW / EVAL
+BPR_RECORD = 8                                            # {alpha, lambda, sum f t, sum f cost, g(0), g(1), halvings, iteration}
+
+
+def _same_device(ref, *tensors):
+    for t in tensors:
+        if t.device != ref.device:
+            raise ValueError("all tensors must live on the same device")
+
+
+def msa_assign_trees_gap(plan: Plan, weights, origins, od_ptr, od_dest, od_volume, is_road, aux_flow, sptt_part=None,
+                         unrouted_part=None):
+    """:func:`msa_assign_trees` that also returns ``(sptt_part, unrouted_part)``, float64 ``(num_origins,)``: per origin
+    the sum, in pair order, of ``volume * dist[dest]`` over its reachable pairs, and the volume of the unreachable ones
+    (tarl_msa_assign_sssp_gap; no atomics on these two, so they repeat bit for bit)."""
+    for t, dt, nm in ((weights, torch.float64, "weights"), (origins, torch.int64, "origins"),
+                      (od_ptr, torch.int64, "od_ptr"), (od_dest, torch.int64, "od_dest"),
+                      (od_volume, torch.float64, "od_volume"), (is_road, torch.uint8, "is_road"),
+                      (aux_flow, torch.float64, "aux_flow")):
+        _contig(t, dt, nm)
+    S = origins.numel()
+    if weights.dim() != 1 or weights.numel() != plan.num_edges:
+        raise ValueError(f"weights must be ({plan.num_edges},) float64 in original edge order, got {tuple(weights.shape)}")
+    if od_ptr.numel() != S + 1 or od_volume.numel() != od_dest.numel():
+        raise ValueError("od_ptr must have num_origins + 1 entries and od_volume one per od_dest")
+    if is_road.numel() != plan.num_nodes or aux_flow.numel() != plan.num_nodes:
+        raise ValueError("is_road and aux_flow need one entry per node")
+    if sptt_part is None:
+        sptt_part = torch.zeros(S, dtype=torch.float64, device=weights.device)
+    if unrouted_part is None:
+        unrouted_part = torch.zeros(S, dtype=torch.float64, device=weights.device)
+    for t, nm in ((sptt_part, "sptt_part"), (unrouted_part, "unrouted_part")):
+        _contig(t, torch.float64, nm)
+        if t.numel() != S:
+            raise ValueError(f"{nm} needs one entry per origin")
+    _same_device(weights, origins, od_ptr, od_dest, od_volume, is_road, aux_flow, sptt_part, unrouted_part)
+    L, S, need, scratch = _tree_args(plan, weights, origins, "origins")
+    _lib.check(L.tarl_msa_assign_sssp_gap(plan.handle, weights.data_ptr(), origins.data_ptr(), S, od_ptr.data_ptr(),
+                                          od_dest.data_ptr(), od_volume.data_ptr(), is_road.data_ptr(),
+                                          _lib.ptr(scratch), need, aux_flow.data_ptr(), sptt_part.data_ptr(),
+                                          unrouted_part.data_ptr(), _lib.current_stream()))
+    return sptt_part, unrouted_part
+
+
+def msa_assign_gap(next_hop, od_origin, od_dest, od_volume, is_road, node_cost, aux_flow, pair_cost=None):
+    """:func:`msa_assign` that also returns ``pair_cost`` float64 ``(num_pairs,)``: the left-to-right sum of ``node_cost``
+    over the nodes each pair enters, +inf where there is no path (tarl_msa_assign_gap)."""
+    for t, dt, nm in ((next_hop, torch.int64, "next_hop"), (od_origin, torch.int64, "od_origin"),
+                      (od_dest, torch.int64, "od_dest"), (od_volume, torch.float64, "od_volume"),
+                      (is_road, torch.uint8, "is_road"), (node_cost, torch.float64, "node_cost"),
+                      (aux_flow, torch.float64, "aux_flow")):
+        _contig(t, dt, nm)
+    if next_hop.dim() != 2 or next_hop.size(0) != next_hop.size(1):
+        raise ValueError(f"next_hop must be (N, N), got {tuple(next_hop.shape)}")
+    N, P = next_hop.size(0), od_origin.numel()
+    if od_dest.numel() != P or od_volume.numel() != P:
+        raise ValueError("od_origin, od_dest and od_volume need one entry per pair")
+    if is_road.numel() != N or node_cost.numel() != N or aux_flow.numel() != N:
+        raise ValueError("is_road, node_cost and aux_flow need one entry per node")
+    if pair_cost is None:
+        pair_cost = torch.empty(P, dtype=torch.float64, device=next_hop.device)
+    _contig(pair_cost, torch.float64, "pair_cost")
+    if pair_cost.numel() != P:
+        raise ValueError("pair_cost needs one entry per pair")
+    _same_device(next_hop, od_origin, od_dest, od_volume, is_road, node_cost, aux_flow, pair_cost)
+    L = _lib.load()
+    _lib.check(L.tarl_msa_assign_gap(next_hop.data_ptr(), N, od_origin.data_ptr(), od_dest.data_ptr(),
+                                     od_volume.data_ptr(), P, is_road.data_ptr(), node_cost.data_ptr(),
+                                     aux_flow.data_ptr(), pair_cost.data_ptr(), _lib.current_stream()))
+    return pair_cost
+
+
+def bpr_step(flow, aon_flow, target_prev, free_flow, capacity, is_road, *, objective="ue", rule="fw", msa_step=0.0,
+             iteration=2, cost_out=None, record=None):
+    """The step between two all-or-nothing assignments in one launch (tarl_bpr_step): forms the target (``cfw``: the
+    conjugate combination with ``target_prev``), finds the step (``msa``: ``msa_step``; else the exact line search),
+    updates ``flow`` and ``target_prev`` IN PLACE and returns ``(cost_out, record)``: the objective's node costs at the
+    new flow (0 off the roads) and the float64 record ``[alpha, lambda, sum f t, sum f cost, g(0), g(1), halvings,
+    iteration]``. ``iteration <= 1`` is the first load (``lambda = 1``). ``rule="eval"`` changes nothing and evaluates
+    ``flow`` (``aon_flow`` and ``target_prev`` may be None)."""
+    if objective not in BPR_OBJECTIVES:
+        raise ValueError(f"objective must be one of {tuple(BPR_OBJECTIVES)}, got {objective!r}")
+    if rule not in BPR_RULES:
+        raise ValueError(f"rule must be one of {tuple(BPR_RULES)}, got {rule!r}")
+    msa_step = float(msa_step)
+    if rule == "msa" and not 0.0 <= msa_step <= 1.0:
+        raise ValueError("msa_step must lie in [0, 1]")
+    N = flow.numel() if isinstance(flow, torch.Tensor) else 0
+    need = [(flow, torch.float64, "flow"), (free_flow, torch.float64, "free_flow"),
+            (capacity, torch.float64, "capacity"), (is_road, torch.uint8, "is_road")]
+    if rule != "eval" or aon_flow is not None:
+        need.append((aon_flow, torch.float64, "aon_flow"))
+    if rule != "eval" or target_prev is not None:
+        need.append((target_prev, torch.float64, "target_prev"))
+    if cost_out is not None:
+        need.append((cost_out, torch.float64, "cost_out"))
+    for t, dt, nm in need:
+        _contig(t, dt, nm)
+        if t.dim() != 1 or t.numel() != N:
+            raise ValueError(f"{nm} must be ({N},), got {tuple(t.shape)}")
+    if record is not None:
+        _contig(record, torch.float64, "record")
+        if record.numel() != BPR_RECORD:
+            raise ValueError(f"record must hold {BPR_RECORD} float64 values")
+    if cost_out is None:
+        cost_out = torch.empty(N, dtype=torch.float64, device=flow.device)
+    if record is None:
+        record = torch.zeros(BPR_RECORD, dtype=torch.float64, device=flow.device)
+    _same_device(flow, *[t for t, _, _ in need], cost_out, record)
+    L = _lib.load()
+    _lib.check(L.tarl_bpr_step(flow.data_ptr(), _lib.ptr(aon_flow), _lib.ptr(target_prev), free_flow.data_ptr(),
+                               capacity.data_ptr(), is_road.data_ptr(), N, BPR_OBJECTIVES[objective], BPR_RULES[rule],
+                               msa_step, int(iteration), cost_out.data_ptr(), record.data_ptr(),
+                               _lib.current_stream()))
+    return cost_out, record
+
+
 def select_next_hop(x, Nmax, agent_features, next_hop):
     """x[b, i, SELECTED_ROAD] = next_hop[b, i, DESTINATION[head agent of i]] (src/agents/base.py:572-580)."""
     L = _lib.load()
