@@ -151,6 +151,32 @@ int tarl_graphdist_rollout(const tarl_plan* plan, const float* logits, int64_t B
 /* tarl_graphdist_mode (:45-55): one-hot (fp32, like zeros_like(proba)) of the per-node argmax, first maximum wins. */
 int tarl_graphdist_mode(const tarl_plan* plan, const float* proba, int64_t B, float* mode_onehot, int32_t* choice,
                         tarl_stream stream);
+/* tarl_graphdist_mode_rollout: the MODE counterpart of tarl_graphdist_rollout — the deterministic action of
+ *   GraphDistribution(logits / temperature) (:45-55: per source node the out-edge with the largest PROBABILITY, the first
+ *   maximum in original edge order wins; torchrl's ExplorationType.MODE, src/rl/ppo_trainer.py:149) and its log_prob
+ *   (:82-96) for per-frame logits [B][E] in ONE launch, without materialising the probabilities. The comparison is made on
+ *   p as tarl_graphdist_softmax computes it, not on the logits (unequal logits may round to equal p; a node whose
+ *   candidates all carry the prior head's -1e20 sentinel has equal p everywhere: the first edge wins). Action and log_prob
+ *   are bit-identical to tarl_graphdist_softmax -> tarl_graphdist_mode -> tarl_graphdist_logprob_entropy_fwd.
+ *   Outputs, each nullable (at least one given), as tarl_graphdist_rollout: choice int32 [B][N] (edge id, -1 = none);
+ *   choice8 uint8 [B][N] (rank of the chosen out-edge in the node's CSR list, 0x80 | previous rank for a node without
+ *   out-edges); sel8 uint8 [N][B] = tarl_fused.sel8, updated in place (== tarl_fused_apply_choice of the action);
+ *   log_prob [B]. No scratch, no noise. */
+int tarl_graphdist_mode_rollout(const tarl_plan* plan, const float* logits, int64_t B, float temperature, int32_t* choice,
+                                uint8_t* choice8, uint8_t* sel8, float* log_prob, tarl_stream stream);
+/* tarl_episode_summary: what an evaluation reports (src/rl/ppo_trainer.py:89-127: the return is the sum of the rewards;
+ *   src/runner.py:147-150: arrived agents = DONE == 1 and their mean ARRIVAL_TIME - DEPARTURE_TIME; the leg histogram's
+ *   "on the way" = the ON_WAY flag count), per environment, from agent_features fp32 [B][num_agents][9] (environment stride
+ *   a_bstride floats; row 0 is the dummy and is skipped):
+ *   counts int32 [B][3] = {arrived (DONE == 1), on the way (ON_WAY == 1 and not arrived), not yet departed (neither)};
+ *   sums fp64 [B][3] = {sum tt, sum tt^2, max tt} over the arrived agents, tt = ARRIVAL_TIME - DEPARTURE_TIME (fp32
+ *     difference, widened); max tt = 0 where nobody arrived; fixed summation order, no floating-point atomics;
+ *   episode_return fp64 [B] (nullable) = sum over t < T of reward [T][B] (nullable when T == 0) in frame order;
+ *   hist int32 [B][num_bins] (nullable; 1 <= num_bins <= 16384, bin_width > 0): travel-time histogram of the arrived
+ *     agents, bin min(floor(tt / bin_width), num_bins - 1), tt < 0 (or NaN) counted in bin 0. */
+int tarl_episode_summary(const float* agent_features, int64_t B, int64_t num_agents, int64_t a_bstride,
+                         const float* reward, int64_t T, float bin_width, int32_t num_bins, int32_t* counts, double* sums,
+                         double* episode_return, int32_t* hist, tarl_stream stream);
 /* tarl_graphdist_logprob_entropy_fwd (:82-96): log_prob [B] = sum_e a_e log(p_e + 1e-8), -inf when the action is not
  *   exactly one edge per source node; entropy [B] = -sum_e p_e log(p_e + 1e-8). Action given as one-hot or choice.
  *   Outputs nullable. One workgroup per batch row, fixed reduction order. */

@@ -2,7 +2,8 @@
 --scenario, --mode, --timestep_size, --start-end-time, --epochs, --rollout-steps, --seed, --device, --output-dir,
 --profile, --torch-compile) plus ``--steps`` (used by the reference's README but missing from its parser) and
 ``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method``,
-``--dijkstra-method`` and ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``)."""
+``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
+``--checkpoint`` and the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``."""
 import argparse
 import os
 import sys
@@ -66,6 +67,17 @@ OPTIONS = (
     ("--equilibrium-gap", dict(type=float, default=1e-4, help="--equilibrium-metrics: relative-gap target")),
     ("--equilibrium-max-iter", dict(type=int, default=500,
                                     help="--equilibrium-metrics: iteration limit per problem (conjugate Frank-Wolfe)")),
+    ("--eval-envs", dict(type=int, default=0,
+                         help="mpnn / mpnn+ppo: also evaluate the policy on K vectorised environments (same network and "
+                              "population, K noise streams) with its deterministic (MODE) action: mean, standard error and "
+                              "a normal-approximation interval of return and travel times over the K realisations; train: "
+                              "eval_vec/* in train_log.jsonl, eval: a printed block, eval_envs.json and eval_envs.csv")),
+    ("--eval-sampled", dict(action="store_true", help="--eval-envs: also report a run with sampled actions")),
+    ("--iterations", dict(type=int, default=1,
+                          help="train: collector batches (total frames per environment = iterations x rollout steps)")),
+    ("--checkpoint", dict(type=str, default=None,
+                          help="mpnn / mpnn+ppo: load a policy.pt written by --mode train into the policy network; a file "
+                               "whose keys or shapes do not match the network is refused")),
 )
 
 

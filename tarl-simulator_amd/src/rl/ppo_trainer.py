@@ -8,6 +8,11 @@ optionally a sampled rollout); its scalars ``eval/avg_return``, ``eval/episode_l
 arrays behind the reference's histograms (``eval/nodes_metrics/avg_vc|std_vc``) and leg-histogram figure go into the same
 record; matplotlib figures are not drawn.
 
+Extension: ``eval_envs`` K > 0 adds a vectorised evaluation (``tarl_hip.evaluator.VecEvaluator``: the same policy on K
+environments of its own fused engine, MODE, with ``stochastic_eval`` also sampled) to every periodic evaluation; its
+scalars ``eval_vec/*`` (``eval_vec_stochastic/*``) carry the spread over the K realisations of the stochastic simulator
+that the single drop-in rollout cannot give. The ``eval/*`` record is unchanged.
+
 Extension: ``num_envs`` (default 1) vectorises the rollout over B environments per GPU; under ``torchrun`` every rank
 trains on its own environments and gradients are averaged with one RCCL all-reduce per optimiser step.
 """
@@ -68,9 +73,43 @@ def _evaluate(prefix, deterministic, eval_env, policy_module, frames_per_batch):
     return rec, frames
 
 
+def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature):
+    """The K-environment evaluator of ``ppo_train(eval_envs=K)``: its own fused engine on copies of ``eval_env``'s graph
+    state and agent table (the drop-in environment is left alone), noise seed ``seed + 104729``."""
+    from tarl_hip import ops
+    from tarl_hip.engine import SimEngine
+    from tarl_hip.evaluator import VecEvaluator
+    sim = eval_env.simulator
+    g = sim.graph
+    if not ops.fused_path_supported(g.edge_index, sim.Nmax):
+        raise ValueError("eval_envs needs the packed (fused) path, which cannot represent this graph (Nmax > 127, an "
+                         "out-degree above 126 or parallel edges): there is no fall-back for the vectorised evaluation")
+    engine = SimEngine(g.x.clone(), g.edge_index, g.edge_attr, sim.Nmax, sim.agent.agent_features.clone(),
+                       congestion_constant=getattr(g, "congestion_constant", None), num_envs=int(eval_envs),
+                       device=g.x.device, timestep=sim.timestep, seed=seed + 104729, fused=True)
+    dests = None
+    if getattr(policy_net, "policy_head", "embedding") == "embedding_dijkstra" and \
+            policy_net.resolve_prior_method() != "all_pairs":
+        dests = destination_set(engine.agents, engine.N)
+    return VecEvaluator.from_policy_net(engine, policy_net, prior_dests=dests, temperature=temperature)
+
+
+def vec_eval_record(prefix, res):
+    """The scalars of one vectorised evaluation (tarl_hip.evaluator.EvalResult) for the training log. After a domain exit
+    only ``envs``, ``domain_exit`` and the time are numbers; the statistics are ``None`` (never an average of such a run)."""
+    rec = {f"{prefix}/envs": res.envs, f"{prefix}/domain_exit": bool(res.domain_exit),
+           f"{prefix}/computation_time_ms": res.computation_time_ms}
+    agg = res.aggregate or {}
+    for key, src, stat in (("avg_return", "episode_return", "mean"), ("avg_return_se", "episode_return", "se"),
+                           ("avg_travel_time", "avg_travel_time", "mean"), ("avg_travel_time_se", "avg_travel_time", "se"),
+                           ("arrived", "arrived", "mean"), ("p95_travel_time", "p95_travel_time", "mean")):
+        rec[f"{prefix}/{key}"] = agg[src][stat] if src in agg else None
+    return rec
+
+
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
-              eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0):
+              eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0):
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
     from tarl_hip.trainer import VecPPOTrainer
@@ -127,6 +166,12 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
         except Exception:  # noqa: BLE001
             writer = None
     trainer.keep_grad = log is not None
+    if int(eval_envs) < 0:
+        raise ValueError("eval_envs must be >= 0")
+    # rank 0 alone evaluates (as it alone logs); the evaluator enters no collective
+    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature)
+                if eval_envs and eval_env is not None and log is not None else None)
+    ppo_train.last_vec_eval = vec_eval
     frames = 0
     it = 0
     h = sim.h
@@ -161,12 +206,18 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                 ev, fr = _evaluate("eval_stochastic", False, eval_env, policy_module, frames_per_batch)
                 rec.update(ev)
                 ppo_train.last_eval["eval_stochastic"] = fr
+            if vec_eval is not None:      # like _evaluate: frames_per_batch frames or the episode's end, whichever is first
+                n_eval = min(int(frames_per_batch), vec_eval.episode_frames)
+                for prefix, det in (("eval_vec", True),) + ((("eval_vec_stochastic", False),) if stochastic_eval else ()):
+                    res = vec_eval.run(n_eval, deterministic=det)
+                    rec.update(vec_eval_record(prefix, res))
+                    ppo_train.last_eval[prefix] = res
         if rec is not None:
             log.write(json.dumps(rec) + "\n")
             log.flush()
             if writer is not None:
                 for k, v in rec.items():
-                    if k in ("global_step", "iter_seconds"):
+                    if k in ("global_step", "iter_seconds") or v is None:
                         continue
                     if isinstance(v, list):
                         if k.endswith("_vc"):

@@ -33,8 +33,27 @@ class RunnerArgs:
     equilibrium_metrics: bool = False    # eval: TSTT at UE and SO, both relative gaps, Price of Anarchy (algorithms/equilibrium.py)
     equilibrium_gap: float = 1e-4        # its relative-gap target
     equilibrium_max_iter: int = 500      # and its iteration limit per problem
+    eval_envs: int = 0             # mpnn / mpnn+ppo: K > 0 adds the vectorised evaluation (tarl_hip.evaluator) on K environments
+    eval_sampled: bool = False     # ... and also a sampled one next to the deterministic (MODE) one
+    iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
+    checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
+
+    @property
+    def total_frames(self) -> int:
+        return int(self.iterations) * int(self.rollout_steps)
 
     def __post_init__(self):
+        if self.eval_envs is None or int(self.eval_envs) < 0:
+            raise ValueError(f"eval_envs must be >= 0, got {self.eval_envs!r}")
+        if self.eval_envs and self.algo in ("random", "dijkstra"):
+            raise ValueError(f"eval_envs evaluates a policy network on the vectorised engine: not available for algo "
+                             f"{self.algo!r} (use mpnn or mpnn+ppo)")
+        if self.eval_sampled and not self.eval_envs:
+            raise ValueError("eval_sampled adds a sampled run to the vectorised evaluation: it needs eval_envs > 0")
+        if int(self.iterations) < 1:
+            raise ValueError(f"iterations must be >= 1, got {self.iterations!r}")
+        if self.checkpoint is not None and self.algo in ("random", "dijkstra"):
+            raise ValueError(f"checkpoint holds a policy network's parameters: not available for algo {self.algo!r}")
         from .agents.base import DijkstraAgents
         if self.dijkstra_method not in DijkstraAgents.METHODS:
             raise ValueError(f"dijkstra_method must be one of {DijkstraAgents.METHODS}, got {self.dijkstra_method!r}")
@@ -47,6 +66,30 @@ class RunnerArgs:
             raise ValueError("value_head 'graph_transformer' reads the observation of every frame, which the 'embedding' "
                              "head's rollout does not build: use a state-dependent policy head (edge_mlp*, "
                              "embedding_dijkstra or graph_transformer)")
+
+
+CHECKPOINT_PREFIX = "module.0.module."      # ProbabilisticActor -> TensorDictModule -> the network (ppo_train's keys)
+
+
+def checkpoint_state(file_state, expected):
+    """Map the state dict of a ``policy.pt`` written by ``ppo_train`` (keys ``module.0.module.<name>``, ``gt_pe`` among them
+    where the network has one) onto a network whose ``state_dict()`` is ``expected``: -> {name: tensor}. A file whose keys
+    or shapes do not match the network exactly is refused, with the offending key named."""
+    mapped = {}
+    for k, v in file_state.items():
+        if not k.startswith(CHECKPOINT_PREFIX):
+            raise ValueError(f"checkpoint key {k!r} does not start with {CHECKPOINT_PREFIX!r}: not a policy.pt of ppo_train")
+        name = k[len(CHECKPOINT_PREFIX):]
+        if name not in expected:
+            raise ValueError(f"checkpoint key {k!r} has no counterpart in the network (policy head / graph mismatch?)")
+        if tuple(v.shape) != tuple(expected[name].shape):
+            raise ValueError(f"checkpoint key {k!r} has shape {tuple(v.shape)}, the network's {name!r} has "
+                             f"{tuple(expected[name].shape)}")
+        mapped[name] = v
+    for name in expected:
+        if name not in mapped:
+            raise ValueError(f"the network's {name!r} is missing from the checkpoint (no key {CHECKPOINT_PREFIX + name!r})")
+    return mapped
 
 
 class Runner:
@@ -126,8 +169,24 @@ class Runner:
                 self.value_net = MPNNValueNetSimple(g.edge_index, g.x.size(0), device=str(self.device))
             self.value_net.load(a.scenario)
             self.env.simulator.agent = self.policy_net     # the policy IS the population store used by the env
+            if a.eval_envs:
+                from tarl_hip import ops
+                if not ops.fused_path_supported(g.edge_index, self.env.simulator.Nmax):
+                    raise ValueError("--eval-envs needs the packed (fused) path, which cannot represent this graph (Nmax > "
+                                     "127, an out-degree above 126 or parallel edges); there is no fall-back for the "
+                                     "vectorised evaluation: run without --eval-envs")
+            if a.checkpoint is not None:
+                self.load_checkpoint(a.checkpoint)
         else:
             raise ValueError(f"Unknown algorithm {a.algo}")
+
+    def load_checkpoint(self, path):
+        """Load a ``policy.pt`` written by ``ppo_train`` into the policy network (in place: views held elsewhere stay valid)."""
+        state = torch.load(path, map_location=self.device)
+        with torch.no_grad():
+            own = self.policy_net.state_dict()
+            for name, v in checkpoint_state(state, own).items():
+                own[name].copy_(v)
 
     def _actor(self, return_log_prob):
         from .reinforcement_learning import GraphDistribution
@@ -160,11 +219,11 @@ class Runner:
         if self.rank == 0:
             out.mkdir(parents=True, exist_ok=True)
         # rank 0 alone writes the checkpoint and the logs; every rank takes part in the training collectives
-        ppo_train(self.env, policy_module, value_module, total_frames=a.rollout_steps,
+        ppo_train(self.env, policy_module, value_module, total_frames=a.total_frames,
                   frames_per_batch=a.rollout_steps, num_epochs=a.epochs, device=self.device,
                   checkpoint_path=(out / "policy.pt") if self.rank == 0 else None,
                   log_dir=str(out) if self.rank == 0 else None, eval_env=eval_env, eval_interval=1,
-                  num_envs=a.num_envs, seed=a.seed)
+                  num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled)
 
     def eval(self):
         a = self.args
@@ -213,7 +272,51 @@ class Runner:
             plt.close("all")
         except Exception as exc:  # noqa: BLE001 - analysis output must not fail the run
             print(f"metric tables / figures skipped: {exc}")
+        if a.eval_envs and a.algo in {"mpnn", "mpnn+ppo"}:
+            return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg,
+                    "vectorised": self._vectorised_eval(n, out_dir)}
         return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg}
+
+    def _vectorised_eval(self, frames, out_dir):
+        """--eval-envs K: the policy on K environments of a fused engine of its own (copies of the graph state and the agent
+        table; noise seed ``seed + 104729``) for the same number of frames as the pass above, MODE and with --eval-sampled
+        also sampled: prints the aggregate block(s), writes eval_envs.json (aggregate + settings) and eval_envs.csv (one row
+        per environment). -> {"mode": EvalResult, "sampled": EvalResult or None}."""
+        import csv
+        import json
+        from tarl_hip.engine import SimEngine
+        from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator
+        from .agents.base import destination_set
+        a, sim = self.args, self.env.simulator
+        g = sim.graph
+        engine = SimEngine(g.x.clone(), g.edge_index, g.edge_attr, sim.Nmax, self.policy_net.agent_features.clone(),
+                           congestion_constant=getattr(g, "congestion_constant", None), num_envs=int(a.eval_envs),
+                           device=g.x.device, timestep=sim.timestep, seed=a.seed + 104729, fused=True)
+        dests = None
+        if a.policy_head == "embedding_dijkstra" and self.policy_net.resolve_prior_method() != "all_pairs":
+            dests = destination_set(engine.agents, engine.N)
+        ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests)
+        results = {"mode": ev.run(frames, deterministic=True),
+                   "sampled": ev.run(frames, deterministic=False) if a.eval_sampled else None}
+        doc, rows = {}, []
+        for key, label in (("mode", "MODE"), ("sampled", "sampled")):
+            res = results[key]
+            if res is None:
+                continue
+            print(f"\n=== Vectorised evaluation ({res.envs} environments, {label}) ===")
+            print(f"{'frames:':22} {res.frames_run:12d}   ({res.computation_time_ms:.1f} ms)")
+            for line in res.summary_lines():
+                print(line)
+            doc[key] = res.to_dict()
+            rows += [dict(kind=key, **r) for r in res.rows()]
+        out_dir.mkdir(parents=True, exist_ok=True)
+        with open(out_dir / "eval_envs.json", "w") as f:
+            json.dump(doc, f, indent=1)
+        with open(out_dir / "eval_envs.csv", "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
+            w.writeheader()
+            w.writerows(rows)
+        return results
 
     def _equilibrium_metrics(self, graph, agent, msa_flows, out_dir):
         """--equilibrium-metrics: solve the user equilibrium and the system optimum of run_msa's static model, print the

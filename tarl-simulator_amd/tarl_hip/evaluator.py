@@ -1,0 +1,353 @@
+"""VecEvaluator — evaluate ONE policy on K vectorised environments of a fused :class:`SimEngine`, deterministically
+(MODE: ``GraphDistribution.mode``, torchrl's ``ExplorationType.MODE`` of the reference's ``_evaluate``,
+src/rl/ppo_trainer.py:89-127,149) or with sampled actions, and report per-environment results with their spread.
+
+The K environments share the network and (unless the caller owns a (K, A, 9) table) the population; they differ in their
+noise streams (``env_base + b``: the Gumbel race of DirectionMPNN.aggregate), so one evaluation yields K realisations of the
+stochastic simulator instead of the single one of the drop-in ``SimulatorEnv.rollout`` pass.
+
+Per frame, on the caller's stream and without a host synchronisation: the head's logits from the packed state (existing
+ops), the action as SELECTED_ROAD bytes (``ops.graphdist_mode_rollout`` / ``ops.graphdist_rollout``), then
+``SimEngine.frame_fused(skip_choice=True)`` with the frame's reward written into a (T, K) buffer. The report comes from
+``ops.episode_summary`` (one launch); the host only turns K numbers per quantity into mean / spread.
+
+Domain exits: a FIFO count that reaches ``Nmax`` leaves the reference's defined domain (the engine's status word). The
+evaluator copies the status word to pinned memory every ``poll_frames`` frames and looks at the copies that have arrived;
+once it sees the flag it queues nothing more, and a run that left the domain returns ``domain_exit=True`` with NO statistics.
+"""
+from __future__ import annotations
+
+import math
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import lib as _lib
+from . import ops
+from .engine import EPISODE_END, EPISODE_START
+
+HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer")
+_MLP_PRECISION = {"edge_mlp": "x3", "edge_mlp_fp32": "fp32", "edge_mlp_bf16": "bf16"}
+PER_ENV_KEYS = ("episode_return", "frames", "arrived", "on_way", "not_departed", "avg_travel_time", "std_travel_time",
+                "max_travel_time", "p50_travel_time", "p95_travel_time")
+
+
+def aggregate(values):
+    """Mean and spread of one per-environment quantity over the K environments. ``None`` entries (an environment without
+    an arrival has no travel time) are left out and counted in ``missing``. ``std`` is the sample standard deviation
+    (ddof = 1), ``se = std / sqrt(n)``, ``ci95 = mean -+ 1.96 se``: a NORMAL-APPROXIMATION interval, ``None`` (like std and
+    se) when fewer than two environments contribute."""
+    v = np.asarray([x for x in values if x is not None], dtype=np.float64)
+    out = {"n": int(v.size), "missing": int(len(values) - v.size), "mean": None, "std": None, "se": None, "min": None,
+           "max": None, "ci95": None, "ci95_kind": "normal approximation, mean -+ 1.96 se"}
+    if v.size == 0:
+        return out
+    out.update(mean=float(v.mean()), min=float(v.min()), max=float(v.max()))
+    if v.size >= 2:
+        std = float(v.std(ddof=1))
+        se = std / math.sqrt(v.size)
+        out.update(std=std, se=se, ci95=(out["mean"] - 1.96 * se, out["mean"] + 1.96 * se))
+    return out
+
+
+def hist_percentile(hist, q, bin_width):
+    """The ``q``-quantile (0 < q <= 1) of binned data as the UPPER edge of the bin that holds the sample of rank
+    ceil(q n) (the inverted empirical CDF, numpy's ``method="inverted_cdf"``); ``None`` for an empty histogram. The last
+    bin collects everything at or above its lower edge, so its upper edge is a lower bound there."""
+    h = np.asarray(hist, dtype=np.int64)
+    n = int(h.sum())
+    if n == 0:
+        return None
+    v = n * float(q) - 1.0
+    i = math.floor(v)
+    idx = min(max(int(i) + (1 if v - i > 0 else 0), 0), n - 1)        # 0-based rank of the sample
+    k = int(np.searchsorted(np.cumsum(h), idx + 1, side="left"))
+    return float((k + 1) * bin_width)
+
+
+@dataclass
+class EvalResult:
+    """Per-environment lists (length ``envs``; ``None`` where undefined) and their aggregates over the environments. After
+    a domain exit every per-environment field and ``aggregate`` is ``None``: such a run is never averaged."""
+    envs: int
+    head: str
+    deterministic: bool
+    frames_run: int
+    domain_exit: bool = False
+    domain_exit_frames: tuple | None = None       # (first, last + 1) frame of the polled block that showed the flag
+    episode_return: list | None = None            # sum of the rewards = -(sum over frames of the network's occupancy)
+    frames: list | None = None
+    arrived: list | None = None                   # DONE == 1
+    on_way: list | None = None                    # ON_WAY flag count (the reference's leg histogram), NOT the occupancy
+    not_departed: list | None = None
+    avg_travel_time: list | None = None           # None for an environment without an arrival
+    std_travel_time: list | None = None           # population standard deviation over the environment's arrived agents
+    max_travel_time: list | None = None
+    p50_travel_time: list | None = None           # from the histogram: upper bin edge
+    p95_travel_time: list | None = None
+    aggregate: dict | None = None
+    envs_without_arrival: int | None = None
+    settings: dict = field(default_factory=dict)
+    computation_time_ms: float = field(default=0.0, compare=False)
+
+    def to_dict(self, per_env=False):
+        d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
+                                           "domain_exit_frames", "aggregate", "envs_without_arrival", "settings",
+                                           "computation_time_ms")}
+        if per_env:
+            d["per_env"] = {k: getattr(self, k) for k in PER_ENV_KEYS}
+        return d
+
+    def rows(self):
+        """One dict per environment (the rows of eval_envs.csv)."""
+        if self.domain_exit:
+            return []
+        return [dict(env=b, **{k: getattr(self, k)[b] for k in PER_ENV_KEYS}) for b in range(self.envs)]
+
+    def summary_lines(self):
+        """The aggregate as printable lines."""
+        if self.domain_exit:
+            a, b = self.domain_exit_frames
+            return [f"domain exit: a FIFO count reached Nmax between frames {a} and {b}; no statistics"]
+        out = []
+        for k in PER_ENV_KEYS:
+            g = self.aggregate[k]
+            if g["mean"] is None:
+                out.append(f"{k + ':':22} no data ({g['missing']} environments without an arrival)")
+                continue
+            s = f"{k + ':':22} {g['mean']:12.3f}"
+            if g["se"] is not None:
+                s += f"  +- {g['se']:.3f} (se)  95% [{g['ci95'][0]:.3f}, {g['ci95'][1]:.3f}] (normal approx.)"
+            s += f"  min {g['min']:.3f}  max {g['max']:.3f}  n {g['n']}"
+            if g["missing"]:
+                s += f"  ({g['missing']} without an arrival left out)"
+            out.append(s)
+        return out
+
+
+def summarise(counts, sums, episode_return, hist, frames, bin_width):
+    """Host side of the report: the kernel's per-environment numbers (numpy arrays) -> the per-environment lists of
+    :class:`EvalResult` and their aggregates."""
+    K = counts.shape[0]
+    per = {k: [] for k in PER_ENV_KEYS}
+    for b in range(K):
+        n = int(counts[b, 0])
+        per["episode_return"].append(float(episode_return[b]))
+        per["frames"].append(int(frames))
+        per["arrived"].append(n)
+        per["on_way"].append(int(counts[b, 1]))
+        per["not_departed"].append(int(counts[b, 2]))
+        if n == 0:
+            for k in ("avg_travel_time", "std_travel_time", "max_travel_time", "p50_travel_time", "p95_travel_time"):
+                per[k].append(None)
+            continue
+        mean = float(sums[b, 0]) / n
+        per["avg_travel_time"].append(mean)
+        per["std_travel_time"].append(math.sqrt(max(0.0, float(sums[b, 1]) / n - mean * mean)))
+        per["max_travel_time"].append(float(sums[b, 2]))
+        per["p50_travel_time"].append(hist_percentile(hist[b], 0.50, bin_width))
+        per["p95_travel_time"].append(hist_percentile(hist[b], 0.95, bin_width))
+    agg = {k: aggregate(v) for k, v in per.items()}
+    return per, agg, sum(1 for n in per["arrived"] if n == 0)
+
+
+class VecEvaluator:
+    def __init__(self, engine, head="embedding", *, emb, temperature=1.0, edge_mlp=None, prior_table=None, dest_slot=None,
+                 prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
+                 keep_actions=False):
+        """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
+        (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
+        or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
+        (graph_transformer). The tensors are read at every frame: views of live parameters evaluate the current policy.
+        ``keep_actions``: also record every frame's action bytes in ``actions`` (T, K, N) uint8 (tests)."""
+        if engine.fs is None:
+            raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
+                                 "represent this graph and there is no fall-back")
+        if head not in HEADS:
+            raise ValueError(f"head must be one of {HEADS}")
+        if head in _MLP_PRECISION and edge_mlp is None:
+            raise ValueError(f"head {head!r} needs edge_mlp (ops.EdgeMlpWeights)")
+        if head == "embedding_dijkstra" and prior_table is None:
+            raise ValueError("head 'embedding_dijkstra' needs prior_table (and dest_slot for a per-destination table)")
+        if head == "graph_transformer" and (gt_pe is None or gt_weights is None):
+            raise ValueError("head 'graph_transformer' needs gt_pe and gt_weights")
+        if int(poll_frames) < 1:
+            raise ValueError("poll_frames must be >= 1")
+        self.eng, self.head = engine, head
+        self.emb = emb
+        self.temperature = float(temperature)
+        self.edge_mlp, self.prior_table, self.dest_slot = edge_mlp, prior_table, dest_slot
+        self.prior_weight, self.gt_pe, self.gt_weights = float(prior_weight), gt_pe, gt_weights
+        self.bin_width, self.num_bins, self.poll_frames = float(bin_width), int(num_bins), int(poll_frames)
+        self.keep_actions = bool(keep_actions)
+        K, N, E, dev = engine.B, engine.N, engine.E, engine.device
+        plan = engine.plan
+        # scratch, allocated once
+        self.log_prob = torch.zeros(K, dtype=torch.float32, device=dev)
+        self.action8 = torch.zeros((K, N), dtype=torch.uint8, device=dev)          # the last frame's action bytes
+        self.summary = {"counts": torch.zeros((K, 3), dtype=torch.int32, device=dev),
+                        "sums": torch.zeros((K, 3), dtype=torch.float64, device=dev),
+                        "episode_return": torch.zeros(K, dtype=torch.float64, device=dev),
+                        "hist": torch.zeros((K, self.num_bins), dtype=torch.int32, device=dev)}
+        self.reward = self.actions = self._flag_host = None
+        if head == "embedding":
+            self.mode8 = torch.zeros((1, N), dtype=torch.uint8, device=dev)
+            self.mode_lp = torch.zeros(1, dtype=torch.float32, device=dev)
+        else:
+            self.logits = torch.empty((K, E), dtype=torch.float32, device=dev)
+            need = int(_lib.load().tarl_graphdist_rollout_scratch_bytes(plan.handle, K))
+            self.dist_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+            if head == "edge_mlp_bf16":
+                self.obs = torch.empty((K, N, 16), dtype=torch.bfloat16, device=dev)
+            elif head != "embedding_dijkstra":
+                self.obs = torch.empty((K, N, 16), dtype=torch.float32, device=dev)
+            if head == "graph_transformer":
+                n = int(_lib.load().tarl_policy_gt_fwd_scratch_floats(plan.handle, K))
+                self.gt_scratch = torch.empty(n, dtype=torch.float32, device=dev)
+
+    @classmethod
+    def from_policy_net(cls, engine, policy_net, prior_dests=None, **kw):
+        """The evaluator of an ``MPNNPolicyNet`` (src/agents/mpnn_agent.py) under its ``policy_head``; the parameter tensors
+        are held as views, so later optimiser steps (in place) are seen. ``prior_dests``: for the per-destination prior,
+        ``(dests, dest_slot)`` of src.agents.base.destination_set over the engine's agent tables."""
+        head = getattr(policy_net, "policy_head", "embedding")
+        args = dict(emb=policy_net.nodes_embedding.weight.data.reshape(-1), prior_weight=getattr(policy_net, "prior_weight", 1.0))
+        if head in _MLP_PRECISION:
+            m = policy_net.edge_mlp
+            args["edge_mlp"] = ops.EdgeMlpWeights(*(p.data for p in (m[0].weight, m[0].bias, m[2].weight, m[2].bias,
+                                                                    m[4].weight, m[4].bias)))
+        elif head == "embedding_dijkstra":
+            if policy_net.resolve_prior_method() == "all_pairs":
+                args["prior_table"] = policy_net.dist_matrix
+            else:       # one column per destination of every environment's agent table, as the trainer builds it
+                from .trainer import VecPPOTrainer
+                if prior_dests is None:
+                    raise ValueError("the per-destination prior needs prior_dests = destination_set(engine.agents, N)")
+                args["prior_table"], args["dest_slot"] = VecPPOTrainer._build_prior_dest(
+                    engine, policy_net.free_flow_weights(), *prior_dests)
+        elif head == "graph_transformer":
+            args["gt_pe"] = policy_net.gt_pe
+            args["gt_weights"] = ops.GtWeights(policy_net.transformer.kernel_tensors())
+        args.update(kw)
+        return cls(engine, head, **args)
+
+    # -- sizes ---------------------------------------------------------------------------------------------------------
+    @property
+    def episode_frames(self):
+        """Frames from a reset until the episode ends: the frame whose step pushes the clock past EPISODE_END is the last
+        (``break_when_any_done=True`` of the reference's rollout)."""
+        return int((EPISODE_END - EPISODE_START) // self.eng.timestep + 1)
+
+    def _reserve(self, T):
+        K, N, dev = self.eng.B, self.eng.N, self.eng.device
+        if self.reward is None or self.reward.size(0) < T:
+            self.reward = torch.zeros((T, K), dtype=torch.float32, device=dev)
+            self._flag_host = torch.zeros(T // self.poll_frames + 2, dtype=torch.int32).pin_memory()
+            if self.keep_actions:
+                self.actions = torch.zeros((T, K, N), dtype=torch.uint8, device=dev)
+
+    # -- the action of one frame -----------------------------------------------------------------------------------------
+    def _logits(self):
+        eng, plan, fs = self.eng, self.eng.plan, self.eng.fs
+        if self.head == "embedding_dijkstra":
+            return ops.fused_prior_logits(plan, fs, eng._x, eng.Nmax, eng.agents, self.emb, self.prior_table,
+                                          self.prior_weight, out=self.logits, dest_slot=self.dest_slot)
+        if self.head == "edge_mlp_bf16":
+            obs = ops.fused_obs16_bf16(plan, fs, eng._x, eng.Nmax, eng.agents, out=self.obs)
+            return ops.policy_edge_mlp(plan, obs, eng.ec, self.edge_mlp, out=self.logits)
+        obs = ops.fused_obs16(plan, fs, eng._x, eng.Nmax, eng.agents, out=self.obs)
+        if self.head == "graph_transformer":
+            return ops.policy_gt_logits(plan, obs, eng.ec, self.gt_pe, self.gt_weights, out=self.logits,
+                                        scratch=self.gt_scratch)
+        return ops.policy_edge_mlp(plan, obs, eng.ec, self.edge_mlp, precision=_MLP_PRECISION[self.head], out=self.logits)
+
+    def _start(self, deterministic):
+        """Once per run, after the reset. The embedding head is state-independent: its MODE action is computed once (B = 1)
+        and loaded into every environment's SELECTED_ROAD bytes, which the frames leave alone; sampled, the engine draws
+        from its own tables."""
+        if self.head != "embedding":
+            return
+        eng = self.eng
+        if deterministic:
+            logits = ops.policy_edge_logits(eng.plan, eng.static_node_features[0], self.emb).view(1, -1)
+            ops.graphdist_mode_rollout(eng.plan, logits, self.temperature, choice8=self.mode8, log_prob=self.mode_lp)
+            self.action8.copy_(self.mode8.expand_as(self.action8))
+            self.log_prob.copy_(self.mode_lp.expand_as(self.log_prob))
+            ops.fused_set_actions(eng.plan, eng.fs, self.action8)
+        else:
+            eng.prepare_policy(self.emb, self.temperature)
+
+    def _frame(self, t, deterministic):
+        eng = self.eng
+        rec = self.actions[t] if self.keep_actions else None
+        if self.head == "embedding":
+            if rec is not None and deterministic:
+                rec.copy_(self.action8)
+            return eng.frame_fused(skip_choice=deterministic, reward=self.reward[t])
+        logits = self._logits()
+        if deterministic:
+            ops.graphdist_mode_rollout(eng.plan, logits, self.temperature, choice8=rec, sel8=eng.fs.sel8,
+                                       log_prob=self.log_prob)
+        else:
+            ops.graphdist_rollout(eng.plan, logits, self.temperature, seed=eng.seed ^ 0x5DEECE66D,
+                                  counter=eng.sample_counter + 1, choice8=rec, sel8=eng.fs.sel8, log_prob=self.log_prob,
+                                  scratch=self.dist_scratch)
+        return eng.frame_fused(skip_choice=True, reward=self.reward[t])
+
+    # -- the evaluation ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def run(self, frames=None, deterministic=True):
+        """Reset the engine, run ``frames`` frames (default: until the episode ends) and return an :class:`EvalResult`."""
+        t_start = time.perf_counter()
+        eng, fs = self.eng, self.eng.fs
+        T = self.episode_frames if frames is None else int(frames)
+        if T < 1:
+            raise ValueError("frames must be >= 1")
+        self._reserve(T)
+        self._flag_host.zero_()
+        fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
+        eng.reset()
+        self._start(bool(deterministic))
+        polls = []                  # (frames queued when the status word was copied, event)
+        seen = False
+        done = 0
+        for t in range(T):
+            self._frame(t, bool(deterministic))
+            done = t + 1
+            if done % self.poll_frames == 0 or done == T:
+                self._flag_host[len(polls)].copy_(fs.flags[0], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                polls.append((done, ev))
+                # look only at copies that have arrived: the launch pipeline is never stalled
+                seen = any(e.query() and int(self._flag_host[j]) & _lib.FLAG_COUNT_AT_NMAX for j, (_, e) in enumerate(polls))
+                if seen:
+                    break
+        polls[-1][1].synchronize()
+        settings = dict(bin_width=self.bin_width, num_bins=self.num_bins, temperature=self.temperature, seed=eng.seed,
+                        env_base=fs.env_base, poll_frames=self.poll_frames, agents=eng.A - 1, nodes=eng.N)
+        res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
+        first = 0
+        for j, (upto, _) in enumerate(polls):
+            v = int(self._flag_host[j])
+            if v & _lib.FLAG_COUNT_AT_NMAX:
+                res.domain_exit, res.domain_exit_frames = True, (first, upto)
+                # frames queued behind the flagged block ran on a state outside the domain (memory-safe: csrc/fused.hip
+                # bounds every slot index by Nmax); the status word is re-armed so that the engine is usable after reset()
+                res.frames_run = upto
+                fs.flags.zero_()
+                res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
+                return res
+            ops.raise_on_flags(v)      # any other bit is a configuration error, as everywhere else
+            first = upto
+        s = ops.episode_summary(eng.agents, reward=self.reward, frames=done, bin_width=self.bin_width,
+                                num_bins=self.num_bins, out=self.summary)
+        host = {k: v.cpu().numpy() for k, v in s.items()}
+        per, res.aggregate, res.envs_without_arrival = summarise(host["counts"], host["sums"], host["episode_return"],
+                                                                 host["hist"], done, self.bin_width)
+        for k, v in per.items():
+            setattr(res, k, v)
+        res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
+        return res

@@ -42,6 +42,8 @@ SIGNATURES = {
     "tarl_graphdist_rollout_scratch_bytes": (C.c_int64, [_p, _i64]),
     "tarl_graphdist_rollout": (C.c_int, [_p, _p, _i64, _f32, _p, _u64, _u64, _p, _p, _p, _p, _p, _p]),
     "tarl_graphdist_mode": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "tarl_graphdist_mode_rollout": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p, _p, _p]),
+    "tarl_episode_summary": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _f32, _i32, _p, _p, _p, _p, _p]),
     "tarl_graphdist_logprob_entropy_fwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _p]),
     "tarl_graphdist_logprob_entropy_bwd": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p, _p, _p, _p, _p]),
     "tarl_policy_edge_logits_fwd": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _p]),

@@ -553,6 +553,71 @@ def graphdist_rollout(plan: Plan, logits, temperature=1.0, *, uniform=None, seed
     return log_prob
 
 
+def graphdist_mode_rollout(plan: Plan, logits, temperature=1.0, *, choice=None, choice8=None, sel8=None, log_prob=None):
+    """mode() + log_prob() of GraphDistribution(logits / temperature) in one launch (bit-identical to softmax -> mode ->
+    logprob): the deterministic action of an evaluation. logits (B, E); outputs written in place where given, as
+    :func:`graphdist_rollout`: choice int32 (B, N), choice8 uint8 (B, N) rank bytes, sel8 uint8 (N, B) = the packed state's
+    SELECTED_ROAD bytes; returns log_prob (B,)."""
+    L = _lib.load()
+    _contig(logits, torch.float32, "logits")
+    E, N = plan.num_edges, plan.num_nodes
+    B = _rows(logits, E, "logits")
+    for name, t, dt, n in (("choice", choice, torch.int32, B * N), ("choice8", choice8, torch.uint8, B * N),
+                           ("sel8", sel8, torch.uint8, B * N)):
+        if t is not None:
+            _contig(t, dt, name)
+            if t.numel() != n:
+                raise ValueError(f"{name} must hold B * num_nodes values")
+    if log_prob is None:
+        log_prob = torch.empty(B, dtype=torch.float32, device=logits.device)
+    else:
+        _contig(log_prob, torch.float32, "log_prob")
+        if log_prob.numel() != B:
+            raise ValueError("log_prob must hold B values")
+    _lib.check(L.tarl_graphdist_mode_rollout(plan.handle, logits.data_ptr(), B, float(temperature), _lib.ptr(choice),
+                                             _lib.ptr(choice8), _lib.ptr(sel8), log_prob.data_ptr(),
+                                             _lib.current_stream()))
+    return log_prob
+
+
+def episode_summary(agent_features, *, reward=None, frames=None, bin_width=10.0, num_bins=720, out=None):
+    """Per-environment summary of an episode from the agent tables ``agent_features`` (B, A, 9) (row 0, the dummy, is
+    skipped) and the per-frame rewards ``reward`` (T, B) (its first ``frames`` rows; None: no return). Returns the dict
+    ``counts`` int32 (B, 3) {arrived, on the way, not departed}, ``sums`` fp64 (B, 3) {sum tt, sum tt^2, max tt} over the
+    arrived agents, ``episode_return`` fp64 (B,), ``hist`` int32 (B, num_bins) travel-time histogram (bin ``min(floor(tt /
+    bin_width), num_bins - 1)``); ``out``: such a dict to write into (allocated once by the caller)."""
+    L = _lib.load()
+    if agent_features.dim() != 3:
+        raise ValueError("agent_features must be (B, A, 9)")
+    B = agent_features.size(0)
+    A, abs_ = _agents(agent_features, B)
+    T = 0
+    if reward is not None:
+        _contig(reward, torch.float32, "reward")
+        if reward.dim() != 2 or reward.size(1) != B:
+            raise ValueError("reward must be (T, B)")
+        T = reward.size(0) if frames is None else int(frames)
+        if not 0 <= T <= reward.size(0):
+            raise ValueError("frames must be in [0, reward.size(0)]")
+    if int(num_bins) < 1 or not float(bin_width) > 0.0:
+        raise ValueError("num_bins must be >= 1 and bin_width positive")
+    dev = agent_features.device
+    if out is None:
+        out = {"counts": torch.empty((B, 3), dtype=torch.int32, device=dev),
+               "sums": torch.empty((B, 3), dtype=torch.float64, device=dev),
+               "episode_return": torch.empty(B, dtype=torch.float64, device=dev),
+               "hist": torch.empty((B, int(num_bins)), dtype=torch.int32, device=dev)}
+    for name, dt, shp in (("counts", torch.int32, (B, 3)), ("sums", torch.float64, (B, 3)),
+                          ("episode_return", torch.float64, (B,)), ("hist", torch.int32, (B, int(num_bins)))):
+        _contig(out[name], dt, name)
+        if tuple(out[name].shape) != shp:
+            raise ValueError(f"{name} must be {shp}")
+    _lib.check(L.tarl_episode_summary(agent_features.data_ptr(), B, A, abs_, _lib.ptr(reward) if T else None, T,
+                                      float(bin_width), int(num_bins), out["counts"].data_ptr(), out["sums"].data_ptr(),
+                                      out["episode_return"].data_ptr(), out["hist"].data_ptr(), _lib.current_stream()))
+    return out
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")
@@ -1377,14 +1442,17 @@ def _gt_args(plan: Plan, obs16, ec: EdgeConst, pe):
     return obs16.size(0)
 
 
-def policy_gt_logits(plan: Plan, obs16, ec: EdgeConst, pe, w: GtWeights, out=None):
+def policy_gt_logits(plan: Plan, obs16, ec: EdgeConst, pe, w: GtWeights, out=None, scratch=None):
     """The graph-transformer head's logits (M, E) from observations ``obs16`` (M, N, 16) (the :func:`policy_obs16` layout),
-    the edge attribute of ``ec`` and the positional encoding ``pe`` (N, 16); evaluation-mode BatchNorm / dropout."""
+    the edge attribute of ``ec`` and the positional encoding ``pe`` (N, 16); evaluation-mode BatchNorm / dropout.
+    ``scratch``: a caller-owned fp32 buffer of at least tarl_policy_gt_fwd_scratch_floats(plan, M) elements."""
     L = _lib.load()
     M = _gt_args(plan, obs16, ec, pe)
     logits = out if out is not None else torch.empty((M, plan.num_edges), dtype=torch.float32, device=obs16.device)
     n = int(L.tarl_policy_gt_fwd_scratch_floats(plan.handle, M))
-    scratch = torch.empty(n, dtype=torch.float32, device=obs16.device)
+    if scratch is None or scratch.numel() < n:
+        scratch = torch.empty(n, dtype=torch.float32, device=obs16.device)
+    _contig(scratch, torch.float32, "scratch")
     _lib.check(L.tarl_policy_gt_fwd(plan.handle, obs16.data_ptr(), M, ec.edge_attr.data_ptr(), pe.data_ptr(), w.table,
                                     scratch.data_ptr(), n, logits.data_ptr(), _lib.current_stream()))
     return logits
