@@ -143,7 +143,9 @@ int tarl_graphdist_sample(const tarl_plan* plan, const float* proba, int64_t B, 
  *   scratch: tarl_graphdist_rollout_scratch_bytes(plan, B) bytes, 8-byte aligned. Outputs, each nullable: choice int32
  *   [B][N] (edge id, -1 = none); choice8 uint8 [B][N] = the rank byte of the rollout buffers (rank of the chosen
  *   out-edge, or 0x80 | previous rank where nothing was drawn); sel8 uint8 [N][B] = tarl_fused.sel8, updated in place
- *   (== tarl_fused_apply_choice of the drawn action: the choice phase of SimulatorEnv._step, :228-233); log_prob [B]. */
+ *   (== tarl_fused_apply_choice of the drawn action: the choice phase of SimulatorEnv._step, :228-233); log_prob [B].
+ *   choice8 / sel8 need out-degree <= 126 (bit 7 of the byte means "drew nothing"): refused otherwise, before any
+ *   launch; choice alone has no such limit. */
 int64_t tarl_graphdist_rollout_scratch_bytes(const tarl_plan* plan, int64_t B);
 int tarl_graphdist_rollout(const tarl_plan* plan, const float* logits, int64_t B, float temperature, const float* uniform,
                            uint64_t seed, uint64_t counter, void* scratch, int32_t* choice, uint8_t* choice8,

@@ -533,6 +533,8 @@ int tarl_graphdist_rollout_at(const tarl_plan* plan, const float* logits, int64_
   TARL_REQUIRE(B >= 1 && B < ((int64_t)1 << 31), "bad B");
   TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
   TARL_REQUIRE(((uintptr_t)scratch) % 8 == 0, "scratch must be 8-byte aligned");
+  // bit 7 of the rank byte is SEL_CARRIED (as tarl_graphdist_mode_rollout); the int32 edge id alone has no such limit
+  TARL_REQUIRE((!choice8 && !sel8) || plan->max_out <= 126, "out-degree above 126 has no rank byte");
   if (plan->N == 0) return TARL_OK;
   double* base = (double*)scratch;
   float* un = (float*)(base + B * plan->N);
