@@ -258,18 +258,36 @@ def msa_assign(next_hop, od_origin, od_dest, od_volume, is_road, aux_flow):
                                  od_origin.numel(), is_road.data_ptr(), aux_flow.data_ptr(), _lib.current_stream()))
 
 
-def _tree_args(plan: Plan, weights, sources, name):
-    _contig(weights, torch.float64, "weights")
-    _contig(sources, torch.int64, name)
+def _tree_check(plan: Plan, weights, wdtype, roots, name, od=None):
+    """The checks every shortest-path tree wrapper shares (csrc/sp_trees.h), all before the first library call:
+    ``weights`` (E,) of ``wdtype`` and ``roots`` (R,) int64 (``name`` in the messages), both contiguous on the device;
+    ``od`` = the (od_ptr, od_dest, od_volume, is_road, aux_flow) of an assignment. -> R."""
+    _contig(weights, wdtype, "weights")
+    _contig(roots, torch.int64, name)
     if weights.dim() != 1 or weights.numel() != plan.num_edges:
-        raise ValueError(f"weights must be ({plan.num_edges},) float64 in original edge order, got {tuple(weights.shape)}")
-    if sources.dim() != 1:
+        raise ValueError(f"weights must be ({plan.num_edges},) {str(wdtype).split('.')[-1]} in original edge order, got "
+                         f"{tuple(weights.shape)}")
+    if roots.dim() != 1:
         raise ValueError(f"{name} must be 1-D")
+    if od is not None:
+        od_ptr, od_dest, od_volume, is_road, aux_flow = od
+        for t, dt, nm in ((od_ptr, torch.int64, "od_ptr"), (od_dest, torch.int64, "od_dest"),
+                          (od_volume, torch.float64, "od_volume"), (is_road, torch.uint8, "is_road"),
+                          (aux_flow, torch.float64, "aux_flow")):
+            _contig(t, dt, nm)
+        if od_ptr.numel() != roots.numel() + 1 or od_volume.numel() != od_dest.numel():
+            raise ValueError("od_ptr must have num_origins + 1 entries and od_volume one per od_dest")
+        if is_road.numel() != plan.num_nodes or aux_flow.numel() != plan.num_nodes:
+            raise ValueError("is_road and aux_flow need one entry per node")
+    return roots.numel()
+
+
+def _tree_scratch(plan: Plan, weights, R, scratch_query):
+    """-> (L, the bytes ``scratch_query`` asks for R roots, a scratch buffer of that size or None)."""
     L = _lib.load()
-    S = sources.numel()
-    need = int(L.tarl_msa_scratch_bytes(plan.handle, S))
+    need = int(getattr(L, scratch_query)(plan.handle, R))
     scratch = torch.empty(need, dtype=torch.uint8, device=weights.device) if need > 0 else None
-    return L, S, need, scratch
+    return L, need, scratch
 
 
 def shortest_path_trees(plan: Plan, weights, sources, *, want_dist=True, want_pred=True):
@@ -279,7 +297,8 @@ def shortest_path_trees(plan: Plan, weights, sources, *, want_dist=True, want_pr
     the source and unreachable nodes). Rows of out-of-range sources are left as allocated (uninitialised)."""
     if not (want_dist or want_pred):
         raise ValueError("no output requested")
-    L, S, need, scratch = _tree_args(plan, weights, sources, "sources")
+    S = _tree_check(plan, weights, torch.float64, sources, "sources")
+    L, need, scratch = _tree_scratch(plan, weights, S, "tarl_msa_scratch_bytes")
     N = plan.num_nodes
     d = torch.empty((S, N), dtype=torch.float64, device=weights.device) if want_dist else None
     p = torch.empty((S, N), dtype=torch.int32, device=weights.device) if want_pred else None
@@ -292,15 +311,8 @@ def msa_assign_trees(plan: Plan, weights, origins, od_ptr, od_dest, od_volume, i
     """All-or-nothing assignment along per-origin trees (tarl_msa_assign_sssp): the OD pairs sorted by origin, those of
     ``origins[j]`` at ``[od_ptr[j], od_ptr[j+1])``; aux_flow (N,) float64 += volume of every pair on the road nodes of
     its path (origin excluded). Same semantics as :func:`msa_assign` on the all-pairs table."""
-    L, S, need, scratch = _tree_args(plan, weights, origins, "origins")
-    for t, dt, nm in ((od_ptr, torch.int64, "od_ptr"), (od_dest, torch.int64, "od_dest"),
-                      (od_volume, torch.float64, "od_volume"), (is_road, torch.uint8, "is_road"),
-                      (aux_flow, torch.float64, "aux_flow")):
-        _contig(t, dt, nm)
-    if od_ptr.numel() != S + 1 or od_volume.numel() != od_dest.numel():
-        raise ValueError("od_ptr must have num_origins + 1 entries and od_volume one per od_dest")
-    if is_road.numel() != plan.num_nodes or aux_flow.numel() != plan.num_nodes:
-        raise ValueError("is_road and aux_flow need one entry per node")
+    S = _tree_check(plan, weights, torch.float64, origins, "origins", od=(od_ptr, od_dest, od_volume, is_road, aux_flow))
+    L, need, scratch = _tree_scratch(plan, weights, S, "tarl_msa_scratch_bytes")
     _lib.check(L.tarl_msa_assign_sssp(plan.handle, weights.data_ptr(), origins.data_ptr(), S, od_ptr.data_ptr(),
                                       od_dest.data_ptr(), od_volume.data_ptr(), is_road.data_ptr(), _lib.ptr(scratch),
                                       need, aux_flow.data_ptr(), _lib.current_stream()))
@@ -323,18 +335,7 @@ def msa_assign_trees_gap(plan: Plan, weights, origins, od_ptr, od_dest, od_volum
     """:func:`msa_assign_trees` that also returns ``(sptt_part, unrouted_part)``, float64 ``(num_origins,)``: per origin
     the sum, in pair order, of ``volume * dist[dest]`` over its reachable pairs, and the volume of the unreachable ones
     (tarl_msa_assign_sssp_gap; no atomics on these two, so they repeat bit for bit)."""
-    for t, dt, nm in ((weights, torch.float64, "weights"), (origins, torch.int64, "origins"),
-                      (od_ptr, torch.int64, "od_ptr"), (od_dest, torch.int64, "od_dest"),
-                      (od_volume, torch.float64, "od_volume"), (is_road, torch.uint8, "is_road"),
-                      (aux_flow, torch.float64, "aux_flow")):
-        _contig(t, dt, nm)
-    S = origins.numel()
-    if weights.dim() != 1 or weights.numel() != plan.num_edges:
-        raise ValueError(f"weights must be ({plan.num_edges},) float64 in original edge order, got {tuple(weights.shape)}")
-    if od_ptr.numel() != S + 1 or od_volume.numel() != od_dest.numel():
-        raise ValueError("od_ptr must have num_origins + 1 entries and od_volume one per od_dest")
-    if is_road.numel() != plan.num_nodes or aux_flow.numel() != plan.num_nodes:
-        raise ValueError("is_road and aux_flow need one entry per node")
+    S = _tree_check(plan, weights, torch.float64, origins, "origins", od=(od_ptr, od_dest, od_volume, is_road, aux_flow))
     if sptt_part is None:
         sptt_part = torch.zeros(S, dtype=torch.float64, device=weights.device)
     if unrouted_part is None:
@@ -344,7 +345,7 @@ def msa_assign_trees_gap(plan: Plan, weights, origins, od_ptr, od_dest, od_volum
         if t.numel() != S:
             raise ValueError(f"{nm} needs one entry per origin")
     _same_device(weights, origins, od_ptr, od_dest, od_volume, is_road, aux_flow, sptt_part, unrouted_part)
-    L, S, need, scratch = _tree_args(plan, weights, origins, "origins")
+    L, need, scratch = _tree_scratch(plan, weights, S, "tarl_msa_scratch_bytes")
     _lib.check(L.tarl_msa_assign_sssp_gap(plan.handle, weights.data_ptr(), origins.data_ptr(), S, od_ptr.data_ptr(),
                                           od_dest.data_ptr(), od_volume.data_ptr(), is_road.data_ptr(),
                                           _lib.ptr(scratch), need, aux_flow.data_ptr(), sptt_part.data_ptr(),
@@ -445,16 +446,9 @@ def destination_trees(plan: Plan, weights, dests, *, want_next_hop=True, want_di
     as allocated (uninitialised)."""
     if not (want_next_hop or want_dist):
         raise ValueError("no output requested")
-    _contig(weights, torch.float32, "weights")
-    _contig(dests, torch.int64, "dests")
-    if weights.dim() != 1 or weights.numel() != plan.num_edges:
-        raise ValueError(f"weights must be ({plan.num_edges},) float32 in original edge order, got {tuple(weights.shape)}")
-    if dests.dim() != 1:
-        raise ValueError("dests must be 1-D")
-    L = _lib.load()
-    D, N = dests.numel(), plan.num_nodes
-    need = int(L.tarl_dest_trees_scratch_bytes(plan.handle, D))
-    scratch = torch.empty(need, dtype=torch.uint8, device=weights.device) if need > 0 else None
+    D = _tree_check(plan, weights, torch.float32, dests, "dests")
+    L, need, scratch = _tree_scratch(plan, weights, D, "tarl_dest_trees_scratch_bytes")
+    N = plan.num_nodes
     nh = torch.empty((D, N), dtype=torch.int32, device=weights.device) if want_next_hop else None
     d = torch.empty((D, N), dtype=torch.float64, device=weights.device) if want_dist else None
     _lib.check(L.tarl_dest_trees(plan.handle, weights.data_ptr(), dests.data_ptr(), D, _lib.ptr(scratch), need,
@@ -1308,16 +1302,9 @@ def prior_dest_table(plan: Plan, weights, dests):
     order, ``dests`` (D,) int64 -> fp32 (N, D), table[u, j] = the fp32 rounding of the fp64 shortest-path distance
     u -> dests[j] (+inf: unreachable, 0 at the destination). Column j equals the all-pairs ``dist[:, dests[j]]`` wherever
     :func:`destination_trees`' exactness condition holds."""
-    _contig(weights, torch.float32, "weights")
-    _contig(dests, torch.int64, "dests")
-    if weights.dim() != 1 or weights.numel() != plan.num_edges:
-        raise ValueError(f"weights must be ({plan.num_edges},) float32 in original edge order, got {tuple(weights.shape)}")
-    if dests.dim() != 1:
-        raise ValueError("dests must be 1-D")
-    L = _lib.load()
-    D, N = dests.numel(), plan.num_nodes
-    _, need = prior_dest_table_bytes(plan, D)
-    scratch = torch.empty(need, dtype=torch.uint8, device=weights.device) if need > 0 else None
+    D = _tree_check(plan, weights, torch.float32, dests, "dests")
+    L, need, scratch = _tree_scratch(plan, weights, D, "tarl_prior_dest_table_scratch_bytes")
+    N = plan.num_nodes
     table = torch.empty((N, D), dtype=torch.float32, device=weights.device)
     _lib.check(L.tarl_prior_dest_table(plan.handle, weights.data_ptr(), dests.data_ptr(), D, _lib.ptr(scratch), need,
                                        table.data_ptr(), _lib.current_stream()))

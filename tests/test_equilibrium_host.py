@@ -15,13 +15,9 @@ import torch
 from conftest import PKG, ROOT
 
 import equilibrium_restatement as R
+from fake_plan import fake_plan
 
 NEW = ("tarl_msa_assign_sssp_gap", "tarl_msa_assign_gap", "tarl_bpr_step")
-
-
-class _FakePlan(ctypes.Structure):
-    _fields_ = [("N", ctypes.c_int64), ("E", ctypes.c_int64), ("G", ctypes.c_int64)] + \
-               [(f"pad{i}", ctypes.c_int64) for i in range(32)]
 
 
 @pytest.fixture(scope="module")
@@ -75,8 +71,7 @@ def test_assign_gap_entry_points_reject_bad_arguments(L):
     args = list(ok)
     args[5] = 0
     assert L.tarl_msa_assign_gap(*args) == 0                    # nothing to do: no launch
-    p = _FakePlan()
-    p.N, p.E = 100, 400
+    p = fake_plan(100, 400)
     pp = ctypes.byref(p)
     need = L.tarl_msa_scratch_bytes(pp, 3)
     ok = [pp, fake, fake, 3, fake, fake, fake, fake, fake, need, fake, fake, fake, null]

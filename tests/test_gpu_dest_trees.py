@@ -1,9 +1,7 @@
 """GPU: per-destination shortest-path trees (csrc/dest_trees.hip: tarl_dest_trees, tarl_select_next_hop_dest) and
-``DijkstraAgents(method="per_destination")``. The CPU side is restated here: a heapq Dijkstra on the REVERSE graph that
-accumulates fp64 in the kernel's order (w(u,v) + dist[v]), and the documented tie rule of the next hops (fewest hops to
-the destination over tight edges, then the smallest successor id)."""
-import heapq
-import math
+``DijkstraAgents(method="per_destination")``. The CPU side is tree_restatement.py's: a heapq Dijkstra on the REVERSE
+graph that accumulates fp64 in the kernel's order (w(u,v) + dist[v]), and the documented tie rule of the next hops (fewest
+hops to the destination over tight edges, then the smallest successor id)."""
 import os
 import sys
 
@@ -11,9 +9,9 @@ import pytest
 import torch
 
 from conftest import PKG
+from tree_restatement import adjacency, check_table, cpu_dijkstra, cpu_tie_rule
 
 pytestmark = pytest.mark.gpu
-INF = math.inf
 
 
 @pytest.fixture(scope="module")
@@ -23,103 +21,16 @@ def ops():
     return _ops
 
 
-# ---- CPU restatement ------------------------------------------------------------------------------------------------------
-def _reverse(ei, w, N):
-    """In-edges per node: rev[v] = [(u, w(u,v)), ...]."""
-    rev = [[] for _ in range(N)]
-    for u, v, we in zip(ei[0].tolist(), ei[1].tolist(), w.tolist()):
-        rev[v].append((u, we))
-    return rev
-
-
-def cpu_reverse_dijkstra(rev, N, d):
-    """dist[u] = shortest u -> d, summed w1 + (w2 + (...)): Dijkstra from d on the reverse graph."""
-    dist = [INF] * N
-    done = [False] * N
-    dist[d] = 0.0
-    heap = [(0.0, d)]
-    while heap:
-        dv, v = heapq.heappop(heap)
-        if done[v]:
-            continue
-        done[v] = True
-        for u, we in rev[v]:
-            nd = we + dv
-            if nd < dist[u]:
-                dist[u] = nd
-                heapq.heappush(heap, (nd, u))
-    return dist
-
-
-def cpu_tie_rule_next_hop(rev, dist, N, d):
-    """BFS levels backwards from d over the tight edges; next_hop[u] = smallest v of the previous level with a tight
-    edge u -> v. d holds itself, unreached nodes -1."""
-    nh = [-1] * N
-    nh[d] = d
-    seen = [False] * N
-    seen[d] = True
-    level = [d]
-    while level:
-        best = {}
-        for v in level:
-            for u, we in rev[v]:
-                if not seen[u] and dist[u] < INF and we + dist[v] == dist[u]:
-                    if u not in best or v < best[u]:
-                        best[u] = v
-        for u, v in best.items():
-            seen[u] = True
-            nh[u] = v
-        level = sorted(best)
-    return nh
-
-
-def check_table(ei, w, N, dests, dist, nh, walks=0):
-    """Every reachable u != d has its next hop on a tight edge, the table reaches d from every reachable node, and
-    (for ``walks`` sampled nodes per destination) the weights collected along the walk, summed in the kernel's order,
-    give dist[u] exactly."""
-    src, dst = ei[0], ei[1]
-    w64 = w.to(torch.float64)
-    gen = torch.Generator().manual_seed(3)
-    tight_w = {}
-    for u, v, we in zip(src.tolist(), dst.tolist(), w64.tolist()):
-        tight_w.setdefault((u, v), []).append(we)
-    steps = max(1, math.ceil(math.log2(N))) + 1
-    for j, d in enumerate(dests.tolist()):
-        dd, h = dist[j].cpu(), nh[j].cpu().to(torch.int64)
-        reached = torch.isfinite(dd)
-        assert int(h[d]) == d and float(dd[d]) == 0.0
-        assert bool((h[~reached] == -1).all()) and bool((h[reached] >= 0).all())
-        tight = (h[src] == dst) & (w64 + dd[dst] == dd[src])
-        has = torch.zeros(N, dtype=torch.bool).index_put_((src,), tight, accumulate=True)
-        need = reached.clone()
-        need[d] = False
-        assert bool(has[need].all()), f"destination {d}: a next hop off the tight edges"
-        nxt = torch.where(h >= 0, h, torch.full_like(h, d))
-        for _ in range(steps):                                 # pointer doubling: 2^steps >= N hops
-            nxt = nxt[nxt]
-        assert bool((nxt[reached] == d).all()), f"destination {d}: the table does not reach it"
-        cand = torch.nonzero(need).view(-1)
-        for u in cand[torch.randperm(cand.numel(), generator=gen)[:walks]].tolist():
-            ws, node = [], u
-            while node != d:
-                v = int(h[node])
-                ws.append(next(x for x in tight_w[(node, v)] if x + float(dd[v]) == float(dd[node])))
-                node = v
-            s = 0.0
-            for x in reversed(ws):
-                s = x + s
-            assert s == float(dd[u]), f"walk {u} -> {d}"
-
-
 def _check_vs_cpu(ops, plan, ei, w, N, dests, cpu_dests=None, walks=4):
     nh, dist = ops.destination_trees(plan, w.cuda(), dests.cuda(), want_dist=True)
-    rev = _reverse(ei, w, N)
+    rev = adjacency(ei, w, N, reverse=True)
     for j, d in enumerate(dests.tolist()):
         if cpu_dests is not None and d not in cpu_dests:
             continue
-        dc = cpu_reverse_dijkstra(rev, N, d)
+        dc, _ = cpu_dijkstra(rev, N, d, reverse=True)
         assert torch.equal(dist[j].cpu(), torch.tensor(dc, dtype=torch.float64)), f"distances to {d}"
-        want = cpu_tie_rule_next_hop(rev, dc, N, d)
+        want = cpu_tie_rule(rev, dc, N, d, reverse=True)
+        want[d] = d                                            # the destination holds itself, unreached nodes -1
         assert torch.equal(nh[j].cpu(), torch.tensor(want, dtype=torch.int32)), f"tie rule towards {d}"
     check_table(ei, w, N, dests, dist, nh, walks=walks)
     for _ in range(2):                                         # launch after launch: bit for bit

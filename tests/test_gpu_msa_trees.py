@@ -1,8 +1,7 @@
 """GPU: per-origin shortest-path trees (csrc/msa.hip: tarl_sssp_f64, tarl_msa_assign_sssp) and run_msa's
-``method="per_origin"``. The CPU side is restated here: a heapq Dijkstra that accumulates fp64 left to right (the
+``method="per_origin"``. The CPU side is tree_restatement.py's: a heapq Dijkstra that accumulates fp64 left to right (the
 reference's distances bit for bit) and the documented tie rule of the predecessors (fewest hops over tight edges, then
 the smallest predecessor id)."""
-import heapq
 import math
 import os
 import sys
@@ -12,9 +11,9 @@ import pytest
 import torch
 
 from conftest import PKG, load_golden
+from tree_restatement import adjacency, check_tree, cpu_dijkstra, cpu_tie_rule
 
 pytestmark = pytest.mark.gpu
-INF = math.inf
 
 
 @pytest.fixture(scope="module")
@@ -22,80 +21,6 @@ def ops():
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     from tarl_hip import ops as _ops
     return _ops
-
-
-# ---- CPU restatement ------------------------------------------------------------------------------------------------------
-def _adjacency(ei, w, N):
-    out = [[] for _ in range(N)]
-    for u, v, we in zip(ei[0].tolist(), ei[1].tolist(), w.tolist()):
-        out[u].append((v, we))
-    return out
-
-
-def cpu_dijkstra(out, N, s, targets=None):
-    """(dist list, pred list of the settling relaxation). Stops early once every node of ``targets`` is settled."""
-    dist = [INF] * N
-    pred = [-1] * N
-    done = [False] * N
-    left = set(targets) if targets is not None else None
-    dist[s] = 0.0
-    heap = [(0.0, s)]
-    while heap:
-        d, u = heapq.heappop(heap)
-        if done[u]:
-            continue
-        done[u] = True
-        if left is not None:
-            left.discard(u)
-            if not left:
-                break
-        for v, we in out[u]:
-            nd = d + we
-            if nd < dist[v]:
-                dist[v] = nd
-                pred[v] = u
-                heapq.heappush(heap, (nd, v))
-    return dist, pred
-
-
-def cpu_tie_rule_pred(out, dist, N, s):
-    """BFS levels from s over the tight edges; pred[v] = smallest u of the previous level with a tight edge u -> v."""
-    pred = [-1] * N
-    seen = [False] * N
-    seen[s] = True
-    level = [s]
-    while level:
-        best = {}
-        for u in level:
-            for v, we in out[u]:
-                if not seen[v] and dist[v] < INF and dist[u] + we == dist[v]:
-                    if v not in best or u < best[v]:
-                        best[v] = u
-        for v, u in best.items():
-            seen[v] = True
-            pred[v] = u
-        level = sorted(best)
-    return pred
-
-
-def check_tree(ei, w, N, sources, dist, pred):
-    """Every reached v != s has a tight predecessor, and the tree reaches s from every reached node within N steps."""
-    src, dst = ei[0], ei[1]
-    for j, s in enumerate(sources.tolist()):
-        d, p = dist[j].cpu(), pred[j].cpu().to(torch.int64)
-        reached = torch.isfinite(d)
-        assert int(p[s]) == -1 and float(d[s]) == 0.0
-        assert bool((p[~reached] == -1).all())
-        tight = (p[dst] == src) & (d[src] + w == d[dst])
-        has = torch.zeros(N, dtype=torch.bool).index_put_((dst,), tight, accumulate=True)
-        need = reached.clone()
-        need[s] = False
-        assert bool(has[need].all()), f"source {s}: a reached node without a tight predecessor"
-        # pointer doubling: after 2^k >= N steps every reached node must sit on s (an acyclic tree rooted at s)
-        nxt = torch.where(p >= 0, p, torch.full_like(p, s))
-        for _ in range(max(1, math.ceil(math.log2(N))) + 1):
-            nxt = nxt[nxt]
-        assert bool((nxt[reached] == s).all()), f"source {s}: predecessor walk does not reach the source"
 
 
 def _torus(W, H, het, seed=1):
@@ -117,7 +42,7 @@ def test_trees_heterogeneous_torus(ops, W, H, k):
     plan = ops.Plan(ei, N)
     srcs = _sources(N, k, seed=W * H)
     dist, pred = ops.shortest_path_trees(plan, w.cuda(), srcs.cuda())
-    out = _adjacency(ei, w, N)
+    out = adjacency(ei, w, N)
     for j, s in enumerate(srcs.tolist()):
         dc, _ = cpu_dijkstra(out, N, s)
         assert torch.equal(dist[j].cpu(), torch.tensor(dc, dtype=torch.float64)), f"distances from {s}"
@@ -131,11 +56,11 @@ def test_trees_homogeneous_torus_tie_rule(ops):
     plan = ops.Plan(ei, N)
     srcs = torch.arange(0, N, 7, dtype=torch.int64)
     dist, pred = ops.shortest_path_trees(plan, w.cuda(), srcs.cuda())
-    out = _adjacency(ei, w, N)
+    out = adjacency(ei, w, N)
     for j, s in enumerate(srcs.tolist()):
         dc, _ = cpu_dijkstra(out, N, s)
         assert torch.equal(dist[j].cpu(), torch.tensor(dc, dtype=torch.float64))
-        want = cpu_tie_rule_pred(out, dc, N, s)
+        want = cpu_tie_rule(out, dc, N, s)
         assert torch.equal(pred[j].cpu(), torch.tensor(want, dtype=torch.int32)), f"tie rule from {s}"
     check_tree(ei, w, N, srcs, dist, pred)
     for _ in range(2):
@@ -158,11 +83,11 @@ def test_trees_matsim_grid_src_dest(ops, tmp_path):
     plan = ops.Plan(ei, N)
     srcs = torch.arange(N, dtype=torch.int64)
     dist, pred = ops.shortest_path_trees(plan, w.cuda(), srcs.cuda())
-    out = _adjacency(ei, w, N)
+    out = adjacency(ei, w, N)
     for s in range(N):
         dc, _ = cpu_dijkstra(out, N, s)
         assert torch.equal(dist[s].cpu(), torch.tensor(dc, dtype=torch.float64)), f"distances from {s}"
-        want = cpu_tie_rule_pred(out, dc, N, s)
+        want = cpu_tie_rule(out, dc, N, s)
         assert torch.equal(pred[s].cpu(), torch.tensor(want, dtype=torch.int32)), f"tie rule from {s}"
     assert bool(torch.isinf(dist).any()) and bool((pred == -1).sum() > N)
     check_tree(ei, w, N, srcs, dist, pred)
@@ -272,7 +197,7 @@ def test_per_origin_config5_small_population_vs_cpu(ops):
     got = _flows(run_msa(graph, ag, max_iter=1, method="per_origin"), R)
     ff = net.x[:, 3 * net.Nmax + 2].to(torch.float64)
     w = ff[net.edge_index[1]]
-    out = _adjacency(net.edge_index, w, R)
+    out = adjacency(net.edge_index, w, R)
     feats = ag.agent_features[1:].cpu()
     want = torch.zeros(R, dtype=torch.float64)
     trips = {}

@@ -2,7 +2,6 @@
 tarl_prior_dest_table and the *_dest prior entry points). Every graph here satisfies the exactness condition of
 tarl_dest_trees (exponent span of the weights + ceil(log2 hops) <= 28 bits), which each check asserts; there the table's
 columns, the logits, the draws and the updates equal the all-pairs path bit for bit."""
-import heapq
 import math
 import os
 import sys
@@ -11,6 +10,7 @@ import pytest
 import torch
 
 from conftest import PKG
+from tree_restatement import adjacency, cpu_dijkstra
 
 pytestmark = pytest.mark.gpu
 UNREACHABLE = -1e20
@@ -330,23 +330,6 @@ def test_module_forward_and_dijkstra_logits_per_destination(ops):
 
 
 # ---- a graph beyond the all-pairs limit ------------------------------------------------------------------------------------
-def _host_dijkstra(rev, N, d):
-    """fp64 distances of every node to d over the reversed graph (rev[v] = [(u, w(u, v))])."""
-    dist = [math.inf] * N
-    dist[d] = 0.0
-    pq = [(0.0, d)]
-    while pq:
-        dv, v = heapq.heappop(pq)
-        if dv > dist[v]:
-            continue
-        for u, wu in rev[v]:
-            nd = wu + dv
-            if nd < dist[u]:
-                dist[u] = nd
-                heapq.heappush(pq, (nd, u))
-    return dist
-
-
 def test_large_graph_auto_never_builds_all_pairs(ops):
     """25 x 50 torus (N = 5 000) with auto: per_destination, no dist_matrix, a (N, D) table whose sampled columns equal the
     fp32 rounding of a host fp64 Dijkstra, and a short rollout without flags."""
@@ -373,12 +356,11 @@ def test_large_graph_auto_never_builds_all_pairs(ops):
                                                          l[4].bias], rollout_steps=8, sub_batch_size=16,
                        policy="embedding_dijkstra", prior_free_flow=pol.free_flow_weights(), prior_dests=(dests, slot))
     assert tr.prior_table.shape == (N, dests.numel()) and pol._dist_matrix is None
-    rev = [[] for _ in range(N)]
-    for u, v, we in zip(net.edge_index[0].tolist(), net.edge_index[1].tolist(), ff.cpu().double().tolist()):
-        rev[v].append((u, we))
+    rev = adjacency(net.edge_index, ff.cpu().double(), N, reverse=True)
     table = tr.prior_table.cpu()
     for j in torch.randperm(dests.numel(), generator=torch.Generator().manual_seed(7))[:16].tolist():
-        ref = torch.tensor(_host_dijkstra(rev, N, int(dests[j])), dtype=torch.float64).to(torch.float32)
+        dc, _ = cpu_dijkstra(rev, N, int(dests[j]), reverse=True)
+        ref = torch.tensor(dc, dtype=torch.float64).to(torch.float32)
         assert torch.equal(table[:, j], ref), j
     tr.collect()
     tr.check_flags()

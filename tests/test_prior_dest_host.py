@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import PKG, ROOT
+from fake_plan import fake_plan as _plan
 
 NEW = ("tarl_prior_dest_table_scratch_bytes", "tarl_prior_dest_table", "tarl_policy_prior_logits_dest",
        "tarl_fused_prior_logits_dest", "tarl_fused_rollout_prior_dest")
@@ -19,18 +20,6 @@ NEW = ("tarl_prior_dest_table_scratch_bytes", "tarl_prior_dest_table", "tarl_pol
 def L():
     from tarl_hip import lib
     return lib.load()
-
-
-class _FakePlan(ctypes.Structure):
-    """Leading fields of struct tarl_plan (csrc/tarl_common.h): enough for the host-side checks, no device arrays."""
-    _fields_ = [("N", ctypes.c_int64), ("E", ctypes.c_int64), ("G", ctypes.c_int64)] + \
-               [(f"pad{i}", ctypes.c_int64) for i in range(32)]
-
-
-def _plan(N, E):
-    p = _FakePlan()
-    p.N, p.E = N, E
-    return p
 
 
 def test_cli_prior_method_parsing_and_default():

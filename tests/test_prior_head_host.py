@@ -10,20 +10,9 @@ import pytest
 import torch
 
 from conftest import PKG, ROOT
+from fake_plan import fake_plan as _plan
 
 NEW = ("tarl_policy_prior_logits", "tarl_fused_prior_logits", "tarl_fused_rollout_prior")
-
-
-class _FakePlan(ctypes.Structure):
-    """Leading fields of struct tarl_plan (csrc/tarl_common.h): enough for the host-side checks, no device arrays."""
-    _fields_ = [("N", ctypes.c_int64), ("E", ctypes.c_int64), ("G", ctypes.c_int64)] + \
-               [(f"pad{i}", ctypes.c_int64) for i in range(32)]
-
-
-def _plan(N, E):
-    p = _FakePlan()
-    p.N, p.E = N, E
-    return p
 
 
 @pytest.fixture(scope="module")
