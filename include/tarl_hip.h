@@ -855,6 +855,38 @@ int tarl_select_next_hop_dest(float* x, int64_t B, int64_t x_bstride, int64_t ld
                               const float* agent_features, int64_t num_agents, int64_t a_bstride, const int32_t* dest_slot,
                               const int32_t* next_hop, int64_t num_dests, tarl_stream stream);
 
+/* ---- the shortest-path baseline on the packed state (vectorised evaluation of the dijkstra agent) -----------------------------
+ * K environments that each route on their own congested travel times, on the fused path (csrc/baseline.hip,
+ * csrc/dest_trees.hip). Every refresh: tarl_fused_edge_travel_time, then tarl_dest_trees_batched; every frame:
+ * tarl_fused_select_next_hop_dest, then tarl_fused_frame with the action taken from the packed state.
+ * tarl_fused_edge_travel_time == tarl_edge_travel_time on the packed state: travel_time fp32 [B][E], original edge order,
+ *   max(FREE_FLOW[u], congestion_constant[v] / (MAX[u] + 10 - N[u])) from the count byte of tarl_fused.hdp and the static
+ *   node records. Bit-identical to tarl_edge_travel_time on the x that tarl_fused_export writes.
+ * tarl_dest_trees_batched == tarl_dest_trees for B weight sets: weights fp32 [B][E] with w_bstride floats between the sets
+ *   (0 shares one set), next_hop_out int32 [B][num_dests][N]; slice [b] is tarl_dest_trees on weights[b] bit for bit (the
+ *   same kernel, its workgroups striding over the B * num_dests pairs): distances, tie rule and conventions as above, an
+ *   out-of-range destination writes nothing for its slots.
+ *   scratch: tarl_dest_trees_batched_scratch_bytes(plan, B, num_dests) bytes (O(min(B * num_dests, 1024) x N)); -1 on a
+ *   bad argument (B < 1, num_dests < 0).
+ * tarl_fused_select_next_hop_dest == tarl_select_next_hop_dest on the packed state: for every row i and environment b the
+ *   head id comes from tarl_fused.hdp, the destination from tarl_fused.a_dest [B][num_agents], the next hop from
+ *   next_hop[b * nh_bstride + dest_slot[dest] * N + i] (nh_bstride in int32 elements; 0 shares one table). Written: the sel8
+ *   code = the rank of the out-edge of i whose target is the next hop, or the raw code with the value in tarl_fused.sel when
+ *   no out-edge of i matches (the destination itself, -1, a foreign entry): such a row moves nobody, as in the reference.
+ *   tarl_select_next_hop_dest's rules hold: an empty FIFO reads agent 0; a head, destination or slot out of range leaves the
+ *   row's previous selection untouched. After this call the SELECTED_ROAD column of tarl_fused_export equals, bit for bit,
+ *   the column tarl_select_next_hop_dest writes into the exported x of the same state with environment b's table.
+ *   choice8 (optional) uint8 [B][N]: the rows' sel8 bytes after the call, env-major. */
+int tarl_fused_edge_travel_time(const tarl_plan* plan, const tarl_fused* f, int64_t B, float* travel_time,
+                                tarl_stream stream);
+int64_t tarl_dest_trees_batched_scratch_bytes(const tarl_plan* plan, int64_t B, int64_t num_dests);
+int tarl_dest_trees_batched(const tarl_plan* plan, const float* weights, int64_t B, int64_t w_bstride, const int64_t* dests,
+                            int64_t num_dests, void* scratch, int64_t scratch_bytes, int32_t* next_hop_out,
+                            tarl_stream stream);
+int tarl_fused_select_next_hop_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                                    const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride,
+                                    int64_t num_dests, uint8_t* choice8, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

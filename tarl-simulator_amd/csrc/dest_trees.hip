@@ -6,7 +6,8 @@
 // The trees are sp_trees.h's, from the destination backwards: candidates are marked over the CSC in-lists and pulled over
 // the CSR out-lists, so dist[u] is the fp64 sum w1 + (w2 + (... + wk)) of the shortest path u -> d and the link of a node
 // is its next hop (sp_trees.h states when that equals networkx's left-to-right sum bit for bit). The workgroup's scratch
-// row is (dist fp64 [N], hop int32 [N]), with four N-bit bitmaps in LDS.
+// row is (dist fp64 [N], hop int32 [N]), with four N-bit bitmaps in LDS. tarl_dest_trees_batched runs the same kernel over
+// B weight sets x D destinations (the vectorised baseline of tarl_hip/evaluator.py: one table per environment).
 //
 // k_prior_dest_table runs the distance phase alone for the shortest-path prior head (prior.hip) and writes the fp32
 // rounding of each distance straight into the destination's column of a candidate-major [N][D] table: no next hops, no
@@ -17,7 +18,7 @@ __global__ __launch_bounds__(SPT_BLOCK) void k_dest_trees(
     const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src, const int32_t* __restrict__ out_ptr,
     const int32_t* __restrict__ out_dst, const int32_t* __restrict__ out_eid, const float* __restrict__ w, int64_t N,
     const int64_t* __restrict__ dests, int64_t D, uint8_t* __restrict__ scratch, int64_t row_bytes,
-    int32_t* __restrict__ next_hop_out, double* __restrict__ dist_out) {
+    int32_t* __restrict__ next_hop_out, double* __restrict__ dist_out, int64_t B, int64_t w_bstride) {
   extern __shared__ uint32_t dt_lds[];
   const int tid = threadIdx.x;
   const int32_t W = (int32_t)((N + 31) >> 5);
@@ -28,12 +29,15 @@ __global__ __launch_bounds__(SPT_BLOCK) void k_dest_trees(
   double* dist = (double*)(scratch + (int64_t)blockIdx.x * row_bytes);
   int32_t* hop = (int32_t*)(dist + N);
 
-  for (int64_t j = blockIdx.x; j < D; j += gridDim.x) {
-    const int64_t d64 = dests[j];
+  // the workgroups stride over the B * D (weight set, destination) pairs, pair = b * D + slot: tarl_dest_trees is B = 1
+  for (int64_t j = blockIdx.x; j < B * D; j += gridDim.x) {
+    const int64_t wb = j / D;
+    const int64_t d64 = dests[j - wb * D];
     if (d64 < 0 || d64 >= N) continue;      // uniform: an out-of-range destination writes nothing
     const int32_t d = (int32_t)d64;
-    spt_distances<float, true>(in_ptr, in_src, out_ptr, out_dst, out_eid, w, N, W, tid, d, dist, F, C, V);
-    if (next_hop_out) spt_links<float>(in_ptr, in_src, out_ptr, out_dst, out_eid, w, N, W, tid, dist, hop, F, C, NF, V);
+    const float* wj = w + wb * w_bstride;
+    spt_distances<float, true>(in_ptr, in_src, out_ptr, out_dst, out_eid, wj, N, W, tid, d, dist, F, C, V);
+    if (next_hop_out) spt_links<float>(in_ptr, in_src, out_ptr, out_dst, out_eid, wj, N, W, tid, dist, hop, F, C, NF, V);
 
     // ---- outputs: d on its own slot, -1 where d is unreachable; hop is only valid where the BFS visited (V) ----
     for (int64_t u = tid; u < N; u += SPT_BLOCK) {
@@ -110,7 +114,36 @@ extern "C" int tarl_dest_trees(const tarl_plan* plan, const float* weights, cons
   TARL_REQUIRE(plan && weights && dests, "null argument");
   TARL_REQUIRE(next_hop_out || dist_out, "no output requested");
   return spt_launch(DT_QUERY, k_dest_trees, plan, weights, dests, num_dests, scratch, scratch_bytes, stream, next_hop_out,
-                    dist_out);
+                    dist_out, (int64_t)1, (int64_t)0);
+}
+
+// B weight sets at once: the same kernel over B * num_dests pairs. spt_launch sizes grid and scratch by the roots it is
+// given, so this entry sizes them by the pairs itself.
+extern "C" int64_t tarl_dest_trees_batched_scratch_bytes(const tarl_plan* plan, int64_t B, int64_t num_dests) {
+  if (!plan || B < 1 || num_dests < 0) return -1;
+  return spt_scratch_bytes(plan, B * num_dests, DT_QUERY.node_bytes);
+}
+
+extern "C" int tarl_dest_trees_batched(const tarl_plan* plan, const float* weights, int64_t B, int64_t w_bstride,
+                                       const int64_t* dests, int64_t num_dests, void* scratch, int64_t scratch_bytes,
+                                       int32_t* next_hop_out, tarl_stream stream) {
+  static const spt_query Q = {"tarl_dest_trees_batched", true, 4, 12,
+                              "graph too large for the per-destination trees (N > 327680)",
+                              "scratch too small (tarl_dest_trees_batched_scratch_bytes)"};
+  if (!(plan && weights && dests && next_hop_out)) return spt_invalid(Q, "null argument");
+  if (B < 1 || num_dests < 0 || w_bstride < 0 || (w_bstride != 0 && w_bstride < plan->E)) return spt_invalid(Q, "bad sizes");
+  const int64_t N = plan->N, pairs = B * num_dests;
+  const int64_t lds = 4 * Q.bitmaps * ((N + 31) / 32);
+  if (lds > SPT_LDS_MAX) return spt_invalid(Q, Q.too_large);
+  if (pairs == 0 || N == 0) return TARL_OK;
+  if (!scratch || scratch_bytes < spt_scratch_bytes(plan, pairs, Q.node_bytes)) return spt_invalid(Q, Q.scratch_small);
+  if (lds > 64 * 1024)
+    TARL_CHECK_HIP(hipFuncSetAttribute((const void*)k_dest_trees, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_dest_trees, dim3((unsigned)spt_workgroups(pairs)), dim3(SPT_BLOCK), (size_t)lds, (hipStream_t)stream,
+                     plan->in_ptr, plan->in_src, plan->out_ptr, plan->out_dst, plan->out_eid, weights, N, dests, num_dests,
+                     (uint8_t*)scratch, spt_row_bytes(N, Q.node_bytes), next_hop_out, (double*)nullptr, B, w_bstride);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
 }
 
 extern "C" int tarl_select_next_hop_dest(float* x, int64_t B, int64_t x_bstride, int64_t ldx, int32_t Nmax,

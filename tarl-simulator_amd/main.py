@@ -3,7 +3,8 @@
 --profile, --torch-compile) plus ``--steps`` (used by the reference's README but missing from its parser) and
 ``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method``,
 ``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
-``--checkpoint`` and the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``."""
+``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
+comparison ``--eval-baseline`` and the vectorised dijkstra evaluation ``--dijkstra-envs``."""
 import argparse
 import os
 import sys
@@ -73,6 +74,17 @@ OPTIONS = (
                               "a normal-approximation interval of return and travel times over the K realisations; train: "
                               "eval_vec/* in train_log.jsonl, eval: a printed block, eval_envs.json and eval_envs.csv")),
     ("--eval-sampled", dict(action="store_true", help="--eval-envs: also report a run with sampled actions")),
+    ("--eval-baseline", dict(choices=("none", "dijkstra"), default="none",
+                             help="--eval-envs: also run the shortest-path (dijkstra) router on a second engine with the same "
+                                  "seed, K and population (the same noise streams: common random numbers) and report the "
+                                  "per-environment differences policy - baseline with their standard error; train: "
+                                  "eval_vec_baseline/* and eval_vec_paired/* in train_log.jsonl, eval: two more printed "
+                                  "blocks, `baseline` and `paired` in eval_envs.json, baseline_* columns in eval_envs.csv")),
+    ("--dijkstra-envs", dict(type=int, default=0,
+                             help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
+                                  "vectorised environments (each routing on its own congested travel times, in the "
+                                  "environment's step order); prints the aggregate block, writes dijkstra_envs.json and "
+                                  "dijkstra_envs.csv")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--checkpoint", dict(type=str, default=None,

@@ -13,6 +13,11 @@ environments of its own fused engine, MODE, with ``stochastic_eval`` also sample
 scalars ``eval_vec/*`` (``eval_vec_stochastic/*``) carry the spread over the K realisations of the stochastic simulator
 that the single drop-in rollout cannot give. The ``eval/*`` record is unchanged.
 
+Extension: ``eval_baseline="dijkstra"`` (with ``eval_envs``) evaluates the shortest-path router once, at the first periodic
+evaluation, on a second engine with the same seed, K and population (rank 0 alone, no collective): it is a function of the
+seed only, so its per-environment values are cached, and every record that carries ``eval_vec/*`` also carries
+``eval_vec_baseline/*`` and the paired differences policy - baseline ``eval_vec_paired/*`` (common random numbers).
+
 Extension: ``num_envs`` (default 1) vectorises the rollout over B environments per GPU; under ``torchrun`` every rank
 trains on its own environments and gradients are averaged with one RCCL all-reduce per optimiser step.
 """
@@ -73,20 +78,27 @@ def _evaluate(prefix, deterministic, eval_env, policy_module, frames_per_batch):
     return rec, frames
 
 
-def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature):
-    """The K-environment evaluator of ``ppo_train(eval_envs=K)``: its own fused engine on copies of ``eval_env``'s graph
-    state and agent table (the drop-in environment is left alone), noise seed ``seed + 104729``."""
+def _eval_engine(eval_env, eval_envs, seed, agent_features=None):
+    """A fused engine of its own on copies of ``eval_env``'s graph state and agent table (``agent_features``: another copy
+    of that table to start from; the drop-in environment is left alone), noise seed ``seed + 104729``: two of them see the
+    same noise streams."""
     from tarl_hip import ops
     from tarl_hip.engine import SimEngine
-    from tarl_hip.evaluator import VecEvaluator
     sim = eval_env.simulator
     g = sim.graph
     if not ops.fused_path_supported(g.edge_index, sim.Nmax):
         raise ValueError("eval_envs needs the packed (fused) path, which cannot represent this graph (Nmax > 127, an "
                          "out-degree above 126 or parallel edges): there is no fall-back for the vectorised evaluation")
-    engine = SimEngine(g.x.clone(), g.edge_index, g.edge_attr, sim.Nmax, sim.agent.agent_features.clone(),
-                       congestion_constant=getattr(g, "congestion_constant", None), num_envs=int(eval_envs),
-                       device=g.x.device, timestep=sim.timestep, seed=seed + 104729, fused=True)
+    agents = sim.agent.agent_features if agent_features is None else agent_features
+    return SimEngine(g.x.clone(), g.edge_index, g.edge_attr, sim.Nmax, agents.clone(),
+                     congestion_constant=getattr(g, "congestion_constant", None), num_envs=int(eval_envs),
+                     device=g.x.device, timestep=sim.timestep, seed=seed + 104729, fused=True)
+
+
+def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature):
+    """The K-environment evaluator of ``ppo_train(eval_envs=K)``."""
+    from tarl_hip.evaluator import VecEvaluator
+    engine = _eval_engine(eval_env, eval_envs, seed)
     dests = None
     if getattr(policy_net, "policy_head", "embedding") == "embedding_dijkstra" and \
             policy_net.resolve_prior_method() != "all_pairs":
@@ -109,7 +121,8 @@ def vec_eval_record(prefix, res):
 
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
-              eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0):
+              eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
+              eval_baseline="none"):
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
     from tarl_hip.trainer import VecPPOTrainer
@@ -172,6 +185,13 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature)
                 if eval_envs and eval_env is not None and log is not None else None)
     ppo_train.last_vec_eval = vec_eval
+    if eval_baseline not in ("none", "dijkstra"):
+        raise ValueError(f"eval_baseline must be 'none' or 'dijkstra', got {eval_baseline!r}")
+    if eval_baseline != "none" and not eval_envs:
+        raise ValueError("eval_baseline needs eval_envs > 0")
+    baseline_res = None                       # the router's EvalResult: evaluated once, a function of the seed only
+    # the population as the policy's evaluator saw it (training marks its agents on the way / arrived in this table)
+    baseline_agents = eval_env.simulator.agent.agent_features.clone() if vec_eval is not None and eval_baseline != "none" else None
     frames = 0
     it = 0
     h = sim.h
@@ -212,6 +232,15 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                     res = vec_eval.run(n_eval, deterministic=det)
                     rec.update(vec_eval_record(prefix, res))
                     ppo_train.last_eval[prefix] = res
+                if eval_baseline == "dijkstra":
+                    from tarl_hip.evaluator import VecEvaluator, paired_report, paired_scalars
+                    if baseline_res is None:      # its engine and tables are released once the numbers are cached
+                        baseline_res = VecEvaluator(_eval_engine(eval_env, eval_envs, seed, baseline_agents),
+                                                    "dijkstra").run(n_eval)
+                    rec.update(vec_eval_record("eval_vec_baseline", baseline_res))
+                    rep = paired_report(ppo_train.last_eval["eval_vec"], baseline_res)
+                    rec.update({f"eval_vec_paired/{k}": v for k, v in paired_scalars(rep).items()})
+                    ppo_train.last_eval["eval_vec_baseline"], ppo_train.last_eval["eval_vec_paired"] = baseline_res, rep
         if rec is not None:
             log.write(json.dumps(rec) + "\n")
             log.flush()

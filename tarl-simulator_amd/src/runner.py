@@ -35,6 +35,8 @@ class RunnerArgs:
     equilibrium_max_iter: int = 500      # and its iteration limit per problem
     eval_envs: int = 0             # mpnn / mpnn+ppo: K > 0 adds the vectorised evaluation (tarl_hip.evaluator) on K environments
     eval_sampled: bool = False     # ... and also a sampled one next to the deterministic (MODE) one
+    eval_baseline: str = "none"    # eval_envs: "dijkstra" adds the shortest-path baseline on a second engine + the paired report
+    dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -50,6 +52,16 @@ class RunnerArgs:
                              f"{self.algo!r} (use mpnn or mpnn+ppo)")
         if self.eval_sampled and not self.eval_envs:
             raise ValueError("eval_sampled adds a sampled run to the vectorised evaluation: it needs eval_envs > 0")
+        if self.eval_baseline not in ("none", "dijkstra"):
+            raise ValueError(f"eval_baseline must be 'none' or 'dijkstra', got {self.eval_baseline!r}")
+        if self.eval_baseline != "none" and not (self.eval_envs and self.algo in ("mpnn", "mpnn+ppo")):
+            raise ValueError("eval_baseline compares the vectorised evaluation of a policy network with the shortest-path "
+                             "router: it needs eval_envs > 0 and algo mpnn or mpnn+ppo")
+        if self.dijkstra_envs is None or int(self.dijkstra_envs) < 0:
+            raise ValueError(f"dijkstra_envs must be >= 0, got {self.dijkstra_envs!r}")
+        if self.dijkstra_envs and not (self.algo == "dijkstra" and self.mode == "eval"):
+            raise ValueError("dijkstra_envs evaluates the shortest-path router on the vectorised engine: only with algo "
+                             "'dijkstra' and mode 'eval'")
         if int(self.iterations) < 1:
             raise ValueError(f"iterations must be >= 1, got {self.iterations!r}")
         if self.checkpoint is not None and self.algo in ("random", "dijkstra"):
@@ -140,6 +152,14 @@ class Runner:
             self.agent.load(scenario=a.scenario)
             self.simulator.config_parameters(timestep_size=a.timestep_size, start_time=a.start_end_time[0])
             self.agent.set_time(a.start_end_time[0])
+            if a.dijkstra_envs:
+                from tarl_hip import ops
+                if not ops.fused_path_supported(self.simulator.graph.edge_index, self.simulator.Nmax):
+                    raise ValueError("--dijkstra-envs needs the packed (fused) path, which cannot represent this graph (Nmax "
+                                     "> 127, an out-degree above 126 or parallel edges); there is no fall-back for the "
+                                     "vectorised evaluation: run without --dijkstra-envs")
+                # the population as loaded: the single-environment pass below marks its agents on the way / arrived
+                self._dijkstra_population = self.agent.agent_features.clone()
         elif a.algo in {"mpnn", "mpnn+ppo"}:
             from .agents.mpnn_agent import MPNNPolicyNet, MPNNValueNetSimple
             self.env = SimulatorEnv(device=str(self.device), timestep_size=a.timestep_size,
@@ -223,7 +243,8 @@ class Runner:
                   frames_per_batch=a.rollout_steps, num_epochs=a.epochs, device=self.device,
                   checkpoint_path=(out / "policy.pt") if self.rank == 0 else None,
                   log_dir=str(out) if self.rank == 0 else None, eval_env=eval_env, eval_interval=1,
-                  num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled)
+                  num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled,
+                  eval_baseline=a.eval_baseline)
 
     def eval(self):
         a = self.args
@@ -275,23 +296,60 @@ class Runner:
         if a.eval_envs and a.algo in {"mpnn", "mpnn+ppo"}:
             return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg,
                     "vectorised": self._vectorised_eval(n, out_dir)}
+        if a.dijkstra_envs and a.algo == "dijkstra":
+            return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg,
+                    "vectorised": self._vectorised_dijkstra(n, out_dir)}
         return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg}
+
+    def _eval_engine(self, sim, agent_features, num_envs):
+        """A fused engine of its own for a vectorised evaluation: copies of the graph state and of the agent table, noise
+        seed ``seed + 104729``. Two such engines see the same noise streams (common random numbers)."""
+        from tarl_hip.engine import SimEngine
+        g = sim.graph
+        return SimEngine(g.x.clone(), g.edge_index, g.edge_attr, sim.Nmax, agent_features.clone(),
+                         congestion_constant=getattr(g, "congestion_constant", None), num_envs=int(num_envs),
+                         device=g.x.device, timestep=sim.timestep, seed=self.args.seed + 104729, fused=True)
+
+    @staticmethod
+    def _print_block(title, res):
+        print(f"\n=== {title} ===")
+        print(f"{'frames:':22} {res.frames_run:12d}   ({res.computation_time_ms:.1f} ms)")
+        for line in res.summary_lines():
+            print(line)
+
+    def _vectorised_dijkstra(self, frames, out_dir):
+        """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra":
+        every environment routes on its own congested travel times, in the environment's step order) for the same number of
+        frames as the pass above; prints the aggregate block, writes dijkstra_envs.json / dijkstra_envs.csv in the format of
+        eval_envs.*. -> {"mode": EvalResult}."""
+        import csv
+        import json
+        from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator
+        engine = self._eval_engine(self.simulator, self._dijkstra_population, self.args.dijkstra_envs)
+        res = VecEvaluator(engine, "dijkstra", refresh_rate=self.agent.refresh_rate).run(frames)
+        self._print_block(f"Vectorised evaluation ({res.envs} environments, dijkstra)", res)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        with open(out_dir / "dijkstra_envs.json", "w") as f:
+            json.dump({"mode": res.to_dict()}, f, indent=1)
+        with open(out_dir / "dijkstra_envs.csv", "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
+            w.writeheader()
+            w.writerows(dict(kind="mode", **r) for r in res.rows())
+        return {"mode": res}
 
     def _vectorised_eval(self, frames, out_dir):
         """--eval-envs K: the policy on K environments of a fused engine of its own (copies of the graph state and the agent
         table; noise seed ``seed + 104729``) for the same number of frames as the pass above, MODE and with --eval-sampled
         also sampled: prints the aggregate block(s), writes eval_envs.json (aggregate + settings) and eval_envs.csv (one row
-        per environment). -> {"mode": EvalResult, "sampled": EvalResult or None}."""
+        per environment). With --eval-baseline dijkstra the shortest-path router then runs on a second engine of the same seed,
+        K and population: a ``Baseline (dijkstra)`` block, a paired block, ``baseline`` / ``paired`` in the JSON, ``baseline_*``
+        columns in the CSV. -> {"mode": EvalResult, "sampled": EvalResult or None[, "baseline": EvalResult, "paired": dict]}."""
         import csv
         import json
-        from tarl_hip.engine import SimEngine
         from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator
         from .agents.base import destination_set
         a, sim = self.args, self.env.simulator
-        g = sim.graph
-        engine = SimEngine(g.x.clone(), g.edge_index, g.edge_attr, sim.Nmax, self.policy_net.agent_features.clone(),
-                           congestion_constant=getattr(g, "congestion_constant", None), num_envs=int(a.eval_envs),
-                           device=g.x.device, timestep=sim.timestep, seed=a.seed + 104729, fused=True)
+        engine = self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs)
         dests = None
         if a.policy_head == "embedding_dijkstra" and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
@@ -303,17 +361,30 @@ class Runner:
             res = results[key]
             if res is None:
                 continue
-            print(f"\n=== Vectorised evaluation ({res.envs} environments, {label}) ===")
-            print(f"{'frames:':22} {res.frames_run:12d}   ({res.computation_time_ms:.1f} ms)")
-            for line in res.summary_lines():
-                print(line)
+            self._print_block(f"Vectorised evaluation ({res.envs} environments, {label})", res)
             doc[key] = res.to_dict()
             rows += [dict(kind=key, **r) for r in res.rows()]
+        fields = ("kind", "env") + PER_ENV_KEYS
+        if a.eval_baseline == "dijkstra":
+            # the router on a second engine with the same seed, K and population: the same noise streams as the policy run
+            from tarl_hip.evaluator import paired_lines, paired_report
+            base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), "dijkstra").run(frames)
+            rep = paired_report(results["mode"], base)
+            self._print_block("Baseline (dijkstra)", base)
+            print("\n=== Policy \u2212 baseline (paired) ===")
+            for line in paired_lines(rep):
+                print(line)
+            results["baseline"], results["paired"] = base, rep
+            doc["baseline"], doc["paired"] = base.to_dict(), rep
+            fields += tuple(f"baseline_{k}" for k in PER_ENV_KEYS)
+            by_env = {r["env"]: r for r in base.rows()}
+            for r in rows:
+                r.update({f"baseline_{k}": by_env[r["env"]][k] for k in PER_ENV_KEYS} if r["env"] in by_env else {})
         out_dir.mkdir(parents=True, exist_ok=True)
         with open(out_dir / "eval_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "eval_envs.csv", "w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
+            w = csv.DictWriter(f, fieldnames=fields)
             w.writeheader()
             w.writerows(rows)
         return results

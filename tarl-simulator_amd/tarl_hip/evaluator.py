@@ -14,6 +14,20 @@ ops), the action as SELECTED_ROAD bytes (``ops.graphdist_mode_rollout`` / ``ops.
 Domain exits: a FIFO count that reaches ``Nmax`` leaves the reference's defined domain (the engine's status word). The
 evaluator copies the status word to pinned memory every ``poll_frames`` frames and looks at the copies that have arrived;
 once it sees the flag it queues nothing more, and a run that left the domain returns ``domain_exit=True`` with NO statistics.
+
+The shortest-path baseline (head ``"dijkstra"``): the classical router on the same K environments. Every ``refresh_rate``
+frames (frame 0 included) every environment's own congested travel times are read from the packed state
+(``ops.fused_edge_travel_time``) and one reverse shortest-path tree per (environment, distinct destination of the agent
+tables) is rebuilt (``ops.destination_trees_batched``); every frame each row selects the next hop towards its head agent's
+destination (``ops.fused_select_next_hop_dest``) and the frame runs with that action. The step order is the ENVIRONMENT's —
+choice, core, withdraw / insert, reward (``SimulatorEnv._step``) — and deliberately NOT the classical loop's (insert,
+withdraw, choice, core) of the drop-in ``DijkstraAgents``: the baseline faces exactly the environment the policy faces. The
+noise streams are keyed by (seed, frame counter, env_base + b), so a baseline run on an engine of the same seed sees the
+Gumbel race values of the policy run (common random numbers), and :func:`paired_report` compares the two per environment.
+In that order the core moves a due agent from the last road before its destination ONTO the destination road before the
+withdraw (which collects from roads ADJACENT to the destination) sees it; there the table names the road itself, the row
+moves nobody, and the agent stays: the router delivers only agents whose last hop was delayed. Read its
+``arrived`` with that in mind; the return (the network's occupancy) compares as it stands.
 """
 from __future__ import annotations
 
@@ -28,7 +42,7 @@ from . import lib as _lib
 from . import ops
 from .engine import EPISODE_END, EPISODE_START
 
-HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer")
+HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra")
 _MLP_PRECISION = {"edge_mlp": "x3", "edge_mlp_fp32": "fp32", "edge_mlp_bf16": "bf16"}
 PER_ENV_KEYS = ("episode_return", "frames", "arrived", "on_way", "not_departed", "avg_travel_time", "std_travel_time",
                 "max_travel_time", "p50_travel_time", "p95_travel_time")
@@ -153,15 +167,92 @@ def summarise(counts, sums, episode_return, hist, frames, bin_width):
     return per, agg, sum(1 for n in per["arrived"] if n == 0)
 
 
+PAIRED_METRICS = (("episode_return", "episode_return"), ("arrivals", "arrived"), ("mean_travel_time", "avg_travel_time"),
+                  ("p50_travel_time", "p50_travel_time"), ("p95_travel_time", "p95_travel_time"))
+_PAIRED_SETTINGS = ("seed", "env_base", "bin_width", "num_bins")
+
+
+def paired_report(a: EvalResult, b: EvalResult) -> dict:
+    """Per-environment differences a - b of two evaluations of the SAME environments (same K, seed, env_base and bins,
+    and for two completed runs the same ``frames_run``: ``ValueError`` otherwise) — e.g. a policy against the
+    ``"dijkstra"`` baseline under common random numbers.
+    Per metric of :data:`PAIRED_METRICS`: ``n`` usable pairs (a travel-time metric uses only the environments where BOTH
+    runs had an arrival), the mean of the differences, their sample standard deviation (ddof = 1), ``se = std / sqrt(n)``
+    and ``ci95 = mean -+ 1.96 se``, a NORMAL-APPROXIMATION interval; std, se and ci95 are ``None`` for n < 2, the mean too
+    for n = 0. A run that left the domain has no statistics: ``{"available": False, "reason": ...}`` and no numbers."""
+    if a.envs != b.envs:
+        raise ValueError(f"paired_report needs the same environments: envs {a.envs} / {b.envs}")
+    for k in _PAIRED_SETTINGS:
+        if a.settings.get(k) != b.settings.get(k):
+            raise ValueError(f"paired_report needs equal {k}: {a.settings.get(k)!r} / {b.settings.get(k)!r}")
+    head = {"a": a.head, "b": b.head, "envs": a.envs}
+    if a.domain_exit or b.domain_exit:      # (such a run stopped early: its frames_run is not compared)
+        who = " and ".join(f"{n} ({r.head})" for n, r in (("a", a), ("b", b)) if r.domain_exit)
+        return dict(head, available=False, reason=f"domain exit in {who}: a run that left the domain has no statistics")
+    if a.frames_run != b.frames_run:
+        raise ValueError(f"paired_report needs the same frames: frames_run {a.frames_run} / {b.frames_run}")
+    head["frames_run"] = a.frames_run
+    metrics = {}
+    for name, key in PAIRED_METRICS:
+        d = np.asarray([x - y for x, y in zip(getattr(a, key), getattr(b, key)) if x is not None and y is not None],
+                       dtype=np.float64)
+        m = {"n": int(d.size), "dropped": int(a.envs - d.size), "mean": None, "std": None, "se": None, "ci95": None,
+             "ci95_kind": "normal approximation, mean -+ 1.96 se"}
+        if d.size >= 1:
+            m["mean"] = float(d.mean())
+        if d.size >= 2:
+            std = float(d.std(ddof=1))
+            se = std / math.sqrt(d.size)
+            m.update(std=std, se=se, ci95=(m["mean"] - 1.96 * se, m["mean"] + 1.96 * se))
+        metrics[name] = m
+    return dict(head, available=True, metrics=metrics)
+
+
+def paired_lines(report: dict):
+    """:func:`paired_report` as printable lines."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    out = []
+    for name, m in report["metrics"].items():
+        if m["mean"] is None:
+            out.append(f"{name + ':':22} no usable pair")
+            continue
+        s = f"{name + ':':22} {m['mean']:12.3f}"
+        if m["se"] is not None:
+            s += f"  +- {m['se']:.3f} (se)  95% [{m['ci95'][0]:.3f}, {m['ci95'][1]:.3f}] (normal approx.)"
+        s += f"  n {m['n']}"
+        if m["dropped"]:
+            s += f"  ({m['dropped']} environments without an arrival in one of the runs left out)"
+        out.append(s)
+    return out
+
+
+def paired_scalars(report: dict):
+    """The numbers of :func:`paired_report` as flat ``metric/field`` scalars (the trainer's log records)."""
+    if not report["available"]:
+        return {"available": 0}
+    out = {"available": 1}
+    for name, m in report["metrics"].items():
+        out[f"{name}/n"] = m["n"]
+        for k in ("mean", "se"):
+            if m[k] is not None:
+                out[f"{name}/{k}"] = m[k]
+    return out
+
+
 class VecEvaluator:
-    def __init__(self, engine, head="embedding", *, emb, temperature=1.0, edge_mlp=None, prior_table=None, dest_slot=None,
-                 prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
-                 keep_actions=False):
+    def __init__(self, engine, head="embedding", *, emb=None, temperature=1.0, edge_mlp=None, prior_table=None,
+                 dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
+                 keep_actions=False, refresh_rate=10, baseline_dests=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
         (graph_transformer). The tensors are read at every frame: views of live parameters evaluate the current policy.
-        ``keep_actions``: also record every frame's action bytes in ``actions`` (T, K, N) uint8 (tests)."""
+        ``keep_actions``: also record every frame's action bytes in ``actions`` (T, K, N) uint8 (tests).
+        Head ``"dijkstra"`` (the shortest-path baseline, no ``emb``): ``refresh_rate`` frames between two rebuilds of the K
+        per-environment next-hop tables; ``baseline_dests`` = (dests int64 (D,), dest_slot int32 (N,)) of
+        src.agents.base.destination_set over the engine's agent tables (default: computed here by the same rule). The
+        (K, D, N) int32 table and the tree scratch are allocated once; more than half the free device memory is refused."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -173,8 +264,12 @@ class VecEvaluator:
             raise ValueError("head 'embedding_dijkstra' needs prior_table (and dest_slot for a per-destination table)")
         if head == "graph_transformer" and (gt_pe is None or gt_weights is None):
             raise ValueError("head 'graph_transformer' needs gt_pe and gt_weights")
+        if head != "dijkstra" and emb is None:
+            raise ValueError(f"head {head!r} needs emb (the flat embedding tensor)")
         if int(poll_frames) < 1:
             raise ValueError("poll_frames must be >= 1")
+        if int(refresh_rate) < 1:
+            raise ValueError("refresh_rate must be >= 1")
         self.eng, self.head = engine, head
         self.emb = emb
         self.temperature = float(temperature)
@@ -182,6 +277,7 @@ class VecEvaluator:
         self.prior_weight, self.gt_pe, self.gt_weights = float(prior_weight), gt_pe, gt_weights
         self.bin_width, self.num_bins, self.poll_frames = float(bin_width), int(num_bins), int(poll_frames)
         self.keep_actions = bool(keep_actions)
+        self.refresh_rate = int(refresh_rate)
         K, N, E, dev = engine.B, engine.N, engine.E, engine.device
         plan = engine.plan
         # scratch, allocated once
@@ -195,6 +291,8 @@ class VecEvaluator:
         if head == "embedding":
             self.mode8 = torch.zeros((1, N), dtype=torch.uint8, device=dev)
             self.mode_lp = torch.zeros(1, dtype=torch.float32, device=dev)
+        elif head == "dijkstra":
+            self._init_baseline(baseline_dests)
         else:
             self.logits = torch.empty((K, E), dtype=torch.float32, device=dev)
             need = int(_lib.load().tarl_graphdist_rollout_scratch_bytes(plan.handle, K))
@@ -206,6 +304,32 @@ class VecEvaluator:
             if head == "graph_transformer":
                 n = int(_lib.load().tarl_policy_gt_fwd_scratch_floats(plan.handle, K))
                 self.gt_scratch = torch.empty(n, dtype=torch.float32, device=dev)
+
+    def _init_baseline(self, baseline_dests):
+        """The baseline's buffers, once per evaluator: travel times (K, E), the next-hop table (K, D, N) and the tree scratch
+        (O(min(K D, 1024) N)). Refused beyond half the free device memory, like the graph-transformer critic's store."""
+        eng = self.eng
+        K, N, E, dev = eng.B, eng.N, eng.E, eng.device
+        if baseline_dests is None:      # src.agents.base.destination_set's rule: every distinct DESTINATION, row 0 included
+            d = torch.unique(eng.agents[..., 1].reshape(-1).to(torch.int64))
+            d = d[(d >= 0) & (d < N)].contiguous()
+            slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
+            slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=dev)
+            baseline_dests = (d, slot)
+        self.dests, self.dest_slot = baseline_dests
+        D = int(self.dests.numel())
+        table_bytes, scratch_bytes = ops.destination_trees_batched_bytes(eng.plan, K, D)
+        if scratch_bytes < 0:
+            raise _lib.TarlError("tarl_dest_trees_batched_scratch_bytes refused the evaluator's sizes")
+        free = int(torch.cuda.mem_get_info(dev)[0])
+        if table_bytes + scratch_bytes > free // 2:
+            raise _lib.TarlError(f"the shortest-path baseline's next-hop table ({table_bytes / 2**30:.2f} GiB for K = {K} "
+                                 f"environments x D = {D} destinations x N = {N} nodes) and tree scratch "
+                                 f"({scratch_bytes / 2**30:.2f} GiB) exceed half the free device memory "
+                                 f"({free / 2**30:.2f} GiB free): evaluate fewer environments at a time")
+        self.weights = torch.empty((K, E), dtype=torch.float32, device=dev)
+        self.table = torch.full((K, D, N), -1, dtype=torch.int32, device=dev)
+        self.tree_scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=dev)
 
     @classmethod
     def from_policy_net(cls, engine, policy_net, prior_dests=None, **kw):
@@ -268,7 +392,7 @@ class VecEvaluator:
         and loaded into every environment's SELECTED_ROAD bytes, which the frames leave alone; sampled, the engine draws
         from its own tables."""
         if self.head != "embedding":
-            return
+            return      # (the baseline builds its tables at frame 0: 0 % refresh_rate == 0)
         eng = self.eng
         if deterministic:
             logits = ops.policy_edge_logits(eng.plan, eng.static_node_features[0], self.emb).view(1, -1)
@@ -282,6 +406,14 @@ class VecEvaluator:
     def _frame(self, t, deterministic):
         eng = self.eng
         rec = self.actions[t] if self.keep_actions else None
+        if self.head == "dijkstra":     # choice -> core -> withdraw / insert -> reward: the environment's step order
+            if eng._packed_stale:
+                eng.resync()
+            if t % self.refresh_rate == 0:
+                ops.fused_edge_travel_time(eng.plan, eng.fs, out=self.weights)
+                ops.destination_trees_batched(eng.plan, self.weights, self.dests, out=self.table, scratch=self.tree_scratch)
+            ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec)
+            return eng.frame_fused(skip_choice=True, reward=self.reward[t])
         if self.head == "embedding":
             if rec is not None and deterministic:
                 rec.copy_(self.action8)
@@ -305,6 +437,8 @@ class VecEvaluator:
         T = self.episode_frames if frames is None else int(frames)
         if T < 1:
             raise ValueError("frames must be >= 1")
+        if self.head == "dijkstra" and not deterministic:
+            raise ValueError("head 'dijkstra' has no sampled mode: the shortest-path router is deterministic given the state")
         self._reserve(T)
         self._flag_host.zero_()
         fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
@@ -328,6 +462,8 @@ class VecEvaluator:
         polls[-1][1].synchronize()
         settings = dict(bin_width=self.bin_width, num_bins=self.num_bins, temperature=self.temperature, seed=eng.seed,
                         env_base=fs.env_base, poll_frames=self.poll_frames, agents=eng.A - 1, nodes=eng.N)
+        if self.head == "dijkstra":
+            settings.update(refresh_rate=self.refresh_rate, destinations=int(self.dests.numel()))
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):

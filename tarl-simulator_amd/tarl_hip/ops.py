@@ -473,6 +473,87 @@ def select_next_hop_dest(x, Nmax, agent_features, dest_slot, next_hop):
                                            _lib.current_stream()))
 
 
+# ---- the shortest-path baseline on the packed state (tarl_hip/evaluator.py, head "dijkstra") ---------------------------------
+def fused_edge_travel_time(plan: Plan, fs, out=None):
+    """:func:`edge_travel_time` on the packed state (tarl_fused_edge_travel_time): (B, E) fp32, original edge order,
+    bit-identical to ``edge_travel_time`` on the exported ``x``."""
+    L = _lib.load()
+    E = plan.num_edges
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    if out is None:
+        out = torch.empty((fs.B, E), dtype=torch.float32, device=fs.sel8.device)
+    _contig(out, torch.float32, "out")
+    if out.dim() != 2 or out.size(0) != fs.B or out.size(1) != E:
+        raise ValueError(f"out must be (B, E) = ({fs.B}, {E}), got {tuple(out.shape)}")
+    _lib.check(L.tarl_fused_edge_travel_time(plan.handle, fs.ref, fs.B, out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def destination_trees_batched_bytes(plan: Plan, B: int, num_dests: int):
+    """-> (table bytes, scratch bytes) of :func:`destination_trees_batched` for ``B`` weight sets and ``num_dests``
+    destinations; scratch is -1 for a bad argument."""
+    return (4 * int(B) * int(num_dests) * plan.num_nodes,
+            int(_lib.load().tarl_dest_trees_batched_scratch_bytes(plan.handle, int(B), int(num_dests))))
+
+
+def destination_trees_batched(plan: Plan, weights, dests, *, B=None, out=None, scratch=None):
+    """:func:`destination_trees` for B weight sets at once (tarl_dest_trees_batched): ``weights`` (B, E) fp32, or (E,)
+    with ``B`` given (one set shared by B slices), ``dests`` (D,) int64 -> next_hop int32 (B, D, N); slice ``[b]`` equals
+    ``destination_trees(plan, weights[b], dests)`` bit for bit. ``out`` / ``scratch`` (uint8): caller-owned buffers (rows of
+    out-of-range destinations keep what ``out`` held)."""
+    _contig(weights, torch.float32, "weights")
+    _contig(dests, torch.int64, "dests")
+    E, N = plan.num_edges, plan.num_nodes
+    if weights.dim() == 1 and weights.numel() == E and B is not None:
+        B, stride = int(B), 0
+    elif weights.dim() == 2 and weights.size(1) == E and B in (None, weights.size(0)):
+        B, stride = weights.size(0), E
+    else:
+        raise ValueError(f"weights must be (B, {E}) fp32 in original edge order, or ({E},) with B given, got "
+                         f"{tuple(weights.shape)}")
+    if B < 1 or dests.dim() != 1:
+        raise ValueError("B must be >= 1 and dests 1-D")
+    D = dests.numel()
+    L = _lib.load()
+    need = int(L.tarl_dest_trees_batched_scratch_bytes(plan.handle, B, D))
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=weights.device)
+    _contig(scratch, torch.uint8, "scratch")
+    if out is None:
+        out = torch.empty((B, D, N), dtype=torch.int32, device=weights.device)
+    _contig(out, torch.int32, "out")
+    if tuple(out.shape) != (B, D, N):
+        raise ValueError(f"out must be (B, D, N) = ({B}, {D}, {N}), got {tuple(out.shape)}")
+    _lib.check(L.tarl_dest_trees_batched(plan.handle, weights.data_ptr(), B, stride, dests.data_ptr(), D,
+                                         scratch.data_ptr(), scratch.numel(), out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def fused_select_next_hop_dest(plan: Plan, fs, dest_slot, next_hop, choice8=None):
+    """:func:`select_next_hop_dest` on the packed state (tarl_fused_select_next_hop_dest): the SELECTED_ROAD bytes of ``fs``
+    <- the next hop towards the destination of every row's head agent. ``next_hop`` int32 (D, N) shared by the
+    environments, or (B, D, N) with environment b's table; ``dest_slot`` (N,) int32. ``choice8`` (B, N) uint8 (optional):
+    the rows' bytes after the call, env-major."""
+    L = _lib.load()
+    N = plan.num_nodes
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    _contig(dest_slot, torch.int32, "dest_slot")
+    _contig(next_hop, torch.int32, "next_hop")
+    if dest_slot.dim() != 1 or dest_slot.numel() != N or next_hop.dim() not in (2, 3) or next_hop.size(-1) != N or \
+            (next_hop.dim() == 3 and next_hop.size(0) != fs.B):
+        raise ValueError(f"dest_slot must be ({N},) and next_hop (D, {N}) or ({fs.B}, D, {N}), got "
+                         f"{tuple(dest_slot.shape)} and {tuple(next_hop.shape)}")
+    D = next_hop.size(-2)
+    if choice8 is not None:
+        _contig(choice8, torch.uint8, "choice8")
+        if tuple(choice8.shape) != (fs.B, N):
+            raise ValueError(f"choice8 must be (B, N) = ({fs.B}, {N})")
+    _lib.check(L.tarl_fused_select_next_hop_dest(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, dest_slot.data_ptr(),
+                                                 next_hop.data_ptr(), D * N if next_hop.dim() == 3 else 0, D,
+                                                 _lib.ptr(choice8), _lib.current_stream()))
+    return choice8
+
+
 def reset_state(x, Nmax, agent_features=None):
     L = _lib.load()
     B, N, bs, ldx = _state(x, Nmax)

@@ -9,7 +9,12 @@ agents; embedding head, MODE, --frames frames), warm, median of --reps runs with
     --kernel-envs environments, with the MODE kernel's share of its byte bound (4 B E read + 2 B N written at 6.3 TB/s).
 
     python tools/time_eval.py [--frames 256] [--reps 5] [--envs 1,64,1024] [--train-envs 4096] [--kernel-envs 4096]
-                              [--only kernels|evaluator]
+                              [--only kernels|evaluator] [--head embedding|dijkstra]
+
+``--head dijkstra`` times the shortest-path baseline instead (VecEvaluator head "dijkstra": travel times + K x D reverse
+trees every 10 frames, the select kernel every frame), next to the drop-in ``--algo dijkstra --dijkstra-method
+per_destination`` loop on the same graph and population, and the select kernel alone against its byte count; a K whose
+next-hop table does not fit half the free device memory is reported and left out.
 
 ``--only kernels`` runs the last part alone (the run to put under ``rocprofv3 --kernel-trace --stats``), ``--only evaluator``
 one VecEvaluator evaluation at the largest K (the run behind profiles/eval_kernel_stats.txt)."""
@@ -92,6 +97,81 @@ def time_kernels(r, B, reps):
     print(f"  tarl_graphdist_rollout       {samp:8.1f} us   (the sampler on the same logits: {bound / samp * 100:.1f} %)", flush=True)
 
 
+def dropin_dijkstra(T, reps):
+    """The drop-in classical loop (``--algo dijkstra --dijkstra-method per_destination``): T steps from a fresh set-up."""
+    from src.runner import Runner, RunnerArgs
+
+    def run():
+        r = Runner(RunnerArgs(algo="dijkstra", scenario=SCENARIO, mode="eval", dijkstra_method="per_destination",
+                              start_end_time=[21540, 21540 + T]))
+        r.setup()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(T):
+            r.simulator.run()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    run()
+    out = [run() for _ in range(reps)]
+    return statistics.median(out), min(out), max(out)
+
+
+def time_select(ev, reps):
+    """tarl_fused_select_next_hop_dest alone on the evaluator's last state and tables (HIP events)."""
+    eng = ev.eng
+    us = event_us(lambda: ops.fused_select_next_hop_dest(eng.plan, eng.fs, ev.dest_slot, ev.table), reps)
+    nbytes = 21 * eng.N * eng.B
+    bound = nbytes / (COPY_TBPS * 1e12) * 1e6
+    print(f"  tarl_fused_select_next_hop_dest, K = {eng.B}: {us:8.1f} us   byte count {nbytes / 1e6:.2f} MB (21 B per row and "
+          f"environment) = {bound:.2f} us at {COPY_TBPS} TB/s -> {bound / us * 100:.1f} % of that rate", flush=True)
+
+
+def time_baseline(r, T, reps, envs, only):
+    from tarl_hip import lib
+    print(f"{SCENARIO}, head dijkstra (refresh every 10 frames), {T} frames; wall clock around a device synchronisation, "
+          f"median (min - max) of {reps} runs after one warm-up", flush=True)
+    if only is None:
+        med, lo, hi = dropin_dijkstra(T, reps)
+        base_frame_us = med / T * 1e3
+        print(f"drop-in dijkstra loop, per_destination (1 environment): {med:10.1f} ms ({lo:.1f} - {hi:.1f}) for {T} steps = "
+              f"{base_frame_us:9.1f} us per environment-frame", flush=True)
+    for K in ([max(envs)] if only == "evaluator" else envs):
+        try:
+            ev = VecEvaluator(engine_for(r, K), "dijkstra")
+        except lib.TarlError as exc:
+            print(f"VecEvaluator dijkstra K = {K:5d}: not run: {exc}", flush=True)
+            continue
+        times = []
+        for i in range((1 if only == "evaluator" else reps) + 1):       # run 0 warms up; a line per run keeps long runs visible
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = ev.run(T)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+            print(f"  K = {K}: run {i}{' (warm-up)' if i == 0 else ''} {times[-1]:.1f} ms", flush=True)
+        med, lo, hi = statistics.median(times[1:]), min(times[1:]), max(times[1:])
+        n, D = res.frames_run, res.settings["destinations"]
+        per = med / (n * K) * 1e3
+        trees = K * D * ((n + 9) // 10)
+        note = f" DOMAIN EXIT in frames {res.domain_exit_frames}" if res.domain_exit else ""
+        vs = "" if only else f" ({base_frame_us / per:.1f} x the drop-in loop)"
+        print(f"VecEvaluator dijkstra K = {K:5d}, D = {D}: {med:10.1f} ms ({lo:.1f} - {hi:.1f}) for {n} frames = {per:9.3f} us per "
+              f"environment-frame{vs}; {trees} trees per run{note}", flush=True)
+        if only is None:        # the policy evaluation (embedding head, MODE) at the same K, for comparison
+            pol = VecEvaluator.from_policy_net(engine_for(r, K), r.policy_net)
+            last = []
+            pm, plo, phi = spread(lambda: last.append(pol.run(T)), reps)
+            pn = last[-1].frames_run
+            pnote = f" DOMAIN EXIT in frames {last[-1].domain_exit_frames}" if last[-1].domain_exit else ""
+            print(f"VecEvaluator embedding MODE K = {K:5d}: {pm:10.1f} ms ({plo:.1f} - {phi:.1f}) for {pn} frames = "
+                  f"{pm / (pn * K) * 1e3:9.3f} us per environment-frame{pnote}", flush=True)
+            del pol
+        if only is None:
+            time_select(ev, 20)
+        del ev
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
@@ -100,10 +180,14 @@ def main():
     ap.add_argument("--train-envs", type=int, default=4096)
     ap.add_argument("--kernel-envs", type=int, default=4096)
     ap.add_argument("--only", choices=("kernels", "evaluator"), default=None)
+    ap.add_argument("--head", choices=("embedding", "dijkstra"), default="embedding")
     a = ap.parse_args()
     T = a.frames
     envs = [int(v) for v in a.envs.split(",")]
     r = runner_for(SCENARIO)
+    if a.head == "dijkstra":
+        time_baseline(r, T, a.reps, envs, a.only)
+        return
     if a.only == "kernels":
         time_kernels(r, a.kernel_envs, 20)
         return
