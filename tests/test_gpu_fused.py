@@ -48,6 +48,74 @@ def check_records(ops, plan, fs, x, Nmax, ag, cc, ec):
     assert int((((fs.tl & 1) == 0) | (fs.gc8 > 0)).sum()) > 0
 
 
+def fused_vs_unfused_frames(ops, net, plan, pops, frames, *, with_cc=True, dt=1, raw_sel=None):
+    """The frame loop of test_fused_equals_unfused_frame_by_frame (tests/test_gpu_irregular.py runs it too): ``frames``
+    frames from the empty network with populations ``pops`` (B, A + 1, 9), host-supplied uniforms and Gumbel noise, the
+    per-op chain against the fused frame; actions, log-prob, entropy, state, agents, dtt, the pop and withdraw masks, reward
+    and counts compared at every frame, the maintained records every ten. ``raw_sel`` = (frame, count, rows, values): at
+    that frame SELECTED_ROAD of ``rows`` is overwritten with ``values`` (roads that are no neighbour) on both sides, the
+    fused state packed again, and the next ``count`` frames run without the choice phase, so that the raw codes are what
+    the Direction gather meets. Returns (pops + withdrawals seen, the per-op side's agent table)."""
+    N, Nmax, E = net.num_roads, net.Nmax, net.edge_index.size(1)
+    B, A = pops.size(0), pops.size(1) - 1
+    ec = ops.EdgeConst(net.edge_attr, "cuda")
+    cc = dev(net.congestion_constant) if with_cc else None
+    x1, a1 = dev(net.x.unsqueeze(0).repeat(B, 1, 1)), dev(pops.clone())
+    x2, a2 = x1.clone(), a1.clone()
+    fs = ops.FusedState(plan, B, A + 1, "cuda", Nmax)
+    ops.fused_pack(plan, fs, x2, Nmax, a2, cc, ec=ec)
+    emb = torch.randn(N, generator=torch.Generator().manual_seed(1)).cuda()
+    tables = ops.fused_policy_prepare(plan, fs, emb, 0.9)
+    gen = torch.Generator().manual_seed(2)
+    r1, c1 = torch.empty(B, device="cuda"), torch.empty((B, N), device="cuda")
+    r2, c2 = torch.empty(B, device="cuda"), torch.empty((N, B), device="cuda")
+    ch2 = torch.empty((N, B), dtype=torch.int32, device="cuda")
+    lp2, en2 = torch.empty(B, device="cuda"), torch.empty(B, device="cuda")
+    pop2 = torch.empty((B, N), dtype=torch.uint8, device="cuda")
+    wd2 = torch.empty((B, N), dtype=torch.uint8, device="cuda")
+    dtt2 = torch.empty((B, E), device="cuda")
+    events = 0
+    for s in range(frames):
+        t = 100 + dt * s
+        u_s = dev(torch.rand((B, plan.num_groups), generator=gen))
+        gum = dev(ops.gumbel_from_uniform_cpu(torch.rand((B, E), generator=gen)))
+        if raw_sel is not None and s == raw_sel[0]:
+            rows = torch.as_tensor(raw_sel[2], device="cuda")
+            x1[:, rows, 3 * Nmax + 5] = x2[:, rows, 3 * Nmax + 5] = torch.as_tensor(raw_sel[3], dtype=torch.float32, device="cuda")
+            ops.fused_pack(plan, fs, x2, Nmax, a2, cc, ec=ec)
+            assert bool((fs.sel8[rows] & 0x7F == 0x7F).all())              # carried as raw values
+        draw = raw_sel is None or not raw_sel[0] <= s < raw_sel[0] + raw_sel[1]
+        if draw:
+            # unfused chain
+            logits = ops.policy_edge_logits(plan, x1[:, :, 3 * Nmax:], emb)
+            p = ops.graphdist_softmax(plan, logits, 0.9)
+            _, ch1 = ops.graphdist_sample(plan, p, uniform=u_s, want_onehot=False, want_choice=True)
+            lp1, en1 = ops.graphdist_logprob_entropy(plan, p, choice=ch1)
+            ops.apply_action(plan, x1, Nmax, choice=ch1)
+        dtt1, pop1 = ops.core_step(plan, x1, Nmax, ec, t, congestion_constant=cc, gumbel=gum)
+        wd1 = ops.withdraw_step(plan, x1, Nmax, a1, t)
+        ops.insert_step(x1, Nmax, a1, t, congestion_constant=cc, reward=r1, counts=c1)
+        # fused frame
+        if draw:
+            ops.fused_frame(plan, fs, tables, a2, ec, t, use_cong=with_cc, prev_time=t - dt, uniform=u_s, gumbel=gum,
+                            dtt=dtt2, popped=pop2, withdrawn=wd2, choice=ch2, log_prob=lp2, entropy=en2, reward=r2, counts=c2)
+        else:
+            ops.fused_frame(plan, fs, None, a2, ec, t, use_cong=with_cc, prev_time=t - dt, gumbel=gum, dtt=dtt2,
+                            popped=pop2, withdrawn=wd2, reward=r2, counts=c2)
+        ops.fused_export(plan, fs, x2, Nmax, t)       # back to the reference's column layout
+        if draw:
+            assert torch.equal(ch1, ch2.t()), f"actions frame {s}"
+            assert torch.allclose(lp1, lp2, rtol=LP_RTOL, atol=1e-5) and torch.equal(en1, en2), f"policy frame {s}"
+        assert torch.equal(x1, x2), f"state frame {s}"
+        assert torch.equal(a1, a2), f"agents frame {s}"
+        assert torch.equal(dtt1, dtt2) and torch.equal(pop1, pop2) and torch.equal(wd1, wd2), f"masks frame {s}"
+        assert torch.equal(r1, r2) and torch.equal(c1, c2.t())
+        events += int(pop1.sum()) + int(wd1.sum())
+        if s % 10 == 0 or s == frames - 1:
+            check_records(ops, plan, fs, x2, Nmax, a2, cc, ec)
+    return events, a1
+
+
 @pytest.mark.parametrize("W,H,het,B,A,frames,with_cc,Nmax,tiny,dt,prune", [
     (3, 3, True, 3, 1500, 60, True, None, False, 1, 0.0),
     (4, 4, False, 2, 600, 80, True, None, False, 1, 0.0),
@@ -85,54 +153,11 @@ def test_fused_equals_unfused_frame_by_frame(ops, W, H, het, B, A, frames, with_
         nm = net.Nmax
         net.x[::3, 3 * nm + 0] = torch.tensor([2.0, 3.0]).repeat(net.num_roads)[:net.x[::3].size(0)]
         net.congestion_constant = net.x[:, 3 * nm + 2] * (net.x[:, 3 * nm + 0] + 10 - net.critical_number)
-    N, Nmax, E = net.num_roads, net.Nmax, net.edge_index.size(1)
-    plan = ops.Plan(net.edge_index, N)
+    plan = ops.Plan(net.edge_index, net.num_roads)
     if prune:
-        assert plan.row_siblings == (prune < 0.02) and plan.num_row_chunks > N // 4 and not plan.siblings4
-    ec = ops.EdgeConst(net.edge_attr, "cuda")
-    cc = dev(net.congestion_constant) if with_cc else None
-    pops = torch.stack([synth.population(A, N, seed=40 + b, t0=100, t1=130) for b in range(B)])
-    x1, a1 = dev(net.x.unsqueeze(0).repeat(B, 1, 1)), dev(pops.clone())
-    x2, a2 = x1.clone(), a1.clone()
-    fs = ops.FusedState(plan, B, A + 1, "cuda", Nmax)
-    ops.fused_pack(plan, fs, x2, Nmax, a2, cc, ec=ec)
-    emb = torch.randn(N, generator=torch.Generator().manual_seed(1)).cuda()
-    tables = ops.fused_policy_prepare(plan, fs, emb, 0.9)
-    gen = torch.Generator().manual_seed(2)
-    r1, c1 = torch.empty(B, device="cuda"), torch.empty((B, N), device="cuda")
-    r2, c2 = torch.empty(B, device="cuda"), torch.empty((N, B), device="cuda")
-    ch2 = torch.empty((N, B), dtype=torch.int32, device="cuda")
-    lp2, en2 = torch.empty(B, device="cuda"), torch.empty(B, device="cuda")
-    pop2 = torch.empty((B, N), dtype=torch.uint8, device="cuda")
-    wd2 = torch.empty((B, N), dtype=torch.uint8, device="cuda")
-    dtt2 = torch.empty((B, E), device="cuda")
-    events = 0
-    for s in range(frames):
-        t = 100 + dt * s
-        u_s = dev(torch.rand((B, N), generator=gen))
-        gum = dev(ops.gumbel_from_uniform_cpu(torch.rand((B, E), generator=gen)))
-        # unfused chain
-        logits = ops.policy_edge_logits(plan, x1[:, :, 3 * Nmax:], emb)
-        p = ops.graphdist_softmax(plan, logits, 0.9)
-        _, ch1 = ops.graphdist_sample(plan, p, uniform=u_s, want_onehot=False, want_choice=True)
-        lp1, en1 = ops.graphdist_logprob_entropy(plan, p, choice=ch1)
-        ops.apply_action(plan, x1, Nmax, choice=ch1)
-        dtt1, pop1 = ops.core_step(plan, x1, Nmax, ec, t, congestion_constant=cc, gumbel=gum)
-        wd1 = ops.withdraw_step(plan, x1, Nmax, a1, t)
-        ops.insert_step(x1, Nmax, a1, t, congestion_constant=cc, reward=r1, counts=c1)
-        # fused frame
-        ops.fused_frame(plan, fs, tables, a2, ec, t, use_cong=with_cc, prev_time=t - dt, uniform=u_s, gumbel=gum, dtt=dtt2,
-                        popped=pop2, withdrawn=wd2, choice=ch2, log_prob=lp2, entropy=en2, reward=r2, counts=c2)
-        ops.fused_export(plan, fs, x2, Nmax, t)       # back to the reference's column layout
-        assert torch.equal(ch1, ch2.t()), f"actions frame {s}"
-        assert torch.allclose(lp1, lp2, rtol=LP_RTOL, atol=1e-5) and torch.equal(en1, en2), f"policy frame {s}"
-        assert torch.equal(x1, x2), f"state frame {s}"
-        assert torch.equal(a1, a2), f"agents frame {s}"
-        assert torch.equal(dtt1, dtt2) and torch.equal(pop1, pop2) and torch.equal(wd1, wd2), f"masks frame {s}"
-        assert torch.equal(r1, r2) and torch.equal(c1, c2.t())
-        events += int(pop1.sum()) + int(wd1.sum())
-        if s % 10 == 0 or s == frames - 1:
-            check_records(ops, plan, fs, x2, Nmax, a2, cc, ec)
+        assert plan.row_siblings == (prune < 0.02) and plan.num_row_chunks > net.num_roads // 4 and not plan.siblings4
+    pops = torch.stack([synth.population(A, net.num_roads, seed=40 + b, t0=100, t1=130) for b in range(B)])
+    events, a1 = fused_vs_unfused_frames(ops, net, plan, pops, frames, with_cc=with_cc, dt=dt)
     assert events > 0 and (tiny or float(a1[:, :, 8].sum()) > 0)
 
 
