@@ -24,12 +24,12 @@
 // backwards to the attention; pass E walks them again for Q1 / K1 / V / G and x0. Weight gradients: every one is a sum over
 // items (sample, node) or (sample, edge) of products of two recorded vectors — stage 1 sums fixed chunks of items per output
 // in item order, stage 2 adds the chunk partials in chunk order into the caller's buffers. No atomics: bit-reproducible.
-#include <math.h>
-
+//
+// The node side (the helpers, embedding, projections, the attention + layer body forwards and backwards, the Q / K / V / G
+// gradient walk, the weight-gradient reduction) is gt_core.h, shared with the critic (gt_value.hip). This file keeps the
+// parameter table, the edge side, the gather of the gradients of Q2 / K2 from the edge records, and the entry points.
 #include "fused_common.h"
-
-#define GT_BLOCK 256
-#define GT_CHUNK 1024      // items per stage-1 partial sum of the weight gradients
+#include "gt_core.h"
 
 // ---- the pointer table: trainable parameters in kernel order (GT_NP), then the BatchNorm running statistics -------------
 enum {
@@ -60,66 +60,21 @@ __host__ __device__ constexpr int edge_par(int L) { return L == 0 ? P0_WE_W : P1
 __host__ __device__ constexpr int edge_run(int L) { return L == 0 ? R0_N1E_M : R1_N1E_M; }
 
 // ---- record layouts --------------------------------------------------------------------------------------------------------
-// node record (sample, node): 16-float slots; the forward keeps the first NF_SLOTS, the backward all NB_SLOTS
-enum {
-  NQ1 = 0, NK1, NVG1, NQ2, NK2, NX0, NF_SLOTS,
-  NV1 = NF_SLOTS, NSG, NAGG, NTH1, NY, NH, NR, NSH2, NX1, NOBS, NPE,
-  NGQ2, NGK2, NGX1, NGS, NGH, NGY, NGT, NGAGG, NGQ1, NGK1, NGV, NGG, NGX0, NB_SLOTS
-};
+// node record (sample, node), gt_core.h's per-layer scheme: the forward keeps layer 0's {Q, K, V sigmoid(G), x0} and layer
+// 1's Q, K (NF_SLOTS); the backward also layer 0's activations and gradients, then x1, obs16, pe and the gradients of Q2,
+// K2 and x0 (NB_SLOTS)
+enum { NQ2 = F_LAYER + FQ, NK2, NF_SLOTS };
+enum { NX1 = NF_SLOTS + B_LAYER, NOBS, NPE, NGQ2, NGK2, NGX0, NB_SLOTS };
+static_assert(NF_SLOTS == 6 && NB_SLOTS == 30, "the scratch sizes are part of the ABI");
+using L0 = GtLayer<P0_WQ, R0_N1_M, 0, NF_SLOTS>;
+using L1 = GtLayer<P1_WQ, -1, F_LAYER, -1>;          // Q and K alone: no statistics, no backward slots of its own
+static_assert(P0_N2_B - P0_WQ == LN2_B && P1_WK - P1_WQ == LWK && R0_N2_V - R0_N1_M == LN2_V, "not gt_core.h's layer block");
+enum { NQ1 = L0::F + FQ, NK1 = L0::F + FK };
 // edge record (sample, edge), backward only: 18 slots per layer, then the edge attribute and the logit's gradient
 enum { EIN = 0, EE, EQ, EIJ, ETH, EZ, EH, ER, ESH, EOUT, EGE, EGT, EGZ, EGH, EGS, EGOUT, EGIN, EGQ, E_LAYER_SLOTS };
 enum { E_ATTR = 2 * E_LAYER_SLOTS, E_GLOGIT, E_SLOTS };
 // hoisted per-edge / per-node constants: [E][32] = {e0, E1}, then [N][16] = P
 #define HOIST_E 32
-
-__device__ __forceinline__ void ld16(const float* __restrict__ p, float* v) {
-  const float4* q = reinterpret_cast<const float4*>(p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float4 t = q[i];
-    v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
-  }
-}
-__device__ __forceinline__ void st16(float* __restrict__ p, const float* v) {
-  float4* q = reinterpret_cast<float4*>(p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-}
-// y = W x (+ b), W [16][16] row-major (nn.Linear), ascending input index
-__device__ __forceinline__ void lin16(const float* __restrict__ W, const float* __restrict__ b, const float* x, float* y) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    float a = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) a += W[i * 16 + j] * x[j];
-    y[i] = b ? a + b[i] : a;
-  }
-}
-// y (+)= W^T g
-__device__ __forceinline__ void lin16t(const float* __restrict__ W, const float* g, float* y, bool acc) {
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    float a = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) a += W[i * 16 + j] * g[i];
-    y[j] = acc ? y[j] + a : a;
-  }
-}
-// evaluation-mode BatchNorm1d: out = (x - mean) / sqrt(var + 1e-5) * w + b; xh = the normalised input
-__device__ __forceinline__ void bn16(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ rm,
-                                     const float* __restrict__ rv, const float* x, float* xh, float* out) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    xh[i] = (x[i] - rm[i]) / sqrtf(rv[i] + 1e-5f);
-    out[i] = xh[i] * w[i] + b[i];
-  }
-}
-// gradient through it: g_in = g_out * w / sqrt(var + 1e-5)
-__device__ __forceinline__ void bn16_bwd(const float* __restrict__ w, const float* __restrict__ rv, const float* g, float* gi) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) gi[i] = g[i] * w[i] / sqrtf(rv[i] + 1e-5f);
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---- hoist -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GT_BLOCK) void k_gt_hoist(GtW W, const float* __restrict__ edge_attr,
@@ -136,10 +91,7 @@ __global__ __launch_bounds__(GT_BLOCK) void k_gt_hoist(GtW W, const float* __res
     st16(hoist + gid * HOIST_E + 16, e1);
   } else if (gid < E + N) {
     const int64_t n = gid - E;
-    float p[16], q[16];
-    ld16(pe + n * 16, p);
-    lin16(W.p[P_PE_EMB], nullptr, p, q);
-    st16(hoist + E * HOIST_E + n * 16, q);
+    pe_hoist(W.p[P_PE_EMB], pe + n * 16, hoist + E * HOIST_E + n * 16);
   }
 }
 
@@ -152,44 +104,15 @@ __global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeA(GtW W, const float* __res
   const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
   if (gid >= MN) return;
   const int64_t n = gid % N;
-  float o[16], x0[16], p[16], t[16], g[16];
-  ld16(obs + gid * 16, o);
-  ld16(P + n * 16, p);
-  lin16(W.p[P_NODE_EMB], nullptr, o, x0);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) x0[i] = x0[i] + p[i];
+  float o[16], x0[16], t[16], g[16];
+  embed(W.p[P_NODE_EMB], obs + gid * 16, P + n * 16, o, x0);
   float* r = nrec + gid * NS;
-  lin16(W.p[P0_WQ], nullptr, x0, t);
-  st16(r + NQ1 * 16, t);
-  lin16(W.p[P0_WK], nullptr, x0, t);
-  st16(r + NK1 * 16, t);
-  st16(r + NX0 * 16, x0);
-  lin16(W.p[P0_WV], nullptr, x0, t);
-  lin16(W.p[P0_NG_W], W.p[P0_NG_B], x0, g);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) g[i] = sigmoidf_(g[i]);
+  node_proj<L0, BWD, false>(W, x0, r, t, g);
   if (BWD) {
-    st16(r + NV1 * 16, t);
-    st16(r + NSG * 16, g);
+    float p[16];
     st16(r + NOBS * 16, o);
     ld16(pe + n * 16, p);
     st16(r + NPE * 16, p);
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) t[i] = t[i] * g[i];
-  st16(r + NVG1 * 16, t);
-}
-
-// attention score of in-edge (u -> v) for head h: sum_{d in h} Q_v[d] K_u[d] / 2
-__device__ __forceinline__ void scores4(const float* q, const float* __restrict__ ku, float* s) {
-  float k[16];
-  ld16(ku, k);
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    float a = 0.0f;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) a += q[4 * h + d] * k[4 * h + d];
-    s[h] = a / 2.0f;
   }
 }
 
@@ -204,64 +127,11 @@ __global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeB(GtW W, const int32_t* __r
   if (gid >= MN) return;
   const int64_t m = gid / N, v = gid - m * N;
   float* r = nrec + gid * NS;
-  const float* base = nrec + m * N * NS;
-  float q[16], s[4], mx[4], den[4], agg[16];
-  ld16(r + NQ1 * 16, q);
-  const int k0 = in_ptr[v], k1 = in_ptr[v + 1];
-#pragma unroll
-  for (int h = 0; h < 4; ++h) { mx[h] = -INFINITY; den[h] = 0.0f; }
-  for (int k = k0; k < k1; ++k) {
-    scores4(q, base + (int64_t)in_src[k] * NS + NK1 * 16, s);
-#pragma unroll
-    for (int h = 0; h < 4; ++h) mx[h] = fmaxf(mx[h], s[h]);
-  }
-  for (int k = k0; k < k1; ++k) {
-    scores4(q, base + (int64_t)in_src[k] * NS + NK1 * 16, s);
-#pragma unroll
-    for (int h = 0; h < 4; ++h) den[h] += expf(s[h] - mx[h]);
-  }
-#pragma unroll
-  for (int h = 0; h < 4; ++h) den[h] = den[h] + 1e-16f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) agg[i] = 0.0f;
-  for (int k = k0; k < k1; ++k) {
-    const int64_t u = in_src[k];
-    scores4(q, base + u * NS + NK1 * 16, s);
-    float vg[16];
-    ld16(base + u * NS + NVG1 * 16, vg);
-    float a[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) a[h] = expf(s[h] - mx[h]) / den[h];
-    if (BWD) *reinterpret_cast<float4*>(alpha + (m * E + in_eid[k]) * 4) = make_float4(a[0], a[1], a[2], a[3]);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) agg[i] += a[i >> 2] * vg[i];
-  }
-  float x0[16], t[16], th[16], y[16], hh[16], rr[16], f[16], sh[16], x1[16];
-  ld16(r + NX0 * 16, x0);
-  lin16(W.p[P0_WO_W], W.p[P0_WO_B], agg, t);           // WO(out) + x_ (gt_conv.py:183)
-#pragma unroll
-  for (int i = 0; i < 16; ++i) t[i] = t[i] + x0[i];
-  bn16(W.p[P0_N1_W], W.p[P0_N1_B], W.p[R0_N1_M], W.p[R0_N1_V], t, th, y);
-  lin16(W.p[P0_F0_W], W.p[P0_F0_B], y, hh);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) rr[i] = fmaxf(hh[i], 0.0f);
-  lin16(W.p[P0_F3_W], W.p[P0_F3_B], rr, f);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) f[i] = y[i] + f[i];    // norm2(ffn_in + out) (gt_conv.py:192)
-  bn16(W.p[P0_N2_W], W.p[P0_N2_B], W.p[R0_N2_M], W.p[R0_N2_V], f, sh, x1);
-  lin16(W.p[P1_WQ], nullptr, x1, t);
-  st16(r + NQ2 * 16, t);
-  lin16(W.p[P1_WK], nullptr, x1, t);
-  st16(r + NK2 * 16, t);
-  if (BWD) {
-    st16(r + NAGG * 16, agg);
-    st16(r + NTH1 * 16, th);
-    st16(r + NY * 16, y);
-    st16(r + NH * 16, hh);
-    st16(r + NR * 16, rr);
-    st16(r + NSH2 * 16, sh);
-    st16(r + NX1 * 16, x1);
-  }
+  float x1[16], t[16];
+  layer_fwd<L0, NS, BWD>(W, in_src, in_eid, in_ptr[v], in_ptr[v + 1], r, nrec + m * N * NS,
+                         BWD ? alpha + m * E * 4 : nullptr, x1);
+  node_proj<L1, BWD, true>(W, x1, r, t, nullptr);
+  if (BWD) st16(r + NX1 * 16, x1);
 }
 
 // ---- one edge layer -------------------------------------------------------------------------------------------------------------
@@ -412,52 +282,13 @@ __global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeD(GtW W, const int32_t* __r
 #pragma unroll
     for (int i = 0; i < 16; ++i) gK[i] += a[i] * b[i] / 2.0f;
   }
-  float gx1[16], gs[16], gh[16], gy[16], gt[16], gagg[16];
+  float gx1[16], gt[16], gagg[16];
   lin16t(W.p[P1_WQ], gQ, gx1, false);
   lin16t(W.p[P1_WK], gK, gx1, true);
-  bn16_bwd(W.p[P0_N2_W], W.p[R0_N2_V], gx1, gs);
-  lin16t(W.p[P0_F3_W], gs, gh, false);
-  ld16(r + NH * 16, a);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) gh[i] = a[i] > 0.0f ? gh[i] : 0.0f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) gy[i] = gs[i];
-  lin16t(W.p[P0_F0_W], gh, gy, true);
-  bn16_bwd(W.p[P0_N1_W], W.p[R0_N1_V], gy, gt);
-  lin16t(W.p[P0_WO_W], gt, gagg, false);
   st16(r + NGQ2 * 16, gQ);
   st16(r + NGK2 * 16, gK);
-  st16(r + NGX1 * 16, gx1);
-  st16(r + NGS * 16, gs);
-  st16(r + NGH * 16, gh);
-  st16(r + NGY * 16, gy);
-  st16(r + NGT * 16, gt);
-  st16(r + NGAGG * 16, gagg);
-  // softmax backward per head: g_score = alpha * (g_alpha - sum_k alpha_k g_alpha_k), g_alpha = <g_agg, V_u sigma(G_u)>_head
-  float dot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int k = in_ptr[n]; k < in_ptr[n + 1]; ++k) {
-      const int64_t eid = in_eid[k];
-      ld16(base + (int64_t)in_src[k] * NS + NVG1 * 16, b);
-      const float4 al = *reinterpret_cast<const float4*>(alpha + (m * E + eid) * 4);
-      const float av[4] = {al.x, al.y, al.z, al.w};
-      float ga[4];
-#pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        float s = 0.0f;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) s += gagg[4 * h + d] * b[4 * h + d];
-        ga[h] = s;
-      }
-      if (pass == 0) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) dot[h] += av[h] * ga[h];
-      } else {
-        *reinterpret_cast<float4*>(gscore + (m * E + eid) * 4) =
-            make_float4(av[0] * (ga[0] - dot[0]), av[1] * (ga[1] - dot[1]), av[2] * (ga[2] - dot[2]), av[3] * (ga[3] - dot[3]));
-      }
-    }
-  }
+  body_bwd<L0>(W, r, gx1, gt, gagg);
+  softmax_bwd<L0, NS>(in_src, in_eid, in_ptr[n], in_ptr[n + 1], base, gagg, alpha + m * E * 4, gscore + m * E * 4);
 }
 
 // ---- node pass E: gradients of Q1 / K1 / V1 / G1 and x0 ------------------------------------------------------------------------------
@@ -475,158 +306,44 @@ __global__ __launch_bounds__(GT_BLOCK) void k_gt_nodeE(GtW W, const int32_t* __r
   float* r = nrec + gid * NS;
   const float* base = nrec + m * N * NS;
   const float* eb = erec + m * E * ES;
-  float gQ[16], gK[16], gVG[16], a[16], b[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { gQ[i] = 0.0f; gK[i] = 0.0f; gVG[i] = 0.0f; }
-  for (int k = in_ptr[n]; k < in_ptr[n + 1]; ++k) {
-    const int64_t eid = in_eid[k];
-    ld16(eb + eid * ES + EGQ * 16, a);
-    const float4 gsc = *reinterpret_cast<const float4*>(gscore + (m * E + eid) * 4);
-    const float gv[4] = {gsc.x, gsc.y, gsc.z, gsc.w};
-    ld16(base + (int64_t)in_src[k] * NS + NK1 * 16, b);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) gQ[i] += (a[i] + gv[i >> 2]) * b[i] / 2.0f;
-  }
-  for (int k = out_ptr[n]; k < out_ptr[n + 1]; ++k) {
-    const int64_t eid = out_eid[k], v = out_dst[k];
-    ld16(eb + eid * ES + EGQ * 16, a);
-    const float4 gsc = *reinterpret_cast<const float4*>(gscore + (m * E + eid) * 4);
-    const float gv[4] = {gsc.x, gsc.y, gsc.z, gsc.w};
-    ld16(base + v * NS + NQ1 * 16, b);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) gK[i] += (a[i] + gv[i >> 2]) * b[i] / 2.0f;
-    const float4 al = *reinterpret_cast<const float4*>(alpha + (m * E + eid) * 4);
-    const float av[4] = {al.x, al.y, al.z, al.w};
-    ld16(base + v * NS + NGAGG * 16, b);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) gVG[i] += av[i >> 2] * b[i];
-  }
-  float V[16], sg[16], gV[16], gG[16], gx0[16];
-  ld16(r + NV1 * 16, V);
-  ld16(r + NSG * 16, sg);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    gV[i] = gVG[i] * sg[i];
-    gG[i] = gVG[i] * V[i] * (sg[i] * (1.0f - sg[i]));
-  }
-  ld16(r + NGT * 16, gx0);                 // the residual of WO(out) + x_
-  lin16t(W.p[P0_WQ], gQ, gx0, true);
-  lin16t(W.p[P0_WK], gK, gx0, true);
-  lin16t(W.p[P0_WV], gV, gx0, true);
-  lin16t(W.p[P0_NG_W], gG, gx0, true);
-  st16(r + NGQ1 * 16, gQ);
-  st16(r + NGK1 * 16, gK);
-  st16(r + NGV * 16, gV);
-  st16(r + NGG * 16, gG);
+  float gx0[16];
+  qkvg_bwd<L0, NS, ES>(W, in_src, in_eid, in_ptr[n], in_ptr[n + 1], out_dst, out_eid, out_ptr[n], out_ptr[n + 1], r, base,
+                       alpha + m * E * 4, gscore + m * E * 4, eb + EGQ * 16, gx0);
   st16(r + NGX0 * 16, gx0);
 }
 
-// ---- weight gradients: sum over items of g[i] * a[j] (outer), g[i] (bias) or g[i] * a[i] (BatchNorm weight) ------------------------
-enum { T_OUTER = 0, T_BIAS, T_DIAG };
-struct GtTerm {
-  int16_t param, edge, g, a, kind, rows, cols;
-  int32_t off;    // offset of the parameter's outputs in the partial-sum rows
-};
-#define GT_NTERMS GT_NP_
-struct GtTerms {
-  GtTerm t[GT_NTERMS];
-};
-struct GtG {
-  float* p[GT_NP_];
-};
-
-static GtTerms make_terms(int* nout) {
-  GtTerms T{};
-  int k = 0, off = 0;
-  auto add = [&](int param, int edge, int g, int a, int kind, int rows, int cols) {
-    T.t[k] = GtTerm{(int16_t)param, (int16_t)edge, (int16_t)g, (int16_t)a, (int16_t)kind, (int16_t)rows, (int16_t)cols, off};
-    off += rows * cols;
-    ++k;
-  };
-  add(P_NODE_EMB, 0, NGX0, NOBS, T_OUTER, 16, 16);
-  add(P_PE_EMB, 0, NGX0, NPE, T_OUTER, 16, 16);
-  add(P_EDGE_EMB, 1, EGIN, E_ATTR, T_OUTER, 16, 1);
-  add(P0_WQ, 0, NGQ1, NX0, T_OUTER, 16, 16);
-  add(P0_WK, 0, NGK1, NX0, T_OUTER, 16, 16);
-  add(P0_WV, 0, NGV, NX0, T_OUTER, 16, 16);
-  add(P0_NG_W, 0, NGG, NX0, T_OUTER, 16, 16);
-  add(P0_NG_B, 0, NGG, 0, T_BIAS, 16, 1);
-  add(P0_WO_W, 0, NGT, NAGG, T_OUTER, 16, 16);
-  add(P0_WO_B, 0, NGT, 0, T_BIAS, 16, 1);
-  add(P0_N1_W, 0, NGY, NTH1, T_DIAG, 16, 1);
-  add(P0_N1_B, 0, NGY, 0, T_BIAS, 16, 1);
-  add(P0_F0_W, 0, NGH, NY, T_OUTER, 16, 16);
-  add(P0_F0_B, 0, NGH, 0, T_BIAS, 16, 1);
-  add(P0_F3_W, 0, NGS, NR, T_OUTER, 16, 16);
-  add(P0_F3_B, 0, NGS, 0, T_BIAS, 16, 1);
-  add(P0_N2_W, 0, NGX1, NSH2, T_DIAG, 16, 1);
-  add(P0_N2_B, 0, NGX1, 0, T_BIAS, 16, 1);
+// ---- the weight gradients' terms (gt_core.h); second stream: the edge records ---------------------------------------------------------
+static GtTermList<GT_NP_> make_terms() {
+  GtTermList<GT_NP_> T;
+  T.add(P_NODE_EMB, 0, NGX0, NOBS, T_OUTER, 16, 16);
+  T.add(P_PE_EMB, 0, NGX0, NPE, T_OUTER, 16, 16);
+  T.add(P_EDGE_EMB, 1, EGIN, E_ATTR, T_OUTER, 16, 1);
+  T.add_node_layer<L0>();
   for (int L = 0; L < 2; ++L) {
     const int P = edge_par(L), o = L * E_LAYER_SLOTS;
-    add(P + 0, 1, o + EGE, o + EIN, T_OUTER, 16, 16);
-    add(P + 1, 1, o + EGE, 0, T_BIAS, 16, 1);
-    add(P + 2, 1, o + EGT, o + EIJ, T_OUTER, 16, 16);
-    add(P + 3, 1, o + EGT, 0, T_BIAS, 16, 1);
-    add(P + 4, 1, o + EGZ, o + ETH, T_DIAG, 16, 1);
-    add(P + 5, 1, o + EGZ, 0, T_BIAS, 16, 1);
-    add(P + 6, 1, o + EGH, o + EZ, T_OUTER, 16, 16);
-    add(P + 7, 1, o + EGH, 0, T_BIAS, 16, 1);
-    add(P + 8, 1, o + EGS, o + ER, T_OUTER, 16, 16);
-    add(P + 9, 1, o + EGS, 0, T_BIAS, 16, 1);
-    add(P + 10, 1, o + EGOUT, o + ESH, T_DIAG, 16, 1);
-    add(P + 11, 1, o + EGOUT, 0, T_BIAS, 16, 1);
+    T.add(P + 0, 1, o + EGE, o + EIN, T_OUTER, 16, 16);
+    T.add(P + 1, 1, o + EGE, 0, T_BIAS, 16, 1);
+    T.add(P + 2, 1, o + EGT, o + EIJ, T_OUTER, 16, 16);
+    T.add(P + 3, 1, o + EGT, 0, T_BIAS, 16, 1);
+    T.add(P + 4, 1, o + EGZ, o + ETH, T_DIAG, 16, 1);
+    T.add(P + 5, 1, o + EGZ, 0, T_BIAS, 16, 1);
+    T.add(P + 6, 1, o + EGH, o + EZ, T_OUTER, 16, 16);
+    T.add(P + 7, 1, o + EGH, 0, T_BIAS, 16, 1);
+    T.add(P + 8, 1, o + EGS, o + ER, T_OUTER, 16, 16);
+    T.add(P + 9, 1, o + EGS, 0, T_BIAS, 16, 1);
+    T.add(P + 10, 1, o + EGOUT, o + ESH, T_DIAG, 16, 1);
+    T.add(P + 11, 1, o + EGOUT, 0, T_BIAS, 16, 1);
     if (L == 0) {
-      add(P1_WQ, 0, NGQ2, NX1, T_OUTER, 16, 16);
-      add(P1_WK, 0, NGK2, NX1, T_OUTER, 16, 16);
+      T.add(P1_WQ, 0, NGQ2, NX1, T_OUTER, 16, 16);
+      T.add(P1_WK, 0, NGK2, NX1, T_OUTER, 16, 16);
     }
   }
-  add(P_LIN_W, 1, E_GLOGIT, E_LAYER_SLOTS + EOUT, T_OUTER, 1, 16);
-  add(P_LIN_B, 1, E_GLOGIT, 0, T_BIAS, 1, 1);
-  *nout = off;
+  T.add(P_LIN_W, 1, E_GLOGIT, E_LAYER_SLOTS + EOUT, T_OUTER, 1, 16);
+  T.add(P_LIN_B, 1, E_GLOGIT, 0, T_BIAS, 1, 1);
   return T;
 }
 
-// stage 1: block (term, chunk), one thread per output, items of the chunk in ascending order
-__global__ __launch_bounds__(GT_BLOCK) void k_gt_wgrad1(GtTerms T, const float* __restrict__ nrec,
-                                                        const float* __restrict__ erec, int64_t n_node, int64_t n_edge,
-                                                        int nout, float* __restrict__ partial) {
-  const GtTerm& t = T.t[blockIdx.x];
-  const int64_t items = t.edge ? n_edge : n_node;
-  const int64_t i0 = (int64_t)blockIdx.y * GT_CHUNK;
-  const int o = threadIdx.x;
-  if (i0 >= items || o >= t.rows * t.cols) return;
-  const int64_t stride = t.edge ? E_SLOTS * 16 : NB_SLOTS * 16;
-  const float* S = t.edge ? erec : nrec;
-  const int gi = t.g * 16 + (t.kind == T_OUTER ? o / t.cols : o);
-  const int ai = t.a * 16 + (t.kind == T_OUTER ? o % t.cols : o);
-  const int64_t i1 = i0 + GT_CHUNK < items ? i0 + GT_CHUNK : items;
-  float acc = 0.0f;
-  if (t.kind == T_BIAS) {
-    for (int64_t it = i0; it < i1; ++it) acc += S[it * stride + gi];
-  } else {
-    for (int64_t it = i0; it < i1; ++it) acc += S[it * stride + gi] * S[it * stride + ai];
-  }
-  partial[(int64_t)blockIdx.y * nout + t.off + o] = acc;
-}
-
-// stage 2: the chunk partials in chunk order, added to the caller's gradient
-__global__ __launch_bounds__(GT_BLOCK) void k_gt_wgrad2(GtTerms T, GtG G, int64_t n_node, int64_t n_edge, int nout,
-                                                        const float* __restrict__ partial) {
-  const GtTerm& t = T.t[blockIdx.x];
-  const int o = threadIdx.x;
-  if (o >= t.rows * t.cols) return;
-  const int64_t chunks = ((t.edge ? n_edge : n_node) + GT_CHUNK - 1) / GT_CHUNK;
-  float acc = 0.0f;
-  for (int64_t c = 0; c < chunks; ++c) acc += partial[c * nout + t.off + o];
-  G.p[t.param][o] += acc;
-}
-
 // ---- entry points --------------------------------------------------------------------------------------------------------------------
-static int gt_nout() {
-  static int n = -1;
-  if (n < 0) make_terms(&n);
-  return n;
-}
 static int64_t hoist_floats(const tarl_plan* plan) { return plan->E * HOIST_E + plan->N * 16; }
 
 extern "C" int64_t tarl_policy_gt_fwd_scratch_floats(const tarl_plan* plan, int64_t M) {
@@ -636,8 +353,8 @@ extern "C" int64_t tarl_policy_gt_fwd_scratch_floats(const tarl_plan* plan, int6
 
 extern "C" int64_t tarl_policy_gt_bwd_scratch_floats(const tarl_plan* plan, int64_t M) {
   if (!plan || M < 0) return -1;
-  const int64_t chunks = ceil_div(M * (plan->E > plan->N ? plan->E : plan->N), GT_CHUNK);
-  return hoist_floats(plan) + M * plan->N * NB_SLOTS * 16 + M * plan->E * (E_SLOTS * 16 + 8) + chunks * gt_nout();
+  return hoist_floats(plan) + M * plan->N * NB_SLOTS * 16 + M * plan->E * (E_SLOTS * 16 + 8) +
+         gt_wgrad_chunks(M * plan->N, M * plan->E) * make_terms().nout;
 }
 
 static int gt_check(const tarl_plan* plan, const float* obs16, int64_t M, const float* edge_attr, const float* pe,
@@ -645,10 +362,7 @@ static int gt_check(const tarl_plan* plan, const float* obs16, int64_t M, const 
   TARL_REQUIRE(plan && obs16 && edge_attr && pe && w, "null argument");
   TARL_REQUIRE(M >= 1, "bad sample count");
   TARL_REQUIRE(((uintptr_t)obs16) % 16 == 0 && ((uintptr_t)pe) % 16 == 0, "obs16 / pe must be 16-byte aligned");
-  for (int i = 0; i < GT_NW_; ++i) {
-    TARL_REQUIRE(w[i] != nullptr, "parameter pointer is null");
-    W->p[i] = w[i];
-  }
+  TARL_REQUIRE(gt_table(w, W->p, GT_NW_), "parameter pointer is null");
   return TARL_OK;
 }
 
@@ -707,11 +421,8 @@ extern "C" int tarl_policy_gt_bwd(const tarl_plan* plan, const float* obs16, int
   TARL_REQUIRE(grad_logits && scratch && grads, "null grad_logits / scratch / grads");
   TARL_REQUIRE(((uintptr_t)scratch) % 16 == 0, "scratch must be 16-byte aligned");
   TARL_REQUIRE(scratch_floats >= tarl_policy_gt_bwd_scratch_floats(plan, M), "scratch smaller than tarl_policy_gt_bwd_scratch_floats");
-  GtG G;
-  for (int i = 0; i < GT_NP_; ++i) {
-    TARL_REQUIRE(grads[i] != nullptr, "gradient pointer is null");
-    G.p[i] = grads[i];
-  }
+  GtGrads<GT_NP_> G;
+  TARL_REQUIRE(gt_table(grads, G.p, GT_NP_), "gradient pointer is null");
   if (plan->N == 0) return TARL_OK;
   hipStream_t s = (hipStream_t)stream;
   const int64_t N = plan->N, E = plan->E, MN = M * N, ME = M * E;
@@ -743,16 +454,8 @@ extern "C" int tarl_policy_gt_bwd(const tarl_plan* plan, const float* obs16, int
                      plan->out_dst, plan->out_eid, MN, N, E, nrec, (const float*)erec, (const float*)alpha,
                      (const float*)gscore);
   TARL_LAUNCH_CHECK();
-  int nout = 0;
-  const GtTerms T = make_terms(&nout);
-  const int64_t chunks = ceil_div(MN > ME ? MN : ME, GT_CHUNK);
-  TARL_REQUIRE(chunks < 65536, "too many gradient chunks for one grid dimension");
-  hipLaunchKernelGGL(k_gt_wgrad1, dim3(GT_NTERMS, (unsigned)chunks), dim3(GT_BLOCK), 0, s, T, (const float*)nrec,
-                     (const float*)erec, MN, ME, nout, partial);
-  TARL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_gt_wgrad2, dim3(GT_NTERMS), dim3(GT_BLOCK), 0, s, T, G, MN, ME, nout, (const float*)partial);
-  TARL_LAUNCH_CHECK();
-  return TARL_OK;
+  return gt_wgrad_launch(__func__, "too many gradient chunks for one grid dimension", make_terms(), G, nrec, NB_SLOTS * 16, MN,
+                         erec, E_SLOTS * 16, ME, partial, s);
 }
 
 // the count bytes of the rollout buffers (NUMBER_OF_AGENT after the frame, env-minor [N][B]) from the packed state

@@ -1492,19 +1492,22 @@ GT_BUFFER_KEYS = tuple(f"gt_layers.{L}.{n}.{s}" for L, norms in ((0, ("norm1", "
 class GtWeights:
     """The graph-transformer head's tensors in kernel order (``GT_PARAM_KEYS`` then ``GT_BUFFER_KEYS``), fp32 device tensors
     (contiguous views, no copies); ``tensors`` maps each key to its tensor, e.g. a ``GraphTransformerNet.state_dict()``."""
+    PARAM_KEYS, BUFFER_KEYS = GT_PARAM_KEYS, GT_BUFFER_KEYS
 
     def __init__(self, tensors):
-        self.params = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_PARAM_KEYS]
-        self.buffers = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_BUFFER_KEYS]
+        self.params = [_contig(tensors[k].detach(), torch.float32, k) for k in self.PARAM_KEYS]
+        self.buffers = [_contig(tensors[k].detach(), torch.float32, k) for k in self.BUFFER_KEYS]
         self.table = _ptr_array(self.params + self.buffers)
 
 
-def _gt_args(plan: Plan, obs16, ec: EdgeConst, pe):
+def _gt_args(plan: Plan, obs16, pe, least=0):
+    """Checks the observations (M, N, 16) and the positional encoding (N, 16) of either graph-transformer network; -> M
+    (``least`` = 1: the critic takes no empty batch and says so)."""
     _contig(obs16, torch.float32, "obs16")
     _contig(pe, torch.float32, "pe")
     N = plan.num_nodes
-    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (N, 16):
-        raise ValueError(f"obs16 must be (M, {N}, 16)")
+    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (N, 16) or obs16.size(0) < least:
+        raise ValueError(f"obs16 must be (M, {N}, 16)" + (f" with M >= {least}" if least else ""))
     if tuple(pe.shape) != (N, 16):
         raise ValueError(f"pe must be ({N}, 16)")
     return obs16.size(0)
@@ -1515,7 +1518,7 @@ def policy_gt_logits(plan: Plan, obs16, ec: EdgeConst, pe, w: GtWeights, out=Non
     the edge attribute of ``ec`` and the positional encoding ``pe`` (N, 16); evaluation-mode BatchNorm / dropout.
     ``scratch``: a caller-owned fp32 buffer of at least tarl_policy_gt_fwd_scratch_floats(plan, M) elements."""
     L = _lib.load()
-    M = _gt_args(plan, obs16, ec, pe)
+    M = _gt_args(plan, obs16, pe)
     logits = out if out is not None else torch.empty((M, plan.num_edges), dtype=torch.float32, device=obs16.device)
     n = int(L.tarl_policy_gt_fwd_scratch_floats(plan.handle, M))
     if scratch is None or scratch.numel() < n:
@@ -1545,7 +1548,7 @@ def policy_gt_bwd(plan: Plan, obs16, ec: EdgeConst, pe, w: GtWeights, grad_logit
     ``GT_PARAM_KEYS`` entry, shaped like the parameter. Deterministic (no atomics). ``scratch``: an fp32 device tensor of
     at least ``gt_bwd_scratch_bytes(plan, M) / 4`` elements to reuse across calls (allocated per call when None)."""
     L = _lib.load()
-    M = _gt_args(plan, obs16, ec, pe)
+    M = _gt_args(plan, obs16, pe)
     gl = _contig(grad_logits, torch.float32, "grad_logits")
     if gl.numel() != M * plan.num_edges:
         raise ValueError("grad_logits must be (M, E)")
@@ -1608,25 +1611,10 @@ GT_VALUE_BUFFER_KEYS = tuple(f"gt_layers.{L}.{n}.{s}" for L in (0, 1) for n in (
                              for s in ("running_mean", "running_var"))
 
 
-class GtValueWeights:
+class GtValueWeights(GtWeights):
     """The graph-transformer critic's tensors in kernel order (``GT_VALUE_PARAM_KEYS`` then ``GT_VALUE_BUFFER_KEYS``), fp32
     device tensors (contiguous views, no copies); ``tensors`` maps each key to its tensor."""
-
-    def __init__(self, tensors):
-        self.params = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_VALUE_PARAM_KEYS]
-        self.buffers = [_contig(tensors[k].detach(), torch.float32, k) for k in GT_VALUE_BUFFER_KEYS]
-        self.table = _ptr_array(self.params + self.buffers)
-
-
-def _gtv_args(plan: Plan, obs16, pe):
-    _contig(obs16, torch.float32, "obs16")
-    _contig(pe, torch.float32, "pe")
-    N = plan.num_nodes
-    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (N, 16) or obs16.size(0) < 1:
-        raise ValueError(f"obs16 must be (M, {N}, 16) with M >= 1")
-    if tuple(pe.shape) != (N, 16):
-        raise ValueError(f"pe must be ({N}, 16)")
-    return obs16.size(0)
+    PARAM_KEYS, BUFFER_KEYS = GT_VALUE_PARAM_KEYS, GT_VALUE_BUFFER_KEYS
 
 
 def value_gt_fwd_scratch_bytes(plan: Plan, M: int) -> int:
@@ -1659,7 +1647,7 @@ def value_gt_forward(plan: Plan, obs16, pe, w: GtValueWeights, out=None, scratch
     and the positional encoding ``pe`` (N, 16); evaluation-mode BatchNorm / dropout. ``scratch``: an fp32 device tensor of
     at least ``value_gt_fwd_scratch_bytes(plan, M) / 4`` elements to reuse (allocated per call when None)."""
     L = _lib.load()
-    M = _gtv_args(plan, obs16, pe)
+    M = _gt_args(plan, obs16, pe, least=1)
     value = out if out is not None else torch.empty(M, dtype=torch.float32, device=obs16.device)
     _contig(value, torch.float32, "value")
     if value.numel() != M:
@@ -1675,7 +1663,7 @@ def value_gt_backward(plan: Plan, obs16, pe, w: GtValueWeights, grad_value, grad
     ``GT_VALUE_PARAM_KEYS`` entry, shaped like the parameter. Deterministic (no atomics). ``scratch``: an fp32 device tensor
     of at least ``value_gt_bwd_scratch_bytes(plan, M) / 4`` elements to reuse (allocated per call when None)."""
     L = _lib.load()
-    M = _gtv_args(plan, obs16, pe)
+    M = _gt_args(plan, obs16, pe, least=1)
     gv = _contig(grad_value, torch.float32, "grad_value")
     if gv.numel() != M:
         raise ValueError("grad_value must hold M elements")

@@ -12,7 +12,7 @@ from conftest import PKG, ROOT
 sys.path.insert(0, PKG)
 import gt_restatement as R_  # noqa: E402
 import gt_value_restatement as RV  # noqa: E402
-import test_gpu_gt_head as H  # noqa: E402  (graphs, observations, summation bound of the policy head's tests)
+import gt_cases as H  # noqa: E402  (graphs, observations, summation bound shared with the policy head's tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,19 +59,9 @@ def test_forward_and_backward_match_the_reference_golden():
             assert any(s in "." + k[5:] for s in EDGE_SIDE) and float(v.abs().max()) == 0.0, k
 
 
-def _random_state(seed, scale=0.4):
+def _random_state(seed):
     """Scaled random weights for the critic's keys (as the policy tests' ``_random_state``)."""
-    from tarl_hip import ops
-    sd = H._reference_state(seed)
-    gen = torch.Generator().manual_seed(seed + 1)
-    for k in ops.GT_VALUE_PARAM_KEYS:
-        if k.endswith("weight") and "norm" not in k:
-            sd[k] = torch.randn(sd[k].shape, generator=gen) / sd[k].size(-1) * (1e-4 if k == "node_emb.weight" else 1.0)
-        if k.endswith("bias") or "norm" in k:
-            sd[k] = sd[k] + scale * torch.randn(sd[k].shape, generator=gen)
-    for k in ops.GT_VALUE_BUFFER_KEYS:
-        sd[k] = (torch.rand(16, generator=gen) + 0.5) if k.endswith("var") else 0.3 * torch.randn(16, generator=gen)
-    return sd
+    return H._random_state(seed, critic=True)
 
 
 CASES = [("torus8", 1, "random"), ("torus16", 7, "random"), ("config4", 1, "reference"), ("config4", 7, "random"),
