@@ -887,6 +887,28 @@ int tarl_fused_select_next_hop_dest(const tarl_plan* plan, const tarl_fused* f, 
                                     const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride,
                                     int64_t num_dests, uint8_t* choice8, tarl_stream stream);
 
+/* ---- per-road link counts of a vectorised evaluation ------------------------------------------------------------------------
+ * The reference's compute_node_metrics / plot_daily_counts (src/transportation_simulator.py:563-746) concatenate the per-step
+ * masks response_mpnn.update_history (roads whose head was popped) and agent.withdraw_history (roads with at least one agent
+ * withdrawn), each stamped with the clock at which the step STARTED, bin them by time // 3600 and sum them.
+ * tarl_link_counts_accumulate: counts int32 [B][H][N] += over the F frames f (clock_f = t0 + f * timestep, bin
+ *   h_f = clock_f / bin_seconds - first_bin) of popped[f][b][n] + withdrawn[f][b][n]; popped / withdrawn uint8 [F][B][N], each
+ *   slice as tarl_fused_frame wrote it (0 / 1; only bit 0 of a byte is read, so any other value stays memory-safe and cannot
+ *   carry into a neighbour). One launch for all F frames, one writer per element, no atomics.
+ *   1 <= F <= TARL_LINK_COUNTS_MAX_FRAMES (partial sums are packed 8 bits each and grow by at most 2 per frame). Refused on
+ *   the host, before anything is launched: a first frame below first_bin, a last frame in a bin >= H, timestep < 0,
+ *   bin_seconds < 1.
+ * tarl_link_count_stats: over the K environments of counts_a int32 [K][H][N] — or, with counts_b (nullable, same shape), of
+ *   the per-environment difference a - b (the paired form) — per (row, n), row < H a bin and row == H the episode total
+ *   (the sum over the bins, per environment): sum and sumsq int64 [H + 1][N] (sum d, sum d^2), vmin and vmax int32
+ *   [H + 1][N]. Integer arithmetic only; the caller keeps K * max|d|^2 below 2^63. */
+#define TARL_LINK_COUNTS_MAX_FRAMES 127
+int tarl_link_counts_accumulate(const uint8_t* popped, const uint8_t* withdrawn, int64_t F, int64_t B, int64_t N, int64_t t0,
+                                int64_t timestep, int64_t bin_seconds, int64_t first_bin, int64_t H, int32_t* counts,
+                                tarl_stream stream);
+int tarl_link_count_stats(const int32_t* counts_a, const int32_t* counts_b, int64_t K, int64_t H, int64_t N, int64_t* sum,
+                          int64_t* sumsq, int32_t* vmin, int32_t* vmax, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

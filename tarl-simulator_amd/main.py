@@ -4,7 +4,8 @@
 ``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method``,
 ``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
 ``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
-comparison ``--eval-baseline`` and the vectorised dijkstra evaluation ``--dijkstra-envs``."""
+comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` and the per-road link counts of either
+``--eval-link-counts`` / ``--eval-link-bin``."""
 import argparse
 import os
 import sys
@@ -85,6 +86,13 @@ OPTIONS = (
                                   "vectorised environments (each routing on its own congested travel times, in the "
                                   "environment's step order); prints the aggregate block, writes dijkstra_envs.json and "
                                   "dijkstra_envs.csv")),
+    ("--eval-link-counts", dict(action="store_true",
+                                help="--eval-envs / --dijkstra-envs, eval: count per road the frames in which its head was "
+                                     "popped plus those in which an agent was withdrawn from it, over the K environments; a "
+                                     "`Link counts` block, eval_link_counts.csv (dijkstra_link_counts.csv) with mean, standard "
+                                     "error and interval per road against the MSA (and, with --equilibrium-metrics, UE / SO) "
+                                     "flows and, with --eval-baseline, the paired difference; `link_counts` in the JSON file")),
+    ("--eval-link-bin", dict(type=int, default=3600, metavar="SECONDS", help="--eval-link-counts: width of the time bins")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--checkpoint", dict(type=str, default=None,

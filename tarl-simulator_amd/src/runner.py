@@ -37,6 +37,8 @@ class RunnerArgs:
     eval_sampled: bool = False     # ... and also a sampled one next to the deterministic (MODE) one
     eval_baseline: str = "none"    # eval_envs: "dijkstra" adds the shortest-path baseline on a second engine + the paired report
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
+    eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
+    eval_link_bin: int = 3600      # ... in time bins of this many seconds
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -62,6 +64,11 @@ class RunnerArgs:
         if self.dijkstra_envs and not (self.algo == "dijkstra" and self.mode == "eval"):
             raise ValueError("dijkstra_envs evaluates the shortest-path router on the vectorised engine: only with algo "
                              "'dijkstra' and mode 'eval'")
+        if self.eval_link_counts and not (self.eval_envs or self.dijkstra_envs):
+            raise ValueError("eval_link_counts counts per-road pops and withdrawals in the vectorised evaluation: it needs "
+                             "eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_link_bin is None or int(self.eval_link_bin) < 1:
+            raise ValueError(f"eval_link_bin must be >= 1 second, got {self.eval_link_bin!r}")
         if int(self.iterations) < 1:
             raise ValueError(f"iterations must be >= 1, got {self.iterations!r}")
         if self.checkpoint is not None and self.algo in ("random", "dijkstra"):
@@ -275,6 +282,7 @@ class Runner:
         # the reference's eval report (src/runner.py:166-174, 219-226): phase-time pie, node metrics, leg histogram, road
         # optimality, and the simulated daily counts against the MSA assignment's expected flows
         out_dir = Path(a.output_dir)
+        self._link_expected = {}        # the flow vectors computed below, handed on to the link-count report
         try:
             sim.plot_computation_time(str(out_dir))
             sim.compute_node_metrics(str(out_dir))
@@ -287,6 +295,7 @@ class Runner:
                 f.write("road,expected_hourly_flow\n")
                 f.writelines(f"{r},{v}\n" for r, v in expected.items())
             sim.plot_daily_counts(expected, str(out_dir))
+            self._link_expected["msa"] = expected
             if a.equilibrium_metrics:
                 self._equilibrium_metrics(sim.graph, agent, expected, out_dir)
             import matplotlib.pyplot as plt
@@ -317,6 +326,27 @@ class Runner:
         for line in res.summary_lines():
             print(line)
 
+    def _link_kw(self):
+        a = self.args
+        return dict(link_counts=True, link_bin_seconds=a.eval_link_bin) if a.eval_link_counts else {}
+
+    def _link_counts_output(self, res, baseline, path):
+        """--eval-link-counts: the ``Link counts`` block, one CSV row per road at ``path`` (episode total: mean, sd, se,
+        interval, min, max; per-bin means; per expected-flow vector that Runner.eval computed its flow, difference and GEH;
+        with a baseline its mean and the paired difference) -> the summary for the JSON file (never the K x H x N tensor)."""
+        import csv
+        from tarl_hip.evaluator import link_count_lines, link_count_report, link_count_summary
+        rep = link_count_report(res, expected=getattr(self, "_link_expected", {}), baseline=baseline)
+        print("\n=== Link counts ===")
+        for line in link_count_lines(rep):
+            print(line)
+        if rep["available"]:
+            with open(path, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=rep["columns"])
+                w.writeheader()
+                w.writerows(rep["rows"])
+        return link_count_summary(rep)
+
     def _vectorised_dijkstra(self, frames, out_dir):
         """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra":
         every environment routes on its own congested travel times, in the environment's step order) for the same number of
@@ -326,11 +356,14 @@ class Runner:
         import json
         from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator
         engine = self._eval_engine(self.simulator, self._dijkstra_population, self.args.dijkstra_envs)
-        res = VecEvaluator(engine, "dijkstra", refresh_rate=self.agent.refresh_rate).run(frames)
+        res = VecEvaluator(engine, "dijkstra", refresh_rate=self.agent.refresh_rate, **self._link_kw()).run(frames)
         self._print_block(f"Vectorised evaluation ({res.envs} environments, dijkstra)", res)
         out_dir.mkdir(parents=True, exist_ok=True)
+        doc = {"mode": res.to_dict()}
+        if self.args.eval_link_counts:
+            doc["link_counts"] = self._link_counts_output(res, None, out_dir / "dijkstra_link_counts.csv")
         with open(out_dir / "dijkstra_envs.json", "w") as f:
-            json.dump({"mode": res.to_dict()}, f, indent=1)
+            json.dump(doc, f, indent=1)
         with open(out_dir / "dijkstra_envs.csv", "w", newline="") as f:
             w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
             w.writeheader()
@@ -353,7 +386,7 @@ class Runner:
         dests = None
         if a.policy_head == "embedding_dijkstra" and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
-        ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests)
+        ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw())
         results = {"mode": ev.run(frames, deterministic=True),
                    "sampled": ev.run(frames, deterministic=False) if a.eval_sampled else None}
         doc, rows = {}, []
@@ -368,7 +401,8 @@ class Runner:
         if a.eval_baseline == "dijkstra":
             # the router on a second engine with the same seed, K and population: the same noise streams as the policy run
             from tarl_hip.evaluator import paired_lines, paired_report
-            base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), "dijkstra").run(frames)
+            base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), "dijkstra",
+                                **self._link_kw()).run(frames)
             rep = paired_report(results["mode"], base)
             self._print_block("Baseline (dijkstra)", base)
             print("\n=== Policy \u2212 baseline (paired) ===")
@@ -381,6 +415,9 @@ class Runner:
             for r in rows:
                 r.update({f"baseline_{k}": by_env[r["env"]][k] for k in PER_ENV_KEYS} if r["env"] in by_env else {})
         out_dir.mkdir(parents=True, exist_ok=True)
+        if a.eval_link_counts:      # of the MODE run (and against the baseline of the same environments, where there is one)
+            doc["link_counts"] = self._link_counts_output(results["mode"], results.get("baseline"),
+                                                          out_dir / "eval_link_counts.csv")
         with open(out_dir / "eval_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "eval_envs.csv", "w", newline="") as f:
@@ -419,3 +456,5 @@ class Runner:
         with open(out_dir / "equilibrium_flows.csv", "w") as f:
             f.write("road,ue_flow,so_flow\n")
             f.writelines(f"{r},{v},{rep['so_flows'][r]}\n" for r, v in rep["ue_flows"].items())
+        if hasattr(self, "_link_expected"):
+            self._link_expected.update(ue=rep["ue_flows"], so=rep["so_flows"])

@@ -105,6 +105,11 @@ class EvalResult:
     envs_without_arrival: int | None = None
     settings: dict = field(default_factory=dict)
     computation_time_ms: float = field(default=0.0, compare=False)
+    # link_counts=True (never after a domain exit): per-road counts of pops + withdrawals per time bin
+    link_counts: np.ndarray | None = field(default=None, compare=False)     # (K, H, N) int32, bin h = link_first_bin + h
+    link_first_bin: int | None = None             # floor(EPISODE_START / link_bin_seconds)
+    link_bin_seconds: int | None = None
+    link_stats: dict | None = field(default=None, compare=False)            # link_moments over the K environments
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -240,10 +245,190 @@ def paired_scalars(report: dict):
     return out
 
 
+# ---- per-road link counts (VecEvaluator(link_counts=True)) --------------------------------------------------------------------
+LINK_RING_BYTES = 256 << 20         # both mask rings of the evaluator together
+LINK_EXPECTED = {"msa": "expected_msa", "ue": "ue_flow", "so": "so_flow"}      # expected-flow vector -> its column
+LINK_PARTIAL_NOTE = ("counts are not rescaled: a run shorter than the demand's horizon sees only part of the demand, so the "
+                     "simulated totals fall short of the expected flows by the trips that had not yet passed")
+
+
+def link_moments(ints, K):
+    """Host side of ``ops.link_count_stats``: its integer arrays ``sum``, ``sumsq`` (int64), ``min``, ``max`` (int32), each
+    (H + 1, N) with the episode total in the last row, -> the same plus ``mean`` and, for K >= 2, the sample standard
+    deviation ``std`` (ddof = 1, from the exact integer K sum d^2 - (sum d)^2), ``se = std / sqrt(K)`` and ``ci95_lo`` /
+    ``ci95_hi = mean -+ 1.96 se`` (normal approximation), all float64; ``None`` for K = 1, as in :func:`aggregate`."""
+    K = int(K)
+    s, q = np.asarray(ints["sum"], dtype=np.int64), np.asarray(ints["sumsq"], dtype=np.int64)
+    out = {"n": K, "sum": s, "sumsq": q, "min": np.asarray(ints["min"], dtype=np.int32),
+           "max": np.asarray(ints["max"], dtype=np.int32), "mean": s / float(K), "std": None, "se": None, "ci95_lo": None,
+           "ci95_hi": None}
+    if K >= 2:
+        std = np.sqrt((K * q - s * s) / float(K * (K - 1)))
+        se = std / math.sqrt(K)
+        out.update(std=std, se=se, ci95_lo=out["mean"] - 1.96 * se, ci95_hi=out["mean"] + 1.96 * se)
+    return out
+
+
+def geh(m, c):
+    """The GEH statistic ``sqrt(2 (m - c)^2 / (m + c))`` of a simulated count m against an expected count c, elementwise;
+    0 where both are 0."""
+    m, c = np.asarray(m, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    tot = m + c
+    return np.sqrt(2.0 * (m - c) ** 2 / np.where(tot == 0, 1.0, tot)) * (tot != 0)
+
+
+def link_bin_names(first_bin, num_bins, bin_seconds):
+    """Column names of the stored bins, by ABSOLUTE bin: ``count_5h``, ``count_6h`` for hourly bins, ``count_bin<k>`` else."""
+    return [f"count_{first_bin + h}h" if int(bin_seconds) == 3600 else f"count_bin{first_bin + h}" for h in range(num_bins)]
+
+
+def _flow_vector(flows, N, name):
+    if isinstance(flows, dict):
+        v = np.zeros(N, dtype=np.float64)
+        for road, flow in flows.items():
+            if 0 <= int(road) < N:
+                v[int(road)] = float(flow)
+        return v
+    v = np.asarray(flows, dtype=np.float64).reshape(-1)
+    if v.size != N:
+        raise ValueError(f"expected flows {name!r} must hold one value per road ({N}), got {v.size}")
+    return v
+
+
+def _pearson(a, b):
+    a, b = a - a.mean(), b - b.mean()
+    den = math.sqrt(float((a * a).sum()) * float((b * b).sum()))
+    return float((a * b).sum()) / den if den > 0 else float("nan")
+
+
+def _paired_link_moments(a: EvalResult, b: EvalResult):
+    """The two-input statistics call on the two count tensors (uploaded; the kernel is the only implementation)."""
+    dev = torch.device("cuda")
+    st = ops.link_count_stats(torch.from_numpy(a.link_counts).to(dev), torch.from_numpy(b.link_counts).to(dev))
+    return link_moments({k: v.cpu().numpy() for k, v in st.items()}, a.envs)
+
+
+def link_count_report(result: EvalResult, expected=None, baseline: EvalResult | None = None) -> dict:
+    """Per-road rows and a summary of the link counts of one evaluation (``VecEvaluator(link_counts=True)``).
+    Every row: ``road``, the episode total's ``mean``, ``sd``, ``se``, ``ci95_lo``, ``ci95_hi`` (``None`` for K = 1), ``min``,
+    ``max`` over the K environments, and the per-bin means (:func:`link_bin_names`). ``expected``: ``{name: flows}`` with
+    names of :data:`LINK_EXPECTED` (``msa``, ``ue``, ``so``) and flows a ``{road: flow}`` map (roads it lacks: 0) or an array
+    (N,); per name the row gains the flow (column ``expected_msa`` / ``ue_flow`` / ``so_flow``), ``diff_<name>`` = mean -
+    expected and ``geh_<name>`` (:func:`geh`), the summary RMSE, mean absolute difference, share of roads with GEH < 5, Pearson
+    correlation (nan for a constant vector) and simulated total over expected total. NOTHING is rescaled
+    (:data:`LINK_PARTIAL_NOTE`, carried as ``note``). ``baseline``: the evaluation of another head on the same environments
+    (same K, seed, frames and bins: ``ValueError`` otherwise); the row gains ``baseline_mean`` and the paired difference
+    result - baseline, ``paired_diff_mean`` / ``paired_diff_se`` / ``paired_diff_ci95_lo`` / ``_hi``, from the two-input
+    ``ops.link_count_stats``; the summary counts the roads whose interval excludes 0. A run without link counts (a domain
+    exit has none): ``{"available": False, "reason": ...}``."""
+    if result.domain_exit or result.link_counts is None:
+        why = "a run that left the domain has no statistics" if result.domain_exit else "the run did not count links"
+        return {"available": False, "reason": why}
+    K, H, N = result.link_counts.shape
+    st = result.link_stats
+    names = link_bin_names(result.link_first_bin, H, result.link_bin_seconds)
+    spread = st["std"] is not None
+    rows = []
+    for n in range(N):
+        row = {"road": n, "mean": float(st["mean"][H, n]), "sd": float(st["std"][H, n]) if spread else None,
+               "se": float(st["se"][H, n]) if spread else None, "ci95_lo": float(st["ci95_lo"][H, n]) if spread else None,
+               "ci95_hi": float(st["ci95_hi"][H, n]) if spread else None, "min": int(st["min"][H, n]),
+               "max": int(st["max"][H, n])}
+        row.update({name: float(st["mean"][h, n]) for h, name in enumerate(names)})
+        rows.append(row)
+    mean = st["mean"][H].astype(np.float64)
+    summary = {"envs": K, "roads": N, "frames_run": result.frames_run, "simulated_total": float(mean.sum()),
+               "roads_counted": int((st["max"][H] > 0).sum()), "expected": {}}
+    columns = ["road", "mean", "sd", "se", "ci95_lo", "ci95_hi", "min", "max"] + names
+    for name, flows in (expected or {}).items():
+        if name not in LINK_EXPECTED:
+            raise ValueError(f"expected flows must be named among {tuple(LINK_EXPECTED)}, got {name!r}")
+        c = _flow_vector(flows, N, name)
+        d, g = mean - c, geh(mean, c)
+        col = LINK_EXPECTED[name]
+        for n, row in enumerate(rows):
+            row.update({col: float(c[n]), f"diff_{name}": float(d[n]), f"geh_{name}": float(g[n])})
+        columns += [col, f"diff_{name}", f"geh_{name}"]
+        tot = float(c.sum())
+        summary["expected"][name] = {"rmse": float(math.sqrt(float((d * d).mean()))), "mean_abs_diff": float(np.abs(d).mean()),
+                                     "geh_below_5_share": float((g < 5.0).mean()), "pearson": _pearson(mean, c),
+                                     "total_ratio": float(mean.sum()) / tot if tot != 0 else float("nan"),
+                                     "expected_total": tot}
+    rep = {"available": True, "head": result.head, "bin_seconds": result.link_bin_seconds,
+           "first_bin": result.link_first_bin, "bins": names, "note": LINK_PARTIAL_NOTE}
+    if baseline is not None:
+        if baseline.envs != K:
+            raise ValueError(f"link_count_report needs the same environments: envs {K} / {baseline.envs}")
+        for k in ("seed", "env_base"):
+            if result.settings.get(k) != baseline.settings.get(k):
+                raise ValueError(f"link_count_report needs equal {k}: {result.settings.get(k)!r} / {baseline.settings.get(k)!r}")
+        if baseline.domain_exit or baseline.link_counts is None:
+            summary["paired"] = {"available": False, "reason": "the baseline run has no link counts"}
+        else:
+            if baseline.link_counts.shape != result.link_counts.shape or baseline.frames_run != result.frames_run or \
+                    (baseline.link_first_bin, baseline.link_bin_seconds) != (result.link_first_bin, result.link_bin_seconds):
+                raise ValueError("link_count_report needs the same frames and bins in both runs")
+            pd = _paired_link_moments(result, baseline)
+            pair = pd["std"] is not None
+            for n, row in enumerate(rows):
+                row.update(baseline_mean=float(baseline.link_stats["mean"][H, n]), paired_diff_mean=float(pd["mean"][H, n]),
+                           paired_diff_se=float(pd["se"][H, n]) if pair else None,
+                           paired_diff_ci95_lo=float(pd["ci95_lo"][H, n]) if pair else None,
+                           paired_diff_ci95_hi=float(pd["ci95_hi"][H, n]) if pair else None)
+            columns += ["baseline_mean", "paired_diff_mean", "paired_diff_se", "paired_diff_ci95_lo", "paired_diff_ci95_hi"]
+            excl = int(((pd["ci95_lo"][H] > 0) | (pd["ci95_hi"][H] < 0)).sum()) if pair else None
+            summary["paired"] = {"available": True, "baseline_head": baseline.head, "roads_interval_excludes_zero": excl,
+                                 "mean_abs_paired_diff": float(np.abs(pd["mean"][H]).mean()),
+                                 "baseline_total": float(baseline.link_stats["mean"][H].sum())}
+    rep.update(columns=columns, rows=rows, summary=summary)
+    return rep
+
+
+def link_count_lines(report: dict):
+    """:func:`link_count_report` as printable lines (the ``Link counts`` block)."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    s = report["summary"]
+    out = [f"{'roads counted:':22} {s['roads_counted']:12d} of {s['roads']}  (pops + withdrawals per road, {s['envs']} "
+           f"environments, {s['frames_run']} frames, bins of {report['bin_seconds']} s: {', '.join(report['bins'])})",
+           f"{'simulated total:':22} {s['simulated_total']:12.3f}  (sum over the roads of the mean episode total)"]
+    if not s["expected"]:
+        out.append("expected flows:        not available (the MSA / equilibrium block was skipped): no comparison columns")
+    for name, e in s["expected"].items():
+        out.append(f"{'vs ' + name + ':':22} RMSE {e['rmse']:.3f}  mean |diff| {e['mean_abs_diff']:.3f}  GEH < 5 on "
+                   f"{100.0 * e['geh_below_5_share']:.1f} % of the roads  Pearson r {e['pearson']:.4f}  simulated / expected "
+                   f"total {e['total_ratio']:.4f}")
+    if s["expected"]:
+        out.append(f"note: {report['note']}")
+    p = s.get("paired")
+    if p is not None and not p["available"]:
+        out.append(f"paired:                not available: {p['reason']}")
+    elif p is not None:
+        line = f"{'policy - ' + p['baseline_head'] + ':':22} mean |paired diff| {p['mean_abs_paired_diff']:.3f} per road"
+        if p["roads_interval_excludes_zero"] is not None:
+            line += f"; the 95% interval excludes 0 on {p['roads_interval_excludes_zero']} of {s['roads']} roads (normal approx.)"
+        else:
+            line += "; one environment: no interval"
+        out.append(line)
+    return out
+
+
+def link_count_summary(report: dict):
+    """The report without its rows, nan as ``None``: what the JSON files carry (never the K x H x N tensor)."""
+    def clean(v):
+        if isinstance(v, dict):
+            return {k: clean(x) for k, x in v.items()}
+        if isinstance(v, float) and math.isnan(v):
+            return None
+        return v
+    return clean({k: v for k, v in report.items() if k != "rows"})
+
+
 class VecEvaluator:
     def __init__(self, engine, head="embedding", *, emb=None, temperature=1.0, edge_mlp=None, prior_table=None,
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
-                 keep_actions=False, refresh_rate=10, baseline_dests=None):
+                 keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
+                 link_block=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -252,7 +437,12 @@ class VecEvaluator:
         Head ``"dijkstra"`` (the shortest-path baseline, no ``emb``): ``refresh_rate`` frames between two rebuilds of the K
         per-environment next-hop tables; ``baseline_dests`` = (dests int64 (D,), dest_slot int32 (N,)) of
         src.agents.base.destination_set over the engine's agent tables (default: computed here by the same rule). The
-        (K, D, N) int32 table and the tree scratch are allocated once; more than half the free device memory is refused."""
+        (K, D, N) int32 table and the tree scratch are allocated once; more than half the free device memory is refused.
+        ``link_counts``: also count, per environment, road and time bin of ``link_bin_seconds``, the frames in which the
+        road's head was popped plus those in which an agent was withdrawn from it (the reference's compute_node_metrics /
+        plot_daily_counts, src/transportation_simulator.py:563-746). The frames write their two masks into rings of
+        ``link_block`` frames (default: the largest block <= ``poll_frames`` and <= ops.LINK_COUNTS_MAX_FRAMES that keeps
+        both rings within 256 MB, at least 1) and one ``ops.link_counts_accumulate`` launch follows every block."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -280,6 +470,19 @@ class VecEvaluator:
         self.refresh_rate = int(refresh_rate)
         K, N, E, dev = engine.B, engine.N, engine.E, engine.device
         plan = engine.plan
+        self.link_counts = bool(link_counts)
+        if self.link_counts:
+            self.link_bin_seconds = int(link_bin_seconds)
+            if self.link_bin_seconds < 1:
+                raise ValueError("link_bin_seconds must be >= 1")
+            if link_block is None:
+                link_block = max(1, min(self.poll_frames, ops.LINK_COUNTS_MAX_FRAMES, LINK_RING_BYTES // (2 * K * N)))
+            self.link_block = int(link_block)
+            if not 1 <= self.link_block <= ops.LINK_COUNTS_MAX_FRAMES:
+                raise ValueError(f"link_block must be in [1, {ops.LINK_COUNTS_MAX_FRAMES}] (ops.LINK_COUNTS_MAX_FRAMES)")
+            self.link_popped = torch.zeros((self.link_block, K, N), dtype=torch.uint8, device=dev)
+            self.link_withdrawn = torch.zeros((self.link_block, K, N), dtype=torch.uint8, device=dev)
+            self.link_acc = None        # (K, H, N) int32, sized by run() for its frames
         # scratch, allocated once
         self.log_prob = torch.zeros(K, dtype=torch.float32, device=dev)
         self.action8 = torch.zeros((K, N), dtype=torch.uint8, device=dev)          # the last frame's action bytes
@@ -406,6 +609,10 @@ class VecEvaluator:
     def _frame(self, t, deterministic):
         eng = self.eng
         rec = self.actions[t] if self.keep_actions else None
+        masks = {}
+        if self.link_counts:        # this frame's slice of the two rings; without link counts the call is as it always was
+            j = t % self.link_block
+            masks = dict(popped=self.link_popped[j], withdrawn=self.link_withdrawn[j])
         if self.head == "dijkstra":     # choice -> core -> withdraw / insert -> reward: the environment's step order
             if eng._packed_stale:
                 eng.resync()
@@ -413,11 +620,11 @@ class VecEvaluator:
                 ops.fused_edge_travel_time(eng.plan, eng.fs, out=self.weights)
                 ops.destination_trees_batched(eng.plan, self.weights, self.dests, out=self.table, scratch=self.tree_scratch)
             ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec)
-            return eng.frame_fused(skip_choice=True, reward=self.reward[t])
+            return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
         if self.head == "embedding":
             if rec is not None and deterministic:
                 rec.copy_(self.action8)
-            return eng.frame_fused(skip_choice=deterministic, reward=self.reward[t])
+            return eng.frame_fused(skip_choice=deterministic, reward=self.reward[t], **masks)
         logits = self._logits()
         if deterministic:
             ops.graphdist_mode_rollout(eng.plan, logits, self.temperature, choice8=rec, sel8=eng.fs.sel8,
@@ -426,7 +633,7 @@ class VecEvaluator:
             ops.graphdist_rollout(eng.plan, logits, self.temperature, seed=eng.seed ^ 0x5DEECE66D,
                                   counter=eng.sample_counter + 1, choice8=rec, sel8=eng.fs.sel8, log_prob=self.log_prob,
                                   scratch=self.dist_scratch)
-        return eng.frame_fused(skip_choice=True, reward=self.reward[t])
+        return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
 
     # -- the evaluation ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -444,12 +651,23 @@ class VecEvaluator:
         fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
         eng.reset()
         self._start(bool(deterministic))
+        if self.link_counts:
+            clock0, step, bins = int(eng.time), int(eng.timestep), self.link_bin_seconds
+            first_bin = clock0 // bins
+            H = (clock0 + (T - 1) * step) // bins - first_bin + 1
+            if self.link_acc is None or self.link_acc.size(1) != H:
+                self.link_acc = torch.empty((eng.B, H, eng.N), dtype=torch.int32, device=eng.device)
+            self.link_acc.zero_()
         polls = []                  # (frames queued when the status word was copied, event)
         seen = False
         done = 0
         for t in range(T):
             self._frame(t, bool(deterministic))
             done = t + 1
+            if self.link_counts and (done % self.link_block == 0 or done == T):      # one launch per block of the rings
+                f0 = t - t % self.link_block
+                ops.link_counts_accumulate(self.link_popped, self.link_withdrawn, self.link_acc, t0=clock0 + f0 * step,
+                                           timestep=step, bin_seconds=bins, first_bin=first_bin, frames=done - f0)
             if done % self.poll_frames == 0 or done == T:
                 self._flag_host[len(polls)].copy_(fs.flags[0], non_blocking=True)
                 ev = torch.cuda.Event()
@@ -485,5 +703,9 @@ class VecEvaluator:
                                                                  host["hist"], done, self.bin_width)
         for k, v in per.items():
             setattr(res, k, v)
+        if self.link_counts:
+            st = ops.link_count_stats(self.link_acc)
+            res.link_counts, res.link_first_bin, res.link_bin_seconds = self.link_acc.cpu().numpy(), first_bin, bins
+            res.link_stats = link_moments({k: v.cpu().numpy() for k, v in st.items()}, eng.B)
         res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
         return res

@@ -693,6 +693,82 @@ def episode_summary(agent_features, *, reward=None, frames=None, bin_width=10.0,
     return out
 
 
+LINK_COUNTS_MAX_FRAMES = 127      # = TARL_LINK_COUNTS_MAX_FRAMES of include/tarl_hip.h
+
+
+def _meta(t, dtype, shape, name):
+    """dtype, shape and layout of ``t`` (checked before its device, so that a wrong call is named for what is wrong)."""
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def link_counts_accumulate(popped, withdrawn, counts, *, t0, timestep=1, bin_seconds=3600, first_bin=None, frames=None):
+    """``counts`` int32 (B, H, N) += the per-bin sums of ``popped`` + ``withdrawn`` uint8 (F, B, N), the per-frame masks of
+    ``SimEngine.frame_fused`` for ``frames`` (default: all F) consecutive frames whose first started at clock ``t0``
+    (integers: frame f at ``t0 + f * timestep``, bin ``clock // bin_seconds - first_bin``; ``first_bin`` defaults to the
+    bin of ``t0``). One launch; at most :data:`LINK_COUNTS_MAX_FRAMES` frames; a frame outside the H stored bins is refused
+    before anything is launched. Returns ``counts``."""
+    if popped.dim() != 3:
+        raise ValueError(f"popped must be (F, B, N), got {tuple(popped.shape)}")
+    _meta(popped, torch.uint8, popped.shape, "popped")
+    _meta(withdrawn, torch.uint8, popped.shape, "withdrawn")
+    Fcap, B, N = popped.shape
+    if counts.dim() != 3:
+        raise ValueError(f"counts must be (B, H, N), got {tuple(counts.shape)}")
+    H = counts.size(1)
+    _meta(counts, torch.int32, (B, H, N), "counts")
+    F = Fcap if frames is None else int(frames)
+    if not 1 <= F <= Fcap:
+        raise ValueError(f"frames must be in [1, {Fcap}], got {F}")
+    if F > LINK_COUNTS_MAX_FRAMES:
+        raise ValueError(f"one call takes at most {LINK_COUNTS_MAX_FRAMES} frames (TARL_LINK_COUNTS_MAX_FRAMES), got {F}")
+    t0, timestep, bin_seconds = int(t0), int(timestep), int(bin_seconds)
+    if t0 < 0 or timestep < 0 or bin_seconds < 1:
+        raise ValueError("t0 and timestep must be >= 0 and bin_seconds >= 1")
+    first_bin = t0 // bin_seconds if first_bin is None else int(first_bin)
+    lo, hi = t0 // bin_seconds - first_bin, (t0 + (F - 1) * timestep) // bin_seconds - first_bin
+    if first_bin < 0 or lo < 0 or hi >= H:
+        raise ValueError(f"bin out of range: the frames fall in bins {lo} .. {hi} of the {H} stored (first_bin {first_bin})")
+    for t, dt, name in ((popped, torch.uint8, "popped"), (withdrawn, torch.uint8, "withdrawn"), (counts, torch.int32, "counts")):
+        _check_dev(t, dt, name)
+    _lib.check(_lib.load().tarl_link_counts_accumulate(popped.data_ptr(), withdrawn.data_ptr(), F, B, N, t0, timestep,
+                                                       bin_seconds, first_bin, H, counts.data_ptr(), _lib.current_stream()))
+    return counts
+
+
+def link_count_stats(counts_a, counts_b=None, *, out=None):
+    """Integer moments over the K environments of ``counts_a`` int32 (K, H, N) — or, with ``counts_b`` of the same shape, of
+    the per-environment difference a - b — per (row, road), the rows being the H bins and the episode total (row H): the
+    dict ``sum`` and ``sumsq`` int64 (H + 1, N), ``min`` and ``max`` int32 (H + 1, N); ``out``: such a dict to write into."""
+    if counts_a.dim() != 3:
+        raise ValueError(f"counts_a must be (K, H, N), got {tuple(counts_a.shape)}")
+    K, H, N = counts_a.shape
+    if K < 1 or H < 1 or N < 1:
+        raise ValueError("counts_a must not be empty")
+    _meta(counts_a, torch.int32, (K, H, N), "counts_a")
+    if counts_b is not None:
+        _meta(counts_b, torch.int32, (K, H, N), "counts_b")
+    spec = (("sum", torch.int64), ("sumsq", torch.int64), ("min", torch.int32), ("max", torch.int32))
+    if out is not None:
+        for name, dt in spec:
+            _meta(out[name], dt, (H + 1, N), name)
+    _check_dev(counts_a, torch.int32, "counts_a")
+    if counts_b is not None:
+        _check_dev(counts_b, torch.int32, "counts_b")
+    if out is None:
+        out = {name: torch.empty((H + 1, N), dtype=dt, device=counts_a.device) for name, dt in spec}
+    for name, dt in spec:
+        _check_dev(out[name], dt, name)
+    _lib.check(_lib.load().tarl_link_count_stats(counts_a.data_ptr(), _lib.ptr(counts_b), K, H, N, out["sum"].data_ptr(),
+                                                 out["sumsq"].data_ptr(), out["min"].data_ptr(), out["max"].data_ptr(),
+                                                 _lib.current_stream()))
+    return out
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")
