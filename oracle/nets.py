@@ -39,8 +39,8 @@ def value_mpnn(sd, edge_index, agent_features, nf, ef, ai, tm):
     src, dst = edge_index
     msg_in = torch.cat([x[:, dst], ef.unsqueeze(-1)], dim=-1)
     m = torch.tanh(msg_in @ sd["message_mlp.1.weight"].t() + sd["message_mlp.1.bias"]).squeeze(-1)
-    summ = torch.zeros((M, N)).index_add_(1, src, m)
-    deg = torch.zeros(N).index_add_(0, src, torch.ones(src.numel()))
+    summ = torch.zeros((M, N), dtype=m.dtype).index_add_(1, src, m)
+    deg = torch.zeros(N, dtype=m.dtype).index_add_(0, src, torch.ones(src.numel(), dtype=m.dtype))
     a = torch.where(deg > 0, summ / deg.clamp(min=1), torch.zeros_like(summ))
     nd = torch.tanh(a * sd["node_mlp.0.weight"].view(()) + sd["node_mlp.0.bias"].view(()))
     h = torch.relu(tm.view(M, 1) @ sd["time_net.0.weight"].t() + sd["time_net.0.bias"])

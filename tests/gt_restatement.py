@@ -5,6 +5,9 @@ edge output. ``sd`` maps GraphTransformerNet state-dict keys to tensors; autogra
 ``capture`` (a list) records, per parameter use, the per-item operand and output of every Linear / BatchNorm, so that after
 ``backward()`` :func:`term_magnitudes` gives, for each parameter element, the sum over items (sample, node) or (sample, edge)
 of the absolute values of the terms its gradient is the sum of: the scale of the rounding error of a summed gradient.
+
+Two seams for the tests of the tests: ``_SCORES`` (a list, when set) receives the scores of every segment softmax
+(gt_cases.attention_census), and gt_mutants.py swaps ``_segment_softmax`` / ``_gather_k`` for deliberately wrong variants.
 """
 import torch
 
@@ -52,8 +55,18 @@ def _ffn(sd, key, x):
     return _lin(sd, key + ".mlp.3", torch.relu(_lin(sd, key + ".mlp.0", x)))
 
 
+_SCORES = None      # optional recorder: a list that receives (scores (M, E, H) detached, index, N) of every segment softmax
+
+
+def _gather_k(K, u):
+    """K of every edge's source node: (M, N, 16) -> (M, E, 16)."""
+    return K.index_select(1, u)
+
+
 def _segment_softmax(s, index, N):
     """s (M, E, H) over the edges of each target index (PyG 2.5 utils.softmax: max subtracted, + 1e-16)."""
+    if _SCORES is not None:
+        _SCORES.append((s.detach(), index, N))
     M, E, H = s.shape
     mx = torch.full((M, N, H), float("-inf"), dtype=s.dtype, device=s.device).scatter_reduce(1, index.view(1, E, 1).expand(M, E, H),
                                                                                s.detach(), "amax", include_self=True)
@@ -84,7 +97,7 @@ def _gt_logits(sd, obs, edge_index, edge_attr, pe):
         p = f"gt_layers.{L}."
         Q = _lin(sd, p + "WQ", x, False)
         K = _lin(sd, p + "WK", x, False)
-        Qi, Kj = Q.index_select(1, v), K.index_select(1, u)
+        Qi, Kj = Q.index_select(1, v), _gather_k(K, u)
         q = (Qi * Kj) / 2.0
         eij = _lin(sd, p + "WE", e) * q
         if L == 0:        # the last layer's node update reaches only x2 (pool / value), not the logits

@@ -30,7 +30,7 @@ def _gt_value(sd, obs, edge_index, pe):
         K = G._lin(sd, p + "WK", x, False)
         V = G._lin(sd, p + "WV", x, False)
         gate = G._lin(sd, p + "n_gate", x)
-        score = (Q.index_select(1, v) * K.index_select(1, u)).view(M, E, 4, 4).sum(-1) / 2.0
+        score = (Q.index_select(1, v) * G._gather_k(K, u)).view(M, E, 4, 4).sum(-1) / 2.0
         alpha = G._segment_softmax(score, v, N)
         msg = (alpha.unsqueeze(-1) * (V * torch.sigmoid(gate)).index_select(1, u).view(M, E, 4, 4)).reshape(M, E, 16)
         agg = torch.zeros((M, N, 16), dtype=x.dtype, device=x.device).index_add(1, v, msg)

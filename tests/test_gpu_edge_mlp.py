@@ -113,6 +113,41 @@ def test_edge_mlp_chunk_walk_edge_cases_all_precisions(drop, M):
         assert err <= tol * scale, (prec, obs.dtype, drop, M, err, scale)      # (a NaN left in `out` = a chunk nobody wrote)
 
 
+def test_edge_mlp_on_an_irregular_graph_all_precisions_and_backward():
+    """MIXED: 400 edges in no order (neither source- nor target-sorted, degrees 0 - 9), M = 5 — the four forwards as in the
+    chunk-walk test above, and tarl_policy_edge_mlp_bwd against float64 autograd of the head to 1e-4 of each gradient's scale."""
+    import irregular_graphs
+    from oracle import nets
+    from tarl_hip import ops
+    net = irregular_graphs.graph("MIXED")
+    N, E, M = net.num_roads, net.edge_index.size(1), 5
+    ei, ea = net.edge_index, net.edge_attr
+    assert E == 400 and not bool((ei[0][1:] >= ei[0][:-1]).all()) and not bool((ei[1][1:] >= ei[1][:-1]).all())
+    plan = ops.Plan(ei, N)
+    ec = ops.EdgeConst(ea, "cuda")
+    gen = torch.Generator().manual_seed(400)
+    ws = [torch.randn(s, generator=gen) * 0.2 for s in ((64, 33), (64,), (32, 64), (32,), (1, 32), (1,))]
+    w = ops.EdgeMlpWeights(*[t.cuda() for t in ws])
+    x16 = torch.randn((M, N, 16), generator=gen) * 2.0
+    coef = torch.randn((M, E), generator=gen)
+    ws64 = [t.double().requires_grad_(True) for t in ws]
+    ref = nets.edge_mlp_logits(x16.double(), ei, ea.double().expand(M, -1, -1), *ws64)
+    (ref * coef.double()).sum().backward()
+    ref = ref.detach()
+    scale = float(ref.abs().max())
+    xg = x16.cuda()
+    for prec, obs, tol in (("fp32", xg, 1e-5), ("x3", xg, 1e-4), ("bf16", xg, 2e-2), (None, xg.to(torch.bfloat16), 2e-2)):
+        out = torch.full((M, E), float("nan"), device="cuda")
+        ops.policy_edge_mlp(plan, obs, ec, w, precision=prec, out=out)
+        err = float((out.cpu().double() - ref).abs().max())
+        assert err <= tol * scale, (prec, obs.dtype, err, scale)
+    grads = [torch.zeros_like(t) for t in (w.w1, w.b1, w.w2, w.b2, w.w3, w.b3)]
+    ops.policy_edge_mlp_bwd(plan, xg, ec, w, coef.cuda(), grads)
+    for gr, want, name in zip(grads, ws64, ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")):
+        close(gr.cpu().double().reshape(-1), want.grad.reshape(-1), f"grad {name}")
+        assert float(want.grad.abs().max()) > 0, name
+
+
 def test_fused_obs16_matches_the_exported_state():
     from tarl_hip import ops, synth
     from tarl_hip.engine import SimEngine

@@ -131,14 +131,29 @@ def test_adam_matches_torch_optim(ops):
         assert torch.allclose(q.cpu(), p.detach(), rtol=1e-6, atol=1e-7), f"step {step}"
 
 
-@pytest.mark.parametrize("B", [8, 300, 1000])
-def test_policy_logits_backward_many_rows_vs_autograd(ops, B):
+def _logits_graph(graph):
+    if graph == "torus":
+        from tarl_hip import synth
+        return synth.torus_network(5, 4, heterogeneous=True, seed=2)
+    import irregular_graphs
+    return irregular_graphs.graph(graph)
+
+
+@pytest.mark.parametrize("graph,B", [pytest.param("torus", 8, id="8"), pytest.param("torus", 300, id="300"),
+                                     pytest.param("torus", 1000, id="1000"), ("MIXED", 300), ("MIXED", 1000), ("HUB126", 300),
+                                     ("HUB126", 1000)])
+def test_policy_logits_backward_many_rows_vs_autograd(ops, graph, B):
     """tarl_policy_edge_logits_bwd: the reference's live head (logit = embedding of the target road,
     src/agents/mpnn_agent.py:215-217) differentiated over B batch rows that share ONE observation (the optimiser minibatch:
-    a broadcast view, stride 0) — from 256 rows on through the row-chunked kernels — against torch autograd; twice the same bits."""
-    from tarl_hip import synth
-    net = synth.torus_network(5, 4, heterogeneous=True, seed=2)
+    a broadcast view, stride 0) — from 256 rows on through the row-chunked kernels — against torch autograd; twice the same bits.
+    On a 5 x 4 torus (four in-edges everywhere: the unrolled branch of the chunk kernel), and on the irregular road graphs
+    MIXED and HUB126 against float64 autograd: the generic branch (in-degrees 0 - 9 and 126, edge ids in no order), roads
+    without in-edges in the reduction, N = 280 across two blocks, and a short last row chunk (300 and 1 000 rows in 64s)."""
+    net = _logits_graph(graph)
     N, E = net.num_roads, net.edge_index.size(1)
+    indeg = torch.bincount(net.edge_index[1], minlength=N)
+    if graph != "torus":
+        assert int((indeg == 0).sum()) > 0 and int((indeg != 4).sum()) > N // 2 and B % 64 != 0
     plan = ops.Plan(net.edge_index, N)
     gen = torch.Generator().manual_seed(B)
     emb = torch.randn(N, generator=gen, requires_grad=True)
@@ -149,11 +164,55 @@ def test_policy_logits_backward_many_rows_vs_autograd(ops, B):
     logits = ops.policy_edge_logits(plan, nfb, emb.detach().cuda())
     ref = emb[net.x[:, 3 * net.Nmax + 6].long()][net.edge_index[1]].unsqueeze(0).expand(B, E)
     assert torch.equal(logits.cpu(), ref.detach())
-    (ref * g).sum().backward()
+    if graph == "torus":
+        (ref * g).sum().backward()
+        want = emb.grad
+    else:
+        emb64 = emb.detach().double().requires_grad_(True)
+        (emb64[net.x[:, 3 * net.Nmax + 6].long()][net.edge_index[1]].unsqueeze(0).expand(B, E) * g.double()).sum().backward()
+        want = emb64.grad
+        assert float(want[indeg == 0].abs().max()) == 0.0
     ge = ops.policy_edge_logits_bwd(plan, nfb, g.cuda(), N)
-    scale = max(1.0, float(emb.grad.abs().max()))
-    assert float((ge.cpu() - emb.grad).abs().max()) <= 1e-5 * scale
+    scale = max(1.0, float(want.abs().max()))
+    assert float((ge.cpu() - want).abs().max()) <= 1e-5 * scale
     assert torch.equal(ge, ops.policy_edge_logits_bwd(plan, nfb, g.cuda(), N))
     # the same rows as separate observations (batch stride != 0): the per-row kernel, same gradient
     gs = ops.policy_edge_logits_bwd(plan, nfb.contiguous(), g.cuda(), N)
     assert float((gs - ge).abs().max()) <= 1e-5 * scale
+
+
+def test_policy_logits_backward_flushes_when_a_rows_road_index_changes(ops):
+    """Eight separate observation rows (batch stride != 0) on MIXED in which one road's ROAD_INDEX changes from row to row:
+    its own index in rows 0 - 2, -1 (no embedding: logit 0, no gradient) in rows 3 - 4, another road's in rows 5 - 7. The
+    per-row kernel must flush its running sum at every change (``idx != cur``) — against float64 autograd of the same
+    expression. The other road's embedding receives two adds (its own run and the moved one): a sum of two terms is the
+    same in either order, so the result is still the same bits twice."""
+    net = _logits_graph("MIXED")
+    N, E, B = net.num_roads, net.edge_index.size(1), 8
+    dst = net.edge_index[1]
+    indeg = torch.bincount(dst, minlength=N)
+    a = int(torch.nonzero(indeg == 9)[0])
+    j = int(torch.nonzero((indeg > 0) & (torch.arange(N) != a))[0])
+    plan = ops.Plan(net.edge_index, N)
+    gen = torch.Generator().manual_seed(B)
+    emb = torch.randn(N, generator=gen)
+    g = torch.randn((B, E), generator=gen)
+    nf = net.x[:, 3 * net.Nmax:].unsqueeze(0).repeat(B, 1, 1)
+    nf[3:5, a, 6] = -1.0
+    nf[5:8, a, 6] = float(j)
+    nfd = nf.cuda().contiguous()
+    assert nfd.stride(0) != 0
+    idx = nf[..., 6].long()                                              # (B, N)
+    emb64 = emb.double().requires_grad_(True)
+    ref = torch.where(idx >= 0, emb64[idx.clamp(min=0)], torch.zeros((), dtype=torch.float64))[:, dst]
+    logits = ops.policy_edge_logits(plan, nfd, emb.cuda())
+    assert torch.equal(logits.cpu(), ref.detach().float())
+    assert float(logits[3, dst.cuda() == a].abs().max()) == 0.0 and float(emb[a]) != 0.0
+    (ref * g.double()).sum().backward()
+    ge = ops.policy_edge_logits_bwd(plan, nfd, g.cuda(), N)
+    scale = max(1.0, float(emb64.grad.abs().max()))
+    assert float((ge.cpu() - emb64.grad).abs().max()) <= 1e-5 * scale
+    # the flush is observable: without it road a's rows 5 - 7 would go to its own embedding
+    in_a = dst == a
+    assert abs(float(g[5:8][:, in_a].double().sum())) > 100 * 1e-5 * scale
+    assert torch.equal(ge, ops.policy_edge_logits_bwd(plan, nfd, g.cuda(), N))

@@ -69,3 +69,46 @@ def test_forward_and_gradients_match_torch():
         scale = max(1e-6, float(want.abs().max()))
         assert float((gr - want).abs().max()) <= 2e-5 * scale, name
         assert float(want.abs().max()) > 0, name
+
+
+def test_forward_and_gradients_on_an_irregular_graph():
+    """MIXED (80 roads, 400 edges in no order, out-degrees 0 - 9): the out-edge walk beyond four edges, a road without
+    out-edges (mean of nothing = 0) and ``ef[out_eid[k]]`` on an edge list whose CSR order is not its own — against
+    oracle.nets.value_mpnn in float64, unit-scale inputs as above. That the edge id matters is shown on the reference:
+    the same edge attributes in another order move the float64 value by more than 10 x the forward tolerance."""
+    import irregular_graphs
+    from oracle import nets
+    from src.agents.mpnn_agent import MPNNValueNet
+    g = irregular_graphs.graph("MIXED")
+    ei, N, E = g.edge_index, g.num_roads, g.edge_index.size(1)
+    outdeg = torch.bincount(ei[0], minlength=N)
+    assert int((outdeg == 0).sum()) > 0 and int(outdeg.max()) == 9 and not bool((ei[0][1:] >= ei[0][:-1]).all())
+    torch.manual_seed(3)
+    net = MPNNValueNet(ei.cuda(), N, device="cuda")
+    net.eval()
+    sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}
+    gen = torch.Generator().manual_seed(8)
+    M, A = 3, 200
+    nf = torch.randn((M, N, 7), generator=gen) * 0.5
+    ef = torch.rand((M, E), generator=gen)
+    ai = torch.randint(0, A, (M, N), generator=gen)
+    agent_features = torch.randn((A, 9), generator=gen) * 0.5
+    net.agent_features = agent_features.cuda()
+    tm = torch.tensor([0.3, -1.2, 2.0])
+    w = torch.tensor([0.7, -1.3, 0.4])
+    ref_sd = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    ref = lambda e: nets.value_mpnn(ref_sd, ei, agent_features.double(), nf.double(), e.double(), ai, tm.double())
+    v_ref = ref(ef)
+    (v_ref * w.double()).sum().backward()
+    tol = RTOL * v_ref.detach().abs() + 1e-6
+    with torch.no_grad():
+        moved = (ref(ef[:, torch.randperm(E, generator=gen)]) - v_ref).abs()
+    assert bool((moved > 10 * tol).all()), (moved, tol)
+    v = net(nf.cuda(), ef.unsqueeze(-1).cuda(), ai.cuda(), tm.view(-1, 1).cuda()).view(-1)
+    assert bool(((v.cpu().double() - v_ref.detach()).abs() <= tol).all()), (v, v_ref)
+    (v * w.cuda()).sum().backward()
+    for name, p in net.named_parameters():
+        gr, want = p.grad.cpu().double(), ref_sd[name].grad
+        scale = max(1e-6, float(want.abs().max()))
+        assert float((gr - want).abs().max()) <= 2e-5 * scale, name
+        assert float(want.abs().max()) > 0, name
