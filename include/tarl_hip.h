@@ -909,6 +909,29 @@ int tarl_link_counts_accumulate(const uint8_t* popped, const uint8_t* withdrawn,
 int tarl_link_count_stats(const int32_t* counts_a, const int32_t* counts_b, int64_t K, int64_t H, int64_t N, int64_t* sum,
                           int64_t* sumsq, int32_t* vmin, int32_t* vmax, tarl_stream stream);
 
+/* ---- per-road occupancy of a vectorised evaluation --------------------------------------------------------------------------
+ * Sums over frames of NUMBER_OF_AGENT, the quantity the reward is made of (reward = -sum over n of NUMBER_OF_AGENT after the
+ * step), binned like the link counts: frame f of a call starts at clock_f = t0 + f * timestep and belongs to bin
+ * h_f = clock_f / bin_seconds - first_bin.
+ * tarl_occupancy_accumulate: ring fp32 [F][N][K], F consecutive frames' `counts` slices exactly as tarl_fused_frame writes
+ *   them (env-minor, the value AFTER the frame); thr int32 [N], the count from which a road admits nobody
+ *   (ceil(MAX - 3): the negation of Direction's has_room and of the insert's capacity rule; a road with thr <= 0 is at
+ *   capacity in every frame). With c = the ring's value converted by truncation, NaN or negative -> 0, above 255 -> 255 (a
+ *   foreign value miscounts its own element and nothing else):
+ *     veh  int32 [K][H][N] += sum over the frames f in bin h of c[f][n][k]        (vehicle-frames)
+ *     full int32 [K][H][N] += the number of frames f in bin h with c[f][n][k] >= thr[n]
+ *     peak int32 [K][1][N]  = max(peak, max over f of c[f][n][k])
+ *   so a second call continues the first. The layouts are those of tarl_link_count_stats, which serves veh and full as they
+ *   are (one- and two-input form) and peak with H = 1. One launch for all F frames; one workgroup owns a tile of 64
+ *   environments x 64 roads for all frames and bins and is its only writer, no atomics.
+ *   1 <= F <= 2^23: the partial sums of one call are int32 and 255 * 2^23 < 2^31 (no cap of 127 as for the link counts; the
+ *   caller keeps the accumulated totals within int32, e.g. 255 * frames per bin). Refused on the host, before anything is
+ *   launched and with the accumulators untouched: a null argument, a first frame below first_bin, a last frame in a bin
+ *   >= H, timestep < 0, bin_seconds < 1, K, N, H, K * N * H or F * K * N at or above 2^40. */
+int tarl_occupancy_accumulate(const float* ring, const int32_t* thr, int64_t F, int64_t K, int64_t N, int64_t t0,
+                              int64_t timestep, int64_t bin_seconds, int64_t first_bin, int64_t H, int32_t* veh,
+                              int32_t* full, int32_t* peak, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

@@ -93,6 +93,13 @@ OPTIONS = (
                                      "error and interval per road against the MSA (and, with --equilibrium-metrics, UE / SO) "
                                      "flows and, with --eval-baseline, the paired difference; `link_counts` in the JSON file")),
     ("--eval-link-bin", dict(type=int, default=3600, metavar="SECONDS", help="--eval-link-counts: width of the time bins")),
+    ("--eval-occupancy", dict(action="store_true",
+                              help="--eval-envs / --dijkstra-envs, eval: sum per road and time bin (of --eval-link-bin seconds) "
+                                   "the vehicles on it after every frame, count the frames in which it was at capacity and "
+                                   "keep its peak, over the K environments; an `Occupancy` block, eval_occupancy.csv "
+                                   "(dijkstra_occupancy.csv) with vehicle-seconds, occupancy per bin, v/c, peak and frames "
+                                   "at capacity per road and, with --eval-baseline, the paired differences; `occupancy` in "
+                                   "the JSON file")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--checkpoint", dict(type=str, default=None,

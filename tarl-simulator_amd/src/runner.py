@@ -39,6 +39,7 @@ class RunnerArgs:
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
     eval_link_bin: int = 3600      # ... in time bins of this many seconds
+    eval_occupancy: bool = False   # eval_envs / dijkstra_envs: per-road occupancy and time at capacity (bins of eval_link_bin)
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -67,6 +68,9 @@ class RunnerArgs:
         if self.eval_link_counts and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_link_counts counts per-road pops and withdrawals in the vectorised evaluation: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_occupancy and not (self.eval_envs or self.dijkstra_envs):
+            raise ValueError("eval_occupancy sums per-road vehicle counts and frames at capacity in the vectorised "
+                             "evaluation: it needs eval_envs > 0 or dijkstra_envs > 0")
         if self.eval_link_bin is None or int(self.eval_link_bin) < 1:
             raise ValueError(f"eval_link_bin must be >= 1 second, got {self.eval_link_bin!r}")
         if int(self.iterations) < 1:
@@ -328,7 +332,27 @@ class Runner:
 
     def _link_kw(self):
         a = self.args
-        return dict(link_counts=True, link_bin_seconds=a.eval_link_bin) if a.eval_link_counts else {}
+        kw = dict(link_counts=True, link_bin_seconds=a.eval_link_bin) if a.eval_link_counts else {}
+        if a.eval_occupancy:
+            kw.update(occupancy=True, link_bin_seconds=a.eval_link_bin)
+        return kw
+
+    def _occupancy_output(self, res, baseline, path):
+        """--eval-occupancy: the ``Occupancy`` block, one CSV row per road at ``path`` (capacity and threshold; vehicle-seconds
+        of the episode: mean, sd, se, interval, min, max; mean occupancy per bin; v/c; peak; frames at capacity; with a
+        baseline the paired differences) -> the summary for the JSON file (never the K x H x N tensors)."""
+        import csv
+        from tarl_hip.evaluator import occupancy_lines, occupancy_report, occupancy_summary
+        rep = occupancy_report(res, baseline=baseline)
+        print("\n=== Occupancy ===")
+        for line in occupancy_lines(rep):
+            print(line)
+        if rep["available"]:
+            with open(path, "w", newline="") as f:
+                w = csv.DictWriter(f, fieldnames=rep["columns"])
+                w.writeheader()
+                w.writerows(rep["rows"])
+        return occupancy_summary(rep)
 
     def _link_counts_output(self, res, baseline, path):
         """--eval-link-counts: the ``Link counts`` block, one CSV row per road at ``path`` (episode total: mean, sd, se,
@@ -362,6 +386,8 @@ class Runner:
         doc = {"mode": res.to_dict()}
         if self.args.eval_link_counts:
             doc["link_counts"] = self._link_counts_output(res, None, out_dir / "dijkstra_link_counts.csv")
+        if self.args.eval_occupancy:
+            doc["occupancy"] = self._occupancy_output(res, None, out_dir / "dijkstra_occupancy.csv")
         with open(out_dir / "dijkstra_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "dijkstra_envs.csv", "w", newline="") as f:
@@ -418,6 +444,8 @@ class Runner:
         if a.eval_link_counts:      # of the MODE run (and against the baseline of the same environments, where there is one)
             doc["link_counts"] = self._link_counts_output(results["mode"], results.get("baseline"),
                                                           out_dir / "eval_link_counts.csv")
+        if a.eval_occupancy:
+            doc["occupancy"] = self._occupancy_output(results["mode"], results.get("baseline"), out_dir / "eval_occupancy.csv")
         with open(out_dir / "eval_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "eval_envs.csv", "w", newline="") as f:

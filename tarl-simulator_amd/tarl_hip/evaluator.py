@@ -110,6 +110,11 @@ class EvalResult:
     link_first_bin: int | None = None             # floor(EPISODE_START / link_bin_seconds)
     link_bin_seconds: int | None = None
     link_stats: dict | None = field(default=None, compare=False)            # link_moments over the K environments
+    # occupancy=True (never after a domain exit): sums over frames of NUMBER_OF_AGENT, the quantity the reward is made of
+    occupancy: dict | None = field(default=None, compare=False)             # veh, full (K, H, N), peak (K, 1, N) int32
+    occupancy_stats: dict | None = field(default=None, compare=False)       # link_moments of each of the three arrays
+    occupancy_frames_per_bin: list | None = None  # frames run in each of the H bins (bin h = occupancy_meta first_bin + h)
+    occupancy_meta: dict | None = field(default=None, compare=False)        # first_bin, bin_seconds, timestep, max, thr
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -424,11 +429,197 @@ def link_count_summary(report: dict):
     return clean({k: v for k, v in report.items() if k != "rows"})
 
 
+# ---- per-road occupancy and time at capacity (VecEvaluator(occupancy=True)) ----------------------------------------------------
+OCCUPANCY_RING_BYTES = 256 << 20    # the fp32 ring of frame_fused's `counts` slices
+CONGESTION_FILE = 3                 # src/feature_helpers.py: has_room = n_i < max_i - CONGESTION_FILE
+
+
+def capacity_threshold(max_agents):
+    """``thr[n] = ceil(MAX[n] - 3)`` int32: the count from which road n admits nobody, the negation of Direction's
+    ``has_room = n_i < max_i - CONGESTION_FILE`` and of the insert's capacity rule, taken literally (a road with MAX <= 3 is
+    at capacity in every frame)."""
+    return np.ceil(np.asarray(max_agents, dtype=np.float64) - CONGESTION_FILE).astype(np.int32)
+
+
+def occupancy_bin_names(first_bin, num_bins, bin_seconds):
+    """Column names of the stored bins, by ABSOLUTE bin: ``occ_5h``, ``occ_6h`` for hourly bins, ``occ_bin<k>`` else."""
+    return [f"occ_{first_bin + h}h" if int(bin_seconds) == 3600 else f"occ_bin{first_bin + h}" for h in range(num_bins)]
+
+
+def _paired_occupancy_moments(a: EvalResult, b: EvalResult, key):
+    """The two-input statistics call on one of the accumulators of two runs (uploaded; the kernel is the only
+    implementation)."""
+    dev = torch.device("cuda")
+    st = ops.link_count_stats(torch.from_numpy(a.occupancy[key]).to(dev), torch.from_numpy(b.occupancy[key]).to(dev))
+    return link_moments({k: v.cpu().numpy() for k, v in st.items()}, a.envs)
+
+
+def _opt(moments, key, row, n, scale=1.0):
+    return float(moments[key][row, n]) * scale if moments[key] is not None else None
+
+
+def occupancy_report(result: EvalResult, baseline: EvalResult | None = None) -> dict:
+    """Per-road rows and a summary of the occupancy of one evaluation (``VecEvaluator(occupancy=True)``), formed in float64
+    on the host from the integer accumulators ``veh`` (vehicle-frames per environment, bin and road), ``full`` (frames at
+    capacity) and ``peak`` and their integer moments over the K environments.
+    Every row: ``road``, ``max_agents`` (MAX) and ``thr``; ``veh_seconds_*`` of the episode (vehicle-frames x timestep):
+    mean, sd, se, ci95_lo, ci95_hi (``None`` for K = 1), min, max over K; the mean occupancy per bin
+    (:func:`occupancy_bin_names`: veh / frames in the bin, averaged over K; ``None`` for a bin without a frame); ``vc_mean``,
+    the time-averaged count / max(MAX, 1) (the reference's v/c ratio); ``peak_mean`` / ``peak_max``; ``full_frames_mean`` /
+    ``_min`` / ``_max`` and ``full_share`` of the frames run. ``baseline``: the evaluation of another head on the same
+    environments (same K, seed, frames and bins: ``ValueError`` otherwise); the row gains the baseline's means and the paired
+    differences result - baseline of veh_seconds and full_frames with se and interval, from the two-input
+    ``ops.link_count_stats``. The summary: network vehicle-hours per environment (mean, se, interval over K; paired with a
+    baseline), per bin the network mean and population sd of v/c averaged over K, the share of road-frames at capacity,
+    the mean number of roads ever at capacity, the roads whose paired interval excludes 0, and the identity
+    sum(veh[b]) == -episode_return[b]. A run without occupancy (a domain exit has none):
+    ``{"available": False, "reason": ...}``."""
+    if result.domain_exit or result.occupancy is None:
+        why = "a run that left the domain has no statistics" if result.domain_exit else "the run did not accumulate occupancy"
+        return {"available": False, "reason": why}
+    veh, full, peak = (result.occupancy[k] for k in ("veh", "full", "peak"))
+    K, H, N = veh.shape
+    meta, st = result.occupancy_meta, result.occupancy_stats
+    step, T = int(meta["timestep"]), int(result.frames_run)
+    cap = np.asarray(meta["max"], dtype=np.float64)
+    thr = np.asarray(meta["thr"], dtype=np.int64)
+    fpb = np.asarray(result.occupancy_frames_per_bin, dtype=np.float64)
+    names = occupancy_bin_names(meta["first_bin"], H, meta["bin_seconds"])
+    sv, sf, sp = st["veh"], st["full"], st["peak"]
+    den = np.maximum(cap, 1.0)
+    rows = []
+    for n in range(N):
+        row = {"road": n, "max_agents": float(cap[n]), "thr": int(thr[n]),
+               "veh_seconds_mean": float(sv["mean"][H, n]) * step, "veh_seconds_sd": _opt(sv, "std", H, n, step),
+               "veh_seconds_se": _opt(sv, "se", H, n, step), "veh_seconds_ci95_lo": _opt(sv, "ci95_lo", H, n, step),
+               "veh_seconds_ci95_hi": _opt(sv, "ci95_hi", H, n, step), "veh_seconds_min": int(sv["min"][H, n]) * step,
+               "veh_seconds_max": int(sv["max"][H, n]) * step}
+        row.update({name: float(sv["mean"][h, n]) / fpb[h] if fpb[h] > 0 else None for h, name in enumerate(names)})
+        row.update(vc_mean=float(sv["mean"][H, n]) / T / den[n], peak_mean=float(sp["mean"][0, n]),
+                   peak_max=int(sp["max"][0, n]), full_frames_mean=float(sf["mean"][H, n]), full_frames_min=int(sf["min"][H, n]),
+                   full_frames_max=int(sf["max"][H, n]), full_share=float(sf["mean"][H, n]) / T)
+        rows.append(row)
+    columns = list(rows[0])
+    v64, f64 = veh.astype(np.int64), full.astype(np.int64)
+    veh_env = v64.sum(axis=(1, 2))                                     # vehicle-frames per environment
+    ret = np.asarray(result.episode_return, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vc = v64 / fpb[None, :, None] / den[None, None, :]             # (K, H, N); nan in a bin without a frame
+    vc_mean, vc_sd = vc.mean(axis=2).mean(axis=0), vc.std(axis=2).mean(axis=0)
+    summary = {"envs": K, "roads": N, "frames_run": T, "timestep": step,
+               "vehicle_hours": aggregate(list(veh_env * step / 3600.0)),
+               "vc_mean_per_bin": [float(x) for x in vc_mean], "vc_sd_per_bin": [float(x) for x in vc_sd],
+               "frames_per_bin": [int(x) for x in fpb],
+               "share_road_frames_at_capacity": float(f64.sum()) / (float(K) * T * N),
+               "mean_roads_ever_at_capacity": float((f64.sum(axis=1) > 0).sum(axis=1).mean()),
+               "largest_peak": int(peak.max()),
+               "identity": {"holds": bool(np.array_equal(veh_env.astype(np.float64), -ret)),
+                            "vehicle_frames": [int(x) for x in veh_env], "minus_episode_return": [float(-x) for x in ret]}}
+    rep = {"available": True, "head": result.head, "bin_seconds": int(meta["bin_seconds"]), "first_bin": int(meta["first_bin"]),
+           "bins": names}
+    if baseline is not None:
+        if baseline.envs != K:
+            raise ValueError(f"occupancy_report needs the same environments: envs {K} / {baseline.envs}")
+        for k in ("seed", "env_base"):
+            if result.settings.get(k) != baseline.settings.get(k):
+                raise ValueError(f"occupancy_report needs equal {k}: {result.settings.get(k)!r} / {baseline.settings.get(k)!r}")
+        if baseline.domain_exit or baseline.occupancy is None:
+            summary["paired"] = {"available": False, "reason": "the baseline run has no occupancy"}
+        else:
+            bm = baseline.occupancy_meta
+            if baseline.occupancy["veh"].shape != veh.shape or baseline.frames_run != T or \
+                    any(bm[k] != meta[k] for k in ("first_bin", "bin_seconds", "timestep")):
+                raise ValueError("occupancy_report needs the same frames and bins in both runs")
+            pv, pf = (_paired_occupancy_moments(result, baseline, k) for k in ("veh", "full"))
+            bv, bf = baseline.occupancy_stats["veh"], baseline.occupancy_stats["full"]
+            for n, row in enumerate(rows):
+                row.update(baseline_veh_seconds_mean=float(bv["mean"][H, n]) * step,
+                           paired_veh_seconds_mean=float(pv["mean"][H, n]) * step,
+                           paired_veh_seconds_se=_opt(pv, "se", H, n, step),
+                           paired_veh_seconds_ci95_lo=_opt(pv, "ci95_lo", H, n, step),
+                           paired_veh_seconds_ci95_hi=_opt(pv, "ci95_hi", H, n, step),
+                           baseline_full_frames_mean=float(bf["mean"][H, n]), paired_full_frames_mean=float(pf["mean"][H, n]),
+                           paired_full_frames_se=_opt(pf, "se", H, n), paired_full_frames_ci95_lo=_opt(pf, "ci95_lo", H, n),
+                           paired_full_frames_ci95_hi=_opt(pf, "ci95_hi", H, n))
+            columns = list(rows[0])
+            pair = pv["std"] is not None
+            excl = {k: int(((m["ci95_lo"][H] > 0) | (m["ci95_hi"][H] < 0)).sum()) if pair else None
+                    for k, m in (("veh_seconds", pv), ("full_frames", pf))}
+            base_env = baseline.occupancy["veh"].astype(np.int64).sum(axis=(1, 2))
+            summary["paired"] = {"available": True, "baseline_head": baseline.head,
+                                 "vehicle_hours": aggregate(list((veh_env - base_env) * step / 3600.0)),
+                                 "baseline_vehicle_hours": aggregate(list(base_env * step / 3600.0)),
+                                 "roads_interval_excludes_zero": excl}
+    rep.update(columns=columns, rows=rows, summary=summary)
+    return rep
+
+
+def _pm(g, unit=""):
+    s = f"{g['mean']:12.3f}{unit}"
+    if g["se"] is not None:
+        s += f"  +- {g['se']:.3f} (se)  95% [{g['ci95'][0]:.3f}, {g['ci95'][1]:.3f}] (normal approx.)"
+    return s + f"  min {g['min']:.3f}  max {g['max']:.3f}  n {g['n']}"
+
+
+def occupancy_lines(report: dict):
+    """:func:`occupancy_report` as printable lines (the ``Occupancy`` block), the ten roads with the most frames at capacity
+    included."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    s = report["summary"]
+    out = [f"{'vehicle-hours:':22} {_pm(s['vehicle_hours'])}  (network total per environment, {s['envs']} environments, "
+           f"{s['frames_run']} frames of {s['timestep']} s)"]
+    p = s.get("paired")
+    if p is not None and not p["available"]:
+        out.append(f"paired:                not available: {p['reason']}")
+    elif p is not None:
+        g = p["vehicle_hours"]
+        line = f"{'policy - ' + p['baseline_head'] + ':':22} {g['mean']:12.3f} vehicle-hours"
+        if g["se"] is not None:
+            line += f"  +- {g['se']:.3f} (se)  95% [{g['ci95'][0]:.3f}, {g['ci95'][1]:.3f}] (normal approx.)"
+        e = p["roads_interval_excludes_zero"]
+        if e["veh_seconds"] is not None:
+            line += (f"; per road the 95% interval excludes 0 on {e['veh_seconds']} (vehicle-seconds) and {e['full_frames']} "
+                     f"(frames at capacity) of {s['roads']} roads")
+        else:
+            line += "; one environment: no interval"
+        out.append(line)
+    for name, frames, m, sd in zip(report["bins"], s["frames_per_bin"], s["vc_mean_per_bin"], s["vc_sd_per_bin"]):
+        out.append(f"{'v/c ' + name + ':':22} mean {m:.4f}  sd {sd:.4f} over the roads, averaged over the environments "
+                   f"({frames} frames)")
+    out.append(f"{'at capacity:':22} {100.0 * s['share_road_frames_at_capacity']:.3f} % of the road-frames; "
+               f"{s['mean_roads_ever_at_capacity']:.2f} of {s['roads']} roads ever at capacity (mean over the environments); "
+               f"largest count {s['largest_peak']}")
+    i = s["identity"]
+    out.append(f"{'identity:':22} sum of vehicle-frames == -episode return in every environment: "
+               f"{'yes' if i['holds'] else 'NO'} (environment 0: {i['vehicle_frames'][0]} / {i['minus_episode_return'][0]:.0f})")
+    top = sorted(report["rows"], key=lambda r: (-r["full_frames_mean"], r["road"]))[:10]
+    out.append("roads with the most frames at capacity (mean over the environments):")
+    for r in top:
+        out.append(f"  road {r['road']:6d}  full {r['full_frames_mean']:10.2f} frames ({100.0 * r['full_share']:.1f} %)  "
+                   f"peak {r['peak_max']:3d} of MAX {r['max_agents']:.0f} (thr {r['thr']})  "
+                   f"vehicle-seconds {r['veh_seconds_mean']:.1f}")
+    return out
+
+
+def occupancy_summary(report: dict):
+    """The report without its rows, nan as ``None``: what the JSON files carry (never the K x H x N tensors)."""
+    def clean(v):
+        if isinstance(v, dict):
+            return {k: clean(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [clean(x) for x in v]
+        if isinstance(v, float) and math.isnan(v):
+            return None
+        return v
+    return clean({k: v for k, v in report.items() if k != "rows"})
+
+
 class VecEvaluator:
     def __init__(self, engine, head="embedding", *, emb=None, temperature=1.0, edge_mlp=None, prior_table=None,
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
-                 link_block=None):
+                 link_block=None, occupancy=False, occupancy_block=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -442,7 +633,13 @@ class VecEvaluator:
         road's head was popped plus those in which an agent was withdrawn from it (the reference's compute_node_metrics /
         plot_daily_counts, src/transportation_simulator.py:563-746). The frames write their two masks into rings of
         ``link_block`` frames (default: the largest block <= ``poll_frames`` and <= ops.LINK_COUNTS_MAX_FRAMES that keeps
-        both rings within 256 MB, at least 1) and one ``ops.link_counts_accumulate`` launch follows every block."""
+        both rings within 256 MB, at least 1) and one ``ops.link_counts_accumulate`` launch follows every block.
+        ``occupancy``: also sum, per environment, road and time bin of ``link_bin_seconds`` (both per-road reports share one
+        binning), the road's NUMBER_OF_AGENT after every frame, count the frames in which it was at capacity
+        (:func:`capacity_threshold` of the engine's static MAX column, computed once on the host) and keep its peak. The
+        frames write their ``counts`` slice into an fp32 ring (F, N, K) of ``occupancy_block`` frames (default: the largest
+        block <= ``poll_frames`` that keeps the ring within 256 MB, at least 1) and one ``ops.occupancy_accumulate`` launch
+        follows every block. Without the flag nothing is allocated and every frame is called as it always was."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -483,6 +680,21 @@ class VecEvaluator:
             self.link_popped = torch.zeros((self.link_block, K, N), dtype=torch.uint8, device=dev)
             self.link_withdrawn = torch.zeros((self.link_block, K, N), dtype=torch.uint8, device=dev)
             self.link_acc = None        # (K, H, N) int32, sized by run() for its frames
+        self.occupancy = bool(occupancy)
+        if self.occupancy:
+            self.link_bin_seconds = int(link_bin_seconds)
+            if self.link_bin_seconds < 1:
+                raise ValueError("link_bin_seconds must be >= 1")
+            if occupancy_block is None:
+                occupancy_block = max(1, min(self.poll_frames, OCCUPANCY_RING_BYTES // (4 * K * N)))
+            self.occupancy_block = int(occupancy_block)
+            if not 1 <= self.occupancy_block <= ops.OCCUPANCY_MAX_FRAMES:
+                raise ValueError(f"occupancy_block must be in [1, {ops.OCCUPANCY_MAX_FRAMES}] (ops.OCCUPANCY_MAX_FRAMES)")
+            self.occ_ring = torch.zeros((self.occupancy_block, N, K), dtype=torch.float32, device=dev)
+            self.occ_max = engine.static_node_features[0, :, 0].detach().cpu().numpy().astype(np.float64)
+            self.occ_thr_host = capacity_threshold(self.occ_max)
+            self.occ_thr = torch.from_numpy(self.occ_thr_host).to(dev)
+            self.occ_acc = None         # veh, full (K, H, N) and peak (K, 1, N) int32, sized by run() for its frames
         # scratch, allocated once
         self.log_prob = torch.zeros(K, dtype=torch.float32, device=dev)
         self.action8 = torch.zeros((K, N), dtype=torch.uint8, device=dev)          # the last frame's action bytes
@@ -610,9 +822,11 @@ class VecEvaluator:
         eng = self.eng
         rec = self.actions[t] if self.keep_actions else None
         masks = {}
-        if self.link_counts:        # this frame's slice of the two rings; without link counts the call is as it always was
+        if self.link_counts:        # this frame's slice of the two rings; without either flag the call is as it always was
             j = t % self.link_block
             masks = dict(popped=self.link_popped[j], withdrawn=self.link_withdrawn[j])
+        if self.occupancy:          # and of the counts ring
+            masks["counts"] = self.occ_ring[t % self.occupancy_block]
         if self.head == "dijkstra":     # choice -> core -> withdraw / insert -> reward: the environment's step order
             if eng._packed_stale:
                 eng.resync()
@@ -651,13 +865,21 @@ class VecEvaluator:
         fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
         eng.reset()
         self._start(bool(deterministic))
-        if self.link_counts:
+        if self.link_counts or self.occupancy:      # one binning for both per-road reports
             clock0, step, bins = int(eng.time), int(eng.timestep), self.link_bin_seconds
             first_bin = clock0 // bins
             H = (clock0 + (T - 1) * step) // bins - first_bin + 1
+        if self.link_counts:
             if self.link_acc is None or self.link_acc.size(1) != H:
                 self.link_acc = torch.empty((eng.B, H, eng.N), dtype=torch.int32, device=eng.device)
             self.link_acc.zero_()
+        if self.occupancy:
+            if self.occ_acc is None or self.occ_acc["veh"].size(1) != H:
+                self.occ_acc = {"veh": torch.empty((eng.B, H, eng.N), dtype=torch.int32, device=eng.device),
+                                "full": torch.empty((eng.B, H, eng.N), dtype=torch.int32, device=eng.device),
+                                "peak": torch.empty((eng.B, 1, eng.N), dtype=torch.int32, device=eng.device)}
+            for v in self.occ_acc.values():
+                v.zero_()
         polls = []                  # (frames queued when the status word was copied, event)
         seen = False
         done = 0
@@ -668,6 +890,11 @@ class VecEvaluator:
                 f0 = t - t % self.link_block
                 ops.link_counts_accumulate(self.link_popped, self.link_withdrawn, self.link_acc, t0=clock0 + f0 * step,
                                            timestep=step, bin_seconds=bins, first_bin=first_bin, frames=done - f0)
+            if self.occupancy and (done % self.occupancy_block == 0 or done == T):   # one launch per block of the ring
+                f0 = t - t % self.occupancy_block
+                ops.occupancy_accumulate(self.occ_ring, self.occ_thr, self.occ_acc["veh"], self.occ_acc["full"],
+                                         self.occ_acc["peak"], t0=clock0 + f0 * step, timestep=step, bin_seconds=bins,
+                                         first_bin=first_bin, frames=done - f0)
             if done % self.poll_frames == 0 or done == T:
                 self._flag_host[len(polls)].copy_(fs.flags[0], non_blocking=True)
                 ev = torch.cuda.Event()
@@ -707,5 +934,15 @@ class VecEvaluator:
             st = ops.link_count_stats(self.link_acc)
             res.link_counts, res.link_first_bin, res.link_bin_seconds = self.link_acc.cpu().numpy(), first_bin, bins
             res.link_stats = link_moments({k: v.cpu().numpy() for k, v in st.items()}, eng.B)
+        if self.occupancy:
+            res.occupancy, res.occupancy_stats = {}, {}
+            for k, acc in self.occ_acc.items():
+                st = ops.link_count_stats(acc)
+                res.occupancy[k] = acc.cpu().numpy()
+                res.occupancy_stats[k] = link_moments({j: v.cpu().numpy() for j, v in st.items()}, eng.B)
+            bins_of = (clock0 + np.arange(done, dtype=np.int64) * step) // bins - first_bin
+            res.occupancy_frames_per_bin = [int(x) for x in np.bincount(bins_of, minlength=H)]
+            res.occupancy_meta = dict(first_bin=int(first_bin), bin_seconds=int(bins), timestep=int(step),
+                                      max=self.occ_max.copy(), thr=self.occ_thr_host.copy())
         res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
         return res

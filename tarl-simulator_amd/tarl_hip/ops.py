@@ -769,6 +769,52 @@ def link_count_stats(counts_a, counts_b=None, *, out=None):
     return out
 
 
+OCCUPANCY_MAX_FRAMES = 1 << 23      # 255 * 2^23 < 2^31: the int32 partial sums of one tarl_occupancy_accumulate call
+
+
+def occupancy_accumulate(ring, thr, veh, full, peak, *, t0, timestep=1, bin_seconds=3600, first_bin=None, frames=None):
+    """``ring`` fp32 (F, N, K): the ``counts`` slices of ``SimEngine.frame_fused`` (env-minor, the count after the frame) of
+    ``frames`` (default: all F) consecutive frames whose first started at clock ``t0``; ``thr`` int32 (N,): the count from
+    which a road is at capacity. ``veh`` int32 (K, H, N) += the per-bin sums of the counts, ``full`` int32 (K, H, N) += the
+    per-bin number of frames with count >= thr, ``peak`` int32 (K, 1, N) = max(peak, the largest count): a second call
+    continues the first. Bins as :func:`link_counts_accumulate` (frame f at ``t0 + f * timestep``, bin
+    ``clock // bin_seconds - first_bin``; ``first_bin`` defaults to the bin of ``t0``). A value is converted by truncation,
+    NaN and negatives count 0, anything above 255 counts 255. One launch; at most :data:`OCCUPANCY_MAX_FRAMES` frames; a
+    frame outside the H stored bins is refused before anything is launched. Returns ``(veh, full, peak)``."""
+    if ring.dim() != 3:
+        raise ValueError(f"ring must be (F, N, K), got {tuple(ring.shape)}")
+    _meta(ring, torch.float32, ring.shape, "ring")
+    Fcap, N, K = ring.shape
+    _meta(thr, torch.int32, (N,), "thr")
+    if veh.dim() != 3:
+        raise ValueError(f"veh must be (K, H, N), got {tuple(veh.shape)}")
+    H = veh.size(1)
+    _meta(veh, torch.int32, (K, H, N), "veh")
+    _meta(full, torch.int32, (K, H, N), "full")
+    _meta(peak, torch.int32, (K, 1, N), "peak")
+    if K < 1 or N < 1 or H < 1:
+        raise ValueError("ring and the accumulators must not be empty")
+    F = Fcap if frames is None else int(frames)
+    if not 1 <= F <= Fcap:
+        raise ValueError(f"frames must be in [1, {Fcap}], got {F}")
+    if F > OCCUPANCY_MAX_FRAMES:
+        raise ValueError(f"one call takes at most {OCCUPANCY_MAX_FRAMES} frames, got {F}")
+    t0, timestep, bin_seconds = int(t0), int(timestep), int(bin_seconds)
+    if t0 < 0 or timestep < 0 or bin_seconds < 1:
+        raise ValueError("t0 and timestep must be >= 0 and bin_seconds >= 1")
+    first_bin = t0 // bin_seconds if first_bin is None else int(first_bin)
+    lo, hi = t0 // bin_seconds - first_bin, (t0 + (F - 1) * timestep) // bin_seconds - first_bin
+    if first_bin < 0 or lo < 0 or hi >= H:
+        raise ValueError(f"bin out of range: the frames fall in bins {lo} .. {hi} of the {H} stored (first_bin {first_bin})")
+    for t, dt, name in ((ring, torch.float32, "ring"), (thr, torch.int32, "thr"), (veh, torch.int32, "veh"),
+                        (full, torch.int32, "full"), (peak, torch.int32, "peak")):
+        _check_dev(t, dt, name)
+    _lib.check(_lib.load().tarl_occupancy_accumulate(ring.data_ptr(), thr.data_ptr(), F, K, N, t0, timestep, bin_seconds,
+                                                     first_bin, H, veh.data_ptr(), full.data_ptr(), peak.data_ptr(),
+                                                     _lib.current_stream()))
+    return veh, full, peak
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")

@@ -2,17 +2,20 @@
 # Developer tool: register / spill / scratch figures of the frame kernels' bench instantiations, from the compiler's own
 # resource remarks (-Rpass-analysis=kernel-resource-usage) and the static instruction mix of the device ISA (--save-temps).
 # usage: tools/kernel_resources.sh [extra hipcc flags]   (run from anywhere; writes nothing into the tree)
+#        SRC=occupancy.hip tools/kernel_resources.sh    every kernel of another file of csrc/, under its mangled name
 cd "$(dirname "$0")/../tarl-simulator_amd/csrc"
 T=$(mktemp -d)
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Rpass-analysis=kernel-resource-usage \
-  --save-temps=obj "$@" -c fused.hip -o $T/fused.o 2> $T/remarks.txt
-python3 - $T <<'PY'
+  --save-temps=obj "$@" -c ${SRC:=fused.hip} -o $T/out.o 2> $T/remarks.txt
+python3 - $T $SRC <<'PY'
 import re, sys, glob
 T = sys.argv[1]
 want = {"_Z12k_fused_rowsILi4ELb1ELb0ELb1EE": "k_fused_rows<4,SIB,rollout,O32>", "_Z17k_fused_directionILi4ELb1ELb1ELb1EE": "k_fused_direction<4,SIB,CNT,O32>",
         "_Z15k_fused_insert2ILi8EE": "k_fused_insert2<8>", "_Z15k_fused_insert2ILi2EE": "k_fused_insert2<2>", "_Z14k_fused_insertill": "k_fused_insert"}
 txt = open(T + "/remarks.txt").read()
 blocks = re.split(r"Function Name: ", txt)[1:]
+if sys.argv[2] != "fused.hip":
+    want = {b.split()[0]: b.split()[0][:36] for b in blocks}
 res = {}
 for b in blocks:
     name = b.split()[0]
