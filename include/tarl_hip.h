@@ -932,6 +932,45 @@ int tarl_occupancy_accumulate(const float* ring, const int32_t* thr, int64_t F, 
                               int64_t timestep, int64_t bin_seconds, int64_t first_bin, int64_t H, int32_t* veh,
                               int32_t* full, int32_t* peak, tarl_stream stream);
 
+/* ---- per-trip report of a vectorised evaluation ------------------------------------------------------------------------------
+ * What an episode leaves behind in the K agent tables, agents fp32 [K][A][9] with environment k at agents + k * a_bstride
+ * (as tarl_episode_summary takes them; row 0, the dummy, is skipped). An agent has ARRIVED when DONE == 1; its travel time is
+ * tt = ARRIVAL_TIME - DEPARTURE_TIME in fp32, widened to fp64 (so that sum tt agrees with tarl_episode_summary's sums); it is
+ * ON THE WAY when it has not arrived and ON_WAY == 1. No floating-point atomics; every fp64 sum follows the fixed order
+ * written at the top of csrc/trips.hip, which does not depend on a_bstride: two runs on one input are bit-identical.
+ * tarl_trip_agent_stats: over the K environments, per agent; every output has A entries and entry 0 is written as zero.
+ *   n_done, n_way int32: the environments in which the agent arrived / was on the way at the end; tt_sum, tt_sumsq fp64 over
+ *   the environments in which it arrived; tt_min, tt_max fp32 (+inf / -inf where n_done == 0). agents_b (nullable; same K and
+ *   A, its own b_bstride): the baseline run. Environment k is a usable pair for agent a when a arrived in BOTH runs; with
+ *   d = (double)tt_a - (double)tt_b over the usable pairs: n_both int32, d_sum, d_sumsq fp64, n_faster (d < 0) and n_slower
+ *   (d > 0) int32. The five paired outputs are required with agents_b and ignored (may be null) without it. ff (nullable)
+ *   fp64 [A], a free-flow time per agent, and n_under int32 (both or neither): the environments in which the agent arrived
+ *   with (double)tt < ff[a] (never for ff = +inf, which means none), which shows how good a yardstick ff is (it is a reference value, not a lower bound).
+ * tarl_trip_bin_stats: over the agents, per (environment, time bin); every output is [K][H]. The bin of a clock value c is
+ *   clamp((int64)floorf(c) / bin_seconds - first_bin, 0, H - 1) (a NaN or negative clock counts as 0, one from 2^62 on falls
+ *   in the last bin). The departure of an agent is the same in every environment, so the caller sorts the agents by departure
+ *   bin once per population: perm int32 [max(A - 1, 1)] lists the agents 1 .. A - 1 bin by bin (within a bin in the order in
+ *   which their travel times are to be added) and seg int32 [H + 1] the start of every bin's segment in perm, seg[H] = A - 1.
+ *   An entry of perm outside [1, A) is skipped and seg is clamped to [0, A - 1]: foreign values miscount, nothing is read or
+ *   written out of bounds. dep_done, dep_way int32: the agents of departure bin h that arrived / are on the way at the end;
+ *   dep_tt fp64: sum tt over the arrived agents of departure bin h; arr int32: the agents that arrived, binned by
+ *   ARRIVAL_TIME (the arrivals curve of the leg histogram). ff (nullable) fp64 [A]: a free-flow time per agent, +inf = none;
+ *   with it dep_ff fp64 = sum ff over the arrived agents of departure bin h with a finite ff and dep_ff_n int32 their number
+ *   (both required with ff, ignored without it), so that the mean free-flow time by departure time, dep_ff / dep_ff_n, is taken
+ *   over the right set (the mean delay is dep_tt / dep_done - dep_ff / dep_ff_n; the two sets are equal where every arrived
+ *   agent has a finite ff).
+ * Refused on the host, before anything is launched and with the outputs untouched: a null argument, K or A < 1 or >= 2^31,
+ *   a_bstride < 9 A, bin_seconds < 1, first_bin < 0, H outside [1, TARL_TRIP_MAX_BINS], K * H >= 2^31. */
+#define TARL_TRIP_MAX_BINS 4096
+int tarl_trip_agent_stats(const float* agents, const float* agents_b, const double* ff, int64_t K, int64_t num_agents,
+                          int64_t a_bstride, int64_t b_bstride, int32_t* n_under, int32_t* n_done, int32_t* n_way, double* tt_sum, double* tt_sumsq, float* tt_min,
+                          float* tt_max, int32_t* n_both, double* d_sum, double* d_sumsq, int32_t* n_faster, int32_t* n_slower,
+                          tarl_stream stream);
+int tarl_trip_bin_stats(const float* agents, int64_t K, int64_t num_agents, int64_t a_bstride, const int32_t* perm,
+                        const int32_t* seg, const double* ff, int64_t bin_seconds, int64_t first_bin, int64_t H,
+                        int32_t* dep_done, int32_t* dep_way, int32_t* arr, double* dep_tt, double* dep_ff, int32_t* dep_ff_n,
+                        tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

@@ -5,7 +5,7 @@
 ``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
 ``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
 comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` and the per-road link counts of either
-``--eval-link-counts`` / ``--eval-link-bin``."""
+``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy`` and ``--eval-trips``)."""
 import argparse
 import os
 import sys
@@ -100,6 +100,12 @@ OPTIONS = (
                                    "(dijkstra_occupancy.csv) with vehicle-seconds, occupancy per bin, v/c, peak and frames "
                                    "at capacity per road and, with --eval-baseline, the paired differences; `occupancy` in "
                                    "the JSON file")),
+    ("--eval-trips", dict(action="store_true",
+                          help="--eval-envs / --dijkstra-envs, eval: reduce the K agent tables per traveller: arrival share, "
+                               "travel time (mean, sd, se, interval, min, max) over the environments, delay against the "
+                               "free-flow time and, with --eval-baseline, the paired difference per trip; a `Trips` block "
+                               "with a table by departure time (bins of --eval-link-bin seconds), eval_trips.csv and "
+                               "eval_trips_by_departure.csv (dijkstra_trips*.csv); `trips` in the JSON file")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--checkpoint", dict(type=str, default=None,

@@ -40,6 +40,7 @@ class RunnerArgs:
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
     eval_link_bin: int = 3600      # ... in time bins of this many seconds
     eval_occupancy: bool = False   # eval_envs / dijkstra_envs: per-road occupancy and time at capacity (bins of eval_link_bin)
+    eval_trips: bool = False       # eval_envs / dijkstra_envs: per-traveller travel time and delay (bins of eval_link_bin)
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -71,6 +72,9 @@ class RunnerArgs:
         if self.eval_occupancy and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_occupancy sums per-road vehicle counts and frames at capacity in the vectorised "
                              "evaluation: it needs eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_trips and not (self.eval_envs or self.dijkstra_envs):
+            raise ValueError("eval_trips reduces the agent tables of the vectorised evaluation per traveller: it needs "
+                             "eval_envs > 0 or dijkstra_envs > 0")
         if self.eval_link_bin is None or int(self.eval_link_bin) < 1:
             raise ValueError(f"eval_link_bin must be >= 1 second, got {self.eval_link_bin!r}")
         if int(self.iterations) < 1:
@@ -335,7 +339,30 @@ class Runner:
         kw = dict(link_counts=True, link_bin_seconds=a.eval_link_bin) if a.eval_link_counts else {}
         if a.eval_occupancy:
             kw.update(occupancy=True, link_bin_seconds=a.eval_link_bin)
+        if a.eval_trips:        # the free-flow edge weights are those the policy net's shortest-path prior is built from
+            sim = self.simulator if a.algo == "dijkstra" else self.env.simulator
+            g, h = sim.graph, sim.h
+            kw.update(trips=True, link_bin_seconds=a.eval_link_bin,
+                      trip_free_flow=g.x[:, h.FREE_FLOW_TIME_TRAVEL][g.edge_index[1]])
         return kw
+
+    def _trips_output(self, res, baseline, path, path_by_departure):
+        """--eval-trips: the ``Trips`` block, one CSV row per agent at ``path`` and one per departure bin at
+        ``path_by_departure`` -> the summary for the JSON file (never the A-row tables)."""
+        import csv
+        from tarl_hip.evaluator import trip_lines, trip_report, trip_summary
+        rep = trip_report(res, baseline=baseline)
+        print("\n=== Trips ===")
+        for line in trip_lines(rep):
+            print(line)
+        if rep["available"]:
+            for where, cols, rows in ((path, rep["columns"], rep["rows"]),
+                                      (path_by_departure, rep["by_departure_columns"], rep["by_departure"])):
+                with open(where, "w", newline="") as f:
+                    w = csv.DictWriter(f, fieldnames=cols)
+                    w.writeheader()
+                    w.writerows(rows)
+        return trip_summary(rep)
 
     def _occupancy_output(self, res, baseline, path):
         """--eval-occupancy: the ``Occupancy`` block, one CSV row per road at ``path`` (capacity and threshold; vehicle-seconds
@@ -388,6 +415,9 @@ class Runner:
             doc["link_counts"] = self._link_counts_output(res, None, out_dir / "dijkstra_link_counts.csv")
         if self.args.eval_occupancy:
             doc["occupancy"] = self._occupancy_output(res, None, out_dir / "dijkstra_occupancy.csv")
+        if self.args.eval_trips:
+            doc["trips"] = self._trips_output(res, None, out_dir / "dijkstra_trips.csv",
+                                              out_dir / "dijkstra_trips_by_departure.csv")
         with open(out_dir / "dijkstra_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "dijkstra_envs.csv", "w", newline="") as f:
@@ -413,8 +443,13 @@ class Runner:
         if a.policy_head == "embedding_dijkstra" and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
         ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw())
-        results = {"mode": ev.run(frames, deterministic=True),
-                   "sampled": ev.run(frames, deterministic=False) if a.eval_sampled else None}
+        results = {"mode": ev.run(frames, deterministic=True), "sampled": None}
+        pair = None
+        if a.eval_trips and a.eval_baseline == "dijkstra" and not results["mode"].domain_exit:
+            # the MODE run's agent tables, for the baseline's paired launch: a sampled run would overwrite them
+            pair = engine.agents.clone() if a.eval_sampled else engine.agents
+        if a.eval_sampled:
+            results["sampled"] = ev.run(frames, deterministic=False)
         doc, rows = {}, []
         for key, label in (("mode", "MODE"), ("sampled", "sampled")):
             res = results[key]
@@ -428,7 +463,7 @@ class Runner:
             # the router on a second engine with the same seed, K and population: the same noise streams as the policy run
             from tarl_hip.evaluator import paired_lines, paired_report
             base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), "dijkstra",
-                                **self._link_kw()).run(frames)
+                                **self._link_kw()).run(frames, trip_pair=pair)
             rep = paired_report(results["mode"], base)
             self._print_block("Baseline (dijkstra)", base)
             print("\n=== Policy \u2212 baseline (paired) ===")
@@ -446,6 +481,9 @@ class Runner:
                                                           out_dir / "eval_link_counts.csv")
         if a.eval_occupancy:
             doc["occupancy"] = self._occupancy_output(results["mode"], results.get("baseline"), out_dir / "eval_occupancy.csv")
+        if a.eval_trips:
+            doc["trips"] = self._trips_output(results["mode"], results.get("baseline"), out_dir / "eval_trips.csv",
+                                              out_dir / "eval_trips_by_departure.csv")
         with open(out_dir / "eval_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "eval_envs.csv", "w", newline="") as f:

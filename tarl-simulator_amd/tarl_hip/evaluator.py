@@ -115,6 +115,11 @@ class EvalResult:
     occupancy_stats: dict | None = field(default=None, compare=False)       # link_moments of each of the three arrays
     occupancy_frames_per_bin: list | None = None  # frames run in each of the H bins (bin h = occupancy_meta first_bin + h)
     occupancy_meta: dict | None = field(default=None, compare=False)        # first_bin, bin_seconds, timestep, max, thr
+    # trips=True (never after a domain exit): the agent tables reduced per agent and per (environment, time bin)
+    trips: dict | None = field(default=None, compare=False)                 # ops.trip_agent_stats, numpy arrays (A,)
+    trip_bins: dict | None = field(default=None, compare=False)             # ops.trip_bin_stats, numpy arrays (K, H)
+    trip_meta: dict | None = field(default=None, compare=False)             # first_bin, bin_seconds, origin, destination,
+    #                                                                         departure, free_flow (A,), paired
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -615,11 +620,270 @@ def occupancy_summary(report: dict):
     return clean({k: v for k, v in report.items() if k != "rows"})
 
 
+# ---- per-trip report (VecEvaluator(trips=True)) ----------------------------------------------------------------------------------
+TRIP_FF_CHUNK_BYTES = 256 << 20     # the fp64 distance rows of one ops.destination_trees call of the free-flow times
+TRIP_CHANCE = 0.025                 # share of agents without an effect whose 95 % interval lies on one side of 0
+TRIP_FF_NOTE = ("free_flow is a reference value, not a lower bound: the withdraw rule and the step order decide when a trip "
+                "ends, so a travel time can lie below it")
+
+
+def trip_free_flow_times(engine, weights):
+    """The free-flow time of every agent of ``engine`` (environment 0's table) -> fp64 (A,) on the device: FREE_FLOW of its
+    origin road plus the distance origin -> destination under the edge weights ``weights`` fp32 (E,) from
+    ``ops.destination_trees(want_dist=True)`` over the distinct destinations (src.agents.base.destination_set's rule), built
+    a block of destinations at a time; +inf where the destination cannot be reached or an id is out of range, and for the
+    dummy row 0. :data:`TRIP_FF_NOTE` applies."""
+    N, dev = engine.N, engine.device
+    w = weights.detach().to(dev, torch.float32).reshape(-1).contiguous()
+    if w.numel() != engine.E:
+        raise ValueError(f"trip_free_flow must hold one weight per edge ({engine.E}), got {w.numel()}")
+    ag = engine.agents[0]
+    o, d = ag[:, 0].to(torch.int64), ag[:, 1].to(torch.int64)
+    ok = (o >= 0) & (o < N) & (d >= 0) & (d < N)
+    ok[0] = False
+    dests = torch.unique(d[ok]).contiguous()
+    ff = torch.full((engine.A,), float("inf"), dtype=torch.float64, device=dev)
+    if dests.numel() == 0:
+        return ff
+    slot = torch.full((N,), -1, dtype=torch.int64, device=dev)
+    slot[dests] = torch.arange(dests.numel(), dtype=torch.int64, device=dev)
+    oc, sl = o.clamp(0, N - 1), slot[d.clamp(0, N - 1)]
+    own = engine.static_node_features[0, :, 2].to(torch.float64)        # FREE_FLOW_TIME_TRAVEL of the origin road
+    rows = max(1, TRIP_FF_CHUNK_BYTES // (8 * N))
+    for c0 in range(0, int(dests.numel()), rows):
+        _, dist = ops.destination_trees(engine.plan, w, dests[c0:c0 + rows].contiguous(), want_next_hop=False, want_dist=True)
+        here = ok & (sl >= c0) & (sl < c0 + dist.size(0))
+        val = own[oc] + dist[(sl - c0).clamp(0, dist.size(0) - 1), oc]
+        ff = torch.where(here, val, ff)
+    return ff
+
+
+def _trip_moments(n, s1, s2):
+    """mean, sd (ddof 1), se and interval of n values with sum s1 and sum of squares s2, the rules of :func:`aggregate`:
+    the mean needs one value, the others two."""
+    out = {"mean": None, "sd": None, "se": None, "ci95_lo": None, "ci95_hi": None}
+    n = int(n)
+    if n >= 1:
+        out["mean"] = float(s1) / n
+    if n >= 2:
+        sd = math.sqrt(max(0.0, (float(s2) - float(s1) * float(s1) / n) / (n - 1)))
+        se = sd / math.sqrt(n)
+        out.update(sd=sd, se=se, ci95_lo=out["mean"] - 1.96 * se, ci95_hi=out["mean"] + 1.96 * se)
+    return out
+
+
+def trip_bin_names(first_bin, num_bins, bin_seconds):
+    """Labels of the stored bins, by ABSOLUTE bin: ``5h``, ``6h`` for hourly bins, ``bin<k>`` else."""
+    return [f"{first_bin + h}h" if int(bin_seconds) == 3600 else f"bin{first_bin + h}" for h in range(num_bins)]
+
+
+def _trip_same_population(a: EvalResult, b: EvalResult):
+    return all(np.array_equal(a.trip_meta[k], b.trip_meta[k]) for k in ("origin", "destination", "departure"))
+
+
+def trip_report(result: EvalResult, baseline: EvalResult | None = None) -> dict:
+    """Per-agent rows, a by-departure table and a summary of the trips of one evaluation (``VecEvaluator(trips=True)``),
+    formed in float64 on the host from the kernels' counts and sums.
+    Every row: ``agent``, ``origin``, ``destination``, ``departure``, ``free_flow`` (``None``: none); ``arrival_share`` =
+    n_done / K and ``envs_on_way``; ``tt_mean``, ``tt_sd`` (ddof 1), ``tt_se``, ``tt_ci95_lo`` / ``_hi`` (mean -+ 1.96 se, normal
+    approximation), ``tt_min``, ``tt_max`` over the environments in which the agent arrived — the mean, min and max ``None``
+    without an arrival, the spread ``None`` below two, as in :func:`aggregate`; ``delay_mean`` = tt_mean - free_flow and
+    ``delay_ratio`` = tt_mean / free_flow (``None`` without either). :data:`TRIP_FF_NOTE` applies.
+    ``baseline``: the evaluation of another head on the same environments, run with ``run(..., trip_pair=<this run's agent
+    tables>)`` (same K, seed, env_base, frames, bins and population: ``ValueError`` otherwise). The row gains
+    ``baseline_arrival_share``, ``baseline_tt_mean`` and, over the environments in which the agent arrived in BOTH runs, the
+    paired difference result - baseline: ``paired_n``, ``paired_diff_mean``, ``paired_diff_se``, ``paired_diff_ci95_lo`` /
+    ``_hi``, ``n_faster`` and ``n_slower`` (environments in which the trip was faster / slower than under the baseline).
+    The summary classifies every agent with paired_n >= 2 as faster (interval entirely below 0), slower (entirely above) or
+    neither, the sign of the mean deciding where se = 0, and sets next to both counts the number expected by chance alone,
+    :data:`TRIP_CHANCE` x the classified agents. A run without trips (a domain exit has none):
+    ``{"available": False, "reason": ...}``."""
+    if result.domain_exit or result.trips is None:
+        why = "a run that left the domain has no statistics" if result.domain_exit else "the run did not reduce its trips"
+        return {"available": False, "reason": why}
+    tr, tb, meta = result.trips, result.trip_bins, result.trip_meta
+    K, H = tb["dep_done"].shape
+    A = tr["n_done"].shape[0]
+    ff = meta["free_flow"]
+    has_ff = ff is not None
+    pair = None
+    if baseline is not None:
+        if baseline.envs != K:
+            raise ValueError(f"trip_report needs the same environments: envs {K} / {baseline.envs}")
+        for k in ("seed", "env_base"):
+            if result.settings.get(k) != baseline.settings.get(k):
+                raise ValueError(f"trip_report needs equal {k}: {result.settings.get(k)!r} / {baseline.settings.get(k)!r}")
+        if baseline.domain_exit or baseline.trips is None:
+            pair = {"available": False, "reason": "the baseline run has no trips"}
+        else:
+            bm = baseline.trip_meta
+            if baseline.frames_run != result.frames_run or baseline.trip_bins["dep_done"].shape != (K, H) or \
+                    any(bm[k] != meta[k] for k in ("first_bin", "bin_seconds")):
+                raise ValueError("trip_report needs the same frames and bins in both runs")
+            if baseline.trips["n_done"].shape[0] != A or not _trip_same_population(result, baseline):
+                raise ValueError("trip_report needs the same population in both runs (origin, destination, departure)")
+            if not bm.get("paired") or "n_both" not in baseline.trips:
+                pair = {"available": False, "reason": "the baseline run was not paired with this one (run(trip_pair=...))"}
+            else:
+                pair = {"available": True, "baseline_head": baseline.head}
+    paired = pair is not None and pair["available"]
+    n_done = tr["n_done"].astype(np.int64)
+    rows = []
+    cls = {"faster": 0, "slower": 0, "neither": 0}
+    for a in range(1, A):
+        n = int(n_done[a])
+        m = _trip_moments(n, tr["tt_sum"][a], tr["tt_sumsq"][a])
+        f = float(ff[a]) if has_ff and math.isfinite(float(ff[a])) else None
+        row = {"agent": a, "origin": int(meta["origin"][a]), "destination": int(meta["destination"][a]),
+               "departure": float(meta["departure"][a]), "free_flow": f, "arrival_share": n / K,
+               "envs_on_way": int(tr["n_way"][a]), "tt_mean": m["mean"], "tt_sd": m["sd"], "tt_se": m["se"],
+               "tt_ci95_lo": m["ci95_lo"], "tt_ci95_hi": m["ci95_hi"], "tt_min": float(tr["tt_min"][a]) if n else None,
+               "tt_max": float(tr["tt_max"][a]) if n else None,
+               "delay_mean": m["mean"] - f if n and f is not None else None,
+               "delay_ratio": m["mean"] / f if n and f is not None and f > 0 else None}
+        if paired:      # the baseline's launch holds d = baseline - result: the difference result - baseline is its negative
+            bt = baseline.trips
+            nb = int(bt["n_both"][a])
+            d = _trip_moments(nb, -float(bt["d_sum"][a]), bt["d_sumsq"][a])
+            row.update(baseline_arrival_share=int(bt["n_done"][a]) / K,
+                       baseline_tt_mean=float(bt["tt_sum"][a]) / int(bt["n_done"][a]) if int(bt["n_done"][a]) else None,
+                       paired_n=nb, paired_diff_mean=d["mean"], paired_diff_se=d["se"], paired_diff_ci95_lo=d["ci95_lo"],
+                       paired_diff_ci95_hi=d["ci95_hi"], n_faster=int(bt["n_slower"][a]), n_slower=int(bt["n_faster"][a]))
+            if nb >= 2:
+                lo, hi = (d["ci95_lo"], d["ci95_hi"]) if d["se"] > 0 else (d["mean"], d["mean"])
+                cls["faster" if hi < 0 else ("slower" if lo > 0 else "neither")] += 1
+        rows.append(row)
+    columns = list(rows[0]) if rows else []
+    live = n_done[1:]
+    trips_total = int(live.sum())
+    summary = {"envs": K, "agents": A - 1, "frames_run": result.frames_run, "trips": trips_total,
+               "arrived_in_every": int((live == K).sum()), "arrived_in_some": int(((live > 0) & (live < K)).sum()),
+               "arrived_in_none": int((live == 0).sum()), "agents_on_way_somewhere": int((tr["n_way"][1:] > 0).sum()),
+               "free_flow": None, "top_delays": []}
+    if has_ff:
+        f = np.asarray(ff, dtype=np.float64)[1:]
+        use = np.isfinite(f) & (live > 0)
+        w = live[use].astype(np.float64)
+        tts, fs = tr["tt_sum"][1:][use].astype(np.float64), f[use]
+        per_delay, per_ratio = tts / w - fs, (tts / w) / np.where(fs > 0, fs, np.nan)
+        n_use = int(w.sum())
+        spread = lambda v: float(np.nanstd(v, ddof=1)) if np.isfinite(v).sum() >= 2 else None      # noqa: E731
+        summary["free_flow"] = {
+            "agents": int(use.sum()), "trips": n_use, "note": TRIP_FF_NOTE,
+            "mean_delay": float((tts - w * fs).sum()) / n_use if n_use else None,
+            "delay_ratio": float(tts.sum()) / float((w * fs).sum()) if n_use and float((w * fs).sum()) > 0 else None,
+            "mean_delay_sd_over_agents": spread(per_delay), "delay_ratio_sd_over_agents": spread(per_ratio),
+            "share_trips_below_free_flow": int(tr["n_under"][1:].sum()) / n_use if n_use else None}
+        top = sorted((r for r in rows if r["delay_mean"] is not None), key=lambda r: (-r["delay_mean"], r["agent"]))[:10]
+        summary["top_delays"] = [{k: r[k] for k in ("agent", "origin", "destination", "departure", "free_flow", "tt_mean",
+                                                    "delay_mean", "arrival_share")} for r in top]
+    # by departure time: per bin over the K environments
+    names = trip_bin_names(meta["first_bin"], H, meta["bin_seconds"])
+    dep_bin = trip_host_bin(meta["departure"][1:], meta["bin_seconds"], meta["first_bin"], H)
+    scheduled = np.bincount(dep_bin, minlength=H)
+    dd, dt = tb["dep_done"].astype(np.float64), tb["dep_tt"].astype(np.float64)
+    by_rows = []
+    for h in range(H):
+        g = aggregate(list(dd[:, h]))
+        tt = aggregate([dt[k, h] / dd[k, h] if dd[k, h] > 0 else None for k in range(K)])
+        row = {"bin": names[h], "scheduled": int(scheduled[h]), "arrived_mean": g["mean"], "arrived_se": g["se"],
+               "on_way_mean": float(tb["dep_way"][:, h].mean()), "tt_mean": tt["mean"], "tt_se": tt["se"], "delay_mean": None,
+               "delay_se": None, "arrivals_mean": float(tb["arr"][:, h].mean())}
+        if has_ff:
+            fn, fs = tb["dep_ff_n"].astype(np.float64), tb["dep_ff"].astype(np.float64)
+            dl = aggregate([dt[k, h] / dd[k, h] - fs[k, h] / fn[k, h] if dd[k, h] > 0 and fn[k, h] > 0 else None
+                            for k in range(K)])
+            row.update(delay_mean=dl["mean"], delay_se=dl["se"])
+        by_rows.append(row)
+    if pair is not None:
+        if paired:
+            n_cls = sum(cls.values())
+            pair.update(agents_classified=n_cls, agents_faster=cls["faster"], agents_slower=cls["slower"],
+                        agents_neither=cls["neither"], expected_by_chance=TRIP_CHANCE * n_cls,
+                        pairs=int(baseline.trips["n_both"][1:].sum()),
+                        mean_paired_diff=(-float(baseline.trips["d_sum"][1:].sum()) / int(baseline.trips["n_both"][1:].sum())
+                                          if int(baseline.trips["n_both"][1:].sum()) else None))
+        summary["paired"] = pair
+    return {"available": True, "head": result.head, "bin_seconds": int(meta["bin_seconds"]), "first_bin": int(meta["first_bin"]),
+            "bins": names, "columns": columns, "rows": rows, "by_departure_columns": list(by_rows[0]),
+            "by_departure": by_rows, "summary": summary}
+
+
+def trip_host_bin(clock, bin_seconds, first_bin, num_bins):
+    """The kernels' bin rule on the host: ``clamp(floor(c) // bin_seconds - first_bin, 0, num_bins - 1)`` of fp32 clock values
+    (NaN and negatives as 0) -> int64."""
+    c = np.nan_to_num(np.asarray(clock, dtype=np.float32).astype(np.float64), nan=0.0, posinf=2.0 ** 62, neginf=0.0)
+    c = np.clip(np.floor(c), 0.0, 2.0 ** 62)
+    return np.clip(c.astype(np.int64) // int(bin_seconds) - int(first_bin), 0, int(num_bins) - 1)
+
+
+def _f(v, fmt=".2f"):
+    return "-" if v is None else format(v, fmt)
+
+
+def trip_lines(report: dict):
+    """:func:`trip_report` as printable lines (the ``Trips`` block)."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    s = report["summary"]
+    out = [f"{'agents:':22} {s['agents']:12d}   arrived in every environment {s['arrived_in_every']}, in some "
+           f"{s['arrived_in_some']}, in none {s['arrived_in_none']} ({s['envs']} environments, {s['frames_run']} frames; "
+           f"{s['trips']} trips completed, {s['agents_on_way_somewhere']} agents still on the way somewhere)"]
+    f = s["free_flow"]
+    if f is None:
+        out.append("free flow:             not available (no free-flow weights): no delay columns")
+    elif not f["trips"]:
+        out.append("free flow:             no completed trip with a free-flow time")
+    else:
+        out.append(f"{'mean delay:':22} {f['mean_delay']:12.3f} s  (tt - free flow, trip-weighted over {f['trips']} trips of "
+                   f"{f['agents']} agents; sd over the agents {_f(f['mean_delay_sd_over_agents'], '.3f')})")
+        out.append(f"{'delay ratio:':22} {_f(f['delay_ratio'], '12.4f')}    (sum tt / sum free flow; sd over the agents "
+                   f"{_f(f['delay_ratio_sd_over_agents'], '.4f')})")
+        out.append(f"{'below free flow:':22} {100.0 * f['share_trips_below_free_flow']:12.2f} % of the trips have tt < free flow "
+                   f"(a reference value, not a lower bound)")
+        out.append("agents with the largest mean delay:")
+        for r in s["top_delays"]:
+            out.append(f"  agent {r['agent']:7d}  {r['origin']:6d} -> {r['destination']:6d}  departs {r['departure']:9.1f}  "
+                       f"free flow {r['free_flow']:8.1f}  tt {r['tt_mean']:9.2f}  delay {r['delay_mean']:9.2f}  "
+                       f"arrived in {100.0 * r['arrival_share']:.0f} %")
+    out.append(f"By departure time (bins of {report['bin_seconds']} s; means over the environments, arrived with its standard error):")
+    out.append(f"  {'bin':>8} {'scheduled':>9} {'arrived':>18} {'mean tt':>10} {'mean delay':>10} {'arrivals in bin':>15}")
+    for r in report["by_departure"]:
+        arrived = f"{_f(r['arrived_mean'])}" + (f" +- {_f(r['arrived_se'])}" if r["arrived_se"] is not None else "")
+        out.append(f"  {r['bin']:>8} {r['scheduled']:9d} {arrived:>18} {_f(r['tt_mean']):>10} {_f(r['delay_mean']):>10} "
+                   f"{_f(r['arrivals_mean']):>15}")
+    p = s.get("paired")
+    if p is not None and not p["available"]:
+        out.append(f"paired:                not available: {p['reason']}")
+    elif p is not None:
+        out.append(f"{'policy - ' + p['baseline_head'] + ':':22} {_f(p['mean_paired_diff'], '12.3f')} s mean paired difference "
+                   f"over {p['pairs']} trips completed in both runs")
+        out.append(f"{'per agent:':22} faster under the policy {p['agents_faster']}, slower {p['agents_slower']}, neither "
+                   f"{p['agents_neither']} of {p['agents_classified']} agents with >= 2 pairs (95% interval of the paired "
+                   f"difference entirely below / above 0, normal approx.); expected by chance alone: "
+                   f"{p['expected_by_chance']:.1f} on either side")
+    return out
+
+
+def trip_summary(report: dict):
+    """The report without its per-agent and by-departure rows, nan as ``None``: what the JSON files carry (never the A-row
+    tables)."""
+    def clean(v):
+        if isinstance(v, dict):
+            return {k: clean(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [clean(x) for x in v]
+        if isinstance(v, float) and (math.isnan(v) or math.isinf(v)):
+            return None
+        return v
+    return clean({k: v for k, v in report.items() if k not in ("rows", "by_departure")})
+
+
 class VecEvaluator:
     def __init__(self, engine, head="embedding", *, emb=None, temperature=1.0, edge_mlp=None, prior_table=None,
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
-                 link_block=None, occupancy=False, occupancy_block=None):
+                 link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -639,7 +903,13 @@ class VecEvaluator:
         (:func:`capacity_threshold` of the engine's static MAX column, computed once on the host) and keep its peak. The
         frames write their ``counts`` slice into an fp32 ring (F, N, K) of ``occupancy_block`` frames (default: the largest
         block <= ``poll_frames`` that keeps the ring within 256 MB, at least 1) and one ``ops.occupancy_accumulate`` launch
-        follows every block. Without the flag nothing is allocated and every frame is called as it always was."""
+        follows every block. Without the flag nothing is allocated and every frame is called as it always was.
+        ``trips``: after the episode also reduce the K agent tables per agent over the environments
+        (``ops.trip_agent_stats``) and per environment and time bin of ``link_bin_seconds`` over the agents
+        (``ops.trip_bin_stats``): two calls after ``ops.episode_summary``, none per frame. ``run()`` refuses environments
+        whose ORIGIN, DESTINATION or DEPARTURE_TIME differ (per-agent statistics over different populations mean nothing).
+        ``trip_free_flow`` fp32 (E,): free-flow edge weights; the free-flow time of every agent
+        (:func:`trip_free_flow_times`, one ``ops.destination_trees`` pass here) then serves as the reference for its delay."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -695,6 +965,14 @@ class VecEvaluator:
             self.occ_thr_host = capacity_threshold(self.occ_max)
             self.occ_thr = torch.from_numpy(self.occ_thr_host).to(dev)
             self.occ_acc = None         # veh, full (K, H, N) and peak (K, 1, N) int32, sized by run() for its frames
+        self.trips = bool(trips)
+        if self.trips:
+            self.link_bin_seconds = int(link_bin_seconds)
+            if self.link_bin_seconds < 1:
+                raise ValueError("link_bin_seconds must be >= 1")
+            self.trip_ff = None if trip_free_flow is None else trip_free_flow_times(engine, trip_free_flow)
+        elif trip_free_flow is not None:
+            raise ValueError("trip_free_flow is the reference of the per-trip report: it needs trips=True")
         # scratch, allocated once
         self.log_prob = torch.zeros(K, dtype=torch.float32, device=dev)
         self.action8 = torch.zeros((K, N), dtype=torch.uint8, device=dev)          # the last frame's action bytes
@@ -851,8 +1129,12 @@ class VecEvaluator:
 
     # -- the evaluation ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def run(self, frames=None, deterministic=True):
-        """Reset the engine, run ``frames`` frames (default: until the episode ends) and return an :class:`EvalResult`."""
+    def run(self, frames=None, deterministic=True, trip_pair=None):
+        """Reset the engine, run ``frames`` frames (default: until the episode ends) and return an :class:`EvalResult`.
+        ``trip_pair`` (``trips=True``): the agent tables (K, A, 9) that another run on the same environments left behind
+        (its ``engine.agents``, still on the device); this run's per-agent launch then also pairs the two, trip by trip:
+        ``trips`` gains n_both, d_sum, d_sumsq, n_faster, n_slower with d = this run - the other (``trip_report`` of the OTHER
+        run takes this one as its ``baseline``)."""
         t_start = time.perf_counter()
         eng, fs = self.eng, self.eng.fs
         T = self.episode_frames if frames is None else int(frames)
@@ -860,15 +1142,28 @@ class VecEvaluator:
             raise ValueError("frames must be >= 1")
         if self.head == "dijkstra" and not deterministic:
             raise ValueError("head 'dijkstra' has no sampled mode: the shortest-path router is deterministic given the state")
+        if trip_pair is not None and not self.trips:
+            raise ValueError("trip_pair pairs the trips of two runs: it needs trips=True")
         self._reserve(T)
         self._flag_host.zero_()
         fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
         eng.reset()
+        if self.trips:
+            pop = eng.agents[:, :, :3]
+            if not bool((pop == pop[:1]).all()):
+                raise ValueError("trips=True needs the same population in every environment: ORIGIN, DESTINATION or "
+                                 "DEPARTURE_TIME differ between the agent tables")
+            if trip_pair is not None and (tuple(trip_pair.shape) != tuple(eng.agents.shape) or
+                                          not bool((trip_pair[:, :, :3] == pop).all())):
+                raise ValueError("trip_pair must hold the same population as this engine's agent tables")
         self._start(bool(deterministic))
-        if self.link_counts or self.occupancy:      # one binning for both per-road reports
+        if self.link_counts or self.occupancy or self.trips:      # one binning for the per-road reports and the trips
             clock0, step, bins = int(eng.time), int(eng.timestep), self.link_bin_seconds
             first_bin = clock0 // bins
             H = (clock0 + (T - 1) * step) // bins - first_bin + 1
+        if self.trips and H > ops.TRIP_MAX_BINS:
+            raise ValueError(f"trips=True stores at most {ops.TRIP_MAX_BINS} time bins (ops.TRIP_MAX_BINS); {T} frames in bins "
+                             f"of {bins} s reach {H}: widen link_bin_seconds")
         if self.link_counts:
             if self.link_acc is None or self.link_acc.size(1) != H:
                 self.link_acc = torch.empty((eng.B, H, eng.N), dtype=torch.int32, device=eng.device)
@@ -944,5 +1239,24 @@ class VecEvaluator:
             res.occupancy_frames_per_bin = [int(x) for x in np.bincount(bins_of, minlength=H)]
             res.occupancy_meta = dict(first_bin=int(first_bin), bin_seconds=int(bins), timestep=int(step),
                                       max=self.occ_max.copy(), thr=self.occ_thr_host.copy())
+        if self.trips:
+            self._trip_reduce(res, trip_pair, first_bin, bins, H)
         res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
         return res
+
+    def _trip_reduce(self, res, trip_pair, first_bin, bins, H):
+        """The two trip reductions of a finished run into ``res``. Clock values outside the H bins of the frames (a
+        departure before the first frame's bin) are clamped into the first / last bin by the kernel."""
+        eng = self.eng
+        # the agents sorted by departure bin: once per run, for all K environments (run() has checked that they agree)
+        order = ops.trip_departure_order(eng.agents[0, :, 2], bin_seconds=bins, first_bin=first_bin, num_bins=H)
+        per_agent = ops.trip_agent_stats(eng.agents, trip_pair, free_flow=self.trip_ff)
+        per_bin = ops.trip_bin_stats(eng.agents, bin_seconds=bins, first_bin=first_bin, num_bins=H, free_flow=self.trip_ff,
+                                     order=order)
+        res.trips = {k: v.cpu().numpy() for k, v in per_agent.items()}
+        res.trip_bins = {k: v.cpu().numpy() for k, v in per_bin.items()}
+        pop = eng.agents[0, :, :3].cpu().numpy()
+        res.trip_meta = dict(first_bin=int(first_bin), bin_seconds=int(bins), origin=pop[:, 0].astype(np.int64),
+                             destination=pop[:, 1].astype(np.int64), departure=pop[:, 2].copy(),
+                             free_flow=None if self.trip_ff is None else self.trip_ff.cpu().numpy(),
+                             paired=trip_pair is not None)

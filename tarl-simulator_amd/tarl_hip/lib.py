@@ -141,6 +141,8 @@ SIGNATURES = {
     "tarl_link_counts_accumulate": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
     "tarl_link_count_stats": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "tarl_occupancy_accumulate": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "tarl_trip_agent_stats": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64] + [_p] * 12 + [_p]),
+    "tarl_trip_bin_stats": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64] + [_p] * 6 + [_p]),
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),

@@ -815,6 +815,154 @@ def occupancy_accumulate(ring, thr, veh, full, peak, *, t0, timestep=1, bin_seco
     return veh, full, peak
 
 
+TRIP_MAX_BINS = 4096      # = TARL_TRIP_MAX_BINS of include/tarl_hip.h: the arrivals histogram of one environment lives in LDS
+_TRIP_AGENT_SPEC = (("n_done", torch.int32), ("n_way", torch.int32), ("tt_sum", torch.float64), ("tt_sumsq", torch.float64),
+                    ("tt_min", torch.float32), ("tt_max", torch.float32))
+_TRIP_PAIR_SPEC = (("n_both", torch.int32), ("d_sum", torch.float64), ("d_sumsq", torch.float64), ("n_faster", torch.int32),
+                   ("n_slower", torch.int32))
+_TRIP_BIN_SPEC = (("dep_done", torch.int32), ("dep_way", torch.int32), ("arr", torch.int32), ("dep_tt", torch.float64))
+_TRIP_FF_SPEC = (("dep_ff", torch.float64), ("dep_ff_n", torch.int32))
+
+
+def _trip_tables(agents, name):
+    """(K, A, 9) fp32 agent tables -> (K, A, a_bstride), meta first and device last as :func:`_meta` does."""
+    if agents.dim() != 3:
+        raise ValueError(f"{name} must be (K, A, 9), got {tuple(agents.shape)}")
+    if agents.dtype != torch.float32:
+        raise TypeError(f"{name} must be {torch.float32}, got {agents.dtype}")
+    K, A = agents.size(0), agents.size(1)
+    if K < 1 or A < 1:
+        raise ValueError(f"{name} must not be empty")
+    if agents.size(2) != 9 or agents.stride(2) != 1 or agents.stride(1) != 9 or (K > 1 and agents.stride(0) < 9 * A):
+        raise ValueError(f"{name} must be (K, A, 9) with contiguous rows and tables that do not overlap")
+    return K, A, agents.stride(0) if K > 1 else 9 * A
+
+
+def _trip_out(out, spec, shape, device):
+    if out is None:
+        out = {}
+    for name, dt in spec:
+        if name in out:
+            _meta(out[name], dt, shape, name)
+        else:
+            out[name] = torch.empty(shape, dtype=dt, device=device)
+    return out
+
+
+def trip_agent_stats(agents, agents_b=None, *, free_flow=None, out=None):
+    """Per agent over the K environments of the agent tables ``agents`` fp32 (K, A, 9) after an episode
+    (tarl_trip_agent_stats; row 0, the dummy, is skipped and entry 0 of every output is zero). Returns the dict ``n_done``,
+    ``n_way`` int32 (A,): the environments in which the agent arrived (DONE == 1) / was still on the way; ``tt_sum``,
+    ``tt_sumsq`` fp64 (A,) of the travel time ARRIVAL_TIME - DEPARTURE_TIME (fp32, widened) over the environments in which it
+    arrived; ``tt_min``, ``tt_max`` fp32 (A,), +inf / -inf for an agent that never arrived. ``agents_b``: the tables of a
+    second run of the same shape (the baseline); the dict gains, over the environments in which the agent arrived in BOTH runs
+    and with d = tt - tt_b in fp64, ``n_both`` int32, ``d_sum``, ``d_sumsq`` fp64, ``n_faster`` (d < 0) and ``n_slower``
+    (d > 0) int32. ``free_flow`` fp64 (A,): a free-flow time per agent; the dict gains ``n_under`` int32, the environments in
+    which the agent arrived with tt < free_flow. The fp64 sums follow a fixed order (csrc/trips.hip): bit-identical from run to run. ``out``: such a dict
+    (or a part of it) to write into."""
+    K, A, abs_ = _trip_tables(agents, "agents")
+    bbs = 0
+    if agents_b is not None:
+        Kb, Ab, bbs = _trip_tables(agents_b, "agents_b")
+        if (Kb, Ab) != (K, A):
+            raise ValueError(f"agents_b must be {(K, A, 9)} like agents, got {tuple(agents_b.shape)}")
+    if free_flow is not None:
+        _meta(free_flow, torch.float64, (A,), "free_flow")
+    under = (("n_under", torch.int32),) if free_flow is not None else ()
+    spec = under + _TRIP_AGENT_SPEC + (_TRIP_PAIR_SPEC if agents_b is not None else ())
+    dev = agents.device
+    out = _trip_out(out, spec, (A,), dev)
+    _check_dev(agents, torch.float32, "agents")
+    if agents_b is not None:
+        _check_dev(agents_b, torch.float32, "agents_b")
+    if free_flow is not None:
+        _check_dev(free_flow, torch.float64, "free_flow")
+    for name, dt in spec:
+        _check_dev(out[name], dt, name)
+    pair = [out[n].data_ptr() for n, _ in _TRIP_PAIR_SPEC] if agents_b is not None else [None] * 5
+    _lib.check(_lib.load().tarl_trip_agent_stats(agents.data_ptr(), _lib.ptr(agents_b), _lib.ptr(free_flow), K, A, abs_, bbs,
+                                                 out["n_under"].data_ptr() if under else None,
+                                                 *[out[n].data_ptr() for n, _ in _TRIP_AGENT_SPEC], *pair,
+                                                 _lib.current_stream()))
+    return out
+
+
+def _trip_bins(bin_seconds, first_bin, num_bins):
+    bin_seconds, first_bin, num_bins = int(bin_seconds), int(first_bin), int(num_bins)
+    if bin_seconds < 1 or first_bin < 0:
+        raise ValueError("bin_seconds must be >= 1 and first_bin >= 0")
+    if not 1 <= num_bins <= TRIP_MAX_BINS:
+        raise ValueError(f"num_bins must be in [1, {TRIP_MAX_BINS}] (ops.TRIP_MAX_BINS), got {num_bins}")
+    return bin_seconds, first_bin, num_bins
+
+
+def trip_clock_bin(clock, bin_seconds, first_bin, num_bins):
+    """The stored bin of every clock value of ``clock`` (fp32 tensor) -> int64: ``clamp(floor(c) // bin_seconds - first_bin,
+    0, num_bins - 1)``, a NaN or negative clock taken as 0 and one from 2^62 on as the last bin — the rule of
+    tarl_trip_bin_stats, in torch."""
+    c = torch.nan_to_num(clock.to(torch.float32), nan=0.0, posinf=float(2 ** 63), neginf=0.0).clamp(min=0.0)
+    q = torch.div(torch.floor(c.clamp(max=float(2 ** 62))).to(torch.int64), int(bin_seconds), rounding_mode="trunc") - int(first_bin)
+    q = torch.where(c >= float(2 ** 62), torch.full_like(q, int(num_bins) - 1), q)
+    return q.clamp(0, int(num_bins) - 1)
+
+
+def trip_departure_order(departure, *, bin_seconds, first_bin, num_bins):
+    """The agents sorted by departure bin, once per population: ``departure`` fp32 (A,) (the DEPARTURE_TIME column of one
+    agent table, row 0 the dummy) -> (perm int32 (max(A - 1, 1),): the agents 1 .. A - 1 bin by bin, ascending id within a
+    bin; seg int32 (num_bins + 1,): where every bin's segment starts in perm, seg[num_bins] = A - 1). Torch plumbing on the
+    tensor's device; what :func:`trip_bin_stats` takes as ``order``."""
+    bin_seconds, first_bin, num_bins = _trip_bins(bin_seconds, first_bin, num_bins)
+    if departure.dim() != 1 or departure.numel() < 1:
+        raise ValueError(f"departure must be (A,), got {tuple(departure.shape)}")
+    A, dev = departure.numel(), departure.device
+    bins = trip_clock_bin(departure[1:], bin_seconds, first_bin, num_bins)
+    srt, idx = torch.sort(bins, stable=True)
+    perm = torch.zeros(max(A - 1, 1), dtype=torch.int32, device=dev)
+    perm[:A - 1] = (idx + 1).to(torch.int32)
+    seg = torch.searchsorted(srt, torch.arange(num_bins + 1, dtype=torch.int64, device=dev)).to(torch.int32)
+    return perm, seg
+
+
+def trip_bin_stats(agents, *, bin_seconds, first_bin, num_bins, free_flow=None, order=None, out=None):
+    """Per (environment, time bin) over the agents of the tables ``agents`` fp32 (K, A, 9) after an episode
+    (tarl_trip_bin_stats; row 0 is skipped), bin h = absolute bin ``first_bin + h`` of ``bin_seconds`` seconds, clock values
+    outside the ``num_bins`` stored bins clamped into the first / last one. Returns the dict, each (K, num_bins):
+    ``dep_done``, ``dep_way`` int32: the agents whose DEPARTURE_TIME falls into the bin and that arrived / are on the way at the
+    end; ``dep_tt`` fp64: the sum of the travel times of the former; ``arr`` int32: the agents that arrived, binned by
+    ARRIVAL_TIME. ``free_flow`` fp64 (A,): a free-flow time per agent (+inf: none); the dict gains ``dep_ff`` fp64, the sum
+    of the free-flow times of the arrived agents of the bin that have a finite one, and ``dep_ff_n`` int32, their number.
+    The agents are binned by the DEPARTURE_TIME of environment 0, which the caller guarantees to be every environment's
+    (``VecEvaluator`` checks it); ``order``: :func:`trip_departure_order` of that column and the same bins, built once per
+    population (default: built here). At most :data:`TRIP_MAX_BINS` bins; a refused call leaves ``out`` untouched."""
+    K, A, abs_ = _trip_tables(agents, "agents")
+    bin_seconds, first_bin, H = _trip_bins(bin_seconds, first_bin, num_bins)
+    if K * H >= 1 << 31:
+        raise ValueError(f"K * num_bins must stay below 2^31, got {K} * {H}")
+    dev = agents.device
+    if free_flow is not None:
+        _meta(free_flow, torch.float64, (A,), "free_flow")
+    spec = _TRIP_BIN_SPEC + (_TRIP_FF_SPEC if free_flow is not None else ())
+    if order is not None:
+        _meta(order[0], torch.int32, (max(A - 1, 1),), "order[0] (perm)")
+        _meta(order[1], torch.int32, (H + 1,), "order[1] (seg)")
+    out = _trip_out(out, spec, (K, H), dev)
+    _check_dev(agents, torch.float32, "agents")
+    if free_flow is not None:
+        _check_dev(free_flow, torch.float64, "free_flow")
+    if order is None:
+        order = trip_departure_order(agents[0, :, 2], bin_seconds=bin_seconds, first_bin=first_bin, num_bins=H)
+    perm, seg = order
+    for t, name in ((perm, "perm"), (seg, "seg")):
+        _check_dev(t, torch.int32, name)
+    for name, dt in spec:
+        _check_dev(out[name], dt, name)
+    ffo = [out[n].data_ptr() for n, _ in _TRIP_FF_SPEC] if free_flow is not None else [None, None]
+    _lib.check(_lib.load().tarl_trip_bin_stats(agents.data_ptr(), K, A, abs_, perm.data_ptr(), seg.data_ptr(),
+                                               _lib.ptr(free_flow), bin_seconds, first_bin, H,
+                                               *[out[n].data_ptr() for n, _ in _TRIP_BIN_SPEC], *ffo, _lib.current_stream()))
+    return out
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")

@@ -3,6 +3,7 @@
 # resource remarks (-Rpass-analysis=kernel-resource-usage) and the static instruction mix of the device ISA (--save-temps).
 # usage: tools/kernel_resources.sh [extra hipcc flags]   (run from anywhere; writes nothing into the tree)
 #        SRC=occupancy.hip tools/kernel_resources.sh    every kernel of another file of csrc/, under its mangled name
+#        SRC=trips.hip tools/kernel_resources.sh        (the per-trip reductions: the figures of DESIGN 4.16)
 cd "$(dirname "$0")/../tarl-simulator_amd/csrc"
 T=$(mktemp -d)
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Rpass-analysis=kernel-resource-usage \
