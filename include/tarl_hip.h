@@ -355,7 +355,8 @@ int tarl_value_mpnn_bwd(const tarl_plan* plan, const float* node_features, int64
  *                  ld_slots = tarl_fused_slot_floats(Nmax) (>= 3*Nmax, padded to a multiple of 16 floats)
  *   acc_lp int64 [acc_slots][B], acc_n / acc_w fp32 [acc_slots][B]: per-frame accumulator banks (log-prob in 2^-32 fixed
  *   point, sum of counts, agents withdrawn; zeroed by pack; acc_slots >= 1 banks spread the atomics of the many
- *   workgroups that serve one environment)
+ *   workgroups that serve one environment). Every call leaves all banks zero; acc_lp is filled, read and re-armed only
+ *   by calls that are given a log_prob pointer)
  *   a_origin / a_dest int32 [B][A], a_dep fp32 [B][A], a_status uint8 [B][A] (0 waiting, 1 on the way, 2 done);
  *   a_order int32 [B][A] (optional, may be NULL): each environment's agent ids sorted by DEPARTURE_TIME — with it the
  *   insert kernel scans a window of that order from the cursor cur_lo int32 [B] instead of every agent every frame;

@@ -1301,6 +1301,19 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 }
 
 // ---- insert + reward + log-prob reduction (one wave per environment) -----------------------------------------------------
+// The accumulator banks (tarl_fused.acc_lp / acc_n / acc_w, [acc_slots][B], bank = blockIdx.y % acc_slots of the writer):
+//   acc_n  (fp32)   the row pass: the frame's count sum, one coalesced atomic per lane and workgroup; every mode, every frame
+//   acc_w  (fp32)   the row pass: agents withdrawn in the frame (its event rows; zero for most (bank, environment) pairs)
+//   acc_lp (int64)  the per-frame choice (fused_choice_body: k_fused_choice, the choice role of k_fused_insert_choice), and
+//                   only when the caller asked for a log-prob (want_lp): the frame API, TARL_ROLLOUT_MERGE = 0 and 1 (mode 1
+//                   alternates between acc_lp and the caller's acc_scratch by frame parity). The all-frames draw of mode 2
+//                   (k_fused_choice_all) and the state-dependent heads write the log-prob themselves and never touch it.
+// RULE: every bank holds zero bits on entry to and on exit from every call, in every mode. The insert launch of a frame is
+// the banks' only reader; it re-arms what it read, and only where the value loaded was not zero already. It reads acc_lp
+// exactly where the same call's choice filled it — where its log_prob pointer is not null (template parameter LP, chosen by
+// launch_insert from the pointer) — so a launch without a log-prob finds acc_lp zero and leaves it alone. An environment of
+// the packed kernel that goes to the one-environment body afterwards has its banks reduced and re-armed there, once.
+// The sums are exact in any order (small integers in fp32, fixed point in int64): acc_slots changes no result.
 __device__ __forceinline__ bool fused_target(const FusedBufs& fb, PlanOut P, const uint8_t* __restrict__ sel8, int64_t b,
                                              int64_t B, int64_t N, int32_t origin, int32_t* road, int32_t* cap) {
   if (origin < 0 || origin >= N) return false;
@@ -1358,6 +1371,7 @@ struct InsLds {
 #define s_un_k L.un_k
 #define s_un_hd L.un_hd
 #define s_un_tl L.un_tl
+template <bool LP>
 __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax, int64_t B, int64_t N, const FusedBufs& fb, PlanOut P,
                                                   const uint8_t* __restrict__ sel8, float* __restrict__ ag, int64_t A,
                                                   int64_t a_bstride, int use_cong, float t,
@@ -1379,17 +1393,23 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
     s_adm = 0;
   }
   // the frame's accumulator banks (filled by the choice kernel and the row pass, complete before this launch) depend on
-  // nothing below: they are requested first and reduced last
+  // nothing below: they are requested first and reduced last. A bank is re-armed only where it does not already hold
+  // zero bits; the log-prob banks are neither read nor written without LP (nobody filled them: see the section header)
   long long lpf = 0;
   float nf = 0.0f, wf = 0.0f;
   if (wid == 0) {
     for (int64_t sl_ = lane; sl_ < fb.acc_slots; sl_ += 64) {
-      lpf += fb.acc_lp[sl_ * B + b];
-      nf += fb.acc_n[sl_ * B + b];
-      wf += fb.acc_w[sl_ * B + b];
-      fb.acc_lp[sl_ * B + b] = 0;
-      fb.acc_n[sl_ * B + b] = 0.0f;
-      fb.acc_w[sl_ * B + b] = 0.0f;
+      const float n = fb.acc_n[sl_ * B + b], w = fb.acc_w[sl_ * B + b];
+      long long v = 0;
+      if constexpr (LP) v = fb.acc_lp[sl_ * B + b];
+      nf += n;
+      wf += w;
+      lpf += v;
+      if (__float_as_uint(n) != 0u) fb.acc_n[sl_ * B + b] = 0.0f;
+      if (__float_as_uint(w) != 0u) fb.acc_w[sl_ * B + b] = 0.0f;
+      if constexpr (LP) {
+        if (v != 0) fb.acc_lp[sl_ * B + b] = 0;
+      }
     }
   }
   __syncthreads();
@@ -1627,13 +1647,15 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
   // phase 4: the frame's accumulator banks (requested at the top) -> reward, log-prob
   if (wid == 0) {
     for (int off = 32; off > 0; off >>= 1) {
-      lpf += __shfl_down(lpf, off);
+      if constexpr (LP) lpf += __shfl_down(lpf, off);
       nf += __shfl_down(nf, off);      // sums of small integers: exact in fp32 in any order
       wf += __shfl_down(wf, off);
     }
     if (lane == 0) {
       if (reward) reward[b] = -(nf + (float)s_adm);
-      if (log_prob) log_prob[b] = (lpf < -(1ll << 49)) ? -INFINITY : (float)((double)lpf / LP_FIX);
+      if constexpr (LP) {
+        if (log_prob) log_prob[b] = (lpf < -(1ll << 49)) ? -INFINITY : (float)((double)lpf / LP_FIX);
+      }
       if (entropy) entropy[b] = entropy_in[0];
       if (out.leg) {
         out.leg[2 * b + 0] = s_adm;
@@ -1653,6 +1675,7 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
 #undef s_un_hd
 #undef s_un_tl
 
+template <bool LP>
 __global__ __launch_bounds__(INSB) void k_fused_insert(int Nmax, int64_t B, int64_t N, const FusedBufs* __restrict__ fbp, PlanOut P,
                                                        const uint8_t* __restrict__ sel8, float* __restrict__ ag,
                                                        int64_t A, int64_t a_bstride, int use_cong, float t,
@@ -1661,7 +1684,7 @@ __global__ __launch_bounds__(INSB) void k_fused_insert(int Nmax, int64_t B, int6
                                                        float* __restrict__ reward, FrameOut out,
                                                        float* __restrict__ log_prob, float* __restrict__ entropy) {
   __shared__ InsLds L;
-  fused_insert_body(L, blockIdx.x, Nmax, B, N, *fbp, P, sel8, ag, A, a_bstride, use_cong, t, scratch, entropy_in, reward,
+  fused_insert_body<LP>(L, blockIdx.x, Nmax, B, N, *fbp, P, sel8, ag, A, a_bstride, use_cong, t, scratch, entropy_in, reward,
                     out, log_prob, entropy);
 }
 
@@ -1676,7 +1699,7 @@ __global__ __launch_bounds__(INSB) void k_fused_insert(int Nmax, int64_t B, int6
 // the cursor this kernel has already advanced — the same cursor it would have computed — and reduces the accumulator
 // banks itself: nothing else of that environment has been written by then). 16 384 environments: 65 us with one wave
 // each, 50 / 40 / 36 us with 2 / 4 / 8 per wave.
-template <int EPW>
+template <int EPW, bool LP>
 __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int64_t N, const FusedBufs* __restrict__ fbp, PlanOut P,
                                                         const uint8_t* __restrict__ sel8, float* __restrict__ ag,
                                                         int64_t A, int64_t a_bstride, int use_cong, float t,
@@ -1697,14 +1720,26 @@ __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int
     L.adm2[h] = 0;
     L.lo2[h] = 0x7fffffff;
   }
-  // the frame's accumulator banks: requested first, consumed (and re-armed) only once the pair is known to stay here
+  // the frame's accumulator banks: requested first, consumed (and re-armed) only once the environment is known to stay
+  // here. Bit i of a mask: the value this lane loaded in step i of the bank loop does not hold zero bits and must be
+  // re-armed (steps beyond the mask's 32 bits are re-armed unconditionally). Without LP the log-prob banks are not touched.
   long long lpf = 0;
   float nf = 0.0f, wf = 0.0f;
+  uint32_t nz_n = 0u, nz_w = 0u, nz_lp = 0u;
   if (live) {
-    for (int64_t sl_ = l; sl_ < fb.acc_slots; sl_ += LPE) {
-      lpf += fb.acc_lp[sl_ * B + b];
-      nf += fb.acc_n[sl_ * B + b];
-      wf += fb.acc_w[sl_ * B + b];
+    int it = 0;
+    for (int64_t sl_ = l; sl_ < fb.acc_slots; sl_ += LPE, ++it) {
+      const uint32_t bit = it < 32 ? (1u << it) : 0u;
+      const float n = fb.acc_n[sl_ * B + b], w = fb.acc_w[sl_ * B + b];
+      nf += n;
+      wf += w;
+      nz_n |= __float_as_uint(n) != 0u ? bit : 0u;
+      nz_w |= __float_as_uint(w) != 0u ? bit : 0u;
+      if constexpr (LP) {
+        const long long v = fb.acc_lp[sl_ * B + b];
+        lpf += v;
+        nz_lp |= v != 0 ? bit : 0u;
+      }
     }
   }
   const int32_t lo = live ? fb.cur_lo[b] : 0;
@@ -1760,10 +1795,14 @@ __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int
   if (live && l == 0) fb.cur_lo[b] = L.lo2[h] == 0x7fffffff ? (int32_t)A : L.lo2[h];
   const bool mine = live && L.cnt2[h] <= INS_CAP2;
   if (mine) {
-    for (int64_t sl_ = l; sl_ < fb.acc_slots; sl_ += LPE) {   // the banks are consumed: re-arm them
-      fb.acc_lp[sl_ * B + b] = 0;
-      fb.acc_n[sl_ * B + b] = 0.0f;
-      fb.acc_w[sl_ * B + b] = 0.0f;
+    int it = 0;
+    for (int64_t sl_ = l; sl_ < fb.acc_slots; sl_ += LPE, ++it) {   // the banks are consumed: re-arm what is not zero
+      const uint32_t bit = it < 32 ? (1u << it) : 0u;
+      if (bit == 0u || (nz_n & bit)) fb.acc_n[sl_ * B + b] = 0.0f;
+      if (bit == 0u || (nz_w & bit)) fb.acc_w[sl_ * B + b] = 0.0f;
+      if constexpr (LP) {
+        if (bit == 0u || (nz_lp & bit)) fb.acc_lp[sl_ * B + b] = 0;
+      }
     }
     // phase 2: admission straight from the list (see fused_insert_body): rank among the candidates of the same road
     float* agb = ag + b * a_bstride;
@@ -1814,13 +1853,15 @@ __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int
   __syncthreads();
   // phase 3: the accumulator banks -> reward, log-prob (LPE-lane reductions)
   for (int off = LPE / 2; off > 0; off >>= 1) {
-    lpf += __shfl_down(lpf, off, LPE);
+    if constexpr (LP) lpf += __shfl_down(lpf, off, LPE);
     nf += __shfl_down(nf, off, LPE);      // sums of small integers: exact in fp32 in any order
     wf += __shfl_down(wf, off, LPE);
   }
   if (mine && l == 0) {
     if (reward) reward[b] = -(nf + (float)L.adm2[h]);
-    if (log_prob) log_prob[b] = (lpf < -(1ll << 49)) ? -INFINITY : (float)((double)lpf / LP_FIX);
+    if constexpr (LP) {
+      if (log_prob) log_prob[b] = (lpf < -(1ll << 49)) ? -INFINITY : (float)((double)lpf / LP_FIX);
+    }
     if (entropy) entropy[b] = entropy_in[0];
     if (out.leg) {
       out.leg[2 * b + 0] = L.adm2[h];
@@ -1831,7 +1872,7 @@ __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int
     __syncthreads();
     for (int e = 0; e < EPW; ++e) {
       if (b0 + e < B && L.cnt2[e] > INS_CAP2)
-        fused_insert_body(L, b0 + e, Nmax, B, N, fb, P, sel8, ag, A, a_bstride, use_cong, t, scratch, entropy_in, reward,
+        fused_insert_body<LP>(L, b0 + e, Nmax, B, N, fb, P, sel8, ag, A, a_bstride, use_cong, t, scratch, entropy_in, reward,
                           out, log_prob, entropy);
       __syncthreads();
     }
@@ -1859,6 +1900,7 @@ struct ChoiceArgs {
   unsigned gx;             // environment tiles (x extent of the choice grid)
   unsigned choice_blocks;  // gx * node chunks
 };
+template <bool LP>
 __global__ __launch_bounds__(TILE) void k_fused_insert_choice(ChoiceArgs C, int Nmax, int64_t B, int64_t N,
                                                               const FusedBufs* __restrict__ fbp,
                                                               PlanOut P, const uint8_t* __restrict__ sel8,
@@ -1872,7 +1914,7 @@ __global__ __launch_bounds__(TILE) void k_fused_insert_choice(ChoiceArgs C, int 
   __shared__ InsLds L;
   if (blockIdx.x < (unsigned)B) {
     if (threadIdx.x >= INSB) return;   // whole waves leave before any barrier
-    fused_insert_body(L, (int64_t)blockIdx.x, Nmax, B, N, *fbp, P, sel8, ag, A, a_bstride, use_cong, t, scratch, entropy_in,
+    fused_insert_body<LP>(L, (int64_t)blockIdx.x, Nmax, B, N, *fbp, P, sel8, ag, A, a_bstride, use_cong, t, scratch, entropy_in,
                       reward, out, log_prob, entropy);
   } else {
     const unsigned cb = blockIdx.x - (unsigned)B;
@@ -2184,6 +2226,11 @@ static int check_frame_args(const tarl_plan* plan, const tarl_fused* f, int64_t 
   return TARL_OK;
 }
 
+static int launch_insert(int epw, hipStream_t s, int Nmax, int64_t B, int64_t N, const FusedBufs* fbt, PlanOut P,
+                         const uint8_t* sel_t, float* agent_features, int64_t A, int64_t a_bstride, int use_cong, float time,
+                         int32_t* ins_scratch, const float* entropy1, float* reward_t, const FrameOut& out, float* lp_t,
+                         float* ent_t);
+
 extern "C" int tarl_fused_frame(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax,
                                 const float* thresholds, const int64_t* log_probs, const float* entropy1,
                                 const float* uniform, uint64_t policy_seed, uint64_t policy_counter,
@@ -2226,10 +2273,9 @@ extern "C" int tarl_fused_frame(const tarl_plan* plan, const tarl_fused* f, int6
   rc = launch_rows(grid, threads, s, plan, f, fbd, (int)Nmax, B, agent_features, A, a_bstride, time, out);
   if (rc) return rc;
   if (timed) (void)tarl_prof_mark(s, 2);
-  hipLaunchKernelGGL(k_fused_insert, dim3((unsigned)B), dim3(INSB), 0, s, (int)Nmax, B, plan->N, fbd, P,
-                     (const uint8_t*)f->sel8, agent_features, A, a_bstride, use_cong, time, ins_scratch, entropy1, reward,
-                     out, log_prob, entropy);
-  TARL_LAUNCH_CHECK();
+  rc = launch_insert(1, s, (int)Nmax, B, plan->N, fbd, P, (const uint8_t*)f->sel8, agent_features, A, a_bstride, use_cong,
+                     time, ins_scratch, entropy1, reward, out, log_prob, entropy);
+  if (rc) return rc;
   if (timed) (void)tarl_prof_mark(s, 3);
   return TARL_OK;
 }
@@ -2314,20 +2360,37 @@ static int launch_insert(int epw, hipStream_t s, int Nmax, int64_t B, int64_t N,
                          const uint8_t* sel_t, float* agent_features, int64_t A, int64_t a_bstride, int use_cong, float time,
                          int32_t* ins_scratch, const float* entropy1, float* reward_t, const FrameOut& out, float* lp_t,
                          float* ent_t) {
-#define INS2_LAUNCH(EPW_)                                                                                                         \
-  hipLaunchKernelGGL((k_fused_insert2<EPW_>), dim3((unsigned)ceil_div(B, EPW_)), dim3(INSB), 0, s, Nmax, B, N, fbt, P, sel_t,   \
-                     agent_features, A, a_bstride, use_cong, time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t)
-  if (epw == 8) {
-    INS2_LAUNCH(8);
-  } else if (epw == 4) {
-    INS2_LAUNCH(4);
-  } else if (epw == 2) {
-    INS2_LAUNCH(2);
+  // the log-prob banks are part of the launch only where a log-prob is asked for (lp_t): a compile-time parameter, so the
+  // 64-bit sum, its shuffles and its registers are not in the other instantiation at all
+#define INS2_LAUNCH(EPW_, LP_)                                                                                                    \
+  hipLaunchKernelGGL((k_fused_insert2<EPW_, LP_>), dim3((unsigned)ceil_div(B, EPW_)), dim3(INSB), 0, s, Nmax, B, N, fbt, P,      \
+                     sel_t, agent_features, A, a_bstride, use_cong, time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t)
+#define INS1_LAUNCH(LP_)                                                                                                          \
+  hipLaunchKernelGGL((k_fused_insert<LP_>), dim3((unsigned)B), dim3(INSB), 0, s, Nmax, B, N, fbt, P, sel_t, agent_features, A,   \
+                     a_bstride, use_cong, time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t)
+  if (lp_t) {
+    if (epw == 8) {
+      INS2_LAUNCH(8, true);
+    } else if (epw == 4) {
+      INS2_LAUNCH(4, true);
+    } else if (epw == 2) {
+      INS2_LAUNCH(2, true);
+    } else {
+      INS1_LAUNCH(true);
+    }
   } else {
-    hipLaunchKernelGGL(k_fused_insert, dim3((unsigned)B), dim3(INSB), 0, s, Nmax, B, N, fbt, P, sel_t, agent_features, A,
-                       a_bstride, use_cong, time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t);
+    if (epw == 8) {
+      INS2_LAUNCH(8, false);
+    } else if (epw == 4) {
+      INS2_LAUNCH(4, false);
+    } else if (epw == 2) {
+      INS2_LAUNCH(2, false);
+    } else {
+      INS1_LAUNCH(false);
+    }
   }
 #undef INS2_LAUNCH
+#undef INS1_LAUNCH
   TARL_LAUNCH_CHECK();
   return TARL_OK;
 }
@@ -2485,14 +2548,14 @@ extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, in
       const ChoiceArgs C{plan->out_ptr, plan->out_eid, plan->group_of_node, plan->G, thresholds,
                          (const long long*)log_probs, policy_seed, policy_counter0 + (uint64_t)(t + 1), nchunk_choice(),
                          want_lp, slice(t + 1), acc_buf[cur ^ 1], grid_c.x, grid_c.x * grid_c.y};
-      hipLaunchKernelGGL(k_fused_insert_choice, dim3(C.choice_blocks + (unsigned)B), dim3(threads), 0, s, C, (int)Nmax,
-                         B, N, fbt, P, sel_t, agent_features, A, a_bstride, use_cong, time, ins_scratch, entropy1,
-                         reward_t, out, lp_t, ent_t);
-      TARL_LAUNCH_CHECK();
-    } else {
-      hipLaunchKernelGGL(k_fused_insert, dim3((unsigned)B), dim3(INSB), 0, s, (int)Nmax, B, N, fbt, P, sel_t,
+      hipLaunchKernelGGL(lp_t ? k_fused_insert_choice<true> : k_fused_insert_choice<false>,
+                         dim3(C.choice_blocks + (unsigned)B), dim3(threads), 0, s, C, (int)Nmax, B, N, fbt, P, sel_t,
                          agent_features, A, a_bstride, use_cong, time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t);
       TARL_LAUNCH_CHECK();
+    } else {
+      rc = launch_insert(1, s, (int)Nmax, B, N, fbt, P, sel_t, agent_features, A, a_bstride, use_cong, time, ins_scratch,
+                         entropy1, reward_t, out, lp_t, ent_t);
+      if (rc) return rc;
       if (t + 1 < T) {   // unmerged: the next frame's choice as its own launch
         hipLaunchKernelGGL(k_fused_choice, grid_c, dim3(threads), 0, s, plan->out_ptr, plan->out_eid,
                            plan->group_of_node, plan->G, B, N, acc_buf[cur], fb.acc_slots, thresholds,

@@ -20,11 +20,12 @@ EPISODE_END = 7 * 3600          # done = time > 7 * 3600
 
 class SimEngine:
     def __init__(self, x, edge_index, edge_attr, Nmax, agent_features, *, congestion_constant=None, num_envs=None,
-                 device="cuda", timestep=1, seed=0, plan=None, fused=True, env_base=0):
+                 device="cuda", timestep=1, seed=0, plan=None, fused=True, env_base=0, acc_slots=None):
         """``x`` (N,F) or (B,N,F); ``agent_features`` (A,9) or (B,A,9). 2-D inputs are replicated ``num_envs`` times;
         3-D inputs are used in place (views are kept, so a caller-owned tensor keeps tracking the state).
         ``env_base`` (fused path): global id of this batch's environment 0 — the noise streams of environment b are those
-        of global environment ``env_base + b`` under ``seed``, whichever batch (or rank) it is simulated in."""
+        of global environment ``env_base + b`` under ``seed``, whichever batch (or rank) it is simulated in.
+        ``acc_slots`` (fused path): accumulator banks of the packed state (None: ops.ACC_SLOTS)."""
         dev = torch.device(device)
         self.Nmax = int(Nmax)
 
@@ -62,7 +63,8 @@ class SimEngine:
         self.dtt = None
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)    # status word of the unfused kernels
         # fused fast path (csrc/fused.hip): packed hot records + agent SoA mirroring x / agents
-        self.fs = ops.FusedState(self.plan, self.B, self.A, self.device, self.Nmax, env_base=env_base) if fused else None
+        self.fs = (ops.FusedState(self.plan, self.B, self.A, self.device, self.Nmax, env_base=env_base,
+                                  acc_slots=ops.ACC_SLOTS if acc_slots is None else acc_slots) if fused else None)
         self.sample_counter = 0
         if self.fs is not None:
             self.resync()

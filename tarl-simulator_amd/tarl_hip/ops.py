@@ -1298,15 +1298,23 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, step, *, lr=1e-3, beta1=0.9, be
 
 
 # ---- fused rollout frame ----------------------------------------------------------------------------------------------
+# default number of accumulator banks of a FusedState (measured against 16, 8 and 4);
+# TARL_ACC_SLOTS (developer knob, read once): another default for a same-box A/B through bench.py
+ACC_SLOTS = int(os.environ.get("TARL_ACC_SLOTS") or 32)
+
+
 class FusedState:
     """Side buffers of the fused path (``tarl_fused`` in include/tarl_hip.h), ENV-MINOR ([node][env]): the packed dense
     words (hdp, tl, post, sel8), the event-only byte gc8, static node records, the slot-interleaved FIFO store and the
     agent SoA. They hold the state between :func:`fused_pack` and :func:`fused_export`."""
 
-    def __init__(self, plan: Plan, B: int, A: int, device, Nmax: int = 15, env_base: int = 0):
+    def __init__(self, plan: Plan, B: int, A: int, device, Nmax: int = 15, env_base: int = 0, acc_slots: int = ACC_SLOTS):
         """``env_base``: global id of environment 0 of this batch — the device noise streams are indexed by
         ``env_base + b`` (include/tarl_hip.h: tarl_fused.env_base), so a shard of a larger batch reproduces the larger
-        batch's trajectories."""
+        batch's trajectories. ``acc_slots``: accumulator banks per environment (1 .. 4096); the banks hold exact sums, so
+        the number changes the atomics' spread and the insert launch's traffic, never a result."""
+        if isinstance(acc_slots, bool) or not isinstance(acc_slots, int) or not 1 <= acc_slots <= 4096:
+            raise ValueError(f"acc_slots must be an integer in 1 .. 4096 (got {acc_slots!r})")
         L = _lib.load()
         N, E = plan.num_nodes, plan.num_edges
         if Nmax > 127 or plan.max_out > 126:
@@ -1327,7 +1335,7 @@ class FusedState:
         self.node_rec = torch.zeros((N, 36), **i32)          # static records (fused_common.h: NodeRec / InRec)
         self.in_rec = torch.zeros((E + 4, 5), **i32)
         self.out_pad = torch.zeros(E + 4, **i32)
-        self.acc_slots = 32      # accumulator banks (spread the per-environment atomics of the N/chunk workgroups)
+        self.acc_slots = acc_slots      # accumulator banks (spread the per-environment atomics of the N/chunk workgroups)
         self.acc_lp = torch.zeros((self.acc_slots, B), dtype=torch.int64, device=device)
         self.acc_n = torch.zeros((self.acc_slots, B), **f32)
         self.acc_w = torch.zeros((self.acc_slots, B), **f32)

@@ -12,7 +12,9 @@ python3 - $T $SRC <<'PY'
 import re, sys, glob
 T = sys.argv[1]
 want = {"_Z12k_fused_rowsILi4ELb1ELb0ELb1EE": "k_fused_rows<4,SIB,rollout,O32>", "_Z17k_fused_directionILi4ELb1ELb1ELb1EE": "k_fused_direction<4,SIB,CNT,O32>",
-        "_Z15k_fused_insert2ILi8EE": "k_fused_insert2<8>", "_Z15k_fused_insert2ILi2EE": "k_fused_insert2<2>", "_Z14k_fused_insertill": "k_fused_insert"}
+        "_Z15k_fused_insert2ILi8ELb0EE": "k_fused_insert2<8,noLP>", "_Z15k_fused_insert2ILi8ELb1EE": "k_fused_insert2<8,LP>",
+        "_Z15k_fused_insert2ILi2ELb0EE": "k_fused_insert2<2,noLP>", "_Z14k_fused_insertILb0EE": "k_fused_insert<noLP>",
+        "_Z14k_fused_insertILb1EE": "k_fused_insert<LP>"}
 txt = open(T + "/remarks.txt").read()
 blocks = re.split(r"Function Name: ", txt)[1:]
 if sys.argv[2] != "fused.hip":
