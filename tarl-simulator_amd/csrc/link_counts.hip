@@ -6,7 +6,7 @@
 // one agent withdrawn), each stamped with the clock at which the step STARTED, are concatenated, binned by
 // time // 3600 and summed. So count[b][h][n] = sum over the frames t with floor(clock_t / bin_seconds) == h of
 // popped_t[b][n] + withdrawn_t[b][n]; a road popped and withdrawn from in one frame counts 2.
-#include "tarl_common.h"
+#include "eval_bins.h"
 
 #define LC_BLOCK 256
 #define LC_LANES 4   // (b, n) elements per thread == partial sums packed into one 32-bit register, 8 bits each
@@ -19,8 +19,7 @@
 // thread that owns the last, partial group always reads bytes, each bounded by M. Only bit 0 of a mask byte is read, so the
 // four 8-bit partial sums grow by at most 2 per frame and TARL_LINK_COUNTS_MAX_FRAMES = 127 frames keep every one below 256
 // whatever the bytes hold. The partial sums stay in the register for a run of frames in one bin and are added to
-// counts[b][h][n] when the bin changes (and after the last frame). The bins of the first and the last frame are checked on
-// the host, and the clock does not run backwards (timestep >= 0), so every h in between is in [0, H).
+// counts[b][h][n] when the bin changes (and after the last frame); every such h is in [0, H) (eval_bins.h).
 __device__ __forceinline__ uint32_t lc_load4(const uint8_t* __restrict__ p, int64_t e0, int n_own, bool word) {
   if (word) return *reinterpret_cast<const uint32_t*>(p + e0);
   uint32_t w = 0;
@@ -38,16 +37,8 @@ __global__ __launch_bounds__(LC_BLOCK) void k_link_counts_accumulate(const uint8
   const int64_t e0 = ((int64_t)blockIdx.x * LC_BLOCK + threadIdx.x) * LC_LANES;
   if (e0 >= M) return;
   const int n_own = (int)((M - e0) < LC_LANES ? (M - e0) : LC_LANES);
-  int64_t f = 0;
-  while (f < F) {
-    // the run [f, f1) of frames in this frame's bin: two divisions per run, uniform over the launch (scalar arithmetic)
-    const int64_t bin = (t0 + f * timestep) / bin_seconds, h = bin - first_bin;
-    int64_t f1 = F;
-    if (timestep > 0) {      // first frame at or past the bin's upper edge: > f, because frame f lies below that edge
-      const int64_t edge = (bin + 1) * bin_seconds - t0;
-      f1 = (edge + timestep - 1) / timestep;
-      f1 = f1 < F ? f1 : F;
-    }
+  for (int64_t f = 0; f < F;) {
+    int64_t h, f1 = bin_run(t0, timestep, bin_seconds, first_bin, f, F, h);      // the run [f, f1) of frames in bin h
     uint32_t acc = 0;
 #pragma unroll 4
     for (; f < f1; ++f) {
@@ -77,11 +68,7 @@ extern "C" int tarl_link_counts_accumulate(const uint8_t* popped, const uint8_t*
   TARL_REQUIRE(F >= 1 && F <= TARL_LINK_COUNTS_MAX_FRAMES, "F must be in [1, TARL_LINK_COUNTS_MAX_FRAMES]");
   const int64_t lim = (int64_t)1 << 40;
   TARL_REQUIRE(B >= 1 && N >= 1 && H >= 1 && B < lim && N < lim && H < lim && B * N < lim && B * N * H < lim, "bad sizes");
-  TARL_REQUIRE(t0 >= 0 && t0 < lim && timestep >= 0 && timestep < lim && first_bin >= 0, "bad clock");
-  TARL_REQUIRE(bin_seconds >= 1 && bin_seconds < lim, "bin_seconds must be positive");
-  const int64_t h_first = t0 / bin_seconds - first_bin, h_last = (t0 + (F - 1) * timestep) / bin_seconds - first_bin;
-  TARL_REQUIRE(h_first >= 0, "bin out of range: the first frame falls below first_bin");
-  TARL_REQUIRE(h_last < H, "bin out of range: the last frame falls in a bin >= H");
+  TARL_REQUIRE_BINS(t0, timestep, bin_seconds, first_bin, F, H);
   const int64_t M = B * N;
   hipLaunchKernelGGL(k_link_counts_accumulate, dim3((unsigned)ceil_div(ceil_div(M, LC_LANES), LC_BLOCK)), dim3(LC_BLOCK), 0,
                      (hipStream_t)stream, popped, withdrawn, F, M, N, H, t0, timestep, bin_seconds, first_bin, counts);

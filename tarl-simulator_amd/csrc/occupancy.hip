@@ -9,7 +9,7 @@
 //   veh[b][h][n]  = sum over t in bin h of c_t[b][n]            (vehicle-frames)
 //   full[b][h][n] = #{t in bin h : c_t[b][n] >= thr[n]}         (frames in which the road admits nobody)
 //   peak[b][0][n] = max over t of c_t[b][n]
-#include "tarl_common.h"
+#include "eval_bins.h"
 
 #define OC_TILE 64              // environments x roads of one workgroup
 #define OC_PAD (OC_TILE + 1)    // row stride of the LDS tile, in int32
@@ -39,8 +39,6 @@ __device__ __forceinline__ int32_t oc_count(float v) { return v > 0.0f ? (v >= 2
 //   the compiler pairs two reads as ds_read2_b32, the LDS serves them as two such ds_read_b32 accesses.
 // Tiles at the K and N edges are partial: a load outside reads the nearest element inside instead (in bounds, and the
 // frame loop stays free of branches), the LDS tile is always written in full, and the stores are predicated per element.
-// The bins of the first and the last frame are checked on the host and the clock does not run backwards, so every h in
-// between is in [0, H).
 //
 // oc_flush: the thread's 16 partial results through the tile into dst[i * k_stride], i < k_rows: this lane's road of the
 // environments k0 + w + 4 i that exist (k_rows is uniform over the wave). PEAK: max-merge instead of add.
@@ -88,16 +86,8 @@ __global__ __launch_bounds__(OC_TILE* OC_WAVES) void k_occupancy_accumulate(cons
   const int64_t k_left = K - k0 - w;
   const int k_rows = k_left <= 0 ? 0 : (int)(k_left >= OC_TILE ? OC_ROWS : (k_left + OC_WAVES - 1) / OC_WAVES);
   const int64_t e0 = (k0 + w) * H * N + n0 + l;      // element [k0 + w][0][n0 + l] of veh and full
-  int64_t f = 0;
-  while (f < F) {
-    // the run [f, f1) of frames in this frame's bin: two divisions per run, uniform over the launch (scalar arithmetic)
-    const int64_t bin = (t0 + f * timestep) / bin_seconds, h = bin - first_bin;
-    int64_t f1 = F;
-    if (timestep > 0) {      // first frame at or past the bin's upper edge: > f, because frame f lies below that edge
-      const int64_t edge = (bin + 1) * bin_seconds - t0;
-      f1 = (edge + timestep - 1) / timestep;
-      f1 = f1 < F ? f1 : F;
-    }
+  for (int64_t f = 0; f < F;) {
+    int64_t h, f1 = bin_run(t0, timestep, bin_seconds, first_bin, f, F, h);      // the run [f, f1) of frames in bin h
     int32_t av[OC_ROWS], af[OC_ROWS];
 #pragma unroll
     for (int i = 0; i < OC_ROWS; ++i) av[i] = af[i] = 0;
@@ -129,11 +119,7 @@ extern "C" int tarl_occupancy_accumulate(const float* ring, const int32_t* thr, 
   TARL_REQUIRE(K >= 1 && N >= 1 && H >= 1 && K < lim && N < lim && H < lim && K * N < lim && K * N * H < lim &&
                    K * N * F < lim,
                "bad sizes");
-  TARL_REQUIRE(t0 >= 0 && t0 < lim && timestep >= 0 && timestep < lim && first_bin >= 0, "bad clock");
-  TARL_REQUIRE(bin_seconds >= 1 && bin_seconds < lim, "bin_seconds must be positive");
-  const int64_t h_first = t0 / bin_seconds - first_bin, h_last = (t0 + (F - 1) * timestep) / bin_seconds - first_bin;
-  TARL_REQUIRE(h_first >= 0, "bin out of range: the first frame falls below first_bin");
-  TARL_REQUIRE(h_last < H, "bin out of range: the last frame falls in a bin >= H");
+  TARL_REQUIRE_BINS(t0, timestep, bin_seconds, first_bin, F, H);
   const int64_t k_tiles = ceil_div(K, OC_TILE), tiles = k_tiles * ceil_div(N, OC_TILE);
   TARL_REQUIRE(tiles < ((int64_t)1 << 31), "bad sizes: too many tiles for one launch");
   hipLaunchKernelGGL(k_occupancy_accumulate, dim3((unsigned)tiles), dim3(OC_TILE * OC_WAVES), 0, (hipStream_t)stream, ring,

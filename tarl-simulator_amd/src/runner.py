@@ -346,57 +346,41 @@ class Runner:
                       trip_free_flow=g.x[:, h.FREE_FLOW_TIME_TRAVEL][g.edge_index[1]])
         return kw
 
-    def _trips_output(self, res, baseline, path, path_by_departure):
-        """--eval-trips: the ``Trips`` block, one CSV row per agent at ``path`` and one per departure bin at
-        ``path_by_departure`` -> the summary for the JSON file (never the A-row tables)."""
+    @staticmethod
+    def _report_output(title, report, lines_fn, summary_fn, tables):
+        """One report of the vectorised evaluation: its ``title`` block and, where it is available, one CSV file per
+        ``(path, columns_key, rows_key)`` of ``tables`` -> the summary for the JSON file (never a table or a tensor)."""
         import csv
-        from tarl_hip.evaluator import trip_lines, trip_report, trip_summary
-        rep = trip_report(res, baseline=baseline)
-        print("\n=== Trips ===")
-        for line in trip_lines(rep):
+        print(f"\n=== {title} ===")
+        for line in lines_fn(report):
             print(line)
-        if rep["available"]:
-            for where, cols, rows in ((path, rep["columns"], rep["rows"]),
-                                      (path_by_departure, rep["by_departure_columns"], rep["by_departure"])):
-                with open(where, "w", newline="") as f:
-                    w = csv.DictWriter(f, fieldnames=cols)
+        if report["available"]:
+            for path, columns, rows in tables:
+                with open(path, "w", newline="") as f:
+                    w = csv.DictWriter(f, fieldnames=report[columns])
                     w.writeheader()
-                    w.writerows(rows)
-        return trip_summary(rep)
+                    w.writerows(report[rows])
+        return summary_fn(report)
 
-    def _occupancy_output(self, res, baseline, path):
-        """--eval-occupancy: the ``Occupancy`` block, one CSV row per road at ``path`` (capacity and threshold; vehicle-seconds
-        of the episode: mean, sd, se, interval, min, max; mean occupancy per bin; v/c; peak; frames at capacity; with a
-        baseline the paired differences) -> the summary for the JSON file (never the K x H x N tensors)."""
-        import csv
-        from tarl_hip.evaluator import occupancy_lines, occupancy_report, occupancy_summary
-        rep = occupancy_report(res, baseline=baseline)
-        print("\n=== Occupancy ===")
-        for line in occupancy_lines(rep):
-            print(line)
-        if rep["available"]:
-            with open(path, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=rep["columns"])
-                w.writeheader()
-                w.writerows(rep["rows"])
-        return occupancy_summary(rep)
-
-    def _link_counts_output(self, res, baseline, path):
-        """--eval-link-counts: the ``Link counts`` block, one CSV row per road at ``path`` (episode total: mean, sd, se,
-        interval, min, max; per-bin means; per expected-flow vector that Runner.eval computed its flow, difference and GEH;
-        with a baseline its mean and the paired difference) -> the summary for the JSON file (never the K x H x N tensor)."""
-        import csv
-        from tarl_hip.evaluator import link_count_lines, link_count_report, link_count_summary
-        rep = link_count_report(res, expected=getattr(self, "_link_expected", {}), baseline=baseline)
-        print("\n=== Link counts ===")
-        for line in link_count_lines(rep):
-            print(line)
-        if rep["available"]:
-            with open(path, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=rep["columns"])
-                w.writeheader()
-                w.writerows(rep["rows"])
-        return link_count_summary(rep)
+    def _reports_output(self, doc, res, baseline, out_dir, prefix):
+        """--eval-link-counts, --eval-occupancy, --eval-trips: each report of ``res`` (against ``baseline``, the evaluation of
+        the same environments, where there is one) printed, written to ``<prefix>_<report>.csv`` (one row per road; the
+        link counts with the expected flows that Runner.eval computed; the trips one row per agent, and per departure bin in
+        ``<prefix>_trips_by_departure.csv``) and summarised in ``doc``."""
+        from tarl_hip import evaluator as E
+        a = self.args
+        if a.eval_link_counts:
+            rep = E.link_count_report(res, expected=getattr(self, "_link_expected", {}), baseline=baseline)
+            doc["link_counts"] = self._report_output("Link counts", rep, E.link_count_lines, E.link_count_summary,
+                                                     [(out_dir / f"{prefix}_link_counts.csv", "columns", "rows")])
+        if a.eval_occupancy:
+            doc["occupancy"] = self._report_output("Occupancy", E.occupancy_report(res, baseline=baseline), E.occupancy_lines,
+                                                   E.occupancy_summary, [(out_dir / f"{prefix}_occupancy.csv", "columns", "rows")])
+        if a.eval_trips:
+            doc["trips"] = self._report_output(
+                "Trips", E.trip_report(res, baseline=baseline), E.trip_lines, E.trip_summary,
+                [(out_dir / f"{prefix}_trips.csv", "columns", "rows"),
+                 (out_dir / f"{prefix}_trips_by_departure.csv", "by_departure_columns", "by_departure")])
 
     def _vectorised_dijkstra(self, frames, out_dir):
         """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra":
@@ -411,13 +395,7 @@ class Runner:
         self._print_block(f"Vectorised evaluation ({res.envs} environments, dijkstra)", res)
         out_dir.mkdir(parents=True, exist_ok=True)
         doc = {"mode": res.to_dict()}
-        if self.args.eval_link_counts:
-            doc["link_counts"] = self._link_counts_output(res, None, out_dir / "dijkstra_link_counts.csv")
-        if self.args.eval_occupancy:
-            doc["occupancy"] = self._occupancy_output(res, None, out_dir / "dijkstra_occupancy.csv")
-        if self.args.eval_trips:
-            doc["trips"] = self._trips_output(res, None, out_dir / "dijkstra_trips.csv",
-                                              out_dir / "dijkstra_trips_by_departure.csv")
+        self._reports_output(doc, res, None, out_dir, "dijkstra")
         with open(out_dir / "dijkstra_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "dijkstra_envs.csv", "w", newline="") as f:
@@ -476,14 +454,7 @@ class Runner:
             for r in rows:
                 r.update({f"baseline_{k}": by_env[r["env"]][k] for k in PER_ENV_KEYS} if r["env"] in by_env else {})
         out_dir.mkdir(parents=True, exist_ok=True)
-        if a.eval_link_counts:      # of the MODE run (and against the baseline of the same environments, where there is one)
-            doc["link_counts"] = self._link_counts_output(results["mode"], results.get("baseline"),
-                                                          out_dir / "eval_link_counts.csv")
-        if a.eval_occupancy:
-            doc["occupancy"] = self._occupancy_output(results["mode"], results.get("baseline"), out_dir / "eval_occupancy.csv")
-        if a.eval_trips:
-            doc["trips"] = self._trips_output(results["mode"], results.get("baseline"), out_dir / "eval_trips.csv",
-                                              out_dir / "eval_trips_by_departure.csv")
+        self._reports_output(doc, results["mode"], results.get("baseline"), out_dir, "eval")      # of the MODE run
         with open(out_dir / "eval_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "eval_envs.csv", "w", newline="") as f:

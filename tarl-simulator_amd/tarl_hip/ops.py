@@ -706,6 +706,24 @@ def _meta(t, dtype, shape, name):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _bin_schedule(frames, Fcap, Fmax, t0, timestep, bin_seconds, first_bin, H, fmax_name=""):
+    """The frame count, clock and bin arguments of an accumulate call, checked -> ``(F, t0, timestep, bin_seconds, first_bin)``:
+    ``frames`` defaults to the ring's ``Fcap`` and is at most the kernel's ``Fmax``, ``first_bin`` to the bin of ``t0``."""
+    F = Fcap if frames is None else int(frames)
+    if not 1 <= F <= Fcap:
+        raise ValueError(f"frames must be in [1, {Fcap}], got {F}")
+    if F > Fmax:
+        raise ValueError(f"one call takes at most {Fmax} frames{fmax_name}, got {F}")
+    t0, timestep, bin_seconds = int(t0), int(timestep), int(bin_seconds)
+    if t0 < 0 or timestep < 0 or bin_seconds < 1:
+        raise ValueError("t0 and timestep must be >= 0 and bin_seconds >= 1")
+    first_bin = t0 // bin_seconds if first_bin is None else int(first_bin)
+    lo, hi = t0 // bin_seconds - first_bin, (t0 + (F - 1) * timestep) // bin_seconds - first_bin
+    if first_bin < 0 or lo < 0 or hi >= H:
+        raise ValueError(f"bin out of range: the frames fall in bins {lo} .. {hi} of the {H} stored (first_bin {first_bin})")
+    return F, t0, timestep, bin_seconds, first_bin
+
+
 def link_counts_accumulate(popped, withdrawn, counts, *, t0, timestep=1, bin_seconds=3600, first_bin=None, frames=None):
     """``counts`` int32 (B, H, N) += the per-bin sums of ``popped`` + ``withdrawn`` uint8 (F, B, N), the per-frame masks of
     ``SimEngine.frame_fused`` for ``frames`` (default: all F) consecutive frames whose first started at clock ``t0``
@@ -721,18 +739,8 @@ def link_counts_accumulate(popped, withdrawn, counts, *, t0, timestep=1, bin_sec
         raise ValueError(f"counts must be (B, H, N), got {tuple(counts.shape)}")
     H = counts.size(1)
     _meta(counts, torch.int32, (B, H, N), "counts")
-    F = Fcap if frames is None else int(frames)
-    if not 1 <= F <= Fcap:
-        raise ValueError(f"frames must be in [1, {Fcap}], got {F}")
-    if F > LINK_COUNTS_MAX_FRAMES:
-        raise ValueError(f"one call takes at most {LINK_COUNTS_MAX_FRAMES} frames (TARL_LINK_COUNTS_MAX_FRAMES), got {F}")
-    t0, timestep, bin_seconds = int(t0), int(timestep), int(bin_seconds)
-    if t0 < 0 or timestep < 0 or bin_seconds < 1:
-        raise ValueError("t0 and timestep must be >= 0 and bin_seconds >= 1")
-    first_bin = t0 // bin_seconds if first_bin is None else int(first_bin)
-    lo, hi = t0 // bin_seconds - first_bin, (t0 + (F - 1) * timestep) // bin_seconds - first_bin
-    if first_bin < 0 or lo < 0 or hi >= H:
-        raise ValueError(f"bin out of range: the frames fall in bins {lo} .. {hi} of the {H} stored (first_bin {first_bin})")
+    F, t0, timestep, bin_seconds, first_bin = _bin_schedule(frames, Fcap, LINK_COUNTS_MAX_FRAMES, t0, timestep, bin_seconds,
+                                                            first_bin, H, " (TARL_LINK_COUNTS_MAX_FRAMES)")
     for t, dt, name in ((popped, torch.uint8, "popped"), (withdrawn, torch.uint8, "withdrawn"), (counts, torch.int32, "counts")):
         _check_dev(t, dt, name)
     _lib.check(_lib.load().tarl_link_counts_accumulate(popped.data_ptr(), withdrawn.data_ptr(), F, B, N, t0, timestep,
@@ -794,18 +802,8 @@ def occupancy_accumulate(ring, thr, veh, full, peak, *, t0, timestep=1, bin_seco
     _meta(peak, torch.int32, (K, 1, N), "peak")
     if K < 1 or N < 1 or H < 1:
         raise ValueError("ring and the accumulators must not be empty")
-    F = Fcap if frames is None else int(frames)
-    if not 1 <= F <= Fcap:
-        raise ValueError(f"frames must be in [1, {Fcap}], got {F}")
-    if F > OCCUPANCY_MAX_FRAMES:
-        raise ValueError(f"one call takes at most {OCCUPANCY_MAX_FRAMES} frames, got {F}")
-    t0, timestep, bin_seconds = int(t0), int(timestep), int(bin_seconds)
-    if t0 < 0 or timestep < 0 or bin_seconds < 1:
-        raise ValueError("t0 and timestep must be >= 0 and bin_seconds >= 1")
-    first_bin = t0 // bin_seconds if first_bin is None else int(first_bin)
-    lo, hi = t0 // bin_seconds - first_bin, (t0 + (F - 1) * timestep) // bin_seconds - first_bin
-    if first_bin < 0 or lo < 0 or hi >= H:
-        raise ValueError(f"bin out of range: the frames fall in bins {lo} .. {hi} of the {H} stored (first_bin {first_bin})")
+    F, t0, timestep, bin_seconds, first_bin = _bin_schedule(frames, Fcap, OCCUPANCY_MAX_FRAMES, t0, timestep, bin_seconds,
+                                                            first_bin, H)
     for t, dt, name in ((ring, torch.float32, "ring"), (thr, torch.int32, "thr"), (veh, torch.int32, "veh"),
                         (full, torch.int32, "full"), (peak, torch.int32, "peak")):
         _check_dev(t, dt, name)

@@ -73,8 +73,9 @@ SHAPES = ((1, 1, 1), (5, 6, 7), (3, 21, 64), (2, 257, 64))      # (B, N, F): B N
 def crafted_cases():
     """Every accumulate case of the GPU suite. Per shape: no bin edge inside the block; the edge at its first frame; the
     edge at its last frame; several edges inside with bins skipped (timestep 25, bins of 10 s). Then two consecutive calls
-    into the same counts, the second continuing the first one's last bin (64 + 30 frames, an edge inside the first), and
-    all-ones masks at the declared maximum F, twice into the same bin: exactly 2 F, then 4 F = 508 > 255."""
+    into the same counts, the second continuing the first one's last bin (64 + 30 frames, an edge inside the first),
+    all-ones masks at the declared maximum F, twice into the same bin: exactly 2 F, then 4 F = 508 > 255, and a clock that
+    stands still (timestep 0): every frame of the call falls in one bin."""
     cases = []
     for i, (B, N, F) in enumerate(SHAPES):
         p, w = _masks(F, B, N, seed=100 + i)
@@ -86,6 +87,8 @@ def crafted_cases():
     cases.append(_case("two-calls", p, w, 7200 - 40, 1, 3600, 64))
     ones = np.ones((2 * MAX_FRAMES, 1, 5), dtype=np.uint8)
     cases.append(_case("all-ones-max-F-twice", ones, ones, 36000, 1, 3600, MAX_FRAMES))
+    p, w = _masks(7, 5, 6, seed=201)
+    cases.append(_case("5x6x7-timestep-0", p, w, 4000, 0, 3600, 7))
     return cases
 
 

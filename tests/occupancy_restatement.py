@@ -113,7 +113,8 @@ def crafted_cases():
     """Every accumulate case of the GPU suite. Per shape: no bin edge inside the call; the edge at its first frame; the edge at
     its last frame; several edges inside with bins skipped (timestep 25, bins of 10 s). Then consecutive calls into the same
     accumulators: 64 + 30 frames with an edge inside the first call and the second continuing its last bin (the last block
-    partial), and 9 frames in blocks of 4 on a shape with partial tiles on both axes."""
+    partial), 9 frames in blocks of 4 on a shape with partial tiles on both axes, and a clock that stands still (timestep 0):
+    every frame of the call falls in one bin."""
     cases = []
     for i, (K, N, F) in enumerate(SHAPES):
         ring, thr, _ = _ring(F, N, K, seed=300 + i)
@@ -123,6 +124,8 @@ def crafted_cases():
     cases.append(_case("two-calls", ring, thr, 7200 - 40, 1, 3600, 64))
     ring, thr, _ = _ring(9, 63, 65, seed=401)
     cases.append(_case("three-calls", ring, thr, 7200 - 5, 1, 3600, 4))
+    ring, thr, _ = _ring(7, 6, 5, seed=402)
+    cases.append(_case("5x6x7-timestep-0", ring, thr, 4000, 0, 3600, 7))
     return cases
 
 

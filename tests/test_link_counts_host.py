@@ -53,7 +53,7 @@ def test_stats_restatement_and_geh_by_hand():
 
 def test_crafted_cases_cover_what_the_issue_lists():
     cases = {c["name"]: c for c in R.crafted_cases()}
-    assert len(cases) == 4 * len(R.SHAPES) + 2
+    assert len(cases) == 4 * len(R.SHAPES) + 3
     for B, N, F in R.SHAPES:
         for kind in ("no-edge", "edge-first", "edge-last", "skipping"):
             c = cases[f"{B}x{N}x{F}-{kind}"]
@@ -74,6 +74,11 @@ def test_crafted_cases_cover_what_the_issue_lists():
     assert [c["popped"].shape[0] for c in two["calls"]] == [64, 30] and two["calls"][1]["partial"]
     last_of_first = (two["calls"][0]["t0"] + 63) // 3600
     assert two["calls"][0]["t0"] // 3600 == last_of_first - 1 and two["calls"][1]["t0"] // 3600 == last_of_first
+    still = cases["5x6x7-timestep-0"]                                      # the clock stands still: one bin holds every frame
+    assert still["timestep"] == 0 and still["calls"][0]["popped"].shape == (7, 5, 6) and still["H"] == 3
+    got = R.run_case(still)
+    assert not got[:, 0].any() and not got[:, 2].any()
+    assert np.array_equal(got[:, 1], (still["calls"][0]["popped"].astype(np.int32) + still["calls"][0]["withdrawn"]).sum(axis=0))
     ones = cases["all-ones-max-F-twice"]
     assert [c["popped"].shape for c in ones["calls"]] == [(R.MAX_FRAMES, 1, 5)] * 2
     got = R.run_case(ones)
@@ -188,9 +193,8 @@ def test_report_for_one_environment_and_for_a_run_without_counts():
 def test_paired_report_against_numpy(K, monkeypatch):
     """The paired numbers come from the two-input statistics kernel; here its numpy restatement stands in for the launch, so
     that the host arithmetic behind it is checked without a GPU."""
-    from tarl_hip import evaluator as E
-    monkeypatch.setattr(E, "_paired_link_moments",
-                        lambda a, b: E.link_moments(R.stats(a.link_counts, b.link_counts), a.envs))
+    from tarl_hip import eval_reports, evaluator as E
+    monkeypatch.setattr(eval_reports, "_paired_moments", lambda a, b, K: E.link_moments(R.stats(a, b), K))
     res, a = _result(K, seed=1)
     base, b = _result(K, seed=2, head="dijkstra")
     rep = E.link_count_report(res, baseline=base)

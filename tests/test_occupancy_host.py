@@ -69,6 +69,11 @@ def test_crafted_cases_cover_what_the_issue_lists():
     c = by["130x70x5-no-edge"]
     n = int(np.argmax(c["thr"] > 1))
     assert {0, int(c["thr"][n]) - 1, int(c["thr"][n]), int(c["thr"][n]) + 1, 127} <= set(c["ring"][:, n, :].ravel().tolist())
+    c = by["5x6x7-timestep-0"]                                             # the clock stands still: one bin holds every frame
+    assert c["timestep"] == 0 and c["ring"].shape == (7, 6, 5) and c["H"] == 3 and set(bins(c)) == {1}
+    veh, full, peak = R.run_case(c)
+    counts = R.to_count(c["ring"])
+    assert np.array_equal(veh[:, 1], counts.sum(axis=0).T) and np.array_equal(peak[:, 0], counts.max(axis=0).T)
     assert len(by["two-calls"]["calls"]) == 2 and by["two-calls"]["calls"][1]["partial"]
     assert [x["partial"] for x in by["three-calls"]["calls"]] == [False, False, True]
 
@@ -215,9 +220,8 @@ def test_report_of_a_run_with_no_vehicle_and_of_runs_without_occupancy():
 def test_paired_report_against_numpy(K, monkeypatch):
     """The paired numbers come from the two-input statistics kernel; here its numpy restatement stands in for the launch, so
     that the host arithmetic behind it is checked without a GPU."""
-    from tarl_hip import evaluator as E
-    monkeypatch.setattr(E, "_paired_occupancy_moments",
-                        lambda a, b, key: E.link_moments(R.stats(a.occupancy[key], b.occupancy[key]), a.envs))
+    from tarl_hip import eval_reports, evaluator as E
+    monkeypatch.setattr(eval_reports, "_paired_moments", lambda a, b, K: E.link_moments(R.stats(a, b), K))
     res, a = _result(K, seed=1)
     base, b = _result(K, seed=2, head="dijkstra")
     rep = E.occupancy_report(res, baseline=base)

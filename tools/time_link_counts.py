@@ -55,8 +55,8 @@ def alternating(evs, T, reps):
 def time_kernels(ev, reps=20):
     K, N, F = ev.eng.B, ev.eng.N, ev.link_block
     acc = torch.zeros((K, 1, N), dtype=torch.int32, device="cuda")
-    us = event_us(lambda: ops.link_counts_accumulate(ev.link_popped, ev.link_withdrawn, acc, t0=21540, timestep=1,
-                                                     bin_seconds=3600), reps)
+    us = event_us(lambda: ops.link_counts_accumulate(ev.link_popped, ev.link_withdrawn, acc, t0=21600, timestep=1,
+                                                     bin_seconds=3600), reps)      # (a bin's first frame: F <= 127 stay inside it)
     nbytes = 2 * F * K * N + 8 * K * N
     bound = nbytes / (COPY_TBPS * 1e12) * 1e6
     print(f"  tarl_link_counts_accumulate, K = {K}, F = {F}: {us:8.1f} us   byte count {nbytes / 1e6:.1f} MB (2 F K N mask bytes "
