@@ -605,6 +605,44 @@ def gen_routing():
     save("routing", **rec)
 
 
+def gen_routing_irregular():
+    """Next-hop tables of real networkx on the two irregular road graphs of tests/irregular_graphs.py (hubs of degree 9 /
+    126, dead ends, roads nobody can enter, an edge list in no order), built the way DijkstraAgents.choice builds them
+    (src/agents/base.py:551-570: to_networkx with the weights as ``edge_attr``, ``nx.all_pairs_dijkstra_path``, path[1] or
+    the node itself, -1 where there is no path). Two weight sets: ``ff`` = the free-flow time of the target road, ``r5`` =
+    ``ff`` rounded to multiples of 5 s (three distinct values: heavily tied away from any lattice). MIXED carries both,
+    HUB126 ``r5`` only."""
+    import networkx as nx
+    from torch_geometric.utils import to_networkx
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import irregular_graphs as ig
+    rec = {}
+    for name, sets in (("MIXED", ("ff", "r5")), ("HUB126", ("r5",))):
+        net = ig.graph(name)
+        N, ei = net.num_roads, net.edge_index
+        ff = net.x[:, 3 * net.Nmax + 2][ei[1]].contiguous()
+        weights = dict(ff=ff, r5=torch.round(ff / 5) * 5)
+        rec[f"{name}__edge_index"] = ei
+        for tag in sets:
+            w = weights[tag]
+            g = to_networkx(Data(x=net.x, edge_index=ei, edge_attr=w, num_nodes=N), edge_attrs=["edge_attr"],
+                            to_undirected=False)
+            assert g.number_of_edges() == ei.size(1)           # no parallel dual edges: DiGraph keeps every one
+            paths = dict(nx.all_pairs_dijkstra_path(g, weight="edge_attr"))
+            nh = torch.full((N, N), -1, dtype=torch.int64)
+            for src, dst_dict in paths.items():
+                for dst, path in dst_dict.items():
+                    if len(path) >= 2:
+                        nh[src, dst] = path[1]
+                    elif len(path) == 1:
+                        nh[src, dst] = src
+            rec[f"{name}__w_{tag}"] = w
+            rec[f"{name}__next_hop_{tag}"] = nh.to(torch.int16)
+            print(f"  routing_irregular {name}/{tag}: networkx {nx.__version__}, {int((nh < 0).sum())} unreachable pairs",
+                  file=sys.stderr)
+    save("routing_irregular", **rec)
+
+
 if __name__ == "__main__":
     assert os.path.isdir(REF), f"reference tree not found at {REF} (this script only runs in the build container)"
     gen_core_steps()
@@ -618,3 +656,4 @@ if __name__ == "__main__":
     gen_value_mpnn()
     gen_builders()
     gen_routing()
+    gen_routing_irregular()

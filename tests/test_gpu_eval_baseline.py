@@ -312,6 +312,55 @@ def _load_population(net):
                                          t1=EPISODE_START + LOAD["span"])
 
 
+def _assert_replayed_by_the_oracle(net, pop, K, T, succ):
+    """``VecEvaluator(head="dijkstra")`` on K environments for T frames against baseline_restatement.replay, environment by
+    environment: SELECTED_ROAD on every node at every frame (``succ`` (N, max out-degree): every node's successors in the
+    plan's out-list order, padded with a value no road has; a raw byte: the oracle's value is no successor of the node),
+    every reward, the final state and agent table, and the EvalResult against eval_restatement. -> (res, the replays)."""
+    import baseline_restatement as BR
+    import eval_restatement as R
+    from tarl_hip import ops
+    from tarl_hip.engine import EPISODE_START
+    N, Nmax, ei = net.num_roads, net.Nmax, net.edge_index
+    ev = _baseline_evaluator(net, pop, K, keep_actions=True)
+    eng = ev.eng
+    noise0 = eng.noise_counter + 1
+    res = ev.run(T)
+    assert not res.domain_exit and res.frames_run == T and res.head == "dijkstra" and res.deterministic
+    dests = {int(d) for d in pop[:, 1].tolist()}
+    assert res.settings["refresh_rate"] == 10 and res.settings["destinations"] == len(dests)
+    rw = ev.reward[:T].cpu()
+    actions = ev.actions[:T].cpu().long()
+    ff = net.x[:, 3 * Nmax + 2][ei[0]]
+    succ = succ.float()
+    runs = []
+    for b in range(K):
+        r = BR.replay(net, pop, T, 10, lambda t: ops.noise_export(eng.plan, "gumbel", eng.seed, noise0 + t, [b])[0].cpu(),
+                      EPISODE_START)
+        assert r["max_count"] < Nmax
+        for t in range(T):
+            code = actions[t, b]
+            ranked = code < SEL_RAW
+            value = succ[torch.arange(N), code.clamp(max=succ.size(1) - 1)]
+            assert torch.equal(value[ranked], r["sel"][t][ranked]), f"SELECTED_ROAD of environment {b}, frame {t}"
+            assert not bool((succ[~ranked] == r["sel"][t][~ranked].unsqueeze(1)).any()), f"raw bytes, environment {b}, frame {t}"
+            assert rw[t, b] == r["reward"][t], f"reward of environment {b}, frame {t}"
+        assert torch.equal(r["x"], eng.x[b].cpu()), f"final state of environment {b}"
+        assert torch.equal(r["agents"], eng.agents[b].cpu()), f"agent table of environment {b}"
+        print(f"[baseline replay] environment {b}: largest count {r['max_count']:.0f} of {Nmax}, "
+              f"{int(r['agents'][1:, 8].sum())} arrivals, edges off free flow per refresh "
+              f"{[int((w != ff).sum()) for w in r['weights']]}")
+        runs.append(r)
+    want = R.per_env(R.summary(torch.stack([r["agents"] for r in runs]).numpy(),
+                               np.asarray([r["reward"] for r in runs], dtype=np.float32).T, 10.0, 720), 10.0)
+    for b, w in enumerate(want):
+        got = dict(arrived=res.arrived[b], on_way=res.on_way[b], not_departed=res.not_departed[b],
+                   episode_return=res.episode_return[b], avg=res.avg_travel_time[b], std=res.std_travel_time[b],
+                   max=res.max_travel_time[b], p50=res.p50_travel_time[b], p95=res.p95_travel_time[b])
+        assert got == w, (b, got, w)
+    return res, runs, actions
+
+
 def test_baseline_evaluation_replayed_by_the_oracle():
     """3 environments, 120 frames, 500 agents that leave within 120 s for one of eight roads (chosen on the CPU oracle under
     torch's own noise: largest count 11 of 15 in every environment, 100 - 500 edges off free flow at every refresh after the
@@ -322,52 +371,49 @@ def test_baseline_evaluation_replayed_by_the_oracle():
     values the kernels consumed. Device SELECTED_ROAD == the oracle's on every node at every frame (a raw byte: the oracle's
     value is no successor of the node; the final export compares those values too), every reward, the final state and
     agent table, and the EvalResult against eval_restatement: exact."""
-    import baseline_restatement as BR
-    import eval_restatement as R
-    from tarl_hip import ops
-    from tarl_hip.engine import EPISODE_START
     net = _torus8()
     N, Nmax, ei, K, T = net.num_roads, net.Nmax, net.edge_index, 3, 120
     pop = _load_population(net)
-    ev = _baseline_evaluator(net, pop, K, keep_actions=True)
-    eng = ev.eng
-    noise0 = eng.noise_counter + 1
-    res = ev.run(T)
-    assert not res.domain_exit and res.frames_run == T and res.head == "dijkstra" and res.deterministic
-    assert res.settings["refresh_rate"] == 10 and res.settings["destinations"] == len(set(LOAD["dests"]))
-    out_ptr, out_eid = R.csr(ei, N)
-    rw = ev.reward[:T].cpu()
-    actions = ev.actions[:T].cpu().long()
+    res, runs, _ = _assert_replayed_by_the_oracle(net, pop, K, T, ei[1].view(N, 4))      # source-sorted: the out-lists
     ff = net.x[:, 3 * Nmax + 2][ei[0]]
-    runs = []
-    for b in range(K):
-        r = BR.replay(net, pop, T, 10, lambda t: ops.noise_export(eng.plan, "gumbel", eng.seed, noise0 + t, [b])[0].cpu(),
-                      EPISODE_START)
-        assert r["max_count"] < Nmax
-        for t in range(T):
-            code = actions[t, b]
-            ranked = code < SEL_RAW
-            value = ei[1][out_eid[(out_ptr[:-1] + code.clamp(max=3))]].float()
-            assert torch.equal(value[ranked], r["sel"][t][ranked]), f"SELECTED_ROAD of environment {b}, frame {t}"
-            succ = ei[1].view(N, 4).float()
-            assert not bool((succ[~ranked] == r["sel"][t][~ranked].unsqueeze(1)).any()), f"raw bytes, environment {b}, frame {t}"
-            assert rw[t, b] == r["reward"][t], f"reward of environment {b}, frame {t}"
-        assert torch.equal(r["x"], eng.x[b].cpu()), f"final state of environment {b}"
-        assert torch.equal(r["agents"], eng.agents[b].cpu()), f"agent table of environment {b}"
-        print(f"[baseline replay] environment {b}: largest count {r['max_count']:.0f} of {Nmax}, "
-              f"{int(r['agents'][1:, 8].sum())} arrivals, edges off free flow per refresh "
-              f"{[int((w != ff).sum()) for w in r['weights']]}")
-        runs.append(r)
     # not vacuous: congestion moves the weights, and the environments route on different tables
     assert any(bool((w != ff).any()) for w in runs[0]["weights"][1:])
     assert any(not torch.equal(runs[0]["tables"][k], runs[b]["tables"][k]) for k in range(T // 10) for b in (1, 2))
-    want = R.per_env(R.summary(torch.stack([r["agents"] for r in runs]).numpy(),
-                               np.asarray([r["reward"] for r in runs], dtype=np.float32).T, 10.0, 720), 10.0)
-    for b, w in enumerate(want):
-        got = dict(arrived=res.arrived[b], on_way=res.on_way[b], not_departed=res.not_departed[b],
-                   episode_return=res.episode_return[b], avg=res.avg_travel_time[b], std=res.std_travel_time[b],
-                   max=res.max_travel_time[b], p50=res.p50_travel_time[b], p95=res.p95_travel_time[b])
-        assert got == w, (b, got, w)
+    assert min(res.arrived) >= 5
+
+
+IRREGULAR_LOAD = dict(agents=600, span=30, frames=40, dests=[5, 17, 33, 48, 61, 12, 13, 70])
+
+
+def test_baseline_evaluation_replayed_by_the_oracle_on_an_irregular_graph():
+    """The same replay on MIXED (tests/irregular_graphs.py: 80 roads, out-degrees 0 - 9, an edge list in no order, two dead
+    ends, two roads nobody can enter), 3 environments, 40 frames, 600 agents that leave within 30 s for six ordinary roads,
+    the road with nine out-edges or a dead end. Nobody starts on a dead end: the environment inserts an agent into the
+    SELECTED_ROAD of its origin, and a road that leads nowhere selects -1 (outside the reference's domain). On the CPU
+    oracle under torch's own noise: largest count 23 - 25 of 41, 37 - 40 arrivals, 190 - 250 edges off free flow at every
+    refresh, the table rebuilt differently at every refresh, 640 - 680 selections of out-rank >= 4 and about 140 raw ones
+    (the other dead end and the rows already at their destination); the test prints what the device's noise gives."""
+    import baseline_restatement as BR
+    import irregular_graphs as ig
+    import sp_cases as S
+    from tarl_hip.engine import EPISODE_START
+    c = S.case("MIXED")
+    net, N, K, T = c.net, c.N, 3, IRREGULAR_LOAD["frames"]
+    _, dout = ig.degrees(net)
+    leads_on = torch.nonzero(dout > 0).view(-1)
+    dests = IRREGULAR_LOAD["dests"]
+    assert int(dout[12]) == 9 and int(dout[13]) == 0 and all(int(dout[d]) > 0 for d in dests if d != 13)
+    pop = BR.few_destination_population(IRREGULAR_LOAD["agents"], N, dests, seed=7, t0=EPISODE_START,
+                                        t1=EPISODE_START + IRREGULAR_LOAD["span"])
+    pop[:, 0] = leads_on[pop[:, 0].long() % leads_on.numel()].float()
+    res, runs, actions = _assert_replayed_by_the_oracle(net, pop, K, T, S.out_table(c))
+    ff = net.x[:, 3 * net.Nmax + 2][c.ei[0]]
+    beyond = int(((actions >= 4) & (actions < SEL_RAW)).sum())
+    print(f"[baseline replay] MIXED: {beyond} selections of out-rank >= 4, {int((actions == SEL_RAW).sum())} raw, "
+          f"arrivals {res.arrived}")
+    assert beyond > 0 and bool((actions == SEL_RAW).any())
+    assert any(bool((w != ff).any()) for w in runs[0]["weights"][1:])
+    assert any(not torch.equal(runs[0]["weights"][k], runs[b]["weights"][k]) for k in range(1, T // 10) for b in (1, 2))
     assert min(res.arrived) >= 5
 
 
