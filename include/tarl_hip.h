@@ -972,6 +972,34 @@ int tarl_trip_bin_stats(const float* agents, int64_t K, int64_t num_agents, int6
                         int32_t* dep_done, int32_t* dep_way, int32_t* arr, double* dep_tt, double* dep_ff, int32_t* dep_ff_n,
                         tarl_stream stream);
 
+/* ---- dynamic relative gap of a vectorised evaluation -----------------------------------------------------------------------------
+ * How far the simulated trips are from the best path in hindsight under the time-dependent road times the episode itself
+ * produced (csrc/td_paths.hip states every formula; all arithmetic fp64 unless said otherwise). Bins as tarl_trip_bin_stats:
+ * bin h of H is the absolute bin first_bin + h of bin_seconds seconds, S(h) = (first_bin + h) * bin_seconds.
+ * tarl_td_road_times: veh int32 [K][H][N] and frames_per_bin int32 [H] (the occupancy sums of tarl_occupancy_accumulate and
+ *   the frames that fell into each bin), max_agents / free_flow / cong fp32 [N] (MAX_NUMBER_OF_AGENT, FREE_FLOW_TIME_TRAVEL and
+ *   the congestion constant of every road) -> tau fp32 [K][H][N] = (float) max(FF, cong / ((MAX + 10) - veh / frames)), FF for a
+ *   bin without frames and +inf for a denominator <= 0, and env fp64 [K][H + 1][N]: env[k][H][n] = +inf,
+ *   env[k][h][n] = min(S(h) + tau[k][h][n], env[k][h + 1][n]). One thread per (k, n), every element written.
+ * tarl_td_hindsight: per (environment k, agent a) of the agent tables (fp32 [K][A][9], environment k at agents + k *
+ *   a_bstride) the earliest clock at which a left its destination road: with leave(n, t) = min(t + tau[k][h][n],
+ *   env[k][h + 1][n]) at h = clamp((int64)floor(t) / bin_seconds - first_bin, 0, H - 1), L[origin] = leave(origin, DEPARTURE_TIME)
+ *   and L[v] = min over in-edges (u -> v) of leave(v, L[u]), best[k][a] = L[destination]. best fp64 [K][A], every entry
+ *   written: +inf for an unreachable destination, an id outside [0, N), the dummy row 0 and an agent with DONE != 1 (not
+ *   searched). A NaN tau counts as +inf. One 256-thread workgroup per search over at most 1 024 workgroups, each with an fp64
+ *   label row of N in `scratch` (tarl_td_hindsight_scratch_bytes(plan, K, A) bytes; -1 for a bad argument); the result does
+ *   not depend on the schedule: two runs are bit-identical.
+ * Refused on the host, before anything is launched and with the outputs untouched: a null argument, K, A or N < 1, K >= 65 536
+ *   (road times) or 2^31, a_bstride < 9 A, bin_seconds < 1, first_bin < 0, H outside [1, TARL_TRIP_MAX_BINS], a graph beyond
+ *   the limit of tarl_dest_trees (N > 327 680), a scratch smaller than tarl_td_hindsight_scratch_bytes. */
+int tarl_td_road_times(const int32_t* veh, const int32_t* frames_per_bin, const float* max_agents, const float* free_flow,
+                       const float* cong, int64_t K, int64_t H, int64_t N, int64_t bin_seconds, int64_t first_bin, float* tau,
+                       double* env, tarl_stream stream);
+int64_t tarl_td_hindsight_scratch_bytes(const tarl_plan* plan, int64_t K, int64_t num_agents);
+int tarl_td_hindsight(const tarl_plan* plan, const float* tau, const double* env, const float* agents, int64_t K,
+                      int64_t num_agents, int64_t a_bstride, int64_t bin_seconds, int64_t first_bin, int64_t H, void* scratch,
+                      int64_t scratch_bytes, double* best, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

@@ -5,7 +5,8 @@
 ``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
 ``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
 comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` and the per-road link counts of either
-``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy`` and ``--eval-trips``)."""
+``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy``, ``--eval-trips`` and
+``--eval-dynamic-gap``)."""
 import argparse
 import os
 import sys
@@ -106,6 +107,15 @@ OPTIONS = (
                                "free-flow time and, with --eval-baseline, the paired difference per trip; a `Trips` block "
                                "with a table by departure time (bins of --eval-link-bin seconds), eval_trips.csv and "
                                "eval_trips_by_departure.csv (dijkstra_trips*.csv); `trips` in the JSON file")),
+    ("--eval-dynamic-gap", dict(action="store_true",
+                                help="--eval-envs / --dijkstra-envs, eval: measure every completed trip against the quickest "
+                                     "path in hindsight under the time-dependent road times the run itself produced (mean "
+                                     "occupancy per bin of --eval-link-bin seconds): a `Dynamic gap` block with the relative gap "
+                                     "over the environments, eval_dynamic_gap.csv and eval_dynamic_gap_by_departure.csv "
+                                     "(dijkstra_dynamic_gap*.csv) and, with --eval-baseline, the paired difference; "
+                                     "`dynamic_gap` in the JSON file")),
+    ("--eval-dynamic-gap-envs", dict(type=int, default=None, metavar="J",
+                                     help="--eval-dynamic-gap: search the first J of the K environments only (default: all)")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--checkpoint", dict(type=str, default=None,

@@ -41,6 +41,8 @@ class RunnerArgs:
     eval_link_bin: int = 3600      # ... in time bins of this many seconds
     eval_occupancy: bool = False   # eval_envs / dijkstra_envs: per-road occupancy and time at capacity (bins of eval_link_bin)
     eval_trips: bool = False       # eval_envs / dijkstra_envs: per-traveller travel time and delay (bins of eval_link_bin)
+    eval_dynamic_gap: bool = False # eval_envs / dijkstra_envs, eval: the trips against the best path in hindsight (same bins)
+    eval_dynamic_gap_envs: int = None   # ... over the first J of the K environments (default: all)
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -75,6 +77,15 @@ class RunnerArgs:
         if self.eval_trips and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_trips reduces the agent tables of the vectorised evaluation per traveller: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_dynamic_gap and not ((self.eval_envs or self.dijkstra_envs) and self.mode == "eval"):
+            raise ValueError("eval_dynamic_gap measures the trips of the vectorised evaluation against the best path in "
+                             "hindsight: it needs mode 'eval' and eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_dynamic_gap_envs is not None:
+            if not self.eval_dynamic_gap:
+                raise ValueError("eval_dynamic_gap_envs limits the environments of eval_dynamic_gap: it needs that flag")
+            if not 1 <= int(self.eval_dynamic_gap_envs) <= int(self.eval_envs or self.dijkstra_envs):
+                raise ValueError(f"eval_dynamic_gap_envs must be in [1, {int(self.eval_envs or self.dijkstra_envs)}] (the "
+                                 f"environments of the evaluation), got {self.eval_dynamic_gap_envs!r}")
         if self.eval_link_bin is None or int(self.eval_link_bin) < 1:
             raise ValueError(f"eval_link_bin must be >= 1 second, got {self.eval_link_bin!r}")
         if int(self.iterations) < 1:
@@ -344,6 +355,8 @@ class Runner:
             g, h = sim.graph, sim.h
             kw.update(trips=True, link_bin_seconds=a.eval_link_bin,
                       trip_free_flow=g.x[:, h.FREE_FLOW_TIME_TRAVEL][g.edge_index[1]])
+        if a.eval_dynamic_gap:
+            kw.update(dynamic_gap=True, dynamic_gap_envs=a.eval_dynamic_gap_envs, link_bin_seconds=a.eval_link_bin)
         return kw
 
     @staticmethod
@@ -363,7 +376,7 @@ class Runner:
         return summary_fn(report)
 
     def _reports_output(self, doc, res, baseline, out_dir, prefix):
-        """--eval-link-counts, --eval-occupancy, --eval-trips: each report of ``res`` (against ``baseline``, the evaluation of
+        """--eval-link-counts, --eval-occupancy, --eval-trips, --eval-dynamic-gap: each report of ``res`` (against ``baseline``, the evaluation of
         the same environments, where there is one) printed, written to ``<prefix>_<report>.csv`` (one row per road; the
         link counts with the expected flows that Runner.eval computed; the trips one row per agent, and per departure bin in
         ``<prefix>_trips_by_departure.csv``) and summarised in ``doc``."""
@@ -381,6 +394,20 @@ class Runner:
                 "Trips", E.trip_report(res, baseline=baseline), E.trip_lines, E.trip_summary,
                 [(out_dir / f"{prefix}_trips.csv", "columns", "rows"),
                  (out_dir / f"{prefix}_trips_by_departure.csv", "by_departure_columns", "by_departure")])
+        if a.eval_dynamic_gap:
+            from functools import partial
+            rep = E.dynamic_gap_report(res, baseline=baseline)
+            doc["dynamic_gap"] = self._report_output(
+                "Dynamic gap", rep, partial(E.dynamic_gap_lines, paired=False), E.dynamic_gap_summary,
+                [(out_dir / f"{prefix}_dynamic_gap.csv", "columns", "rows"),
+                 (out_dir / f"{prefix}_dynamic_gap_by_departure.csv", "by_departure_columns", "by_departure")])
+            if baseline is not None:      # the baseline's own block, then the paired difference of the relative gap
+                doc["dynamic_gap"]["baseline"] = self._report_output(
+                    f"Dynamic gap: baseline ({baseline.head})", E.dynamic_gap_report(baseline), E.dynamic_gap_lines,
+                    E.dynamic_gap_summary, [(out_dir / f"{prefix}_dynamic_gap_baseline.csv", "columns", "rows")])
+                print("\n=== Dynamic gap: policy \u2212 baseline (paired) ===")
+                for line in E.dynamic_gap_paired_lines(rep):
+                    print(line)
 
     def _vectorised_dijkstra(self, frames, out_dir):
         """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra":

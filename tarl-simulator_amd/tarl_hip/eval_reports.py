@@ -1,5 +1,5 @@
 """The reports of the vectorised evaluation beyond the per-environment aggregate — per-road link counts, per-road occupancy
-and time at capacity, per-trip travel times — each as ``*_report`` (rows and a summary, formed in float64 on the host from the
+and time at capacity, per-trip travel times, the dynamic relative gap — each as ``*_report`` (rows and a summary, formed in float64 on the host from the
 kernels' integer accumulators), ``*_lines`` (its printable block) and ``*_summary`` (what the JSON files carry), and the pieces
 they share. :mod:`tarl_hip.evaluator` re-exports every public name and is never imported here: an ``EvalResult`` is only read."""
 from __future__ import annotations
@@ -625,3 +625,132 @@ def trip_lines(report: dict):
 
 
 trip_summary = _summary
+
+
+# ---- dynamic relative gap (VecEvaluator(dynamic_gap=True)) ------------------------------------------------------------------------
+DYNAMIC_GAP_NOTE = ("g = travel time - hindsight time: the hindsight time is the quickest way from origin to destination (both "
+                    "roads traversed) under the road times of the run's own mean occupancy per time bin, waiting allowed; "
+                    "RG = sum g / sum tt over the completed trips of an environment. g can be negative: the road time is a bin "
+                    "mean and the withdraw rule decides when a trip ends")
+
+
+def _gap_relative(per_env):
+    """RG_k per environment, ``None`` without a usable trip."""
+    return [float((per_env["tt_sum"][k] - per_env["ht_sum"][k]) / per_env["tt_sum"][k])
+            if int(per_env["n"][k]) > 0 and float(per_env["tt_sum"][k]) != 0.0 else None for k in range(len(per_env["n"]))]
+
+
+def dynamic_gap_report(result: "EvalResult", baseline: "EvalResult | None" = None) -> dict:
+    """Per-agent rows, a by-departure table and a summary of the dynamic gap of one evaluation
+    (``VecEvaluator(dynamic_gap=True)``), formed in float64 on the host from the device's sums. :data:`DYNAMIC_GAP_NOTE` is the
+    definition.
+    Every row: ``agent``, ``origin``, ``destination``, ``departure``; ``envs_usable``, the environments in which the agent
+    arrived and had a finite hindsight time; ``gap_mean``, ``gap_sd`` (ddof 1), ``gap_se``, ``gap_ci95_lo`` / ``_hi``, ``gap_min``,
+    ``gap_max`` over them (``None`` as in :func:`aggregate`) and ``envs_negative`` (g < 0).
+    The summary: ``relative_gap``, :func:`aggregate` of RG_k over the environments (mean, std, se, ci95; an environment without
+    a usable trip is missing) and ``relative_gap_per_env``; ``mean_gap``, the trip-weighted mean of g in seconds;
+    ``share_negative`` (g < 0) and ``share_nonpositive`` (g <= 0) of the usable trips; ``top_gaps``, the ten agents with the
+    largest mean gap; ``searches`` and ``search_wall_ms``.
+    ``baseline``: the evaluation of another head on the same environments with ``dynamic_gap=True`` (same K, seed, env_base,
+    frames, bins, population and ``dynamic_gap_envs``: ``ValueError`` otherwise); the summary gains ``paired``, the difference
+    RG_k(result) - RG_k(baseline) over the environments in which both have one: n, mean, std, se, ci95.
+    A run without the gap (a domain exit has none): ``{"available": False, "reason": ...}``."""
+    if (gone := _unavailable(result, result.dynamic_gap, "the run did not compute the dynamic gap")) is not None:
+        return gone
+    dg = result.dynamic_gap
+    pa, pe, pb, meta = dg["per_agent"], dg["per_env"], dg["per_bin"], dg["meta"]
+    J, H = pb["n"].shape
+    A = pa["n"].shape[0]
+    rg = _gap_relative(pe)
+    pair = None
+    if baseline is not None:
+        _check_pair("dynamic_gap_report", result, baseline)
+        if baseline.domain_exit or baseline.dynamic_gap is None:
+            pair = {"available": False, "reason": "the baseline run has no dynamic gap"}
+        else:
+            bm = baseline.dynamic_gap["meta"]
+            if baseline.frames_run != result.frames_run or baseline.dynamic_gap["per_bin"]["n"].shape != (J, H) or \
+                    any(bm[k] != meta[k] for k in ("first_bin", "bin_seconds", "envs")):
+                raise ValueError("dynamic_gap_report needs the same frames, bins and dynamic_gap_envs in both runs")
+            if baseline.dynamic_gap["per_agent"]["n"].shape[0] != A or \
+                    not all(np.array_equal(bm[k], meta[k]) for k in ("origin", "destination", "departure")):
+                raise ValueError("dynamic_gap_report needs the same population in both runs (origin, destination, departure)")
+            brg = _gap_relative(baseline.dynamic_gap["per_env"])
+            d = np.asarray([x - y for x, y in zip(rg, brg) if x is not None and y is not None], dtype=np.float64)
+            pair = {"available": True, "baseline_head": baseline.head, "n": int(d.size), "dropped": int(J - d.size),
+                    **_sample_moments(d), "ci95_kind": _CI95_KIND, "baseline_relative_gap": aggregate(brg)}
+    rows = []
+    for a in range(1, A):
+        n = int(pa["n"][a])
+        m = _trip_moments(n, pa["g_sum"][a], pa["g_sumsq"][a])
+        rows.append({"agent": a, "origin": int(meta["origin"][a]), "destination": int(meta["destination"][a]),
+                     "departure": float(meta["departure"][a]), "envs_usable": n, "gap_mean": m["mean"], "gap_sd": m["sd"],
+                     "gap_se": m["se"], "gap_ci95_lo": m["ci95_lo"], "gap_ci95_hi": m["ci95_hi"],
+                     "gap_min": float(pa["g_min"][a]) if n else None, "gap_max": float(pa["g_max"][a]) if n else None,
+                     "envs_negative": int(pa["n_neg"][a])})
+    trips = int(pe["n"].sum())
+    top = sorted((r for r in rows if r["gap_mean"] is not None), key=lambda r: (-r["gap_mean"], r["agent"]))[:10]
+    summary = {"envs": J, "agents": A - 1, "frames_run": result.frames_run, "trips": trips,
+               "searches": int(meta["searches"]), "search_wall_ms": float(meta["wall_ms"]),
+               "relative_gap": aggregate(rg), "relative_gap_per_env": rg,
+               "mean_gap": float(pe["tt_sum"].sum() - pe["ht_sum"].sum()) / trips if trips else None,
+               "share_negative": int(pe["n_neg"].sum()) / trips if trips else None,
+               "share_nonpositive": int(pe["n_nonpos"].sum()) / trips if trips else None,
+               "top_gaps": [{k: r[k] for k in ("agent", "origin", "destination", "departure", "envs_usable", "gap_mean")}
+                            for r in top]}
+    names = trip_bin_names(meta["first_bin"], H, meta["bin_seconds"])
+    by_rows = []
+    for h in range(H):
+        g = aggregate([float(pb["g_sum"][k, h]) / int(pb["n"][k, h]) if int(pb["n"][k, h]) > 0 else None for k in range(J)])
+        by_rows.append({"bin": names[h], "trips_mean": float(pb["n"][:, h].mean()), "gap_mean": g["mean"], "gap_se": g["se"],
+                        "envs": g["n"]})
+    if pair is not None:
+        summary["paired"] = pair
+    return {"available": True, "head": result.head, "definition": DYNAMIC_GAP_NOTE, "bin_seconds": int(meta["bin_seconds"]),
+            "first_bin": int(meta["first_bin"]), "bins": names, "columns": list(rows[0]) if rows else [], "rows": rows,
+            "by_departure_columns": list(by_rows[0]), "by_departure": by_rows, "summary": summary}
+
+
+def dynamic_gap_paired_lines(report: dict):
+    """The paired part of :func:`dynamic_gap_report` as printable lines; empty for a report without a baseline."""
+    p = report["summary"].get("paired") if report["available"] else None
+    if p is None:
+        return []
+    if not p["available"]:
+        return [f"paired:                not available: {p['reason']}"]
+    if p["mean"] is None:
+        return [f"{'policy - ' + p['baseline_head'] + ':':22} no environment with a relative gap in both runs"]
+    return [f"{'policy - ' + p['baseline_head'] + ':':22} {p['mean']:12.5f}{_interval(p)}  n {p['n']}  (paired difference of the "
+            f"relative gap per environment)"]
+
+
+def dynamic_gap_lines(report: dict, paired=True):
+    """:func:`dynamic_gap_report` as printable lines (the ``Dynamic gap`` block); ``paired=False`` leaves the paired line to
+    :func:`dynamic_gap_paired_lines`."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    s = report["summary"]
+    out = [f"definition:            {report['definition']}",
+           f"{'searches:':22} {s['searches']:12d}   hindsight searches over {s['envs']} environments in {s['search_wall_ms']:.1f} ms "
+           f"(road times and reductions included)"]
+    g = s["relative_gap"]
+    if g["mean"] is None:
+        out.append("relative gap:          no environment with a completed trip that has a hindsight time")
+    else:
+        out.append(f"{'relative gap:':22} {g['mean']:12.5f}{_interval(g)}  n {g['n']}"
+                   + (f"  ({g['missing']} environments without a usable trip left out)" if g["missing"] else ""))
+        out.append(f"{'mean gap:':22} {s['mean_gap']:12.3f} s  (trip-weighted over {s['trips']} trips); g < 0 in "
+                   f"{100.0 * s['share_negative']:.2f} % of the trips, g <= 0 in {100.0 * s['share_nonpositive']:.2f} %")
+        out.append("agents with the largest mean gap:")
+        for r in s["top_gaps"]:
+            out.append(f"  agent {r['agent']:7d}  {r['origin']:6d} -> {r['destination']:6d}  departs {r['departure']:9.1f}  "
+                       f"gap {r['gap_mean']:9.2f}  over {r['envs_usable']} environments")
+    out.append(f"By departure time (bins of {report['bin_seconds']} s; means over the environments with their standard error):")
+    out.append(f"  {'bin':>8} {'trips':>10} {'mean gap':>20}")
+    for r in report["by_departure"]:
+        gap = _f(r["gap_mean"]) + (f" +- {_f(r['gap_se'])}" if r["gap_se"] is not None else "")
+        out.append(f"  {r['bin']:>8} {_f(r['trips_mean']):>10} {gap:>20}")
+    return out + (dynamic_gap_paired_lines(report) if paired else [])
+
+
+dynamic_gap_summary = _summary

@@ -42,12 +42,12 @@ import torch
 from . import lib as _lib
 from . import ops
 from .engine import EPISODE_END, EPISODE_START
-from .eval_reports import (CONGESTION_FILE, LINK_EXPECTED, LINK_PARTIAL_NOTE, LINK_RING_BYTES,  # noqa: F401
+from .eval_reports import (CONGESTION_FILE, DYNAMIC_GAP_NOTE, LINK_EXPECTED, LINK_PARTIAL_NOTE, LINK_RING_BYTES,  # noqa: F401
                            OCCUPANCY_RING_BYTES, TRIP_CHANCE, TRIP_FF_CHUNK_BYTES, TRIP_FF_NOTE, _CI95_KIND, _interval, _sample_moments,
-                           aggregate, capacity_threshold, geh, link_bin_names, link_count_lines, link_count_report,
-                           link_count_summary, link_moments, occupancy_bin_names, occupancy_lines, occupancy_report,
-                           occupancy_summary, trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report,
-                           trip_summary)
+                           aggregate, capacity_threshold, dynamic_gap_lines, dynamic_gap_paired_lines, dynamic_gap_report,
+                           dynamic_gap_summary, geh, link_bin_names, link_count_lines, link_count_report, link_count_summary,
+                           link_moments, occupancy_bin_names, occupancy_lines, occupancy_report, occupancy_summary,
+                           trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report, trip_summary)
 
 HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra")
 _MLP_PRECISION = {"edge_mlp": "x3", "edge_mlp_fp32": "fp32", "edge_mlp_bf16": "bf16"}
@@ -109,6 +109,8 @@ class EvalResult:
     trip_bins: dict | None = field(default=None, compare=False)             # ops.trip_bin_stats, numpy arrays (K, H)
     trip_meta: dict | None = field(default=None, compare=False)             # first_bin, bin_seconds, origin, destination,
     #                                                                         departure, free_flow (A,), paired
+    # dynamic_gap=True (never after a domain exit): the trips against the best path in hindsight, DESIGN 4.17
+    dynamic_gap: dict | None = field(default=None, compare=False)           # best (J, A) fp64, per_agent, per_env, per_bin, meta
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -250,7 +252,8 @@ class VecEvaluator:
     def __init__(self, engine, head="embedding", *, emb=None, temperature=1.0, edge_mlp=None, prior_table=None,
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
-                 link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None):
+                 link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
+                 dynamic_gap_envs=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -276,7 +279,13 @@ class VecEvaluator:
         (``ops.trip_bin_stats``): two calls after ``ops.episode_summary``, none per frame. ``run()`` refuses environments
         whose ORIGIN, DESTINATION or DEPARTURE_TIME differ (per-agent statistics over different populations mean nothing).
         ``trip_free_flow`` fp32 (E,): free-flow edge weights; the free-flow time of every agent
-        (:func:`trip_free_flow_times`, one ``ops.destination_trees`` pass here) then serves as the reference for its delay."""
+        (:func:`trip_free_flow_times`, one ``ops.destination_trees`` pass here) then serves as the reference for its delay.
+        ``dynamic_gap``: after the episode also measure every completed trip against the best path in hindsight under the
+        time-dependent road times the episode produced: the occupancy accumulators run internally (without
+        ``occupancy=True`` the result carries no ``occupancy`` report), ``run()`` checks the population as for ``trips``, and
+        for the first ``dynamic_gap_envs`` environments (default: all K) one ``ops.td_road_times`` and one
+        ``ops.td_hindsight`` call follow the episode summary, reduced in fp64 on the device. ``run()`` refuses before the
+        first frame what does not fit half the free device memory."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -305,7 +314,15 @@ class VecEvaluator:
         K, N, E, dev = engine.B, engine.N, engine.E, engine.device
         plan = engine.plan
         self.link_counts, self.occupancy, self.trips = bool(link_counts), bool(occupancy), bool(trips)
-        if self.link_counts or self.occupancy or self.trips:      # one binning for the per-road reports and the trips
+        self.dynamic_gap = bool(dynamic_gap)
+        if dynamic_gap_envs is not None and not self.dynamic_gap:
+            raise ValueError("dynamic_gap_envs limits the environments of the dynamic gap: it needs dynamic_gap=True")
+        if self.dynamic_gap:
+            self.dynamic_gap_envs = K if dynamic_gap_envs is None else int(dynamic_gap_envs)
+            if not 1 <= self.dynamic_gap_envs <= K:
+                raise ValueError(f"dynamic_gap_envs must be in [1, {K}] (the engine's environments), got {dynamic_gap_envs!r}")
+        self._occ_acc_on = self.occupancy or self.dynamic_gap      # the gap reads the occupancy sums: accumulated either way
+        if self.link_counts or self._occ_acc_on or self.trips:      # one binning for the per-road reports and the trips
             self.link_bin_seconds = int(link_bin_seconds)
             if self.link_bin_seconds < 1:
                 raise ValueError("link_bin_seconds must be >= 1")
@@ -318,7 +335,7 @@ class VecEvaluator:
             self.link_popped = torch.zeros((self.link_block, K, N), dtype=torch.uint8, device=dev)
             self.link_withdrawn = torch.zeros((self.link_block, K, N), dtype=torch.uint8, device=dev)
             self.link_acc = None        # (K, H, N) int32, sized by run() for its frames
-        if self.occupancy:
+        if self._occ_acc_on:
             if occupancy_block is None:
                 occupancy_block = self._ring_block(OCCUPANCY_RING_BYTES, 4 * K * N)
             self.occupancy_block = int(occupancy_block)
@@ -469,7 +486,7 @@ class VecEvaluator:
         if self.link_counts:        # this frame's slice of the two rings; without either flag the call is as it always was
             j = t % self.link_block
             masks = dict(popped=self.link_popped[j], withdrawn=self.link_withdrawn[j])
-        if self.occupancy:          # and of the counts ring
+        if self._occ_acc_on:        # and of the counts ring
             masks["counts"] = self.occ_ring[t % self.occupancy_block]
         if self.head == "dijkstra":     # choice -> core -> withdraw / insert -> reward: the environment's step order
             if eng._packed_stale:
@@ -514,29 +531,31 @@ class VecEvaluator:
         self._flag_host.zero_()
         fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
         eng.reset()
-        if self.trips:
+        if self.trips or self.dynamic_gap:
             pop = eng.agents[:, :, :3]
             if not bool((pop == pop[:1]).all()):
-                raise ValueError("trips=True needs the same population in every environment: ORIGIN, DESTINATION or "
-                                 "DEPARTURE_TIME differ between the agent tables")
+                raise ValueError(f"{'trips=True' if self.trips else 'dynamic_gap=True'} needs the same population in every "
+                                 "environment: ORIGIN, DESTINATION or DEPARTURE_TIME differ between the agent tables")
             if trip_pair is not None and (tuple(trip_pair.shape) != tuple(eng.agents.shape) or
                                           not bool((trip_pair[:, :, :3] == pop).all())):
                 raise ValueError("trip_pair must hold the same population as this engine's agent tables")
         self._start(bool(deterministic))
         sched = H = None
-        if self.link_counts or self.occupancy or self.trips:      # one binning for the per-road reports and the trips
+        if self.link_counts or self._occ_acc_on or self.trips:      # one binning for the per-road reports and the trips
             t0, step, bins = int(eng.time), int(eng.timestep), self.link_bin_seconds
             H = (t0 + (T - 1) * step) // bins - t0 // bins + 1
             sched = _BinSchedule(t0, step, bins, t0 // bins, H)
         if self.trips and H > ops.TRIP_MAX_BINS:
             raise ValueError(f"trips=True stores at most {ops.TRIP_MAX_BINS} time bins (ops.TRIP_MAX_BINS); {T} frames in bins "
                              f"of {sched.bin_seconds} s reach {H}: widen link_bin_seconds")
+        if self.dynamic_gap:
+            self._gap_reserve(sched)
         acc = dict(dtype=torch.int32, device=eng.device)
         if self.link_counts:
             if self.link_acc is None or self.link_acc.size(1) != H:
                 self.link_acc = torch.empty((eng.B, H, eng.N), **acc)
             self.link_acc.zero_()
-        if self.occupancy:
+        if self._occ_acc_on:
             if self.occ_acc is None or self.occ_acc["veh"].size(1) != H:
                 self.occ_acc = {"veh": torch.empty((eng.B, H, eng.N), **acc), "full": torch.empty((eng.B, H, eng.N), **acc),
                                 "peak": torch.empty((eng.B, 1, eng.N), **acc)}
@@ -551,7 +570,7 @@ class VecEvaluator:
             if self.link_counts and _due(done, self.link_block, T):         # one launch per block of the rings
                 ops.link_counts_accumulate(self.link_popped, self.link_withdrawn, self.link_acc,
                                            **sched.block(done, self.link_block))
-            if self.occupancy and _due(done, self.occupancy_block, T):      # one launch per block of the ring
+            if self._occ_acc_on and _due(done, self.occupancy_block, T):      # one launch per block of the ring
                 ops.occupancy_accumulate(self.occ_ring, self.occ_thr, *self.occ_acc.values(),      # (veh, full, peak)
                                          **sched.block(done, self.occupancy_block))
             if _due(done, self.poll_frames, T):
@@ -606,6 +625,8 @@ class VecEvaluator:
                                       max=self.occ_max.copy(), thr=self.occ_thr_host.copy())
         if self.trips:
             self._trip_reduce(res, trip_pair, sched)
+        if self.dynamic_gap:
+            self._gap_reduce(res, sched, done)
         res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
         return res
 
@@ -625,3 +646,77 @@ class VecEvaluator:
                              destination=pop[:, 1].astype(np.int64), departure=pop[:, 2].copy(),
                              free_flow=None if self.trip_ff is None else self.trip_ff.cpu().numpy(),
                              paired=trip_pair is not None)
+
+    # -- the dynamic relative gap ---------------------------------------------------------------------------------
+    def _gap_reserve(self, sched):
+        """The buffers of the dynamic gap for the run's H bins, before the first frame: tau (J, H, N) fp32, env (J, H + 1, N)
+        and best (J, A) fp64, the label rows of the searches. Refused beyond half the free device memory."""
+        eng = self.eng
+        J, H, N, A, dev = self.dynamic_gap_envs, sched.H, eng.N, eng.A, eng.device
+        if H > ops.TRIP_MAX_BINS:
+            raise ValueError(f"dynamic_gap=True stores at most {ops.TRIP_MAX_BINS} time bins (ops.TRIP_MAX_BINS); the frames "
+                             f"reach {H} bins of {sched.bin_seconds} s: widen link_bin_seconds")
+        buf = getattr(self, "_gap_buf", None)
+        if buf is not None and buf["tau"].shape == (J, H, N):
+            return
+        self._gap_buf = None
+        scratch = ops.td_hindsight_bytes(eng.plan, J, A)
+        if scratch < 0:
+            raise _lib.TarlError("tarl_td_hindsight_scratch_bytes refused the evaluator's sizes")
+        tables = 4 * J * H * N + 8 * J * (H + 1) * N + 8 * J * A
+        free = int(torch.cuda.mem_get_info(dev)[0])
+        if tables + scratch > free // 2:
+            raise _lib.TarlError(f"the dynamic gap's road times and envelope ({tables / 2**30:.2f} GiB for dynamic_gap_envs = {J} "
+                                 f"environments x H = {H} bins x N = {N} roads, A = {A} agents) and search scratch "
+                                 f"({scratch / 2**30:.2f} GiB) exceed half the free device memory ({free / 2**30:.2f} GiB "
+                                 f"free): lower dynamic_gap_envs or widen link_bin_seconds")
+        st = eng.static_node_features[0]
+        mx, ff = st[:, 0].contiguous(), st[:, 2].contiguous()
+        cc = eng.cc
+        if cc is None:      # the simulator's own fp32 expression (oracle/sim.py::congestion_constants)
+            cc = ff * (mx + 10 - st[:, 4] * ff / 3600)
+        self._gap_buf = dict(tau=torch.empty((J, H, N), dtype=torch.float32, device=dev),
+                             env=torch.empty((J, H + 1, N), dtype=torch.float64, device=dev),
+                             best=torch.empty((J, A), dtype=torch.float64, device=dev),
+                             scratch=torch.empty(max(scratch, 1), dtype=torch.uint8, device=dev),
+                             frames=torch.zeros(H, dtype=torch.int32, device=dev), max=mx, ff=ff,
+                             cc=cc.to(torch.float32).contiguous())
+
+    def _gap_reduce(self, res, sched, done):
+        """Road times, searches and the fp64 reductions of a finished run into ``res.dynamic_gap``."""
+        eng, b = self.eng, self._gap_buf
+        J, H, A = self.dynamic_gap_envs, sched.H, eng.A
+        t_start = time.perf_counter()
+        bins_of = (sched.t0 + np.arange(done, dtype=np.int64) * sched.timestep) // sched.bin_seconds - sched.first_bin
+        frames = np.bincount(bins_of, minlength=H).astype(np.int32)
+        b["frames"].copy_(torch.from_numpy(frames))
+        kw = dict(bin_seconds=sched.bin_seconds, first_bin=sched.first_bin)
+        ag = eng.agents[:J]
+        ops.td_road_times(self.occ_acc["veh"][:J], b["frames"], b["max"], b["ff"], b["cc"], out=(b["tau"], b["env"]), **kw)
+        best = ops.td_hindsight(eng.plan, b["tau"], b["env"], ag, out=b["best"], scratch=b["scratch"], **kw)
+        # plumbing: (J, A) -> per agent, per environment, per (environment, departure bin), fp64 on the device
+        done_m = ag[:, :, 8] == 1.0
+        t0 = ag[:, :, 2].to(torch.float64)
+        tt = (ag[:, :, 3] - ag[:, :, 2]).to(torch.float64)
+        ht = best - t0
+        use = done_m & torch.isfinite(ht)
+        use[:, 0] = False
+        zero = torch.zeros((), dtype=torch.float64, device=eng.device)
+        g = torch.where(use, tt - torch.where(use, ht, zero), zero)
+        neg = use & (g < 0)
+        inf = torch.full((), float("inf"), dtype=torch.float64, device=eng.device)
+        per_agent = {"n": use.sum(0), "g_sum": g.sum(0), "g_sumsq": (g * g).sum(0), "g_min": torch.where(use, g, inf).amin(0),
+                     "g_max": torch.where(use, g, -inf).amax(0), "n_neg": neg.sum(0)}
+        per_env = {"tt_sum": torch.where(use, tt, zero).sum(1), "ht_sum": torch.where(use, ht, zero).sum(1), "n": use.sum(1),
+                   "n_neg": neg.sum(1), "n_nonpos": (use & (g <= 0)).sum(1)}
+        dep_bin = ops.trip_clock_bin(ag[0, :, 2], sched.bin_seconds, sched.first_bin, H)
+        idx = dep_bin.unsqueeze(0).expand(J, A)
+        per_bin = {"g_sum": torch.zeros((J, H), dtype=torch.float64, device=eng.device).scatter_add_(1, idx, g),
+                   "n": torch.zeros((J, H), dtype=torch.int64, device=eng.device).scatter_add_(1, idx, use.to(torch.int64))}
+        host = lambda d: {k: v.cpu().numpy() for k, v in d.items()}      # noqa: E731
+        pop = ag[0, :, :3].cpu().numpy()
+        res.dynamic_gap = dict(best=best.cpu().numpy(), per_agent=host(per_agent), per_env=host(per_env), per_bin=host(per_bin))
+        res.dynamic_gap["meta"] = dict(
+            envs=J, first_bin=sched.first_bin, bin_seconds=sched.bin_seconds, frames_per_bin=[int(x) for x in frames],
+            origin=pop[:, 0].astype(np.int64), destination=pop[:, 1].astype(np.int64), departure=pop[:, 2].copy(),
+            searches=int(done_m[:, 1:].sum()), wall_ms=(time.perf_counter() - t_start) * 1000.0)

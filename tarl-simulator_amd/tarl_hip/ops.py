@@ -961,6 +961,89 @@ def trip_bin_stats(agents, *, bin_seconds, first_bin, num_bins, free_flow=None, 
     return out
 
 
+# ---- dynamic relative gap (tarl_hip/evaluator.py, dynamic_gap=True) ----------------------------------------------------------
+def td_road_times(veh, frames_per_bin, max_agents, free_flow, cong, *, bin_seconds, first_bin, out=None):
+    """Time-dependent road times of an episode and their FIFO envelope (tarl_td_road_times). ``veh`` int32 (K, H, N): the
+    occupancy sums of :func:`occupancy_accumulate`; ``frames_per_bin`` int32 (H,): the frames that fell into each bin;
+    ``max_agents``, ``free_flow``, ``cong`` fp32 (N,): MAX_NUMBER_OF_AGENT, FREE_FLOW_TIME_TRAVEL and the congestion constant
+    of every road. Returns ``(tau, env)``: ``tau`` fp32 (K, H, N) = (float) max(FF, cong / ((MAX + 10) - veh / frames)) in
+    fp64 — FF for a bin without frames, +inf for a denominator <= 0 — and ``env`` fp64 (K, H + 1, N) with ``env[:, H] = +inf``
+    and ``env[:, h] = min((first_bin + h) * bin_seconds + tau[:, h], env[:, h + 1])``. ``out``: such a pair to write into; a
+    refused call leaves it untouched."""
+    if veh.dim() != 3:
+        raise ValueError(f"veh must be (K, H, N), got {tuple(veh.shape)}")
+    K, H, N = veh.shape
+    if K < 1 or H < 1 or N < 1:
+        raise ValueError("veh must not be empty")
+    _meta(veh, torch.int32, (K, H, N), "veh")
+    _meta(frames_per_bin, torch.int32, (H,), "frames_per_bin")
+    for t, name in ((max_agents, "max_agents"), (free_flow, "free_flow"), (cong, "cong")):
+        _meta(t, torch.float32, (N,), name)
+    bin_seconds, first_bin, H = _trip_bins(bin_seconds, first_bin, H)
+    if K >= 65536:
+        raise ValueError(f"one call takes fewer than 65536 environments, got {K}")
+    if out is not None:
+        _meta(out[0], torch.float32, (K, H, N), "out[0] (tau)")
+        _meta(out[1], torch.float64, (K, H + 1, N), "out[1] (env)")
+    for t, dt, name in ((veh, torch.int32, "veh"), (frames_per_bin, torch.int32, "frames_per_bin"),
+                        (max_agents, torch.float32, "max_agents"), (free_flow, torch.float32, "free_flow"),
+                        (cong, torch.float32, "cong")):
+        _check_dev(t, dt, name)
+    if out is None:
+        out = (torch.empty((K, H, N), dtype=torch.float32, device=veh.device),
+               torch.empty((K, H + 1, N), dtype=torch.float64, device=veh.device))
+    tau, env = out
+    _check_dev(tau, torch.float32, "out[0] (tau)")
+    _check_dev(env, torch.float64, "out[1] (env)")
+    _lib.check(_lib.load().tarl_td_road_times(veh.data_ptr(), frames_per_bin.data_ptr(), max_agents.data_ptr(),
+                                              free_flow.data_ptr(), cong.data_ptr(), K, H, N, bin_seconds, first_bin,
+                                              tau.data_ptr(), env.data_ptr(), _lib.current_stream()))
+    return tau, env
+
+
+def td_hindsight_bytes(plan: Plan, K: int, num_agents: int) -> int:
+    """Scratch bytes of :func:`td_hindsight` for K x num_agents searches (one fp64 label row of N per resident workgroup);
+    -1 for a bad argument."""
+    return int(_lib.load().tarl_td_hindsight_scratch_bytes(plan.handle, int(K), int(num_agents)))
+
+
+def td_hindsight(plan: Plan, tau, env, agents, *, bin_seconds, first_bin, out=None, scratch=None):
+    """The hindsight arrival of every (environment, agent) under the road times of :func:`td_road_times`
+    (tarl_td_hindsight): ``tau`` fp32 (K, H, N), ``env`` fp64 (K, H + 1, N), ``agents`` fp32 (K, A, 9) after the episode ->
+    ``best`` fp64 (K, A), every entry written: the earliest clock at which the agent could have left its destination road
+    (both end roads traversed, waiting for a later bin allowed), +inf for an unreachable destination, an id out of range,
+    row 0 and an agent with DONE != 1. ``out`` fp64 (K, A) and ``scratch`` uint8 (:func:`td_hindsight_bytes`): caller-owned
+    buffers; a refused call leaves ``out`` untouched. The graph-size limit is :func:`destination_trees`'s."""
+    K, A, abs_ = _trip_tables(agents, "agents")
+    N = plan.num_nodes
+    if tau.dim() != 3:
+        raise ValueError(f"tau must be (K, H, N), got {tuple(tau.shape)}")
+    H = tau.size(1)
+    _meta(tau, torch.float32, (K, H, N), "tau")
+    _meta(env, torch.float64, (K, H + 1, N), "env")
+    bin_seconds, first_bin, H = _trip_bins(bin_seconds, first_bin, H)
+    if out is not None:
+        _meta(out, torch.float64, (K, A), "out")
+    if scratch is not None:
+        if scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous():
+            raise TypeError("scratch must be a contiguous 1-D uint8 tensor")
+    for t, dt, name in ((agents, torch.float32, "agents"), (tau, torch.float32, "tau"), (env, torch.float64, "env")):
+        _check_dev(t, dt, name)
+    need = td_hindsight_bytes(plan, K, A)
+    if need < 0:
+        raise _lib.TarlError("tarl_td_hindsight_scratch_bytes refused the sizes")
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=agents.device)
+    _check_dev(scratch, torch.uint8, "scratch")
+    if out is None:
+        out = torch.empty((K, A), dtype=torch.float64, device=agents.device)
+    _check_dev(out, torch.float64, "out")
+    _lib.check(_lib.load().tarl_td_hindsight(plan.handle, tau.data_ptr(), env.data_ptr(), agents.data_ptr(), K, A, abs_,
+                                             bin_seconds, first_bin, H, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                             _lib.current_stream()))
+    return out
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")
