@@ -417,7 +417,7 @@ typedef struct tarl_fused {
    * library keeps a device-resident copy of this table of pointers there (written by a one-thread launch at the head of every
    * such call, on the call's stream), and the row pass and the insert kernels read the pointers they need from it through the
    * scalar cache instead of carrying all of them as kernel arguments — 27 pointer arguments cost those kernels a dozen
-   * scalar-register pairs each, most of them spilled (csrc/fused.hip: k_set_bufs). */
+   * scalar-register pairs each, most of them spilled (csrc/fused_pack.hip: k_set_bufs). */
   void* bufs_dev;
 } tarl_fused;
 

@@ -1,4 +1,4 @@
-// fused_common.h — definitions shared by the two rollout implementations: fused.hip (env-minor, launches per frame)
+// fused_common.h — definitions shared by the two rollout implementations: fused_*.hip (env-minor, launches per frame)
 // and rollout_env.hip (one workgroup per environment, LDS-resident records, all T frames in one launch).
 #pragma once
 
@@ -227,7 +227,7 @@ __device__ __forceinline__ float entry_tt(const float4 st, float n) {
   return (t_cong != t_cong) ? t_cong : fmaxf(st.y, t_cong);
 }
 
-// fused.hip
+// fused_pack.hip
 FusedBufs tarl_to_bufs(const tarl_fused* f);
 int tarl_check_fused_core(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax);
 int tarl_fused_dead_slots(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int materialise,

@@ -1,0 +1,265 @@
+// fused_rollout.hip — the host loops of the fused path: one frame (tarl_fused_frame), T frames with the live policy
+// (tarl_fused_rollout) and T frames with a state-dependent policy head (tarl_fused_rollout_policy), written against the launch
+// functions of the kernel files. (Design: fused_frame.h.)
+#include "fused_frame.h"
+
+// the side outputs of frame t of a T-frame rollout: slice t of every series the caller asked for; the event byte gc8 is
+// stored for every row in the last frame only (FrameOut::write_gc)
+static FrameOut rollout_frame_out(int64_t t, int64_t T, int64_t N, int64_t B, uint8_t* counts, int32_t metrics_envs,
+                                  float* dtt_node, uint8_t* events, int32_t* leg) {
+  const int64_t m = metrics_envs;
+  return FrameOut{counts ? counts + t * N * B : nullptr, nullptr, nullptr, nullptr,   // no frame-API outputs in a rollout
+                  events ? events + t * N * m : nullptr, dtt_node ? dtt_node + t * N * m : nullptr, metrics_envs,
+                  leg ? leg + t * 2 * B : nullptr, t + 1 == T ? 1 : 0};
+}
+
+extern "C" int tarl_fused_frame(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax,
+                                const float* thresholds, const int64_t* log_probs, const float* entropy1,
+                                const float* uniform, uint64_t policy_seed, uint64_t policy_counter,
+                                float* agent_features, int64_t A, int64_t a_bstride, const float* edge_attr,
+                                const float* log_edge_attr, float log_eps, int use_cong, float time, float prev_time,
+                                const float* gumbel, uint64_t seed, uint64_t counter, float* delta_travel_time,
+                                uint8_t* popped, uint8_t* withdrawn, int32_t* ins_scratch, int32_t* choice,
+                                float* log_prob, float* entropy, float* reward, float* counts, tarl_stream stream) {
+  int rc = tarl_check_fused_core(plan, f, B, Nmax);
+  if (rc) return rc;
+  // thresholds == NULL: SELECTED_ROAD was set by the caller (tarl_fused_apply_choice); no sample / log-prob in this call
+  TARL_REQUIRE((thresholds && log_probs && entropy1) || (!thresholds && !log_prob && !entropy && !choice),
+               "policy tables missing (call tarl_fused_policy_prepare), or outputs of the skipped choice phase requested");
+  rc = tarl_check_frame_args(plan, f, B, agent_features, A, a_bstride, ins_scratch, edge_attr, log_edge_attr);
+  if (rc) return rc;
+  if (plan->N == 0) return TARL_OK;
+  const FusedBufs fb = tarl_to_bufs(f);
+  const PlanOut P{plan->out_ptr, plan->out_dst};
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned threads = tile_threads(B);
+  const dim3 grid((unsigned)ceil_div(B, threads), (unsigned)num_chunks(plan));
+  if (thresholds) {
+    rc = tarl_launch_choice(s, plan, f, B, fb.acc_lp, thresholds, log_probs, uniform, policy_seed, policy_counter, f->sel8,
+                            (const uint8_t*)f->sel8, choice, log_prob != nullptr ? 1 : 0);
+    if (rc) return rc;
+  }
+  const FusedBufs* fbd = nullptr;
+  rc = tarl_upload_bufs(f, fb, nullptr, s, &fbd);
+  if (rc) return rc;
+  const bool timed = tarl_prof_mark(s, 0) != nullptr;
+  const dim3 grid_d((unsigned)ceil_div(B, threads), (unsigned)ceil_div(plan->N, nchunk_dir()));
+  const FrameOut out{nullptr, counts, popped, withdrawn, nullptr, nullptr, 0, nullptr, 1};
+  rc = tarl_launch_direction(grid_d, threads, s, plan, f, edge_attr, log_edge_attr, (const uint8_t*)f->sel8, gumbel,
+                             delta_travel_time, log_eps, time, prev_time, seed, counter, B, (int)Nmax, out);
+  if (rc) return rc;
+  if (timed) (void)tarl_prof_mark(s, 1);
+  rc = tarl_launch_rows(grid, threads, s, plan, f, fbd, (int)Nmax, B, agent_features, A, a_bstride, time, out);
+  if (rc) return rc;
+  if (timed) (void)tarl_prof_mark(s, 2);
+  rc = tarl_launch_insert(1, s, (int)Nmax, B, plan->N, fbd, P, (const uint8_t*)f->sel8, agent_features, A, a_bstride,
+                          use_cong, time, ins_scratch, entropy1, reward, out, log_prob, entropy);
+  if (rc) return rc;
+  if (timed) (void)tarl_prof_mark(s, 3);
+  return TARL_OK;
+}
+
+// T consecutive frames with device noise: the collector loop in one foreign call. Each frame is direction -> rows ->
+// insert on the caller's stream. The action of frame t is slice t of the action buffer, which is also the
+// SELECTED_ROAD column that frame's Direction gather and insert read. With an action buffer and choice_scratch (the
+// default, TARL_ROLLOUT_MERGE=2) the live policy's draws for ALL frames are made on a side stream in blocks of
+// frames (the sample does not depend on the state: fused_choice.hip, tarl_choice_ahead_queue), the first, short block is
+// waited for; otherwise frame t+1's choice shares the launch of frame t's insert (k_fused_insert_choice, mode 1) or is a
+// launch of its own (mode 0). Per-frame draws on a side stream and folding them into the row pass were measured and
+// rejected.
+extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                  const float* times_host, float prev_time, const float* thresholds,
+                                  const int64_t* log_probs, const float* entropy1, uint64_t policy_seed,
+                                  uint64_t policy_counter0, float* agent_features, int64_t A, int64_t a_bstride,
+                                  const float* edge_attr, const float* log_edge_attr, float log_eps, int use_cong,
+                                  uint64_t seed, uint64_t counter0, int32_t* ins_scratch, uint8_t* sel_scratch,
+                                  int64_t* acc_scratch, int32_t* choice_scratch, uint8_t* choice, float* log_prob,
+                                  float* entropy, float* reward,
+                                  uint8_t* counts, int32_t metrics_envs, float* dtt_node, uint8_t* events, int32_t* leg,
+                                  tarl_stream stream) {
+  int rc = tarl_check_fused_core(plan, f, B, Nmax);
+  if (rc) return rc;
+  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
+  TARL_REQUIRE(thresholds && log_probs && entropy1, "policy tables missing (call tarl_fused_policy_prepare)");
+  rc = tarl_check_frame_args(plan, f, B, agent_features, A, a_bstride, ins_scratch, edge_attr, log_edge_attr);
+  if (rc) return rc;
+  TARL_REQUIRE(metrics_envs >= 0 && metrics_envs <= B, "metrics_envs out of range");
+  TARL_REQUIRE(metrics_envs > 0 || (!dtt_node && !events), "per-node series need metrics_envs > 0");
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t N = plan->N, NB = N * B;
+  const unsigned threads = tile_threads(B);
+  const dim3 grid((unsigned)ceil_div(B, threads), (unsigned)num_chunks(plan));
+  const dim3 grid_c((unsigned)ceil_div(B, threads), (unsigned)ceil_div(N, nchunk_choice()));
+  const dim3 grid_d((unsigned)ceil_div(B, threads), (unsigned)ceil_div(N, nchunk_dir()));
+  const int want_lp = log_prob != nullptr ? 1 : 0;
+  const FusedBufs fb = tarl_to_bufs(f);
+  const PlanOut P{plan->out_ptr, plan->out_dst};
+  // slice t of the action buffer (or, without one, the ping-pong pair f->sel8 / sel_scratch)
+  auto slice = [&](int64_t t) -> uint8_t* {
+    if (choice) return choice + t * NB;
+    return (sel_scratch && (t & 1)) ? sel_scratch : f->sel8;
+  };
+  // steady state: frame t's insert and frame t+1's choice share ONE launch (k_fused_insert_choice); needs two distinct
+  // SELECTED_ROAD slices and double-buffered log-prob accumulator banks
+  // TARL_ROLLOUT_MERGE: 2 (default) = all actions precomputed on a side stream (needs the action buffer + choice_scratch),
+  // 1 = frame t+1's choice shares frame t's insert launch, 0 = a choice launch per frame
+  const char* knob = getenv("TARL_ROLLOUT_MERGE");
+  const int mode = knob ? atoi(knob) : 2;
+  const bool ahead = mode >= 2 && choice && choice_scratch && tarl_choice_ahead_fits(plan, T);
+  const bool merge = !ahead && mode >= 1 && (choice || sel_scratch) && acc_scratch && T > 1;
+  long long* acc_buf[2] = {(long long*)f->acc_lp, merge ? (long long*)acc_scratch : (long long*)f->acc_lp};
+  if (merge) TARL_CHECK_HIP(hipMemsetAsync(acc_scratch, 0, (size_t)(f->acc_slots * B) * sizeof(int64_t), s));
+  const FusedBufs* fbd = nullptr;      // [0]: the table with acc_buf[0], [1]: with acc_buf[1]
+  rc = tarl_upload_bufs(f, fb, acc_buf[1], s, &fbd);
+  if (rc) return rc;
+  const hipEvent_t* drawn = nullptr;   // ahead: one event per block of frames whose actions the side stream has drawn
+  if (ahead)
+    rc = tarl_choice_ahead_queue(s, plan, f, B, T, thresholds, log_probs, policy_seed, policy_counter0, choice_scratch, choice,
+                                 log_prob, &drawn);
+  else
+    rc = tarl_launch_choice(s, plan, f, B, acc_buf[0], thresholds, log_probs, nullptr, policy_seed, policy_counter0, slice(0),
+                            (const uint8_t*)f->sel8, nullptr, want_lp);
+  if (rc) return rc;
+  const int epw_packed = tarl_insert_envs_per_wave(f, A, B, T, times_host);
+  for (int64_t t = 0; t < T; ++t) {
+    const int cur = merge ? (int)(t & 1) : 0;
+    const float time = times_host[t];
+    const FusedBufs* fbt = fbd + cur;
+    const uint8_t* sel_t = slice(t);
+    const FrameOut out = rollout_frame_out(t, T, N, B, counts, metrics_envs, dtt_node, events, leg);
+    if (ahead) {
+      rc = tarl_choice_ahead_wait(s, drawn, t);
+      if (rc) return rc;
+    }
+    const bool timed = tarl_prof_mark(s, 0) != nullptr;
+    rc = tarl_launch_direction(grid_d, threads, s, plan, f, edge_attr, log_edge_attr, sel_t, nullptr, nullptr, log_eps, time,
+                               t > 0 ? times_host[t - 1] : prev_time, seed, counter0 + (uint64_t)t, B, (int)Nmax, out,
+                               (counts && t > 0) ? counts + (t - 1) * NB : nullptr);   // the counts after frame t - 1
+    if (rc) return rc;
+    if (timed) (void)tarl_prof_mark(s, 1);
+    rc = tarl_launch_rows(grid, threads, s, plan, f, fbt, (int)Nmax, B, agent_features, A, a_bstride, time, out);
+    if (rc) return rc;
+    if (timed) (void)tarl_prof_mark(s, 2);
+    float* reward_t = reward ? reward + t * B : nullptr;
+    float* lp_t = (log_prob && !ahead) ? log_prob + t * B : nullptr;   // ahead: written by k_fused_choice_all
+    float* ent_t = entropy ? entropy + t * B : nullptr;
+    if (merge && t + 1 < T) {
+      const ChoiceArgs C{plan->out_ptr, plan->out_eid, plan->group_of_node, plan->G, thresholds,
+                         (const long long*)log_probs, policy_seed, policy_counter0 + (uint64_t)(t + 1), nchunk_choice(),
+                         want_lp, slice(t + 1), acc_buf[cur ^ 1], grid_c.x, grid_c.x * grid_c.y};
+      rc = tarl_launch_insert_choice(C, threads, s, (int)Nmax, B, N, fbt, P, sel_t, agent_features, A, a_bstride, use_cong,
+                                     time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t);
+    } else {
+      rc = tarl_launch_insert(ahead ? epw_packed : 1, s, (int)Nmax, B, N, fbt, P, sel_t, agent_features, A, a_bstride,
+                              use_cong, time, ins_scratch, entropy1, reward_t, out, lp_t, ent_t);
+      if (!rc && !ahead && t + 1 < T)   // unmerged: the next frame's choice as its own launch
+        rc = tarl_launch_choice(s, plan, f, B, acc_buf[cur], thresholds, log_probs, nullptr, policy_seed,
+                                policy_counter0 + (uint64_t)(t + 1), slice(t + 1), sel_t, nullptr, want_lp);
+    }
+    if (rc) return rc;
+    if (timed) (void)tarl_prof_mark(s, 3);
+  }
+  if (slice(T - 1) != f->sel8)   // the last frame's SELECTED_ROAD lives in the action buffer / scratch: bring it home
+    TARL_CHECK_HIP(hipMemcpyAsync(f->sel8, slice(T - 1), (size_t)NB, hipMemcpyDeviceToDevice, s));
+  return TARL_OK;
+}
+
+// ---- T frames with a STATE-DEPENDENT policy (the per-edge MLP head) in one foreign call --------------------------------------
+// Nothing of GraphDistribution can be hoisted: per frame observation (tarl_fused_obs16) -> logits (tarl_policy_edge_mlp_fwd)
+// -> action + log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> Direction -> rows -> insert, eight launches queued
+// back to back by one host loop in C (the same entry points a caller could queue himself, minus a foreign-call round
+// trip per launch). The observations of the frames an optimiser minibatch will use are drawn beforehand (the draw does
+// not depend on the data): keep_ptr_host[t] .. keep_ptr_host[t + 1] index the (environment, slot) pairs of frame t.
+__global__ __launch_bounds__(FB) void k_obs_keep(const float4* __restrict__ obs, int64_t row4,
+                                                 const int32_t* __restrict__ env, const int32_t* __restrict__ slot,
+                                                 float4* __restrict__ keep) {
+  const int64_t j = (int64_t)blockIdx.x * FB + threadIdx.x;
+  if (j >= row4) return;
+  keep[(int64_t)slot[blockIdx.y] * row4 + j] = obs[(int64_t)env[blockIdx.y] * row4 + j];
+}
+
+extern "C" int tarl_fused_rollout_policy(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                                         const float* times_host, float prev_time, const float* x, int64_t x_bstride,
+                                         int64_t ldx, float* agent_features, int64_t A, int64_t a_bstride,
+                                         const float* edge_attr, const float* log_edge_attr, float log_eps, int use_cong,
+                                         const float* w1, const float* b1, const float* w2, const float* b2,
+                                         const float* w3, const float* b3, int precision, float temperature,
+                                         uint64_t policy_seed, uint64_t policy_counter0, uint64_t seed,
+                                         uint64_t counter0, const int64_t* keep_ptr_host, const int32_t* keep_env,
+                                         const int32_t* keep_slot, float* obs_keep, float* obs_scratch,
+                                         float* logits_scratch, void* dist_scratch, int32_t* ins_scratch,
+                                         uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
+                                         int32_t metrics_envs, float* dtt_node, uint8_t* events, int32_t* leg,
+                                         tarl_stream stream) {
+  int rc = tarl_check_fused_core(plan, f, B, Nmax);
+  if (rc) return rc;
+  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
+  TARL_REQUIRE(x && obs_scratch && logits_scratch && dist_scratch, "observation / logits / sampler scratch missing");
+  TARL_REQUIRE(!keep_ptr_host || (keep_env && keep_slot && obs_keep), "keep list without its arrays");
+  TARL_REQUIRE(precision >= 0 && precision <= 2,
+               "precision: 0 = fp32 MFMA logits, 1 = bf16 logits on bf16 observations, 2 = fp32-accurate logits on the bf16 pipe (bf16x3)");
+  rc = tarl_check_frame_args(plan, f, B, agent_features, A, a_bstride, ins_scratch, edge_attr, log_edge_attr);
+  if (rc) return rc;
+  TARL_REQUIRE(metrics_envs >= 0 && metrics_envs <= B, "metrics_envs out of range");
+  TARL_REQUIRE(metrics_envs > 0 || (!dtt_node && !events), "per-node series need metrics_envs > 0");
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t N = plan->N, NB = N * B;
+  const unsigned threads = tile_threads(B);
+  const dim3 grid((unsigned)ceil_div(B, threads), (unsigned)num_chunks(plan));
+  const dim3 grid_d((unsigned)ceil_div(B, threads), (unsigned)ceil_div(N, nchunk_dir()));
+  const FusedBufs fbh = tarl_to_bufs(f);
+  const FusedBufs* fb = nullptr;
+  rc = tarl_upload_bufs(f, fbh, nullptr, s, &fb);
+  if (rc) return rc;
+  const PlanOut P{plan->out_ptr, plan->out_dst};
+  const int epw_packed = tarl_insert_envs_per_wave(f, A, B, T, times_host);
+  for (int64_t t = 0; t < T; ++t) {
+    const bool keep_t = keep_ptr_host && keep_ptr_host[t + 1] > keep_ptr_host[t];
+    const int64_t lo = keep_t ? keep_ptr_host[t] : 0, n = keep_t ? keep_ptr_host[t + 1] - lo : 0;
+    TARL_REQUIRE(n < 65536, "more than 65535 kept observations in one frame");
+    if (precision == 1) {
+      // bf16 logits read bf16 observations (half the bytes written here and gathered by the MLP); the fp32 rows an
+      // optimiser step keeps are evaluated for their few environments only
+      rc = tarl_fused_obs16_bf16(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride,
+                                 (uint16_t*)obs_scratch, stream);
+      if (rc) return rc;
+      if (keep_t) {
+        rc = tarl_fused_obs16_rows(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, keep_env + lo,
+                                   keep_slot + lo, n, obs_keep, stream);
+        if (rc) return rc;
+      }
+    } else {
+      rc = tarl_fused_obs16(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, obs_scratch, stream);
+      if (rc) return rc;
+      if (keep_t) {
+        hipLaunchKernelGGL(k_obs_keep, dim3((unsigned)ceil_div(N * 4, FB), (unsigned)n), dim3(FB), 0, s,
+                           (const float4*)obs_scratch, N * 4, keep_env + lo, keep_slot + lo, (float4*)obs_keep);
+        TARL_LAUNCH_CHECK();
+      }
+    }
+    // (live timing, bench.py: HIP events around the per-edge MLP of the timed frames — slot 0 of tarl_prof_collect)
+    const bool timed = tarl_prof_mark(s, 0) != nullptr;
+    rc = tarl_policy_edge_mlp_fwd(plan, obs_scratch, B, edge_attr, w1, b1, w2, b2, w3, b3,
+                                  precision == 1 ? 2 : (precision == 2 ? 3 : 0), logits_scratch, stream);
+    if (rc) return rc;
+    if (timed) (void)tarl_prof_mark(s, 1);
+    rc = tarl_graphdist_rollout_at(plan, logits_scratch, B, temperature, nullptr, policy_seed,
+                                   policy_counter0 + (uint64_t)t, dist_scratch, nullptr,
+                                   choice8 ? choice8 + t * NB : nullptr, f->sel8, log_prob ? log_prob + t * B : nullptr,
+                                   f->env_base, stream);
+    if (rc) return rc;
+    const float time = times_host[t];
+    const FrameOut out = rollout_frame_out(t, T, N, B, counts, metrics_envs, dtt_node, events, leg);
+    rc = tarl_launch_direction(grid_d, threads, s, plan, f, edge_attr, log_edge_attr, (const uint8_t*)f->sel8, nullptr, nullptr,
+                               log_eps, time, t > 0 ? times_host[t - 1] : prev_time, seed, counter0 + (uint64_t)t, B, (int)Nmax, out);
+    if (rc) return rc;
+    rc = tarl_launch_rows(grid, threads, s, plan, f, fb, (int)Nmax, B, agent_features, A, a_bstride, time, out);
+    if (rc) return rc;
+    rc = tarl_launch_insert(epw_packed, s, (int)Nmax, B, N, fb, P, (const uint8_t*)f->sel8, agent_features, A, a_bstride,
+                            use_cong, time, ins_scratch, nullptr, reward ? reward + t * B : nullptr, out, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  return TARL_OK;
+}

@@ -1,6 +1,6 @@
 // noise.hip — the device noise of the production (Philox) path, written out for a listed set of environments.
 //
-// The rollout kernels (fused.hip, rollout_env.hip, sim.hip) draw their randomness themselves: a Gumbel value per in-edge
+// The rollout kernels (fused_*.hip, rollout_env.hip, sim.hip) draw their randomness themselves: a Gumbel value per in-edge
 // and frame for DirectionMPNN.aggregate's race (the reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139)
 // and a uniform per source node and frame for GraphDistribution.sample (src/reinforcement_learning.py:66). Both are pure
 // functions of (seed, counter, global environment id, index): tarl_noise_export evaluates exactly those functions — the

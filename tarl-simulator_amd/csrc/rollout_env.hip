@@ -1,6 +1,6 @@
 // rollout_env.hip — the whole T-frame rollout of one environment in ONE workgroup, hot records resident in LDS.
 //
-// Why a second implementation: the env-minor path (fused.hip) streams every per-(node, environment) record through HBM
+// Why a second implementation: the env-minor path (fused_*.hip) streams every per-(node, environment) record through HBM
 // four times per frame and pays four dependent launches per frame; with few environments it is bound by those launches'
 // latency (~10 us each), with many by HBM. A CDNA4 CU has 160 KB of LDS — enough for ALL hot state of one environment
 // of a few thousand roads (56 B per road: rec0, rec1, the post record, the chosen agent, SELECTED_ROAD, plus the static
@@ -11,7 +11,7 @@
 // shared by every environment and stay L2-resident.
 //
 // The arithmetic, the noise streams (Philox keys, counters, indices) and the order-sensitive rules are those of
-// fused.hip's kernels, so the two paths produce identical states, agents, actions, rewards and counts; the per-frame
+// the fused_*.hip kernels, so the two paths produce identical states, agents, actions, rewards and counts; the per-frame
 // log-prob is summed in the same 2^-32 fixed point (bit-identical, order-independent).
 //
 // Threads own CONTIGUOUS node ranges (consecutive nodes and consecutive CSC positions share Philox blocks), and therefore

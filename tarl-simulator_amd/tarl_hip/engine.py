@@ -62,7 +62,7 @@ class SimEngine:
         self.counts = torch.zeros((self.B, self.N), dtype=torch.float32, device=self.device)
         self.dtt = None
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)    # status word of the unfused kernels
-        # fused fast path (csrc/fused.hip): packed hot records + agent SoA mirroring x / agents
+        # fused fast path (csrc/fused_*.hip): packed hot records + agent SoA mirroring x / agents
         self.fs = (ops.FusedState(self.plan, self.B, self.A, self.device, self.Nmax, env_base=env_base,
                                   acc_slots=ops.ACC_SLOTS if acc_slots is None else acc_slots) if fused else None)
         self.sample_counter = 0

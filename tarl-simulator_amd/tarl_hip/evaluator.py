@@ -593,7 +593,7 @@ class VecEvaluator:
             v = int(self._flag_host[j])
             if v & _lib.FLAG_COUNT_AT_NMAX:
                 res.domain_exit, res.domain_exit_frames = True, (first, upto)
-                # frames queued behind the flagged block ran on a state outside the domain (memory-safe: csrc/fused.hip
+                # frames queued behind the flagged block ran on a state outside the domain (memory-safe: csrc/fused_rows.hip
                 # bounds every slot index by Nmax); the status word is re-armed so that the engine is usable after reset()
                 res.frames_run = upto
                 fs.flags.zero_()

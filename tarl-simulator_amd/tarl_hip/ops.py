@@ -20,13 +20,21 @@ EPS_GUMBEL = 1e-12   # src/direction_mpnn.py:136
 FUSED_LAYOUT = "v11"
 
 
-def frame_kernel_source_hash() -> str:
-    """sha256 (first 16 hex digits) of the frame kernels' sources, csrc/fused.hip + csrc/fused_common.h: a PMC traffic record
-    (tools/pmc_bench.py -> profiles/*.json) is only paired with kernel times measured on the very code it was taken on."""
+# the three frame kernels with their launch dispatch, and every csrc header they include: what a PMC traffic record measured.
+# (Pack, export, the action draw and the host loops are not in it; the packed layout is, through fused_common.h.)
+FRAME_KERNEL_SOURCES = ("fused_direction.hip", "fused_rows.hip", "fused_insert.hip",
+                        "fused_common.h", "fused_frame.h", "fused_choice.h", "tarl_common.h")
+
+
+def frame_kernel_source_hash(csrc: str | None = None) -> str:
+    """sha256 (first 16 hex digits) of FRAME_KERNEL_SOURCES, in that order: a PMC traffic record (tools/pmc_bench.py ->
+    profiles/*.json) is only paired with kernel times measured on the very code it was taken on. ``csrc``: another directory
+    holding the sources (default: this tree's csrc/)."""
     import hashlib
     h = hashlib.sha256()
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
-    for name in ("fused.hip", "fused_common.h"):
+    if csrc is None:
+        csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
+    for name in FRAME_KERNEL_SOURCES:
         with open(os.path.join(csrc, name), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

@@ -1,7 +1,7 @@
 """Exact checks of the live policy's action draw (imported by the replay tests; not a conftest).
 
 The device draws node i's action by inverse CDF over its fp32 threshold table (``eng.tables.thresholds``, plan CSR order,
-csrc/fused.hip ``k_fused_policy_prepare``): the drawn rank is the number of thresholds in the node's range at or below the
+csrc/fused_choice.hip ``k_policy_tables``): the drawn rank is the number of thresholds in the node's range at or below the
 uniform u (``choice_node``: an integer count; ``fused_choice_body`` / ``rollout_env.hip``: the first threshold above u —
 the same thing, the thresholds being non-decreasing). The oracle (``oracle/dist.GraphDist.sample``, the reference's
 ``s < cumsum`` rule) does the same with its own thresholds, computed on the CPU. The two tables are not bit-identical

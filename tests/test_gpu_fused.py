@@ -1,4 +1,4 @@
-"""GPU: the fused rollout frame (csrc/fused.hip: 3 launches, env-minor layout) reproduces, frame by frame, the unfused
+"""GPU: the fused rollout frame (csrc/fused_*.hip: 3 launches, env-minor layout) reproduces, frame by frame, the unfused
 kernels, the oracle and the reference's golden rollouts — state (after export), agents, actions, rewards, counts and
 masks bit-identical; log-probs to fp32 rounding (same terms, different fixed summation order; tolerance 1e-5 rel)."""
 import pytest
@@ -329,7 +329,7 @@ def test_rollout_launcher_equals_frame_loop(ops, monkeypatch, B, T, merge):
     assert float(rw1.abs().sum()) > 0 or T < 5
 
 
-@pytest.mark.parametrize("knob", ["TARL_INSERT_EPW=1", "TARL_INSERT_EPW=2", "TARL_INSERT_EPW=8", "TARL_INSERT_PAIR=0",
+@pytest.mark.parametrize("knob", ["TARL_INSERT_EPW=1", "TARL_INSERT_EPW=2", "TARL_INSERT_EPW=4", "TARL_INSERT_EPW=8", "TARL_INSERT_PAIR=0",
                                   "TARL_CHOICE_QUAD=0", "TARL_DIR_SIBLINGS=0", "TARL_ADDR32=0", "TARL_ROWS_SIBLINGS=0"])
 def test_rollout_launcher_developer_knobs(ops, knob):
     """The rollout's kernel variants that a developer knob selects once per process (environments per wave of the insert

@@ -1,4 +1,4 @@
-"""GPU: the accumulator banks of the fused frame (csrc/fused.hip: acc_lp / acc_n / acc_w, ``FusedState(acc_slots=...)``).
+"""GPU: the accumulator banks of the fused frame (csrc/fused_insert.hip: acc_lp / acc_n / acc_w, ``FusedState(acc_slots=...)``).
 
 The insert launch reads the log-prob banks only where a log-prob is asked for, re-arms a bank only where it does not
 already hold zero, and the number of banks is a constructor argument. None of this may change a result: the banks hold
@@ -100,7 +100,7 @@ def scenario_modes():
 
 
 def scenario_backlog():
-    """B = 9 (the second wave of the eight-environment kernel holds one environment), 180 agents per environment (fewer
+    """B = 9 (the last wave of the eight- and of the four-environment kernel holds one environment), 180 agents per environment (fewer
     than the whole list holds) all due in the first second, T = 16, for the default bank count and for 3 banks."""
     res = {}
     for acc in (None, 3):
@@ -183,22 +183,27 @@ def test_rollout_modes_agree(tmp_path):
 
 def test_long_backlog_falls_back_to_one_environment_body(tmp_path):
     """Every agent due in the first second: with eight environments per wave (TARL_INSERT_EPW=8) an environment's share of
-    the candidate list is 24 entries, and an environment that admits more than 24 agents in a frame had more than 24
-    candidates — it sat the packed part out and went through the one-environment body. Against the
+    the candidate list is 24 entries, with four (TARL_INSERT_EPW=4) 48, and an environment that admits more than its share
+    in a frame had more candidates than that — it sat the packed part out and went through the one-environment body.
+    (The 180 agents of an environment are all candidates of the first frame; on the CPU, from the origins and the roads'
+    capacities, that frame admits 132 or more of them in every environment under any of 2 000 random actions.) Against the
     one-wave-per-environment kernel (TARL_INSERT_EPW=1): identical, for 32 banks and for 3."""
-    res = children("backlog", tmp_path, "TARL_INSERT_EPW", ("8", "1"))
-    packed, single = res["8"], res["1"]
+    res = children("backlog", tmp_path, "TARL_INSERT_EPW", ("8", "4", "1"))
+    single = res["1"]
     departed = single["accNone.leg"][..., 0]                     # [T][B]
-    over = departed > INS_CAP // 8
-    n_env, n_frames = int(over.any(dim=0).sum()), int(over.sum())
-    print(f"{n_env} of {departed.size(1)} environments overflowed their share of the list ({n_frames} (frame, environment) "
-          f"pairs; most admitted in one frame: {int(departed.max())})")
-    assert n_env >= 2, "no wave had several environments over their share: the fall-back was not exercised"
-    assert bool(over[:, 8].any()), "the environment alone in the last wave did not overflow"
+    for epw in (8, 4):
+        over = departed > INS_CAP // epw
+        n_env, n_frames = int(over.any(dim=0).sum()), int(over.sum())
+        print(f"EPW {epw}: {n_env} of {departed.size(1)} environments overflowed their share of the list ({n_frames} (frame, "
+              f"environment) pairs; most admitted in one frame: {int(departed.max())})")
+        assert n_env >= 2, f"EPW {epw}: no wave had several environments over their share: the fall-back was not exercised"
+        assert bool(over[:, 8].any()), f"EPW {epw}: the environment alone in the last wave did not overflow"
     assert int(single["accNone.leg"][..., 1].sum()) > 0, "nobody was withdrawn"
-    assert packed.keys() == single.keys()
-    for k in single:
-        assert torch.equal(packed[k], single[k]), f"EPW 8 against EPW 1: {k} differs"
+    for epw in ("8", "4"):
+        packed = res[epw]
+        assert packed.keys() == single.keys()
+        for k in single:
+            assert torch.equal(packed[k], single[k]), f"EPW {epw} against EPW 1: {k} differs"
     for k in single:
         if k.startswith("accNone."):
             assert torch.equal(single["acc3." + k[8:]], single[k]), f"3 banks against 32: {k[8:]} differs"

@@ -1,7 +1,7 @@
 """GPU: the frame and rollout kernels on irregular road graphs (tests/irregular_graphs.py: hubs with up to nine, and with
 126, in- and out-edges, dead ends, feeder links, an edge list in no order). One comparison chain, bit-exact throughout
-(log-probs to fp32 rounding): CPU oracle -> per-op kernels (sim.hip, agents.hip) -> fused frame (fused.hip) -> one-call
-rollouts (fused.hip's launcher, rollout_env.hip's LDS-resident workgroup). tests/test_irregular_host.py shows on the CPU
+(log-probs to fp32 rounding): CPU oracle -> per-op kernels (sim.hip, agents.hip) -> fused frame (fused_*.hip) -> one-call
+rollouts (fused_rollout.hip's launcher, rollout_env.hip's LDS-resident workgroup). tests/test_irregular_host.py shows on the CPU
 that these inputs drive traffic through in-edges of in-rank >= 4 and out-edges of out-rank >= 4 hundreds of times, and that
 an implementation which dropped them, or broke ties the other way, would leave the oracle's trajectory.
 The MIXED tests come first in the file, the HUB126 tests last."""

@@ -2,22 +2,29 @@
 # Developer tool: register / spill / scratch figures of the frame kernels' bench instantiations, from the compiler's own
 # resource remarks (-Rpass-analysis=kernel-resource-usage) and the static instruction mix of the device ISA (--save-temps).
 # usage: tools/kernel_resources.sh [extra hipcc flags]   (run from anywhere; writes nothing into the tree)
+#        default SRC: the three frame-kernel files, fused_direction.hip fused_rows.hip fused_insert.hip
 #        SRC=occupancy.hip tools/kernel_resources.sh    every kernel of another file of csrc/, under its mangled name
 #        SRC=trips.hip tools/kernel_resources.sh        (the per-trip reductions: the figures of DESIGN 4.16)
 cd "$(dirname "$0")/../tarl-simulator_amd/csrc"
 T=$(mktemp -d)
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Rpass-analysis=kernel-resource-usage \
-  --save-temps=obj "$@" -c ${SRC:=fused.hip} -o $T/out.o 2> $T/remarks.txt
-python3 - $T $SRC <<'PY'
+FRAME="fused_direction.hip fused_rows.hip fused_insert.hip"
+for f in ${SRC:=$FRAME}; do
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Rpass-analysis=kernel-resource-usage \
+    --save-temps=obj "$@" -c $f -o $T/${f%.hip}.o 2>> $T/remarks.txt
+done
+python3 - $T "$SRC" "$FRAME" <<'PY'
 import re, sys, glob
 T = sys.argv[1]
 want = {"_Z12k_fused_rowsILi4ELb1ELb0ELb1EE": "k_fused_rows<4,SIB,rollout,O32>", "_Z17k_fused_directionILi4ELb1ELb1ELb1EE": "k_fused_direction<4,SIB,CNT,O32>",
         "_Z15k_fused_insert2ILi8ELb0EE": "k_fused_insert2<8,noLP>", "_Z15k_fused_insert2ILi8ELb1EE": "k_fused_insert2<8,LP>",
-        "_Z15k_fused_insert2ILi2ELb0EE": "k_fused_insert2<2,noLP>", "_Z14k_fused_insertILb0EE": "k_fused_insert<noLP>",
-        "_Z14k_fused_insertILb1EE": "k_fused_insert<LP>"}
+        "_Z15k_fused_insert2ILi2ELb0EE": "k_fused_insert2<2,noLP>",
+        "_Z15k_fused_insert2ILi2ELb1EE": "k_fused_insert2<2,LP>", "_Z15k_fused_insert2ILi4ELb0EE": "k_fused_insert2<4,noLP>",
+        "_Z15k_fused_insert2ILi4ELb1EE": "k_fused_insert2<4,LP>", "_Z14k_fused_insertILb0EE": "k_fused_insert<noLP>",
+        "_Z14k_fused_insertILb1EE": "k_fused_insert<LP>", "_Z21k_fused_insert_choiceILb0EE": "k_fused_insert_choice<noLP>",
+        "_Z21k_fused_insert_choiceILb1EE": "k_fused_insert_choice<LP>"}
 txt = open(T + "/remarks.txt").read()
 blocks = re.split(r"Function Name: ", txt)[1:]
-if sys.argv[2] != "fused.hip":
+if sys.argv[2] != sys.argv[3]:
     want = {b.split()[0]: b.split()[0][:36] for b in blocks}
 res = {}
 for b in blocks:
@@ -27,11 +34,10 @@ for b in blocks:
             g = lambda pat, b=b: (re.search(pat + r": (\d+)", b) or [None, "?"])[1]
             res[nice] = dict(sgpr=g("TotalSGPRs"), vgpr=g("VGPRs"), sspill=g("SGPRs Spill"), vspill=g("VGPRs Spill"), scratch=g(r"ScratchSize \[bytes/lane\]"),
                              occ=g(r"Occupancy \[waves/SIMD\]"), lds=g(r"LDS Size \[bytes/block\]"))
-asm = glob.glob(T + "/*gfx950*.s")
 mix = {}
-if asm:
+for asm in glob.glob(T + "/*gfx950*.s"):
     cur = None
-    for line in open(asm[0]):
+    for line in open(asm):
         m = re.match(r"^(_Z\w+):", line)
         if m:
             cur = next((nice for k, nice in want.items() if m.group(1).startswith(k)), None)

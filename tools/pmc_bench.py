@@ -76,7 +76,7 @@ def main():
     ap.add_argument("--note", type=str, default="")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
-    from tarl_hip.ops import FUSED_LAYOUT, frame_kernel_source_hash
+    from tarl_hip.ops import FRAME_KERNEL_SOURCES, FUSED_LAYOUT, frame_kernel_source_hash
     allc = per_kernel_all(a.dirs)
     if "FETCH_SIZE" not in allc or "WRITE_SIZE" not in allc:
         raise SystemExit("FETCH_SIZE and WRITE_SIZE passes are required")
@@ -97,7 +97,7 @@ def main():
                     "that fill 64-byte lines and tallies a partial-line store at 32 B per request. "
                     f"Mean over the last iteration's frames >= {a.first_frame}. " + a.note).strip(),
            "config": cfg, "layout": FUSED_LAYOUT, "source_sha16": frame_kernel_source_hash(),
-           "source_sha16_of": "tarl-simulator_amd/csrc/fused.hip + fused_common.h (bench.py ignores a record taken on other code)",
+           "source_sha16_of": "tarl-simulator_amd/csrc: " + " + ".join(FRAME_KERNEL_SOURCES) + " (bench.py ignores a record taken on other code)",
            "first_frame": a.first_frame, "kernels": {}}
     for k, per_iter in ROLLOUT_KERNELS.items():
         if k not in allc["FETCH_SIZE"] or k not in allc["WRITE_SIZE"]:
