@@ -164,10 +164,20 @@ struct FrameOut {
 #endif
 #define SLW TARL_SLW
 #define SLW_ALIGN (SLW == 8 ? 8 : 1)
-__device__ __forceinline__ void slot_store(float* w, float id, float arr, float dep) {
+// (F: float, or float in a named address space — fused_frame.h: gbase — which the accesses then keep)
 #if TARL_SLW == 8
-  reinterpret_cast<float4*>(w)[0] = make_float4(id, arr, dep, 0.0f);
-  reinterpret_cast<float4*>(w)[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+typedef float slot_f4 __attribute__((ext_vector_type(4)));   // 16-byte accesses of the 32-byte record, in F's address space
+template <class F> struct SlotVec { typedef slot_f4 type; };
+template <> struct SlotVec<const float> { typedef const slot_f4 type; };
+template <> struct SlotVec<__attribute__((address_space(1))) float> { typedef __attribute__((address_space(1))) slot_f4 type; };
+template <> struct SlotVec<const __attribute__((address_space(1))) float> { typedef const __attribute__((address_space(1))) slot_f4 type; };
+#endif
+template <class F>
+__device__ __forceinline__ void slot_store(F* w, float id, float arr, float dep) {
+#if TARL_SLW == 8
+  typename SlotVec<F>::type* w4 = (typename SlotVec<F>::type*)w;
+  w4[0] = slot_f4{id, arr, dep, 0.0f};
+  w4[1] = slot_f4{0.0f, 0.0f, 0.0f, 0.0f};
 #else
   w[0] = id;
   w[1] = arr;
@@ -177,9 +187,10 @@ __device__ __forceinline__ void slot_store(float* w, float id, float arr, float 
 struct SlotRec {
   float id, arr, dep;
 };
-__device__ __forceinline__ SlotRec slot_load(const float* r) {
+template <class F>
+__device__ __forceinline__ SlotRec slot_load(F* r) {
 #if TARL_SLW == 8
-  const float4 v = *reinterpret_cast<const float4*>(r);
+  const slot_f4 v = *(typename SlotVec<F>::type*)r;
   return SlotRec{v.x, v.y, v.z};
 #else
   return SlotRec{r[0], r[1], r[2]};

@@ -46,6 +46,8 @@
 // leaves the reference's defined domain (it raises IndexError one or two steps later): the kernels set
 // FLAG_COUNT_AT_NMAX in the device status word and the host raises when it reads it.
 #pragma once
+#include <type_traits>
+
 #include "fused_common.h"
 
 struct PlanOut {   // CSR by source
@@ -65,6 +67,66 @@ template <bool O32, class T>
 __device__ __forceinline__ const T& at32(const T* base, uint32_t idx) {
   if (O32) return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (size_t)(idx * (uint32_t)sizeof(T)));
   return base[idx];
+}
+
+// What is reached through the pointer table (FusedBufs in device memory, tarl_fused.bufs_dev). A pointer that was loaded from
+// memory carries no address space: an access through it is compiled as FLAT — no scalar-base form (the O32 addressing above
+// is lost on exactly these arrays), counted on vmcnt AND lgkmcnt, and free to return out of order, so the compiler waits
+// with a zero count while one is in flight. glob(p) names the element p points at as GLOBAL memory (loads, stores, the two
+// atomics the frame kernels use), gat<O32>(base, idx) is at32<> in that address space, gbase(base) the array's base for plain
+// indexing of scalar element types (slot records: slot_load / slot_store take either kind of pointer).
+#define TARL_GLOBAL __attribute__((address_space(1)))
+template <int BYTES> struct GWord;
+template <> struct GWord<1> { typedef uint8_t type; };
+template <> struct GWord<4> { typedef uint32_t type; };
+template <> struct GWord<8> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
+template <> struct GWord<16> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
+// GRef<T>: the proxy the three functions return (T const-qualified when the table's pointer is). It converts to T (a load) and
+// takes a T (a store: a compile error through a pointer to const). It is no value: `auto v = glob(p)` keeps the proxy —
+// write `T v = glob(p)` or glob(p).load() — and a proxy assigned to a proxy does not compile (say .load() on the right).
+template <class T>
+struct GRef {   // T as one machine word of its size: the HIP vector classes have no members for another address space
+  typedef typename std::remove_const<T>::type V;
+  typedef typename GWord<sizeof(T)>::type W;
+  W TARL_GLOBAL* p;
+  __device__ __forceinline__ V load() const { return __builtin_bit_cast(V, *p); }
+  __device__ __forceinline__ operator V() const { return load(); }
+  __device__ __forceinline__ void operator=(const V& v) const {
+    static_assert(!std::is_const<T>::value, "store through a pointer to const");
+    *p = __builtin_bit_cast(W, v);
+  }
+  void operator=(const GRef&) const = delete;
+  // atomicAdd / atomicOr of the HIP headers (relaxed, agent scope) on a global address: 4-byte T (the machine word IS a T)
+  __device__ __forceinline__ V atomic_add(V v) const {
+    static_assert(sizeof(T) == 4 && !std::is_const<T>::value, "atomic on a 4-byte element that is not const");
+    return __hip_atomic_fetch_add((V TARL_GLOBAL*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ V atomic_or(V v) const {
+    static_assert(sizeof(T) == 4 && !std::is_const<T>::value, "atomic on a 4-byte element that is not const");
+    return __hip_atomic_fetch_or((V TARL_GLOBAL*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+template <class T>
+__device__ __forceinline__ T TARL_GLOBAL* gbase(T* base) {
+  return (T TARL_GLOBAL*)base;
+}
+template <class T>
+__device__ __forceinline__ GRef<T> glob(T* p) {
+  return GRef<T>{(typename GRef<T>::W TARL_GLOBAL*)p};
+}
+template <bool O32, class T>
+__device__ __forceinline__ GRef<T> gat(T* base, uint32_t idx) {
+  typedef typename GRef<T>::W W;
+  if (O32) {
+    // The byte offset is made a value of its own in the block of the access (an empty asm: no instruction). Otherwise the
+    // zero-extended offset of a 4-byte element is shared with the post-word loads at the head of the kernel, reaches this block
+    // as a 64-bit register pair whose upper half the instruction selector cannot see to be zero, and the access is
+    // compiled with a 64-bit address per lane (v_lshl_add_u64) instead of `v_off, s[base]`.
+    uint32_t off = idx * (uint32_t)sizeof(T);
+    asm("" : "+v"(off));
+    return GRef<T>{(W TARL_GLOBAL*)((const char TARL_GLOBAL*)base + (size_t)off)};
+  }
+  return GRef<T>{(W TARL_GLOBAL*)base + idx};
 }
 
 // the choice role of the merged insert + choice launch (fused_insert.hip: k_fused_insert_choice; built by the rollout loop)

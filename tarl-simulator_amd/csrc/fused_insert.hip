@@ -21,9 +21,11 @@ __device__ __forceinline__ bool fused_target(const FusedBufs& fb, PlanOut P, con
   if (origin < 0 || origin >= N) return false;
   const int64_t orow = (int64_t)origin * B + b;
   const uint32_t c = sel8[orow] & 0x7Fu;
-  const long long r = (long long)(c == SEL_RAW ? fb.sel[orow] : (float)P.out_dst[P.out_ptr[origin] + (int32_t)c]);
+  const long long r = (long long)(c == SEL_RAW ? (float)glob(&fb.sel[orow]) : (float)P.out_dst[P.out_ptr[origin] + (int32_t)c]);
   if (r < 0 || r >= N) return false;
-  const long long room = (long long)(fb.st0[r].x - TARL_CONGESTION_FILE - (float)(fb.hdp[r * B + b].x & HD_CNT));
+  const float maxn = glob(&fb.st0[r].x);
+  const uint32_t hd = glob(&fb.hdp[r * B + b].x);
+  const long long room = (long long)(maxn - TARL_CONGESTION_FILE - (float)(hd & HD_CNT));
   *road = (int32_t)r;
   *cap = (int32_t)(room > 0x7fffffff ? 0x7fffffff : room);
   return room > 0;
@@ -40,16 +42,17 @@ __device__ __forceinline__ bool fused_target_words(const FusedBufs& fb, PlanOut 
   const int64_t orow = (int64_t)origin * B + b;
   const uint32_t c = sel8[orow] & 0x7Fu;
   const int32_t* o4 = fb.nodes[origin].out4;
-  const int32_t t0 = o4[0], t1 = o4[1], t2 = o4[2], t3 = o4[3];
+  const int32_t t0 = glob(o4), t1 = glob(o4 + 1), t2 = glob(o4 + 2), t3 = glob(o4 + 3);
   long long r;
   if (c < 4u)
     r = (long long)(float)(c == 0u ? t0 : (c == 1u ? t1 : (c == 2u ? t2 : t3)));
   else
-    r = (long long)(c == SEL_RAW ? fb.sel[orow] : (float)P.out_dst[P.out_ptr[origin] + (int32_t)c]);
+    r = (long long)(c == SEL_RAW ? (float)glob(&fb.sel[orow]) : (float)P.out_dst[P.out_ptr[origin] + (int32_t)c]);
   if (r < 0 || r >= N) return false;
-  const uint32_t hd = fb.hdp[r * B + b].x;
-  *tl_out = fb.tl[r * B + b];
-  const long long room = (long long)(fb.st0[r].x - TARL_CONGESTION_FILE - (float)(hd & HD_CNT));
+  const uint32_t hd = glob(&fb.hdp[r * B + b].x);
+  *tl_out = glob(&fb.tl[r * B + b]);
+  const float maxn = glob(&fb.st0[r].x);
+  const long long room = (long long)(maxn - TARL_CONGESTION_FILE - (float)(hd & HD_CNT));
   *road = (int32_t)r;
   *hd_out = hd;
   return room > 0;
@@ -70,8 +73,9 @@ struct InsLds {
 // origin, agent} record and the "already inserted" byte.
 __device__ __forceinline__ void insert_window_load(const FusedBufs& fb, int64_t b, int64_t A, int64_t k, float t, bool* due,
                                                    bool* waiting, int32_t* origin, int32_t* a) {
-  const uint4 w = fb.a_win[b * A + k];
-  *waiting = fb.a_ins[b * A + k] == 0;
+  const uint4 w = glob(&fb.a_win[b * A + k]);
+  const uint8_t ins = glob(&fb.a_ins[b * A + k]);
+  *waiting = ins == 0;
   *due = __uint_as_float(w.x) <= t;
   *origin = (int32_t)w.y;
   *a = (int32_t)w.z;
@@ -114,7 +118,7 @@ __device__ __forceinline__ void insert_admit_list(const InsLds& L, int base, int
       rank += (same && L.un_agent[base + k] < a) ? 1 : 0;
     }
     const int64_t rrow = (int64_t)r * B + b;
-    const float4 str = fb.st0[r];
+    const float4 str = glob(&fb.st0[r]);
     const uint32_t hd = L.un_hd[base + idx];
     const uint32_t n0i = hd & HD_CNT;
     const float n0 = (float)n0i;
@@ -126,20 +130,20 @@ __device__ __forceinline__ void insert_admit_list(const InsLds& L, int base, int
       const float tt = (t_cong != t_cong) ? t_cong : fmaxf(str.y, t_cong);
       const int hoff = tl_hoff(L.un_tl[base + idx]);
       if (slot >= 0 && slot < Nmax) {
-        slot_store(fb.slots + rrow * fb.lds + SLW * phys(hoff, (int)slot, Nmax), (float)a, t, t + tt);
+        slot_store(gbase(fb.slots) + rrow * fb.lds + SLW * phys(hoff, (int)slot, Nmax), (float)a, t, t + tt);
       }
       agb[(int64_t)a * AG_COLS + AG_ON_WAY] = 1.0f;
-      fb.a_status[b * A + a] = 1;
-      fb.a_ins[b * A + L.un_k[base + idx]] = 1;
-      if (rank == m - 1) fb.tl[rrow] = tl_word((uint32_t)a, hoff, TLF_AUTH);  // new tail; gc8 authoritative from here on
+      glob(&fb.a_status[b * A + a]) = (uint8_t)1;
+      glob(&fb.a_ins[b * A + L.un_k[base + idx]]) = (uint8_t)1;
+      if (rank == m - 1) glob(&fb.tl[rrow]) = tl_word((uint32_t)a, hoff, TLF_AUTH);  // new tail; gc8 authoritative from here on
       if (rank == 0) {
         const uint32_t cnt = n0i + (uint32_t)m;      // n0 + m <= MAX - 3 < 255
         if (n0i == 0u) {   // new head: id + departure, arrival
-          fb.hdp[rrow] = make_uint2(((uint32_t)a << 8) | cnt | (hd & HD_DIRTY), __float_as_uint(t + tt));
+          glob(&fb.hdp[rrow]) = make_uint2(((uint32_t)a << 8) | cnt | (hd & HD_DIRTY), __float_as_uint(t + tt));
         } else {
-          fb.hdp[rrow].x = hd + (uint32_t)m;
+          glob(&fb.hdp[rrow].x) = hd + (uint32_t)m;
         }
-        if (out.write_gc || b < out.m_env) fb.gc8[rrow] = (uint8_t)r1_code(-1);   // the arrivals overwrote a pending garbage slot: none pending now
+        if (out.write_gc || b < out.m_env) glob(&fb.gc8[rrow]) = (uint8_t)r1_code(-1);   // the arrivals overwrote a pending garbage slot: none pending now
         if (out.counts8) out.counts8[rrow] = (uint8_t)cnt;
         if (out.countsf) out.countsf[rrow] = (float)cnt;
         atomicAdd(adm, (int32_t)m);
@@ -176,16 +180,16 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
   float nf = 0.0f, wf = 0.0f;
   if (wid == 0) {
     for (int64_t sl_ = lane; sl_ < fb.acc_slots; sl_ += 64) {
-      const float n = fb.acc_n[sl_ * B + b], w = fb.acc_w[sl_ * B + b];
+      const float n = glob(&fb.acc_n[sl_ * B + b]), w = glob(&fb.acc_w[sl_ * B + b]);
       long long v = 0;
-      if constexpr (LP) v = fb.acc_lp[sl_ * B + b];
+      if constexpr (LP) v = glob(&fb.acc_lp[sl_ * B + b]);
       nf += n;
       wf += w;
       lpf += v;
-      if (__float_as_uint(n) != 0u) fb.acc_n[sl_ * B + b] = 0.0f;
-      if (__float_as_uint(w) != 0u) fb.acc_w[sl_ * B + b] = 0.0f;
+      if (__float_as_uint(n) != 0u) glob(&fb.acc_n[sl_ * B + b]) = 0.0f;
+      if (__float_as_uint(w) != 0u) glob(&fb.acc_w[sl_ * B + b]) = 0.0f;
       if constexpr (LP) {
-        if (v != 0) fb.acc_lp[sl_ * B + b] = 0;
+        if (v != 0) glob(&fb.acc_lp[sl_ * B + b]) = 0ll;
       }
     }
   }
@@ -193,9 +197,9 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
   if (fb.a_order) {
     // Windowed scan: agents sorted by departure time; everything before cur_lo is known not to be waiting any more and
     // everything after the first not-yet-due entry is not due either, so a frame normally looks at one chunk.
-    const int32_t* ord = fb.a_order + b * A;
-    const float* dsort = fb.a_dep_sorted + b * A;
-    const int32_t lo = fb.cur_lo[b];
+    const auto ord = gbase(fb.a_order) + b * A;
+    const auto dsort = gbase(fb.a_dep_sorted) + b * A;
+    const int32_t lo = glob(&fb.cur_lo[b]);
     if (tid == 0) L.lo = 0x7fffffff;
     __syncthreads();
     for (int64_t k0 = lo; k0 < A; k0 += INSB) {
@@ -209,8 +213,8 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
         } else {            // sequential departures; per-agent arrays only for entries that are due
           due = dsort[k] <= t;
           a = due ? ord[k] : 0;
-          waiting = due && fb.a_status[b * A + a] == 0;
-          origin = waiting ? fb.a_origin[b * A + a] : 0;
+          waiting = due && gbase(fb.a_status)[b * A + a] == 0;
+          origin = waiting ? gbase(fb.a_origin)[b * A + a] : 0;
         }
         notdue = !due;
         if (!due) {
@@ -232,7 +236,7 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
       if (__syncthreads_or(notdue ? 1 : 0)) break;   // sorted by departure: nothing beyond this chunk is due
     }
     __syncthreads();
-    if (tid == 0) fb.cur_lo[b] = L.lo == 0x7fffffff ? (int32_t)A : L.lo;
+    if (tid == 0) glob(&fb.cur_lo[b]) = L.lo == 0x7fffffff ? (int32_t)A : L.lo;
   } else {
     for (int64_t a0 = tid; a0 < A; a0 += 4 * INSB) {  // 4 independent (status, departure) loads in flight per thread
       uint8_t stt[4];
@@ -240,15 +244,15 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
   #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int64_t a = a0 + (int64_t)j * INSB;
-        stt[j] = a < A ? fb.a_status[b * A + a] : (uint8_t)1;
-        dp[j] = a < A ? fb.a_dep[b * A + a] : 0.0f;
+        stt[j] = a < A ? gbase(fb.a_status)[b * A + a] : (uint8_t)1;
+        dp[j] = a < A ? gbase(fb.a_dep)[b * A + a] : 0.0f;
       }
   #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (stt[j] == 0 && dp[j] <= t) {
           const int64_t a = a0 + (int64_t)j * INSB;
           int32_t road = 0, cap = 0;
-          if (fused_target(fb, P, sel8, b, B, N, fb.a_origin[b * A + a], &road, &cap)) {
+          if (fused_target(fb, P, sel8, b, B, N, gbase(fb.a_origin)[b * A + a], &road, &cap)) {
             const int32_t pos = atomicAdd(&L.cnt, 1);
             if (pos < INS_CAP) {
               L.un_agent[pos] = (int32_t)a;
@@ -282,8 +286,8 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
       const int64_t a = a0 + tid;
       bool cnd = false;
       int32_t road = 0, cap = 0;
-      if (a < A && fb.a_status[b * A + a] == 0 && fb.a_dep[b * A + a] <= t)
-        cnd = fused_target(fb, P, sel8, b, B, N, fb.a_origin[b * A + a], &road, &cap);
+      if (a < A && gbase(fb.a_status)[b * A + a] == 0 && gbase(fb.a_dep)[b * A + a] <= t)
+        cnd = fused_target(fb, P, sel8, b, B, N, gbase(fb.a_origin)[b * A + a], &road, &cap);
       const unsigned long long bal = __ballot(cnd);
       const int lane_off = __popcll(bal & ((1ull << lane) - 1ull));
       if (lane == 0) L.wave[wid] = __popcll(bal);
@@ -319,8 +323,8 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
       rank += (same && k < idx) ? 1 : 0;
     }
     const int64_t rrow = (int64_t)r * B + b;
-    const float4 str = fb.st0[r];
-    const uint32_t hd = fb.hdp[rrow].x;
+    const float4 str = glob(&fb.st0[r]);
+    const uint32_t hd = glob(&fb.hdp[rrow].x);
     const uint32_t n0i = hd & HD_CNT;
     const float n0 = (float)n0i;
     const long long cap = (long long)(str.x - TARL_CONGESTION_FILE - n0);
@@ -330,17 +334,17 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
       const long long slot = (long long)n0i + rank;
       const float t_cong = use_cong ? str.w / (str.x + 10.0f - n0) : 0.0f;
       const float tt = (t_cong != t_cong) ? t_cong : fmaxf(str.y, t_cong);
-      const int hoff = tl_hoff(fb.tl[rrow]);   // the tail word's owner below rewrites it with the same offset
+      const int hoff = tl_hoff(glob(&fb.tl[rrow]));   // the tail word's owner below rewrites it with the same offset
       if (slot >= 0 && slot < Nmax) {
-        slot_store(fb.slots + rrow * fb.lds + SLW * phys(hoff, (int)slot, Nmax), (float)a, t, t + tt);
+        slot_store(gbase(fb.slots) + rrow * fb.lds + SLW * phys(hoff, (int)slot, Nmax), (float)a, t, t + tt);
       }
       agb[(int64_t)a * AG_COLS + AG_ON_WAY] = 1.0f;
-      fb.a_status[b * A + a] = 1;
-      if (fb.a_ins) fb.a_ins[b * A + fb.a_rank[b * A + a]] = 1;
+      glob(&fb.a_status[b * A + a]) = (uint8_t)1;
+      if (fb.a_ins) gbase(fb.a_ins)[b * A + gbase(fb.a_rank)[b * A + a]] = 1;
       if (rank == 0 && n0i == 0u) {   // new head: id + departure (count byte unchanged), arrival
-        fb.hdp[rrow] = make_uint2(((uint32_t)a << 8) | n0i | (hd & HD_DIRTY), __float_as_uint(t + tt));
+        glob(&fb.hdp[rrow]) = make_uint2(((uint32_t)a << 8) | n0i | (hd & HD_DIRTY), __float_as_uint(t + tt));
       }
-      if (rank == m - 1) fb.tl[rrow] = tl_word((uint32_t)a, hoff, TLF_AUTH);  // new tail; gc8 authoritative from here on
+      if (rank == m - 1) glob(&fb.tl[rrow]) = tl_word((uint32_t)a, hoff, TLF_AUTH);  // new tail; gc8 authoritative from here on
       if (rank == 0) commit = (int32_t)m;
     }
     cand_agent[idx] = commit;
@@ -352,9 +356,9 @@ __device__ __forceinline__ void fused_insert_body(InsLds& L, int64_t b, int Nmax
     const int32_t cmt = cand_agent[idx];
     if (cmt > 0) {
       const int64_t rrow = (int64_t)cand_road[idx] * B + b;
-      if (out.write_gc || b < out.m_env) fb.gc8[rrow] = (uint8_t)r1_code(-1);
-      const uint32_t hd = fb.hdp[rrow].x + (uint32_t)cmt;   // count byte: n0 + cmt <= MAX - 3 < 255
-      fb.hdp[rrow].x = hd;
+      if (out.write_gc || b < out.m_env) glob(&fb.gc8[rrow]) = (uint8_t)r1_code(-1);
+      const uint32_t hd = glob(&fb.hdp[rrow].x) + (uint32_t)cmt;   // count byte: n0 + cmt <= MAX - 3 < 255
+      glob(&fb.hdp[rrow].x) = hd;
       if (out.counts8) out.counts8[rrow] = (uint8_t)(hd & HD_CNT);
       if (out.countsf) out.countsf[rrow] = (float)(hd & HD_CNT);
       atomicAdd(&L.adm, cmt);
@@ -438,19 +442,19 @@ __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int
     int it = 0;
     for (int64_t sl_ = l; sl_ < fb.acc_slots; sl_ += LPE, ++it) {
       const uint32_t bit = it < 32 ? (1u << it) : 0u;
-      const float n = fb.acc_n[sl_ * B + b], w = fb.acc_w[sl_ * B + b];
+      const float n = glob(&fb.acc_n[sl_ * B + b]), w = glob(&fb.acc_w[sl_ * B + b]);
       nf += n;
       wf += w;
       nz_n |= __float_as_uint(n) != 0u ? bit : 0u;
       nz_w |= __float_as_uint(w) != 0u ? bit : 0u;
       if constexpr (LP) {
-        const long long v = fb.acc_lp[sl_ * B + b];
+        const long long v = glob(&fb.acc_lp[sl_ * B + b]);
         lpf += v;
         nz_lp |= v != 0 ? bit : 0u;
       }
     }
   }
-  const int32_t lo = live ? fb.cur_lo[b] : 0;
+  const int32_t lo = live ? gbase(fb.cur_lo)[b] : 0;
   __syncthreads();
   // phase 1: the departure window, LPE entries per environment and step
   bool done = !live;
@@ -488,16 +492,16 @@ __global__ __launch_bounds__(INSB) void k_fused_insert2(int Nmax, int64_t B, int
   bool over = false;
 #pragma unroll
   for (int e = 0; e < EPW; ++e) over = over || (L.cnt2[e] > INS_CAP2);
-  if (live && l == 0) fb.cur_lo[b] = L.lo2[h] == 0x7fffffff ? (int32_t)A : L.lo2[h];
+  if (live && l == 0) glob(&fb.cur_lo[b]) = L.lo2[h] == 0x7fffffff ? (int32_t)A : L.lo2[h];
   const bool mine = live && L.cnt2[h] <= INS_CAP2;
   if (mine) {
     int it = 0;
     for (int64_t sl_ = l; sl_ < fb.acc_slots; sl_ += LPE, ++it) {   // the banks are consumed: re-arm what is not zero
       const uint32_t bit = it < 32 ? (1u << it) : 0u;
-      if (bit == 0u || (nz_n & bit)) fb.acc_n[sl_ * B + b] = 0.0f;
-      if (bit == 0u || (nz_w & bit)) fb.acc_w[sl_ * B + b] = 0.0f;
+      if (bit == 0u || (nz_n & bit)) glob(&fb.acc_n[sl_ * B + b]) = 0.0f;
+      if (bit == 0u || (nz_w & bit)) glob(&fb.acc_w[sl_ * B + b]) = 0.0f;
       if constexpr (LP) {
-        if (bit == 0u || (nz_lp & bit)) fb.acc_lp[sl_ * B + b] = 0;
+        if (bit == 0u || (nz_lp & bit)) glob(&fb.acc_lp[sl_ * B + b]) = 0ll;
       }
     }
     // phase 2: admission straight from the list, by rank among the candidates of the same road

@@ -41,14 +41,15 @@ __device__ __forceinline__ bool row_phase_a(uint32_t i, uint32_t b, const RowSta
     for (int q = 0; q < 4; ++q)
       pop = pop | ((q < nr.out_deg) & up & ((pj4[q] & PF_NONEMPTY) != 0u) & ((pj4[q] >> 8) == head));
     for (int32_t q = 4; q < nr.out_deg; ++q) {   // out-degree above four: the rest one by one
-      const uint32_t pj = at32<O32>(post, (uint32_t)fb.out_pad[nr.out0 + q] * B + b);
+      const int32_t j = glob(&fb.out_pad[nr.out0 + q]);
+      const uint32_t pj = at32<O32>(post, (uint32_t)j * B + b);
       pop = pop | (up & ((pj & PF_NONEMPTY) != 0u) & ((pj >> 8) == head));
     }
   }
   const int q = (int)n0i;
   const bool lazy = (who == 0u) & (q < Nmax - 1);
   const uint32_t ni = n0i + arrived;   // count after the Direction update
-  if ((int)ni >= Nmax) atomicOr(fb.flags, FLAG_COUNT_AT_NMAX);
+  if ((int)ni >= Nmax) glob(fb.flags).atomic_or(FLAG_COUNT_AT_NMAX);
   const uint32_t head_id = (n0i == 0u) ? who : head_id0;
   // an empty row's head is this frame's garbage triple (0, t, t + tt): its departure needs the division only there
   const float head_dep = (n0i == 0u) ? t + nr.tt0 : __uint_as_float(hp.y);
@@ -71,12 +72,12 @@ __device__ __forceinline__ bool row_phase_a(uint32_t i, uint32_t b, const RowSta
   // Direction gather's tests need an agent in the row or MAX_NUMBER_OF_AGENT <= 3 (rows that small keep the eager word),
   // export and delta_travel_time derive it from the clock. The tail word changes only when its flag has to go.
   if (n0i == 0u && nr.maxn <= TARL_CONGESTION_FILE)
-    at32<O32>(fb.hdp, row) = make_uint2((head_id << 8) | ni | (hp.x & HD_DIRTY), __float_as_uint(head_dep));
+    gat<O32>(fb.hdp, row) = make_uint2((head_id << 8) | ni | (hp.x & HD_DIRTY), __float_as_uint(head_dep));
   if (tlw & TLF_AUTH) {
-    at32<O32>(fb.tl, row) = tlw & ~TLF_AUTH;      // tail and ring offset stay
+    gat<O32>(fb.tl, row) = tlw & ~TLF_AUTH;      // tail and ring offset stay
     // ... and the post word's mirror of the flag goes with it (other workgroups may be gathering this word for their
     // Response test right now: they look at PF_NONEMPTY and the tail id, which do not change)
-    at32<O32>(fb.post, row) = pa & ~PF_TLAUTH;
+    gat<O32>(fb.post, row) = pa & ~PF_TLAUTH;
   }
   if (FAPI && out.countsf) __builtin_nontemporal_store((float)ni, &out.countsf[row]);
   if (FAPI && out.popped) out.popped[(int64_t)b * N + i] = 0;
@@ -125,7 +126,7 @@ __device__ __forceinline__ float2 row_phase_b(uint32_t i, uint32_t b, bool pop, 
   float head_dep = (n0i == 0u) ? dep_new : __uint_as_float(hp.y);
   {
     // The FIFO is a ring buffer: logical slot s lives at physical slot (hoff + s) mod Nmax.
-    float* sl = fb.slots + (int64_t)row * fb.lds;  // slot s = sl[3s .. 3s+2] = {id, arrival, departure}
+    const auto sl = gbase(fb.slots) + (int64_t)row * fb.lds;  // slot s = sl[3s .. 3s+2] = {id, arrival, departure}
     int hoff = tl_hoff(tlw);     // (the event byte gc8 is write-only here: no load sits between the row and its slots)
     if (!lazy && q < Nmax) {
       slot_store(sl + SLW * phys(hoff, q, Nmax), (float)who, t, dep_new);
@@ -163,7 +164,8 @@ __device__ __forceinline__ float2 row_phase_b(uint32_t i, uint32_t b, bool pop, 
         const long long id = (long long)idf;
         if (id < 0 || id >= A) break;
         if (!(depf <= t)) break;  // tested first: most heads are still travelling, and the lookup below is a gather
-        const long long dest = (long long)fb.a_dest[(int64_t)b * A + id];
+        const int32_t dest32 = glob(&fb.a_dest[(int64_t)b * A + id]);
+        const long long dest = (long long)dest32;
         if (w0 < 0) {
           w0 = 0;
           if (road >= 0 && road < N) {
@@ -178,7 +180,7 @@ __device__ __forceinline__ float2 row_phase_b(uint32_t i, uint32_t b, bool pop, 
         a[AG_DONE] = 1.0f;
         a[AG_ON_WAY] = 0.0f;
         a[AG_ARR] = t;
-        fb.a_status[(int64_t)b * A + id] = 2;
+        glob(&fb.a_status[(int64_t)b * A + id]) = (uint8_t)2;
         ++c;
       }
     }
@@ -209,9 +211,9 @@ __device__ __forceinline__ float2 row_phase_b(uint32_t i, uint32_t b, bool pop, 
       else if (n >= Nmax)
         tail_id = (n == Nmax) ? (uint32_t)(long long)sl[SLW * phys(hoff, n - 1, Nmax)] : 0u;
     }
-    fb.hdp[row] = make_uint2((head_id << 8) | (uint32_t)n | (exact ? HD_DIRTY : 0u), __float_as_uint(head_dep));
-    fb.tl[row] = tl_word(tail_id, hoff, TLF_AUTH);
-    if (out.write_gc || b < (uint32_t)out.m_env) fb.gc8[row] = (uint8_t)r1_code(lazy ? q : -1);
+    glob(&fb.hdp[row]) = make_uint2((head_id << 8) | (uint32_t)n | (exact ? HD_DIRTY : 0u), __float_as_uint(head_dep));
+    glob(&fb.tl[row]) = tl_word(tail_id, hoff, TLF_AUTH);
+    if (out.write_gc || b < (uint32_t)out.m_env) glob(&fb.gc8[row]) = (uint8_t)r1_code(lazy ? q : -1);
     // per-node count before insertion (the insert kernel adds this frame's arrivals)
     if (out.counts8 && c > 0) out.counts8[row] = (uint8_t)n;      // (phase A stored ni - pop for this row already)
     if (FAPI && out.countsf) out.countsf[row] = (float)n;
@@ -297,10 +299,11 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     uint32_t pa[NCH], tlw[NCH], pj[NCH][4];
     uint2 hp[NCH];
     uint32_t ovf = 0u;       // bit r: row r found the event list full; bit 4 + r: its pop flag
+    // (the rows' own post words in front of the downstream ones: the second round below needs the former alone)
+#pragma unroll
+    for (int r = 0; r < NCH; ++r) pa[r] = at32<O32>(post, (uint32_t)ri[r] * B + b);
 #pragma unroll
     for (int r = 0; r < NCH; ++r) {
-      const uint32_t row = (uint32_t)ri[r] * B + b;
-      pa[r] = at32<O32>(post, row);
       if (SIB) {
         if (r == 0) {
           const int32_t* od = rchunks[blockIdx.y].out4;
@@ -326,8 +329,8 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
       hp[r] = make_uint2(0u, 0u);
       tlw[r] = 0u;
       if (Nmax < 2 || (pa[r] & (PF_ARRIVED | PF_NONEMPTY | PF_TLAUTH))) {   // (a one-slot FIFO has no lazy garbage slot)
-        hp[r] = at32<O32>(fb.hdp, row);
-        tlw[r] = at32<O32>(fb.tl, row);
+        hp[r] = gat<O32>(fb.hdp, row);
+        tlw[r] = gat<O32>(fb.tl, row);
       }
     }
 #pragma unroll
@@ -369,14 +372,14 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const float2 nc = row_phase_b<FAPI>((uint32_t)i_r, b, ((ovf >> (4 + r)) & 1u) != 0u, pa_r, hp_r, tl_r, nodes[i_r], out_ptr,
                                       out_dst, Nmax, B, N, fb, ag, A, a_bstride, t, out);
         nsum -= nc.y;
-        if (nc.y != 0.0f) atomicAdd(&fb.acc_w[(int64_t)(blockIdx.y % (unsigned)fb.acc_slots) * B + b], nc.y);
+        if (nc.y != 0.0f) glob(&fb.acc_w[(int64_t)(blockIdx.y % (unsigned)fb.acc_slots) * B + b]).atomic_add(nc.y);
       }
     }
   }
   // idle rows' share of the environment's count sum goes out now: a wave without a list entry is done after the barrier
   // (its slots go to the next workgroup while the event path, a chain of dependent loads a few lanes wide, runs on)
   const int64_t bank0 = (int64_t)(blockIdx.y % (unsigned)fb.acc_slots) * B;
-  if (valid && nsum != 0.0f) atomicAdd(&fb.acc_n[bank0 + b], nsum);
+  if (valid && nsum != 0.0f) glob(&fb.acc_n[bank0 + b]).atomic_add(nsum);
   __syncthreads();
   const int32_t cnt = s_cnt < EV_CAP ? s_cnt : EV_CAP;
   for (int32_t idx = threadIdx.x; idx < cnt; idx += blockDim.x) {
@@ -390,8 +393,8 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     const float2 nc = row_phase_b<FAPI>((uint32_t)i2, b2, (item & 256u) != 0u, wd.x, make_uint2(wd.y, wd.z), wd.w, nodes[i2],
                                   out_ptr, out_dst, Nmax, B, N, fb, ag, A, a_bstride, t, out);
     if (nc.y != 0.0f) {      // withdrawn agents leave the count sum (small integers: exact in fp32 in any order)
-      atomicAdd(&fb.acc_n[bank0 + b2], -nc.y);
-      atomicAdd(&fb.acc_w[bank0 + b2], nc.y);
+      glob(&fb.acc_n[bank0 + b2]).atomic_add(-nc.y);
+      glob(&fb.acc_w[bank0 + b2]).atomic_add(nc.y);
     }
   }
 }

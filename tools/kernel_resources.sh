@@ -42,7 +42,7 @@ for asm in glob.glob(T + "/*gfx950*.s"):
         if m:
             cur = next((nice for k, nice in want.items() if m.group(1).startswith(k)), None)
             if cur:
-                mix[cur] = dict(valu=0, salu=0, vmem=0, smem=0, lds=0, lanespill=0)
+                mix[cur] = dict(valu=0, salu=0, vmem=0, smem=0, lds=0, lanespill=0, flat=0)
             continue
         if cur is None:
             continue
@@ -60,13 +60,15 @@ for asm in glob.glob(T + "/*gfx950*.s"):
             mix[cur]["salu"] += 1
         elif op.startswith("global_") or op.startswith("buffer_") or op.startswith("flat_") or op.startswith("scratch_"):
             mix[cur]["vmem"] += 1
+            if op.startswith("flat_"):      # an access without an address space (a pointer that was loaded from memory)
+                mix[cur]["flat"] += 1
         elif op.startswith("ds_"):
             mix[cur]["lds"] += 1
-print(f"{'kernel':36s} {'SGPR':>4s} {'VGPR':>4s} {'sSpill':>6s} {'vSpill':>6s} {'scratch':>7s} {'occ':>3s} {'LDS':>6s} | static: {'VALU':>5s} {'SALU':>5s} {'SMEM':>4s} {'VMEM':>4s} {'DS':>3s} {'v_read/writelane':>16s}")
+print(f"{'kernel':36s} {'SGPR':>4s} {'VGPR':>4s} {'sSpill':>6s} {'vSpill':>6s} {'scratch':>7s} {'occ':>3s} {'LDS':>6s} | static: {'VALU':>5s} {'SALU':>5s} {'SMEM':>4s} {'VMEM':>4s} {'FLAT':>4s} {'DS':>3s} {'v_read/writelane':>16s}")
 for nice in want.values():
     if nice in res:
         r, m = res[nice], mix.get(nice, {})
         print(f"{nice:36s} {r['sgpr']:>4s} {r['vgpr']:>4s} {r['sspill']:>6s} {r['vspill']:>6s} {r['scratch']:>7s} {r['occ']:>3s} {r['lds']:>6s} | "
-              f"        {m.get('valu', 0):5d} {m.get('salu', 0):5d} {m.get('smem', 0):4d} {m.get('vmem', 0):4d} {m.get('lds', 0):3d} {m.get('lanespill', 0):16d}")
+              f"        {m.get('valu', 0):5d} {m.get('salu', 0):5d} {m.get('smem', 0):4d} {m.get('vmem', 0):4d} {m.get('flat', 0):4d} {m.get('lds', 0):3d} {m.get('lanespill', 0):16d}")
 PY
 rm -rf $T
