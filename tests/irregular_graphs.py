@@ -1,7 +1,10 @@
 """Irregular road graphs for the simulation-step tests: dual graphs of link lists with hubs (in-degree and out-degree far
 beyond the four of a torus), dead ends and feeder links, a degree-agnostic random state, a census of which branches a run
 of the CPU oracle reaches, and oracle replays with one deliberate restriction each (what a kernel that mishandles long
-in-lists / out-lists or the tie order would compute). Plain module: no fixtures, nothing here needs a GPU.
+in-lists / out-lists or the tie order would compute). Two further graphs keep the sibling structure of a torus — rows 4c ..
+4c+3 leave one intersection and share their upstream rows, every road has out-edges — at in-degrees 0 .. 9 and out-degrees
+1 .. 9: the sibling Direction gather and the quad action draw off the torus. Plain module: no fixtures, nothing here needs
+a GPU.
 
 Ranks: the in-rank of a dual edge is its position among the edges with the same destination in ascending edge id (the
 plan's CSC order); the out-rank its position among the edges with the same source (the plan's CSR order). The fused
@@ -73,12 +76,73 @@ def road_network(links, seed, shuffle=True) -> synth.SynthNetwork:
     return net
 
 
+def sibling_links(out_degrees, in_degrees, gen):
+    """Directed links numbered by tail intersection — the roads that leave one intersection are consecutive — with the
+    heads dealt to them by a seeded shuffle of every intersection's in-degree worth of heads, redrawn until no link is a
+    self-loop. With out-degrees that are multiples of four the four roads 4c .. 4c+3 of the dual graph leave the same
+    intersection: siblings, which share their whole in-list."""
+    assert sum(out_degrees) == sum(in_degrees) and all(d % 4 == 0 for d in out_degrees)
+    tails = torch.tensor([v for v, k in enumerate(out_degrees) for _ in range(k)])
+    heads = torch.tensor([v for v, k in enumerate(in_degrees) for _ in range(k)])
+    while True:
+        dealt = heads[torch.randperm(heads.numel(), generator=gen)]
+        if not bool((dealt == tails).any()):
+            return list(zip(tails.tolist(), dealt.tolist()))
+
+
+def sibling_network(seed) -> synth.SynthNetwork:
+    """SIBS: the dual graph of :func:`sibling_links`, its edge list reordered by (pi(source), target) for a seeded
+    permutation pi of the roads: every in-list is ordered by pi(source) — the same order for all siblings — every out-list
+    stays in ascending target order, and the list as a whole is neither source- nor destination-sorted."""
+    gen = torch.Generator().manual_seed(seed)
+    net = road_network(sibling_links(SIBS_OUT, SIBS_IN, gen), seed, shuffle=False)
+    R = net.num_roads
+    pi = torch.randperm(R, generator=gen)
+    order = torch.argsort(pi[net.edge_index[0]] * R + net.edge_index[1])
+    net.edge_index = net.edge_index[:, order].contiguous()
+    net.edge_attr = net.edge_attr[order].contiguous()
+    return net
+
+
+def detach_sibling_tails(net, seed):
+    """SIBS_TAILS from SIBS (``net``, edited in place): in every chunk of in-degree above four, each of the siblings 1 .. 3
+    gives one in-edge of in-rank >= 4, drawn at random, another source — a road that is not in the row's in-list and is
+    not the row itself. The edge keeps its id (so its in-rank), ``edge_attr`` is normalised per source road again. The
+    siblings then share their first four sources and their in-degree, nothing more. Returns the number of edges moved."""
+    gen = torch.Generator().manual_seed(seed)
+    R, ei = net.num_roads, net.edge_index
+    din, _ = degrees(net)
+    moved = 0
+    for row in range(R):
+        if row % 4 == 0 or int(din[row]) <= 4:
+            continue
+        eids = torch.nonzero(ei[1] == row).view(-1)
+        e = int(eids[4 + int(torch.randint(0, eids.numel() - 4, (1,), generator=gen))])
+        taken = set(ei[0][eids].tolist()) | {row}
+        free = [r for r in range(R) if r not in taken]
+        ei[0, e] = free[int(torch.randint(0, len(free), (1,), generator=gen))]
+        moved += 1
+    w = net.edge_attr.view(-1)
+    net.edge_attr = (w / torch.zeros(R).index_add_(0, ei[0], w)[ei[0]]).to(torch.float32).view(-1, 1).contiguous()
+    assert ops.fused_path_supported(ei, net.Nmax)
+    return moved
+
+
 RING = 12
 MIXED_HUBS = [(9, 9), (5, 8), (8, 5), (3, 1), (1, 3), (0, 2), (2, 0)]
 HUB126_HUBS = [(126, 126), (0, 2), (2, 0)]
 MIXED_SEED, HUB126_SEED = 9, 1
 MIXED_DEGREES = {0, 1, 3, 4, 5, 8, 9}
-CENSUS = {"MIXED": dict(per_road=40, T=80), "HUB126": dict(per_road=12, T=80)}     # agents per road, frames
+# the sibling graphs: 12 intersections, 56 roads; a road's in-degree is the in-degree of the intersection it leaves, its
+# out-degree the out-degree of the intersection it enters
+SIBS_OUT = [4] * 10 + [8] * 2
+SIBS_IN = [9, 4, 1, 5, 0, 8, 3, 4, 2, 8, 4, 8]
+SIBS_SEED, SIBS_TAILS_SEED = 2, 2
+SIBS_TAILS_MOVED = 18      # six chunks of in-degree above four, three siblings each
+# agents per road, frames
+CENSUS = {"MIXED": dict(per_road=40, T=80), "HUB126": dict(per_road=12, T=80),
+          "SIBS": dict(per_road=40, T=80), "SIBS_TAILS": dict(per_road=40, T=80)}
+TIE_WHICH = {"SIBS": 1, "SIBS_TAILS": 1}      # which road of the wanted in-degree carries the crafted tie (tie_case)
 
 
 def degrees(net):
@@ -93,16 +157,26 @@ def _graph(name):
         net = road_network(hub_links(MIXED_HUBS, RING, MIXED_SEED), MIXED_SEED)
         din, dout = degrees(net)
         assert MIXED_DEGREES <= set(din.tolist()) and MIXED_DEGREES <= set(dout.tolist()), (din.unique(), dout.unique())
-    else:
+    elif name == "HUB126":
         net = road_network(hub_links(HUB126_HUBS, RING, HUB126_SEED), HUB126_SEED)
         din, dout = degrees(net)
         assert int(din.max()) == 126 and int(dout.max()) == 126 and 256 < net.num_roads <= 512
+    elif name in ("SIBS", "SIBS_TAILS"):
+        net = sibling_network(SIBS_SEED)
+        if name == "SIBS_TAILS":
+            assert detach_sibling_tails(net, SIBS_TAILS_SEED) == SIBS_TAILS_MOVED
+        din, dout = degrees(net)
+        assert net.num_roads == 56 and set(din.tolist()) == set(SIBS_IN) and int(dout.min()) > 0      # G == N: the quad draw
+    else:
+        raise KeyError(name)
     return net
 
 
 def graph(name):
-    """``"MIXED"`` (about 80 roads, in- and out-degrees {0, 1, 3, 4, 5, 8, 9} and more) or ``"HUB126"`` (about 280 roads,
-    one hub at the degree limit of the packed path: 126 in, 126 out) — a fresh copy, the caller may edit it."""
+    """``"MIXED"`` (about 80 roads, in- and out-degrees {0, 1, 3, 4, 5, 8, 9} and more), ``"HUB126"`` (about 280 roads,
+    one hub at the degree limit of the packed path: 126 in, 126 out), ``"SIBS"`` (56 roads, four siblings per chunk with
+    in-degrees 0 .. 9 and out-degrees 4 and 8, every road with out-edges) or ``"SIBS_TAILS"`` (SIBS whose siblings share
+    only their first four sources, out-degrees 1 .. 9) — a fresh copy, the caller may edit it."""
     n = _graph(name)
     return synth.SynthNetwork(x=n.x.clone(), edge_index=n.edge_index.clone(), edge_attr=n.edge_attr.clone(), Nmax=n.Nmax,
                               num_roads=n.num_roads, critical_number=n.critical_number.clone(),
@@ -236,21 +310,38 @@ def segment_argmax_last(scores, index, n):
 
 
 COUNTERS = ("a_tail_admissible", "b_tail_in_race", "c_tail_wins", "d_tail_response", "e_relief_admissions")
+SHORT_IN = "f_short_in_admissions"      # counted beside COUNTERS: admissions into a road of in-degree 1 to 3
+
+
+def sibling0_tail_edges(edge_index, num_roads):
+    """``edge_index`` with the source of every in-edge of in-rank >= 4 into a road 4c + r, r > 0, replaced by the source of
+    road 4c's in-edge of the same in-rank (where road 4c has one): the in-lists a kernel would walk that shared the WHOLE
+    in-list between siblings, not only its first four entries."""
+    irank, _ = edge_ranks(edge_index, num_roads)
+    dst = edge_index[1]
+    slot = torch.full((num_roads, int(irank.max()) + 1), -1, dtype=torch.int64)
+    slot[dst, irank] = edge_index[0]
+    lead = slot[dst - dst % 4, irank]
+    swap = (irank >= 4) & (dst % 4 != 0) & (lead >= 0)
+    return torch.stack([torch.where(swap, lead, edge_index[0]), dst])
 
 
 def core_step_counted(x, net, t, uniform, counters, *, drop_in_tail=False, drop_out_tail=False, last_max=False,
-                      edge_attr=None):
+                      sibling0_tail=False, edge_attr=None):
     """``sim.core_step`` on ``x`` (in place), restated from the oracle's own pieces so that the branches it takes can be
     counted into ``counters`` (see :func:`census`) and ONE restriction applied: ``drop_in_tail`` removes every in-edge of
     in-rank >= 4 from the Direction message, ``drop_out_tail`` every out-edge of out-rank >= 4 from the Response message,
-    ``last_max`` breaks ties of the Gumbel race by the last maximum. Without a restriction it IS ``sim.core_step`` (the
-    host suite asserts that). Returns (delta_travel_time, popped)."""
+    ``last_max`` breaks ties of the Gumbel race by the last maximum, ``sibling0_tail`` evaluates the Direction message of
+    every in-edge of in-rank >= 4 on the source sibling 0 has at that rank (:func:`sibling0_tail_edges`: the identity where
+    siblings share their whole in-list). Without a restriction it IS ``sim.core_step`` (the host suite asserts that).
+    Returns (delta_travel_time, popped)."""
     ei, Nmax, R = net.edge_index, net.Nmax, net.num_roads
     ea = (net.edge_attr if edge_attr is None else edge_attr).reshape(-1)
     irank, orank = edge_ranks(ei, R)
     in_tail, out_tail = irank >= 4, orank >= 4
-    agent_id, prob, dtt = sim.direction_message(x, ei, ea, t, Nmax)
-    m1, m2 = direction_masks(x, ei, t, Nmax)
+    ei_dir = sibling0_tail_edges(ei, R) if sibling0_tail else ei
+    agent_id, prob, dtt = sim.direction_message(x, ei_dir, ea, t, Nmax)
+    m1, m2 = direction_masks(x, ei_dir, t, Nmax)
     assert torch.equal(prob, ea * (m1 | m2).float())
     if drop_in_tail:
         prob = torch.where(in_tail, torch.zeros_like(prob), prob)
@@ -269,6 +360,8 @@ def core_step_counted(x, net, t, uniform, counters, *, drop_in_tail=False, drop_
     counters["b_tail_in_race"] += int((adm & in_tail & (racers[ei[1]] >= 2)).sum())
     counters["c_tail_wins"] += int(in_tail[win].sum())
     counters["e_relief_admissions"] += int((m2 & ~m1)[win].sum())
+    din = torch.bincount(ei[1], minlength=R)
+    counters[SHORT_IN] += int((has & (din >= 1) & (din <= 3)).sum())
     sim.direction_update(x, chosen, t, Nmax, net.congestion_constant)
     msg = sim.response_message(x, ei, Nmax)
     counters["d_tail_response"] += int(((msg > 0) & out_tail).sum())
@@ -291,7 +384,7 @@ def env_step_counted(x, agents, net, adj, action, t, uniform, counters, **restri
 
 
 def new_counters():
-    return {k: 0 for k in COUNTERS}
+    return {k: 0 for k in COUNTERS + (SHORT_IN,)}
 
 
 def census_inputs(net, T, seed):
@@ -307,8 +400,9 @@ def census(net, pop, T, seed, t0=100):
     table and the reward after it; the counters over all frames —
     a_tail_admissible: admissible in-edges of in-rank >= 4; b_tail_in_race: those of them in a race of >= 2 admissible
     edges; c_tail_wins: races won by such an edge; d_tail_response: Response messages that fire on an out-edge of out-rank
-    >= 4; e_relief_admissions: agents admitted through the second (gridlock-relief) condition only; max_count: the largest
-    FIFO count seen; done: agents that arrived. The counters come from a shadow copy of each frame run through
+    >= 4; e_relief_admissions: agents admitted through the second (gridlock-relief) condition only; f_short_in_admissions:
+    agents admitted into a road of in-degree 1 to 3 (whose NodeRec::in4 ends in padding); max_count: the largest FIFO count
+    seen; done: agents that arrived. The counters come from a shadow copy of each frame run through
     :func:`core_step_counted`, which must leave the state ``sim.env_step`` leaves."""
     x, ag = net.x.clone(), pop.clone()
     xs, ags = x.clone(), pop.clone()
@@ -341,15 +435,16 @@ def replay_restricted(net, pop, T, seed, frames, t0=100, **restrict):
 
 
 # ---- a crafted tie across the 4 / 5 boundary of a nine-edge race ----------------------------------------------------------------
-def tie_case(net, x, t, in_degree=9):
-    """Edit ``x`` (in place) and return (edge_attr, e3, e4, road): a road with ``in_degree`` in-edges whose in-edges of rank
-    3 and 4 — the last record embedded in NodeRec::in4 and the first of the tail loop — are both admissible at time ``t``
-    and carry the SAME turn probability; with equal Gumbel noise on the two (and less on the others) their scores are
-    bit-equal maxima, and the reference's first-maximum rule admits the head of rank 3's road."""
+def tie_case(net, x, t, in_degree=9, which=0):
+    """Edit ``x`` (in place) and return (edge_attr, e3, e4, road): a road with ``in_degree`` in-edges — the ``which``-th of
+    them in ascending road id — whose in-edges of rank 3 and 4 — the last record embedded in NodeRec::in4 and the first of
+    the tail loop — are both admissible at time ``t`` and carry the SAME turn probability; with equal Gumbel noise on the
+    two (and less on the others) their scores are bit-equal maxima, and the reference's first-maximum rule admits the head
+    of rank 3's road."""
     ei, nmax = net.edge_index, net.Nmax
     c = sim.Cols(nmax)
     din, _ = degrees(net)
-    road = int(torch.nonzero(din == in_degree)[0])
+    road = int(torch.nonzero(din == in_degree)[which])
     eids = torch.nonzero(ei[1] == road).view(-1)
     e3, e4 = int(eids[3]), int(eids[4])
     ea = net.edge_attr.clone()

@@ -35,6 +35,7 @@ def plan_of(ops, net):
     f = ig.plan_facts(net)
     assert (plan.src_sorted, plan.siblings4, plan.row_siblings, plan.num_row_chunks, plan.max_in, plan.max_out) == \
         (f["src_sorted"], f["siblings4"], f["row_siblings"], f["num_row_chunks"], f["max_in"], f["max_out"])
+    assert plan.num_groups == int((ig.degrees(net)[1] > 0).sum())      # the roads that draw an action
     return plan
 
 
@@ -47,7 +48,7 @@ def core_step_case(ops, name):
     R, F, E, Nmax = net.num_roads, net.F, net.edge_index.size(1), net.Nmax
     B, t0 = 3, 200.0
     xs = [ig.random_state(net, seed=100 + b, t=t0) for b in range(B)]
-    ea, e3, e4, road = ig.tie_case(net, xs[0], t0, in_degree=int(ig.degrees(net)[0].max()))
+    ea, e3, e4, road = ig.tie_case(net, xs[0], t0, in_degree=int(ig.degrees(net)[0].max()), which=ig.TIE_WHICH.get(name, 0))
     plan = plan_of(ops, net)
     ec = ops.EdgeConst(ea, "cuda")
     cc = dev(net.congestion_constant)
@@ -127,17 +128,24 @@ def fused_frame_case(ops, name, B, frames):
     """The frame loop of test_fused_equals_unfused_frame_by_frame on the irregular graphs, host-supplied noise. On MIXED,
     at frame 30 (traffic is flowing) two upstream rows of the nine-in-edge road get a raw SELECTED_ROAD — a road that is
     none of their neighbours — on both sides, the fused state is packed again, and five frames run without the choice phase:
-    the Direction gather's exact ``redo`` pass then walks a nine-entry in-list."""
+    the Direction gather's exact ``redo`` pass then walks a nine-entry in-list. On the sibling graphs (SIBS, SIBS_TAILS) the
+    nine-in-edge road is a non-zero sibling, and road 0 gets a raw code too: road 0 is what the padding records of a short
+    in-list name, so the sibling gather repeats the pass of chunks that did not need it — which must change nothing."""
     net = ig.graph(name)
     plan = plan_of(ops, net)
     raw_sel = None
-    if name == "MIXED":
-        assert plan.max_in == 9 and not plan.siblings4 and plan.num_row_chunks > net.num_roads // 4
-        road = int(torch.nonzero(ig.degrees(net)[0] == 9)[0])
+    if name in ("MIXED", "SIBS", "SIBS_TAILS"):
+        sibs = name != "MIXED"
+        assert plan.max_in == 9 and plan.siblings4 == sibs
+        assert plan.num_groups == net.num_roads if sibs else plan.num_row_chunks > net.num_roads // 4
+        road = int(torch.nonzero(ig.degrees(net)[0] == 9)[ig.TIE_WHICH.get(name, 0)])
         ups = net.edge_index[0][net.edge_index[1] == road][[2, 6]].tolist()      # one embedded record, one of the tail
         lists = ig.out_lists(net)
         far = [next(c for c in order if c not in lists[j] and c != road)      # two different roads, no neighbours
                for j, order in zip(ups, (range(net.num_roads), reversed(range(net.num_roads))))]
+        if sibs and 0 not in ups:
+            assert road % 4 != 0 and int((ig.degrees(net)[0] < 4).sum()) > 0
+            ups, far = ups + [0], far + [next(c for c in range(1, net.num_roads) if c not in lists[0])]
         raw_sel = (30, 5, ups, far)
     else:
         assert plan.max_in == 126 and plan.max_out == 126
@@ -161,7 +169,7 @@ def fused_tie_case(ops, name):
     xs, us = [], torch.rand((B, E), generator=torch.Generator().manual_seed(9))
     for b in range(B):
         xb = ig.random_state(net, seed=60 + b, t=t)
-        ea, e3, e4, road = ig.tie_case(net, xb, t, in_degree=int(ig.degrees(net)[0].max()))
+        ea, e3, e4, road = ig.tie_case(net, xb, t, in_degree=int(ig.degrees(net)[0].max()), which=ig.TIE_WHICH.get(name, 0))
         us[b] = ig.tie_uniform(us[b], net, road, e3, e4)
         xs.append(xb)
     A = int(torch.stack(xs)[:, :, :Nmax].max()) + 2
@@ -231,6 +239,9 @@ def rollout_case(ops, setenv, name, B, T):
     ct1 = torch.zeros((T + 1, N, B), device="cuda")
     dtt, pop, wd = (torch.empty((B, E), device="cuda"), torch.empty((B, N), dtype=torch.uint8, device="cuda"),
                     torch.empty((B, N), dtype=torch.uint8, device="cuda"))
+    _, orank = (r.cuda() for r in ig.edge_ranks(net.edge_index, N))
+    short_out = dev((ig.degrees(net)[1] > 0) & (ig.degrees(net)[1] < 4))
+    high_picks, short_picks = torch.zeros(B, dtype=torch.int64, device="cuda"), torch.zeros(B, dtype=torch.int64, device="cuda")
     bufs = {}
     for key, env_minor in (("m1", True), ("m2", True), ("env", False)):
         shp = (lambda t, k: (t, N, k)) if env_minor else (lambda t, k: (t, k, N))
@@ -249,6 +260,8 @@ def rollout_case(ops, setenv, name, B, T):
             _, ch0 = ops.graphdist_sample(e0.plan, p, seed=e1.seed ^ 0x5DEECE66D, counter=s + 1, want_onehot=False,
                                           want_choice=True)
             lp0, _ = ops.graphdist_logprob_entropy(e0.plan, p, choice=ch0, want_entropy=False)
+            high_picks += ((ch0 >= 0) & (orank[ch0.long().clamp(min=0)] >= 4)).sum(1)
+            short_picks += ((ch0 >= 0) & short_out).sum(1)
             e0.step(choice=ch0)
             e1.frame_fused(choice=ch1[t], log_prob=lp1[t], reward=rw1[t], counts=ct1[t + 1], dtt=dtt, popped=pop, withdrawn=wd)
             assert torch.equal(ch0, ch1[t].t()), f"actions frame {s}"
@@ -283,6 +296,8 @@ def rollout_case(ops, setenv, name, B, T):
             assert torch.equal(series["m1"][0], series[key][0]) and torch.equal(series["m1"][1], series[key][1])
         assert int(ev_ref.sum()) > 0
     assert float(rw1.abs().sum()) > 0 and float(e1.agents[:, :, 8].sum()) > 0
+    if name == "SIBS_TAILS":      # the reference side's draws reached what the quad draw does off the torus, in every environment
+        assert int(high_picks.min()) > 0 and int(short_picks.min()) > 0, (high_picks, short_picks)
     ca, cb = torch.zeros_like(ch1[0]), torch.zeros_like(ch1[0])
     ra, rb = torch.zeros(B, device="cuda"), torch.zeros(B, device="cuda")
     for t in range(5):      # hand the state back to the four-launch path
