@@ -933,6 +933,33 @@ int tarl_occupancy_accumulate(const float* ring, const int32_t* thr, int64_t F, 
                               int64_t timestep, int64_t bin_seconds, int64_t first_bin, int64_t H, int32_t* veh,
                               int32_t* full, int32_t* peak, tarl_stream stream);
 
+/* ---- per-turn movement counts of a vectorised evaluation -------------------------------------------------------------------
+ * How many vehicles crossed each route edge e = (u -> v) (DirectionMPNN.aggregate chose e for v and the chosen agent id is
+ * not 0: that agent enters v in this frame, src/direction_mpnn.py) and how many agents the U-turn double pop lost on which
+ * road (an agent that moves from v into an EMPTY road u whose edge u -> v exists too is accepted on both edges by
+ * ResponseMPNN, src/response_mpnn.py: u is popped although nothing left it, and the agent is gone), binned like the link
+ * counts: frame f of a call starts at clock_f = t0 + f * timestep and belongs to bin h_f = clock_f / bin_seconds - first_bin.
+ * tarl_turn_counts_accumulate: rings of F consecutive frames exactly as tarl_fused_frame leaves them: popped uint8
+ *   [F][K][N] (env-major; only bit 0 of a byte is read), sel8 uint8 [F][N][K] (tarl_fused.sel8 AFTER frame f: the
+ *   SELECTED_ROAD byte the frame ran with; bit 7 is ignored) and counts fp32 [F][N][K] (NUMBER_OF_AGENT after frame f), both
+ *   env-minor; prev_counts fp32 [N][K] (nullable: every road empty, as after a reset) = the counts slice of the frame before
+ *   the call's first. With n_pre = counts[f - 1] (prev_counts for f = 0) and N, E the plan's, for every (f, k, u) with
+ *   popped[f][k][u] & 1:
+ *     not n_pre[u][k] > 0 (0, -0.0, NaN)              -> lost  int32 [K][H][N]: lost[k][h_f][u] += 1
+ *     else r = sel8[f][u][k] & 0x7F < out-degree(u)  -> turns int32 [K][H][E]: turns[k][h_f][e] += 1, e = the ORIGINAL edge
+ *                                                       id of the r-th out-edge of u in the plan's CSR order
+ *     else (0x7F, 0x7E, a rank >= the out-degree)     -> unresolved int32 [K]: unresolved[k] += 1
+ *   so every popped bit lands in exactly one table and a second call continues the first. turns and lost have the layout
+ *   of tarl_link_count_stats (its last axis is generic: pass E or N). One launch for all F frames; one thread owns an
+ *   (environment, road) pair and is the only writer of its elements of turns and lost, no atomics there.
+ *   1 <= F <= 2^23. Refused on the host, before anything is launched and with the tables untouched: a null argument
+ *   (prev_counts excepted), a first frame below first_bin, a last frame in a bin >= H, timestep < 0, bin_seconds < 1, a plan
+ *   without an edge, K, H, K * N * H, K * E * H or F * K * N at or above 2^40. */
+int tarl_turn_counts_accumulate(const tarl_plan* plan, const uint8_t* popped, const uint8_t* sel8, const float* counts,
+                                const float* prev_counts, int64_t F, int64_t K, int64_t t0, int64_t timestep,
+                                int64_t bin_seconds, int64_t first_bin, int64_t H, int32_t* turns, int32_t* lost,
+                                int32_t* unresolved, tarl_stream stream);
+
 /* ---- per-trip report of a vectorised evaluation ------------------------------------------------------------------------------
  * What an episode leaves behind in the K agent tables, agents fp32 [K][A][9] with environment k at agents + k * a_bstride
  * (as tarl_episode_summary takes them; row 0, the dummy, is skipped). An agent has ARRIVED when DONE == 1; its travel time is

@@ -5,8 +5,8 @@
 ``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
 ``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
 comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` and the per-road link counts of either
-``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy``, ``--eval-trips`` and
-``--eval-dynamic-gap``)."""
+``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy``, ``--eval-trips``,
+``--eval-dynamic-gap`` and ``--eval-turns``)."""
 import argparse
 import os
 import sys
@@ -116,6 +116,13 @@ OPTIONS = (
                                      "`dynamic_gap` in the JSON file")),
     ("--eval-dynamic-gap-envs", dict(type=int, default=None, metavar="J",
                                      help="--eval-dynamic-gap: search the first J of the K environments only (default: all)")),
+    ("--eval-turns", dict(action="store_true",
+                          help="--eval-envs / --dijkstra-envs, eval: count per route edge u -> v and time bin (of --eval-link-bin "
+                               "seconds) the vehicles that crossed it, and per road the agents lost to the reference's U-turn "
+                               "double pop, over the K environments; a `Turns` block, eval_turns.csv (dijkstra_turns.csv) with "
+                               "mean, standard error and interval per turn, its share of the movements out of its road, for "
+                               "the embedding head the policy's probability and, with --eval-baseline, the paired "
+                               "difference; eval_turns_lost.csv; `turns` in the JSON file")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--checkpoint", dict(type=str, default=None,

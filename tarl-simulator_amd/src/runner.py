@@ -43,6 +43,7 @@ class RunnerArgs:
     eval_trips: bool = False       # eval_envs / dijkstra_envs: per-traveller travel time and delay (bins of eval_link_bin)
     eval_dynamic_gap: bool = False # eval_envs / dijkstra_envs, eval: the trips against the best path in hindsight (same bins)
     eval_dynamic_gap_envs: int = None   # ... over the first J of the K environments (default: all)
+    eval_turns: bool = False       # eval_envs / dijkstra_envs: vehicles per route edge and the agents quirk Q24 loses (same bins)
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -74,6 +75,9 @@ class RunnerArgs:
         if self.eval_occupancy and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_occupancy sums per-road vehicle counts and frames at capacity in the vectorised "
                              "evaluation: it needs eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_turns and not (self.eval_envs or self.dijkstra_envs):
+            raise ValueError("eval_turns counts per-turn movements in the vectorised evaluation: it needs eval_envs > 0 or "
+                             "dijkstra_envs > 0")
         if self.eval_trips and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_trips reduces the agent tables of the vectorised evaluation per traveller: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
@@ -357,6 +361,8 @@ class Runner:
                       trip_free_flow=g.x[:, h.FREE_FLOW_TIME_TRAVEL][g.edge_index[1]])
         if a.eval_dynamic_gap:
             kw.update(dynamic_gap=True, dynamic_gap_envs=a.eval_dynamic_gap_envs, link_bin_seconds=a.eval_link_bin)
+        if a.eval_turns:
+            kw.update(turns=True, link_bin_seconds=a.eval_link_bin)
         return kw
 
     @staticmethod
@@ -376,16 +382,21 @@ class Runner:
         return summary_fn(report)
 
     def _reports_output(self, doc, res, baseline, out_dir, prefix):
-        """--eval-link-counts, --eval-occupancy, --eval-trips, --eval-dynamic-gap: each report of ``res`` (against ``baseline``, the evaluation of
+        """--eval-link-counts, --eval-turns, --eval-occupancy, --eval-trips, --eval-dynamic-gap: each report of ``res`` (against ``baseline``, the evaluation of
         the same environments, where there is one) printed, written to ``<prefix>_<report>.csv`` (one row per road; the
         link counts with the expected flows that Runner.eval computed; the trips one row per agent, and per departure bin in
-        ``<prefix>_trips_by_departure.csv``) and summarised in ``doc``."""
+        ``<prefix>_trips_by_departure.csv``; the turns one row per route edge, and per road with a loss in
+        ``<prefix>_turns_lost.csv``) and summarised in ``doc``."""
         from tarl_hip import evaluator as E
         a = self.args
         if a.eval_link_counts:
             rep = E.link_count_report(res, expected=getattr(self, "_link_expected", {}), baseline=baseline)
             doc["link_counts"] = self._report_output("Link counts", rep, E.link_count_lines, E.link_count_summary,
                                                      [(out_dir / f"{prefix}_link_counts.csv", "columns", "rows")])
+        if a.eval_turns:
+            doc["turns"] = self._report_output("Turns", E.turn_report(res, baseline=baseline), E.turn_lines, E.turn_summary,
+                                               [(out_dir / f"{prefix}_turns.csv", "columns", "rows"),
+                                                (out_dir / f"{prefix}_turns_lost.csv", "lost_columns", "lost_rows")])
         if a.eval_occupancy:
             doc["occupancy"] = self._report_output("Occupancy", E.occupancy_report(res, baseline=baseline), E.occupancy_lines,
                                                    E.occupancy_summary, [(out_dir / f"{prefix}_occupancy.csv", "columns", "rows")])

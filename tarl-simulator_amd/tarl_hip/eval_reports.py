@@ -1,5 +1,5 @@
 """The reports of the vectorised evaluation beyond the per-environment aggregate — per-road link counts, per-road occupancy
-and time at capacity, per-trip travel times, the dynamic relative gap — each as ``*_report`` (rows and a summary, formed in float64 on the host from the
+and time at capacity, per-trip travel times, the dynamic relative gap, per-turn movement counts — each as ``*_report`` (rows and a summary, formed in float64 on the host from the
 kernels' integer accumulators), ``*_lines`` (its printable block) and ``*_summary`` (what the JSON files carry), and the pieces
 they share. :mod:`tarl_hip.evaluator` re-exports every public name and is never imported here: an ``EvalResult`` is only read."""
 from __future__ import annotations
@@ -97,6 +97,7 @@ def _bin_names(prefix, first_bin, num_bins, bin_seconds):
 link_bin_names = partial(_bin_names, "count_")        # (first_bin, num_bins, bin_seconds) -> the link-count columns
 occupancy_bin_names = partial(_bin_names, "occ_")     # ... the occupancy columns
 trip_bin_names = partial(_bin_names, "")              # ... the labels of the by-departure table
+turn_bin_names = partial(_bin_names, "turns_")        # ... the turn-count columns
 
 
 # ---- per-road link counts (VecEvaluator(link_counts=True)) --------------------------------------------------------------------
@@ -754,3 +755,137 @@ def dynamic_gap_lines(report: dict, paired=True):
 
 
 dynamic_gap_summary = _summary
+
+
+# ---- per-turn movement counts (VecEvaluator(turns=True)) --------------------------------------------------------------------------
+TURN_RING_BYTES = 256 << 20         # the three rings of the evaluator together: popped, SELECTED_ROAD bytes, counts
+TURN_LOST_NOTE = ("an agent that moves into an EMPTY road u from a road v with an edge u -> v is accepted on both edges by the "
+                  "reference's ResponseMPNN: u is popped although nothing left it and the agent is queued nowhere from then "
+                  "on (DESIGN quirk Q24); it stays flagged ON_WAY and never arrives")
+
+
+def turn_report(result: "EvalResult", baseline: "EvalResult | None" = None) -> dict:
+    """Per-route-edge rows, the roads with a loss and a summary of the turn counts of one evaluation
+    (``VecEvaluator(turns=True)``), formed in float64 on the host from the integer tables and their integer moments.
+    Every row: ``edge`` (the caller's edge id), ``from_road``, ``to_road``; the episode total's ``mean``, ``sd``, ``se``,
+    ``ci95_lo``, ``ci95_hi`` (``None`` for K = 1), ``min``, ``max`` over the K environments; the per-bin means
+    (:func:`turn_bin_names`); ``share``, the edge's part of all movements out of ``from_road`` (over all environments;
+    ``None`` where nothing left the road); for the state-independent head ``embedding`` the policy's ``policy_prob`` of the
+    edge and ``share_minus_prob``. ``baseline``: the evaluation of another head on the same environments (same K, seed,
+    frames, bins and edges: ``ValueError`` otherwise); the row gains ``baseline_mean`` and the paired difference result -
+    baseline, ``paired_diff_mean`` / ``_se`` / ``_ci95_lo`` / ``_hi``, from the two-input ``ops.link_count_stats``; the summary
+    counts the turns whose interval excludes 0. ``lost_rows``: one row per road with a phantom pop (``road``, ``mean``, ``se``,
+    ``min``, ``max`` of the episode total, the per-bin means). The summary also carries the movements and the lost agents
+    per environment (:func:`aggregate`), the turns used, the ten busiest turns, the per-bin totals and the identity lost ==
+    ON_WAY - queued per environment. A run without turn counts (a domain exit has none):
+    ``{"available": False, "reason": ...}``."""
+    if (gone := _unavailable(result, result.turn_counts, "the run did not count turns")) is not None:
+        return gone
+    tc, tl, meta = result.turn_counts, result.turn_lost, result.turn_meta
+    K, H, E = tc.shape
+    N = tl.shape[2]
+    st, sl = result.turn_stats["turns"], result.turn_stats["lost"]
+    names = turn_bin_names(meta["first_bin"], H, meta["bin_seconds"])
+    src, dst = (np.asarray(meta["edge_index"][i], dtype=np.int64) for i in (0, 1))
+    total = st["sum"][H].astype(np.float64)                             # movements per edge over all environments
+    out_of = np.zeros(N, dtype=np.float64)
+    np.add.at(out_of, src, total)
+    prob = meta.get("policy_prob")
+    rows = []
+    for e in range(E):
+        den = out_of[src[e]]
+        row = {"edge": e, "from_road": int(src[e]), "to_road": int(dst[e]), "mean": float(st["mean"][H, e]),
+               **_spread("", st, H, e), "min": int(st["min"][H, e]), "max": int(st["max"][H, e])}
+        row.update({name: float(st["mean"][h, e]) for h, name in enumerate(names)})
+        row["share"] = float(total[e] / den) if den > 0 else None
+        if prob is not None:
+            row["policy_prob"] = float(prob[e])
+            row["share_minus_prob"] = None if row["share"] is None else row["share"] - float(prob[e])
+        rows.append(row)
+    columns = list(rows[0])
+    lost_rows = []
+    for n in np.nonzero(sl["max"][H] > 0)[0]:
+        row = {"road": int(n), "mean": float(sl["mean"][H, n]), **_spread("", sl, H, n), "min": int(sl["min"][H, n]),
+               "max": int(sl["max"][H, n])}
+        row.update({name.replace("turns_", "lost_"): float(sl["mean"][h, n]) for h, name in enumerate(names)})
+        lost_rows.append(row)
+    lost_columns = ["road", "mean", "sd", "se", "ci95_lo", "ci95_hi", "min", "max"] + [n.replace("turns_", "lost_") for n in names]
+    moved_env = tc.astype(np.int64).sum(axis=(1, 2))
+    lost_env = tl.astype(np.int64).sum(axis=(1, 2))
+    missing = [a - b for a, b in zip(meta["on_way"], meta["queued"])]
+    top = sorted(rows, key=lambda r: (-r["mean"], r["edge"]))[:10]
+    summary = {"envs": K, "edges": E, "roads": N, "frames_run": result.frames_run,
+               "movements": aggregate(list(moved_env.astype(np.float64))), "movements_per_env": [int(x) for x in moved_env],
+               "turns_used": int((st["max"][H] > 0).sum()),
+               "roads_using_two_turns": int((np.bincount(src, weights=(st["max"][H] > 0), minlength=N) >= 2).sum()),
+               "lost": aggregate(list(lost_env.astype(np.float64))), "lost_per_env": [int(x) for x in lost_env],
+               "roads_with_a_loss": len(lost_rows), "lost_note": TURN_LOST_NOTE,
+               "identity": {"holds": [int(x) for x in lost_env] == missing, "on_way": list(meta["on_way"]),
+                            "queued": list(meta["queued"])},
+               "movements_per_bin": [float(x) for x in st["mean"][:H].sum(axis=1)],
+               "lost_per_bin": [float(x) for x in sl["mean"][:H].sum(axis=1)],
+               "top_turns": [{k: r[k] for k in ("edge", "from_road", "to_road", "mean", "share")} for r in top]}
+    rep = {"available": True, "head": result.head, "bin_seconds": int(meta["bin_seconds"]), "first_bin": int(meta["first_bin"]),
+           "bins": names}
+    if baseline is not None:
+        _check_pair("turn_report", result, baseline)
+        if baseline.domain_exit or baseline.turn_counts is None:
+            summary["paired"] = {"available": False, "reason": "the baseline run has no turn counts"}
+        else:
+            bm = baseline.turn_meta
+            if baseline.turn_counts.shape != tc.shape or baseline.frames_run != result.frames_run or \
+                    any(bm[k] != meta[k] for k in ("first_bin", "bin_seconds")) or \
+                    not np.array_equal(bm["edge_index"], meta["edge_index"]):
+                raise ValueError("turn_report needs the same frames, bins and edges in both runs")
+            pd = _paired_moments(tc, baseline.turn_counts, K)
+            bs = baseline.turn_stats["turns"]
+            for e, row in enumerate(rows):
+                row.update(baseline_mean=float(bs["mean"][H, e]), paired_diff_mean=float(pd["mean"][H, e]),
+                           **_spread("paired_diff_", pd, H, e, sd=False))
+            columns = list(rows[0])
+            excl = int(((pd["ci95_lo"][H] > 0) | (pd["ci95_hi"][H] < 0)).sum()) if pd["std"] is not None else None
+            summary["paired"] = {"available": True, "baseline_head": baseline.head, "turns_interval_excludes_zero": excl,
+                                 "mean_abs_paired_diff": float(np.abs(pd["mean"][H]).mean()),
+                                 "baseline_movements": float(bs["mean"][H].sum()),
+                                 "baseline_lost": float(baseline.turn_stats["lost"]["mean"][H].sum())}
+    rep.update(columns=columns, rows=rows, lost_columns=lost_columns, lost_rows=lost_rows, summary=summary)
+    return rep
+
+
+def turn_lines(report: dict):
+    """:func:`turn_report` as printable lines (the ``Turns`` block)."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    s = report["summary"]
+    g, lo = s["movements"], s["lost"]
+    i = s["identity"]
+    out = [f"{'movements:':22} {g['mean']:12.3f}{_interval(g)}  min {g['min']:.0f}  max {g['max']:.0f}  n {g['n']}  (vehicles that "
+           f"crossed a route edge, per environment; {s['envs']} environments, {s['frames_run']} frames)",
+           f"{'turns used:':22} {s['turns_used']:12d} of {s['edges']}  ({s['roads_using_two_turns']} of {s['roads']} roads sent "
+           f"vehicles over at least two of their out-edges)",
+           f"{'agents lost (Q24):':22} {lo['mean']:12.3f}{_interval(lo)}  on {s['roads_with_a_loss']} roads; lost == ON_WAY - queued "
+           f"in every environment: {'yes' if i['holds'] else 'NO'} (environment 0: {s['lost_per_env'][0]} == "
+           f"{i['on_way'][0]} - {i['queued'][0]})"]
+    for name, m, gone in zip(report["bins"], s["movements_per_bin"], s["lost_per_bin"]):
+        out.append(f"{name + ':':22} {m:12.3f} movements, {gone:.3f} lost (mean over the environments)")
+    out.append("busiest turns (mean movements per environment, share of the movements out of the road):")
+    for r in s["top_turns"]:
+        out.append(f"  edge {r['edge']:7d}  {r['from_road']:6d} -> {r['to_road']:6d}  {r['mean']:10.2f}  "
+                   f"share {_f(r['share'], '.3f')}")
+    p = s.get("paired")
+    if p is not None and not p["available"]:
+        out.append(f"paired:                not available: {p['reason']}")
+    elif p is not None:
+        line = (f"{'policy - ' + p['baseline_head'] + ':':22} mean |paired diff| {p['mean_abs_paired_diff']:.3f} per turn "
+                f"(baseline: {p['baseline_movements']:.3f} movements, {p['baseline_lost']:.3f} lost per environment)")
+        if p["turns_interval_excludes_zero"] is not None:
+            line += f"; the 95% interval excludes 0 on {p['turns_interval_excludes_zero']} of {s['edges']} turns (normal approx.)"
+        else:
+            line += "; one environment: no interval"
+        out.append(line)
+    return out
+
+
+def turn_summary(report: dict):
+    """A turn report without its tables (``rows``, ``lost_rows``): what the JSON files carry."""
+    return _json_clean({k: v for k, v in report.items() if k not in ("rows", "lost_rows")})

@@ -43,11 +43,13 @@ from . import lib as _lib
 from . import ops
 from .engine import EPISODE_END, EPISODE_START
 from .eval_reports import (CONGESTION_FILE, DYNAMIC_GAP_NOTE, LINK_EXPECTED, LINK_PARTIAL_NOTE, LINK_RING_BYTES,  # noqa: F401
-                           OCCUPANCY_RING_BYTES, TRIP_CHANCE, TRIP_FF_CHUNK_BYTES, TRIP_FF_NOTE, _CI95_KIND, _interval, _sample_moments,
+                           OCCUPANCY_RING_BYTES, TRIP_CHANCE, TRIP_FF_CHUNK_BYTES, TRIP_FF_NOTE, TURN_RING_BYTES, _CI95_KIND,
+                           _interval, _sample_moments,
                            aggregate, capacity_threshold, dynamic_gap_lines, dynamic_gap_paired_lines, dynamic_gap_report,
                            dynamic_gap_summary, geh, link_bin_names, link_count_lines, link_count_report, link_count_summary,
                            link_moments, occupancy_bin_names, occupancy_lines, occupancy_report, occupancy_summary,
-                           trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report, trip_summary)
+                           trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report, trip_summary,
+                           turn_bin_names, turn_lines, turn_report, turn_summary)
 
 HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra")
 _MLP_PRECISION = {"edge_mlp": "x3", "edge_mlp_fp32": "fp32", "edge_mlp_bf16": "bf16"}
@@ -111,6 +113,11 @@ class EvalResult:
     #                                                                         departure, free_flow (A,), paired
     # dynamic_gap=True (never after a domain exit): the trips against the best path in hindsight, DESIGN 4.17
     dynamic_gap: dict | None = field(default=None, compare=False)           # best (J, A) fp64, per_agent, per_env, per_bin, meta
+    # turns=True (never after a domain exit): vehicles per route edge and time bin, and the agents quirk Q24 loses, DESIGN 4.18
+    turn_counts: np.ndarray | None = field(default=None, compare=False)     # (K, H, E) int32, the caller's edge order
+    turn_lost: np.ndarray | None = field(default=None, compare=False)       # (K, H, N) int32: phantom pops per road
+    turn_stats: dict | None = field(default=None, compare=False)            # link_moments of "turns" and of "lost"
+    turn_meta: dict | None = field(default=None, compare=False)             # first_bin, bin_seconds, edge_index, policy_prob
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -253,7 +260,7 @@ class VecEvaluator:
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
-                 dynamic_gap_envs=None):
+                 dynamic_gap_envs=None, turns=False, turn_block=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -285,7 +292,15 @@ class VecEvaluator:
         ``occupancy=True`` the result carries no ``occupancy`` report), ``run()`` checks the population as for ``trips``, and
         for the first ``dynamic_gap_envs`` environments (default: all K) one ``ops.td_road_times`` and one
         ``ops.td_hindsight`` call follow the episode summary, reduced in fp64 on the device. ``run()`` refuses before the
-        first frame what does not fit half the free device memory."""
+        first frame what does not fit half the free device memory.
+        ``turns``: also count, per environment, ROUTE EDGE u -> v and time bin of ``link_bin_seconds``, the vehicles that
+        crossed the edge, and per road the agents the reference's U-turn double pop loses. The frames write their
+        ``popped`` and ``counts`` slices into rings of ``turn_block`` frames (default: the largest block <= ``poll_frames``
+        that keeps the three rings within 256 MB, at least 1; the counts ring is the occupancy ring where that one is on and
+        has the same block), the SELECTED_ROAD bytes are copied into the third after every frame, and one
+        ``ops.turn_counts_accumulate`` launch follows every block. ``run()`` sizes the (K, H, E) and (K, H, N) tables and
+        refuses what exceeds half the free device memory; it raises when a pop could not be attributed to an edge or when
+        the lost agents do not add up to the ON_WAY agents that are queued nowhere."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -322,7 +337,10 @@ class VecEvaluator:
             if not 1 <= self.dynamic_gap_envs <= K:
                 raise ValueError(f"dynamic_gap_envs must be in [1, {K}] (the engine's environments), got {dynamic_gap_envs!r}")
         self._occ_acc_on = self.occupancy or self.dynamic_gap      # the gap reads the occupancy sums: accumulated either way
-        if self.link_counts or self._occ_acc_on or self.trips:      # one binning for the per-road reports and the trips
+        self.turns = bool(turns)
+        if turn_block is not None and not self.turns:
+            raise ValueError("turn_block sizes the rings of the turn counts: it needs turns=True")
+        if self.link_counts or self._occ_acc_on or self.trips or self.turns:      # one binning for every binned report
             self.link_bin_seconds = int(link_bin_seconds)
             if self.link_bin_seconds < 1:
                 raise ValueError("link_bin_seconds must be >= 1")
@@ -346,6 +364,20 @@ class VecEvaluator:
             self.occ_thr_host = capacity_threshold(self.occ_max)
             self.occ_thr = torch.from_numpy(self.occ_thr_host).to(dev)
             self.occ_acc = None         # veh, full (K, H, N) and peak (K, 1, N) int32, sized by run() for its frames
+        if self.turns:
+            if turn_block is None:
+                turn_block = self._ring_block(TURN_RING_BYTES, 6 * K * N)
+            self.turn_block = int(turn_block)
+            if not 1 <= self.turn_block <= ops.TURN_COUNTS_MAX_FRAMES:
+                raise ValueError(f"turn_block must be in [1, {ops.TURN_COUNTS_MAX_FRAMES}] (ops.TURN_COUNTS_MAX_FRAMES)")
+            self.turn_popped = torch.zeros((self.turn_block, K, N), dtype=torch.uint8, device=dev)
+            self.turn_sel = torch.zeros((self.turn_block, N, K), dtype=torch.uint8, device=dev)
+            if self._occ_acc_on and self.occupancy_block == self.turn_block:
+                self.turn_ring = self.occ_ring      # one counts ring serves both
+            else:
+                self.turn_ring = torch.zeros((self.turn_block, N, K), dtype=torch.float32, device=dev)
+            self.turn_prev = torch.zeros((N, K), dtype=torch.float32, device=dev)      # the block before's last counts slice
+            self.turn_acc = None        # turns (K, H, E), lost (K, H, N), unresolved (K,) int32, sized by run()
         if self.trips:
             self.trip_ff = None if trip_free_flow is None else trip_free_flow_times(engine, trip_free_flow)
         elif trip_free_flow is not None:
@@ -488,6 +520,21 @@ class VecEvaluator:
             masks = dict(popped=self.link_popped[j], withdrawn=self.link_withdrawn[j])
         if self._occ_acc_on:        # and of the counts ring
             masks["counts"] = self.occ_ring[t % self.occupancy_block]
+        if self.turns:              # and of the turn rings: the frame writes a slice once, a second ring gets a copy
+            jt = t % self.turn_block
+            masks.setdefault("popped", self.turn_popped[jt])
+            masks.setdefault("counts", self.turn_ring[jt])
+        done = self._frame_head(t, deterministic, rec, masks)
+        if self.turns:
+            if masks["popped"].data_ptr() != self.turn_popped[jt].data_ptr():
+                self.turn_popped[jt].copy_(masks["popped"])
+            if masks["counts"].data_ptr() != self.turn_ring[jt].data_ptr():
+                self.turn_ring[jt].copy_(masks["counts"])
+            self.turn_sel[jt].copy_(eng.fs.sel8)        # the SELECTED_ROAD bytes this frame ran with
+        return done
+
+    def _frame_head(self, t, deterministic, rec, masks):
+        eng = self.eng
         if self.head == "dijkstra":     # choice -> core -> withdraw / insert -> reward: the environment's step order
             if eng._packed_stale:
                 eng.resync()
@@ -541,7 +588,7 @@ class VecEvaluator:
                 raise ValueError("trip_pair must hold the same population as this engine's agent tables")
         self._start(bool(deterministic))
         sched = H = None
-        if self.link_counts or self._occ_acc_on or self.trips:      # one binning for the per-road reports and the trips
+        if self.link_counts or self._occ_acc_on or self.trips or self.turns:      # one binning for every binned report
             t0, step, bins = int(eng.time), int(eng.timestep), self.link_bin_seconds
             H = (t0 + (T - 1) * step) // bins - t0 // bins + 1
             sched = _BinSchedule(t0, step, bins, t0 // bins, H)
@@ -561,6 +608,8 @@ class VecEvaluator:
                                 "peak": torch.empty((eng.B, 1, eng.N), **acc)}
             for v in self.occ_acc.values():
                 v.zero_()
+        if self.turns:
+            self._turn_reserve(H)
         polls = []                  # (frames queued when the status word was copied, event)
         seen = False
         done = 0
@@ -573,6 +622,11 @@ class VecEvaluator:
             if self._occ_acc_on and _due(done, self.occupancy_block, T):      # one launch per block of the ring
                 ops.occupancy_accumulate(self.occ_ring, self.occ_thr, *self.occ_acc.values(),      # (veh, full, peak)
                                          **sched.block(done, self.occupancy_block))
+            if self.turns and _due(done, self.turn_block, T):               # one launch per block of the three rings
+                blk = sched.block(done, self.turn_block)
+                ops.turn_counts_accumulate(eng.plan, self.turn_popped, self.turn_sel, self.turn_ring, *self.turn_acc.values(),
+                                           prev_counts=self.turn_prev if done > blk["frames"] else None, **blk)
+                self.turn_prev.copy_(self.turn_ring[blk["frames"] - 1])      # n_pre of the next block's first frame
             if _due(done, self.poll_frames, T):
                 self._flag_host[len(polls)].copy_(fs.flags[0], non_blocking=True)
                 ev = torch.cuda.Event()
@@ -623,12 +677,62 @@ class VecEvaluator:
             res.occupancy_frames_per_bin = [int(x) for x in np.bincount(bins_of, minlength=H)]
             res.occupancy_meta = dict(first_bin=sched.first_bin, bin_seconds=sched.bin_seconds, timestep=sched.timestep,
                                       max=self.occ_max.copy(), thr=self.occ_thr_host.copy())
+        if self.turns:
+            self._turn_reduce(res, sched, host["counts"][:, 1])
         if self.trips:
             self._trip_reduce(res, trip_pair, sched)
         if self.dynamic_gap:
             self._gap_reduce(res, sched, done)
         res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
         return res
+
+    # -- per-turn movement counts -------------------------------------------------------------------------------
+    def _turn_reserve(self, H):
+        """The tables of the turn counts for the run's H bins, zeroed, before the first frame: turns (K, H, E), lost (K, H, N)
+        and unresolved (K,) int32. Refused beyond half the free device memory."""
+        eng = self.eng
+        K, N, E, dev = eng.B, eng.N, eng.E, eng.device
+        if self.turn_acc is None or self.turn_acc["turns"].size(1) != H:
+            self.turn_acc = None
+            need = 4 * K * H * (E + N)
+            free = int(torch.cuda.mem_get_info(dev)[0])
+            if need > free // 2:
+                raise _lib.TarlError(f"the turn counts' tables ({need / 2**30:.2f} GiB for K = {K} environments x H = {H} bins x "
+                                     f"(E = {E} edges + N = {N} roads)) exceed half the free device memory "
+                                     f"({free / 2**30:.2f} GiB free): evaluate fewer environments at a time or widen "
+                                     f"link_bin_seconds")
+            self.turn_acc = {"turns": torch.empty((K, H, E), dtype=torch.int32, device=dev),
+                             "lost": torch.empty((K, H, N), dtype=torch.int32, device=dev),
+                             "unresolved": torch.empty(K, dtype=torch.int32, device=dev)}
+        for v in self.turn_acc.values():
+            v.zero_()
+
+    def _turn_reduce(self, res, sched, on_way):
+        """The tables of a finished run into ``res``, after the two checks: every pop was attributed, and per environment the
+        lost agents are the ON_WAY agents that the network no longer holds (``-reward`` of the last frame is its occupancy)."""
+        eng = self.eng
+        unresolved = self.turn_acc["unresolved"].cpu().numpy()
+        if unresolved.any():
+            raise _lib.TarlError(f"turn counts: {int(unresolved.sum())} pops of a non-empty road whose SELECTED_ROAD byte names no "
+                                 f"out-edge (per environment: {unresolved.tolist()}); such a run is not reported")
+        res.turn_counts, res.turn_lost = self.turn_acc["turns"].cpu().numpy(), self.turn_acc["lost"].cpu().numpy()
+        lost = self.turn_acc["lost"].sum(dim=(1, 2)).cpu().numpy()        # (int64 on the device)
+        queued = -self.reward[res.frames_run - 1].cpu().numpy().astype(np.float64)
+        missing = np.asarray(on_way, dtype=np.float64) - queued
+        if not np.array_equal(lost.astype(np.float64), missing):
+            raise _lib.TarlError(f"turn counts: the phantom pops per environment {lost.tolist()} are not the ON_WAY agents "
+                                 f"queued nowhere {missing.tolist()}")
+        res.turn_stats = {}
+        for k in ("turns", "lost"):
+            st = ops.link_count_stats(self.turn_acc[k])
+            res.turn_stats[k] = link_moments({j: v.cpu().numpy() for j, v in st.items()}, eng.B)
+        prob = None
+        if self.head == "embedding":      # the state-independent policy: its probability of every route edge
+            logits = ops.policy_edge_logits(eng.plan, eng.static_node_features[0], self.emb).view(1, -1)
+            prob = ops.graphdist_softmax(eng.plan, logits, self.temperature).view(-1).cpu().numpy().astype(np.float64)
+        res.turn_meta = dict(first_bin=sched.first_bin, bin_seconds=sched.bin_seconds,
+                             edge_index=eng.edge_index.numpy().copy(), on_way=[int(x) for x in on_way],
+                             queued=[int(x) for x in queued], policy_prob=prob)
 
     def _trip_reduce(self, res, trip_pair, sched):
         """The two trip reductions of a finished run into ``res``. Clock values outside the H bins of the frames (a

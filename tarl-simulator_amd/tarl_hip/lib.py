@@ -141,6 +141,7 @@ SIGNATURES = {
     "tarl_link_counts_accumulate": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
     "tarl_link_count_stats": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "tarl_occupancy_accumulate": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "tarl_turn_counts_accumulate": (C.c_int, [_p] * 5 + [_i64] * 7 + [_p] * 4),
     "tarl_trip_agent_stats": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64] + [_p] * 12 + [_p]),
     "tarl_trip_bin_stats": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64] + [_p] * 6 + [_p]),
     "tarl_td_road_times": (C.c_int, [_p] * 5 + [_i64] * 5 + [_p, _p, _p]),

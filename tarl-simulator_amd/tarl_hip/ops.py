@@ -821,6 +821,52 @@ def occupancy_accumulate(ring, thr, veh, full, peak, *, t0, timestep=1, bin_seco
     return veh, full, peak
 
 
+TURN_COUNTS_MAX_FRAMES = 1 << 23      # the limit of one tarl_turn_counts_accumulate call
+
+
+def turn_counts_accumulate(plan, popped, sel8, counts, turns, lost, unresolved, *, prev_counts=None, t0, timestep=1,
+                           bin_seconds=3600, first_bin=None, frames=None):
+    """The rings of ``frames`` (default: all F) consecutive frames of ``SimEngine.frame_fused`` whose first started at clock
+    ``t0``: ``popped`` uint8 (F, K, N) (env-major), ``sel8`` uint8 (F, N, K) (the engine's ``fs.sel8`` after each frame) and
+    ``counts`` fp32 (F, N, K) (env-minor, the count after the frame); ``prev_counts`` fp32 (N, K): the ``counts`` slice of
+    the frame before the first (``None``: every road was empty, as after a reset). ``turns`` int32 (K, H, E) += the vehicles
+    that crossed each route edge per bin, in the ORIGINAL edge order of ``plan``; ``lost`` int32 (K, H, N) += the frames in
+    which a road was popped although it was empty (the agent the U-turn double pop loses); ``unresolved`` int32 (K,) += the
+    pops of a non-empty road whose SELECTED_ROAD byte names no out-edge. Bins as :func:`link_counts_accumulate`. One launch;
+    a frame outside the H stored bins is refused before anything is launched. Returns ``(turns, lost, unresolved)``."""
+    if popped.dim() != 3:
+        raise ValueError(f"popped must be (F, K, N), got {tuple(popped.shape)}")
+    _meta(popped, torch.uint8, popped.shape, "popped")
+    Fcap, K, N = popped.shape
+    E = plan.num_edges
+    if N != plan.num_nodes:
+        raise ValueError(f"popped must be (F, K, {plan.num_nodes}) for this plan, got {tuple(popped.shape)}")
+    _meta(sel8, torch.uint8, (Fcap, N, K), "sel8")
+    _meta(counts, torch.float32, (Fcap, N, K), "counts")
+    if prev_counts is not None:
+        _meta(prev_counts, torch.float32, (N, K), "prev_counts")
+    if turns.dim() != 3:
+        raise ValueError(f"turns must be (K, H, E), got {tuple(turns.shape)}")
+    H = turns.size(1)
+    _meta(turns, torch.int32, (K, H, E), "turns")
+    _meta(lost, torch.int32, (K, H, N), "lost")
+    _meta(unresolved, torch.int32, (K,), "unresolved")
+    if K < 1 or N < 1 or H < 1 or E < 1:
+        raise ValueError("the rings and the tables must not be empty")
+    F, t0, timestep, bin_seconds, first_bin = _bin_schedule(frames, Fcap, TURN_COUNTS_MAX_FRAMES, t0, timestep, bin_seconds,
+                                                            first_bin, H)
+    for t, dt, name in ((popped, torch.uint8, "popped"), (sel8, torch.uint8, "sel8"), (counts, torch.float32, "counts"),
+                        (turns, torch.int32, "turns"), (lost, torch.int32, "lost"), (unresolved, torch.int32, "unresolved")):
+        _check_dev(t, dt, name)
+    if prev_counts is not None:
+        _check_dev(prev_counts, torch.float32, "prev_counts")
+    _lib.check(_lib.load().tarl_turn_counts_accumulate(plan.handle, popped.data_ptr(), sel8.data_ptr(), counts.data_ptr(),
+                                                       _lib.ptr(prev_counts), F, K, t0, timestep, bin_seconds, first_bin, H,
+                                                       turns.data_ptr(), lost.data_ptr(), unresolved.data_ptr(),
+                                                       _lib.current_stream()))
+    return turns, lost, unresolved
+
+
 TRIP_MAX_BINS = 4096      # = TARL_TRIP_MAX_BINS of include/tarl_hip.h: the arrivals histogram of one environment lives in LDS
 _TRIP_AGENT_SPEC = (("n_done", torch.int32), ("n_way", torch.int32), ("tt_sum", torch.float64), ("tt_sumsq", torch.float64),
                     ("tt_min", torch.float32), ("tt_max", torch.float32))
