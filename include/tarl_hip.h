@@ -877,7 +877,19 @@ int tarl_select_next_hop_dest(float* x, int64_t B, int64_t x_bstride, int64_t ld
  *   tarl_select_next_hop_dest's rules hold: an empty FIFO reads agent 0; a head, destination or slot out of range leaves the
  *   row's previous selection untouched. After this call the SELECTED_ROAD column of tarl_fused_export equals, bit for bit,
  *   the column tarl_select_next_hop_dest writes into the exported x of the same state with environment b's table.
- *   choice8 (optional) uint8 [B][N]: the rows' sel8 bytes after the call, env-major. */
+ *   choice8 (optional) uint8 [B][N]: the rows' sel8 bytes after the call, env-major.
+ * tarl_fused_select_next_hop_hold: the same kernel, arguments and host checks with ONE rule added, and NOT
+ *   DijkstraAgents.choice (src/agents/base.py:572-580): where the next hop read from the table equals the head agent's
+ *   destination (integers compared, before the conversion to float) the row's own id i is written instead of the next hop.
+ *   Why: in the environment's step order (SimulatorEnv._step, src/reinforcement_learning.py:222-309: choice, core,
+ *   withdraw / insert, reward) the core moves a due agent from the last road before its destination onto the destination
+ *   road, and the withdraw rule (Agents.withdraw_agent_from_network, src/agents/base.py:348-403: agents on a road ADJACENT
+ *   to their destination whose departure there is due) never collects it. Held one road short, the agent is withdrawn as soon as it is due there. The own id, not -1: insert
+ *   (Agents.insert_agent_into_network, src/agents/base.py:247-331) reads
+ *   SELECTED_ROAD of an agent's origin row as the road to enter (a ready agent whose origin row holds enters the origin road
+ *   itself), and -1 would index the last row in the reference's torch indexing. The row's own id matches no out-edge (the
+ *   network builders make no self-loops; with one, a holding agent would take the loop — not handled), so the code is the
+ *   raw one and the row moves nobody. On the destination road itself the table already holds i: nothing changes there. */
 int tarl_fused_edge_travel_time(const tarl_plan* plan, const tarl_fused* f, int64_t B, float* travel_time,
                                 tarl_stream stream);
 int64_t tarl_dest_trees_batched_scratch_bytes(const tarl_plan* plan, int64_t B, int64_t num_dests);
@@ -885,6 +897,9 @@ int tarl_dest_trees_batched(const tarl_plan* plan, const float* weights, int64_t
                             int64_t num_dests, void* scratch, int64_t scratch_bytes, int32_t* next_hop_out,
                             tarl_stream stream);
 int tarl_fused_select_next_hop_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                                    const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride,
+                                    int64_t num_dests, uint8_t* choice8, tarl_stream stream);
+int tarl_fused_select_next_hop_hold(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
                                     const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride,
                                     int64_t num_dests, uint8_t* choice8, tarl_stream stream);
 

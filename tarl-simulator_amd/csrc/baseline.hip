@@ -52,7 +52,15 @@ __global__ __launch_bounds__(TT_BLOCK) void k_fused_edge_travel_time(const int32
 // slot store holds at the ring offset (k_export_rows); a head, destination or slot out of range leaves the row untouched.
 // The value written is (float)next_hop; the code is the rank of the first out-edge of i whose target converts to that
 // value (k_pack_nodes' rule), else SEL_RAW with the value in `sel`: the destination itself, -1, an entry no out-edge matches.
+// HOLD (tarl_fused_select_next_hop_hold; NOT DijkstraAgents.choice): where the next hop IS the destination, the row's own id
+// is written instead. The comparison is made on the integers, before the conversion. In the environment's step order
+// (SimulatorEnv._step: choice, core, withdraw / insert, reward) the core would carry that head onto its destination road,
+// which the withdraw rule (roads adjacent to the destination) never collects from; held one road short, the head is
+// collected as soon as it is due. No out-edge targets the row itself (the builders make no self-loops; on such a graph a
+// holding head would take the loop), so a holding row stores SEL_RAW and its id and the core moves nobody from it. On the
+// destination road the table already holds the road's id: nothing changes there. Same 21 B per (row, environment).
 #define FS_BLOCK 256
+template <bool HOLD>
 __global__ __launch_bounds__(FS_BLOCK) void k_fused_select_next_hop_dest(
     const uint2* __restrict__ hdp, const uint32_t* __restrict__ tl, const uint8_t* __restrict__ gc8,
     const float* __restrict__ slots, int64_t lds, int Nmax, const NodeRec* __restrict__ nodes,
@@ -78,7 +86,9 @@ __global__ __launch_bounds__(FS_BLOCK) void k_fused_select_next_hop_dest(
     if (dest >= 0 && dest < N) {
       const int32_t slot = dest_slot[dest];
       if (slot >= 0 && slot < D) {
-        const float sv = (float)next_hop[(int64_t)b * nh_bstride + (int64_t)slot * N + i];
+        int32_t nh = next_hop[(int64_t)b * nh_bstride + (int64_t)slot * N + i];
+        if (HOLD && nh == dest) nh = (int32_t)i;
+        const float sv = (float)nh;
         const NodeRec& nr = nodes[i];
         const int32_t deg = nr.out_deg;
 #pragma unroll
@@ -117,9 +127,10 @@ extern "C" int tarl_fused_edge_travel_time(const tarl_plan* plan, const tarl_fus
   return TARL_OK;
 }
 
-extern "C" int tarl_fused_select_next_hop_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax,
-                                               int64_t num_agents, const int32_t* dest_slot, const int32_t* next_hop,
-                                               int64_t nh_bstride, int64_t num_dests, uint8_t* choice8, tarl_stream stream) {
+template <bool HOLD>
+static int fused_select_launch(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                               const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride, int64_t num_dests,
+                               uint8_t* choice8, tarl_stream stream) {
   TARL_REQUIRE(plan && f && dest_slot && next_hop, "null argument");
   const int rc = tarl_check_fused_core(plan, f, B, Nmax);
   if (rc != TARL_OK) return rc;
@@ -127,11 +138,23 @@ extern "C" int tarl_fused_select_next_hop_dest(const tarl_plan* plan, const tarl
   TARL_REQUIRE(num_dests >= 0 && nh_bstride >= 0, "bad sizes");
   if (plan->N == 0) return TARL_OK;
   const int64_t NB = plan->N * B;
-  hipLaunchKernelGGL(k_fused_select_next_hop_dest, dim3((unsigned)ceil_div(NB, FS_BLOCK)), dim3(FS_BLOCK), 0,
+  hipLaunchKernelGGL(k_fused_select_next_hop_dest<HOLD>, dim3((unsigned)ceil_div(NB, FS_BLOCK)), dim3(FS_BLOCK), 0,
                      (hipStream_t)stream, (const uint2*)f->hdp, (const uint32_t*)f->tl, (const uint8_t*)f->gc8,
                      (const float*)f->slots, f->ld_slots, (int)Nmax, (const NodeRec*)f->node_rec,
                      (const int32_t*)f->out_pad, (const int32_t*)f->a_dest, num_agents, (uint32_t)B, (uint32_t)NB, plan->N,
                      dest_slot, next_hop, nh_bstride, num_dests, f->sel8, f->sel, choice8);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
+}
+
+extern "C" int tarl_fused_select_next_hop_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax,
+                                               int64_t num_agents, const int32_t* dest_slot, const int32_t* next_hop,
+                                               int64_t nh_bstride, int64_t num_dests, uint8_t* choice8, tarl_stream stream) {
+  return fused_select_launch<false>(plan, f, B, Nmax, num_agents, dest_slot, next_hop, nh_bstride, num_dests, choice8, stream);
+}
+
+extern "C" int tarl_fused_select_next_hop_hold(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax,
+                                               int64_t num_agents, const int32_t* dest_slot, const int32_t* next_hop,
+                                               int64_t nh_bstride, int64_t num_dests, uint8_t* choice8, tarl_stream stream) {
+  return fused_select_launch<true>(plan, f, B, Nmax, num_agents, dest_slot, next_hop, nh_bstride, num_dests, choice8, stream);
 }

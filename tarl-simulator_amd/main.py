@@ -4,7 +4,7 @@
 ``--num-envs`` (vectorised environments per GPU), ``--policy-head``, ``--value-head``, ``--prior-method``,
 ``--dijkstra-method``, ``--equilibrium-metrics`` (with ``--equilibrium-gap`` / ``--equilibrium-max-iter``), ``--iterations``,
 ``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
-comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` and the per-road link counts of either
+comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` (its router: ``--dijkstra-router``) and the per-road link counts of either
 ``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy``, ``--eval-trips``,
 ``--eval-dynamic-gap`` and ``--eval-turns``)."""
 import argparse
@@ -76,17 +76,25 @@ OPTIONS = (
                               "a normal-approximation interval of return and travel times over the K realisations; train: "
                               "eval_vec/* in train_log.jsonl, eval: a printed block, eval_envs.json and eval_envs.csv")),
     ("--eval-sampled", dict(action="store_true", help="--eval-envs: also report a run with sampled actions")),
-    ("--eval-baseline", dict(choices=("none", "dijkstra"), default="none",
-                             help="--eval-envs: also run the shortest-path (dijkstra) router on a second engine with the same "
+    ("--eval-baseline", dict(choices=("none", "dijkstra", "dijkstra_hold", "free_flow"), default="none",
+                             help="--eval-envs: also run the shortest-path router on a second engine with the same "
                                   "seed, K and population (the same noise streams: common random numbers) and report the "
                                   "per-environment differences policy - baseline with their standard error; train: "
                                   "eval_vec_baseline/* and eval_vec_paired/* in train_log.jsonl, eval: two more printed "
-                                  "blocks, `baseline` and `paired` in eval_envs.json, baseline_* columns in eval_envs.csv")),
+                                  "blocks, `baseline` and `paired` in eval_envs.json, baseline_* columns in eval_envs.csv. "
+                                  "dijkstra: the reference's rule, which in the environment's step order strands its agents "
+                                  "on their destination roads; dijkstra_hold: a row whose next hop is its head's destination "
+                                  "holds, so the agent is withdrawn one road short and the router delivers; free_flow: "
+                                  "dijkstra_hold on tables built once from the empty network")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "
                                   "environment's step order); prints the aggregate block, writes dijkstra_envs.json and "
                                   "dijkstra_envs.csv")),
+    ("--dijkstra-router", dict(choices=("reference", "hold", "free_flow"), default="reference",
+                               help="--dijkstra-envs: the router of the K environments; reference: DijkstraAgents.choice's rule, "
+                                    "hold: the one that holds one road short of the destination and delivers (head "
+                                    "dijkstra_hold), free_flow: hold on tables built once from the empty network")),
     ("--eval-link-counts", dict(action="store_true",
                                 help="--eval-envs / --dijkstra-envs, eval: count per road the frames in which its head was "
                                      "popped plus those in which an agent was withdrawn from it, over the K environments; a "

@@ -13,7 +13,8 @@ environments of its own fused engine, MODE, with ``stochastic_eval`` also sample
 scalars ``eval_vec/*`` (``eval_vec_stochastic/*``) carry the spread over the K realisations of the stochastic simulator
 that the single drop-in rollout cannot give. The ``eval/*`` record is unchanged.
 
-Extension: ``eval_baseline="dijkstra"`` (with ``eval_envs``) evaluates the shortest-path router once, at the first periodic
+Extension: ``eval_baseline="dijkstra"`` (or ``"dijkstra_hold"`` / ``"free_flow"``, the routers that deliver in the environment's
+step order; with ``eval_envs``) evaluates the shortest-path router once, at the first periodic
 evaluation, on a second engine with the same seed, K and population (rank 0 alone, no collective): it is a function of the
 seed only, so its per-environment values are cached, and every record that carries ``eval_vec/*`` also carries
 ``eval_vec_baseline/*`` and the paired differences policy - baseline ``eval_vec_paired/*`` (common random numbers).
@@ -31,6 +32,8 @@ import torch
 
 from ..agents.base import destination_set
 from .modules import unwrap
+
+EVAL_BASELINE_NAMES = ("none", "dijkstra", "dijkstra_hold", "free_flow")      # tarl_hip.evaluator.EVAL_BASELINES, and "none"
 
 
 def _episode_returns(reward_tb, done_t):
@@ -185,8 +188,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature)
                 if eval_envs and eval_env is not None and log is not None else None)
     ppo_train.last_vec_eval = vec_eval
-    if eval_baseline not in ("none", "dijkstra"):
-        raise ValueError(f"eval_baseline must be 'none' or 'dijkstra', got {eval_baseline!r}")
+    if eval_baseline not in EVAL_BASELINE_NAMES:
+        raise ValueError(f"eval_baseline must be one of {EVAL_BASELINE_NAMES}, got {eval_baseline!r}")
     if eval_baseline != "none" and not eval_envs:
         raise ValueError("eval_baseline needs eval_envs > 0")
     baseline_res = None                       # the router's EvalResult: evaluated once, a function of the seed only
@@ -232,11 +235,12 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                     res = vec_eval.run(n_eval, deterministic=det)
                     rec.update(vec_eval_record(prefix, res))
                     ppo_train.last_eval[prefix] = res
-                if eval_baseline == "dijkstra":
-                    from tarl_hip.evaluator import VecEvaluator, paired_report, paired_scalars
+                if eval_baseline != "none":
+                    from tarl_hip.evaluator import EVAL_BASELINES, VecEvaluator, paired_report, paired_scalars
                     if baseline_res is None:      # its engine and tables are released once the numbers are cached
+                        b_head, b_kw = EVAL_BASELINES[eval_baseline]
                         baseline_res = VecEvaluator(_eval_engine(eval_env, eval_envs, seed, baseline_agents),
-                                                    "dijkstra").run(n_eval)
+                                                    b_head, **b_kw).run(n_eval)
                     rec.update(vec_eval_record("eval_vec_baseline", baseline_res))
                     rep = paired_report(ppo_train.last_eval["eval_vec"], baseline_res)
                     rec.update({f"eval_vec_paired/{k}": v for k, v in paired_scalars(rep).items()})

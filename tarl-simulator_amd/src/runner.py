@@ -35,8 +35,10 @@ class RunnerArgs:
     equilibrium_max_iter: int = 500      # and its iteration limit per problem
     eval_envs: int = 0             # mpnn / mpnn+ppo: K > 0 adds the vectorised evaluation (tarl_hip.evaluator) on K environments
     eval_sampled: bool = False     # ... and also a sampled one next to the deterministic (MODE) one
-    eval_baseline: str = "none"    # eval_envs: "dijkstra" adds the shortest-path baseline on a second engine + the paired report
+    eval_baseline: str = "none"    # eval_envs: "dijkstra" adds the shortest-path baseline on a second engine + the paired report;
+    #                                "dijkstra_hold": the router that holds one road short and delivers; "free_flow": that one on static tables
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
+    dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
     eval_link_bin: int = 3600      # ... in time bins of this many seconds
     eval_occupancy: bool = False   # eval_envs / dijkstra_envs: per-road occupancy and time at capacity (bins of eval_link_bin)
@@ -59,8 +61,8 @@ class RunnerArgs:
                              f"{self.algo!r} (use mpnn or mpnn+ppo)")
         if self.eval_sampled and not self.eval_envs:
             raise ValueError("eval_sampled adds a sampled run to the vectorised evaluation: it needs eval_envs > 0")
-        if self.eval_baseline not in ("none", "dijkstra"):
-            raise ValueError(f"eval_baseline must be 'none' or 'dijkstra', got {self.eval_baseline!r}")
+        if self.eval_baseline not in EVAL_BASELINE_NAMES:
+            raise ValueError(f"eval_baseline must be one of {EVAL_BASELINE_NAMES}, got {self.eval_baseline!r}")
         if self.eval_baseline != "none" and not (self.eval_envs and self.algo in ("mpnn", "mpnn+ppo")):
             raise ValueError("eval_baseline compares the vectorised evaluation of a policy network with the shortest-path "
                              "router: it needs eval_envs > 0 and algo mpnn or mpnn+ppo")
@@ -69,6 +71,10 @@ class RunnerArgs:
         if self.dijkstra_envs and not (self.algo == "dijkstra" and self.mode == "eval"):
             raise ValueError("dijkstra_envs evaluates the shortest-path router on the vectorised engine: only with algo "
                              "'dijkstra' and mode 'eval'")
+        if self.dijkstra_router not in DIJKSTRA_ROUTER_NAMES:
+            raise ValueError(f"dijkstra_router must be one of {DIJKSTRA_ROUTER_NAMES}, got {self.dijkstra_router!r}")
+        if self.dijkstra_router != "reference" and not self.dijkstra_envs:
+            raise ValueError("dijkstra_router selects the router of the vectorised dijkstra evaluation: it needs dijkstra_envs > 0")
         if self.eval_link_counts and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_link_counts counts per-road pops and withdrawals in the vectorised evaluation: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
@@ -109,6 +115,9 @@ class RunnerArgs:
                              "head's rollout does not build: use a state-dependent policy head (edge_mlp*, "
                              "embedding_dijkstra or graph_transformer)")
 
+
+EVAL_BASELINE_NAMES = ("none", "dijkstra", "dijkstra_hold", "free_flow")      # tarl_hip.evaluator.EVAL_BASELINES, and "none"
+DIJKSTRA_ROUTER_NAMES = ("reference", "hold", "free_flow")                      # tarl_hip.evaluator.DIJKSTRA_ROUTERS
 
 CHECKPOINT_PREFIX = "module.0.module."      # ProbabilisticActor -> TensorDictModule -> the network (ppo_train's keys)
 
@@ -421,16 +430,19 @@ class Runner:
                     print(line)
 
     def _vectorised_dijkstra(self, frames, out_dir):
-        """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra":
+        """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra", or
+        "dijkstra_hold" with --dijkstra-router hold / free_flow:
         every environment routes on its own congested travel times, in the environment's step order) for the same number of
         frames as the pass above; prints the aggregate block, writes dijkstra_envs.json / dijkstra_envs.csv in the format of
         eval_envs.*. -> {"mode": EvalResult}."""
         import csv
         import json
-        from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator
+        from tarl_hip.evaluator import DIJKSTRA_ROUTERS, PER_ENV_KEYS, VecEvaluator, router_label
         engine = self._eval_engine(self.simulator, self._dijkstra_population, self.args.dijkstra_envs)
-        res = VecEvaluator(engine, "dijkstra", refresh_rate=self.agent.refresh_rate, **self._link_kw()).run(frames)
-        self._print_block(f"Vectorised evaluation ({res.envs} environments, dijkstra)", res)
+        head, refresh = DIJKSTRA_ROUTERS[self.args.dijkstra_router]      # --dijkstra-router: reference / hold / free_flow
+        res = VecEvaluator(engine, head, refresh_rate=self.agent.refresh_rate if refresh is None else refresh,
+                           **self._link_kw()).run(frames)
+        self._print_block(f"Vectorised evaluation ({res.envs} environments, {router_label(res)})", res)
         out_dir.mkdir(parents=True, exist_ok=True)
         doc = {"mode": res.to_dict()}
         self._reports_output(doc, res, None, out_dir, "dijkstra")
@@ -446,7 +458,8 @@ class Runner:
         """--eval-envs K: the policy on K environments of a fused engine of its own (copies of the graph state and the agent
         table; noise seed ``seed + 104729``) for the same number of frames as the pass above, MODE and with --eval-sampled
         also sampled: prints the aggregate block(s), writes eval_envs.json (aggregate + settings) and eval_envs.csv (one row
-        per environment). With --eval-baseline dijkstra the shortest-path router then runs on a second engine of the same seed,
+        per environment). With --eval-baseline dijkstra (dijkstra_hold, free_flow: the routers of DESIGN 4.13a, titled by their
+        head's name) the shortest-path router then runs on a second engine of the same seed,
         K and population: a ``Baseline (dijkstra)`` block, a paired block, ``baseline`` / ``paired`` in the JSON, ``baseline_*``
         columns in the CSV. -> {"mode": EvalResult, "sampled": EvalResult or None[, "baseline": EvalResult, "paired": dict]}."""
         import csv
@@ -461,7 +474,7 @@ class Runner:
         ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw())
         results = {"mode": ev.run(frames, deterministic=True), "sampled": None}
         pair = None
-        if a.eval_trips and a.eval_baseline == "dijkstra" and not results["mode"].domain_exit:
+        if a.eval_trips and a.eval_baseline != "none" and not results["mode"].domain_exit:
             # the MODE run's agent tables, for the baseline's paired launch: a sampled run would overwrite them
             pair = engine.agents.clone() if a.eval_sampled else engine.agents
         if a.eval_sampled:
@@ -475,13 +488,14 @@ class Runner:
             doc[key] = res.to_dict()
             rows += [dict(kind=key, **r) for r in res.rows()]
         fields = ("kind", "env") + PER_ENV_KEYS
-        if a.eval_baseline == "dijkstra":
+        if a.eval_baseline != "none":
             # the router on a second engine with the same seed, K and population: the same noise streams as the policy run
-            from tarl_hip.evaluator import paired_lines, paired_report
-            base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), "dijkstra",
-                                **self._link_kw()).run(frames, trip_pair=pair)
+            from tarl_hip.evaluator import EVAL_BASELINES, paired_lines, paired_report, router_label
+            b_head, b_kw = EVAL_BASELINES[a.eval_baseline]      # dijkstra / dijkstra_hold / free_flow (hold, static tables)
+            base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), b_head,
+                                **b_kw, **self._link_kw()).run(frames, trip_pair=pair)
             rep = paired_report(results["mode"], base)
-            self._print_block("Baseline (dijkstra)", base)
+            self._print_block(f"Baseline ({router_label(base)})", base)
             print("\n=== Policy \u2212 baseline (paired) ===")
             for line in paired_lines(rep):
                 print(line)

@@ -26,8 +26,13 @@ noise streams are keyed by (seed, frame counter, env_base + b), so a baseline ru
 Gumbel race values of the policy run (common random numbers), and :func:`paired_report` compares the two per environment.
 In that order the core moves a due agent from the last road before its destination ONTO the destination road before the
 withdraw (which collects from roads ADJACENT to the destination) sees it; there the table names the road itself, the row
-moves nobody, and the agent stays: the router delivers only agents whose last hop was delayed. Read its
-``arrived`` with that in mind; the return (the network's occupancy) compares as it stands.
+moves nobody, and the agent stays: the router delivers only agents whose last hop was delayed.
+
+Head ``"dijkstra_hold"`` is the router that delivers in that order (NOT the reference's rule): a row whose
+next hop is its head agent's destination selects ITSELF (``ops.fused_select_next_hop_dest(hold=True)``), the core moves
+nobody from it, and the withdraw collects the agent there once it is due. Everything else is the ``"dijkstra"`` head's. With
+``refresh_rate=0`` it builds its tables at frame 0 only: after the reset every count is 0, so this is the free-flow
+(all-or-nothing) router under the router's own weight expression. (``"dijkstra"`` keeps refusing 0, as it always has.)
 """
 from __future__ import annotations
 
@@ -51,7 +56,20 @@ from .eval_reports import (CONGESTION_FILE, DYNAMIC_GAP_NOTE, LINK_EXPECTED, LIN
                            trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report, trip_summary,
                            turn_bin_names, turn_lines, turn_report, turn_summary)
 
-HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra")
+HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra",
+         "dijkstra_hold")
+ROUTER_HEADS = ("dijkstra", "dijkstra_hold")      # the shortest-path routers: no policy tensors, no sampled mode
+# the names of --eval-baseline / ppo_train(eval_baseline=) -> (head, its VecEvaluator arguments); "free_flow": the hold router
+# on tables built once from the empty network
+EVAL_BASELINES = {"dijkstra": ("dijkstra", {}), "dijkstra_hold": ("dijkstra_hold", {}),
+                  "free_flow": ("dijkstra_hold", {"refresh_rate": 0})}
+# the names of --dijkstra-router -> (head, refresh_rate override or None for the agent's own)
+DIJKSTRA_ROUTERS = {"reference": ("dijkstra", None), "hold": ("dijkstra_hold", None), "free_flow": ("dijkstra_hold", 0)}
+
+
+def router_label(res):
+    """The name a printed block gives a router run: its head, and the static tables where it has them."""
+    return res.head + (", refresh_rate 0" if res.settings.get("refresh_rate") == 0 else "")
 _MLP_PRECISION = {"edge_mlp": "x3", "edge_mlp_fp32": "fp32", "edge_mlp_bf16": "bf16"}
 PER_ENV_KEYS = ("episode_return", "frames", "arrived", "on_way", "not_departed", "avg_travel_time", "std_travel_time",
                 "max_travel_time", "p50_travel_time", "p95_travel_time")
@@ -266,8 +284,9 @@ class VecEvaluator:
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
         (graph_transformer). The tensors are read at every frame: views of live parameters evaluate the current policy.
         ``keep_actions``: also record every frame's action bytes in ``actions`` (T, K, N) uint8 (tests).
-        Head ``"dijkstra"`` (the shortest-path baseline, no ``emb``): ``refresh_rate`` frames between two rebuilds of the K
-        per-environment next-hop tables; ``baseline_dests`` = (dests int64 (D,), dest_slot int32 (N,)) of
+        Heads ``"dijkstra"`` and ``"dijkstra_hold"`` (the shortest-path baselines, no ``emb``; the second holds a head one
+        road short of its destination, module docstring): ``refresh_rate`` frames between two rebuilds of the K
+        per-environment next-hop tables, for ``"dijkstra_hold"`` also 0 = built at frame 0 only (the free-flow router); ``baseline_dests`` = (dests int64 (D,), dest_slot int32 (N,)) of
         src.agents.base.destination_set over the engine's agent tables (default: computed here by the same rule). The
         (K, D, N) int32 table and the tree scratch are allocated once; more than half the free device memory is refused.
         ``link_counts``: also count, per environment, road and time bin of ``link_bin_seconds``, the frames in which the
@@ -312,12 +331,12 @@ class VecEvaluator:
             raise ValueError("head 'embedding_dijkstra' needs prior_table (and dest_slot for a per-destination table)")
         if head == "graph_transformer" and (gt_pe is None or gt_weights is None):
             raise ValueError("head 'graph_transformer' needs gt_pe and gt_weights")
-        if head != "dijkstra" and emb is None:
+        if head not in ROUTER_HEADS and emb is None:
             raise ValueError(f"head {head!r} needs emb (the flat embedding tensor)")
         if int(poll_frames) < 1:
             raise ValueError("poll_frames must be >= 1")
-        if int(refresh_rate) < 1:
-            raise ValueError("refresh_rate must be >= 1")
+        if int(refresh_rate) < (0 if head == "dijkstra_hold" else 1):
+            raise ValueError("refresh_rate must be >= 1 (head 'dijkstra_hold' also takes 0: tables built at frame 0 only)")
         self.eng, self.head = engine, head
         self.emb = emb
         self.temperature = float(temperature)
@@ -393,7 +412,7 @@ class VecEvaluator:
         if head == "embedding":
             self.mode8 = torch.zeros((1, N), dtype=torch.uint8, device=dev)
             self.mode_lp = torch.zeros(1, dtype=torch.float32, device=dev)
-        elif head == "dijkstra":
+        elif head in ROUTER_HEADS:
             self._init_baseline(baseline_dests)
         else:
             self.logits = torch.empty((K, E), dtype=torch.float32, device=dev)
@@ -535,13 +554,14 @@ class VecEvaluator:
 
     def _frame_head(self, t, deterministic, rec, masks):
         eng = self.eng
-        if self.head == "dijkstra":     # choice -> core -> withdraw / insert -> reward: the environment's step order
+        if self.head in ROUTER_HEADS:   # choice -> core -> withdraw / insert -> reward: the environment's step order
             if eng._packed_stale:
                 eng.resync()
-            if t % self.refresh_rate == 0:
+            if t == 0 if self.refresh_rate == 0 else t % self.refresh_rate == 0:
                 ops.fused_edge_travel_time(eng.plan, eng.fs, out=self.weights)
                 ops.destination_trees_batched(eng.plan, self.weights, self.dests, out=self.table, scratch=self.tree_scratch)
-            ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec)
+            ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec,
+                                           hold=self.head == "dijkstra_hold")
             return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
         if self.head == "embedding":
             if rec is not None and deterministic:
@@ -570,8 +590,8 @@ class VecEvaluator:
         T = self.episode_frames if frames is None else int(frames)
         if T < 1:
             raise ValueError("frames must be >= 1")
-        if self.head == "dijkstra" and not deterministic:
-            raise ValueError("head 'dijkstra' has no sampled mode: the shortest-path router is deterministic given the state")
+        if self.head in ROUTER_HEADS and not deterministic:
+            raise ValueError(f"head {self.head!r} has no sampled mode: the shortest-path router is deterministic given the state")
         if trip_pair is not None and not self.trips:
             raise ValueError("trip_pair pairs the trips of two runs: it needs trips=True")
         self._reserve(T)
@@ -639,8 +659,10 @@ class VecEvaluator:
         polls[-1][1].synchronize()
         settings = dict(bin_width=self.bin_width, num_bins=self.num_bins, temperature=self.temperature, seed=eng.seed,
                         env_base=fs.env_base, poll_frames=self.poll_frames, agents=eng.A - 1, nodes=eng.N)
-        if self.head == "dijkstra":
+        if self.head in ROUTER_HEADS:
             settings.update(refresh_rate=self.refresh_rate, destinations=int(self.dests.numel()))
+        if self.head == "dijkstra_hold":      # (the "dijkstra" head's settings stay as they were)
+            settings["hold"] = True
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):

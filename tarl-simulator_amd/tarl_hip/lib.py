@@ -138,6 +138,7 @@ SIGNATURES = {
     "tarl_dest_trees_batched_scratch_bytes": (_i64, [_p, _i64, _i64]),
     "tarl_dest_trees_batched": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _p]),
     "tarl_fused_select_next_hop_dest": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _i64, _i64, _p, _p]),
+    "tarl_fused_select_next_hop_hold": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _i64, _i64, _p, _p]),
     "tarl_link_counts_accumulate": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
     "tarl_link_count_stats": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "tarl_occupancy_accumulate": (C.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),

@@ -537,11 +537,13 @@ def destination_trees_batched(plan: Plan, weights, dests, *, B=None, out=None, s
     return out
 
 
-def fused_select_next_hop_dest(plan: Plan, fs, dest_slot, next_hop, choice8=None):
+def fused_select_next_hop_dest(plan: Plan, fs, dest_slot, next_hop, choice8=None, hold=False):
     """:func:`select_next_hop_dest` on the packed state (tarl_fused_select_next_hop_dest): the SELECTED_ROAD bytes of ``fs``
     <- the next hop towards the destination of every row's head agent. ``next_hop`` int32 (D, N) shared by the
     environments, or (B, D, N) with environment b's table; ``dest_slot`` (N,) int32. ``choice8`` (B, N) uint8 (optional):
-    the rows' bytes after the call, env-major."""
+    the rows' bytes after the call, env-major. ``hold`` (tarl_fused_select_next_hop_hold, not the reference's rule): a row
+    whose next hop is its head agent's destination selects ITSELF instead, so that the environment's step order withdraws
+    the agent there instead of stranding it on its destination road."""
     L = _lib.load()
     N = plan.num_nodes
     _check_dev(fs.hdp, torch.int32, "fs.hdp")
@@ -556,9 +558,9 @@ def fused_select_next_hop_dest(plan: Plan, fs, dest_slot, next_hop, choice8=None
         _contig(choice8, torch.uint8, "choice8")
         if tuple(choice8.shape) != (fs.B, N):
             raise ValueError(f"choice8 must be (B, N) = ({fs.B}, {N})")
-    _lib.check(L.tarl_fused_select_next_hop_dest(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, dest_slot.data_ptr(),
-                                                 next_hop.data_ptr(), D * N if next_hop.dim() == 3 else 0, D,
-                                                 _lib.ptr(choice8), _lib.current_stream()))
+    entry = L.tarl_fused_select_next_hop_hold if hold else L.tarl_fused_select_next_hop_dest
+    _lib.check(entry(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, dest_slot.data_ptr(), next_hop.data_ptr(),
+                     D * N if next_hop.dim() == 3 else 0, D, _lib.ptr(choice8), _lib.current_stream()))
     return choice8
 
 
