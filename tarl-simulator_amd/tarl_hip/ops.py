@@ -1304,16 +1304,28 @@ def policy_edge_mlp(plan: Plan, obs16, ec: EdgeConst, w: EdgeMlpWeights, *, bf16
     return logits
 
 
-def policy_edge_mlp_bwd(plan: Plan, obs16, ec: EdgeConst, w: EdgeMlpWeights, grad_logits, grads):
-    """Accumulates into ``grads`` = (gw1, gb1, gw2, gb2, gw3, gb3), tensors shaped like the weights (fp32, contiguous)."""
+def edge_mlp_bwd_scratch_floats(plan: Plan, M: int) -> int:
+    """fp32 elements of device scratch one tarl_policy_edge_mlp_bwd call over ``M`` samples needs (k-major activations and
+    their gradients of every edge + the split partial sums)."""
+    return int(_lib.load().tarl_policy_edge_mlp_bwd_scratch_floats(plan.handle, int(M)))
+
+
+def policy_edge_mlp_bwd(plan: Plan, obs16, ec: EdgeConst, w: EdgeMlpWeights, grad_logits, grads, scratch=None):
+    """Accumulates into ``grads`` = (gw1, gb1, gw2, gb2, gw3, gb3), tensors shaped like the weights (fp32, contiguous).
+    ``scratch``: an fp32 contiguous device tensor of at least ``edge_mlp_bwd_scratch_floats(plan, M)`` elements to reuse
+    across calls (ValueError otherwise; allocated per call when None). The kernels write every element they read."""
     L = _lib.load()
     _contig(obs16, torch.float32, "obs16")
     gl = _contig(grad_logits, torch.float32, "grad_logits")
     M = obs16.size(0)
     if gl.numel() != M * plan.num_edges:
         raise ValueError("grad_logits must be (M, E)")
-    scratch = torch.empty(int(L.tarl_policy_edge_mlp_bwd_scratch_floats(plan.handle, M)), dtype=torch.float32,
-                          device=obs16.device)
+    need = int(L.tarl_policy_edge_mlp_bwd_scratch_floats(plan.handle, M))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=obs16.device)
+    elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.float32 or not scratch.is_contiguous()
+          or scratch.device != obs16.device or scratch.numel() < need):
+        raise ValueError(f"scratch must be a contiguous fp32 tensor on {obs16.device} of at least {need} elements")
     gs = [_contig(g, torch.float32, "grad") for g in grads]
     _lib.check(L.tarl_policy_edge_mlp_bwd(plan.handle, obs16.data_ptr(), M, ec.edge_attr.data_ptr(), *w.ptrs(),
                                           gl.data_ptr(), scratch.data_ptr(), *(g.data_ptr() for g in gs),
