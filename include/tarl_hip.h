@@ -599,8 +599,10 @@ int tarl_fused_prior_logits(const tarl_plan* plan, const tarl_fused* f, const fl
                             float* logits, tarl_stream stream);
 /* tarl_fused_rollout_prior: tarl_fused_rollout_policy with the prior head — T frames in one foreign call, per frame
  *   [tarl_fused_obs16_rows of the kept environments] -> tarl_fused_prior_logits -> tarl_graphdist_rollout (temperature;
- *   policy counter policy_counter0 + t; writes the action into tarl_fused.sel8) -> tarl_fused_frame with that action (Direction,
- *   rows, insert; noise counter counter0 + t) -> the count bytes, with the same results as those calls made one by one.
+ *   policy counter policy_counter0 + t; writes the action into tarl_fused.sel8) -> Direction gather -> row pass -> insert
+ *   with that action (noise counter counter0 + t; the frame kernels write the count bytes), the loop of
+ *   tarl_fused_rollout_policy with another head: arguments checked once per call, same results as tarl_fused_prior_logits,
+ *   tarl_graphdist_rollout and tarl_fused_frame called one by one.
  *   keep_ptr_host / keep_env / keep_slot / obs_keep: as tarl_fused_rollout_policy (fp32 observations of the pre-drawn
  *   minibatch frames: what the PPO update needs to recompute the prior exactly). Scratch (device): logits_scratch fp32
  *   [B][E], dist_scratch (tarl_graphdist_rollout_scratch_bytes), ins_scratch int32 [B][2A]. Outputs, frame-major, nullable:
@@ -687,8 +689,9 @@ int tarl_policy_gt_bwd(const tarl_plan* plan, const float* obs16, int64_t M, con
 /* tarl_fused_rollout_gt: tarl_fused_rollout_prior with the graph-transformer head — T frames in one foreign call, per frame
  *   [tarl_fused_obs16_rows of the kept environments] -> tarl_fused_obs16 (obs_scratch fp32 [B][N][16]) -> the forward above
  *   (gt_scratch: tarl_policy_gt_fwd_scratch_floats(plan, B) floats; the state-independent terms once per call) ->
- *   tarl_graphdist_rollout (temperature; policy counter policy_counter0 + t; writes tarl_fused.sel8) -> tarl_fused_frame
- *   (noise counter counter0 + t) -> the count bytes. Other arguments and outputs as tarl_fused_rollout_prior. */
+ *   tarl_graphdist_rollout (temperature; policy counter policy_counter0 + t; writes tarl_fused.sel8) -> Direction gather ->
+ *   row pass -> insert (noise counter counter0 + t; the frame kernels write the count bytes): the same loop again, same
+ *   results as those calls and tarl_fused_frame made one by one. Other arguments and outputs as tarl_fused_rollout_prior. */
 int tarl_fused_rollout_gt(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
                           const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
                           float* agent_features, int64_t num_agents, int64_t a_bstride, const float* edge_attr,

@@ -1,7 +1,9 @@
 // fused_rollout.hip — the host loops of the fused path: one frame (tarl_fused_frame), T frames with the live policy
-// (tarl_fused_rollout) and T frames with a state-dependent policy head (tarl_fused_rollout_policy), written against the launch
-// functions of the kernel files. (Design: fused_frame.h.)
+// (tarl_fused_rollout) and T frames with a state-dependent policy head (tarl_rollout_head: the one loop under
+// tarl_fused_rollout_policy here, tarl_fused_rollout_prior[_dest] in prior.hip and tarl_fused_rollout_gt in gt_policy.hip),
+// written against the launch functions of the kernel files. (Design: fused_frame.h.)
 #include "fused_frame.h"
+#include "rollout_heads.h"
 
 // the side outputs of frame t of a T-frame rollout: slice t of every series the caller asked for; the event byte gc8 is
 // stored for every row in the last frame only (FrameOut::write_gc)
@@ -165,18 +167,105 @@ extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, in
   return TARL_OK;
 }
 
-// ---- T frames with a STATE-DEPENDENT policy (the per-edge MLP head) in one foreign call --------------------------------------
-// Nothing of GraphDistribution can be hoisted: per frame observation (tarl_fused_obs16) -> logits (tarl_policy_edge_mlp_fwd)
-// -> action + log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> Direction -> rows -> insert, eight launches queued
-// back to back by one host loop in C (the same entry points a caller could queue himself, minus a foreign-call round
-// trip per launch). The observations of the frames an optimiser minibatch will use are drawn beforehand (the draw does
-// not depend on the data): keep_ptr_host[t] .. keep_ptr_host[t + 1] index the (environment, slot) pairs of frame t.
+// ---- T frames with a STATE-DEPENDENT policy head in one foreign call (rollout_heads.h) ----------------------------------------
+// Nothing of GraphDistribution can be hoisted: per frame the head's logits from the packed state (`frame`) -> action +
+// log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> Direction -> rows -> insert, queued back to back by one host loop
+// in C (the same entry points a caller could queue himself, minus a foreign-call round trip per launch and the checks per
+// frame). The arguments are checked and the pointer table is uploaded once per call; the count bytes are the frame
+// kernels' own (FrameOut::counts8), the event byte is stored in the last frame only and the insert is packed
+// (tarl_insert_envs_per_wave). The observations of the frames an optimiser minibatch will use are drawn beforehand (the draw
+// does not depend on the data): keep_ptr_host[t] .. keep_ptr_host[t + 1] index the (environment, slot) pairs of frame t.
+int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
+  const tarl_plan* plan = a.plan;
+  const tarl_fused* f = a.f;
+  const int64_t B = a.B, T = a.T;
+  int rc = tarl_check_fused_core(plan, f, B, a.Nmax);
+  if (rc) return rc;
+  TARL_REQUIRE(T >= 1 && a.times_host, "bad frame count / times");
+  TARL_REQUIRE(a.x && a.logits_scratch && a.dist_scratch, "state / logits / sampler scratch missing");
+  TARL_REQUIRE(!a.keep_ptr_host || (a.keep_env && a.keep_slot && a.obs_keep), "keep list without its arrays");
+  rc = tarl_check_frame_args(plan, f, B, a.agent_features, a.A, a.a_bstride, a.ins_scratch, a.edge_attr, a.log_edge_attr);
+  if (rc) return rc;
+  TARL_REQUIRE(a.metrics_envs >= 0 && a.metrics_envs <= B, "metrics_envs out of range");
+  TARL_REQUIRE(a.metrics_envs > 0 || (!a.dtt_node && !a.events), "per-node series need metrics_envs > 0");
+  if (plan->N == 0) return TARL_OK;
+  hipStream_t s = (hipStream_t)a.stream;
+  const int64_t N = plan->N, NB = N * B;
+  const unsigned threads = tile_threads(B);
+  const dim3 grid((unsigned)ceil_div(B, threads), (unsigned)num_chunks(plan));
+  const dim3 grid_d((unsigned)ceil_div(B, threads), (unsigned)ceil_div(N, nchunk_dir()));
+  const FusedBufs* fb = nullptr;
+  rc = tarl_upload_bufs(f, tarl_to_bufs(f), nullptr, s, &fb);
+  if (rc) return rc;
+  const PlanOut P{plan->out_ptr, plan->out_dst};
+  const int epw_packed = tarl_insert_envs_per_wave(f, a.A, B, T, a.times_host);
+  for (int64_t t = 0; t < T; ++t) {
+    const bool keep_t = a.keep_ptr_host && a.keep_ptr_host[t + 1] > a.keep_ptr_host[t];
+    const int64_t lo = keep_t ? a.keep_ptr_host[t] : 0, n = keep_t ? a.keep_ptr_host[t + 1] - lo : 0;
+    rc = frame(a, ctx, t, a.keep_env + lo, a.keep_slot + lo, n);
+    if (rc) return rc;
+    rc = tarl_graphdist_rollout_at(plan, a.logits_scratch, B, a.temperature, nullptr, a.policy_seed,
+                                   a.policy_counter0 + (uint64_t)t, a.dist_scratch, nullptr,
+                                   a.choice8 ? a.choice8 + t * NB : nullptr, f->sel8, a.log_prob ? a.log_prob + t * B : nullptr,
+                                   f->env_base, a.stream);
+    if (rc) return rc;
+    const float time = a.times_host[t];
+    const FrameOut out = rollout_frame_out(t, T, N, B, a.counts, a.metrics_envs, a.dtt_node, a.events, a.leg);
+    rc = tarl_launch_direction(grid_d, threads, s, plan, f, a.edge_attr, a.log_edge_attr, (const uint8_t*)f->sel8, nullptr,
+                               nullptr, a.log_eps, time, t > 0 ? a.times_host[t - 1] : a.prev_time, a.seed,
+                               a.counter0 + (uint64_t)t, B, (int)a.Nmax, out);
+    if (rc) return rc;
+    rc = tarl_launch_rows(grid, threads, s, plan, f, fb, (int)a.Nmax, B, a.agent_features, a.A, a.a_bstride, time, out);
+    if (rc) return rc;
+    rc = tarl_launch_insert(epw_packed, s, (int)a.Nmax, B, N, fb, P, (const uint8_t*)f->sel8, a.agent_features, a.A,
+                            a.a_bstride, a.use_cong, time, a.ins_scratch, nullptr, a.reward ? a.reward + t * B : nullptr, out,
+                            nullptr, nullptr);
+    if (rc) return rc;
+  }
+  return TARL_OK;
+}
+
+// ---- the per-edge MLP head: observation (tarl_fused_obs16) -> logits (tarl_policy_edge_mlp_fwd) ---------------------------------
 __global__ __launch_bounds__(FB) void k_obs_keep(const float4* __restrict__ obs, int64_t row4,
                                                  const int32_t* __restrict__ env, const int32_t* __restrict__ slot,
                                                  float4* __restrict__ keep) {
   const int64_t j = (int64_t)blockIdx.x * FB + threadIdx.x;
   if (j >= row4) return;
   keep[(int64_t)slot[blockIdx.y] * row4 + j] = obs[(int64_t)env[blockIdx.y] * row4 + j];
+}
+
+struct EdgeMlpHead {
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  int precision;
+  float* obs_scratch;
+};
+
+static int edge_mlp_frame(const HeadRollout& a, void* ctx, int64_t, const int32_t* env, const int32_t* slot, int64_t n) {
+  const EdgeMlpHead& h = *(const EdgeMlpHead*)ctx;
+  hipStream_t s = (hipStream_t)a.stream;
+  const bool obs_bf16 = h.precision == 1;
+  const int64_t row4 = a.plan->N * 4;
+  TARL_REQUIRE(n < 65536, "more than 65535 kept observations in one frame");
+  // bf16 logits read bf16 observations (half the bytes written here and gathered by the MLP); the fp32 rows an
+  // optimiser step keeps are evaluated for their few environments only. fp32 observations: the kept rows are copies
+  int rc = obs_bf16 ? tarl_fused_obs16_bf16(a.plan, a.f, a.x, a.B, a.x_bstride, a.ldx, a.Nmax, a.agent_features, a.A,
+                                            a.a_bstride, (uint16_t*)h.obs_scratch, a.stream)
+                    : tarl_fused_obs16(a.plan, a.f, a.x, a.B, a.x_bstride, a.ldx, a.Nmax, a.agent_features, a.A, a.a_bstride,
+                                       h.obs_scratch, a.stream);
+  if (!rc && obs_bf16) rc = tarl_head_keep_rows(a, env, slot, n);
+  if (rc) return rc;
+  if (n && !obs_bf16) {
+    hipLaunchKernelGGL(k_obs_keep, dim3((unsigned)ceil_div(row4, FB), (unsigned)n), dim3(FB), 0, s,
+                       (const float4*)h.obs_scratch, row4, env, slot, (float4*)a.obs_keep);
+    TARL_LAUNCH_CHECK();
+  }
+  // (live timing, bench.py: HIP events around the per-edge MLP of the timed frames — slot 0 of tarl_prof_collect)
+  const bool timed = tarl_prof_mark(s, 0) != nullptr;
+  rc = tarl_policy_edge_mlp_fwd(a.plan, h.obs_scratch, a.B, a.edge_attr, h.w1, h.b1, h.w2, h.b2, h.w3, h.b3,
+                                h.precision == 1 ? 2 : (h.precision == 2 ? 3 : 0), a.logits_scratch, a.stream);
+  if (rc) return rc;
+  if (timed) (void)tarl_prof_mark(s, 1);
+  return TARL_OK;
 }
 
 extern "C" int tarl_fused_rollout_policy(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
@@ -192,74 +281,14 @@ extern "C" int tarl_fused_rollout_policy(const tarl_plan* plan, const tarl_fused
                                          uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
                                          int32_t metrics_envs, float* dtt_node, uint8_t* events, int32_t* leg,
                                          tarl_stream stream) {
-  int rc = tarl_check_fused_core(plan, f, B, Nmax);
-  if (rc) return rc;
-  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
-  TARL_REQUIRE(x && obs_scratch && logits_scratch && dist_scratch, "observation / logits / sampler scratch missing");
-  TARL_REQUIRE(!keep_ptr_host || (keep_env && keep_slot && obs_keep), "keep list without its arrays");
+  TARL_REQUIRE(obs_scratch, "observation scratch missing");
   TARL_REQUIRE(precision >= 0 && precision <= 2,
                "precision: 0 = fp32 MFMA logits, 1 = bf16 logits on bf16 observations, 2 = fp32-accurate logits on the bf16 pipe (bf16x3)");
-  rc = tarl_check_frame_args(plan, f, B, agent_features, A, a_bstride, ins_scratch, edge_attr, log_edge_attr);
-  if (rc) return rc;
-  TARL_REQUIRE(metrics_envs >= 0 && metrics_envs <= B, "metrics_envs out of range");
-  TARL_REQUIRE(metrics_envs > 0 || (!dtt_node && !events), "per-node series need metrics_envs > 0");
-  if (plan->N == 0) return TARL_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t N = plan->N, NB = N * B;
-  const unsigned threads = tile_threads(B);
-  const dim3 grid((unsigned)ceil_div(B, threads), (unsigned)num_chunks(plan));
-  const dim3 grid_d((unsigned)ceil_div(B, threads), (unsigned)ceil_div(N, nchunk_dir()));
-  const FusedBufs fbh = tarl_to_bufs(f);
-  const FusedBufs* fb = nullptr;
-  rc = tarl_upload_bufs(f, fbh, nullptr, s, &fb);
-  if (rc) return rc;
-  const PlanOut P{plan->out_ptr, plan->out_dst};
-  const int epw_packed = tarl_insert_envs_per_wave(f, A, B, T, times_host);
-  for (int64_t t = 0; t < T; ++t) {
-    const bool keep_t = keep_ptr_host && keep_ptr_host[t + 1] > keep_ptr_host[t];
-    const int64_t lo = keep_t ? keep_ptr_host[t] : 0, n = keep_t ? keep_ptr_host[t + 1] - lo : 0;
-    TARL_REQUIRE(n < 65536, "more than 65535 kept observations in one frame");
-    if (precision == 1) {
-      // bf16 logits read bf16 observations (half the bytes written here and gathered by the MLP); the fp32 rows an
-      // optimiser step keeps are evaluated for their few environments only
-      rc = tarl_fused_obs16_bf16(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride,
-                                 (uint16_t*)obs_scratch, stream);
-      if (rc) return rc;
-      if (keep_t) {
-        rc = tarl_fused_obs16_rows(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, keep_env + lo,
-                                   keep_slot + lo, n, obs_keep, stream);
-        if (rc) return rc;
-      }
-    } else {
-      rc = tarl_fused_obs16(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, obs_scratch, stream);
-      if (rc) return rc;
-      if (keep_t) {
-        hipLaunchKernelGGL(k_obs_keep, dim3((unsigned)ceil_div(N * 4, FB), (unsigned)n), dim3(FB), 0, s,
-                           (const float4*)obs_scratch, N * 4, keep_env + lo, keep_slot + lo, (float4*)obs_keep);
-        TARL_LAUNCH_CHECK();
-      }
-    }
-    // (live timing, bench.py: HIP events around the per-edge MLP of the timed frames — slot 0 of tarl_prof_collect)
-    const bool timed = tarl_prof_mark(s, 0) != nullptr;
-    rc = tarl_policy_edge_mlp_fwd(plan, obs_scratch, B, edge_attr, w1, b1, w2, b2, w3, b3,
-                                  precision == 1 ? 2 : (precision == 2 ? 3 : 0), logits_scratch, stream);
-    if (rc) return rc;
-    if (timed) (void)tarl_prof_mark(s, 1);
-    rc = tarl_graphdist_rollout_at(plan, logits_scratch, B, temperature, nullptr, policy_seed,
-                                   policy_counter0 + (uint64_t)t, dist_scratch, nullptr,
-                                   choice8 ? choice8 + t * NB : nullptr, f->sel8, log_prob ? log_prob + t * B : nullptr,
-                                   f->env_base, stream);
-    if (rc) return rc;
-    const float time = times_host[t];
-    const FrameOut out = rollout_frame_out(t, T, N, B, counts, metrics_envs, dtt_node, events, leg);
-    rc = tarl_launch_direction(grid_d, threads, s, plan, f, edge_attr, log_edge_attr, (const uint8_t*)f->sel8, nullptr, nullptr,
-                               log_eps, time, t > 0 ? times_host[t - 1] : prev_time, seed, counter0 + (uint64_t)t, B, (int)Nmax, out);
-    if (rc) return rc;
-    rc = tarl_launch_rows(grid, threads, s, plan, f, fb, (int)Nmax, B, agent_features, A, a_bstride, time, out);
-    if (rc) return rc;
-    rc = tarl_launch_insert(epw_packed, s, (int)Nmax, B, N, fb, P, (const uint8_t*)f->sel8, agent_features, A, a_bstride,
-                            use_cong, time, ins_scratch, nullptr, reward ? reward + t * B : nullptr, out, nullptr, nullptr);
-    if (rc) return rc;
-  }
-  return TARL_OK;
+  EdgeMlpHead h{w1, b1, w2, b2, w3, b3, precision, obs_scratch};
+  return tarl_rollout_head(HeadRollout{plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A,
+                                       a_bstride, edge_attr, log_edge_attr, log_eps, use_cong, temperature, policy_seed,
+                                       policy_counter0, seed, counter0, keep_ptr_host, keep_env, keep_slot, obs_keep,
+                                       logits_scratch, dist_scratch, ins_scratch, choice8, log_prob, reward, counts,
+                                       metrics_envs, dtt_node, events, leg, stream},
+                           edge_mlp_frame, &h);
 }

@@ -28,7 +28,7 @@
 // The node side (the helpers, embedding, projections, the attention + layer body forwards and backwards, the Q / K / V / G
 // gradient walk, the weight-gradient reduction) is gt_core.h, shared with the critic (gt_value.hip). This file keeps the
 // parameter table, the edge side, the gather of the gradients of Q2 / K2 from the edge records, and the entry points.
-#include "fused_common.h"
+#include "rollout_heads.h"
 #include "gt_core.h"
 
 // ---- the pointer table: trainable parameters in kernel order (GT_NP), then the BatchNorm running statistics -------------
@@ -458,10 +458,23 @@ extern "C" int tarl_policy_gt_bwd(const tarl_plan* plan, const float* obs16, int
                          erec, E_SLOTS * 16, ME, partial, s);
 }
 
-// the count bytes of the rollout buffers (NUMBER_OF_AGENT after the frame, env-minor [N][B]) from the packed state
-__global__ __launch_bounds__(GT_BLOCK) void k_gt_counts8(const uint2* __restrict__ hdp, int64_t n, uint8_t* __restrict__ counts) {
-  const int64_t gid = (int64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
-  if (gid < n) counts[gid] = (uint8_t)(hdp[gid].x & HD_CNT);
+// ---- the rollout head (rollout_heads.h): the state-independent terms once per call, then per frame kept rows -> observation
+// -> forward
+struct GtHead {
+  GtW W;
+  const float* pe;
+  float *obs_scratch, *gt_scratch;
+};
+
+static int gt_frame(const HeadRollout& a, void* ctx, int64_t t, const int32_t* env, const int32_t* slot, int64_t n) {
+  const GtHead& h = *(const GtHead*)ctx;
+  int rc = t == 0 ? launch_hoist(a.plan, h.W, a.edge_attr, h.pe, h.gt_scratch, (hipStream_t)a.stream) : TARL_OK;
+  if (!rc) rc = tarl_head_keep_rows(a, env, slot, n);
+  if (rc) return rc;
+  rc = tarl_fused_obs16(a.plan, a.f, a.x, a.B, a.x_bstride, a.ldx, a.Nmax, a.agent_features, a.A, a.a_bstride, h.obs_scratch,
+                        a.stream);
+  if (rc) return rc;
+  return launch_fwd(a.plan, h.W, h.obs_scratch, h.pe, a.B, a.edge_attr, h.gt_scratch, a.logits_scratch, (hipStream_t)a.stream);
 }
 
 extern "C" int tarl_fused_rollout_gt(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
@@ -474,50 +487,19 @@ extern "C" int tarl_fused_rollout_gt(const tarl_plan* plan, const tarl_fused* f,
                                      float* obs_keep, float* obs_scratch, float* gt_scratch, int64_t gt_scratch_floats,
                                      float* logits_scratch, void* dist_scratch, int32_t* ins_scratch, uint8_t* choice8,
                                      float* log_prob, float* reward, uint8_t* counts, tarl_stream stream) {
-  int rc = tarl_check_fused_core(plan, f, B, Nmax);
-  if (rc) return rc;
-  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
-  TARL_REQUIRE(x && agent_features && obs_scratch && gt_scratch && logits_scratch && dist_scratch && ins_scratch,
-               "state / observation / logits / sampler / insert scratch missing");
-  TARL_REQUIRE(!keep_ptr_host || (keep_env && keep_slot && obs_keep), "keep list without its arrays");
+  TARL_REQUIRE(plan && obs_scratch && gt_scratch, "plan / observation / forward scratch missing");
   TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
   TARL_REQUIRE(((uintptr_t)obs_scratch) % 16 == 0 && ((uintptr_t)gt_scratch) % 16 == 0, "scratch must be 16-byte aligned");
   TARL_REQUIRE(gt_scratch_floats >= tarl_policy_gt_fwd_scratch_floats(plan, B),
                "gt_scratch smaller than tarl_policy_gt_fwd_scratch_floats(plan, B)");
-  GtW W;
-  rc = gt_check(plan, obs_scratch, B, edge_attr, pe, w, &W);
+  GtHead h{{}, pe, obs_scratch, gt_scratch};
+  const int rc = gt_check(plan, obs_scratch, B, edge_attr, pe, w, &h.W);
   if (rc) return rc;
-  if (plan->N == 0) return TARL_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t N = plan->N, NB = N * B;
-  const FusedBufs fb = tarl_to_bufs(f);
-  rc = launch_hoist(plan, W, edge_attr, pe, gt_scratch, s);     // the state-independent terms, once per call
-  if (rc) return rc;
-  for (int64_t t = 0; t < T; ++t) {
-    if (keep_ptr_host && keep_ptr_host[t + 1] > keep_ptr_host[t]) {
-      const int64_t lo = keep_ptr_host[t], n = keep_ptr_host[t + 1] - lo;
-      rc = tarl_fused_obs16_rows(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, keep_env + lo,
-                                 keep_slot + lo, n, obs_keep, stream);
-      if (rc) return rc;
-    }
-    rc = tarl_fused_obs16(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, obs_scratch, stream);
-    if (rc) return rc;
-    rc = launch_fwd(plan, W, obs_scratch, pe, B, edge_attr, gt_scratch, logits_scratch, s);
-    if (rc) return rc;
-    rc = tarl_graphdist_rollout_at(plan, logits_scratch, B, temperature, nullptr, policy_seed, policy_counter0 + (uint64_t)t,
-                                   dist_scratch, nullptr, choice8 ? choice8 + t * NB : nullptr, f->sel8,
-                                   log_prob ? log_prob + t * B : nullptr, f->env_base, stream);
-    if (rc) return rc;
-    rc = tarl_fused_frame(plan, f, B, Nmax, nullptr, nullptr, nullptr, nullptr, 0, 0, agent_features, A, a_bstride, edge_attr,
-                          log_edge_attr, log_eps, use_cong, times_host[t], t > 0 ? times_host[t - 1] : prev_time, nullptr,
-                          seed, counter0 + (uint64_t)t, nullptr, nullptr, nullptr, ins_scratch, nullptr, nullptr, nullptr,
-                          reward ? reward + t * B : nullptr, nullptr, stream);
-    if (rc) return rc;
-    if (counts) {
-      hipLaunchKernelGGL(k_gt_counts8, dim3((unsigned)ceil_div(NB, GT_BLOCK)), dim3(GT_BLOCK), 0, s, fb.hdp, NB,
-                         counts + t * NB);
-      TARL_LAUNCH_CHECK();
-    }
-  }
-  return TARL_OK;
+  // (no per-step logs: metrics_envs = 0 and null series)
+  return tarl_rollout_head(HeadRollout{plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A,
+                                       a_bstride, edge_attr, log_edge_attr, log_eps, use_cong, temperature, policy_seed,
+                                       policy_counter0, seed, counter0, keep_ptr_host, keep_env, keep_slot, obs_keep,
+                                       logits_scratch, dist_scratch, ins_scratch, choice8, log_prob, reward, counts, 0, nullptr,
+                                       nullptr, nullptr, stream},
+                           gt_frame, &h);
 }

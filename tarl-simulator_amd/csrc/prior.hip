@@ -27,8 +27,9 @@
 //     wave-uniform, and the table row dist[v] is one row for the whole wave (the table is stored [candidate][destination]:
 //     the 64 lanes gather inside one row of N floats instead of touching 64 rows). The [64 env][64 edge] tile is turned
 //     through LDS and leaves as 256-byte runs of each environment's logits row.
-// tarl_fused_rollout_prior queues, per frame, prior logits -> tarl_graphdist_rollout_at -> tarl_fused_frame (Direction, rows,
-// insert; SELECTED_ROAD set by the sampler) -> count bytes, in one foreign call.
+// tarl_fused_rollout_prior is the shared rollout loop of the state-dependent heads (tarl_rollout_head, rollout_heads.h) with
+// this head's frame function: per frame kept observation rows -> prior logits, then the loop's tarl_graphdist_rollout_at ->
+// Direction -> rows -> insert (SELECTED_ROAD set by the sampler, count bytes written by the frame kernels), in one foreign call.
 //
 // The *_dest entry points read the same distances from the per-destination table of tarl_prior_dest_table instead:
 // table [N][D] fp32 (candidate-major like dist, one column per destination) and dest_slot int32 [N] (the column of each
@@ -36,7 +37,7 @@
 // the same templates; only the table lookup differs (PriorAllPairs / PriorPerDest).
 #include <math.h>
 
-#include "fused_common.h"
+#include "rollout_heads.h"
 
 #define PRIOR_UNREACHABLE (-1e20f)
 #define PR_BLOCK 256
@@ -238,60 +239,31 @@ extern "C" int tarl_fused_prior_logits_dest(const tarl_plan* plan, const tarl_fu
                      PriorPerDest{table, dest_slot, plan->N, num_dests}, prior_weight, logits, stream);
 }
 
-// the count bytes of the rollout buffers (NUMBER_OF_AGENT after the frame, env-minor [N][B]) from the packed state
-__global__ __launch_bounds__(PR_BLOCK) void k_counts8(const uint2* __restrict__ hdp, int64_t n, uint8_t* __restrict__ counts) {
-  const int64_t gid = (int64_t)blockIdx.x * PR_BLOCK + threadIdx.x;
-  if (gid < n) counts[gid] = (uint8_t)(hdp[gid].x & HD_CNT);
+// ---- the rollout head (rollout_heads.h): kept observation rows and the prior logits of one frame ----------------------------
+template <class Tab>
+struct PriorHead {
+  const float* emb;
+  int64_t num_embeddings;
+  Tab tab;
+  float prior_weight;
+};
+
+template <class Tab>
+static int prior_frame(const HeadRollout& a, void* ctx, int64_t, const int32_t* env, const int32_t* slot, int64_t n) {
+  const PriorHead<Tab>& h = *(const PriorHead<Tab>*)ctx;
+  const int rc = tarl_head_keep_rows(a, env, slot, n);
+  if (rc || a.plan->E == 0) return rc;
+  return launch_prior_fused(a.plan, a.f, a.B, a.Nmax, a.x, a.ldx, a.agent_features, a.A, a.a_bstride, h.emb, h.num_embeddings,
+                            h.tab, h.prior_weight, a.logits_scratch, (hipStream_t)a.stream);
 }
 
-// observation row env[j] of the current frame -> obs_keep[slot[j]] for the kept (frame, environment) pairs, then the frame
 template <class Tab>
-static int rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
-                         const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
-                         float* agent_features, int64_t A, int64_t a_bstride, const float* edge_attr,
-                         const float* log_edge_attr, float log_eps, int use_cong, const float* emb, int64_t num_embeddings,
-                         Tab tab, float prior_weight, float temperature, uint64_t policy_seed, uint64_t policy_counter0,
-                         uint64_t seed, uint64_t counter0, const int64_t* keep_ptr_host, const int32_t* keep_env,
-                         const int32_t* keep_slot, float* obs_keep, float* logits_scratch, void* dist_scratch,
-                         int32_t* ins_scratch, uint8_t* choice8, float* log_prob, float* reward, uint8_t* counts,
-                         tarl_stream stream) {
-  int rc = check_prior_state(plan, f, B, Nmax, x, agent_features, A, emb, num_embeddings, prior_weight);
+static int rollout_prior(const HeadRollout& a, const float* emb, int64_t num_embeddings, Tab tab, float prior_weight) {
+  int rc = check_prior_state(a.plan, a.f, a.B, a.Nmax, a.x, a.agent_features, a.A, emb, num_embeddings, prior_weight);
   if (rc) return rc;
-  TARL_REQUIRE(T >= 1 && times_host, "bad frame count / times");
-  TARL_REQUIRE(logits_scratch && dist_scratch && ins_scratch, "logits / sampler / insert scratch missing");
-  TARL_REQUIRE(!keep_ptr_host || (keep_env && keep_slot && obs_keep), "keep list without its arrays");
-  TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
-  if (plan->N == 0) return TARL_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t N = plan->N, NB = N * B;
-  const FusedBufs fb = tarl_to_bufs(f);
-  for (int64_t t = 0; t < T; ++t) {
-    if (keep_ptr_host && keep_ptr_host[t + 1] > keep_ptr_host[t]) {
-      const int64_t lo = keep_ptr_host[t], n = keep_ptr_host[t + 1] - lo;
-      rc = tarl_fused_obs16_rows(plan, f, x, B, x_bstride, ldx, Nmax, agent_features, A, a_bstride, keep_env + lo,
-                                 keep_slot + lo, n, obs_keep, stream);
-      if (rc) return rc;
-    }
-    if (plan->E > 0) {
-      rc = launch_prior_fused(plan, f, B, Nmax, x, ldx, agent_features, A, a_bstride, emb, num_embeddings, tab, prior_weight,
-                              logits_scratch, s);
-      if (rc) return rc;
-    }
-    rc = tarl_graphdist_rollout_at(plan, logits_scratch, B, temperature, nullptr, policy_seed, policy_counter0 + (uint64_t)t,
-                                   dist_scratch, nullptr, choice8 ? choice8 + t * NB : nullptr, f->sel8,
-                                   log_prob ? log_prob + t * B : nullptr, f->env_base, stream);
-    if (rc) return rc;
-    rc = tarl_fused_frame(plan, f, B, Nmax, nullptr, nullptr, nullptr, nullptr, 0, 0, agent_features, A, a_bstride, edge_attr,
-                          log_edge_attr, log_eps, use_cong, times_host[t], t > 0 ? times_host[t - 1] : prev_time, nullptr,
-                          seed, counter0 + (uint64_t)t, nullptr, nullptr, nullptr, ins_scratch, nullptr, nullptr, nullptr,
-                          reward ? reward + t * B : nullptr, nullptr, stream);
-    if (rc) return rc;
-    if (counts) {
-      hipLaunchKernelGGL(k_counts8, dim3((unsigned)ceil_div(NB, PR_BLOCK)), dim3(PR_BLOCK), 0, s, fb.hdp, NB, counts + t * NB);
-      TARL_LAUNCH_CHECK();
-    }
-  }
-  return TARL_OK;
+  TARL_REQUIRE(a.temperature > 0.0f, "temperature must be positive");
+  PriorHead<Tab> h{emb, num_embeddings, tab, prior_weight};
+  return tarl_rollout_head(a, prior_frame<Tab>, &h);
 }
 
 extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
@@ -307,10 +279,11 @@ extern "C" int tarl_fused_rollout_prior(const tarl_plan* plan, const tarl_fused*
                                         tarl_stream stream) {
   int rc = check_all_pairs(plan, dist, dist_n);
   if (rc) return rc;
-  return rollout_prior(plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A, a_bstride, edge_attr,
-                       log_edge_attr, log_eps, use_cong, emb, num_embeddings, PriorAllPairs{dist, plan->N}, prior_weight,
-                       temperature, policy_seed, policy_counter0, seed, counter0, keep_ptr_host, keep_env, keep_slot,
-                       obs_keep, logits_scratch, dist_scratch, ins_scratch, choice8, log_prob, reward, counts, stream);
+  return rollout_prior(HeadRollout{plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A, a_bstride,
+                                   edge_attr, log_edge_attr, log_eps, use_cong, temperature, policy_seed, policy_counter0, seed,
+                                   counter0, keep_ptr_host, keep_env, keep_slot, obs_keep, logits_scratch, dist_scratch,
+                                   ins_scratch, choice8, log_prob, reward, counts, 0, nullptr, nullptr, nullptr, stream},
+                       emb, num_embeddings, PriorAllPairs{dist, plan->N}, prior_weight);
 }
 
 extern "C" int tarl_fused_rollout_prior_dest(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
@@ -327,9 +300,9 @@ extern "C" int tarl_fused_rollout_prior_dest(const tarl_plan* plan, const tarl_f
                                              tarl_stream stream) {
   int rc = check_per_dest(plan, table, num_dests, dest_slot);
   if (rc) return rc;
-  return rollout_prior(plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A, a_bstride, edge_attr,
-                       log_edge_attr, log_eps, use_cong, emb, num_embeddings,
-                       PriorPerDest{table, dest_slot, plan->N, num_dests}, prior_weight, temperature, policy_seed,
-                       policy_counter0, seed, counter0, keep_ptr_host, keep_env, keep_slot, obs_keep, logits_scratch,
-                       dist_scratch, ins_scratch, choice8, log_prob, reward, counts, stream);
+  return rollout_prior(HeadRollout{plan, f, B, Nmax, T, times_host, prev_time, x, x_bstride, ldx, agent_features, A, a_bstride,
+                                   edge_attr, log_edge_attr, log_eps, use_cong, temperature, policy_seed, policy_counter0, seed,
+                                   counter0, keep_ptr_host, keep_env, keep_slot, obs_keep, logits_scratch, dist_scratch,
+                                   ins_scratch, choice8, log_prob, reward, counts, 0, nullptr, nullptr, nullptr, stream},
+                       emb, num_embeddings, PriorPerDest{table, dest_slot, plan->N, num_dests}, prior_weight);
 }

@@ -1,0 +1,54 @@
+// rollout_heads.h — internal: the T-frame rollout of a STATE-DEPENDENT policy head, written once (tarl_rollout_head,
+// fused_rollout.hip). A head — the per-edge MLP (fused_rollout.hip), the shortest-path prior (prior.hip), the graph
+// transformer (gt_policy.hip) — is "how the packed state of frame t becomes logits_scratch"; what a rollout frame is
+// (sampler, Direction, rows, insert, the side outputs) lives in the loop alone.
+#pragma once
+#include "fused_common.h"
+
+// what every head's entry point takes, in the order of the extern "C" signatures (include/tarl_hip.h)
+struct HeadRollout {
+  const tarl_plan* plan;
+  const tarl_fused* f;
+  int64_t B;
+  int32_t Nmax;
+  int64_t T;
+  const float* times_host;
+  float prev_time;
+  const float* x;
+  int64_t x_bstride, ldx;
+  float* agent_features;
+  int64_t A, a_bstride;
+  const float *edge_attr, *log_edge_attr;
+  float log_eps;
+  int use_cong;
+  float temperature;
+  uint64_t policy_seed, policy_counter0, seed, counter0;
+  const int64_t* keep_ptr_host;     // keep_ptr_host[t] .. keep_ptr_host[t + 1]: the (environment, slot) pairs kept of frame t
+  const int32_t *keep_env, *keep_slot;
+  float *obs_keep, *logits_scratch;
+  void* dist_scratch;
+  int32_t* ins_scratch;
+  uint8_t* choice8;
+  float *log_prob, *reward;
+  uint8_t* counts;
+  int32_t metrics_envs;             // the per-step logs: the edge MLP's entry point alone has the arguments
+  float* dtt_node;
+  uint8_t* events;
+  int32_t* leg;
+  tarl_stream stream;
+};
+
+// Frame t of a head, from the packed state as frame t - 1 left it: the observation rows of the n kept pairs (env[j], slot[j])
+// -> obs_keep (n may be 0), the logits of all environments -> logits_scratch. State-independent work belongs to t == 0.
+typedef int (*head_frame_fn)(const HeadRollout& a, void* ctx, int64_t t, const int32_t* env, const int32_t* slot, int64_t n);
+
+// Checks the common arguments once, then queues per frame: head -> tarl_graphdist_rollout_at (action bytes, log-prob,
+// SELECTED_ROAD) -> Direction -> rows -> insert, the count bytes written by the frame kernels.
+int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx);
+
+// the kept rows straight from the packed state (a head whose logits do not leave fp32 observations behind)
+static inline int tarl_head_keep_rows(const HeadRollout& a, const int32_t* env, const int32_t* slot, int64_t n) {
+  if (n == 0) return TARL_OK;
+  return tarl_fused_obs16_rows(a.plan, a.f, a.x, a.B, a.x_bstride, a.ldx, a.Nmax, a.agent_features, a.A, a.a_bstride, env, slot,
+                               n, a.obs_keep, a.stream);
+}

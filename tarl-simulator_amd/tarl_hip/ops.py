@@ -1768,6 +1768,33 @@ def fused_rollout(plan: Plan, fs: FusedState, tables: PolicyTables, agent_featur
                                     _lib.ptr(events), _lib.ptr(leg), _lib.current_stream()))
 
 
+def _head_rollout(entry, plan: Plan, fs: FusedState, x, agent_features, ec: EdgeConst, times, head, *, use_cong,
+                  temperature, policy_seed, policy_counter0, seed, counter0, scratch, prev_time, keep, obs_keep, choice8,
+                  log_prob, reward, counts, obs_scratch=False, head_scratch=(), logs=None):
+    """The one body of the state-dependent rollouts (csrc/rollout_heads.h): checks what they share and calls ``entry``
+    with the common head of the C argument list, the head's own arguments ``head``, the sampler arguments and keep list,
+    the scratch buffers (``obs_scratch``: the lazily created (B, N, 16) observation buffer, then ``head_scratch``), the
+    outputs and — for the entry point that has them — the per-step ``logs`` (metrics_envs, dtt_node, events, leg)."""
+    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
+    B, N = fs.B, fs.N
+    _, _, bs, ldx = _state(x, fs.Nmax)
+    m_env, dtt_node, events, leg = logs or (0, None, None, None)
+    _check_rollout_outputs(T, B, N, True, m_env, None, counts, log_prob, None, reward, dtt_node, events, leg)
+    _check_rollout_outputs(T, B, N, False, m_env, choice8, None, None, None, None, None, None, None)
+    if obs_scratch and getattr(fs, "obs_scratch", None) is None:
+        fs.obs_scratch = torch.empty((B, N, 16), dtype=torch.float32, device=fs.sel8.device)
+    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
+    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
+    tarr = (C.c_float * T)(*[float(t) for t in times])
+    _lib.check(getattr(L, entry)(
+        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
+        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps, 1 if use_cong else 0, *head, float(temperature),
+        int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot),
+        _lib.ptr(obs_keep), *((fs.obs_scratch.data_ptr(),) if obs_scratch else ()), *head_scratch, logits_scratch,
+        dist_scratch, scratch.data_ptr(), _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts),
+        *((int(m_env), _lib.ptr(dtt_node), _lib.ptr(events), _lib.ptr(leg)) if logs else ()), _lib.current_stream()))
+
+
 def fused_rollout_policy(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeConst, w: EdgeMlpWeights, times, *,
                          use_cong, bf16=False, temperature, policy_seed, policy_counter0, seed, counter0, scratch,
                          prev_time=None, keep=None, obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None,
@@ -1777,25 +1804,12 @@ def fused_rollout_policy(plan: Plan, fs: FusedState, x, agent_features, ec: Edge
     observations (frame t, environment env[j]) for ptr[t] <= j < ptr[t + 1] are copied to ``obs_keep[slot[j]]``
     ((K, N, 16) fp32). ``choice8`` (T, B, N) uint8 ENV-MAJOR rank bytes; ``counts`` (T, N, B) uint8 env-minor; the
     other outputs as :func:`fused_rollout`."""
-    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
-    B, N = fs.B, fs.N
-    _, _, bs, ldx = _state(x, fs.Nmax)
-    _check_rollout_outputs(T, B, N, True, metrics_envs, None, counts, log_prob, None, reward, dtt_node, events, leg)
-    _check_rollout_outputs(T, B, N, False, metrics_envs, choice8, None, None, None, None, None, None, None)
-    if getattr(fs, "obs_scratch", None) is None:
-        fs.obs_scratch = torch.empty((B, N, 16), dtype=torch.float32, device=fs.sel8.device)
-    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
-    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
-    tarr = (C.c_float * T)(*[float(t) for t in times])
-    _lib.check(L.tarl_fused_rollout_policy(
-        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
-        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
-        1 if use_cong else 0, *w.ptrs(), {"fp32": 0, "bf16": 1, "x3": 2}[_edge_mlp_precision(bf16, precision)],
-        float(temperature), int(policy_seed), int(policy_counter0),
-        int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot), _lib.ptr(obs_keep), fs.obs_scratch.data_ptr(),
-        logits_scratch, dist_scratch, scratch.data_ptr(), _lib.ptr(choice8),
-        _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), int(metrics_envs), _lib.ptr(dtt_node), _lib.ptr(events),
-        _lib.ptr(leg), _lib.current_stream()))
+    head = (*w.ptrs(), {"fp32": 0, "bf16": 1, "x3": 2}[_edge_mlp_precision(bf16, precision)])
+    _head_rollout("tarl_fused_rollout_policy", plan, fs, x, agent_features, ec, times, head, use_cong=use_cong,
+                  temperature=temperature, policy_seed=policy_seed, policy_counter0=policy_counter0, seed=seed,
+                  counter0=counter0, scratch=scratch, prev_time=prev_time, keep=keep, obs_keep=obs_keep, choice8=choice8,
+                  log_prob=log_prob, reward=reward, counts=counts, obs_scratch=True,
+                  logs=(metrics_envs, dtt_node, events, leg))
 
 
 # ---- shortest-path prior head (policy_head = "embedding_dijkstra", csrc/prior.hip) ------------------------------------------
@@ -1882,21 +1896,11 @@ def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeC
     tarl_fused_rollout_prior_dest with ``dest_slot``: as :func:`policy_prior_logits`). ``keep`` / ``obs_keep`` /
     ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
     w, targs, sfx = _prior_args(plan, emb, table, prior_weight, dest_slot)
-    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
-    B, N = fs.B, fs.N
-    _, _, bs, ldx = _state(x, fs.Nmax)
-    _check_rollout_outputs(T, B, N, True, 0, None, counts, log_prob, None, reward, None, None, None)
-    _check_rollout_outputs(T, B, N, False, 0, choice8, None, None, None, None, None, None, None)
-    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
-    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
-    tarr = (C.c_float * T)(*[float(t) for t in times])
-    _lib.check(getattr(L, "tarl_fused_rollout_prior" + sfx)(
-        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
-        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps,
-        1 if use_cong else 0, emb.data_ptr(), emb.numel(), *targs, w, float(temperature),
-        int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv), _lib.ptr(kslot),
-        _lib.ptr(obs_keep), logits_scratch, dist_scratch, scratch.data_ptr(),
-        _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward), _lib.ptr(counts), _lib.current_stream()))
+    _head_rollout("tarl_fused_rollout_prior" + sfx, plan, fs, x, agent_features, ec, times,
+                  (emb.data_ptr(), emb.numel(), *targs, w), use_cong=use_cong, temperature=temperature,
+                  policy_seed=policy_seed, policy_counter0=policy_counter0, seed=seed, counter0=counter0, scratch=scratch,
+                  prev_time=prev_time, keep=keep, obs_keep=obs_keep, choice8=choice8, log_prob=log_prob, reward=reward,
+                  counts=counts)
 
 
 # ---- graph-transformer head (policy_head = "graph_transformer", csrc/gt_policy.hip) ------------------------------------------
@@ -1999,29 +2003,17 @@ def fused_rollout_gt(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeCons
                      obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None):
     """``T = len(times)`` frames under the graph-transformer head in one foreign call (tarl_fused_rollout_gt). ``keep`` /
     ``obs_keep`` / ``choice8`` / ``counts`` as :func:`fused_rollout_policy`; ``log_prob`` / ``reward`` (T, B)."""
-    L, T, A, abs_, prev = _rollout_args(fs, agent_features, times, scratch, prev_time)
-    B, N = fs.B, fs.N
-    _, _, bs, ldx = _state(x, fs.Nmax)
     _contig(pe, torch.float32, "pe")
-    if tuple(pe.shape) != (N, 16):
-        raise ValueError(f"pe must be ({N}, 16)")
-    _check_rollout_outputs(T, B, N, True, 0, None, counts, log_prob, None, reward, None, None, None)
-    _check_rollout_outputs(T, B, N, False, 0, choice8, None, None, None, None, None, None, None)
-    if getattr(fs, "obs_scratch", None) is None:
-        fs.obs_scratch = torch.empty((B, N, 16), dtype=torch.float32, device=fs.sel8.device)
-    n = int(L.tarl_policy_gt_fwd_scratch_floats(plan.handle, B))
+    if tuple(pe.shape) != (fs.N, 16):
+        raise ValueError(f"pe must be ({fs.N}, 16)")
+    n = int(_lib.load().tarl_policy_gt_fwd_scratch_floats(plan.handle, fs.B))
     if getattr(fs, "gt_scratch", None) is None or fs.gt_scratch.numel() < n:
         fs.gt_scratch = torch.empty(n, dtype=torch.float32, device=fs.sel8.device)
-    logits_scratch, dist_scratch = _sampler_scratch(L, plan, fs)
-    kptr, kenv, kslot = _keep_args(keep, obs_keep, T, N)
-    tarr = (C.c_float * T)(*[float(t) for t in times])
-    _lib.check(L.tarl_fused_rollout_gt(
-        plan.handle, fs.ref, B, fs.Nmax, T, tarr, prev, x.data_ptr(), bs, ldx, agent_features.data_ptr(), A, abs_,
-        ec.edge_attr.data_ptr(), ec.log_edge_attr.data_ptr(), ec.log_eps, 1 if use_cong else 0, pe.data_ptr(), w.table,
-        float(temperature), int(policy_seed), int(policy_counter0), int(seed), int(counter0), kptr, _lib.ptr(kenv),
-        _lib.ptr(kslot), _lib.ptr(obs_keep), fs.obs_scratch.data_ptr(), fs.gt_scratch.data_ptr(), fs.gt_scratch.numel(),
-        logits_scratch, dist_scratch, scratch.data_ptr(), _lib.ptr(choice8), _lib.ptr(log_prob), _lib.ptr(reward),
-        _lib.ptr(counts), _lib.current_stream()))
+    _head_rollout("tarl_fused_rollout_gt", plan, fs, x, agent_features, ec, times, (pe.data_ptr(), w.table),
+                  use_cong=use_cong, temperature=temperature, policy_seed=policy_seed, policy_counter0=policy_counter0,
+                  seed=seed, counter0=counter0, scratch=scratch, prev_time=prev_time, keep=keep, obs_keep=obs_keep,
+                  choice8=choice8, log_prob=log_prob, reward=reward, counts=counts, obs_scratch=True,
+                  head_scratch=(fs.gt_scratch.data_ptr(), fs.gt_scratch.numel()))
 
 
 # ---- graph-transformer critic (value_head = "graph_transformer", csrc/gt_value.hip) -------------------------------------------

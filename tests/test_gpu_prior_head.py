@@ -220,14 +220,17 @@ def test_unreachable_candidates_and_all_unreachable_nodes():
             assert bool(torch.isfinite(g).all()) and bool(torch.isfinite(ge).all())
 
 
-def test_rollout_prior_equals_the_frames_issued_one_at_a_time():
-    """tarl_fused_rollout_prior over T frames == per frame: packed-state logits, tarl_graphdist_rollout (sel8), the frame."""
+@pytest.mark.parametrize("t1", [21560, 21740])
+def test_rollout_prior_equals_the_frames_issued_one_at_a_time(t1):
+    """tarl_fused_rollout_prior over T frames == per frame: packed-state logits, tarl_graphdist_rollout (sel8), the frame.
+    Departures in 21540 .. t1: about 20 agents due per frame and environment (the rollout's insert runs one environment per
+    wave, like the twin's frames), or about 2 (tarl_insert_envs_per_wave packs 4 environments per wave; the twin still 1)."""
     from tarl_hip import ops, synth
     from tarl_hip.engine import SimEngine
     net = _net(6, 5, seed=7)
     N, B, T, A = net.num_roads, 96, 20, 400
     _, table = _table(net)
-    pops = torch.stack([synth.population(A, N, seed=b, t0=21540, t1=21560) for b in range(B)]).cuda()
+    pops = torch.stack([synth.population(A, N, seed=b, t0=21540, t1=t1) for b in range(B)]).cuda()
     emb = torch.randn(N, generator=torch.Generator().manual_seed(3)).cuda()
     mk = lambda: SimEngine(net.x.cuda().unsqueeze(0).repeat(B, 1, 1).contiguous(), net.edge_index, net.edge_attr, net.Nmax,
                            pops.clone(), congestion_constant=net.congestion_constant, seed=11)
