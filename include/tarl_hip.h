@@ -1045,6 +1045,38 @@ int tarl_td_hindsight(const tarl_plan* plan, const float* tau, const double* env
                       int64_t num_agents, int64_t a_bstride, int64_t bin_seconds, int64_t first_bin, int64_t H, void* scratch,
                       int64_t scratch_bytes, double* best, tarl_stream stream);
 
+/* ---- day-to-day replanning: quickest routes per agent and the router that follows them ---------------------------------------
+ * NOT reference semantics: the reference has no replanning loop, no search that returns a path and no router that reads a
+ * plan per agent (tarl_hip/replanning.py holds the loop). TARL_ABI_VERSION is unchanged: nothing existing moved.
+ * tarl_td_routes: tarl_td_hindsight's search (same tables, same leave(), same labels L) for EVERY agent a >= 1 whose origin and
+ *   destination lie in [0, N), whatever its DONE flag, from its DEPARTURE_TIME; best fp64 [K][A] = L[destination]. After the
+ *   labels have converged the path is walked back from the destination: at v != origin the in-neighbour u with
+ *   leave(v, L[u]) == L[v] (fp64 equality), among several the SMALLEST ROAD ID whatever the order of the in-list. The route is
+ *   stored forward, routes int32 [K][A][max_hops]: routes[k][a][0] = origin .. routes[k][a][len - 1] = destination with
+ *   len = route_len[k][a] (int32 [K][A]); origin == destination gives len 1. len = 0 and best = +inf: an unreachable
+ *   destination, the dummy row 0, an id out of range. len = -(true length): the route is longer than max_hops; the row's
+ *   words are then left as allocated. (len = 0 with a finite best: no tight in-edge, and
+ *   len = -1: more than N roads — neither occurs with tau >= FF > 0, where the labels fall strictly along the walk.) Every best
+ *   and route_len entry is written; route words from len on are left as allocated. Launch shape as tarl_td_hindsight; each
+ *   workgroup's scratch row holds the fp64 labels and, behind them, the walk's stack of max_hops road ids
+ *   (tarl_td_routes_scratch_bytes; -1 for a bad argument); two runs are bit-identical.
+ * Refused on the host, before anything is launched and with the outputs untouched: what tarl_td_hindsight refuses, and
+ *   max_hops outside [1, 2^20].
+ * tarl_fused_select_route: SELECTED_ROAD of every row of the packed state = the road that follows the row on its HEAD agent's
+ *   route. The head decode (an empty row reads agent 0, a DIRTY row its slot), the rank code and the writes to sel8 / sel /
+ *   choice8 are tarl_fused_select_next_hop_hold's. With r = routes[b][head] and len = route_len[b][head] — r_bstride ints between
+ *   two environments' route tables (>= num_agents * max_hops; route_len is then dense [B][A]), or 0: one plan [A][max_hops] and
+ *   [A] shared by all environments — a head outside [0, num_agents) or a len outside [1, max_hops] leaves the row untouched, and
+ *   so does a row that is not on the route. Else with j the smallest index with r[j] == row: the row itself for j == len - 1
+ *   (the destination), else r[j + 1], and the row itself where r[j + 1] == r[len - 1]: the hold rule, compared on the integers. */
+int64_t tarl_td_routes_scratch_bytes(const tarl_plan* plan, int64_t K, int64_t num_agents, int64_t max_hops);
+int tarl_td_routes(const tarl_plan* plan, const float* tau, const double* env, const float* agents, int64_t K,
+                   int64_t num_agents, int64_t a_bstride, int64_t bin_seconds, int64_t first_bin, int64_t H, int64_t max_hops,
+                   void* scratch, int64_t scratch_bytes, double* best, int32_t* routes, int32_t* route_len, tarl_stream stream);
+int tarl_fused_select_route(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                            const int32_t* routes, const int32_t* route_len, int64_t r_bstride, int64_t max_hops,
+                            uint8_t* choice8, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

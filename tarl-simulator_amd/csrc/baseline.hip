@@ -7,7 +7,7 @@
 //   k_fused_select_next_hop_dest  == k_select_next_hop_dest (dest_trees.hip) reading the packed words and the agent SoA and
 //                                    writing the rank byte sel8 instead of a float into a 3 Nmax + 7 float row: every frame.
 // Both are bit-identical, through tarl_fused_export, to their unfused counterparts on the exported x.
-#include "fused_common.h"
+#include "fused_select.h"
 
 // ---- (a) per-edge travel time -------------------------------------------------------------------------------------------
 // The packed words are ENV-MINOR [N][B], the output is ENV-MAJOR [B][E]: a 64 edges x 64 environments tile of count bytes
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(TT_BLOCK) void k_fused_edge_travel_time(const int32
 // collected as soon as it is due. No out-edge targets the row itself (the builders make no self-loops; on such a graph a
 // holding head would take the loop), so a holding row stores SEL_RAW and its id and the core moves nobody from it. On the
 // destination road the table already holds the road's id: nothing changes there. Same 21 B per (row, environment).
-#define FS_BLOCK 256
+// The head decode and the rank code are fused_select.h's, shared with k_fused_select_route (routes.hip).
 template <bool HOLD>
 __global__ __launch_bounds__(FS_BLOCK) void k_fused_select_next_hop_dest(
     const uint2* __restrict__ hdp, const uint32_t* __restrict__ tl, const uint8_t* __restrict__ gc8,
@@ -70,15 +70,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_fused_select_next_hop_dest(
   const uint32_t gid = blockIdx.x * FS_BLOCK + threadIdx.x;      // N * B < 2^31 (tarl_check_fused_core)
   if (gid >= NB) return;
   const uint32_t i = gid / B, b = gid - i * B;
-  const uint32_t hd = hdp[gid].x;
-  long long head = (long long)(hd >> 8);
-  if ((hd & HD_CNT) == 0u) {
-    head = 0;
-    if (hd & HD_DIRTY) {
-      const uint32_t tlw = tl[gid];
-      if (pending_g(tlw, 0, (uint32_t)gc8[gid], Nmax) < 0) head = (long long)slots[(int64_t)gid * lds + SLW * tl_hoff(tlw)];
-    }
-  }
+  const long long head = fs_head_agent(hdp[gid].x, gid, tl, gc8, slots, lds, Nmax);
   bool write = false;
   uint32_t code = SEL_RAW;
   if (head >= 0 && head < A) {
@@ -89,19 +81,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_fused_select_next_hop_dest(
         int32_t nh = next_hop[(int64_t)b * nh_bstride + (int64_t)slot * N + i];
         if (HOLD && nh == dest) nh = (int32_t)i;
         const float sv = (float)nh;
-        const NodeRec& nr = nodes[i];
-        const int32_t deg = nr.out_deg;
-#pragma unroll
-        for (int q = 3; q >= 0; --q)
-          if (q < deg && (float)nr.out4[q] == sv) code = (uint32_t)q;
-        if (code == SEL_RAW && deg > 4) {
-          const int32_t* od = out_pad + nr.out0;
-          for (int32_t q = 4; q < deg && q < (int32_t)SEL_RAW; ++q)
-            if ((float)od[q] == sv) {
-              code = (uint32_t)q;
-              break;
-            }
-        }
+        code = fs_rank_code(nodes[i], out_pad, sv);
         if (code == SEL_RAW) sel[gid] = sv;
         sel8[gid] = (uint8_t)code;
         write = true;

@@ -1,0 +1,44 @@
+// fused_select.h — what the SELECTED_ROAD writers on the PACKED state share: k_fused_select_next_hop_dest (baseline.hip, the
+// next hop from a per-destination table) and k_fused_select_route (routes.hip, the next hop from a per-agent route). Both
+// run one thread per (row i, environment b), flat index gid = i * B + b with the environment fastest, decode the row's head
+// agent the same way and turn the value they select into the same rank byte.
+#pragma once
+#include "fused_common.h"
+
+#define FS_BLOCK 256
+
+// The head agent of packed row gid whose hdp word is hd. k_select_next_hop_dest's rule, word for word: an empty FIFO reads
+// agent 0 — x[i][0] of an empty row is 0 (the pending garbage triple, or a clean row's dead slot) unless the row is DIRTY
+// with no garbage pending, where it is whatever the slot store holds at the ring offset (k_export_rows).
+__device__ __forceinline__ long long fs_head_agent(uint32_t hd, uint32_t gid, const uint32_t* __restrict__ tl,
+                                                   const uint8_t* __restrict__ gc8, const float* __restrict__ slots,
+                                                   int64_t lds, int Nmax) {
+  long long head = (long long)(hd >> 8);
+  if ((hd & HD_CNT) == 0u) {
+    head = 0;
+    if (hd & HD_DIRTY) {
+      const uint32_t tlw = tl[gid];
+      if (pending_g(tlw, 0, (uint32_t)gc8[gid], Nmax) < 0) head = (long long)slots[(int64_t)gid * lds + SLW * tl_hoff(tlw)];
+    }
+  }
+  return head;
+}
+
+// The code of the value sv in row i's SELECTED_ROAD byte: the rank of the first out-edge of i whose target converts to that
+// value (k_pack_nodes' rule), else SEL_RAW (the value then goes into `sel`): the row itself, -1, an entry no out-edge matches.
+__device__ __forceinline__ uint32_t fs_rank_code(const NodeRec& nr, const int32_t* __restrict__ out_pad, float sv) {
+  uint32_t code = SEL_RAW;
+  const int32_t deg = nr.out_deg;
+#pragma unroll
+  for (int q = 3; q >= 0; --q)
+    if (q < deg && (float)nr.out4[q] == sv) code = (uint32_t)q;
+  if (code == SEL_RAW && deg > 4) {
+    const int32_t* od = out_pad + nr.out0;
+    for (int32_t q = 4; q < deg && q < (int32_t)SEL_RAW; ++q)
+      if ((float)od[q] == sv) {
+        code = (uint32_t)q;
+        break;
+      }
+  }
+  return code;
+}

@@ -1,6 +1,7 @@
 // td_paths.hip — the dynamic relative gap of the vectorised evaluation: time-dependent road times from the occupancy sums of
 // an episode (tarl_td_road_times) and, per (environment, agent), the earliest clock at which the agent could have left its
-// destination road had it known them (tarl_td_hindsight). DESIGN 4.17.
+// destination road had it known them (tarl_td_hindsight). DESIGN 4.17. For the day-to-day replanning loop the same search also
+// returns the PATH (tarl_td_routes).
 //
 // Road time. veh int32 [K][H][N] and frames_per_bin int32 [H] are the occupancy accumulators of §4.15; with
 // cbar = (double)veh / (double)frames_per_bin the time of road n in bin h of environment k is
@@ -208,6 +209,100 @@ __global__ __launch_bounds__(SPT_BLOCK) void k_td_hindsight(
   }
 }
 
+// ---- the quickest route per (environment, agent) (NOT reference semantics: the reference has no replanning) ------
+// The labels of k_td_hindsight, then the PATH: every agent a >= 1 whose origin and destination are in range is searched from
+// its DEPARTURE_TIME whatever its DONE flag (a plan is needed for everybody); best[k][a] = L[d] as above. After the labels
+// have converged wave 0 walks back from d: at v != o the in-neighbour u with leave(v, L[u]) == L[v] (fp64 equality; one exists
+// at the least fixed point), among several the SMALLEST ROAD ID whatever the order of the in-list — the lanes take the
+// in-edges 64 at a time and a wave minimum picks u, so v stays uniform over the wave. With tau >= FF > 0 the labels fall
+// strictly along the walk and it cannot cycle; it is nevertheless bounded: a road without a tight in-edge ends it (len = 0)
+// and so do more than N roads (len = -1; tau = 0 may close a tight cycle). The walk meets the roads from d backwards, so lane
+// 0 pushes them onto a stack of max_hops words behind the workgroup's label row as long as they fit and keeps counting when
+// they do not; a route that fits is then copied out forwards, 64 words at a time: routes[k][a][0] = o ..
+// routes[k][a][len - 1] = d, o == d gives len = 1. Nothing else of the row is touched.
+//   route_len = 0: unreachable destination (best = +inf), dummy row 0, an id out of range (best = +inf), no tight in-edge
+//   route_len = -(true length): the route is longer than max_hops; nothing of its row is written.
+// Every route_len and best entry is written; route entries from len on are left as allocated.
+__global__ __launch_bounds__(SPT_BLOCK) void k_td_routes(
+    const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst, const int32_t* __restrict__ in_ptr,
+    const int32_t* __restrict__ in_src, const float* __restrict__ tau, const double* __restrict__ env, int64_t N,
+    const float* __restrict__ ag, int64_t K, int64_t A, int64_t a_bstride, td_bins b, uint8_t* __restrict__ scratch,
+    int64_t row_bytes, int64_t label_bytes, int32_t max_hops, double* __restrict__ best, int32_t* __restrict__ routes,
+    int32_t* __restrict__ route_len) {
+  extern __shared__ uint32_t td_lds[];
+  const int tid = threadIdx.x;
+  const int32_t W = (int32_t)((N + 31) >> 5);
+  uint32_t* F = td_lds;
+  uint32_t* C = F + W;
+  double* L = (double*)(scratch + (int64_t)blockIdx.x * row_bytes);
+  int32_t* stack = (int32_t*)(scratch + (int64_t)blockIdx.x * row_bytes + label_bytes);
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  const float Nf = (float)N;      // N <= 327 680: exact
+  const int32_t NONE = 0x7FFFFFFF;
+
+  for (int64_t j = blockIdx.x; j < K * A; j += gridDim.x) {
+    const int64_t k = j / A, a = j - k * A;
+    const float* row = ag + k * a_bstride + a * AG_COLS;
+    const float of = row[AG_ORIGIN], df = row[AG_DEST];
+    // uniform over the workgroup: the dummy row and a foreign id are not searched
+    const bool search = a >= 1 && of >= 0.0f && of < Nf && df >= 0.0f && df < Nf;
+    if (!search) {
+      if (tid == 0) {
+        best[j] = INF;
+        route_len[j] = 0;
+      }
+      continue;
+    }
+    const int32_t o = (int32_t)of, d = (int32_t)df;
+    const float* tau_k = tau + k * b.H * N;
+    const double* env_k = env + k * ((int64_t)b.H + 1) * N;
+    td_labels(out_ptr, out_dst, in_ptr, in_src, tau_k, env_k, N, W, tid, o, (double)row[AG_DEP], b, L, F, C);
+    if (tid < 64) {      // wave 0; everything below is uniform over it but `u` before the minimum
+      const double ld = L[d];
+      int64_t cnt = 0;
+      if (ld < INF) {
+        int32_t v = d;
+        cnt = 1;
+        if (tid == 0) stack[0] = d;      // (max_hops >= 1)
+        while (v != o) {
+          const double lv = L[v];
+          int32_t u = NONE;
+          const int32_t k1 = in_ptr[v + 1];
+          for (int32_t e = in_ptr[v] + tid; e < k1; e += 64) {
+            const int32_t s = in_src[e];
+            if (s < u && td_leave(tau_k, env_k, N, v, L[s], b) == lv) u = s;
+          }
+          for (int off = 32; off >= 1; off >>= 1) {
+            const int32_t w = __shfl_xor(u, off, 64);
+            u = w < u ? w : u;
+          }
+          if (u == NONE) {
+            cnt = 0;
+            break;
+          }
+          v = u;
+          if (++cnt > N) {
+            cnt = -1;
+            break;
+          }
+          if (cnt <= max_hops && tid == 0) stack[cnt - 1] = v;
+        }
+      }
+      if (cnt > max_hops) cnt = -cnt;
+      if (cnt > 0) {
+        __threadfence_block();      // lane 0's words, before the other lanes read them
+        int32_t* r = routes + j * (int64_t)max_hops;
+        for (int64_t q = tid; q < cnt; q += 64) r[q] = stack[cnt - 1 - q];
+      }
+      if (tid == 0) {
+        best[j] = ld;
+        route_len[j] = (int32_t)cnt;
+      }
+    }
+    __syncthreads();   // the next search re-initialises the row and the stack wave 0 may still be reading
+  }
+}
+
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------
 #define TD_REQUIRE_BINS()                                                                                      \
   do {                                                                                                         \
@@ -257,6 +352,45 @@ extern "C" int tarl_td_hindsight(const tarl_plan* plan, const float* tau, const 
                      (hipStream_t)stream, plan->out_ptr, plan->out_dst, plan->in_ptr, plan->in_src, tau, env, N, agents, K,
                      num_agents, a_bstride, td_make_bins(bin_seconds, first_bin, H), (uint8_t*)scratch, spt_row_bytes(N, 8),
                      best);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+static bool td_routes_sizes_ok(const tarl_plan* plan, int64_t K, int64_t num_agents, int64_t max_hops) {
+  const int64_t lim = (int64_t)1 << 31;
+  return plan && K >= 1 && K < lim && num_agents >= 1 && num_agents < lim && K * num_agents < ((int64_t)1 << 40) &&
+         max_hops >= 1 && max_hops <= ((int64_t)1 << 20);
+}
+
+// a workgroup's scratch row: the fp64 labels of N roads, then the walk's stack of max_hops road ids
+static int64_t td_routes_row_bytes(int64_t N, int64_t max_hops) { return spt_row_bytes(N, 8) + (4 * max_hops + 255) / 256 * 256; }
+
+extern "C" int64_t tarl_td_routes_scratch_bytes(const tarl_plan* plan, int64_t K, int64_t num_agents, int64_t max_hops) {
+  if (!td_routes_sizes_ok(plan, K, num_agents, max_hops)) return -1;
+  return spt_workgroups(K * num_agents) * td_routes_row_bytes(plan->N, max_hops);
+}
+
+extern "C" int tarl_td_routes(const tarl_plan* plan, const float* tau, const double* env, const float* agents, int64_t K,
+                              int64_t num_agents, int64_t a_bstride, int64_t bin_seconds, int64_t first_bin, int64_t H,
+                              int64_t max_hops, void* scratch, int64_t scratch_bytes, double* best, int32_t* routes,
+                              int32_t* route_len, tarl_stream stream) {
+  TARL_REQUIRE(plan && tau && env && agents && best && routes && route_len, "null argument");
+  TARL_REQUIRE(max_hops >= 1 && max_hops <= ((int64_t)1 << 20), "max_hops must be in [1, 2^20]");
+  TARL_REQUIRE(td_routes_sizes_ok(plan, K, num_agents, max_hops), "bad sizes");
+  TARL_REQUIRE(a_bstride >= num_agents * AG_COLS, "agent tables overlap");
+  TD_REQUIRE_BINS();
+  const int64_t N = plan->N;
+  TARL_REQUIRE(4 * 4 * ((N + 31) / 32) <= SPT_LDS_MAX, "graph too large for the route searches (N > 327680)");
+  TARL_REQUIRE(N >= 1, "bad sizes: the graph has no road");
+  TARL_REQUIRE(scratch && scratch_bytes >= spt_workgroups(K * num_agents) * td_routes_row_bytes(N, max_hops),
+               "scratch too small (tarl_td_routes_scratch_bytes)");
+  const int64_t lds = 4 * 2 * ((N + 31) / 32);
+  if (lds > 64 * 1024)   // the dynamic-LDS limit only needs raising above the 64 KB default
+    TARL_CHECK_HIP(hipFuncSetAttribute((const void*)k_td_routes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_td_routes, dim3((unsigned)spt_workgroups(K * num_agents)), dim3(SPT_BLOCK), (size_t)lds,
+                     (hipStream_t)stream, plan->out_ptr, plan->out_dst, plan->in_ptr, plan->in_src, tau, env, N, agents, K,
+                     num_agents, a_bstride, td_make_bins(bin_seconds, first_bin, H), (uint8_t*)scratch,
+                     td_routes_row_bytes(N, max_hops), spt_row_bytes(N, 8), (int32_t)max_hops, best, routes, route_len);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
 }

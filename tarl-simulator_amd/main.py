@@ -6,7 +6,8 @@
 ``--checkpoint``, the vectorised evaluation ``--eval-envs`` / ``--eval-sampled``, its shortest-path baseline with the paired
 comparison ``--eval-baseline``, the vectorised dijkstra evaluation ``--dijkstra-envs`` (its router: ``--dijkstra-router``) and the per-road link counts of either
 ``--eval-link-counts`` / ``--eval-link-bin`` (also the bins of ``--eval-occupancy``, ``--eval-trips``,
-``--eval-dynamic-gap`` and ``--eval-turns``)."""
+``--eval-dynamic-gap`` and ``--eval-turns``), and the day-to-day replanning loop ``--replan-days`` / ``--replan-envs`` /
+``--replan-fraction`` / ``--replan-max-hops``."""
 import argparse
 import os
 import sys
@@ -20,6 +21,18 @@ from src.agents.base import DijkstraAgents  # noqa: E402
 from src.runner import Runner, RunnerArgs  # noqa: E402
 
 ALGOS = ("dijkstra", "random", "mpnn", "mpnn+ppo")
+
+
+def replan_fraction(text):
+    """--replan-fraction: ``msa`` or a share in (0, 1]."""
+    try:
+        v = text if text == "msa" else float(text)
+    except ValueError:
+        v = None
+    if v is None or (v != "msa" and not 0.0 < v <= 1.0):
+        raise argparse.ArgumentTypeError(f"must be 'msa' or a share in (0, 1], got {text!r}")
+    return v
+
 
 # (flag, argparse keyword arguments)
 OPTIONS = (
@@ -95,6 +108,22 @@ OPTIONS = (
                                help="--dijkstra-envs: the router of the K environments; reference: DijkstraAgents.choice's rule, "
                                     "hold: the one that holds one road short of the destination and delivers (head "
                                     "dijkstra_hold), free_flow: hold on tables built once from the empty network")),
+    ("--replan-days", dict(type=int, default=0, metavar="J",
+                           help="eval, any --algo: J > 0 adds the day-to-day replanning loop (DESIGN 4.19, not in the reference): "
+                                "J simulated days on --replan-envs environments of a fused engine of its own; day 0 follows the "
+                                "quickest routes of the empty network, after every day a share of the agents re-routes onto the "
+                                "quickest route under the road times experienced so far; a `Replanning` block with the day table "
+                                "(arrivals, travel time, dynamic relative gap, share that switched), replan_days.csv, "
+                                "replan_envs.json / replan_envs.csv, and replan_*.csv for the --eval-* report flags that are set")),
+    ("--replan-envs", dict(type=int, default=1, metavar="K",
+                           help="--replan-days: the environments of the loop; equal to --eval-envs it adds the paired block "
+                                "policy - replanned on the last day (same seed: common random numbers)")),
+    ("--replan-fraction", dict(type=replan_fraction, default=0.1, metavar="F|msa",
+                               help="--replan-days: the share of the agents that may switch per day, in (0, 1], or msa: "
+                                    "1 / (day + 2)")),
+    ("--replan-max-hops", dict(type=int, default=None, metavar="L",
+                               help="--replan-days: the longest route stored, in roads (default: min(roads, 256)); an agent "
+                                    "whose quickest route is longer has no route")),
     ("--eval-link-counts", dict(action="store_true",
                                 help="--eval-envs / --dijkstra-envs, eval: count per road the frames in which its head was "
                                      "popped plus those in which an agent was withdrawn from it, over the K environments; a "

@@ -46,6 +46,10 @@ class RunnerArgs:
     eval_dynamic_gap: bool = False # eval_envs / dijkstra_envs, eval: the trips against the best path in hindsight (same bins)
     eval_dynamic_gap_envs: int = None   # ... over the first J of the K environments (default: all)
     eval_turns: bool = False       # eval_envs / dijkstra_envs: vehicles per route edge and the agents quirk Q24 loses (same bins)
+    replan_days: int = 0           # eval, any algo: J > 0 adds the day-to-day replanning loop (tarl_hip.replanning)
+    replan_envs: int = 1           # ... on this many environments of an engine of its own
+    replan_fraction: object = 0.1  # ... the share that may switch per day, in (0, 1], or "msa"
+    replan_max_hops: int = None    # ... the longest route stored (default: min(roads, 256))
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
@@ -96,6 +100,16 @@ class RunnerArgs:
             if not 1 <= int(self.eval_dynamic_gap_envs) <= int(self.eval_envs or self.dijkstra_envs):
                 raise ValueError(f"eval_dynamic_gap_envs must be in [1, {int(self.eval_envs or self.dijkstra_envs)}] (the "
                                  f"environments of the evaluation), got {self.eval_dynamic_gap_envs!r}")
+        if self.replan_days is None or int(self.replan_days) < 0:
+            raise ValueError(f"replan_days must be >= 0, got {self.replan_days!r}")
+        if self.replan_days and self.mode != "eval":
+            raise ValueError("replan_days runs the day-to-day replanning loop after the evaluation: it needs mode 'eval'")
+        if self.replan_envs is None or int(self.replan_envs) < 1:
+            raise ValueError(f"replan_envs must be >= 1, got {self.replan_envs!r}")
+        if self.replan_fraction != "msa" and not 0.0 < float(self.replan_fraction) <= 1.0:
+            raise ValueError(f"replan_fraction must be 'msa' or in (0, 1], got {self.replan_fraction!r}")
+        if self.replan_max_hops is not None and not 1 <= int(self.replan_max_hops) <= 1 << 20:
+            raise ValueError(f"replan_max_hops must be in [1, 2^20], got {self.replan_max_hops!r}")
         if self.eval_link_bin is None or int(self.eval_link_bin) < 1:
             raise ValueError(f"eval_link_bin must be >= 1 second, got {self.eval_link_bin!r}")
         if int(self.iterations) < 1:
@@ -199,6 +213,8 @@ class Runner:
                                      "vectorised evaluation: run without --dijkstra-envs")
                 # the population as loaded: the single-environment pass below marks its agents on the way / arrived
                 self._dijkstra_population = self.agent.agent_features.clone()
+            if a.replan_days:
+                self._replan_setup(self.simulator.graph.edge_index, self.simulator.Nmax, self.agent.agent_features)
         elif a.algo in {"mpnn", "mpnn+ppo"}:
             from .agents.mpnn_agent import MPNNPolicyNet, MPNNValueNetSimple
             self.env = SimulatorEnv(device=str(self.device), timestep_size=a.timestep_size,
@@ -234,10 +250,21 @@ class Runner:
                     raise ValueError("--eval-envs needs the packed (fused) path, which cannot represent this graph (Nmax > "
                                      "127, an out-degree above 126 or parallel edges); there is no fall-back for the "
                                      "vectorised evaluation: run without --eval-envs")
+            if a.replan_days:
+                self._replan_setup(g.edge_index, self.env.simulator.Nmax, self.policy_net.agent_features)
             if a.checkpoint is not None:
                 self.load_checkpoint(a.checkpoint)
         else:
             raise ValueError(f"Unknown algorithm {a.algo}")
+
+    def _replan_setup(self, edge_index, Nmax, agent_features):
+        """--replan-days: refuse a graph the packed path cannot hold, and keep the population as loaded (the passes before the
+        loop mark their agents on the way / arrived)."""
+        from tarl_hip import ops
+        if not ops.fused_path_supported(edge_index, Nmax):
+            raise ValueError("--replan-days needs the packed (fused) path, which cannot represent this graph (Nmax > 127, an "
+                             "out-degree above 126 or parallel edges); there is no fall-back: run without --replan-days")
+        self._replan_population = agent_features.clone()
 
     def load_checkpoint(self, path):
         """Load a ``policy.pt`` written by ``ppo_train`` into the policy network (in place: views held elsewhere stay valid)."""
@@ -334,13 +361,14 @@ class Runner:
             plt.close("all")
         except Exception as exc:  # noqa: BLE001 - analysis output must not fail the run
             print(f"metric tables / figures skipped: {exc}")
+        result = {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg}
         if a.eval_envs and a.algo in {"mpnn", "mpnn+ppo"}:
-            return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg,
-                    "vectorised": self._vectorised_eval(n, out_dir)}
-        if a.dijkstra_envs and a.algo == "dijkstra":
-            return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg,
-                    "vectorised": self._vectorised_dijkstra(n, out_dir)}
-        return {"steps": n, "arrived": int(mask.sum()), "avg_travel_time": avg}
+            result["vectorised"] = self._vectorised_eval(n, out_dir)
+        elif a.dijkstra_envs and a.algo == "dijkstra":
+            result["vectorised"] = self._vectorised_dijkstra(n, out_dir)
+        if a.replan_days:
+            result["replanning"] = self._replanning(n, out_dir, sim, result.get("vectorised"))
+        return result
 
     def _eval_engine(self, sim, agent_features, num_envs):
         """A fused engine of its own for a vectorised evaluation: copies of the graph state and of the agent table, noise
@@ -428,6 +456,56 @@ class Runner:
                 print("\n=== Dynamic gap: policy \u2212 baseline (paired) ===")
                 for line in E.dynamic_gap_paired_lines(rep):
                     print(line)
+
+    def _replanning(self, frames, out_dir, sim, vectorised):
+        """--replan-days J: the day-to-day replanning loop (tarl_hip.replanning.Replanner; not in the reference) on
+        --replan-envs environments of a fused engine of its own, ``frames`` frames per day: a ``Replanning`` block with the
+        day table and the last day's aggregate under the name ``routes``; replan_days.csv (one row per day), replan_envs.json
+        (settings, day records, the last day's aggregate) and replan_envs.csv (one row per environment of the last day);
+        replan_<report>.csv for every --eval-* report flag that is set. Where --eval-envs equals --replan-envs the policy's
+        MODE run is paired with the last day (same seed: common random numbers). -> {"result": ReplanResult[, "paired"]}."""
+        import csv
+        import json
+        from tarl_hip.evaluator import PER_ENV_KEYS, paired_lines, paired_report
+        from tarl_hip.replanning import Replanner, replan_lines, replan_report
+        a = self.args
+        kw = {k: v for k, v in self._link_kw().items() if k not in ("occupancy", "dynamic_gap", "dynamic_gap_envs",
+                                                                    "link_bin_seconds")}
+        engine = self._eval_engine(sim, self._replan_population, a.replan_envs)
+        rp = Replanner(engine, days=a.replan_days, fraction=a.replan_fraction, max_hops=a.replan_max_hops,
+                       link_bin_seconds=a.eval_link_bin, seed=a.seed, **kw)
+        result = rp.run(frames)
+        rep = replan_report(result)
+        print(f"\n=== Replanning ({a.replan_days} days, {a.replan_envs} environments) ===")
+        for line in replan_lines(rep):
+            print(line)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        with open(out_dir / "replan_days.csv", "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=rep["columns"])
+            w.writeheader()
+            w.writerows(rep["rows"])
+        doc = {"settings": rep["settings"], "days": rep["rows"], "days_per_env": rep["env_rows"], "note": rep["note"],
+               "domain_exit_day": rep["domain_exit_day"]}
+        out, rows = {"result": result}, []
+        last = result.last
+        if last is not None:
+            self._print_block(f"Vectorised evaluation ({last.envs} environments, routes, last day)", last)
+            doc["routes"] = last.to_dict()
+            rows = [dict(kind="routes", **r) for r in last.rows()]
+            self._reports_output(doc, last, None, out_dir, "replan")
+            mode = (vectorised or {}).get("mode")
+            if mode is not None and a.algo in {"mpnn", "mpnn+ppo"} and a.eval_envs == a.replan_envs:
+                out["paired"] = doc["paired"] = paired_report(mode, last)
+                print("\n=== Policy \u2212 replanned (paired) ===")
+                for line in paired_lines(out["paired"]):
+                    print(line)
+        with open(out_dir / "replan_envs.json", "w") as f:
+            json.dump(doc, f, indent=1)
+        with open(out_dir / "replan_envs.csv", "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
+            w.writeheader()
+            w.writerows(rows)
+        return out
 
     def _vectorised_dijkstra(self, frames, out_dir):
         """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra", or

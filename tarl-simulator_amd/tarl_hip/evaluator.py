@@ -33,6 +33,19 @@ next hop is its head agent's destination selects ITSELF (``ops.fused_select_next
 nobody from it, and the withdraw collects the agent there once it is due. Everything else is the ``"dijkstra"`` head's. With
 ``refresh_rate=0`` it builds its tables at frame 0 only: after the reset every count is 0, so this is the free-flow
 (all-or-nothing) router under the router's own weight expression. (``"dijkstra"`` keeps refusing 0, as it always has.)
+
+Head ``"routes"`` (NOT in the reference, which has no replanning loop) follows a PLAN: one route per agent
+(``ops.td_routes``), shared by the environments or one per environment. Every frame each row selects the road that follows
+it on its head agent's route (``ops.fused_select_route``, with the hold rule one road short of the destination); a row whose
+head has no route or stands off its route keeps its byte. What that byte is decides whether the head delivers: the
+environment inserts a departing agent into the road its ORIGIN row selects (``Agents.insert_agent_into_network``), not into
+the origin road, and an empty row reads the dummy agent 0, who has no route — so an origin row that nobody stands on keeps a
+stale byte and a newcomer seldom lands on its own route. With ``route_fallback=True`` (the default) the free-flow hold router
+(the ``"dijkstra_hold"`` head on ONE table built at frame 0 from the empty network and shared by the environments) therefore
+writes every row first and the plan overrides it wherever the head is on its route: an agent off its route is led to its
+destination by the free-flow tree and follows its plan again from the first road they share. ``route_fallback=False`` is the
+select kernel alone. No refresh, no policy tensors, no sampled mode; the step order is the environment's, as for the routers.
+``set_routes`` swaps the plan between two runs (``tarl_hip.replanning.Replanner`` does, once per simulated day).
 """
 from __future__ import annotations
 
@@ -57,7 +70,8 @@ from .eval_reports import (CONGESTION_FILE, DYNAMIC_GAP_NOTE, LINK_EXPECTED, LIN
                            turn_bin_names, turn_lines, turn_report, turn_summary)
 
 HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra",
-         "dijkstra_hold")
+         "dijkstra_hold", "routes")
+PLAN_HEADS = ("routes",)                          # follows a per-agent plan (set_routes): no policy tensors, no sampled mode
 ROUTER_HEADS = ("dijkstra", "dijkstra_hold")      # the shortest-path routers: no policy tensors, no sampled mode
 # the names of --eval-baseline / ppo_train(eval_baseline=) -> (head, its VecEvaluator arguments); "free_flow": the hold router
 # on tables built once from the empty network
@@ -278,7 +292,7 @@ class VecEvaluator:
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
-                 dynamic_gap_envs=None, turns=False, turn_block=None):
+                 dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -289,6 +303,9 @@ class VecEvaluator:
         per-environment next-hop tables, for ``"dijkstra_hold"`` also 0 = built at frame 0 only (the free-flow router); ``baseline_dests`` = (dests int64 (D,), dest_slot int32 (N,)) of
         src.agents.base.destination_set over the engine's agent tables (default: computed here by the same rule). The
         (K, D, N) int32 table and the tree scratch are allocated once; more than half the free device memory is refused.
+        Head ``"routes"`` (no ``emb``): ``routes`` = (routes int32 (A, L) or (K, A, L), route_len int32 (A,) or (K, A)) of
+        ``ops.td_routes``, held by reference and read at every frame (:meth:`set_routes` swaps it); ``route_fallback``: the
+        free-flow hold router writes every row before the plan does (module docstring; ``baseline_dests`` as for the routers).
         ``link_counts``: also count, per environment, road and time bin of ``link_bin_seconds``, the frames in which the
         road's head was popped plus those in which an agent was withdrawn from it (the reference's compute_node_metrics /
         plot_daily_counts, src/transportation_simulator.py:563-746). The frames write their two masks into rings of
@@ -331,7 +348,11 @@ class VecEvaluator:
             raise ValueError("head 'embedding_dijkstra' needs prior_table (and dest_slot for a per-destination table)")
         if head == "graph_transformer" and (gt_pe is None or gt_weights is None):
             raise ValueError("head 'graph_transformer' needs gt_pe and gt_weights")
-        if head not in ROUTER_HEADS and emb is None:
+        if head in PLAN_HEADS and routes is None:
+            raise ValueError(f"head {head!r} needs routes = (routes, route_len) of ops.td_routes")
+        if routes is not None and head not in PLAN_HEADS:
+            raise ValueError(f"routes is the plan of the heads {PLAN_HEADS}: head {head!r} does not read it")
+        if head not in ROUTER_HEADS + PLAN_HEADS and emb is None:
             raise ValueError(f"head {head!r} needs emb (the flat embedding tensor)")
         if int(poll_frames) < 1:
             raise ValueError("poll_frames must be >= 1")
@@ -414,6 +435,11 @@ class VecEvaluator:
             self.mode_lp = torch.zeros(1, dtype=torch.float32, device=dev)
         elif head in ROUTER_HEADS:
             self._init_baseline(baseline_dests)
+        elif head in PLAN_HEADS:
+            self.set_routes(*routes)
+            self.route_fallback = bool(route_fallback)
+            if self.route_fallback:
+                self._init_baseline(baseline_dests, tables=1)
         else:
             self.logits = torch.empty((K, E), dtype=torch.float32, device=dev)
             need = int(_lib.load().tarl_graphdist_rollout_scratch_bytes(plan.handle, K))
@@ -432,11 +458,14 @@ class VecEvaluator:
         block = min(self.poll_frames, ring_bytes // frame_bytes)
         return max(1, block if cap is None else min(block, cap))
 
-    def _init_baseline(self, baseline_dests):
+    def _init_baseline(self, baseline_dests, tables=None):
         """The baseline's buffers, once per evaluator: travel times (K, E), the next-hop table (K, D, N) and the tree scratch
-        (O(min(K D, 1024) N)). Refused beyond half the free device memory, like the graph-transformer critic's store."""
+        (O(min(K D, 1024) N)). Refused beyond half the free device memory, like the graph-transformer critic's store.
+        ``tables``: the environments that get a table of their own (default: all K; 1 for the "routes" head's fallback, whose
+        one table is built from environment 0's empty network)."""
         eng = self.eng
-        K, N, E, dev = eng.B, eng.N, eng.E, eng.device
+        N, E, dev = eng.N, eng.E, eng.device
+        K = eng.B if tables is None else int(tables)
         if baseline_dests is None:      # src.agents.base.destination_set's rule: every distinct DESTINATION, row 0 included
             d = torch.unique(eng.agents[..., 1].reshape(-1).to(torch.int64))
             d = d[(d >= 0) & (d < N)].contiguous()
@@ -454,9 +483,26 @@ class VecEvaluator:
                                  f"environments x D = {D} destinations x N = {N} nodes) and tree scratch "
                                  f"({scratch_bytes / 2**30:.2f} GiB) exceed half the free device memory "
                                  f"({free / 2**30:.2f} GiB free): evaluate fewer environments at a time")
-        self.weights = torch.empty((K, E), dtype=torch.float32, device=dev)
+        self.weights = torch.empty((eng.B, E), dtype=torch.float32, device=dev)
         self.table = torch.full((K, D, N), -1, dtype=torch.int32, device=dev)
         self.tree_scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=dev)
+
+    def set_routes(self, routes, route_len):
+        """The plan the ``"routes"`` head follows from the next frame on: ``routes`` int32 (A, L) with ``route_len`` (A,)
+        — one plan for every environment — or (K, A, L) with (K, A). Held by reference; nothing is copied or rebuilt."""
+        if self.head not in PLAN_HEADS:
+            raise ValueError(f"set_routes is for the heads {PLAN_HEADS}, not {self.head!r}")
+        K, A = self.eng.B, self.eng.A
+        for t, name in ((routes, "routes"), (route_len, "route_len")):
+            if not t.is_cuda:
+                raise _lib.TarlError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
+            if t.dtype != torch.int32 or not t.is_contiguous():
+                raise TypeError(f"{name} must be a contiguous int32 tensor")
+        if routes.dim() not in (2, 3) or tuple(routes.shape[:-1]) not in ((A,), (K, A)) or routes.size(-1) < 1 or \
+                tuple(route_len.shape) != tuple(routes.shape[:-1]):
+            raise ValueError(f"routes must be ({A}, L) or ({K}, {A}, L) and route_len the same without L, got "
+                             f"{tuple(routes.shape)} and {tuple(route_len.shape)}")
+        self.routes, self.route_len = routes, route_len
 
     @classmethod
     def from_policy_net(cls, engine, policy_net, prior_dests=None, **kw):
@@ -563,6 +609,17 @@ class VecEvaluator:
             ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec,
                                            hold=self.head == "dijkstra_hold")
             return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
+        if self.head in PLAN_HEADS:     # the same order, the choice read from the plan
+            if eng._packed_stale:
+                eng.resync()
+            if self.route_fallback:
+                if t == 0:              # after the reset every count is 0: free-flow times, the same in every environment
+                    ops.fused_edge_travel_time(eng.plan, eng.fs, out=self.weights)
+                    ops.destination_trees_batched(eng.plan, self.weights[:1], self.dests, out=self.table,
+                                                  scratch=self.tree_scratch)
+                ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table[0], hold=True)
+            ops.fused_select_route(eng.plan, eng.fs, self.routes, self.route_len, choice8=rec)
+            return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
         if self.head == "embedding":
             if rec is not None and deterministic:
                 rec.copy_(self.action8)
@@ -592,6 +649,8 @@ class VecEvaluator:
             raise ValueError("frames must be >= 1")
         if self.head in ROUTER_HEADS and not deterministic:
             raise ValueError(f"head {self.head!r} has no sampled mode: the shortest-path router is deterministic given the state")
+        if self.head in PLAN_HEADS and not deterministic:
+            raise ValueError(f"head {self.head!r} has no sampled mode: a plan is followed, nothing is drawn")
         if trip_pair is not None and not self.trips:
             raise ValueError("trip_pair pairs the trips of two runs: it needs trips=True")
         self._reserve(T)
@@ -663,6 +722,10 @@ class VecEvaluator:
             settings.update(refresh_rate=self.refresh_rate, destinations=int(self.dests.numel()))
         if self.head == "dijkstra_hold":      # (the "dijkstra" head's settings stay as they were)
             settings["hold"] = True
+        if self.head in PLAN_HEADS:           # agents a >= 1 without a usable route: unreachable, or longer than max_hops
+            settings.update(max_hops=int(self.routes.size(-1)), routes_per_env=self.routes.dim() == 3, hold=True,
+                            route_fallback=self.route_fallback,
+                            agents_without_route=int((self.route_len[..., 1:] <= 0).sum()))
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):

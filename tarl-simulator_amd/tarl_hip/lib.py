@@ -148,6 +148,9 @@ SIGNATURES = {
     "tarl_td_road_times": (C.c_int, [_p] * 5 + [_i64] * 5 + [_p, _p, _p]),
     "tarl_td_hindsight_scratch_bytes": (_i64, [_p, _i64, _i64]),
     "tarl_td_hindsight": (C.c_int, [_p, _p, _p, _p] + [_i64] * 6 + [_p, _i64, _p, _p]),
+    "tarl_td_routes_scratch_bytes": (_i64, [_p, _i64, _i64, _i64]),
+    "tarl_td_routes": (C.c_int, [_p, _p, _p, _p] + [_i64] * 7 + [_p, _i64, _p, _p, _p, _p]),
+    "tarl_fused_select_route": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _i64, _i64, _p, _p]),
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),

@@ -1100,6 +1100,92 @@ def td_hindsight(plan: Plan, tau, env, agents, *, bin_seconds, first_bin, out=No
     return out
 
 
+# ---- day-to-day replanning (tarl_hip/replanning.py; NOT reference semantics) ----------------------------------
+TD_ROUTES_MAX_HOPS = 1 << 20
+
+
+def td_routes_bytes(plan: Plan, K: int, num_agents: int, max_hops: int) -> int:
+    """Scratch bytes of :func:`td_routes` for K x num_agents searches (per resident workgroup one fp64 label row of N and
+    the walk's stack of ``max_hops`` road ids); -1 for a bad argument (``max_hops`` outside [1, 2^20] among them)."""
+    return int(_lib.load().tarl_td_routes_scratch_bytes(plan.handle, int(K), int(num_agents), int(max_hops)))
+
+
+def td_routes(plan: Plan, tau, env, agents, *, bin_seconds, first_bin, max_hops, out=None, scratch=None):
+    """The quickest time-dependent route of every (environment, agent) under the road times of :func:`td_road_times`
+    (tarl_td_routes): :func:`td_hindsight`'s search for every agent a >= 1 with origin and destination in range, whatever its
+    DONE flag, from its DEPARTURE_TIME -> ``(best, routes, route_len)``: ``best`` fp64 (K, A), ``routes`` int32
+    (K, A, max_hops) stored forward (origin first, destination at ``route_len - 1``) and ``route_len`` int32 (K, A). Ties go
+    to the in-neighbour with the smallest road id. ``route_len`` 0 with ``best`` +inf: unreachable, row 0, an id out of range;
+    ``-(true length)``: longer than ``max_hops`` (the row is then left as it was). ``best`` and ``route_len`` are written
+    everywhere, ``routes`` only up to the length. ``out``: such a triple to write into; ``scratch`` uint8
+    (:func:`td_routes_bytes`); a refused call leaves ``out`` untouched."""
+    K, A, abs_ = _trip_tables(agents, "agents")
+    N = plan.num_nodes
+    if tau.dim() != 3:
+        raise ValueError(f"tau must be (K, H, N), got {tuple(tau.shape)}")
+    H = tau.size(1)
+    _meta(tau, torch.float32, (K, H, N), "tau")
+    _meta(env, torch.float64, (K, H + 1, N), "env")
+    bin_seconds, first_bin, H = _trip_bins(bin_seconds, first_bin, H)
+    max_hops = int(max_hops)
+    if not 1 <= max_hops <= TD_ROUTES_MAX_HOPS:
+        raise ValueError(f"max_hops must be in [1, {TD_ROUTES_MAX_HOPS}], got {max_hops}")
+    if out is not None:
+        _meta(out[0], torch.float64, (K, A), "out[0] (best)")
+        _meta(out[1], torch.int32, (K, A, max_hops), "out[1] (routes)")
+        _meta(out[2], torch.int32, (K, A), "out[2] (route_len)")
+    if scratch is not None:
+        if scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous():
+            raise TypeError("scratch must be a contiguous 1-D uint8 tensor")
+    for t, dt, name in ((agents, torch.float32, "agents"), (tau, torch.float32, "tau"), (env, torch.float64, "env")):
+        _check_dev(t, dt, name)
+    need = td_routes_bytes(plan, K, A, max_hops)
+    if need < 0:
+        raise _lib.TarlError("tarl_td_routes_scratch_bytes refused the sizes")
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=agents.device)
+    _check_dev(scratch, torch.uint8, "scratch")
+    if out is None:
+        out = (torch.empty((K, A), dtype=torch.float64, device=agents.device),
+               torch.empty((K, A, max_hops), dtype=torch.int32, device=agents.device),
+               torch.empty((K, A), dtype=torch.int32, device=agents.device))
+    best, routes, route_len = out
+    _check_dev(best, torch.float64, "out[0] (best)")
+    _check_dev(routes, torch.int32, "out[1] (routes)")
+    _check_dev(route_len, torch.int32, "out[2] (route_len)")
+    _lib.check(_lib.load().tarl_td_routes(plan.handle, tau.data_ptr(), env.data_ptr(), agents.data_ptr(), K, A, abs_,
+                                          bin_seconds, first_bin, H, max_hops, scratch.data_ptr(), scratch.numel(),
+                                          best.data_ptr(), routes.data_ptr(), route_len.data_ptr(), _lib.current_stream()))
+    return best, routes, route_len
+
+
+def fused_select_route(plan: Plan, fs, routes, route_len, choice8=None):
+    """The SELECTED_ROAD bytes of ``fs`` <- the road that follows every row on its head agent's route
+    (tarl_fused_select_route; the hold rule of :func:`fused_select_next_hop_dest` one road short of the destination).
+    ``routes`` int32 (A, L) with ``route_len`` (A,): one plan shared by the environments, or (B, A, L) with (B, A):
+    environment b's. A row whose head has no route (length <= 0) or stands off its route is left untouched. ``choice8``
+    (B, N) uint8 (optional): the rows' bytes after the call, env-major."""
+    N = plan.num_nodes
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    _check_dev(routes, torch.int32, "routes")
+    _check_dev(route_len, torch.int32, "route_len")
+    _contig(routes, torch.int32, "routes")
+    _contig(route_len, torch.int32, "route_len")
+    if routes.dim() not in (2, 3) or tuple(route_len.shape) != tuple(routes.shape[:-1]) or routes.size(-2) != fs.A or \
+            routes.size(-1) < 1 or (routes.dim() == 3 and routes.size(0) != fs.B):
+        raise ValueError(f"routes must be ({fs.A}, L) or ({fs.B}, {fs.A}, L) int32 and route_len the same without L, got "
+                         f"{tuple(routes.shape)} and {tuple(route_len.shape)}")
+    L = routes.size(-1)
+    if choice8 is not None:
+        _contig(choice8, torch.uint8, "choice8")
+        if tuple(choice8.shape) != (fs.B, N):
+            raise ValueError(f"choice8 must be (B, N) = ({fs.B}, {N})")
+    _lib.check(_lib.load().tarl_fused_select_route(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, routes.data_ptr(),
+                                                   route_len.data_ptr(), fs.A * L if routes.dim() == 3 else 0, L,
+                                                   _lib.ptr(choice8), _lib.current_stream()))
+    return choice8
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")
