@@ -3,7 +3,9 @@ beyond the four of a torus), dead ends and feeder links, a degree-agnostic rando
 of the CPU oracle reaches, and oracle replays with one deliberate restriction each (what a kernel that mishandles long
 in-lists / out-lists or the tie order would compute). Two further graphs keep the sibling structure of a torus — rows 4c ..
 4c+3 leave one intersection and share their upstream rows, every road has out-edges — at in-degrees 0 .. 9 and out-degrees
-1 .. 9: the sibling Direction gather and the quad action draw off the torus. Plain module: no fixtures, nothing here needs
+1 .. 9: the sibling Direction gather and the quad action draw off the torus. LONG127 and LONGMIX are small tori whose roads
+hold up to 126 agents in 127-slot FIFOs — the FIFO-length limit of the packed path — with counters of how far the queues,
+the ring offsets and the inserts of a run get (:func:`long_fifo_counters`). Plain module: no fixtures, nothing here needs
 a GPU.
 
 Ranks: the in-rank of a dual edge is its position among the edges with the same destination in ascending edge id (the
@@ -141,7 +143,10 @@ SIBS_SEED, SIBS_TAILS_SEED = 2, 2
 SIBS_TAILS_MOVED = 18      # six chunks of in-degree above four, three siblings each
 # agents per road, frames
 CENSUS = {"MIXED": dict(per_road=40, T=80), "HUB126": dict(per_road=12, T=80),
-          "SIBS": dict(per_road=40, T=80), "SIBS_TAILS": dict(per_road=40, T=80)}
+          "SIBS": dict(per_road=40, T=80), "SIBS_TAILS": dict(per_road=40, T=80),
+          "LONG127": dict(per_road=150, T=300), "LONGMIX": dict(per_road=150, T=300)}
+LONG_GRAPHS = ("LONG127", "LONGMIX")      # 2 x 2 torus, 940 m links: MAX_NUMBER_OF_AGENT 126, Nmax 127 (the packed path's limit)
+LONG_LENGTH, LONG_SPEED, LONGMIX_SHORT_MAX = 940.0, 94.0, 14.0
 TIE_WHICH = {"SIBS": 1, "SIBS_TAILS": 1}      # which road of the wanted in-degree carries the crafted tie (tie_case)
 
 
@@ -167,6 +172,15 @@ def _graph(name):
             assert detach_sibling_tails(net, SIBS_TAILS_SEED) == SIBS_TAILS_MOVED
         din, dout = degrees(net)
         assert net.num_roads == 56 and set(din.tolist()) == set(SIBS_IN) and int(dout.min()) > 0      # G == N: the quad draw
+    elif name in LONG_GRAPHS:
+        net = synth.torus_network(2, 2, length=LONG_LENGTH, freespeed=LONG_SPEED)
+        nmax = net.Nmax
+        if name == "LONGMIX":      # every third road short (as the ``tiny`` case of test_gpu_fused.py), in the same 127-slot ring
+            net.x[::3, 3 * nmax + 0] = LONGMIX_SHORT_MAX
+            net.critical_number = net.x[:, 3 * nmax + 4] * net.x[:, 3 * nmax + 2] / 3600
+            net.congestion_constant = net.x[:, 3 * nmax + 2] * (net.x[:, 3 * nmax + 0] + 10 - net.critical_number)
+        assert net.num_roads == 16 and net.edge_index.size(1) == 64 and nmax == 127 and int(net.x[:, 3 * nmax].max()) == 126
+        assert float(net.x[0, 3 * nmax + 2]) == 10.0 and ops.fused_path_supported(net.edge_index, nmax)
     else:
         raise KeyError(name)
     return net
@@ -176,7 +190,9 @@ def graph(name):
     """``"MIXED"`` (about 80 roads, in- and out-degrees {0, 1, 3, 4, 5, 8, 9} and more), ``"HUB126"`` (about 280 roads,
     one hub at the degree limit of the packed path: 126 in, 126 out), ``"SIBS"`` (56 roads, four siblings per chunk with
     in-degrees 0 .. 9 and out-degrees 4 and 8, every road with out-edges) or ``"SIBS_TAILS"`` (SIBS whose siblings share
-    only their first four sources, out-degrees 1 .. 9) — a fresh copy, the caller may edit it."""
+    only their first four sources, out-degrees 1 .. 9), ``"LONG127"`` (16 roads of a 2 x 2 torus, 940 m each: up to 126
+    agents in a FIFO of Nmax = 127 slots, free-flow 10 s) or ``"LONGMIX"`` (LONG127 with every third road holding at most 14)
+    — a fresh copy, the caller may edit it."""
     n = _graph(name)
     return synth.SynthNetwork(x=n.x.clone(), edge_index=n.edge_index.clone(), edge_attr=n.edge_attr.clone(), Nmax=n.Nmax,
                               num_roads=n.num_roads, critical_number=n.critical_number.clone(),
@@ -434,19 +450,157 @@ def replay_restricted(net, pop, T, seed, frames, t0=100, **restrict):
     return None
 
 
+# ---- long FIFOs: counts, ring offsets and insert positions beyond 63 ---------------------------------------------------------------
+INS_CAP = 192      # csrc/fused_common.h: ready agents per frame the insert kernel keeps in LDS; more go through global scratch
+LONG_COUNTERS = ("count_ge64", "at_max", "at_last_slot", "offset_ge64", "rings_wrapped", "insert_pos_ge64", "insert_frames_ge64",
+                 "withdraw_ge2",
+                 "e_relief_admissions", "max_count", "done", "due_frame0", "max_inserted_frame0")
+
+
+def masked_counts(x, Nmax, mask):
+    """A copy of ``x`` whose NUMBER_OF_AGENT column is read through ``& mask``."""
+    xm = x.clone()
+    xm[:, 3 * Nmax + 1] = (x[:, 3 * Nmax + 1].to(torch.int64) & mask).float()
+    return xm
+
+
+def core_step_count_masked(x, net, t, uniform, mask):
+    """``sim.core_step`` on ``x`` (in place) whose Direction and Response MESSAGES read every count through ``& mask``
+    (:func:`masked_counts`); the update and the pop work on the true counts. With ``mask = -1`` it is ``sim.core_step``."""
+    ei, Nmax, R = net.edge_index, net.Nmax, net.num_roads
+    agent_id, prob, _ = sim.direction_message(masked_counts(x, Nmax, mask), ei, net.edge_attr.reshape(-1), t, Nmax)
+    chosen = sim.direction_aggregate(agent_id, prob, ei[1], R, uniform=uniform)
+    sim.direction_update(x, chosen, t, Nmax, net.congestion_constant)
+    msg = sim.response_message(masked_counts(x, Nmax, mask), ei, Nmax)
+    popped = torch.zeros(R).scatter_reduce_(0, ei[0], msg, reduce="amax", include_self=False) > 0
+    for base in (0, Nmax, 2 * Nmax):      # the pop of sim.response_step
+        x[popped, base:base + Nmax - 1] = x[popped, base + 1:base + Nmax]
+    x[popped, 3 * Nmax + 1] -= 1
+    return popped
+
+
+def insert_capacity_masked(x, agents, t, net, mask):
+    """``sim.insert`` whose CAPACITY is computed from ``count & mask`` (positions and travel times from the true count), by
+    the oracle's own function on a state whose MAX_NUMBER_OF_AGENT is raised by what the mask hides — the congestion time is
+    a function of MAX - count, so it is then put right from the true MAX; an agent that would land behind the last slot is
+    not kept (a narrowed mask cannot index outside a row). With ``mask = -1`` it is ``sim.insert``."""
+    Nmax = net.Nmax
+    c = sim.Cols(Nmax)
+    n0 = x[:, c.N].clone()
+    hidden = n0 - (n0.to(torch.int64) & mask).float()
+    room = torch.minimum(x[:, c.MAXN] - sim.CONGESTION_FILE - (n0 - hidden), Nmax - n0)      # capacity, clamped to the row
+    true_max = x[:, c.MAXN].clone()
+    x[:, c.MAXN] = n0 + room + sim.CONGESTION_FILE
+    sim.insert(x, agents, t, Nmax, None)
+    x[:, c.MAXN] = true_max
+    n1 = x[:, c.N]
+    for r in torch.nonzero(n1 > n0).view(-1).tolist():      # departure = t + max(free flow, congestion time at the true count)
+        a, b = int(n0[r]), int(n1[r])
+        t_cong = net.congestion_constant[r] / (x[r, c.MAXN] + 10 - n0[r])
+        x[r, 2 * Nmax + a:2 * Nmax + b] = float(t) + torch.maximum(x[r, c.FF], t_cong)
+
+
+def env_step_long(x, agents, net, adj, action, t, uniform, stats, hoff, *, message_mask=None, capacity_mask=None):
+    """``sim.env_step`` from the oracle's own pieces, with what the long-FIFO tests count added into ``stats`` and the
+    host-derived ring offsets ``hoff`` (R,) advanced: a road's offset is the number of agents that left its head since the
+    start (pops and withdrawals) modulo Nmax — where a ring buffer packed at offset 0 keeps its head. ``message_mask`` /
+    ``capacity_mask``: ONE restriction of :func:`core_step_count_masked` / :func:`insert_capacity_masked`. Returns the
+    reward."""
+    Nmax = net.Nmax
+    c = sim.Cols(Nmax)
+    sim.apply_action(x, net.edge_index, action, Nmax)
+    if message_mask is None:
+        _, popped = core_step_counted(x, net, t, uniform, stats["branches"])
+    else:
+        popped = core_step_count_masked(x, net, t, uniform, message_mask)
+    n_core = x[:, c.N].clone()
+    sim.withdraw(x, agents, adj, t, Nmax)
+    gone = n_core - x[:, c.N]
+    n_wd = x[:, c.N].clone()
+    if capacity_mask is None:
+        sim.insert(x, agents, t, Nmax, net.congestion_constant)
+    else:
+        insert_capacity_masked(x, agents, t, net, capacity_mask)
+    n = x[:, c.N]
+    left = popped.long() + gone.long()
+    stats["rings_wrapped"] |= hoff + left >= Nmax
+    hoff.copy_((hoff + left) % Nmax)
+    stats["count_ge64"] += int((n >= 64).sum())
+    stats["at_max"] += int((n >= x[:, c.MAXN]).sum())
+    stats["at_last_slot"] += int((n == Nmax - 1).sum())
+    stats["offset_ge64"] += int((hoff >= 64).sum())
+    stats["insert_pos_ge64"] += int((n - torch.maximum(n_wd, torch.full_like(n, 64.0))).clamp(min=0).sum())
+    stats["insert_frames_ge64"] += int(((n > n_wd) & (n > 64)).sum())
+    stats["withdraw_ge2"] += int((gone >= 2).sum())
+    stats["max_count"] = max(stats["max_count"], int(n.max()))
+    stats["max_inserted"] = int((n - n_wd).max())
+    return (-torch.sum(n)).flatten()
+
+
+def new_long_stats(net):
+    stats = {k: 0 for k in LONG_COUNTERS}
+    stats["branches"] = new_counters()
+    stats["rings_wrapped"] = torch.zeros(net.num_roads, dtype=torch.bool)
+    return stats
+
+
+def long_fifo_counters(net, pop, T, seed, t1, t0=100):
+    """The census run (:func:`census`: ``T`` frames of ``sim.env_step`` from the empty network, population ``pop`` due in
+    ``[t0, t1]``, the seeded actions and uniforms of :func:`census_inputs`) with the counters of the long-FIFO tests. Returns
+    (frames, counters): per frame the state, the agent table and the reward; over all frames and roads —
+    count_ge64: road-frames that end with a count >= 64; at_max: those with count >= MAX_NUMBER_OF_AGENT; at_last_slot: those
+    with count == Nmax - 1 (the packed row turns DIRTY); offset_ge64: road-frames whose host-derived ring offset
+    (:func:`env_step_long`) is >= 64; rings_wrapped: per road (bool), that offset passed Nmax; insert_pos_ge64: agents the
+    insert put at FIFO position >= 64; insert_frames_ge64: road-frames in which it put one there; withdraw_ge2: road-frames in which two or more agents arrived; e_relief_admissions:
+    as :func:`census`; max_count: the largest count a frame ends with; done: agents that arrived; due_frame0: agents due at
+    ``t0``; max_inserted_frame0: the most agents one road received in frame 0. Every frame is asserted equal to
+    ``sim.env_step``'s."""
+    assert float(pop[1:, sim.DEPARTURE_TIME].min()) >= t0 and float(pop[1:, sim.DEPARTURE_TIME].max()) <= t1
+    x, ag = net.x.clone(), pop.clone()
+    xs, ags = x.clone(), pop.clone()
+    adj = net.dense_adjacency()
+    stats, hoff, frames = new_long_stats(net), torch.zeros(net.num_roads, dtype=torch.int64), []
+    stats["due_frame0"] = int((pop[1:, sim.DEPARTURE_TIME] <= t0).sum())
+    for s, (action, u) in enumerate(census_inputs(net, T, seed)):
+        out = sim.env_step(x, ag, net.edge_index, net.edge_attr, adj, action, t0 + s, net.Nmax, uniform=u,
+                           congestion_constant=net.congestion_constant)
+        rw = env_step_long(xs, ags, net, adj, action, t0 + s, u, stats, hoff)
+        assert torch.equal(x, xs) and torch.equal(ag, ags) and torch.equal(rw, out["reward"])
+        if s == 0:
+            stats["max_inserted_frame0"] = stats["max_inserted"]
+        frames.append((x.clone(), ag.clone(), out["reward"].clone()))
+    stats["e_relief_admissions"] = stats["branches"]["e_relief_admissions"]
+    stats["done"] = int(ag[:, sim.DONE].sum())
+    return frames, {k: stats[k] for k in LONG_COUNTERS}
+
+
+def replay_long_restricted(net, pop, T, seed, frames, t0=100, **restrict):
+    """The run of :func:`long_fifo_counters` again with one restriction of :func:`env_step_long` (``message_mask=63``: the
+    Direction and Response messages read the counts through ``& 63``; ``capacity_mask=63``: the insert computes its
+    capacity from ``count & 63``; a mask of -1 hides nothing): the first frame whose state or agent table differs from ``frames`` (None: never)."""
+    x, ag = net.x.clone(), pop.clone()
+    adj = net.dense_adjacency()
+    stats, hoff = new_long_stats(net), torch.zeros(net.num_roads, dtype=torch.int64)
+    for s, (action, u) in enumerate(census_inputs(net, T, seed)):
+        env_step_long(x, ag, net, adj, action, t0 + s, u, stats, hoff, **restrict)
+        if not (torch.equal(x, frames[s][0]) and torch.equal(ag, frames[s][1])):
+            return s
+    return None
+
+
 # ---- a crafted tie across the 4 / 5 boundary of a nine-edge race ----------------------------------------------------------------
-def tie_case(net, x, t, in_degree=9, which=0):
+def tie_case(net, x, t, in_degree=9, which=0, ranks=(3, 4)):
     """Edit ``x`` (in place) and return (edge_attr, e3, e4, road): a road with ``in_degree`` in-edges — the ``which``-th of
     them in ascending road id — whose in-edges of rank 3 and 4 — the last record embedded in NodeRec::in4 and the first of
     the tail loop — are both admissible at time ``t`` and carry the SAME turn probability; with equal Gumbel noise on the
     two (and less on the others) their scores are bit-equal maxima, and the reference's first-maximum rule admits the head
-    of rank 3's road."""
+    of rank 3's road. ``ranks``: another pair of in-ranks (a graph without in-lists longer than four)."""
     ei, nmax = net.edge_index, net.Nmax
     c = sim.Cols(nmax)
     din, _ = degrees(net)
     road = int(torch.nonzero(din == in_degree)[which])
     eids = torch.nonzero(ei[1] == road).view(-1)
-    e3, e4 = int(eids[3]), int(eids[4])
+    e3, e4 = int(eids[ranks[0]]), int(eids[ranks[1]])
     ea = net.edge_attr.clone()
     ea[e4] = ea[e3]
     x[road, c.N] = torch.minimum(x[road, c.N], x[road, c.MAXN] - sim.CONGESTION_FILE - 1)      # room downstream

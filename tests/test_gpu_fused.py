@@ -48,14 +48,17 @@ def check_records(ops, plan, fs, x, Nmax, ag, cc, ec):
     assert int((((fs.tl & 1) == 0) | (fs.gc8 > 0)).sum()) > 0
 
 
-def fused_vs_unfused_frames(ops, net, plan, pops, frames, *, with_cc=True, dt=1, raw_sel=None):
+def fused_vs_unfused_frames(ops, net, plan, pops, frames, *, with_cc=True, dt=1, raw_sel=None, visit=None, repack_at=None):
     """The frame loop of test_fused_equals_unfused_frame_by_frame (tests/test_gpu_irregular.py runs it too): ``frames``
     frames from the empty network with populations ``pops`` (B, A + 1, 9), host-supplied uniforms and Gumbel noise, the
     per-op chain against the fused frame; actions, log-prob, entropy, state, agents, dtt, the pop and withdraw masks, reward
     and counts compared at every frame, the maintained records every ten. ``raw_sel`` = (frame, count, rows, values): at
     that frame SELECTED_ROAD of ``rows`` is overwritten with ``values`` (roads that are no neighbour) on both sides, the
     fused state packed again, and the next ``count`` frames run without the choice phase, so that the raw codes are what
-    the Direction gather meets. Returns (pops + withdrawals seen, the per-op side's agent table)."""
+    the Direction gather meets. ``visit(s, fs)`` is called with the packed state at every frame whose records are checked
+    (tests/test_gpu_long_fifo.py reads the count bytes and ring offsets there). ``repack_at``: before that frame the fused
+    state is packed again from the x it has just exported — every ring offset back to 0 in mid-simulation. Returns
+    (pops + withdrawals seen, the per-op side's agent table)."""
     N, Nmax, E = net.num_roads, net.Nmax, net.edge_index.size(1)
     B, A = pops.size(0), pops.size(1) - 1
     ec = ops.EdgeConst(net.edge_attr, "cuda")
@@ -84,6 +87,8 @@ def fused_vs_unfused_frames(ops, net, plan, pops, frames, *, with_cc=True, dt=1,
             x1[:, rows, 3 * Nmax + 5] = x2[:, rows, 3 * Nmax + 5] = torch.as_tensor(raw_sel[3], dtype=torch.float32, device="cuda")
             ops.fused_pack(plan, fs, x2, Nmax, a2, cc, ec=ec)
             assert bool((fs.sel8[rows] & 0x7F == 0x7F).all())              # carried as raw values
+        if s == repack_at:
+            ops.fused_pack(plan, fs, x2, Nmax, a2, cc, ec=ec)
         draw = raw_sel is None or not raw_sel[0] <= s < raw_sel[0] + raw_sel[1]
         if draw:
             # unfused chain
@@ -110,9 +115,12 @@ def fused_vs_unfused_frames(ops, net, plan, pops, frames, *, with_cc=True, dt=1,
         assert torch.equal(a1, a2), f"agents frame {s}"
         assert torch.equal(dtt1, dtt2) and torch.equal(pop1, pop2) and torch.equal(wd1, wd2), f"masks frame {s}"
         assert torch.equal(r1, r2) and torch.equal(c1, c2.t())
+        assert float(c1.max()) < Nmax, f"a count reached Nmax in frame {s}: the inputs left the reference's domain"
         events += int(pop1.sum()) + int(wd1.sum())
         if s % 10 == 0 or s == frames - 1:
             check_records(ops, plan, fs, x2, Nmax, a2, cc, ec)
+            if visit is not None:
+                visit(s, fs)
     return events, a1
 
 

@@ -2,8 +2,9 @@
 environments), k_obs16_rows and k_obs16_cat (256-thread blocks) — against the exported state, bit for bit, at the shapes
 where their tiles end: B in {1, 63, 64, 65, 130} (below, at and above one environment tile, three tiles), N = 36 (a half road
 tile), 288 (more than one 256-thread block), 80 on MIXED (out-degrees up to 9: SELECTED_ROAD rank bytes above 3 go through
-out_dst[out_ptr[i] + rank]) and 37 on a small hub graph (N % 8 odd); every B on the 36-road torus, every graph at B = 65.
-Twice per engine: straight after reset() and after 25 frames, when counts, ON_WAY flags and rank bytes are live.
+out_dst[out_ptr[i] + rank]), 37 on a small hub graph (N % 8 odd) and 16 on LONGMIX (FIFOs of up to 126 in 127-slot rings: count
+features beyond 100, heads read at ring offsets beyond 63); every B on the 36-road torus, every graph at B = 65.
+Twice per engine: straight after reset() and after 25 frames (LONGMIX: 150), when counts, ON_WAY flags and rank bytes are live.
 
 The reference is ``eng.x`` as test_fused_obs16_matches_the_exported_state builds it (the bf16 builder: ``ref.to(bfloat16)``).
 The export turns the SELECTED_ROAD byte into a road through the same device function the builders use, so that column is
@@ -26,19 +27,19 @@ def _net(name):
         return synth.torus_network(3, 3, heterogeneous=True, seed=1)           # 36 roads: four road tiles and a half
     if name == "torus9x8":
         return synth.torus_network(9, 8, heterogeneous=True, seed=2)           # 288 roads: two blocks of k_obs16_rows
-    if name == "MIXED":
-        return ig.graph("MIXED")
+    if name in ("MIXED", "LONGMIX"):
+        return ig.graph(name)
     return ig.road_network(ig.hub_links([(6, 5), (3, 3)], 10, 4), 4)            # "HUBS37": 37 roads
 
 
-CASES = [("torus3x3", B) for B in (1, 63, 64, 65, 130)] + [(g, 65) for g in ("torus9x8", "MIXED", "HUBS37")]
+CASES = [("torus3x3", B) for B in (1, 63, 64, 65, 130)] + [(g, 65) for g in ("torus9x8", "MIXED", "HUBS37", "LONGMIX")]
 
 
-def _engine(net, B, per_road=3):
+def _engine(net, B, per_road=3, window=20):
     from tarl_hip import synth
     from tarl_hip.engine import SimEngine
     N = net.num_roads
-    pops = torch.stack([synth.population(per_road * N, N, seed=b, t0=21540, t1=21560) for b in range(B)])
+    pops = torch.stack([synth.population(per_road * N, N, seed=b, t0=21540, t1=21540 + window) for b in range(B)])
     eng = SimEngine(net.x.cuda().unsqueeze(0).repeat(B, 1, 1).contiguous(), net.edge_index, net.edge_attr, net.Nmax, pops.cuda(),
                     congestion_constant=net.congestion_constant, seed=4)
     eng.reset()
@@ -90,8 +91,9 @@ def _check(eng, net, what):
 def test_packed_state_builders_match_the_exported_state(graph, B):
     net = _net(graph)
     N = net.num_roads
-    assert N == {"torus3x3": 36, "torus9x8": 288, "MIXED": 80, "HUBS37": 37}[graph]
-    eng = _engine(net, B)
+    assert N == {"torus3x3": 36, "torus9x8": 288, "MIXED": 80, "HUBS37": 37, "LONGMIX": 16}[graph]
+    long_fifo = graph == "LONGMIX"
+    eng = _engine(net, B, ig.CENSUS[graph]["per_road"], 30) if long_fifo else _engine(net, B)
     # straight after reset(): the SELECTED_ROAD bytes are what fused_pack made of the network's column (all zero: the rank of
     # road 0 where a road leads there, SEL_RAW with the raw value 0.0 everywhere else — reset leaves them alone)
     ref, code = _check(eng, net, "after reset")
@@ -104,8 +106,11 @@ def test_packed_state_builders_match_the_exported_state(graph, B):
     assert torch.equal(ref[:, :, 7:], eng.agents[:, :1].expand(B, N, 9))                            # nobody: the dummy's row
     # live state
     eng.prepare_policy(torch.randn(N, generator=torch.Generator().manual_seed(1)).cuda())
-    for _ in range(FRAMES):
+    for _ in range(150 if long_fifo else FRAMES):
         eng.frame_fused()
+    if long_fifo:      # before the builders run: rows at ring offsets beyond 63, and the run stayed inside the domain
+        eng.check_flags()
+        assert int(((eng.fs.tl >> 1) & 127).max()) >= 64
     ref, code = _check(eng, net, "after frames")
     assert float(ref[:, :, 1].sum()) > 0 and float(ref[:, :, 14].sum()) > 0                         # counts and ON_WAY flags
     ranks = code[code != SEL_RAW]
@@ -116,6 +121,8 @@ def test_packed_state_builders_match_the_exported_state(graph, B):
         assert bool((code == SEL_RAW).any())                        # a road without out-edges keeps its raw value
     if graph.startswith("torus"):
         assert int(ranks.max()) == 3 and not bool((code == SEL_RAW).any())
+    if long_fifo:
+        assert 100 <= float(ref[:, :, 1].max()) < net.Nmax and int(ranks.max()) == 3      # the count feature of a long queue
 
 
 def _poison(shape):
