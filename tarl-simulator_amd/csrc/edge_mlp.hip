@@ -7,20 +7,25 @@
 // policy of the build (`policy_head="edge_mlp"`): logits change with every frame, so nothing of GraphDistribution can be
 // hoisted out of the rollout.
 //
-// Forward = the one GEMM-shaped op of the policy, hence on the matrix cores: a workgroup owns 128 edges of one sample,
-// gathers their 33 inputs into LDS, and runs both hidden layers as MFMA tiles out of LDS (the 128 x 64 hidden tile never
-// leaves the CU); layer 3 is a 32-long dot product per edge.
-//   * fp32: v_mfma_f32_32x32x2_f32 — exact fp32 products, k-ordered fma chain (parity contract 1e-4 on the logits);
-//   * bf16: v_mfma_f32_32x32x16_bf16 — inputs, weights and the first hidden activation rounded to bf16 (RNE), fp32
-//     accumulation, second hidden layer and output in fp32: BASELINE config 5's "bf16 MPNN features" (tolerance stated
-//     in tests/test_gpu_edge_mlp.py).
-// Backward (minibatch-sized: sub_batch x E edges, once per optimiser step) recomputes the activations per edge on the
-// vector ALU, stores them k-major, and reduces the weight gradients as long dot products in a fixed order
-// (deterministic; no atomics). Inputs are observations: they need no gradient.
+// What this file holds:
+//   * the observation builders (obs16): x from the packed state of the fused engine (fp32, bf16, a few rows) or from the
+//     reference's tensors;
+//   * the forward, the one GEMM-shaped op of the policy, on the matrix cores, register-resident and "transposed": the
+//     WEIGHTS are the A operands, held by every wave for its whole life, 32 EDGES are the columns, and each layer's
+//     accumulator is the next layer's B operand as it stands — no activation touches LDS. Waves are persistent: each walks
+//     a contiguous range of 32-edge chunks through a software pipeline of the two dependent gathers (edge -> node ids ->
+//     node rows, emr_walk). Three precisions of the same layout:
+//       - fp32: v_mfma_f32_32x32x2_f32 — exact fp32 products, k-ordered fma chain (parity contract 1e-4 on the logits);
+//       - bf16: v_mfma_f32_32x32x16_bf16 — inputs, weights and the first hidden activation rounded to bf16 (RNE), fp32
+//         accumulation, second hidden layer and output in fp32: BASELINE config 5's "bf16 MPNN features" (tolerance
+//         stated in tests/test_gpu_edge_mlp.py), on fp32 or on bf16 observation rows;
+//       - x3: fp32 accuracy on the bf16 pipe, every operand split into three exact bf16 pieces;
+//   * the backward (minibatch-sized: sub_batch x E edges, once per optimiser step). Stage 1 recomputes the fp32 forward
+//     per 32 edges with the forward's own MFMA head, takes the two masked gradients on the matrix cores as well and
+//     stores everything k-major; stage 2 reduces the weight gradients as long dot products in a fixed order
+//     (deterministic; no atomics). Inputs are observations: they need no gradient.
 #include "fused_common.h"
 
-#define EM_TILE 128     // edges per workgroup
-#define EM_THREADS 256
 #define EM_IN 33
 #define EM_H1 64
 #define EM_H2 32
@@ -37,14 +42,20 @@ struct EdgeMlpW {
   const float* b3;  // [1]
 };
 
-// C/D layout of the 32x32 MFMAs: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-__device__ __forceinline__ int em_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
   uint32_t u = __float_as_uint(f);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // NaN stays NaN
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
+}
+// v = h + m + l exactly, three bf16 pieces each rounded to nearest even (every subtraction is exact): how a WEIGHT is split
+// when the kernels build their fragments on the device, once per workgroup. (The x3 kernel splits its activations per
+// chunk by truncation instead, emr_split2.)
+__device__ __forceinline__ void emr_split3_rne(float v, uint16_t* h, uint16_t* m, uint16_t* l) {
+  *h = f32_to_bf16_rne(v);
+  const float r1 = v - __uint_as_float((uint32_t)*h << 16);
+  *m = f32_to_bf16_rne(r1);
+  *l = f32_to_bf16_rne(r1 - __uint_as_float((uint32_t)*m << 16));
 }
 
 // One agent row (9 floats, 36 bytes at a 4-byte-aligned address) as two 16-byte loads and one dword instead of nine dwords:
@@ -64,6 +75,27 @@ __device__ __forceinline__ void load_agent_row(const float* __restrict__ arow, f
 // ---- obs16: x = cat(node_features, agent_features[agent_index]) from the packed state of the fused engine ----------------
 // node_features = x[:, 3*Nmax:] = {MAX, NUMBER_OF_AGENT, FREE_FLOW, LENGTH, MAX_FLOW, SELECTED_ROAD, ROAD_INDEX}
 // (TransportationSimulator.state, src/transportation_simulator.py:360-366); agent_index = the head-of-FIFO id.
+// The 16 values of row (road i, environment b) — the one place that says which column goes where — handed to
+// put(q, float4) a quad at a time, in order: quad 0 can leave before SELECTED_ROAD's dependent loads have come back.
+template <class Put>
+__device__ __forceinline__ void obs16_row(const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
+                                          const float* __restrict__ x0, const Layout& L, int64_t B, const FusedBufs& fb,
+                                          const float* __restrict__ ag, int64_t A, int64_t a_bstride, int64_t i, int64_t b,
+                                          Put&& put) {
+  const int64_t gid = i * B + b;
+  const uint32_t hd = fb.hdp[gid].x;
+  const float4 st = fb.st0[i];
+  const float* xs = x0 + i * L.ldx;     // static columns: environment 0 speaks for all
+  const long long head = (long long)(hd >> 8);
+  const float* arow = ag + b * a_bstride + ((head >= 0 && head < A) ? head : 0) * AG_COLS;
+  float ar[9];
+  load_agent_row(arow, ar);
+  put(0, make_float4(st.x, (float)(hd & HD_CNT), st.y, xs[L.col_maxn() + 3]));
+  put(1, make_float4(xs[L.col_maxflow()], sel_value(fb, out_ptr, out_dst, i, gid), st.z, ar[0]));
+  put(2, make_float4(ar[1], ar[2], ar[3], ar[4]));
+  put(3, make_float4(ar[5], ar[6], ar[7], ar[8]));
+}
+
 // A workgroup owns 8 nodes x 64 environments: the packed words are read env-minor (lanes along the environment:
 // coalesced), the 64-byte rows are turned through LDS, and every environment's 8 rows leave as one 512-byte run.
 #define OB_TI 8
@@ -81,19 +113,8 @@ __global__ __launch_bounds__(256) void k_obs16_packed(const int32_t* __restrict_
     const int il = (tid >> 6) + 4 * r;
     const int64_t i = i0 + il;
     if (b < B && i < N) {
-      const int64_t gid = i * B + b;
-      const uint32_t hd = fb.hdp[gid].x;
-      const float4 st = fb.st0[i];
-      const float* xs = x0 + i * L.ldx;     // static columns: environment 0 speaks for all
-      const long long head = (long long)(hd >> 8);
-      const float* arow = ag + b * a_bstride + ((head >= 0 && head < A) ? head : 0) * AG_COLS;
-      float ar[9];
-      load_agent_row(arow, ar);
       float4* o = reinterpret_cast<float4*>(sm + bl * OB_LD + il * 16);
-      o[0] = make_float4(st.x, (float)(hd & HD_CNT), st.y, xs[L.col_maxn() + 3]);
-      o[1] = make_float4(xs[L.col_maxflow()], sel_value(fb, out_ptr, out_dst, i, gid), st.z, ar[0]);
-      o[2] = make_float4(ar[1], ar[2], ar[3], ar[4]);
-      o[3] = make_float4(ar[5], ar[6], ar[7], ar[8]);
+      obs16_row(out_ptr, out_dst, x0, L, B, fb, ag, A, a_bstride, i, b, [&](int q, const float4 v) { o[q] = v; });
     }
   }
   __syncthreads();
@@ -124,22 +145,12 @@ __global__ __launch_bounds__(256) void k_obs16_packed_bf16(const int32_t* __rest
     const int il = (tid >> 6) + 4 * r;
     const int64_t i = i0 + il;
     if (b < B && i < N) {
-      const int64_t gid = i * B + b;
-      const uint32_t hd = fb.hdp[gid].x;
-      const float4 st = fb.st0[i];
-      const float* xs = x0 + i * L.ldx;
-      const long long head = (long long)(hd >> 8);
-      const float* arow = ag + b * a_bstride + ((head >= 0 && head < A) ? head : 0) * AG_COLS;
-      float ar[9];
-      load_agent_row(arow, ar);
-      const float v[16] = {st.x, (float)(hd & HD_CNT), st.y, xs[L.col_maxn() + 3], xs[L.col_maxflow()],
-                           sel_value(fb, out_ptr, out_dst, i, gid), st.z, ar[0], ar[1], ar[2], ar[3], ar[4],
-                           ar[5], ar[6], ar[7], ar[8]};
       uint4* o = reinterpret_cast<uint4*>(sm + bl * OBB_LD + il * 8);
       uint32_t w[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        w[q] = (uint32_t)f32_to_bf16_rne(v[2 * q]) | ((uint32_t)f32_to_bf16_rne(v[2 * q + 1]) << 16);
+      obs16_row(out_ptr, out_dst, x0, L, B, fb, ag, A, a_bstride, i, b, [&](int q, const float4 v) {
+        w[2 * q] = (uint32_t)f32_to_bf16_rne(v.x) | ((uint32_t)f32_to_bf16_rne(v.y) << 16);
+        w[2 * q + 1] = (uint32_t)f32_to_bf16_rne(v.z) | ((uint32_t)f32_to_bf16_rne(v.w) << 16);
+      });
       o[0] = make_uint4(w[0], w[1], w[2], w[3]);
       o[1] = make_uint4(w[4], w[5], w[6], w[7]);
     }
@@ -164,20 +175,8 @@ __global__ __launch_bounds__(FB) void k_obs16_rows(const int32_t* __restrict__ o
                                                    const int32_t* __restrict__ slot, float* __restrict__ keep) {
   const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
   if (i >= N) return;
-  const int64_t b = env[blockIdx.y];
-  const int64_t gid = i * B + b;
-  const uint32_t hd = fb.hdp[gid].x;
-  const float4 st = fb.st0[i];
-  const float* xs = x0 + i * L.ldx;
-  const long long head = (long long)(hd >> 8);
-  const float* arow = ag + b * a_bstride + ((head >= 0 && head < A) ? head : 0) * AG_COLS;
-  float ar[9];
-  load_agent_row(arow, ar);
   float4* o = reinterpret_cast<float4*>(keep + ((int64_t)slot[blockIdx.y] * N + i) * 16);
-  o[0] = make_float4(st.x, (float)(hd & HD_CNT), st.y, xs[L.col_maxn() + 3]);
-  o[1] = make_float4(xs[L.col_maxflow()], sel_value(fb, out_ptr, out_dst, i, gid), st.z, ar[0]);
-  o[2] = make_float4(ar[1], ar[2], ar[3], ar[4]);
-  o[3] = make_float4(ar[5], ar[6], ar[7], ar[8]);
+  obs16_row(out_ptr, out_dst, x0, L, B, fb, ag, A, a_bstride, i, env[blockIdx.y], [&](int q, const float4 v) { o[q] = v; });
 }
 
 // the same from the reference's tensors: node_features (M, N, >=7 cols, row stride nf_ld) + agent rows gathered by
@@ -205,31 +204,13 @@ __global__ __launch_bounds__(FB) void k_obs16_cat(const float* __restrict__ nf, 
 // the second layer simply walks the hidden units in the order the lanes already hold them (W2's columns are permuted
 // to match when its fragments are built). Activations never touch LDS: gather (each half-wave one 32-byte half of the two
 // 64-byte node rows) -> registers -> MFMAs -> 16 fma + one cross-half add -> logit. Waves are persistent: each builds
-// its weight fragments once and walks a contiguous range of 32-edge chunks, prefetching the next chunk's rows.
+// its weight fragments once and walks a contiguous range of 32-edge chunks (emr_walk below).
 #define EMR_WAVES 4
+// C/D layout of the 32x32 MFMAs: the hidden unit (row) that accumulator register r of half-wave h holds
 __device__ __forceinline__ int emr_unit(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-struct EdgeIn {
-  float4 s0, s1, d0, d1;
-  float ea;
-};
-
-__device__ __forceinline__ EdgeIn emr_load(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
-                                           const float* __restrict__ edge_attr, const float* __restrict__ obs,
-                                           int32_t E, int64_t N, int32_t m, int32_t c, int lane) {
-  int32_t e = c * 32 + (lane & 31);
-  e = e < E ? e : E - 1;                     // the tail chunk's spare lanes repeat the last edge (never stored)
-  const float* om = obs + (int64_t)m * N * 16 + 8 * (lane >> 5);
-  const float4* ps = reinterpret_cast<const float4*>(om + (int64_t)src[e] * 16);
-  const float4* pd = reinterpret_cast<const float4*>(om + (int64_t)dst[e] * 16);
-  EdgeIn in;
-  in.s0 = ps[0];
-  in.s1 = ps[1];
-  in.d0 = pd[0];
-  in.d1 = pd[1];
-  in.ea = edge_attr[e];
-  return in;
-}
+// accumulator order over both 32-row tiles of the first hidden layer: position t = 16 * tile + r of half-wave h is this
+// hidden unit. Layer 2 walks its k in that order, so W2's columns are permuted by it wherever its fragments are built.
+__device__ __forceinline__ int emr_acc_unit(int t, int h) { return 32 * (t >> 4) + emr_unit(t & 15, h); }
 
 // max(x, 0) as ONE integer instruction: a float is negative exactly when its bit pattern is a negative int32 (fmaxf
 // costs two: the IEEE mode quiets signalling NaNs first). -0 and negative NaNs become +0, positive NaNs pass through.
@@ -237,31 +218,6 @@ __device__ __forceinline__ float emr_relu(float x) {
   const int32_t i = __float_as_int(x);
   return __int_as_float(i > 0 ? i : 0);
 }
-
-// chunk g = m * CH + c (host: M * CH < 2^31); a wave walks [g0, g1) keeping (m, c) by increments
-struct ChunkWalk {
-  uint32_t g, g1, CH;
-  int32_t m, c, mn, cn;
-  __device__ __forceinline__ bool init(int64_t E, int64_t M, int wave) {
-    CH = (uint32_t)((E + 31) >> 5);
-    const uint32_t total = (uint32_t)M * CH, nw = gridDim.x * EMR_WAVES, gw = blockIdx.x * EMR_WAVES + wave;
-    const uint32_t per = (total + nw - 1) / nw;
-    g = gw * per;
-    g1 = (g + per < total) ? g + per : total;
-    if (g >= g1) return false;
-    mn = (int32_t)(g / CH);
-    cn = (int32_t)(g - (uint32_t)mn * CH);
-    return true;
-  }
-  __device__ __forceinline__ void step() {      // (m, c) <- the chunk just prefetched; (mn, cn) <- its successor
-    m = mn;
-    c = cn;
-    if (++cn == (int32_t)CH) {
-      cn = 0;
-      ++mn;
-    }
-  }
-};
 
 // relu on eight bf16 at once: rounding keeps the sign, and a bf16 is negative exactly when its bit pattern is a negative
 // int16 — v_pk_max_i16 does two activations per instruction
@@ -284,15 +240,15 @@ __device__ __forceinline__ bf16x8 emr_pack(const float4 a, const float4 b) {
   return __builtin_bit_cast(bf16x8, p);
 }
 
-// ---- the forward kernels' walk over their chunks: a two-stage software pipeline of the gathers -----------------------------
+// ---- the kernels' walk over their chunks (forward and backward): a two-stage software pipeline of the gathers --------------
 // The gathers are two dependent rounds (edge -> node ids -> node rows) of ~1-2 us each against ~0.2 us (bf16) to ~1 us
 // (fp32 MFMA) of arithmetic per chunk. A wave therefore keeps P chunks of rows and P chunks of node ids in flight: a step
 // consumes the rows of chunk c and the ids of chunk c + P (both requested P steps ago), then requests the ids of chunk
 // c + 2P and — with the ids it just consumed — the rows of chunk c + P into the registers it has just freed. The buffers
 // are indexed by step mod P with the loop unrolled P times (a shifting queue would have to MOVE registers whose loads are
 // still in flight, i.e. wait for them), and the ids go out before the rows because the memory counter retires in order.
-// P = 2 with bf16 observations (9 registers per chunk in flight), 1 with fp32 observations (17). Until round 5 the fp32
-// and x3 kernels fetched ids and rows of the NEXT chunk in one go — every chunk then waited a full memory round trip for
+// P = 2 with bf16 observations (9 registers per chunk in flight), 1 with fp32 observations (17: the fp32 and x3 forwards and
+// the backward's stage 1). Until round 5 the fp32 and x3 kernels fetched ids and rows of the NEXT chunk in one go — every chunk then waited a full memory round trip for
 // the ids before it could ask for the rows (a quarter of their wave-time parked at that wait, profiles/r05_mlp_counters.txt).
 // A wave's range of chunks is cut into per-sample segments (round 5): inside one the chunk walkers are plain counters
 // that saturate at the segment's last chunk (66 -> ~35 scalar instructions per chunk against three (sample, chunk) walkers
@@ -397,9 +353,111 @@ __device__ __forceinline__ void emr_walk(const int32_t* __restrict__ src, const 
   }
 }
 
-// fp32: v_mfma_f32_32x32x2_f32, exact fp32 products. k runs [x_src 8h..8h+7] [x_dst 8h..8h+7] for half-wave h (8 + 8
-// k-steps of 2), then one k-step {edge_attr, 1} against {W1[:, 32], b1}: the bias enters the accumulation as an exact
-// product. 34 + 32 MFMAs per 32 edges: the matrix cores are the bound (66 x 16 passes).
+// ---- what the kernels share past the walk ------------------------------------------------------------------------------------
+// b2 / w3 in accumulator-row order of half-wave h. Either in registers for the wave's life (fp32, x3) ...
+__device__ __forceinline__ void emr_b2w3_regs(const EdgeMlpW& W, int h, f32x16& b2r, float (&w3r)[16]) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    b2r[r] = W.b2[emr_unit(r, h)];
+    w3r[r] = W.w3[emr_unit(r, h)];
+  }
+}
+// ... or in two LDS tables [half-wave][16] that are re-read every chunk (two addresses per wave: broadcast), so that 32
+// registers go to loads in flight instead (bf16 forward, backward). The caller's __syncthreads() follows.
+__device__ __forceinline__ void emr_b2w3_lds(const EdgeMlpW& W, int tid, float* B2L, float* W3L) {
+  if (tid < 32) {
+    B2L[tid] = W.b2[emr_unit(tid & 15, tid >> 4)];
+    W3L[tid] = W.w3[emr_unit(tid & 15, tid >> 4)];
+  }
+}
+// c0 <- b2 out of its table (b2l = B2L + 16 h): layer 2's initial accumulator
+__device__ __forceinline__ f32x16 emr_acc_from_lds(const float4* b2l) {
+  f32x16 c0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float4 v = b2l[q];
+    c0[4 * q] = v.x;
+    c0[4 * q + 1] = v.y;
+    c0[4 * q + 2] = v.z;
+    c0[4 * q + 3] = v.w;
+  }
+  return c0;
+}
+// layer 3: this half-wave's half of w3 . relu(c0), w3 from registers or from its LDS table (w3l = W3L + 16 h) ...
+__device__ __forceinline__ float emr_dot_w3(const f32x16& c0, const float (&w3r)[16]) {
+  float part = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) part = fmaf(emr_relu(c0[r]), w3r[r], part);
+  return part;
+}
+__device__ __forceinline__ float emr_dot_w3(const f32x16& c0, const float4* w3l) {
+  float part = 0.0f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float4 v = w3l[q];
+    part = fmaf(emr_relu(c0[4 * q]), v.x, part);
+    part = fmaf(emr_relu(c0[4 * q + 1]), v.y, part);
+    part = fmaf(emr_relu(c0[4 * q + 2]), v.z, part);
+    part = fmaf(emr_relu(c0[4 * q + 3]), v.w, part);
+  }
+  return part;
+}
+// ... then the two halves added across the wave and the logit of this lane's edge e stored by the lower half-wave
+// (h == 0) into lrow, the sample's row of logits; live = false: a pipeline step past the end of its segment
+__device__ __forceinline__ void emr_store_logit(float part, float b3, bool live, int h, int32_t e, int32_t E,
+                                                float* __restrict__ lrow) {
+  const float tot = part + __shfl_xor(part, 32);
+  if (live && h == 0 && e < E) lrow[e] = tot + b3;
+}
+
+// The fp32 head: v_mfma_f32_32x32x2_f32, exact fp32 products. k runs [x_src 8h..8h+7] [x_dst 8h..8h+7] for half-wave h
+// (8 + 8 k-steps of 2), then one k-step {edge_attr, 1} against {W1[:, 32], b1}: the bias enters the accumulation as an
+// exact product. 34 + 32 MFMAs per 32 edges. Its fragments (66 registers) are built once per wave.
+struct EmrHeadF32 {
+  float w1a[2][17], w2a[32];
+  __device__ __forceinline__ EmrHeadF32(const EdgeMlpW& W, int lane) {
+    const int h = lane >> 5, j = lane & 31;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int u = 32 * a + j;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        w1a[a][t] = W.w1[u * EM_IN + 8 * h + t];
+        w1a[a][8 + t] = W.w1[u * EM_IN + 16 + 8 * h + t];
+      }
+      w1a[a][16] = h == 0 ? W.w1[u * EM_IN + 32] : W.b1[u];
+    }
+#pragma unroll
+    for (int t = 0; t < 32; ++t) w2a[t] = W.w2[j * EM_H1 + emr_acc_unit(t, h)];
+  }
+  // a chunk's gathered rows -> this lane's 17 k-values
+  __device__ __forceinline__ static void inputs(const ERows<false>& cur, int h, float (&xin)[17]) {
+    const float x[17] = {cur.s0.x, cur.s0.y, cur.s0.z, cur.s0.w, cur.s1.x, cur.s1.y, cur.s1.z, cur.s1.w,
+                         cur.d0.x, cur.d0.y, cur.d0.z, cur.d0.w, cur.d1.x, cur.d1.y, cur.d1.z, cur.d1.w,
+                         h == 0 ? cur.ea : 1.0f};
+#pragma unroll
+    for (int t = 0; t < 17; ++t) xin[t] = x[t];
+  }
+  // layer 1, tile a: the first hidden layer BEFORE its relu, hidden units [32 a, 32 a + 32) in accumulator order
+  __device__ __forceinline__ f32x16 tile1(int a, const float (&xin)[17]) const {
+    f32x16 acc = {0};
+#pragma unroll
+    for (int t = 0; t < 17; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1a[a][t], xin[t], acc, 0, 0, 0);
+    return acc;
+  }
+  // layer 2 over tile a's hidden units, c0 + W2[:, tile a] h1, on top of the caller's accumulator. RELU: `acc` is tile1's
+  // result and each value passes its relu on the way into its MFMA (the forward); otherwise it is h1 already (the
+  // backward, which stores h1, took the relu in place).
+  template <bool RELU>
+  __device__ __forceinline__ f32x16 half2(int a, const f32x16& acc, f32x16 c0) const {
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+      c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2a[16 * a + t], RELU ? emr_relu(acc[t]) : acc[t], c0, 0, 0, 0);
+    return c0;
+  }
+};
+
+// fp32 forward: the head as it stands, b2 / w3 in registers. The matrix cores are the bound (66 MFMAs x 16 passes).
 __global__ __launch_bounds__(EMR_WAVES * 64) void k_edge_mlp_fwd_f32(const int32_t* __restrict__ src,
                                                                      const int32_t* __restrict__ dst, int64_t E,
                                                                      int64_t N, int64_t M,
@@ -409,49 +467,21 @@ __global__ __launch_bounds__(EMR_WAVES * 64) void k_edge_mlp_fwd_f32(const int32
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the chunk walker lives in SGPRs
   const int h = lane >> 5, j = lane & 31;
-  float w1a[2][17], w2a[32];
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const int u = 32 * a + j;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      w1a[a][t] = W.w1[u * EM_IN + 8 * h + t];
-      w1a[a][8 + t] = W.w1[u * EM_IN + 16 + 8 * h + t];
-    }
-    w1a[a][16] = h == 0 ? W.w1[u * EM_IN + 32] : W.b1[u];
-  }
-#pragma unroll
-  for (int t = 0; t < 32; ++t) w2a[t] = W.w2[j * EM_H1 + 32 * (t >> 4) + emr_unit(t & 15, h)];
+  const EmrHeadF32 head(W, lane);
   f32x16 b2r;
   float w3r[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    b2r[r] = W.b2[emr_unit(r, h)];
-    w3r[r] = W.w3[emr_unit(r, h)];
-  }
+  emr_b2w3_regs(W, h, b2r, w3r);
   const float b3 = W.b3[0];
-  const f32x16 zero = {0};
   emr_walk<1, false>(src, dst, edge_attr, obs, E, N, M, wave, lane, [&](const ERows<false>& cur, int32_t m, int32_t c, bool live) {
-    const float xin[17] = {cur.s0.x, cur.s0.y, cur.s0.z, cur.s0.w, cur.s1.x, cur.s1.y, cur.s1.z, cur.s1.w,
-                           cur.d0.x, cur.d0.y, cur.d0.z, cur.d0.w, cur.d1.x, cur.d1.y, cur.d1.z, cur.d1.w,
-                           h == 0 ? cur.ea : 1.0f};
-    f32x16 acc0 = zero, acc1 = zero;
-#pragma unroll
-    for (int t = 0; t < 17; ++t) {
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1a[0][t], xin[t], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1a[1][t], xin[t], acc1, 0, 0, 0);
-    }
-    f32x16 c0 = b2r;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2a[t], emr_relu(acc0[t]), c0, 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2a[16 + t], emr_relu(acc1[t]), c0, 0, 0, 0);
-    float part = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) part = fmaf(emr_relu(c0[r]), w3r[r], part);
-    const float tot = part + __shfl_xor(part, 32);
-    const int32_t e = c * 32 + j;
-    if (live && h == 0 && e < (int32_t)E) logits[(int64_t)m * E + e] = tot + b3;
+    float xin[17];
+    EmrHeadF32::inputs(cur, h, xin);
+    // one chain after the other, as the compiler has always scheduled this kernel: with the two tiles of layer 1
+    // alternating in the instruction stream it is 5 % slower (profiles/edge_mlp_shared_core.txt)
+    const f32x16 acc0 = head.tile1(0, xin);
+    f32x16 c0 = head.half2<true>(0, acc0, b2r);
+    const f32x16 acc1 = head.tile1(1, xin);
+    c0 = head.half2<true>(1, acc1, c0);
+    emr_store_logit(emr_dot_w3(c0, w3r), b3, live, h, c * 32 + j, (int32_t)E, logits + (int64_t)m * E);
   });
 }
 
@@ -493,25 +523,18 @@ __global__ __launch_bounds__(EMR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
       if (q == 0)
         v = f32_to_bf16_rne(W.w1[u * EM_IN + 32]);
       else if (q < 4) {      // b1 = hi + mid + lo, each piece a bf16
-        const float b = W.b1[u];
-        const uint16_t hi = f32_to_bf16_rne(b);
-        const float r1 = b - __uint_as_float((uint32_t)hi << 16);
-        const uint16_t mid = f32_to_bf16_rne(r1);
-        const float r2 = r1 - __uint_as_float((uint32_t)mid << 16);
-        v = q == 1 ? hi : q == 2 ? mid : f32_to_bf16_rne(r2);
+        uint16_t hi, mid, lo;
+        emr_split3_rne(W.b1[u], &hi, &mid, &lo);
+        v = q == 1 ? hi : q == 2 ? mid : lo;
       }
     }
     W1f[idx] = v;
   }
-  for (int idx = tid; idx < 4 * 64 * 8; idx += EMR_WAVES * 64) {
+  for (int idx = tid; idx < 4 * 64 * 8; idx += EMR_WAVES * 64) {      // k-step ks, element q = accumulator position 8 ks + q
     const int q = idx & 7, l = (idx >> 3) & 63, ks = idx >> 9;
-    const int u = 32 * (ks >> 1) + emr_unit(8 * (ks & 1) + q, l >> 5);
-    W2f[idx] = f32_to_bf16_rne(W.w2[(l & 31) * EM_H1 + u]);
+    W2f[idx] = f32_to_bf16_rne(W.w2[(l & 31) * EM_H1 + emr_acc_unit(8 * ks + q, l >> 5)]);
   }
-  if (tid < 32) {
-    B2L[tid] = W.b2[emr_unit(tid & 15, tid >> 4)];
-    W3L[tid] = W.w3[emr_unit(tid & 15, tid >> 4)];
-  }
+  emr_b2w3_lds(W, tid, B2L, W3L);
   __syncthreads();
   bf16x8 w1f[6], w2f[4];
 #pragma unroll
@@ -551,33 +574,14 @@ __global__ __launch_bounds__(EMR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
       hb[s2] = emr_relu8(__builtin_bit_cast(bf16x8, p0));
       hb[2 + s2] = emr_relu8(__builtin_bit_cast(bf16x8, p1));
     }
-    f32x16 c0;
     asm volatile("" ::: "memory");      // keeps the two LDS tables out of loop-invariant registers
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = b2l[q];
-      c0[4 * q] = v.x;
-      c0[4 * q + 1] = v.y;
-      c0[4 * q + 2] = v.z;
-      c0[4 * q + 3] = v.w;
-    }
+    f32x16 c0 = emr_acc_from_lds(b2l);
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[0], hb[0], c0, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[1], hb[1], c0, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[2], hb[2], c0, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[3], hb[3], c0, 0, 0, 0);
-    float part = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = w3l[q];
-      part = fmaf(emr_relu(c0[4 * q]), v.x, part);
-      part = fmaf(emr_relu(c0[4 * q + 1]), v.y, part);
-      part = fmaf(emr_relu(c0[4 * q + 2]), v.z, part);
-      part = fmaf(emr_relu(c0[4 * q + 3]), v.w, part);
-    }
-    const float tot = part + __shfl_xor(part, 32);
-    const int32_t e = __builtin_amdgcn_readfirstlane(c) * 32 + (lane & 31);
-    float* lrow = logits + (int64_t)__builtin_amdgcn_readfirstlane(m) * E;
-    if (live && h == 0 && e < (int32_t)E) lrow[e] = tot + b3;
+    emr_store_logit(emr_dot_w3(c0, w3l), b3, live, h, __builtin_amdgcn_readfirstlane(c) * 32 + (lane & 31), (int32_t)E,
+                    logits + (int64_t)__builtin_amdgcn_readfirstlane(m) * E);
   });
 }
 
@@ -618,12 +622,6 @@ __device__ __forceinline__ Split3 emr_split2(float a, float b) {
   r.l = emr_pack_hi16(sa, sb);
   return r;
 }
-__device__ __forceinline__ void emr_split_host3(float v, uint16_t* h, uint16_t* m, uint16_t* l) {
-  *h = f32_to_bf16_rne(v);
-  const float r1 = v - __uint_as_float((uint32_t)*h << 16);
-  *m = f32_to_bf16_rne(r1);
-  *l = f32_to_bf16_rne(r1 - __uint_as_float((uint32_t)*m << 16));
-}
 struct Frag3 {
   bf16x8 h, m, l;
 };
@@ -650,6 +648,15 @@ __device__ __forceinline__ f32x16 emr_mma6(const Frag3& w, const Frag3& x, f32x1
   return acc;
 }
 
+// element q of lane l in the three piece fragments 3 f, 3 f + 1, 3 f + 2 of a fragment-ordered weight table
+__device__ __forceinline__ void emx_put3(uint16_t* F, int f, int l, int q, float v) {
+  uint16_t ph, pm, pl;
+  emr_split3_rne(v, &ph, &pm, &pl);
+  F[((f * 3 + 0) * 64 + l) * 8 + q] = ph;
+  F[((f * 3 + 1) * 64 + l) * 8 + q] = pm;
+  F[((f * 3 + 2) * 64 + l) * 8 + q] = pl;
+}
+
 #define EMX_W1 (2 * 2 * 3)     // W1 fragments: [tile][k-step][piece]
 #define EMX_W2 (4 * 3)         // W2 fragments: [k-step][piece]
 __global__ __launch_bounds__(EMR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_edge_mlp_fwd_x3(const int32_t* __restrict__ src,
@@ -668,29 +675,20 @@ __global__ __launch_bounds__(EMR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
   for (int idx = tid; idx < 2 * 2 * 64 * 8; idx += EMR_WAVES * 64) {
     const int q = idx & 7, l = (idx >> 3) & 63, f = idx >> 9;           // f = tile * 2 + k-step
     const int a = f >> 1, ks = f & 1, u = 32 * a + (l & 31), hh = l >> 5;
-    uint16_t ph, pm, pl;
-    emr_split_host3(W.w1[u * EM_IN + 16 * ks + 8 * hh + q], &ph, &pm, &pl);
-    W1f[((f * 3 + 0) * 64 + l) * 8 + q] = ph;
-    W1f[((f * 3 + 1) * 64 + l) * 8 + q] = pm;
-    W1f[((f * 3 + 2) * 64 + l) * 8 + q] = pl;
+    emx_put3(W1f, f, l, q, W.w1[u * EM_IN + 16 * ks + 8 * hh + q]);
   }
   for (int idx = tid; idx < 2 * 64 * 8; idx += EMR_WAVES * 64) {
     const int q = idx & 7, l = (idx >> 3) & 63, a = idx >> 9;
     const int u = 32 * a + (l & 31), hh = l >> 5;
     uint16_t wh, wm, wl, bh, bm, bl;
-    emr_split_host3(W.w1[u * EM_IN + 32], &wh, &wm, &wl);
-    emr_split_host3(W.b1[u], &bh, &bm, &bl);
+    emr_split3_rne(W.w1[u * EM_IN + 32], &wh, &wm, &wl);
+    emr_split3_rne(W.b1[u], &bh, &bm, &bl);
     const uint16_t lo8[8] = {wh, wm, wl, wh, wm, wh, bh, bm};
     WEf[idx] = hh == 0 ? lo8[q] : (q == 0 ? bl : (uint16_t)0);
   }
-  for (int idx = tid; idx < 4 * 64 * 8; idx += EMR_WAVES * 64) {
+  for (int idx = tid; idx < 4 * 64 * 8; idx += EMR_WAVES * 64) {      // k-step ks, element q = accumulator position 8 ks + q
     const int q = idx & 7, l = (idx >> 3) & 63, ks = idx >> 9;
-    const int u = 32 * (ks >> 1) + emr_unit(8 * (ks & 1) + q, l >> 5);
-    uint16_t ph, pm, pl;
-    emr_split_host3(W.w2[(l & 31) * EM_H1 + u], &ph, &pm, &pl);
-    W2f[((ks * 3 + 0) * 64 + l) * 8 + q] = ph;
-    W2f[((ks * 3 + 1) * 64 + l) * 8 + q] = pm;
-    W2f[((ks * 3 + 2) * 64 + l) * 8 + q] = pl;
+    emx_put3(W2f, ks, l, q, W.w2[(l & 31) * EM_H1 + emr_acc_unit(8 * ks + q, l >> 5)]);
   }
   __syncthreads();
   // The 26 weight fragments (104 registers) stay in LDS and are read where they are used (a lane's 16 bytes are consecutive:
@@ -712,11 +710,7 @@ __global__ __launch_bounds__(EMR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
   auto lwe = [&](int a) { return *reinterpret_cast<const bf16x8*>(WEf + (a * 64 + lane) * 8); };
   f32x16 b2r;
   float w3r[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    b2r[r] = W.b2[emr_unit(r, h)];
-    w3r[r] = W.w3[emr_unit(r, h)];
-  }
+  emr_b2w3_regs(W, h, b2r, w3r);
   const float b3 = W.b3[0];
   const f32x16 zero = {0};
   emr_walk<1, false>(src, dst, edge_attr, obs, E, N, M, wave, lane, [&](const ERows<false>& cur, int32_t m, int32_t c, bool live) {
@@ -747,12 +741,7 @@ __global__ __launch_bounds__(EMR_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
       for (int q = 0; q < 8; ++q) hv[q] = emr_relu((ks < 2 ? acc0 : acc1)[8 * (ks & 1) + q]);
       c0 = emr_mma6(lw2(ks), emr_split8(hv), c0);
     }
-    float part = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) part = fmaf(emr_relu(c0[r]), w3r[r], part);
-    const float tot = part + __shfl_xor(part, 32);
-    const int32_t e = c * 32 + j;
-    if (live && h == 0 && e < (int32_t)E) logits[(int64_t)m * E + e] = tot + b3;
+    emr_store_logit(emr_dot_w3(c0, w3r), b3, live, h, c * 32 + j, (int32_t)E, logits + (int64_t)m * E);
   });
 }
 
@@ -781,66 +770,27 @@ __global__ __launch_bounds__(EMR_WAVES * 64) void k_edge_mlp_bwd_edges(const int
     const int l = idx & 63, ks = (idx >> 6) & 15, a = idx >> 10;
     W2T[idx] = W.w2[emr_unit(ks, l >> 5) * EM_H1 + 32 * a + (l & 31)];
   }
-  if (tid < 32) {
-    B2L[tid] = W.b2[emr_unit(tid & 15, tid >> 4)];
-    W3L[tid] = W.w3[emr_unit(tid & 15, tid >> 4)];
-  }
+  emr_b2w3_lds(W, tid, B2L, W3L);
   __syncthreads();
-  float w1a[2][17], w2a[32];
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const int u = 32 * a + j;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      w1a[a][t] = W.w1[u * EM_IN + 8 * h + t];
-      w1a[a][8 + t] = W.w1[u * EM_IN + 16 + 8 * h + t];
-    }
-    w1a[a][16] = h == 0 ? W.w1[u * EM_IN + 32] : W.b1[u];
-  }
-#pragma unroll
-  for (int t = 0; t < 32; ++t) w2a[t] = W.w2[j * EM_H1 + 32 * (t >> 4) + emr_unit(t & 15, h)];
+  const EmrHeadF32 head(W, lane);
   const float4* b2l = reinterpret_cast<const float4*>(B2L + 16 * h);
   const float4* w3l = reinterpret_cast<const float4*>(W3L + 16 * h);
   const f32x16 zero = {0};
   const int64_t L = M * E;
-  ChunkWalk cw;
-  if (!cw.init(E, M, wave)) return;
-  EdgeIn nxt = emr_load(src, dst, edge_attr, obs, (int32_t)E, N, cw.mn, cw.cn, lane);
-  for (; cw.g < cw.g1; ++cw.g) {
-    const EdgeIn cur = nxt;
-    cw.step();
-    if (cw.g + 1 < cw.g1) nxt = emr_load(src, dst, edge_attr, obs, (int32_t)E, N, cw.mn, cw.cn, lane);
-    const int32_t e = cw.c * 32 + j;
+  emr_walk<1, false>(src, dst, edge_attr, obs, E, N, M, wave, lane, [&](const ERows<false>& cur, int32_t m, int32_t c, bool) {
+    const int32_t e = c * 32 + j;
     const bool live = e < (int32_t)E;
-    const int64_t l = (int64_t)cw.m * E + (live ? e : 0);
-    const float xin[17] = {cur.s0.x, cur.s0.y, cur.s0.z, cur.s0.w, cur.s1.x, cur.s1.y, cur.s1.z, cur.s1.w,
-                           cur.d0.x, cur.d0.y, cur.d0.z, cur.d0.w, cur.d1.x, cur.d1.y, cur.d1.z, cur.d1.w,
-                           h == 0 ? cur.ea : 1.0f};
-    f32x16 acc0 = zero, acc1 = zero;
-#pragma unroll
-    for (int t = 0; t < 17; ++t) {
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1a[0][t], xin[t], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1a[1][t], xin[t], acc1, 0, 0, 0);
-    }
+    const int64_t l = (int64_t)m * E + (live ? e : 0);
+    float xin[17];
+    EmrHeadF32::inputs(cur, h, xin);
+    f32x16 acc0 = head.tile1(0, xin), acc1 = head.tile1(1, xin);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       acc0[r] = emr_relu(acc0[r]);
       acc1[r] = emr_relu(acc1[r]);
     }
     asm volatile("" ::: "memory");      // keeps the LDS tables out of loop-invariant registers
-    f32x16 c0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = b2l[q];
-      c0[4 * q] = v.x;
-      c0[4 * q + 1] = v.y;
-      c0[4 * q + 2] = v.z;
-      c0[4 * q + 3] = v.w;
-    }
-#pragma unroll
-    for (int t = 0; t < 16; ++t) c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2a[t], acc0[t], c0, 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2a[16 + t], acc1[t], c0, 0, 0, 0);
+    const f32x16 c0 = head.half2<false>(1, acc1, head.half2<false>(0, acc0, emr_acc_from_lds(b2l)));
     const float g = grad_logits[l];
     f32x16 dh2;
 #pragma unroll
@@ -875,7 +825,7 @@ __global__ __launch_bounds__(EMR_WAVES * 64) void k_edge_mlp_bwd_edges(const int
         D2T[u * L + l] = dh2[r];
       }
     }
-  }
+  });
 }
 
 // stage 2: C[p][q] += sum_l A[p][l] * Bm[q][l] for an 8 x 8 block of outputs per workgroup (Bm == NULL: a row of ones,
@@ -1008,25 +958,18 @@ extern "C" int tarl_policy_edge_mlp_fwd(const tarl_plan* plan, const float* obs1
   const int64_t chunks = M * ceil_div(plan->E, 32);
   TARL_REQUIRE(chunks < ((int64_t)1 << 31) && plan->E < ((int64_t)1 << 31) - 32 && plan->N < ((int64_t)1 << 26),
                "edge MLP: batch x edges too large");
-  int64_t blocks = ceil_div(chunks, (int64_t)EMR_WAVES * 16);          // >= 16 chunks per wave
-  // workgroups the chip holds at once (VGPR-bound): fp32 2 per CU, bf16 on fp32 rows 3, bf16 on bf16 rows 4
-  const int64_t resident = 256 * (precision == 0 || precision == 3 ? 2 : (precision == 2 ? 4 : 3));
-  if (blocks > resident) blocks = resident;                             // one round: no tail
-  if (precision == 3) {
-    blocks = ceil_div(chunks, (int64_t)EMR_WAVES * 16);
-    if (blocks > 256 * 4) blocks = 256 * 4;      // 119 registers, 26 KB of LDS: four workgroups per CU, one round
-    hipLaunchKernelGGL(k_edge_mlp_fwd_x3, dim3((unsigned)blocks), dim3(EMR_WAVES * 64), 0, (hipStream_t)stream,
-                       plan->src, plan->dst, plan->E, plan->N, M, obs16, edge_attr, W, logits);
-  }
-  else if (precision == 0)
-    hipLaunchKernelGGL(k_edge_mlp_fwd_f32, dim3((unsigned)blocks), dim3(EMR_WAVES * 64), 0, (hipStream_t)stream,
-                       plan->src, plan->dst, plan->E, plan->N, M, obs16, edge_attr, W, logits);
-  else if (precision == 1)
-    hipLaunchKernelGGL(k_edge_mlp_fwd_bf16<false>, dim3((unsigned)blocks), dim3(EMR_WAVES * 64), 0, (hipStream_t)stream,
-                       plan->src, plan->dst, plan->E, plan->N, M, (const void*)obs16, edge_attr, W, logits);
-  else
-    hipLaunchKernelGGL(k_edge_mlp_fwd_bf16<true>, dim3((unsigned)blocks), dim3(EMR_WAVES * 64), 0, (hipStream_t)stream,
-                       plan->src, plan->dst, plan->E, plan->N, M, (const void*)obs16, edge_attr, W, logits);
+  // >= 16 chunks per wave, and no more workgroups than the chip holds at once (256 CUs x what a CU holds of the kernel,
+  // VGPR- and LDS-bound): one round, no tail
+  auto launch = [&](auto kernel, int64_t per_cu) {
+    int64_t blocks = ceil_div(chunks, (int64_t)EMR_WAVES * 16);
+    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(EMR_WAVES * 64), 0, (hipStream_t)stream, plan->src, plan->dst,
+                       plan->E, plan->N, M, obs16, edge_attr, W, logits);
+  };
+  if (precision == 0) launch(k_edge_mlp_fwd_f32, 2);
+  else if (precision == 1) launch(k_edge_mlp_fwd_bf16<false>, 3);
+  else if (precision == 2) launch(k_edge_mlp_fwd_bf16<true>, 4);
+  else launch(k_edge_mlp_fwd_x3, 4);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
 }

@@ -7,7 +7,8 @@ that every case would notice each unit of work the kernel could lose or misplace
 
 The kernel, restated. Stage 1 (``k_edge_mlp_bwd_edges``): the edges of sample m are cut into CH = ceil(E / 32) chunks of 32 lanes,
 chunk g = m * CH + c; the launch has min(256, ceil(M * CH / 16)) workgroups of four waves, wave gw walks the contiguous range
-[gw * per, min((gw + 1) * per, M * CH)) with per = ceil(M * CH / waves), carrying (m, c) by increments (``struct ChunkWalk``).
+[gw * per, min((gw + 1) * per, M * CH)) with per = ceil(M * CH / waves), carrying (m, c) by increments (``emr_walk``, the walk the
+forwards use as well: one division for the range's first chunk, then c counts up inside a sample and m steps at its end).
 Lane j of chunk (m, c) is edge e = 32 c + j, live when e < E, and stores its record — x, h1, h2 and the gradients d1, d2 of the
 two pre-activations — k-major at the flat index l = m * E + e of a scratch of 225 * L floats, L = M * E. Stage 2 (``k_nt_dot``):
 every gradient is a dot product over l, cut into ND_SPLIT = 64 ranges of span = ceil(L / 64); in a range 256 threads stride in
@@ -103,8 +104,9 @@ def single_edge64(obs, edge_index, edge_attr, weights, m, e):
 
 # ---- how the kernel partitions the work ------------------------------------------------------------------------------------
 class Walk:
-    """``ChunkWalk`` for (E, M): the grid, and per chunk g its wave and the (m, c) the walker holds when it computes it —
-    obtained by WALKING (init's division for the first chunk of a range, step's carry afterwards), not by dividing g."""
+    """The backward's ``emr_walk`` for (E, M): the grid, and per chunk g its wave and the (m, c) the walker holds when it
+    computes it — obtained by WALKING (one division for the first chunk of a range, the carry into the next sample
+    afterwards), not by dividing g."""
 
     def __init__(self, E, M):
         self.E, self.M = E, M
@@ -165,7 +167,7 @@ class Walk:
         return [gw for gw in self.active if gw > 0 and self.c[self.ranges[gw][0]] != 0]
 
     def crossings(self):
-        """(wave, g): g is the first chunk of a new sample INSIDE the wave's range (the carry of ``step``)."""
+        """(wave, g): g is the first chunk of a new sample INSIDE the wave's range (the walker's carry: a new segment)."""
         out = []
         for gw in self.active:
             g0, g1 = self.ranges[gw]
@@ -328,7 +330,7 @@ class Case:
         out["one split range"] = (list(range(*s.bounds(z))), None)
         out["after the first stride pass of one range"] = ((list(range(s.bounds(z)[0] + ND_T, s.bounds(z)[1])), None)
                                                            if s.span > ND_T else None)
-        # the carry of step() lost: the chunks of a range past its first sample read the FIRST sample's observation (their
+        # the walker's carry lost: the chunks of a range past its first sample read the FIRST sample's observation (their
         # store index and grad_logits stay right)
         crossing = sorted({gw for gw, _ in w.crossings()})
         if crossing:

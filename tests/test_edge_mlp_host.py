@@ -1,6 +1,6 @@
 """CPU: pins tests/edge_mlp_restatement.py (the float64 reference of test_gpu_edge_mlp_bwd.py) to what the project already
 trusts — float64 autograd of oracle/nets.edge_mlp_logits and the reference's golden —, checks that the emulation of the
-backward's work partition (``ChunkWalk``'s grid and ranges, the flat index, ``k_nt_dot``'s split ranges and stride passes)
+backward's work partition (the grid and ranges of ``emr_walk``, the flat index, ``k_nt_dot``'s split ranges and stride passes)
 reproduces the facts the case list is built on, so that a change of EMR_WAVES, ND_SPLIT, ND_T or the grid rule fails here
 first, and checks that every GPU case is sensitive: each unit of work the kernel could lose or misplace moves every gradient
 it can reach by at least 10x the tolerance the GPU test applies to it (all of it computable without a GPU).
