@@ -412,13 +412,18 @@ typedef struct tarl_fused {
    * (DEPARTURE_TIME column, src/agents/base.py:244-262). The rollout launcher sizes the insert kernel's share of a wave
    * per environment by it (a frame of dt seconds brings ~due_rate * dt candidates). Never changes a result. */
   float due_rate;
-  int32_t reserved_;
+  /* the policy hold rule of the state-dependent rollouts (tarl_fused_set_policy_hold below; 0 = off, the default — the word
+   * was reserved and zero until the rule existed, so a caller that never heard of it has it off) */
+  int32_t policy_hold;
   /* device scratch of tarl_fused_bufs_bytes() bytes, 16-byte aligned (required by the frame / rollout entry points): the
    * library keeps a device-resident copy of this table of pointers there (written by a one-thread launch at the head of every
    * such call, on the call's stream), and the row pass and the insert kernels read the pointers they need from it through the
    * scalar cache instead of carrying all of them as kernel arguments — 27 pointer arguments cost those kernels a dozen
    * scalar-register pairs each, most of them spilled (csrc/fused_pack.hip: k_set_bufs). */
   void* bufs_dev;
+  /* int32 [B] or NULL, read ONLY while policy_hold != 0 (a caller with the shorter, earlier struct never sets that word):
+   * += the rows held, per environment, by every frame of a state-dependent rollout (tarl_fused_set_policy_hold) */
+  int32_t* policy_held;
 } tarl_fused;
 
 /* floats per (node, environment) row of tarl_fused.slots for FIFOs of Nmax slots */
@@ -1076,6 +1081,40 @@ int tarl_td_routes(const tarl_plan* plan, const float* tau, const double* env, c
 int tarl_fused_select_route(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
                             const int32_t* routes, const int32_t* route_len, int64_t r_bstride, int64_t max_hops,
                             uint8_t* choice8, tarl_stream stream);
+
+/* ---- the hold rule on a POLICY's action (an action shield) -------------------------------------------------------
+ * NOT reference semantics, off by default. The environment's step order (SimulatorEnv._step,
+ * src/reinforcement_learning.py:222-309) is choice, core, withdraw / insert, reward, and the withdraw rule
+ * (Agents.withdraw_agent_from_network, src/agents/base.py:334-403) collects an agent at the head of a road ADJACENT to its
+ * destination once its departure there is due. The core runs first and moves that agent onto the road its row selected: a
+ * policy that picks the destination road strands its agent on it, whatever it has learned. tarl_fused_select_next_hop_hold
+ * fixes this for the routers; this is the same rule as a post-pass over the bytes ANY policy head has just written. The draw,
+ * its log-prob and the PPO update are untouched. TARL_ABI_VERSION is unchanged: nothing existing moved.
+ * tarl_fused_hold_policy_actions: for every row i and environment b of the packed state, on integers throughout: the row
+ *   HOLDS when its FIFO is non-empty (count bits of tarl_fused.hdp != 0), its head agent h = hdp >> 8 lies in
+ *   [0, num_agents), its sel8 byte is a rank c < 0x7F without the carried bit (bit 7) that names one of its out-edges, and
+ *   that edge's target out_dst[out_ptr[i] + c] equals (int) DESTINATION of agent h in agent_features (fp32
+ *   [B][num_agents][9], environment b at agent_features + b * a_bstride). A holding row gets sel8 = the raw code 0x7F and
+ *   tarl_fused.sel = (float) i, tarl_fused_select_next_hop_hold's encoding: the core moves nobody from it and the insert puts
+ *   a departing agent of that origin onto the origin road. Every other row keeps exactly what the policy wrote.
+ *   ONE difference from the routers' rule: an EMPTY row is never touched — no dummy agent 0, no decode of a DIRTY row's slot
+ *   store. The policy's action on an empty row is what the insert reads, and it stays the policy's.
+ *   Not handled (as there): a self-loop. Not done, on purpose: a row adjacent to the destination that chose another road is
+ *   not held, and an agent the insert places directly onto its destination road is not saved.
+ *   choice8 (optional) uint8 [B][N]: the rows' sel8 bytes after the call, env-major, as the select kernels give them.
+ *   held (optional) int32 [B]: += the rows held by this call (integer atomics).
+ *   Host checks: tarl_fused_select_next_hop_dest's on plan, handle, B and Nmax; a null agent table, num_agents outside
+ *   [1, 2^24] or (B > 1) a_bstride < 9 num_agents are refused, all before any HIP call.
+ * tarl_fused_set_policy_hold: the switch for the T-frame rollouts of the state-dependent heads (tarl_fused_rollout_policy,
+ *   tarl_fused_rollout_prior[_dest], tarl_fused_rollout_gt). With on = 1 their shared loop queues the launch above in every
+ *   frame between the draw (tarl_graphdist_rollout) and the Direction launch, WITHOUT choice8 — the rollout's action buffer
+ *   keeps the policy's draw, which the update needs — and with `held` (int32 [B], optional, caller-owned and caller-zeroed).
+ *   With on = 0 (held must then be NULL) the loop queues exactly the launches it queued before the switch existed. Sets
+ *   tarl_fused.policy_hold / policy_held; a null handle, on outside {0, 1} or a counter without the switch are refused. */
+int tarl_fused_hold_policy_actions(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax,
+                                   const float* agent_features, int64_t num_agents, int64_t a_bstride, uint8_t* choice8,
+                                   int32_t* held, tarl_stream stream);
+int tarl_fused_set_policy_hold(tarl_fused* f, int on, int32_t* held);
 
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the

@@ -169,7 +169,8 @@ extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, in
 
 // ---- T frames with a STATE-DEPENDENT policy head in one foreign call (rollout_heads.h) ----------------------------------------
 // Nothing of GraphDistribution can be hoisted: per frame the head's logits from the packed state (`frame`) -> action +
-// log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> Direction -> rows -> insert, queued back to back by one host loop
+// log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> [with tarl_fused_set_policy_hold: the hold rule on SELECTED_ROAD,
+// policy_hold.hip; the action buffer keeps the draw] -> Direction -> rows -> insert, queued back to back by one host loop
 // in C (the same entry points a caller could queue himself, minus a foreign-call round trip per launch and the checks per
 // frame). The arguments are checked and the pointer table is uploaded once per call; the count bytes are the frame
 // kernels' own (FrameOut::counts8), the event byte is stored in the last frame only and the insert is packed
@@ -209,6 +210,10 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
                                    a.choice8 ? a.choice8 + t * NB : nullptr, f->sel8, a.log_prob ? a.log_prob + t * B : nullptr,
                                    f->env_base, a.stream);
     if (rc) return rc;
+    if (f->policy_hold) {   // tarl_fused_set_policy_hold: the hold rule on f->sel8; a.choice8 keeps the draw (policy_hold.hip)
+      rc = tarl_launch_policy_hold(s, plan, f, B, a.agent_features, a.A, a.a_bstride, nullptr, f->policy_held);
+      if (rc) return rc;
+    }
     const float time = a.times_host[t];
     const FrameOut out = rollout_frame_out(t, T, N, B, a.counts, a.metrics_envs, a.dtt_node, a.events, a.leg);
     rc = tarl_launch_direction(grid_d, threads, s, plan, f, a.edge_attr, a.log_edge_attr, (const uint8_t*)f->sel8, nullptr,

@@ -1,7 +1,9 @@
 // fused_select.h — what the SELECTED_ROAD writers on the PACKED state share: k_fused_select_next_hop_dest (baseline.hip, the
 // next hop from a per-destination table) and k_fused_select_route (routes.hip, the next hop from a per-agent route). Both
 // run one thread per (row i, environment b), flat index gid = i * B + b with the environment fastest, decode the row's head
-// agent the same way and turn the value they select into the same rank byte.
+// agent the same way and turn the value they select into the same rank byte. k_fused_hold_policy_actions (policy_hold.hip),
+// the hold rule as a post-pass over a policy's bytes, has the same launch shape and block size but reads no head through
+// fs_head_agent: it never touches an empty row.
 #pragma once
 #include "fused_common.h"
 

@@ -99,6 +99,19 @@ OPTIONS = (
                                   "on their destination roads; dijkstra_hold: a row whose next hop is its head's destination "
                                   "holds, so the agent is withdrawn one road short and the router delivers; free_flow: "
                                   "dijkstra_hold on tables built once from the empty network")),
+    ("--policy-hold", dict(action="store_true",
+                           help="mpnn / mpnn+ppo: apply the hold rule of dijkstra_hold to the POLICY's action (an action shield of "
+                                "the environment, DESIGN 4.20; not in the reference, off by default): a road with a vehicle at its "
+                                "head whose chosen next road is that vehicle's destination selects itself instead, so the "
+                                "environment's step order (choice, core, withdraw) collects the vehicle one road short instead "
+                                "of stranding it on its destination road. One difference from the routers' rule: an empty road "
+                                "is never touched. It does not hold a road next to the destination that chose another road, "
+                                "and does not save a vehicle inserted directly onto its destination road. The policy's draw, "
+                                "log-prob and the PPO update are unchanged. eval: needs --eval-envs and acts on the policy's "
+                                "vectorised evaluation only (one more line in its block, `policy_hold` and `held` in "
+                                "eval_envs.json); train: acts on vectorised training and its eval_vec runs (train/held and "
+                                "eval_vec/held in train_log.jsonl), refused with --policy-head embedding, whose rollout "
+                                "kernels draw every frame's action ahead of the frames")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "

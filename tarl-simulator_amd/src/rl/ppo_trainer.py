@@ -98,15 +98,17 @@ def _eval_engine(eval_env, eval_envs, seed, agent_features=None):
                      device=g.x.device, timestep=sim.timestep, seed=seed + 104729, fused=True)
 
 
-def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature):
-    """The K-environment evaluator of ``ppo_train(eval_envs=K)``."""
+def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_hold=False):
+    """The K-environment evaluator of ``ppo_train(eval_envs=K)``; ``policy_hold``: with the hold rule on the policy's action
+    (DESIGN 4.20)."""
     from tarl_hip.evaluator import VecEvaluator
     engine = _eval_engine(eval_env, eval_envs, seed)
     dests = None
     if getattr(policy_net, "policy_head", "embedding") == "embedding_dijkstra" and \
             policy_net.resolve_prior_method() != "all_pairs":
         dests = destination_set(engine.agents, engine.N)
-    return VecEvaluator.from_policy_net(engine, policy_net, prior_dests=dests, temperature=temperature)
+    kw = {"policy_hold": True} if policy_hold else {}
+    return VecEvaluator.from_policy_net(engine, policy_net, prior_dests=dests, temperature=temperature, **kw)
 
 
 def vec_eval_record(prefix, res):
@@ -125,7 +127,7 @@ def vec_eval_record(prefix, res):
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
-              eval_baseline="none"):
+              eval_baseline="none", policy_hold=False):
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
     from tarl_hip.trainer import VecPPOTrainer
@@ -171,7 +173,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             policy_precision={"edge_mlp_bf16": "bf16", "edge_mlp_fp32": "fp32"}.get(head, "x3"),
                             prior_weight=getattr(policy_net, "prior_weight", 1.0), **prior_kw,
                             gt_params=policy_net.transformer.kernel_tensors() if head == "graph_transformer" else None,
-                            gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw)
+                            gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw,
+                            **({"policy_hold": True} if policy_hold else {}))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)
@@ -185,7 +188,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     if int(eval_envs) < 0:
         raise ValueError("eval_envs must be >= 0")
     # rank 0 alone evaluates (as it alone logs); the evaluator enters no collective
-    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature)
+    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature, policy_hold)
                 if eval_envs and eval_env is not None and log is not None else None)
     ppo_train.last_vec_eval = vec_eval
     if eval_baseline not in EVAL_BASELINE_NAMES:
@@ -217,6 +220,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                    "grad_global_norm": float(trainer.last_grad.norm()) if trainer.last_grad is not None else float("nan"),
                    "transport/avg_vc_ratio": float(vc.mean()), "transport/std_vc_ratio": float(vc.std(unbiased=False)),
                    "iter_seconds": time.perf_counter() - t0}
+            if policy_hold:               # rows the hold rule rewrote in this iteration's frames, per environment
+                rec["train/held"] = float(trainer.held.sum()) / engine.B
             if bool(done.any()):
                 rec["transport/avg_travel_time"] = float((ag0[done, 3] - ag0[done, 2]).mean())
         # periodic evaluation (src/rl/ppo_trainer.py:147-151): MODE rollout, optionally a sampled one, on eval_env
@@ -234,6 +239,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                 for prefix, det in (("eval_vec", True),) + ((("eval_vec_stochastic", False),) if stochastic_eval else ()):
                     res = vec_eval.run(n_eval, deterministic=det)
                     rec.update(vec_eval_record(prefix, res))
+                    if policy_hold and res.held is not None:
+                        rec[f"{prefix}/held"] = float(res.held.mean())
                     ppo_train.last_eval[prefix] = res
                 if eval_baseline != "none":
                     from tarl_hip.evaluator import EVAL_BASELINES, VecEvaluator, paired_report, paired_scalars

@@ -37,6 +37,8 @@ class RunnerArgs:
     eval_sampled: bool = False     # ... and also a sampled one next to the deterministic (MODE) one
     eval_baseline: str = "none"    # eval_envs: "dijkstra" adds the shortest-path baseline on a second engine + the paired report;
     #                                "dijkstra_hold": the router that holds one road short and delivers; "free_flow": that one on static tables
+    policy_hold: bool = False      # mpnn / mpnn+ppo: the hold rule on the policy's action in the vectorised
+    #                                evaluation (eval: needs eval_envs) and in vectorised training (not policy_head "embedding")
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
@@ -70,6 +72,17 @@ class RunnerArgs:
         if self.eval_baseline != "none" and not (self.eval_envs and self.algo in ("mpnn", "mpnn+ppo")):
             raise ValueError("eval_baseline compares the vectorised evaluation of a policy network with the shortest-path "
                              "router: it needs eval_envs > 0 and algo mpnn or mpnn+ppo")
+        if self.policy_hold:
+            if self.algo not in ("mpnn", "mpnn+ppo"):
+                raise ValueError("policy_hold applies the hold rule to a policy network's action: it needs algo mpnn or "
+                                 "mpnn+ppo (the dijkstra routers have their own: dijkstra_router / eval_baseline)")
+            if self.mode == "eval" and not self.eval_envs:
+                raise ValueError("policy_hold acts in the vectorised evaluation: in mode 'eval' it needs eval_envs > 0 (the "
+                                 "single-environment, reference-shaped pass is not changed)")
+            if self.mode == "train" and self.policy_head == "embedding":
+                raise ValueError("policy_hold cannot train policy_head 'embedding': its rollout kernels draw the actions of "
+                                 "all frames ahead of the frames, so the rule has no frame state to read; use a "
+                                 "state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer)")
         if self.dijkstra_envs is None or int(self.dijkstra_envs) < 0:
             raise ValueError(f"dijkstra_envs must be >= 0, got {self.dijkstra_envs!r}")
         if self.dijkstra_envs and not (self.algo == "dijkstra" and self.mode == "eval"):
@@ -310,7 +323,7 @@ class Runner:
                   checkpoint_path=(out / "policy.pt") if self.rank == 0 else None,
                   log_dir=str(out) if self.rank == 0 else None, eval_env=eval_env, eval_interval=1,
                   num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled,
-                  eval_baseline=a.eval_baseline)
+                  eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}))
 
     def eval(self):
         a = self.args
@@ -542,14 +555,15 @@ class Runner:
         columns in the CSV. -> {"mode": EvalResult, "sampled": EvalResult or None[, "baseline": EvalResult, "paired": dict]}."""
         import csv
         import json
-        from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator
+        from tarl_hip.evaluator import PER_ENV_KEYS, VecEvaluator, aggregate
         from .agents.base import destination_set
         a, sim = self.args, self.env.simulator
         engine = self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs)
         dests = None
         if a.policy_head == "embedding_dijkstra" and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
-        ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw())
+        ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw(),
+                                          **({"policy_hold": True} if a.policy_hold else {}))
         results = {"mode": ev.run(frames, deterministic=True), "sampled": None}
         pair = None
         if a.eval_trips and a.eval_baseline != "none" and not results["mode"].domain_exit:
@@ -564,6 +578,15 @@ class Runner:
                 continue
             self._print_block(f"Vectorised evaluation ({res.envs} environments, {label})", res)
             doc[key] = res.to_dict()
+            if a.policy_hold:           # only the policy's engine: the baseline and the replanning loop keep their own rule
+                doc[key]["policy_hold"] = True
+                if res.held is not None:
+                    g = aggregate([int(v) for v in res.held])
+                    doc[key]["held"] = [int(v) for v in res.held]
+                    print(f"{'policy hold:':22} ran with the hold rule on the policy's action (DESIGN 4.20); rows held per "
+                          f"environment {g['mean']:.1f}" + (f" \u00b1 {g['se']:.1f} (se)" if g.get("se") is not None else ""))
+                else:
+                    print(f"{'policy hold:':22} ran with the hold rule on the policy's action (DESIGN 4.20)")
             rows += [dict(kind=key, **r) for r in res.rows()]
         fields = ("kind", "env") + PER_ENV_KEYS
         if a.eval_baseline != "none":

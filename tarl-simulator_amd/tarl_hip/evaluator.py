@@ -150,6 +150,8 @@ class EvalResult:
     turn_lost: np.ndarray | None = field(default=None, compare=False)       # (K, H, N) int32: phantom pops per road
     turn_stats: dict | None = field(default=None, compare=False)            # link_moments of "turns" and of "lost"
     turn_meta: dict | None = field(default=None, compare=False)             # first_bin, bin_seconds, edge_index, policy_prob
+    # policy_hold=True (never after a domain exit): rows the hold rule rewrote, summed over the frames, DESIGN 4.20
+    held: np.ndarray | None = field(default=None, compare=False)            # (K,) int64
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -292,7 +294,7 @@ class VecEvaluator:
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
-                 dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True):
+                 dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True, policy_hold=False):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -336,7 +338,15 @@ class VecEvaluator:
         has the same block), the SELECTED_ROAD bytes are copied into the third after every frame, and one
         ``ops.turn_counts_accumulate`` launch follows every block. ``run()`` sizes the (K, H, E) and (K, H, N) tables and
         refuses what exceeds half the free device memory; it raises when a pop could not be attributed to an edge or when
-        the lost agents do not add up to the ON_WAY agents that are queued nowhere."""
+        the lost agents do not add up to the ON_WAY agents that are queued nowhere.
+        ``policy_hold`` (an action shield, NOT in the reference; policy heads only — the routers and the plan have
+        their own rule): after the head has written a frame's action, a row with a non-empty FIFO whose chosen road IS its
+        head agent's destination selects itself instead (``ops.fused_hold_policy_actions``), so that the environment's step
+        order withdraws the agent there instead of stranding it on its destination road. ``actions`` stays the policy's own
+        choice; ``EvalResult.held`` counts the held rows per environment. Unlike the routers' rule an empty row is never
+        touched. The ``"embedding"`` head then takes the per-frame path of the state-dependent heads: its logits are computed
+        once and broadcast, the action is drawn per frame (``ops.graphdist_mode_rollout`` / ``ops.graphdist_rollout``), then
+        the hold launch and ``frame_fused(skip_choice=True)``. Off, every head runs as it always did."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -354,6 +364,9 @@ class VecEvaluator:
             raise ValueError(f"routes is the plan of the heads {PLAN_HEADS}: head {head!r} does not read it")
         if head not in ROUTER_HEADS + PLAN_HEADS and emb is None:
             raise ValueError(f"head {head!r} needs emb (the flat embedding tensor)")
+        if policy_hold and head in ROUTER_HEADS + PLAN_HEADS:
+            raise ValueError(f"policy_hold is the hold rule for POLICY heads: head {head!r} has its own rule "
+                             "('dijkstra_hold' and 'routes' hold one road short of the destination themselves)")
         if int(poll_frames) < 1:
             raise ValueError("poll_frames must be >= 1")
         if int(refresh_rate) < (0 if head == "dijkstra_hold" else 1):
@@ -365,6 +378,7 @@ class VecEvaluator:
         self.prior_weight, self.gt_pe, self.gt_weights = float(prior_weight), gt_pe, gt_weights
         self.bin_width, self.num_bins, self.poll_frames = float(bin_width), int(num_bins), int(poll_frames)
         self.keep_actions = bool(keep_actions)
+        self.policy_hold = bool(policy_hold)
         self.refresh_rate = int(refresh_rate)
         K, N, E, dev = engine.B, engine.N, engine.E, engine.device
         plan = engine.plan
@@ -430,9 +444,15 @@ class VecEvaluator:
                         "episode_return": torch.zeros(K, dtype=torch.float64, device=dev),
                         "hist": torch.zeros((K, self.num_bins), dtype=torch.int32, device=dev)}
         self.reward = self.actions = self._flag_host = None
+        if self.policy_hold:
+            self.held = torch.zeros(K, dtype=torch.int32, device=dev)       # rows held, per environment, in this run
         if head == "embedding":
             self.mode8 = torch.zeros((1, N), dtype=torch.uint8, device=dev)
             self.mode_lp = torch.zeros(1, dtype=torch.float32, device=dev)
+            if self.policy_hold:        # the per-frame path: the logits of every environment, and the sampler's scratch
+                self.logits = torch.empty((K, E), dtype=torch.float32, device=dev)
+                need = int(_lib.load().tarl_graphdist_rollout_scratch_bytes(plan.handle, K))
+                self.dist_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
         elif head in ROUTER_HEADS:
             self._init_baseline(baseline_dests)
         elif head in PLAN_HEADS:
@@ -564,9 +584,15 @@ class VecEvaluator:
         """Once per run, after the reset. The embedding head is state-independent: its MODE action is computed once (B = 1)
         and loaded into every environment's SELECTED_ROAD bytes, which the frames leave alone; sampled, the engine draws
         from its own tables."""
+        if self.policy_hold:
+            self.held.zero_()
         if self.head != "embedding":
             return      # (the baseline builds its tables at frame 0: 0 % refresh_rate == 0)
         eng = self.eng
+        if self.policy_hold:            # drawn per frame, so that the hold rule sees every frame's state: logits once, broadcast
+            logits = ops.policy_edge_logits(eng.plan, eng.static_node_features[0], self.emb).view(1, -1)
+            self.logits.copy_(logits.expand_as(self.logits))
+            return
         if deterministic:
             logits = ops.policy_edge_logits(eng.plan, eng.static_node_features[0], self.emb).view(1, -1)
             ops.graphdist_mode_rollout(eng.plan, logits, self.temperature, choice8=self.mode8, log_prob=self.mode_lp)
@@ -620,11 +646,11 @@ class VecEvaluator:
                 ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table[0], hold=True)
             ops.fused_select_route(eng.plan, eng.fs, self.routes, self.route_len, choice8=rec)
             return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
-        if self.head == "embedding":
+        if self.head == "embedding" and not self.policy_hold:
             if rec is not None and deterministic:
                 rec.copy_(self.action8)
             return eng.frame_fused(skip_choice=deterministic, reward=self.reward[t], **masks)
-        logits = self._logits()
+        logits = self.logits if self.head == "embedding" else self._logits()
         if deterministic:
             ops.graphdist_mode_rollout(eng.plan, logits, self.temperature, choice8=rec, sel8=eng.fs.sel8,
                                        log_prob=self.log_prob)
@@ -632,6 +658,8 @@ class VecEvaluator:
             ops.graphdist_rollout(eng.plan, logits, self.temperature, seed=eng.seed ^ 0x5DEECE66D,
                                   counter=eng.sample_counter + 1, choice8=rec, sel8=eng.fs.sel8, log_prob=self.log_prob,
                                   scratch=self.dist_scratch)
+        if self.policy_hold:            # rec keeps the policy's own choice: the rule rewrites the packed state's bytes alone
+            ops.fused_hold_policy_actions(eng.plan, eng.fs, eng.agents, held=self.held)
         return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
 
     # -- the evaluation ----------------------------------------------------------------------------------------------------
@@ -726,6 +754,8 @@ class VecEvaluator:
             settings.update(max_hops=int(self.routes.size(-1)), routes_per_env=self.routes.dim() == 3, hold=True,
                             route_fallback=self.route_fallback,
                             agents_without_route=int((self.route_len[..., 1:] <= 0).sum()))
+        if self.policy_hold:                  # (without the flag the settings stay as they were)
+            settings["policy_hold"] = True
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):
@@ -747,6 +777,8 @@ class VecEvaluator:
                                                                  host["hist"], done, self.bin_width)
         for k, v in per.items():
             setattr(res, k, v)
+        if self.policy_hold:
+            res.held = self.held.cpu().numpy().astype(np.int64)
         if self.link_counts:
             st = ops.link_count_stats(self.link_acc)
             res.link_counts = self.link_acc.cpu().numpy()

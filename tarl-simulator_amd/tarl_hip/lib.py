@@ -151,6 +151,8 @@ SIGNATURES = {
     "tarl_td_routes_scratch_bytes": (_i64, [_p, _i64, _i64, _i64]),
     "tarl_td_routes": (C.c_int, [_p, _p, _p, _p] + [_i64] * 7 + [_p, _i64, _p, _p, _p, _p]),
     "tarl_fused_select_route": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _i64, _i64, _p, _p]),
+    "tarl_fused_hold_policy_actions": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i64, _p, _p, _p]),
+    "tarl_fused_set_policy_hold": (C.c_int, [_p, C.c_int, _p]),
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),
@@ -166,7 +168,7 @@ class FusedStruct(C.Structure):
                                            "a_dep", "a_status", "a_order", "cur_lo", "a_dep_sorted", "a_win", "a_ins",
                                            "a_rank")] +
                 [("acc_slots", C.c_int64), ("flags", C.c_void_p), ("env_base", C.c_int64), ("due_rate", C.c_float),
-                 ("reserved_", C.c_int32), ("bufs_dev", C.c_void_p)])
+                 ("policy_hold", C.c_int32), ("bufs_dev", C.c_void_p), ("policy_held", C.c_void_p)])
 
 
 FLAG_COUNT_AT_NMAX, FLAG_AMBIGUOUS_EDGES, FLAG_PACK_RANGE, FLAG_CHOICE_OVERFLOW = 1, 2, 4, 8

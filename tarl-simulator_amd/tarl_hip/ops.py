@@ -1186,6 +1186,44 @@ def fused_select_route(plan: Plan, fs, routes, route_len, choice8=None):
     return choice8
 
 
+def fused_hold_policy_actions(plan: Plan, fs, agent_features, choice8=None, held=None):
+    """The hold rule of DESIGN 4.13a as a post-pass over the SELECTED_ROAD bytes a POLICY head has just written into ``fs``
+    (tarl_fused_hold_policy_actions; an action shield, not the reference's rule): a row with a non-empty FIFO
+    whose chosen out-edge leads to the DESTINATION of its head agent (``agent_features`` (B, A, 9), integers compared)
+    selects ITSELF instead — the raw code with its own id — so that the environment's step order withdraws the agent there
+    instead of stranding it on its destination road. Every other row keeps what the policy wrote; unlike the routers' rule
+    an EMPTY row is never touched. ``choice8`` (B, N) uint8 (optional): the rows' bytes after the call, env-major.
+    ``held`` (B,) int32 (optional): += the rows held by this call."""
+    N = plan.num_nodes
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    A, abs_ = _agents(agent_features, fs.B)
+    if choice8 is not None:
+        _contig(choice8, torch.uint8, "choice8")
+        if tuple(choice8.shape) != (fs.B, N):
+            raise ValueError(f"choice8 must be (B, N) = ({fs.B}, {N})")
+    if held is not None:
+        _contig(held, torch.int32, "held")
+        if tuple(held.shape) != (fs.B,):
+            raise ValueError(f"held must be (B,) = ({fs.B},)")
+    _lib.check(_lib.load().tarl_fused_hold_policy_actions(plan.handle, fs.ref, fs.B, fs.Nmax, agent_features.data_ptr(), A,
+                                                          abs_, _lib.ptr(choice8), _lib.ptr(held), _lib.current_stream()))
+    return choice8
+
+
+def fused_set_policy_hold(fs, on, held=None):
+    """The switch of the state-dependent T-frame rollouts (:func:`fused_rollout_policy`, :func:`fused_rollout_prior`,
+    :func:`fused_rollout_gt`; tarl_fused_set_policy_hold): with ``on`` their loop queues :func:`fused_hold_policy_actions`
+    in every frame between the draw and the Direction launch. The rollout's ``choice8`` keeps the policy's draw. ``held``
+    (B,) int32 (optional, kept alive on ``fs``): += the rows held, per environment. Off (the default) the loop queues
+    exactly the launches it always queued."""
+    if held is not None:
+        _contig(held, torch.int32, "held")
+        if tuple(held.shape) != (fs.B,):
+            raise ValueError(f"held must be (B,) = ({fs.B},)")
+    _lib.check(_lib.load().tarl_fused_set_policy_hold(fs.ref, 1 if on else 0, _lib.ptr(held)))
+    fs.policy_held = held
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")

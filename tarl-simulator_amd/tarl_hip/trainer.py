@@ -70,7 +70,7 @@ class VecPPOTrainer:
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
-                 prior_free_flow=None, prior_dests=None):
+                 prior_free_flow=None, prior_dests=None, policy_hold=False):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -81,7 +81,11 @@ class VecPPOTrainer:
         ``critic_params`` = every parameter of its GraphTransformerNet, ``gt_value_params`` maps the state-dict keys of
         ops.GT_VALUE_PARAM_KEYS + GT_VALUE_BUFFER_KEYS to its tensors, ``gt_value_pe`` (N, 16) is its positional encoding.
         It needs a state-dependent policy head (the rollout builds the observation of every frame) and keeps all (T + 1) * B
-        observations (``obs_all``, fp32 (T+1, B, N, 16)) for GAE's all-frames critic pass."""
+        observations (``obs_all``, fp32 (T+1, B, N, 16)) for GAE's all-frames critic pass.
+        ``policy_hold`` (an action shield of the ENVIRONMENT, not in the reference): in every collected frame a
+        row with a non-empty FIFO whose drawn road is its head agent's destination selects itself instead, between the draw
+        and the frame (ops.fused_set_policy_hold). ``collect()`` stores the draw's bytes and log-prob, so the update is
+        unchanged; ``held`` (B,) int32 counts the held rows of the last ``collect()``. State-dependent heads only."""
         self.eng = engine
         # policy: "embedding" = the reference's live head (logit = embedding of the target road: state-independent, its
         # distribution is tabulated once per update); "edge_mlp" = the per-edge MLP head it carries as parameters
@@ -151,6 +155,13 @@ class VecPPOTrainer:
             raise ValueError("value must be 'simple' or 'graph_transformer'")
         # the state-dependent heads evaluate their logits in front of every frame and draw the minibatch frames up front
         self.state_dep = policy != "embedding"
+        self.policy_hold = bool(policy_hold)
+        if self.policy_hold and not self.state_dep:
+            raise ValueError("policy_hold is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
+                             "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
+                             "between a frame's draw and its Direction launch where the rule could read that frame's state; "
+                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer)")
+        self.held = torch.zeros(engine.B, dtype=torch.int32, device=engine.device) if self.policy_hold else None
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
@@ -315,6 +326,9 @@ class VecPPOTrainer:
         if eng.fs is not None:
             # fused path: every output lands directly in the rollout buffers (no copies), one foreign call per segment
             self.counts[0].zero_()
+            if self.policy_hold:        # the shared loop of the state-dependent rollouts consults the switch per frame
+                self.held.zero_()
+                ops.fused_set_policy_hold(eng.fs, True, self.held)
             if self.state_dep:
                 self._draw_minibatch_frames()
             else:
@@ -327,6 +341,8 @@ class VecPPOTrainer:
             for sl in self._segments(done):
                 host_times += self._queue(sl)[:-1]
             host_times.append(float(eng.time))
+            if self.policy_hold:        # off again: whoever else runs this engine gets the loop as it always was
+                ops.fused_set_policy_hold(eng.fs, False)
             if self.obs_all is not None:      # frame T: the final state (an episode end at T - 1 is not followed by a reset)
                 eng.obs16(out=self.obs_all[T])
             # the device status word travels to pinned host memory behind the rollout; it is looked at when it has
