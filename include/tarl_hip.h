@@ -1116,6 +1116,41 @@ int tarl_fused_hold_policy_actions(const tarl_plan* plan, const tarl_fused* f, i
                                    int32_t* held, tarl_stream stream);
 int tarl_fused_set_policy_hold(tarl_fused* f, int on, int32_t* held);
 
+/* ---- behaviour cloning of the shortest-path router ----------------------------------------------------------------
+ * NOT in the reference: a warm start for the learned heads. TARL_ABI_VERSION is unchanged: nothing existing moved.
+ * tarl_fused_expert_labels: the expert's action of every row in the POLICY's action space, WITHOUT touching the packed state
+ *   (sel8, sel and every other word stay as they are: a rollout driven by the policy can be labelled). For row i of
+ *   environment b, labels[b][i] (uint8 [B][N], env-major) = the rank byte tarl_fused_select_next_hop_dest (hold off) would
+ *   write for that row — same head decode, table lookup and rank search, out-lists longer than four included — and
+ *   TARL_BC_IGNORE where the row is empty (count bits of hdp = 0; tested first, before any gather), where the head,
+ *   destination or table slot is out of range (the select kernel leaves such a row untouched) and where the next hop matches
+ *   no out-edge of i (the select kernel writes the raw code: the destination row itself, -1, a foreign entry).
+ *   Taken before the hold: the destination road is named as a rank, and tarl_fused_hold_policy_actions turns exactly that
+ *   pick into the hold. n_labelled (optional) int32 [B]: += the labelled rows of each environment (integer atomics, one
+ *   instruction per wave). Arguments and host checks: tarl_fused_select_next_hop_dest's, and a null `labels` is refused.
+ * tarl_graphdist_bc: cross-entropy of GraphDistribution(logits / temperature) on labelled nodes, forward and backward.
+ *   logits fp32 [M][E] in original edge order; labels uint8 [M][N]. Node n of sample m is LABELLED when labels[m][n] <
+ *   min(out-degree(n), 0x7F); every other byte is ignored. For a labelled node with out-edges e_0 .. e_{d-1} in the plan's
+ *   CSR order, in fp32: z_j = logits[e_j] / temperature, mx = max z_j, s = sum_j exp(z_j - mx) left to right,
+ *   loss = log s + mx - z_label. nll[m] (fp64) = the sum of the losses of sample m: per tile of 256 nodes a fixed tree
+ *   (lanes l and l + 32, 16, .., 1 of each 64-node wave, then the tile's four waves in order), then the tiles in order.
+ *   n_labelled[m], n_hit[m] (int32, overwritten): the labelled nodes, and those whose first maximum of z in CSR order is the
+ *   label (tarl_graphdist_mode's tie rule). grad_logits (optional) fp32 [M][E], overwritten in full:
+ *   (grad_scale * (exp(z_j - mx) / s - [j == label])) / temperature on the out-edges of a labelled node, 0 elsewhere.
+ *   Deterministic (no floating-point atomics): two runs are bit-identical. scratch: tarl_graphdist_bc_scratch_bytes(plan, M)
+ *   bytes, 8-byte aligned (16 per (sample, tile)); -1 for a null plan, M < 1 or 2^24 or more (sample, tile) pairs (the
+ *   launch is one block of 256 threads per pair: below 2^32 threads), which tarl_graphdist_bc refuses too.
+ *   Refused on the host, before any HIP call: a null argument (grad_logits alone may be null), M < 1, temperature <= 0, a
+ *   misaligned scratch. A refused call leaves the outputs untouched. */
+#define TARL_BC_IGNORE 0xFFu
+int tarl_fused_expert_labels(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                             const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride, int64_t num_dests,
+                             uint8_t* labels, int32_t* n_labelled, tarl_stream stream);
+int64_t tarl_graphdist_bc_scratch_bytes(const tarl_plan* plan, int64_t M);
+int tarl_graphdist_bc(const tarl_plan* plan, const float* logits, int64_t M, float temperature, const uint8_t* labels,
+                      float grad_scale, double* nll, int32_t* n_labelled, int32_t* n_hit, float* grad_logits, void* scratch,
+                      tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

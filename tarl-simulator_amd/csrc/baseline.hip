@@ -71,22 +71,13 @@ __global__ __launch_bounds__(FS_BLOCK) void k_fused_select_next_hop_dest(
   if (gid >= NB) return;
   const uint32_t i = gid / B, b = gid - i * B;
   const long long head = fs_head_agent(hdp[gid].x, gid, tl, gc8, slots, lds, Nmax);
-  bool write = false;
   uint32_t code = SEL_RAW;
-  if (head >= 0 && head < A) {
-    const int32_t dest = a_dest[(int64_t)b * A + head];
-    if (dest >= 0 && dest < N) {
-      const int32_t slot = dest_slot[dest];
-      if (slot >= 0 && slot < D) {
-        int32_t nh = next_hop[(int64_t)b * nh_bstride + (int64_t)slot * N + i];
-        if (HOLD && nh == dest) nh = (int32_t)i;
-        const float sv = (float)nh;
-        code = fs_rank_code(nodes[i], out_pad, sv);
-        if (code == SEL_RAW) sel[gid] = sv;
-        sel8[gid] = (uint8_t)code;
-        write = true;
-      }
-    }
+  float sv = 0.0f;
+  const bool write = fs_next_hop_code<HOLD>(head, i, b, nodes, out_pad, a_dest, A, N, dest_slot, next_hop, nh_bstride, D,
+                                            &code, &sv);
+  if (write) {
+    if (code == SEL_RAW) sel[gid] = sv;
+    sel8[gid] = (uint8_t)code;
   }
   // env-major copy of the row's byte as it stands now (the evaluator's action record: a test hook, one scattered byte)
   if (choice8) choice8[(int64_t)b * N + i] = write ? (uint8_t)code : sel8[gid];

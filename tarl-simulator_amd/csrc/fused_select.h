@@ -44,3 +44,25 @@ __device__ __forceinline__ uint32_t fs_rank_code(const NodeRec& nr, const int32_
   }
   return code;
 }
+
+// The next-hop lookup of k_fused_select_next_hop_dest for head agent `head` of row i in environment b, shared with
+// k_fused_expert_labels (bc.hip), which wants the byte and no store. false: a head, destination or table slot out of range —
+// the select kernel leaves such a row untouched. true: *sv = the value it writes ((float) next hop; with HOLD the row's own
+// id where the next hop is the destination, compared on the integers) and *code = that value's rank byte (fs_rank_code).
+template <bool HOLD>
+__device__ __forceinline__ bool fs_next_hop_code(long long head, uint32_t i, uint32_t b, const NodeRec* __restrict__ nodes,
+                                                 const int32_t* __restrict__ out_pad, const int32_t* __restrict__ a_dest,
+                                                 int64_t A, int64_t N, const int32_t* __restrict__ dest_slot,
+                                                 const int32_t* __restrict__ next_hop, int64_t nh_bstride, int64_t D,
+                                                 uint32_t* code, float* sv) {
+  if (head < 0 || head >= A) return false;
+  const int32_t dest = a_dest[(int64_t)b * A + head];
+  if (dest < 0 || dest >= N) return false;
+  const int32_t slot = dest_slot[dest];
+  if (slot < 0 || slot >= D) return false;
+  int32_t nh = next_hop[(int64_t)b * nh_bstride + (int64_t)slot * N + i];
+  if (HOLD && nh == dest) nh = (int32_t)i;
+  *sv = (float)nh;
+  *code = fs_rank_code(nodes[i], out_pad, *sv);
+  return true;
+}

@@ -175,6 +175,28 @@ OPTIONS = (
                                "difference; eval_turns_lost.csv; `turns` in the JSON file")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
+    ("--pretrain-bc", dict(type=int, default=0, metavar="I",
+                           help="train, mpnn / mpnn+ppo: I > 0 behaviour-cloning iterations before the first PPO iteration "
+                                "(DESIGN 4.21, not in the reference): the shortest-path router labels every occupied road of a "
+                                "rollout on --bc-envs environments with its pick among the road's out-edges, and the policy head "
+                                "is trained on the cross-entropy of those labels; one printed line and one line of bc_log.jsonl "
+                                "per iteration, then the usual policy.pt; with mpnn+ppo training continues from the cloned "
+                                "weights, with mpnn no PPO iteration follows. Evaluate with --policy-hold")),
+    ("--bc-expert", dict(choices=("dijkstra", "free_flow"), default=None,
+                         help="--pretrain-bc: the router imitated; dijkstra (default): every environment's own congested "
+                              "times, tables rebuilt every 10 frames; free_flow: tables built once at frame 0")),
+    ("--bc-driver", dict(choices=("expert", "policy", "dagger"), default=None,
+                         help="--pretrain-bc: who drives the labelled rollout; expert: the holding router itself; policy: the "
+                              "head's sampled action under the hold rule; dagger (default): iteration 0 as expert, every later "
+                              "one as policy")),
+    ("--bc-envs", dict(type=int, default=None, metavar="K", help="--pretrain-bc: environments of its engine (default 16)")),
+    ("--bc-frames", dict(type=int, default=None, metavar="T",
+                         help="--pretrain-bc: frames per iteration (default: --rollout-steps)")),
+    ("--bc-samples", dict(type=int, default=None, metavar="S",
+                          help="--pretrain-bc: (environment, frame) pairs kept per iteration (default 256)")),
+    ("--bc-epochs", dict(type=int, default=None, help="--pretrain-bc: passes over the kept pairs (default 4)")),
+    ("--bc-batch", dict(type=int, default=None, help="--pretrain-bc: minibatch (default: the PPO sub-batch)")),
+    ("--bc-lr", dict(type=float, default=None, help="--pretrain-bc: Adam step size (default: the PPO trainer's)")),
     ("--checkpoint", dict(type=str, default=None,
                           help="mpnn / mpnn+ppo: load a policy.pt written by --mode train into the policy network; a file "
                                "whose keys or shapes do not match the network is refused")),

@@ -111,6 +111,26 @@ def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_ho
     return VecEvaluator.from_policy_net(engine, policy_net, prior_dests=dests, temperature=temperature, **kw)
 
 
+def _pretrain_bc(env, trainer, cfg, seed, log_dir):
+    """The behaviour-cloning iterations in front of PPO: one printed line and one line of ``bc_log.jsonl`` each."""
+    from tarl_hip.imitation import BCTrainer
+    engine = _eval_engine(env, cfg["envs"], seed + 1)
+    bc = BCTrainer(trainer, engine, expert=cfg["expert"], driver=cfg["driver"], frames=cfg["frames"], samples=cfg["samples"],
+                   epochs=cfg["epochs"], batch=cfg["batch"] or trainer.M, lr=cfg["lr"] or trainer.lr, seed=seed)
+    log = open(os.path.join(log_dir, "bc_log.jsonl"), "a") if log_dir is not None else None
+    for _ in range(int(cfg["iterations"])):
+        rec = bc.iterate()
+        print(f"[bc {rec['iteration']}] driver {rec['driver']} ({rec['expert']}), {rec['frames']} frames x {rec['envs']} envs: "
+              f"{rec['labelled']} labelled rows ({100 * rec['labelled_share']:.1f} %), loss {rec['loss_first']:.4f} -> "
+              f"{rec['loss_last']:.4f}, accuracy {rec['accuracy_before']:.3f} -> {rec['accuracy_after']:.3f}, arrivals "
+              f"{rec['arrivals']:.1f}, {rec['collect_seconds']:.2f} s + {rec['update_seconds']:.2f} s")
+        if log is not None:
+            log.write(json.dumps(rec) + "\n")
+            log.flush()
+    if log is not None:
+        log.close()
+
+
 def vec_eval_record(prefix, res):
     """The scalars of one vectorised evaluation (tarl_hip.evaluator.EvalResult) for the training log. After a domain exit
     only ``envs``, ``domain_exit`` and the time are numbers; the statistics are ``None`` (never an average of such a run)."""
@@ -127,7 +147,10 @@ def vec_eval_record(prefix, res):
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
-              eval_baseline="none", policy_hold=False):
+              eval_baseline="none", policy_hold=False, pretrain_bc=None):
+    """``pretrain_bc`` (not in the reference; None = off): a dict {iterations, expert, driver, envs, frames,
+    samples, epochs, batch, lr} — that many behaviour-cloning iterations (tarl_hip.imitation.BCTrainer) run before the first
+    PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``."""
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
     from tarl_hip.trainer import VecPPOTrainer
@@ -185,6 +208,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
         except Exception:  # noqa: BLE001
             writer = None
     trainer.keep_grad = log is not None
+    if pretrain_bc:
+        _pretrain_bc(env, trainer, dict(pretrain_bc), seed, log_dir if rank == 0 else None)
     if int(eval_envs) < 0:
         raise ValueError("eval_envs must be >= 0")
     # rank 0 alone evaluates (as it alone logs); the evaluator enters no collective

@@ -53,6 +53,15 @@ class RunnerArgs:
     replan_fraction: object = 0.1  # ... the share that may switch per day, in (0, 1], or "msa"
     replan_max_hops: int = None    # ... the longest route stored (default: min(roads, 256))
     iterations: int = 1            # train: collector batches; total_frames = iterations * rollout_steps
+    pretrain_bc: int = 0           # train, mpnn / mpnn+ppo: I > 0 behaviour-cloning iterations before PPO
+    bc_expert: str = None          # ... the router imitated: "dijkstra" (default; congested times, refreshed) or "free_flow"
+    bc_driver: str = None          # ... who drives the labelled rollout: "expert", "policy" or "dagger" (default)
+    bc_envs: int = None            # ... environments of the BC engine (default 16)
+    bc_frames: int = None          # ... frames per iteration (default: rollout_steps)
+    bc_samples: int = None         # ... (environment, frame) pairs kept per iteration (default 256)
+    bc_epochs: int = None          # ... passes over the store (default 4)
+    bc_batch: int = None           # ... minibatch (default: the PPO sub-batch)
+    bc_lr: float = None            # ... Adam step size (default: the PPO trainer's)
     checkpoint: str = None         # mpnn / mpnn+ppo: a policy.pt written by ppo_train, loaded after setup()
 
     @property
@@ -127,6 +136,27 @@ class RunnerArgs:
             raise ValueError(f"eval_link_bin must be >= 1 second, got {self.eval_link_bin!r}")
         if int(self.iterations) < 1:
             raise ValueError(f"iterations must be >= 1, got {self.iterations!r}")
+        given = [k for k in BC_FLAGS if getattr(self, k) is not None]
+        if self.pretrain_bc is None or int(self.pretrain_bc) < 0:
+            raise ValueError(f"pretrain_bc must be >= 0, got {self.pretrain_bc!r}")
+        if given and not self.pretrain_bc:
+            raise ValueError(f"{', '.join('--' + k.replace('_', '-') for k in given)} set(s) up the behaviour-cloning "
+                             "iterations: it needs --pretrain-bc I with I > 0")
+        if self.pretrain_bc:
+            if self.mode != "train":
+                raise ValueError("pretrain_bc clones the shortest-path router into the policy before training: it needs mode "
+                                 "'train' (evaluate the cloned policy.pt with --checkpoint)")
+            if self.algo not in ("mpnn", "mpnn+ppo"):
+                raise ValueError(f"pretrain_bc trains a policy network: it needs algo mpnn or mpnn+ppo, not {self.algo!r}")
+            if self.bc_expert is not None and self.bc_expert not in BC_EXPERT_NAMES:
+                raise ValueError(f"bc_expert must be one of {BC_EXPERT_NAMES}, got {self.bc_expert!r}")
+            if self.bc_driver is not None and self.bc_driver not in BC_DRIVER_NAMES:
+                raise ValueError(f"bc_driver must be one of {BC_DRIVER_NAMES}, got {self.bc_driver!r}")
+            for k in ("bc_envs", "bc_frames", "bc_samples", "bc_epochs", "bc_batch"):
+                if getattr(self, k) is not None and int(getattr(self, k)) < 1:
+                    raise ValueError(f"{k} must be >= 1, got {getattr(self, k)!r}")
+            if self.bc_lr is not None and not float(self.bc_lr) > 0.0:
+                raise ValueError(f"bc_lr must be positive, got {self.bc_lr!r}")
         if self.checkpoint is not None and self.algo in ("random", "dijkstra"):
             raise ValueError(f"checkpoint holds a policy network's parameters: not available for algo {self.algo!r}")
         from .agents.base import DijkstraAgents
@@ -145,6 +175,10 @@ class RunnerArgs:
 
 EVAL_BASELINE_NAMES = ("none", "dijkstra", "dijkstra_hold", "free_flow")      # tarl_hip.evaluator.EVAL_BASELINES, and "none"
 DIJKSTRA_ROUTER_NAMES = ("reference", "hold", "free_flow")                      # tarl_hip.evaluator.DIJKSTRA_ROUTERS
+
+BC_FLAGS = ("bc_expert", "bc_driver", "bc_envs", "bc_frames", "bc_samples", "bc_epochs", "bc_batch", "bc_lr")
+BC_EXPERT_NAMES = ("dijkstra", "free_flow")      # tarl_hip.imitation.EXPERTS
+BC_DRIVER_NAMES = ("expert", "policy", "dagger")  # tarl_hip.imitation.DRIVERS
 
 CHECKPOINT_PREFIX = "module.0.module."      # ProbabilisticActor -> TensorDictModule -> the network (ppo_train's keys)
 
@@ -263,6 +297,12 @@ class Runner:
                     raise ValueError("--eval-envs needs the packed (fused) path, which cannot represent this graph (Nmax > "
                                      "127, an out-degree above 126 or parallel edges); there is no fall-back for the "
                                      "vectorised evaluation: run without --eval-envs")
+            if a.pretrain_bc:
+                from tarl_hip import ops
+                if not ops.fused_path_supported(g.edge_index, self.env.simulator.Nmax):
+                    raise ValueError("--pretrain-bc needs the packed (fused) path, which cannot represent this graph (Nmax > "
+                                     "127, an out-degree above 126 or parallel edges); there is no fall-back for behaviour "
+                                     "cloning: run without --pretrain-bc")
             if a.replan_days:
                 self._replan_setup(g.edge_index, self.env.simulator.Nmax, self.policy_net.agent_features)
             if a.checkpoint is not None:
@@ -299,8 +339,9 @@ class Runner:
 
     def train(self):
         a = self.args
-        if not (a.algo == "mpnn+ppo" and a.mode == "train"):
-            raise RuntimeError("Training is only supported for algo 'mpnn+ppo'")
+        bc_only = a.algo == "mpnn" and a.mode == "train" and bool(a.pretrain_bc)      # cloning alone: no PPO iteration follows
+        if not (a.algo == "mpnn+ppo" and a.mode == "train") and not bc_only:
+            raise RuntimeError("Training is only supported for algo 'mpnn+ppo' (and, with --pretrain-bc, 'mpnn')")
         from .rl.modules import TensorDictModule, ValueOperator
         from .rl.ppo_trainer import ppo_train
         policy_module = self._actor(return_log_prob=True)
@@ -318,12 +359,18 @@ class Runner:
         if self.rank == 0:
             out.mkdir(parents=True, exist_ok=True)
         # rank 0 alone writes the checkpoint and the logs; every rank takes part in the training collectives
-        ppo_train(self.env, policy_module, value_module, total_frames=a.total_frames,
+        bc_kw = {}
+        if a.pretrain_bc:
+            bc_kw["pretrain_bc"] = dict(iterations=int(a.pretrain_bc), expert=a.bc_expert or "dijkstra",
+                                        driver=a.bc_driver or "dagger", envs=a.bc_envs or 16,
+                                        frames=a.bc_frames or a.rollout_steps, samples=a.bc_samples or 256,
+                                        epochs=a.bc_epochs or 4, batch=a.bc_batch, lr=a.bc_lr)
+        ppo_train(self.env, policy_module, value_module, total_frames=0 if bc_only else a.total_frames,
                   frames_per_batch=a.rollout_steps, num_epochs=a.epochs, device=self.device,
                   checkpoint_path=(out / "policy.pt") if self.rank == 0 else None,
                   log_dir=str(out) if self.rank == 0 else None, eval_env=eval_env, eval_interval=1,
                   num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled,
-                  eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}))
+                  eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}), **bc_kw)
 
     def eval(self):
         a = self.args

@@ -289,6 +289,47 @@ def _due(done, every, T):      # after `done` of T frames: a block of `every` fr
     return done % every == 0 or done == T
 
 
+def router_buffers(eng, baseline_dests=None, tables=None):
+    """The shortest-path routers' buffers on engine ``eng``, shared by the evaluator's router heads and the behaviour-cloning
+    expert (tarl_hip.imitation): -> (dests int64 (D,), dest_slot int32 (N,), travel times (K, E), the next-hop table
+    (``tables`` or K, D, N) filled with -1, the tree scratch (O(min(K D, 1024) N))). ``baseline_dests`` = (dests, dest_slot)
+    of src.agents.base.destination_set over the engine's agent tables (default: computed here by the same rule). Refused
+    beyond half the free device memory, like the graph-transformer critic's store."""
+    N, E, dev = eng.N, eng.E, eng.device
+    K = eng.B if tables is None else int(tables)
+    if baseline_dests is None:      # src.agents.base.destination_set's rule: every distinct DESTINATION, row 0 included
+        d = torch.unique(eng.agents[..., 1].reshape(-1).to(torch.int64))
+        d = d[(d >= 0) & (d < N)].contiguous()
+        slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=dev)
+        baseline_dests = (d, slot)
+    dests, dest_slot = baseline_dests
+    D = int(dests.numel())
+    table_bytes, scratch_bytes = ops.destination_trees_batched_bytes(eng.plan, K, D)
+    if scratch_bytes < 0:
+        raise _lib.TarlError("tarl_dest_trees_batched_scratch_bytes refused the evaluator's sizes")
+    free = int(torch.cuda.mem_get_info(dev)[0])
+    if table_bytes + scratch_bytes > free // 2:
+        raise _lib.TarlError(f"the shortest-path baseline's next-hop table ({table_bytes / 2**30:.2f} GiB for K = {K} "
+                             f"environments x D = {D} destinations x N = {N} nodes) and tree scratch "
+                             f"({scratch_bytes / 2**30:.2f} GiB) exceed half the free device memory "
+                             f"({free / 2**30:.2f} GiB free): evaluate fewer environments at a time")
+    weights = torch.empty((eng.B, E), dtype=torch.float32, device=dev)
+    table = torch.full((K, D, N), -1, dtype=torch.int32, device=dev)
+    return dests, dest_slot, weights, table, torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=dev)
+
+
+def refresh_router_tables(eng, t, refresh_rate, weights, dests, table, scratch):
+    """The shortest-path routers' refresh in front of frame ``t``, shared by the evaluator's router heads and the behaviour-
+    cloning expert (tarl_hip.imitation): every ``refresh_rate`` frames (0: at frame 0 only) the K environments' congested
+    travel times (``weights`` (K, E)) and their next-hop trees (``table`` (K, D, N)) are rebuilt. -> whether it ran."""
+    if not (t == 0 if refresh_rate == 0 else t % refresh_rate == 0):
+        return False
+    ops.fused_edge_travel_time(eng.plan, eng.fs, out=weights)
+    ops.destination_trees_batched(eng.plan, weights, dests, out=table, scratch=scratch)
+    return True
+
+
 class VecEvaluator:
     def __init__(self, engine, head="embedding", *, emb=None, temperature=1.0, edge_mlp=None, prior_table=None,
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
@@ -479,33 +520,10 @@ class VecEvaluator:
         return max(1, block if cap is None else min(block, cap))
 
     def _init_baseline(self, baseline_dests, tables=None):
-        """The baseline's buffers, once per evaluator: travel times (K, E), the next-hop table (K, D, N) and the tree scratch
-        (O(min(K D, 1024) N)). Refused beyond half the free device memory, like the graph-transformer critic's store.
-        ``tables``: the environments that get a table of their own (default: all K; 1 for the "routes" head's fallback, whose
-        one table is built from environment 0's empty network)."""
-        eng = self.eng
-        N, E, dev = eng.N, eng.E, eng.device
-        K = eng.B if tables is None else int(tables)
-        if baseline_dests is None:      # src.agents.base.destination_set's rule: every distinct DESTINATION, row 0 included
-            d = torch.unique(eng.agents[..., 1].reshape(-1).to(torch.int64))
-            d = d[(d >= 0) & (d < N)].contiguous()
-            slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
-            slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=dev)
-            baseline_dests = (d, slot)
-        self.dests, self.dest_slot = baseline_dests
-        D = int(self.dests.numel())
-        table_bytes, scratch_bytes = ops.destination_trees_batched_bytes(eng.plan, K, D)
-        if scratch_bytes < 0:
-            raise _lib.TarlError("tarl_dest_trees_batched_scratch_bytes refused the evaluator's sizes")
-        free = int(torch.cuda.mem_get_info(dev)[0])
-        if table_bytes + scratch_bytes > free // 2:
-            raise _lib.TarlError(f"the shortest-path baseline's next-hop table ({table_bytes / 2**30:.2f} GiB for K = {K} "
-                                 f"environments x D = {D} destinations x N = {N} nodes) and tree scratch "
-                                 f"({scratch_bytes / 2**30:.2f} GiB) exceed half the free device memory "
-                                 f"({free / 2**30:.2f} GiB free): evaluate fewer environments at a time")
-        self.weights = torch.empty((eng.B, E), dtype=torch.float32, device=dev)
-        self.table = torch.full((K, D, N), -1, dtype=torch.int32, device=dev)
-        self.tree_scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=dev)
+        """The baseline's buffers, once per evaluator (:func:`router_buffers`). ``tables``: the environments that get a table of
+        their own (default: all K; 1 for the "routes" head's fallback, whose one table is built from environment 0's empty
+        network)."""
+        self.dests, self.dest_slot, self.weights, self.table, self.tree_scratch = router_buffers(self.eng, baseline_dests, tables)
 
     def set_routes(self, routes, route_len):
         """The plan the ``"routes"`` head follows from the next frame on: ``routes`` int32 (A, L) with ``route_len`` (A,)
@@ -629,9 +647,7 @@ class VecEvaluator:
         if self.head in ROUTER_HEADS:   # choice -> core -> withdraw / insert -> reward: the environment's step order
             if eng._packed_stale:
                 eng.resync()
-            if t == 0 if self.refresh_rate == 0 else t % self.refresh_rate == 0:
-                ops.fused_edge_travel_time(eng.plan, eng.fs, out=self.weights)
-                ops.destination_trees_batched(eng.plan, self.weights, self.dests, out=self.table, scratch=self.tree_scratch)
+            refresh_router_tables(eng, t, self.refresh_rate, self.weights, self.dests, self.table, self.tree_scratch)
             ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec,
                                            hold=self.head == "dijkstra_hold")
             return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)

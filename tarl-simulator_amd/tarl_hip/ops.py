@@ -1224,6 +1224,83 @@ def fused_set_policy_hold(fs, on, held=None):
     fs.policy_held = held
 
 
+BC_IGNORE = 0xFF        # TARL_BC_IGNORE: the label byte of a row the expert says nothing about
+
+
+def fused_expert_labels(plan: Plan, fs, dest_slot, table, out=None, n_labelled=None):
+    """The shortest-path router's action of every row of ``fs`` as a LABEL in the policy's action space
+    (tarl_fused_expert_labels): the rank byte :func:`fused_select_next_hop_dest` (hold off) would write, with the
+    packed state left untouched. -> uint8 (B, N) env-major (``out``: written in place); ``BC_IGNORE`` on empty rows, on rows
+    the select kernel leaves untouched and on rows where it writes the raw code. ``table`` int32 (D, N) shared by the
+    environments or (B, D, N); ``dest_slot`` (N,) int32. ``n_labelled`` (B,) int32 (optional): += the labelled rows."""
+    N = plan.num_nodes
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    _contig(dest_slot, torch.int32, "dest_slot")
+    _contig(table, torch.int32, "table")
+    if dest_slot.dim() != 1 or dest_slot.numel() != N or table.dim() not in (2, 3) or table.size(-1) != N or \
+            (table.dim() == 3 and table.size(0) != fs.B):
+        raise ValueError(f"dest_slot must be ({N},) and table (D, {N}) or ({fs.B}, D, {N}), got "
+                         f"{tuple(dest_slot.shape)} and {tuple(table.shape)}")
+    D = table.size(-2)
+    if out is None:
+        out = torch.empty((fs.B, N), dtype=torch.uint8, device=table.device)
+    _contig(out, torch.uint8, "out")
+    if tuple(out.shape) != (fs.B, N):
+        raise ValueError(f"out must be (B, N) = ({fs.B}, {N})")
+    if n_labelled is not None:
+        _contig(n_labelled, torch.int32, "n_labelled")
+        if tuple(n_labelled.shape) != (fs.B,):
+            raise ValueError(f"n_labelled must be (B,) = ({fs.B},)")
+    _lib.check(_lib.load().tarl_fused_expert_labels(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, dest_slot.data_ptr(),
+                                                    table.data_ptr(), D * N if table.dim() == 3 else 0, D, out.data_ptr(),
+                                                    _lib.ptr(n_labelled), _lib.current_stream()))
+    return out
+
+
+def graphdist_bc(plan: Plan, logits, labels, temperature=1.0, grad_scale=None, want_grad=True, scratch=None):
+    """Cross-entropy of GraphDistribution(logits / temperature) on the labelled nodes, forward and backward
+    (tarl_graphdist_bc). ``logits`` fp32 (M, E), ``labels`` uint8 (M, N): node n is labelled when its byte is
+    below min(out-degree, 0x7F). -> (nll fp64 (M,), n_labelled int32 (M,), n_hit int32 (M,), grad_logits fp32 (M, E) or
+    None). ``grad_scale``: the factor on every gradient element, 1 / (labelled nodes of the minibatch) for the mean loss;
+    None: taken from a forward-only call first. ``scratch`` (optional): a device tensor of any dtype to reuse across calls;
+    only its size in bytes (at least ``tarl_graphdist_bc_scratch_bytes(plan, M)``) and an 8-byte aligned address matter. The C
+    entry point takes no size, so a smaller one is refused HERE, from the shapes alone: before the tensors are looked at,
+    before anything is allocated and before any HIP call."""
+    L = _lib.load()
+    E, N = plan.num_edges, plan.num_nodes
+    if logits.dim() != 2 or logits.size(1) != E or labels.dim() != 2 or tuple(labels.shape) != (logits.size(0), N):
+        raise ValueError(f"logits must be (M, {E}) and labels (M, {N}), got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    M = logits.size(0)
+    if M < 1 or not float(temperature) > 0.0:
+        raise ValueError("M must be >= 1 and temperature positive")
+    need = int(L.tarl_graphdist_bc_scratch_bytes(plan.handle, M))
+    if need < 0:
+        raise _lib.TarlError("tarl_graphdist_bc_scratch_bytes refused the sizes")
+    if scratch is not None and scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch holds {scratch.numel() * scratch.element_size()} bytes, tarl_graphdist_bc needs {need}")
+    _contig(logits, torch.float32, "logits")
+    _contig(labels, torch.uint8, "labels")
+    if scratch is None:
+        scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=logits.device)
+    elif not scratch.is_cuda or not scratch.is_contiguous():
+        raise _lib.TarlError("scratch must be a contiguous tensor on the GPU")
+    dev = logits.device
+    nll = torch.empty(M, dtype=torch.float64, device=dev)
+    n_lab = torch.empty(M, dtype=torch.int32, device=dev)
+    n_hit = torch.empty(M, dtype=torch.int32, device=dev)
+
+    def call(scale, grad):
+        _lib.check(L.tarl_graphdist_bc(plan.handle, logits.data_ptr(), M, float(temperature), labels.data_ptr(), float(scale),
+                                       nll.data_ptr(), n_lab.data_ptr(), n_hit.data_ptr(), _lib.ptr(grad), scratch.data_ptr(),
+                                       _lib.current_stream()))
+    grad = torch.empty_like(logits) if want_grad else None
+    if want_grad and grad_scale is None:
+        call(0.0, None)
+        grad_scale = 1.0 / max(int(n_lab.sum().item()), 1)
+    call(0.0 if grad_scale is None else grad_scale, grad)
+    return nll, n_lab, n_hit, grad
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")
