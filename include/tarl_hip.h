@@ -1151,6 +1151,61 @@ int tarl_graphdist_bc(const tarl_plan* plan, const float* logits, int64_t M, flo
                       float grad_scale, double* nll, int32_t* n_labelled, int32_t* n_hit, float* grad_logits, void* scratch,
                       tarl_stream stream);
 
+/* ---- the goal-conditioned policy head (policy_head = "goal_mlp"; csrc/goal_mlp.hip) ------------------------------
+ * NOT in the reference: a trainable per-edge MLP 8 -> 16 -> 1 on destination-relative features, the head the cloned router
+ * can be learned by. TARL_ABI_VERSION is unchanged: nothing existing moved. For a route edge e = (u -> v), in fp32 with IEEE
+ * operations only (no FMA):
+ *   d = (long) DESTINATION of u's head agent, read as the prior head reads it; D = table[v][d] through the prior's lookup
+ *   (+inf: unreachable, d outside [0, N), no column); tt = the prior's time_travel(v); c = D + tt. e is REACHABLE when c is
+ *   finite; cmin(u) = the exact minimum of c over u's reachable out-edges; S = time_scale.
+ *   g0 = min((c - cmin) / S, 8) (8 when unreachable); g1 = [v == d]; g2 = min(tt / FF(v) - 1, 8), 0 unless FF(v) > 0;
+ *   g3 = NUMBER_OF_AGENT(v) / MAXN(v), 0 where MAXN <= 0; g4 = the same of u; g5 = min(D / S, 64) / 8;
+ *   g6 = [NUMBER_OF_AGENT(u) == 0]; g7 = min(FF(v) / S, 8).
+ *   pre_j = b1[j] + sum_k W1[j][k] * g_k (k = 0..7 ascending, multiply then add); h_j = pre_j > 0 ? pre_j : 0;
+ *   logit = b2 + sum_j w2[j] * h_j (j = 0..15 ascending). An unreachable edge's logit is exactly -1e20 (the prior head's
+ *   sentinel and its consequences: probability 0 next to a reachable candidate, a uniform draw where all are unreachable).
+ * weights / grads: 161 floats, W1 [16][8] at 0, b1 [16] at 128, w2 [16] at 144, b2 at 160.
+ * table, table_cols, dest_slot: dest_slot == NULL -> table is the all-pairs [N][N] table and table_cols must equal N;
+ *   otherwise table is the per-destination [N][table_cols] table of tarl_prior_dest_table and dest_slot int32 [N] its
+ *   column map (-1: none). time_scale: finite and > 0 (the mean FREE_FLOW over the roads, computed by the host).
+ * tarl_policy_goal_features: obs16 [M][N][16] (tarl_policy_obs16 layout, 16-byte aligned) -> feats fp32 [M][E][8] (16-byte
+ *   aligned), original edge order; every element is written.
+ * tarl_policy_goal_mlp_fwd: obs16 -> logits [M][E].
+ * tarl_policy_goal_mlp_bwd ACCUMULATES (+=) the gradients of sum(grad_logits * logits) over the reachable (sample, edge)
+ *   pairs into grads [161], as tarl_policy_edge_mlp_bwd does; an unreachable pair's grad_logits entry is not read.
+ *   Features are recomputed from obs16. Deterministic: a fixed partition of the pairs over workgroups writes [partition][161]
+ *   partial sums into scratch (fp32, 16-byte aligned, tarl_policy_goal_mlp_bwd_scratch_floats(plan, M) elements, every one
+ *   written before it is read), a second kernel adds them in partition order; no floating-point atomics, two runs are
+ *   bit-identical. The size query answers -1 for a null plan, M < 1 or 2^31 * 256 or more pairs, which the calls refuse too.
+ * tarl_fused_goal_mlp_logits: the same logits from the fused engine's packed state -> logits [B][E], bit-identical to
+ *   tarl_policy_goal_mlp_fwd on tarl_fused_obs16's observations of that state.
+ * tarl_fused_rollout_goal: tarl_fused_rollout_prior with this head (per frame kept observation rows -> the logits launch ->
+ *   the shared loop's sampler, hold rule, Direction, rows, insert); other arguments and outputs as there.
+ * Refused on the host, before any HIP call: a null argument, M or B < 1, time_scale not finite or <= 0, table_cols not
+ *   matching, a misaligned obs16 / feats / scratch, too many tiles for a grid dimension. A refused call writes nothing. */
+int tarl_policy_goal_features(const tarl_plan* plan, const float* obs16, int64_t M, const float* table, int64_t table_cols,
+                              const int32_t* dest_slot, float time_scale, float* feats, tarl_stream stream);
+int tarl_policy_goal_mlp_fwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* table, int64_t table_cols,
+                             const int32_t* dest_slot, float time_scale, const float* weights, float* logits,
+                             tarl_stream stream);
+int64_t tarl_policy_goal_mlp_bwd_scratch_floats(const tarl_plan* plan, int64_t M);
+int tarl_policy_goal_mlp_bwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* table, int64_t table_cols,
+                             const int32_t* dest_slot, float time_scale, const float* weights, const float* grad_logits,
+                             float* grads, float* scratch, tarl_stream stream);
+int tarl_fused_goal_mlp_logits(const tarl_plan* plan, const tarl_fused* f, const float* x, int64_t B, int64_t x_bstride,
+                               int64_t ldx, int32_t Nmax, const float* agent_features, int64_t num_agents, int64_t a_bstride,
+                               const float* table, int64_t table_cols, const int32_t* dest_slot, float time_scale,
+                               const float* weights, float* logits, tarl_stream stream);
+int tarl_fused_rollout_goal(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t T,
+                            const float* times_host, float prev_time, const float* x, int64_t x_bstride, int64_t ldx,
+                            float* agent_features, int64_t num_agents, int64_t a_bstride, const float* edge_attr,
+                            const float* log_edge_attr, float log_eps, int use_cong, const float* table, int64_t table_cols,
+                            const int32_t* dest_slot, float time_scale, const float* weights, float temperature,
+                            uint64_t policy_seed, uint64_t policy_counter0, uint64_t seed, uint64_t counter0,
+                            const int64_t* keep_ptr_host, const int32_t* keep_env, const int32_t* keep_slot, float* obs_keep,
+                            float* logits_scratch, void* dist_scratch, int32_t* ins_scratch, uint8_t* choice8, float* log_prob,
+                            float* reward, uint8_t* counts, tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

@@ -37,18 +37,16 @@
 // the same templates; only the table lookup differs (PriorAllPairs / PriorPerDest).
 #include <math.h>
 
+#include "prior_tables.h"     // PRIOR_UNREACHABLE, PriorAllPairs / PriorPerDest, prior_time_travel (shared with goal_mlp.hip)
 #include "rollout_heads.h"
 
-#define PRIOR_UNREACHABLE (-1e20f)
 #define PR_BLOCK 256
 #define PR_TE 64      // environments per fused tile (one per lane)
 #define PR_TK 64      // CSR positions per fused tile
 
 __device__ __forceinline__ float prior_logit(float em, float d, float ff, float maxn, float maxflow, float na, float w) {
   if (!(d <= 3.4028234663852886e38f)) return em + PRIOR_UNREACHABLE;     // +inf (unreachable) or NaN
-  const float crit = maxflow * ff / 3600.0f;                             // critical_number (:182)
-  const float tc = ff * (maxn + 10.0f - crit) / (maxn + 10.0f - na);     // time_congestion (:183)
-  const float tt = (ff != ff || tc != tc) ? NAN : fmaxf(ff, tc);         // torch.max over the stack (:184)
+  const float tt = prior_time_travel(ff, maxn, maxflow, na);             // :182-184
   return em + w * ((-d) - tt);                                           // logits + logits_dijkstra (:113, :188)
 }
 
@@ -56,29 +54,6 @@ __device__ __forceinline__ float emb_of(const float* __restrict__ emb, int64_t M
   const long long idx = (long long)road;
   return (idx >= 0 && idx < M) ? emb[idx] : 0.0f;        // tarl_policy_edge_logits_fwd's rule
 }
-
-// dist[v][dest]: the N x N all-pairs table
-struct PriorAllPairs {
-  const float* __restrict__ dist;
-  int64_t N;
-  __device__ __forceinline__ float operator()(int64_t v, float dest_f) const {
-    const long long d = (long long)dest_f;                 // agent_destination.to(torch.long) (:186)
-    return (d >= 0 && d < N) ? dist[v * N + d] : INFINITY;
-  }
-};
-
-// table[v][slot[dest]]: the [N][D] per-destination table; no column -> unreachable
-struct PriorPerDest {
-  const float* __restrict__ table;
-  const int32_t* __restrict__ slot;
-  int64_t N, D;
-  __device__ __forceinline__ float operator()(int64_t v, float dest_f) const {
-    const long long d = (long long)dest_f;
-    if (d < 0 || d >= N) return INFINITY;
-    const int32_t s = slot[d];
-    return (s >= 0 && s < D) ? table[v * D + s] : INFINITY;
-  }
-};
 
 // ---- from observations ---------------------------------------------------------------------------------------------------
 template <class Tab>

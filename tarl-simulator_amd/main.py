@@ -52,7 +52,7 @@ OPTIONS = (
     ("--steps", dict(type=int, default=None, help="number of eval steps (overrides start/end time)")),
     ("--num-envs", dict(type=int, default=1, help="vectorised environments per GPU for mpnn+ppo training")),
     ("--policy-head", dict(choices=("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra",
-                                    "graph_transformer"),
+                                    "graph_transformer", "goal_mlp"),
                            default="embedding",
                            help="mpnn / mpnn+ppo: the reference's live embedding head, or the per-edge MLP head it keeps "
                                 "as parameters (state-dependent; edge_mlp: rollout logits at fp32 accuracy on the bf16 matrix "
@@ -60,11 +60,13 @@ OPTIONS = (
                                 "products, edge_mlp_bf16: bf16 logits; the PPO update runs in fp32), or embedding_dijkstra: "
                                 "the embedding plus the free-flow shortest-path prior towards the head agent's destination, "
                                 "or graph_transformer: the reference's GraphTransformerNet edge output (evaluation-mode "
-                                "BatchNorm, Laplacian positional encoding)")),
+                                "BatchNorm, Laplacian positional encoding), or goal_mlp: a small trainable per-edge MLP on "
+                                "destination-relative features (detour over the best turn, distance left, congestion; the "
+                                "distances of --prior-method; not in the reference)")),
     ("--prior-weight", dict(type=float, default=1.0,
                             help="embedding_dijkstra: weight of the shortest-path prior (1.0 = the reference's plain sum)")),
     ("--prior-method", dict(choices=("all_pairs", "per_destination", "auto"), default="all_pairs",
-                            help="embedding_dijkstra: free-flow distances from the all-pairs table (N x N), or one column "
+                            help="embedding_dijkstra, goal_mlp: free-flow distances from the all-pairs table (N x N), or one column "
                                  "per distinct agent destination ([N][D], for large networks), or auto: all_pairs up to "
                                  "4 096 nodes, per_destination above")),
     ("--dijkstra-method", dict(choices=DijkstraAgents.METHODS, default="all_pairs",

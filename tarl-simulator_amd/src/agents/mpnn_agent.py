@@ -70,6 +70,27 @@ class _EdgeMlp(torch.autograd.Function):
         return (None, None, None, None) + tuple(g.view(sh) for g, sh in zip(grads, shapes))
 
 
+class _GoalMlp(torch.autograd.Function):
+    """The goal-conditioned MLP head on the HIP kernels (tarl_policy_goal_mlp_fwd / _bwd); gradients for its four
+    parameters, cut from the kernels' flat (161,) gradient."""
+
+    @staticmethod
+    def forward(ctx, obs16, plan, table, dest_slot, time_scale, w1, b1, w2, b2):
+        from tarl_hip import ops
+        w = ops.GoalMlpWeights(w1, b1, w2, b2)
+        ctx.saved = (obs16, plan, table, dest_slot, time_scale, w, [t.shape for t in (w1, b1, w2, b2)])
+        return ops.policy_goal_mlp(plan, obs16, w, table, time_scale, dest_slot=dest_slot)
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        from tarl_hip import ops
+        obs16, plan, table, dest_slot, time_scale, w, shapes = ctx.saved
+        flat = torch.zeros(ops.GOAL_MLP_PARAMS, dtype=torch.float32, device=obs16.device)
+        ops.policy_goal_mlp_bwd(plan, obs16, w, table, time_scale, grad_logits.contiguous(), flat, dest_slot=dest_slot)
+        parts = torch.split(flat, [int(torch.Size(s).numel()) for s in shapes])
+        return (None, None, None, None, None) + tuple(g.view(s) for g, s in zip(parts, shapes))
+
+
 class MPNNPolicyNet(MessagePassingBase, Agents):
     h = ObservationFeatureHelpers()
     # Which head produces the logits. "embedding": the reference's live forward (logit = nodes_embedding of the target
@@ -83,6 +104,9 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
     # "graph_transformer": the reference's GraphTransformerNet edge output (src/transformer/model.py, as MLAgents builds it),
     # evaluation-mode BatchNorm; its ``transformer`` submodule and ``gt_pe`` buffer exist only after
     # :meth:`use_graph_transformer`, so the other heads' state dicts do not change.
+    # "goal_mlp" (not in the reference): a trainable per-edge MLP 8 -> 16 -> 1 on destination-relative features built from the
+    # prior head's quantities (csrc/goal_mlp.hip); its ``goal_mlp`` submodule and ``goal_scale`` buffer exist only after
+    # :meth:`use_goal_mlp`. It reads the same distance tables as the prior (``prior_method`` below).
     # Where the prior's distances come from: "all_pairs" = ``dist_matrix`` (N x N, tarl_apsp); "per_destination" = one
     # column per distinct DESTINATION of the agent table, (N, D) fp32 (tarl_prior_dest_table; ``dist_matrix`` is never
     # built); "auto" = all_pairs up to ALL_PAIRS_MAX_NODES nodes, per_destination above. The same logits either way
@@ -189,10 +213,39 @@ class MPNNPolicyNet(MessagePassingBase, Agents):
         self.to(self.device)
         return self
 
+    def use_goal_mlp(self, time_scale: float):
+        """Switch to the goal-conditioned head (NOT in the reference; csrc/goal_mlp.hip): creates ``goal_mlp`` (Linear(8, 16),
+        ReLU, Linear(16, 1); U(-0.1, 0.1) weights, zero bias) on destination-relative features and the buffer ``goal_scale``
+        (``time_scale``: the mean FREE_FLOW over the roads, ops.goal_time_scale). Both exist only after this call, so the
+        other heads' state dicts do not change. The distances come from :meth:`prior_tables`."""
+        s = float(time_scale)
+        if not (0.0 < s < float("inf")):
+            raise ValueError("time_scale must be finite and > 0")
+        self.policy_head = "goal_mlp"
+        if getattr(self, "goal_mlp", None) is None:
+            self.goal_mlp = nn.Sequential(nn.Linear(8, 16), nn.ReLU(), nn.Linear(16, 1))
+            for m in self.goal_mlp:
+                if isinstance(m, nn.Linear):
+                    nn.init.uniform_(m.weight, -0.1, 0.1)
+                    nn.init.constant_(m.bias, 0)
+        self.register_buffer("goal_scale", torch.tensor(s, dtype=torch.float32))
+        self.to(self.device)
+        return self
+
     def forward(self, node_features: torch.Tensor, edge_features: torch.Tensor, agent_index: torch.Tensor):
         """node_features (N,7) or (B,N,7) -> logits (E,) or (B,E)."""
         require_cuda(node_features, "node_features")
         plan = cached_plan(self.edge_index, self.num_nodes)
+        if self.policy_head == "goal_mlp":
+            from tarl_hip import ops
+            if getattr(self, "goal_mlp", None) is None:
+                raise RuntimeError("policy_head 'goal_mlp' needs use_goal_mlp(time_scale) first")
+            obs16 = ops.policy_obs16(node_features, agent_index, self.agent_features.to(node_features.device))
+            table, slot = self.prior_tables()
+            m = self.goal_mlp
+            logits = _GoalMlp.apply(obs16, plan, table, slot, float(self.goal_scale), m[0].weight, m[0].bias, m[2].weight,
+                                    m[2].bias)
+            return logits if node_features.dim() == 3 else logits.view(-1)
         if self.policy_head == "graph_transformer":
             from tarl_hip import ops
             from .._compat import cached_edge_const

@@ -104,7 +104,7 @@ def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_ho
     from tarl_hip.evaluator import VecEvaluator
     engine = _eval_engine(eval_env, eval_envs, seed)
     dests = None
-    if getattr(policy_net, "policy_head", "embedding") == "embedding_dijkstra" and \
+    if getattr(policy_net, "policy_head", "embedding") in ("embedding_dijkstra", "goal_mlp") and \
             policy_net.resolve_prior_method() != "all_pairs":
         dests = destination_set(engine.agents, engine.N)
     kw = {"policy_hold": True} if policy_hold else {}
@@ -181,17 +181,21 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     head = getattr(policy_net, "policy_head", "embedding")
     m = policy_net.edge_mlp
     prior_kw = {}
-    if head == "embedding_dijkstra":
+    if head in ("embedding_dijkstra", "goal_mlp"):      # the heads that read the shortest-path tables
         if policy_net.resolve_prior_method() == "all_pairs":
             prior_kw = dict(prior_table=policy_net.dist_matrix)
         else:       # one column per destination of every environment's agent table
             prior_kw = dict(prior_free_flow=policy_net.free_flow_weights(),
                             prior_dests=destination_set(engine.agents, engine.N))
+    if head == "goal_mlp":
+        gm = policy_net.goal_mlp
+        prior_kw["goal_mlp_params"] = [gm[0].weight, gm[0].bias, gm[2].weight, gm[2].bias]
     trainer = VecPPOTrainer(engine, policy_net.nodes_embedding.weight,
                             critic,
                             rollout_steps=frames_per_batch, num_epochs=num_epochs, sub_batch_size=sub_batch_size,
                             extra_params=dormant, seed=seed,
-                            policy=head if head in ("embedding", "embedding_dijkstra", "graph_transformer") else "edge_mlp",
+                            policy=head if head in ("embedding", "embedding_dijkstra", "graph_transformer",
+                                                    "goal_mlp") else "edge_mlp",
                             edge_mlp_params=[m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias],
                             policy_precision={"edge_mlp_bf16": "bf16", "edge_mlp_fp32": "fp32"}.get(head, "x3"),
                             prior_weight=getattr(policy_net, "prior_weight", 1.0), **prior_kw,

@@ -28,6 +28,7 @@ class RunnerArgs:
     policy_head: str = "embedding"
     prior_weight: float = 1.0      # policy_head "embedding_dijkstra": weight of the shortest-path prior
     prior_method: str = "all_pairs"   # its distances: "all_pairs", "per_destination" or "auto" (MPNNPolicyNet.prior_method)
+    #                                   (policy_head "goal_mlp" reads the same tables)
     value_head: str = "simple"     # "graph_transformer": ValueNet (src/agents/transformer_agent.py)
     dijkstra_method: str = "all_pairs"   # DijkstraAgents: "all_pairs", "per_destination" or "auto"
     equilibrium_metrics: bool = False    # eval: TSTT at UE and SO, both relative gaps, Price of Anarchy (algorithms/equilibrium.py)
@@ -91,7 +92,7 @@ class RunnerArgs:
             if self.mode == "train" and self.policy_head == "embedding":
                 raise ValueError("policy_hold cannot train policy_head 'embedding': its rollout kernels draw the actions of "
                                  "all frames ahead of the frames, so the rule has no frame state to read; use a "
-                                 "state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer)")
+                                 "state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer, goal_mlp)")
         if self.dijkstra_envs is None or int(self.dijkstra_envs) < 0:
             raise ValueError(f"dijkstra_envs must be >= 0, got {self.dijkstra_envs!r}")
         if self.dijkstra_envs and not (self.algo == "dijkstra" and self.mode == "eval"):
@@ -170,7 +171,7 @@ class RunnerArgs:
         if self.value_head == "graph_transformer" and self.policy_head == "embedding":
             raise ValueError("value_head 'graph_transformer' reads the observation of every frame, which the 'embedding' "
                              "head's rollout does not build: use a state-dependent policy head (edge_mlp*, "
-                             "embedding_dijkstra or graph_transformer)")
+                             "embedding_dijkstra, graph_transformer or goal_mlp)")
 
 
 EVAL_BASELINE_NAMES = ("none", "dijkstra", "dijkstra_hold", "free_flow")      # tarl_hip.evaluator.EVAL_BASELINES, and "none"
@@ -282,6 +283,9 @@ class Runner:
                 pe = cached_laplacian_pe(g.edge_index if routes is None else routes, roads, g.x.size(0), cache)
             if a.policy_head == "graph_transformer":
                 self.policy_net.use_graph_transformer(pe)
+            if a.policy_head == "goal_mlp":      # the time scale: the mean free-flow time of the graph's rows
+                from tarl_hip import ops
+                self.policy_net.use_goal_mlp(ops.goal_time_scale(g.x[:, 3 * self.env.simulator.Nmax:]))
             self.policy_net.load(a.scenario)
             if a.value_head == "graph_transformer":
                 from .agents.transformer_agent import ValueNet
@@ -607,7 +611,7 @@ class Runner:
         a, sim = self.args, self.env.simulator
         engine = self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs)
         dests = None
-        if a.policy_head == "embedding_dijkstra" and self.policy_net.resolve_prior_method() != "all_pairs":
+        if a.policy_head in ("embedding_dijkstra", "goal_mlp") and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
         ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw(),
                                           **({"policy_hold": True} if a.policy_hold else {}))

@@ -239,6 +239,20 @@ class SimEngine:
                              policy_counter0=policy_counter0, keep=keep, obs_keep=obs_keep, choice8=choice8,
                              log_prob=log_prob, reward=reward, dest_slot=dest_slot)
 
+    def rollout_goal(self, T, weights, table, time_scale, dest_slot=None, *, temperature, policy_seed, policy_counter0,
+                     choice8, log_prob, reward, counts, keep=None, obs_keep=None, check=True):
+        """``T`` frames under the goal-conditioned MLP head (``weights``: ops.GoalMlpWeights, ``table`` / ``dest_slot`` as
+        :meth:`rollout_prior`, ``time_scale``: ops.goal_time_scale) in one foreign call: per frame goal-MLP logits from the
+        packed state -> GraphDistribution sample + log-prob -> the simulation frame. Buffers as :meth:`rollout_policy`.
+        Returns the list of clock values."""
+        if self.fs is None:
+            raise ValueError("rollout_goal needs the fused engine")
+        return self._rollout(T, counts, True, check,
+                             partial(ops.fused_rollout_goal, self.plan, self.fs, self._x, self.agents, self.ec, weights, table,
+                                     time_scale),
+                             temperature=temperature, policy_seed=policy_seed, policy_counter0=policy_counter0, keep=keep,
+                             obs_keep=obs_keep, choice8=choice8, log_prob=log_prob, reward=reward, dest_slot=dest_slot)
+
     def rollout_gt(self, T, pe, weights, *, temperature, policy_seed, policy_counter0, choice8, log_prob, reward, counts,
                    keep=None, obs_keep=None, check=True):
         """``T`` frames under the graph-transformer head (``pe``: (N, 16) positional encoding, ``weights``: ops.GtWeights) in

@@ -69,7 +69,7 @@ from .eval_reports import (CONGESTION_FILE, DYNAMIC_GAP_NOTE, LINK_EXPECTED, LIN
                            trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report, trip_summary,
                            turn_bin_names, turn_lines, turn_report, turn_summary)
 
-HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "dijkstra",
+HEADS = ("embedding", "edge_mlp", "edge_mlp_fp32", "edge_mlp_bf16", "embedding_dijkstra", "graph_transformer", "goal_mlp", "dijkstra",
          "dijkstra_hold", "routes")
 PLAN_HEADS = ("routes",)                          # follows a per-agent plan (set_routes): no policy tensors, no sampled mode
 ROUTER_HEADS = ("dijkstra", "dijkstra_hold")      # the shortest-path routers: no policy tensors, no sampled mode
@@ -335,11 +335,14 @@ class VecEvaluator:
                  dest_slot=None, prior_weight=1.0, gt_pe=None, gt_weights=None, bin_width=10.0, num_bins=720, poll_frames=64,
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
-                 dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True, policy_hold=False):
+                 dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True, policy_hold=False,
+                 goal_mlp=None, goal_scale=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
-        (graph_transformer). The tensors are read at every frame: views of live parameters evaluate the current policy.
+        (graph_transformer); ``goal_mlp``: ops.GoalMlpWeights with ``goal_scale`` (ops.goal_time_scale) and the prior head's
+        ``prior_table`` / ``dest_slot`` (goal_mlp). The tensors are read at every frame: views of live parameters evaluate the
+        current policy.
         ``keep_actions``: also record every frame's action bytes in ``actions`` (T, K, N) uint8 (tests).
         Heads ``"dijkstra"`` and ``"dijkstra_hold"`` (the shortest-path baselines, no ``emb``; the second holds a head one
         road short of its destination, module docstring): ``refresh_rate`` frames between two rebuilds of the K
@@ -397,6 +400,9 @@ class VecEvaluator:
             raise ValueError(f"head {head!r} needs edge_mlp (ops.EdgeMlpWeights)")
         if head == "embedding_dijkstra" and prior_table is None:
             raise ValueError("head 'embedding_dijkstra' needs prior_table (and dest_slot for a per-destination table)")
+        if head == "goal_mlp" and (prior_table is None or goal_mlp is None or goal_scale is None):
+            raise ValueError("head 'goal_mlp' needs goal_mlp (ops.GoalMlpWeights), goal_scale and prior_table (and dest_slot "
+                             "for a per-destination table)")
         if head == "graph_transformer" and (gt_pe is None or gt_weights is None):
             raise ValueError("head 'graph_transformer' needs gt_pe and gt_weights")
         if head in PLAN_HEADS and routes is None:
@@ -417,6 +423,7 @@ class VecEvaluator:
         self.temperature = float(temperature)
         self.edge_mlp, self.prior_table, self.dest_slot = edge_mlp, prior_table, dest_slot
         self.prior_weight, self.gt_pe, self.gt_weights = float(prior_weight), gt_pe, gt_weights
+        self.goal_mlp, self.goal_scale = goal_mlp, goal_scale
         self.bin_width, self.num_bins, self.poll_frames = float(bin_width), int(num_bins), int(poll_frames)
         self.keep_actions = bool(keep_actions)
         self.policy_hold = bool(policy_hold)
@@ -507,7 +514,7 @@ class VecEvaluator:
             self.dist_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
             if head == "edge_mlp_bf16":
                 self.obs = torch.empty((K, N, 16), dtype=torch.bfloat16, device=dev)
-            elif head != "embedding_dijkstra":
+            elif head not in ("embedding_dijkstra", "goal_mlp"):
                 self.obs = torch.empty((K, N, 16), dtype=torch.float32, device=dev)
             if head == "graph_transformer":
                 n = int(_lib.load().tarl_policy_gt_fwd_scratch_floats(plan.handle, K))
@@ -562,6 +569,18 @@ class VecEvaluator:
                     raise ValueError("the per-destination prior needs prior_dests = destination_set(engine.agents, N)")
                 args["prior_table"], args["dest_slot"] = VecPPOTrainer._build_prior_dest(
                     engine, policy_net.free_flow_weights(), *prior_dests)
+        elif head == "goal_mlp":
+            m = policy_net.goal_mlp
+            args["goal_mlp"] = ops.GoalMlpWeights(*(p.data for p in (m[0].weight, m[0].bias, m[2].weight, m[2].bias)))
+            args["goal_scale"] = float(policy_net.goal_scale)
+            if policy_net.resolve_prior_method() == "all_pairs":
+                args["prior_table"] = policy_net.dist_matrix
+            else:
+                from .trainer import VecPPOTrainer
+                if prior_dests is None:
+                    raise ValueError("the per-destination table needs prior_dests = destination_set(engine.agents, N)")
+                args["prior_table"], args["dest_slot"] = VecPPOTrainer._build_prior_dest(
+                    engine, policy_net.free_flow_weights(), *prior_dests)
         elif head == "graph_transformer":
             args["gt_pe"] = policy_net.gt_pe
             args["gt_weights"] = ops.GtWeights(policy_net.transformer.kernel_tensors())
@@ -589,6 +608,9 @@ class VecEvaluator:
         if self.head == "embedding_dijkstra":
             return ops.fused_prior_logits(plan, fs, eng._x, eng.Nmax, eng.agents, self.emb, self.prior_table,
                                           self.prior_weight, out=self.logits, dest_slot=self.dest_slot)
+        if self.head == "goal_mlp":
+            return ops.fused_goal_mlp_logits(plan, fs, eng._x, eng.Nmax, eng.agents, self.goal_mlp, self.prior_table,
+                                             self.goal_scale, dest_slot=self.dest_slot, out=self.logits)
         if self.head == "edge_mlp_bf16":
             obs = ops.fused_obs16_bf16(plan, fs, eng._x, eng.Nmax, eng.agents, out=self.obs)
             return ops.policy_edge_mlp(plan, obs, eng.ec, self.edge_mlp, out=self.logits)

@@ -105,6 +105,9 @@ class BCTrainer:
                 head, kw["edge_mlp"] = self._EVAL_HEAD[ppo.policy_precision], ppo._edge_mlp()
             elif head == "embedding_dijkstra":
                 kw.update(prior_table=ppo.prior_table, dest_slot=ppo.prior_dest_slot)
+            elif head == "goal_mlp":
+                kw.update(prior_table=ppo.prior_table, dest_slot=ppo.prior_dest_slot, goal_mlp=ppo._goal(),
+                          goal_scale=ppo.goal_scale)
             elif head == "graph_transformer":
                 kw.update(gt_pe=ppo.gt_pe, gt_weights=ppo._gt())
             self._policy_ev = VecEvaluator(self.eng, head, **kw)

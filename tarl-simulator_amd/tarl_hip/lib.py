@@ -156,6 +156,15 @@ SIGNATURES = {
     "tarl_fused_expert_labels": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _i64, _i64, _p, _p, _p]),
     "tarl_graphdist_bc_scratch_bytes": (_i64, [_p, _i64]),
     "tarl_graphdist_bc": (C.c_int, [_p, _p, _i64, _f32, _p, _f32, _p, _p, _p, _p, _p, _p]),
+    "tarl_policy_goal_features": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _f32, _p, _p]),
+    "tarl_policy_goal_mlp_fwd": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _f32, _p, _p, _p]),
+    "tarl_policy_goal_mlp_bwd_scratch_floats": (_i64, [_p, _i64]),
+    "tarl_policy_goal_mlp_bwd": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _f32, _p, _p, _p, _p, _p]),
+    "tarl_fused_goal_mlp_logits": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _f32, _p,
+                                             _p, _p]),
+    "tarl_fused_rollout_goal": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p,
+                                          _f32, C.c_int, _p, _i64, _p, _f32, _p, _f32, _u64, _u64, _u64, _u64] +
+                                [_p] * 11 + [_p]),
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),

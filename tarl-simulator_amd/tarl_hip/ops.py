@@ -2104,6 +2104,205 @@ def fused_rollout_prior(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeC
                   counts=counts)
 
 
+# ---- goal-conditioned MLP head (policy_head = "goal_mlp", csrc/goal_mlp.hip) -------------------------------------------------
+GOAL_MLP_FEATURES, GOAL_MLP_HIDDEN, GOAL_MLP_PARAMS = 8, 16, 161
+# state-dict keys of MPNNPolicyNet's ``goal_mlp`` submodule in the kernels' order (offsets 0, 128, 144, 160)
+GOAL_MLP_KEYS = ("goal_mlp.0.weight", "goal_mlp.0.bias", "goal_mlp.2.weight", "goal_mlp.2.bias")
+
+
+class GoalMlpWeights:
+    """The 161 parameters of the goal-conditioned head as ONE flat fp32 device tensor in kernel order: ``goal_mlp.0.weight``
+    (16, 8), ``goal_mlp.0.bias`` (16,), ``goal_mlp.2.weight`` (1, 16), ``goal_mlp.2.bias`` (1,). Built from the four tensors
+    (copied into a flat buffer) or, with ``flat=``, around an existing (161,) tensor (a view of a flat parameter buffer: no
+    copy, updates are seen)."""
+
+    def __init__(self, w1=None, b1=None, w2=None, b2=None, *, flat=None):
+        if flat is None:
+            parts = [(w1, (GOAL_MLP_HIDDEN, GOAL_MLP_FEATURES), "w1"), (b1, (GOAL_MLP_HIDDEN,), "b1"),
+                     (w2, (1, GOAL_MLP_HIDDEN), "w2"), (b2, (1,), "b2")]
+            for t, shp, name in parts:
+                ok = isinstance(t, torch.Tensor) and (tuple(t.shape) == shp or (name == "w2" and tuple(t.shape) == shp[1:]))
+                if not ok:
+                    raise ValueError(f"goal_mlp must be 8 -> 16 -> 1: {name} must be {shp}")
+            flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for t, _, _ in parts])
+        self.flat = _contig(flat.detach(), torch.float32, "goal_mlp weights")
+        if tuple(self.flat.shape) != (GOAL_MLP_PARAMS,):
+            raise ValueError(f"goal_mlp weights must be ({GOAL_MLP_PARAMS},) floats")
+
+    @property
+    def w1(self):
+        return self.flat[:128].view(GOAL_MLP_HIDDEN, GOAL_MLP_FEATURES)
+
+    @property
+    def b1(self):
+        return self.flat[128:144]
+
+    @property
+    def w2(self):
+        return self.flat[144:160]
+
+    @property
+    def b2(self):
+        return self.flat[160:161]
+
+
+def goal_time_scale(x_static) -> float:
+    """``time_scale`` of the goal-conditioned head: the mean FREE_FLOW over the roads of ``x_static`` (the (N, 7) static
+    columns, or any (..., N, >= 3) tensor whose column 2 is FREE_FLOW: the first environment speaks for all), computed in
+    float64 and rounded to fp32. Must be finite and > 0."""
+    t = x_static
+    while t.dim() > 2:
+        t = t[0]
+    if t.dim() != 2 or t.size(1) < 3 or t.size(0) < 1:
+        raise ValueError("x_static must be (N, >= 3) with FREE_FLOW in column 2")
+    s = float(torch.tensor(float(t[:, 2].detach().to("cpu", torch.float64).mean()), dtype=torch.float32))
+    if not (0.0 < s < float("inf")):
+        raise ValueError(f"the mean FREE_FLOW must be finite and > 0, got {s}")
+    return s
+
+
+def _goal_args(plan: Plan, table, time_scale, dest_slot):
+    """-> (the table's C arguments ``table, table_cols, dest_slot``, the fp32 ``time_scale``); the shapes as
+    :func:`_prior_args`."""
+    _contig(table, torch.float32, "prior_table")
+    N = plan.num_nodes
+    s = float(time_scale)
+    if not (0.0 < s < float("inf")):
+        raise ValueError("time_scale must be finite and > 0")
+    if dest_slot is None:
+        if tuple(table.shape) != (N, N):
+            raise ValueError(f"prior_table must be the ({N}, {N}) all-pairs distance table of the plan's graph")
+        return (table.data_ptr(), N, None), s
+    _contig(dest_slot, torch.int32, "dest_slot")
+    if table.dim() != 2 or table.size(0) != N or table.size(1) < 1 or tuple(dest_slot.shape) != (N,):
+        raise ValueError(f"a per-destination prior_table must be ({N}, D >= 1) with a ({N},) dest_slot, got "
+                         f"{tuple(table.shape)} and {tuple(dest_slot.shape)}")
+    return (table.data_ptr(), table.size(1), dest_slot.data_ptr()), s
+
+
+def _goal_obs(plan: Plan, obs16):
+    _contig(obs16, torch.float32, "obs16")
+    if obs16.dim() != 3 or tuple(obs16.shape[1:]) != (plan.num_nodes, 16) or obs16.size(0) < 1:
+        raise ValueError(f"obs16 must be (M >= 1, {plan.num_nodes}, 16)")
+    return obs16.size(0)
+
+
+def _goal_weights(w):
+    if not isinstance(w, GoalMlpWeights):
+        raise ValueError("weights must be ops.GoalMlpWeights")
+    return w.flat
+
+
+def policy_goal_features(plan: Plan, obs16, table, time_scale, dest_slot=None, out=None):
+    """The eight destination-relative features of every (sample, edge) from observations ``obs16`` (M, N, 16) -> (M, E, 8)
+    fp32 in original edge order (tarl_policy_goal_features; the rule: include/tarl_hip.h). ``table`` / ``dest_slot`` as
+    :func:`policy_prior_logits`."""
+    L = _lib.load()
+    targs, s = _goal_args(plan, table, time_scale, dest_slot)
+    M = _goal_obs(plan, obs16)
+    shp = (M, plan.num_edges, GOAL_MLP_FEATURES)
+    feats = out if out is not None else torch.empty(shp, dtype=torch.float32, device=obs16.device)
+    _contig(feats, torch.float32, "feats")
+    if tuple(feats.shape) != shp:
+        raise ValueError(f"feats must be {shp}")
+    _lib.check(L.tarl_policy_goal_features(plan.handle, obs16.data_ptr(), M, *targs, s, feats.data_ptr(),
+                                           _lib.current_stream()))
+    return feats
+
+
+def policy_goal_mlp(plan: Plan, obs16, w: GoalMlpWeights, table, time_scale, dest_slot=None, out=None):
+    """obs16 (M, N, 16) -> logits (M, E) of the goal-conditioned head (tarl_policy_goal_mlp_fwd); an unreachable edge
+    carries exactly -1e20."""
+    L = _lib.load()
+    targs, s = _goal_args(plan, table, time_scale, dest_slot)
+    flat = _goal_weights(w)
+    M = _goal_obs(plan, obs16)
+    logits = out if out is not None else torch.empty((M, plan.num_edges), dtype=torch.float32, device=obs16.device)
+    _contig(logits, torch.float32, "logits")
+    if tuple(logits.shape) != (M, plan.num_edges):
+        raise ValueError(f"logits must be ({M}, {plan.num_edges})")
+    _lib.check(L.tarl_policy_goal_mlp_fwd(plan.handle, obs16.data_ptr(), M, *targs, s, flat.data_ptr(), logits.data_ptr(),
+                                          _lib.current_stream()))
+    return logits
+
+
+GOAL_MLP_BWD_BLOCK, GOAL_MLP_BWD_MAX_PARTS = 256, 1024
+
+
+def goal_mlp_bwd_scratch_floats(plan: Plan, M: int) -> int:
+    """fp32 elements of device scratch one :func:`policy_goal_mlp_bwd` call over ``M`` samples needs, from the shapes alone
+    (the rule of tarl_policy_goal_mlp_bwd_scratch_floats: 161 per partition of the (sample, edge) pairs)."""
+    M, E = int(M), plan.num_edges
+    if M < 1:
+        raise ValueError("M must be >= 1")
+    if E == 0:
+        return 0
+    tiles = -(-M * E // GOAL_MLP_BWD_BLOCK)
+    per = -(-tiles // GOAL_MLP_BWD_MAX_PARTS)
+    return -(-tiles // per) * GOAL_MLP_PARAMS
+
+
+def policy_goal_mlp_bwd(plan: Plan, obs16, w: GoalMlpWeights, table, time_scale, grad_logits, grads, dest_slot=None,
+                        scratch=None):
+    """ACCUMULATES (+=) the gradient of sum(grad_logits * logits) into ``grads``, a (161,) fp32 contiguous tensor in the
+    order of ``GoalMlpWeights.flat``. ``scratch``: an fp32 contiguous device tensor of at least
+    ``goal_mlp_bwd_scratch_floats(plan, M)`` elements (ValueError otherwise, decided from the shapes before any call;
+    allocated per call when None). Deterministic: two calls give the same bits."""
+    L = _lib.load()
+    targs, s = _goal_args(plan, table, time_scale, dest_slot)
+    flat = _goal_weights(w)
+    M = _goal_obs(plan, obs16)
+    gl = _contig(grad_logits, torch.float32, "grad_logits")
+    if gl.numel() != M * plan.num_edges:
+        raise ValueError("grad_logits must be (M, E)")
+    _contig(grads, torch.float32, "grads")
+    if tuple(grads.shape) != (GOAL_MLP_PARAMS,):
+        raise ValueError(f"grads must be ({GOAL_MLP_PARAMS},)")
+    need = goal_mlp_bwd_scratch_floats(plan, M)
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=obs16.device)
+    elif (not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.float32 or not scratch.is_contiguous()
+          or scratch.device != obs16.device or scratch.numel() < need):
+        raise ValueError(f"scratch must be a contiguous fp32 tensor on {obs16.device} of at least {need} elements")
+    if int(L.tarl_policy_goal_mlp_bwd_scratch_floats(plan.handle, M)) != need:
+        raise _lib.TarlError("goal_mlp_bwd_scratch_floats disagrees with the library")
+    _lib.check(L.tarl_policy_goal_mlp_bwd(plan.handle, obs16.data_ptr(), M, *targs, s, flat.data_ptr(), gl.data_ptr(),
+                                          grads.data_ptr(), scratch.data_ptr(), _lib.current_stream()))
+    return grads
+
+
+def fused_goal_mlp_logits(plan: Plan, fs, x, Nmax, agent_features, w: GoalMlpWeights, table, time_scale, dest_slot=None,
+                          out=None):
+    """The same logits from the packed state of the fused engine: (B, E), no observation materialised
+    (tarl_fused_goal_mlp_logits; bit-identical to :func:`policy_goal_mlp` on :func:`fused_obs16` of that state)."""
+    L = _lib.load()
+    targs, s = _goal_args(plan, table, time_scale, dest_slot)
+    flat = _goal_weights(w)
+    B, N, bs, ldx = _state(x, Nmax)
+    A, abs_ = _agents(agent_features, B)
+    logits = out if out is not None else torch.empty((B, plan.num_edges), dtype=torch.float32, device=x.device)
+    _contig(logits, torch.float32, "logits")
+    if tuple(logits.shape) != (B, plan.num_edges):
+        raise ValueError(f"logits must be ({B}, {plan.num_edges})")
+    _lib.check(L.tarl_fused_goal_mlp_logits(plan.handle, fs.ref, x.data_ptr(), B, bs, ldx, Nmax, agent_features.data_ptr(), A,
+                                            abs_, *targs, s, flat.data_ptr(), logits.data_ptr(), _lib.current_stream()))
+    return logits
+
+
+def fused_rollout_goal(plan: Plan, fs: FusedState, x, agent_features, ec: EdgeConst, w: GoalMlpWeights, table, time_scale,
+                       times, *, use_cong, temperature, policy_seed, policy_counter0, seed, counter0, scratch,
+                       prev_time=None, keep=None, obs_keep=None, choice8=None, log_prob=None, reward=None, counts=None,
+                       dest_slot=None):
+    """``T = len(times)`` frames under the goal-conditioned head in one foreign call (tarl_fused_rollout_goal). Buffers as
+    :func:`fused_rollout_prior`."""
+    targs, s = _goal_args(plan, table, time_scale, dest_slot)
+    flat = _goal_weights(w)
+    _head_rollout("tarl_fused_rollout_goal", plan, fs, x, agent_features, ec, times, (*targs, s, flat.data_ptr()),
+                  use_cong=use_cong, temperature=temperature, policy_seed=policy_seed, policy_counter0=policy_counter0,
+                  seed=seed, counter0=counter0, scratch=scratch, prev_time=prev_time, keep=keep, obs_keep=obs_keep,
+                  choice8=choice8, log_prob=log_prob, reward=reward, counts=counts)
+
+
 # ---- graph-transformer head (policy_head = "graph_transformer", csrc/gt_policy.hip) ------------------------------------------
 # state-dict keys of GraphTransformerNet in the kernels' order: the trainable tensors that reach the logits, then the
 # BatchNorm running statistics (include/tarl_hip.h)

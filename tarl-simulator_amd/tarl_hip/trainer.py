@@ -70,7 +70,7 @@ class VecPPOTrainer:
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
-                 prior_free_flow=None, prior_dests=None, policy_hold=False):
+                 prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -104,6 +104,10 @@ class VecPPOTrainer:
         # "graph_transformer" = the reference's GraphTransformerNet edge output (csrc/gt_policy.hip), evaluation-mode
         # BatchNorm: ``gt_params`` maps the state-dict keys of ops.GT_PARAM_KEYS + GT_BUFFER_KEYS to the module's tensors
         # (the parameters must also be in ``extra_params``), ``gt_pe`` (N, 16) is its positional encoding.
+        # "goal_mlp" = the goal-conditioned MLP on destination-relative features (csrc/goal_mlp.hip; not in the reference):
+        # state-DEPENDENT, trainable; ``goal_mlp_params`` = [w1, b1, w2, b2] (goal_mlp.{0,2}.{weight,bias}), consecutive in
+        # ``extra_params`` so that they are ONE run of 161 floats of the flat buffer; the distances come from the prior head's
+        # arguments (``prior_table``, or ``prior_free_flow`` + ``prior_dests``), the time scale from the engine's roads.
         self.policy = policy
         self.prior_table = prior_table
         self.prior_dest_slot = None
@@ -119,11 +123,21 @@ class VecPPOTrainer:
             ids = {id(p) for p in extra_params}
             if not all(id(p) in ids for p in self.edge_mlp_params):
                 raise ValueError("edge_mlp_params must be part of extra_params (the optimiser's flat buffer)")
-        elif policy == "embedding_dijkstra":
+        elif policy in ("embedding_dijkstra", "goal_mlp"):
+            if policy == "goal_mlp":
+                gp = list(goal_mlp_params) if goal_mlp_params is not None else []
+                if engine.fs is None or [tuple(p.shape) for p in gp] != [(16, 8), (16,), (1, 16), (1,)]:
+                    raise ValueError("policy='goal_mlp' needs the fused engine and goal_mlp_params = the four tensors "
+                                     "goal_mlp.{0,2}.{weight,bias} (8 -> 16 -> 1)")
+                pos = {id(p): i for i, p in enumerate(extra_params)}
+                at = [pos.get(id(p), -9) for p in gp]
+                if at[0] < 0 or at != list(range(at[0], at[0] + 4)):
+                    raise ValueError("goal_mlp_params must be part of extra_params (the optimiser's flat buffer), in order and "
+                                     "next to each other")
             if engine.fs is not None and prior_table is None and prior_free_flow is not None and prior_dests is not None:
                 self.prior_table, self.prior_dest_slot = self._build_prior_dest(engine, prior_free_flow, *prior_dests)
             elif engine.fs is None or prior_table is None:
-                raise ValueError("policy='embedding_dijkstra' needs the fused engine and the (N, N) prior_table, or "
+                raise ValueError(f"policy={policy!r} needs the fused engine and the (N, N) prior_table, or "
                                  "prior_free_flow and prior_dests for the per-destination table")
             elif tuple(prior_table.shape) != (engine.N, engine.N):
                 raise ValueError(f"prior_table must be ({engine.N}, {engine.N})")
@@ -143,7 +157,7 @@ class VecPPOTrainer:
                                  f"takes at most {cap} samples and needs {need / 2**20:.0f} MiB of scratch "
                                  f"({free / 2**20:.0f} MiB free); use a smaller sub_batch_size")
         elif policy != "embedding":
-            raise ValueError("policy must be 'embedding', 'edge_mlp', 'embedding_dijkstra' or 'graph_transformer'")
+            raise ValueError("policy must be 'embedding', 'edge_mlp', 'embedding_dijkstra', 'graph_transformer' or 'goal_mlp'")
         self.gt_params = dict(gt_params) if gt_params is not None else None
         self.gt_pe = gt_pe
         self.value = value
@@ -160,7 +174,7 @@ class VecPPOTrainer:
             raise ValueError("policy_hold is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
                              "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
                              "between a frame's draw and its Direction launch where the rule could read that frame's state; "
-                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer)")
+                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
         self.held = torch.zeros(engine.B, dtype=torch.int32, device=engine.device) if self.policy_hold else None
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
@@ -179,6 +193,11 @@ class VecPPOTrainer:
         self.flat = FlatParams([emb_param] + self.critic_params + list(extra_params), device=engine.device)
         # replicas start identical: rank 0's initial weights win
         dist_utils.broadcast_(self.flat.flat, src=0)
+        self.goal_mlp_params = list(goal_mlp_params) if policy == "goal_mlp" else None
+        if policy == "goal_mlp":      # one run of the flat buffer, in the kernels' order; the time scale of the engine's roads
+            self._goal_off = self.flat.offsets[id(self.goal_mlp_params[0])][0]
+            assert self.flat.offsets[id(self.goal_mlp_params[3])][0] == self._goal_off + ops.GOAL_MLP_PARAMS - 1
+            self.goal_scale = ops.goal_time_scale(engine._x[0, :, 3 * engine.Nmax:])
         B, N, dev = engine.B, engine.N, engine.device
         # which rollout kernel family: "env" = one workgroup per environment, records in LDS, one launch for all frames
         # (tarl_rollout_env; env-major buffers), "frames" = four env-minor launches per frame (tarl_fused_rollout).
@@ -191,7 +210,8 @@ class VecPPOTrainer:
         if engine.fs is None:
             mode = "unfused"
         elif self.state_dep:    # per-frame policy evaluation in front of the four-launch frame
-            mode = {"edge_mlp": "frames+policy", "graph_transformer": "frames+gt"}.get(policy, "frames+prior")
+            mode = {"edge_mlp": "frames+policy", "graph_transformer": "frames+gt", "goal_mlp": "frames+goal"}.get(
+                policy, "frames+prior")
         elif mode == "auto":
             mode = "env" if (engine.env_rollout_supported and engine.B * engine.N <= 800_000) else "frames"
         elif mode == "env" and not engine.env_rollout_supported:
@@ -271,8 +291,8 @@ class VecPPOTrainer:
     def _check_gt_value(self, engine, policy, critic_params, extra_params, rollout_steps, sub_batch_size):
         """Refusals of value="graph_transformer", each naming its limit."""
         if policy == "embedding":
-            raise ValueError("value='graph_transformer' needs a state-dependent policy head (edge_mlp, embedding_dijkstra "
-                             "or graph_transformer): the embedding head's rollout builds no observation")
+            raise ValueError("value='graph_transformer' needs a state-dependent policy head (edge_mlp, embedding_dijkstra, "
+                             "graph_transformer or goal_mlp): the embedding head's rollout builds no observation")
         if engine.fs is None or self.gt_value_params is None or self.gt_value_pe is None:
             raise ValueError("value='graph_transformer' needs the fused engine, gt_value_params and the (N, 16) gt_value_pe")
         ids = {id(p) for p in list(critic_params) + list(extra_params)}
@@ -308,6 +328,9 @@ class VecPPOTrainer:
 
     def _gt(self):
         return ops.GtWeights(self.gt_params)
+
+    def _goal(self):
+        return ops.GoalMlpWeights(flat=self.flat.flat[self._goal_off:self._goal_off + ops.GOAL_MLP_PARAMS])
 
     def _gt_value(self):
         return ops.GtValueWeights(self.gt_value_params)
@@ -445,6 +468,8 @@ class VecPPOTrainer:
             times = eng.rollout_policy(n, self._edge_mlp(), precision=self.policy_precision, **logs, **kw)
         elif self.policy == "graph_transformer":
             times = eng.rollout_gt(n, self.gt_pe, self._gt(), **kw)
+        elif self.policy == "goal_mlp":
+            times = eng.rollout_goal(n, self._goal(), self.prior_table, self.goal_scale, self.prior_dest_slot, **kw)
         else:
             times = eng.rollout_prior(n, self._emb(), self.prior_table, prior_weight=self.prior_weight,
                                       dest_slot=self.prior_dest_slot, **kw)
@@ -477,6 +502,9 @@ class VecPPOTrainer:
             return ops.policy_edge_mlp(eng.plan, obs, eng.ec, self._edge_mlp())          # fp32 MFMA
         if self.policy == "graph_transformer":
             return ops.policy_gt_logits(eng.plan, obs, eng.ec, self.gt_pe, self._gt())
+        if self.policy == "goal_mlp":
+            return ops.policy_goal_mlp(eng.plan, obs, self._goal(), self.prior_table, self.goal_scale,
+                                       dest_slot=self.prior_dest_slot)
         if self.policy == "embedding_dijkstra":
             return ops.policy_prior_logits(eng.plan, obs, self._emb(), self.prior_table, self.prior_weight,
                                            dest_slot=self.prior_dest_slot)
@@ -495,6 +523,13 @@ class VecPPOTrainer:
                 self._gt_scratch = torch.empty(need, dtype=torch.float32, device=eng.device)     # once per trainer
             ops.policy_gt_bwd(eng.plan, obs, eng.ec, self.gt_pe, self._gt(), g_logits,
                               [self.flat.grad_view(self.gt_params[k]) for k in ops.GT_PARAM_KEYS], scratch=self._gt_scratch)
+        elif self.policy == "goal_mlp":
+            need = ops.goal_mlp_bwd_scratch_floats(eng.plan, obs.size(0))
+            if getattr(self, "_goal_scratch", None) is None or self._goal_scratch.numel() < need:
+                self._goal_scratch = torch.empty(need, dtype=torch.float32, device=eng.device)     # once per trainer
+            ops.policy_goal_mlp_bwd(eng.plan, obs, self._goal(), self.prior_table, self.goal_scale, g_logits,
+                                    self.flat.grad[self._goal_off:self._goal_off + ops.GOAL_MLP_PARAMS],
+                                    dest_slot=self.prior_dest_slot, scratch=self._goal_scratch)
         else:       # the prior has no parameters: the embedding receives the logits' gradient as is
             g_emb = ops.policy_edge_logits_bwd(eng.plan, obs, g_logits, self.emb_param.numel())
             self.flat.grad_view(self.emb_param).add_(g_emb.view_as(self.emb_param))
