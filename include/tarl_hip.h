@@ -413,7 +413,9 @@ typedef struct tarl_fused {
    * per environment by it (a frame of dt seconds brings ~due_rate * dt candidates). Never changes a result. */
   float due_rate;
   /* the policy hold rule of the state-dependent rollouts (tarl_fused_set_policy_hold below; 0 = off, the default — the word
-   * was reserved and zero until the rule existed, so a caller that never heard of it has it off) */
+   * was reserved and zero until the rule existed, so a caller that never heard of it has it off). Bit 0 is that rule; bit 1
+   * (TARL_DEPARTURE_ROUTER) is the first-hop routing of tarl_fused_set_departure_router, whose arguments the library keeps
+   * beside the handle: the struct itself does not grow. Each setter leaves the other's bit alone. */
   int32_t policy_hold;
   /* device scratch of tarl_fused_bufs_bytes() bytes, 16-byte aligned (required by the frame / rollout entry points): the
    * library keeps a device-resident copy of this table of pointers there (written by a one-thread launch at the head of every
@@ -1115,6 +1117,46 @@ int tarl_fused_hold_policy_actions(const tarl_plan* plan, const tarl_fused* f, i
                                    const float* agent_features, int64_t num_agents, int64_t a_bstride, uint8_t* choice8,
                                    int32_t* held, tarl_stream stream);
 int tarl_fused_set_policy_hold(tarl_fused* f, int on, int32_t* held);
+
+/* ---- first-hop routing: empty origin roads select for their departing agent ---------------------------------------
+ * NOT reference semantics, off by default. The insert rule (Agents.insert_agent_into_network, src/agents/base.py:247-331) puts
+ * a departing agent onto SELECTED_ROAD[origin]; every writer of that value decides for the row's HEAD agent and an empty row
+ * reads the dummy agent 0, so the first hop of every trip heads for agent 0's destination. The rule, per environment b in
+ * the frame whose clock is t, after the head (and the hold launch) has written SELECTED_ROAD and before Direction:
+ *   agent a is READY as the insert has it: a_status == 0 && a_dep <= t (every row of the table, agent 0 included);
+ *   pend(u) = the SMALLEST ready agent id with ORIGIN == u, -1 where there is none (the first one the insert admits);
+ *   road u is ROUTED when its FIFO count (count bits of tarl_fused.hdp; a DIRTY empty row is empty) is 0 and pend(u) >= 0. A
+ *   non-empty row keeps its head's choice. Every row that is not routed keeps sel8 / sel byte for byte.
+ * tarl_fused_pending_departures: pend int32 [N][B], all N * B entries written. With the departure window (a_order, a_win,
+ *   cur_lo, a_dep_sorted) the scan starts at cur_lo[b] and stops at the first entry that is not due; without a_order every
+ *   agent is looked at. Both give the same table; integer atomics only, the result does not depend on scheduling. Reads the
+ *   agent arrays alone: neither the cursor nor a_ins is touched. num_agents: the A of the handle's agent arrays, which the
+ *   handle does not carry.
+ * tarl_fused_route_departures: the TABLE lookup for every routed row, with p = pend(u) as the head: the chain of
+ *   tarl_fused_select_next_hop_hold (d = a_dest[b][p] outside [0, N), slot = dest_slot[d] outside [0, num_dests): untouched;
+ *   nh = next_hop[b or 0][slot][u]; nh == d -> u, the hold rule on integers), except that an unreachable destination
+ *   (nh < 0) leaves the row untouched. Written as the select kernels write: the rank byte, sel where the code is 0x7F,
+ *   choice8 (optional) uint8 [B][N] = the rows' bytes after the call, routed (optional) int32 [B] += the rows written.
+ * tarl_fused_route_departures_plan: the same kernel with the PLAN lookup of tarl_fused_select_route (len check, the
+ *   smallest j with r[j] == u, the destination row -> u, r[j + 1] == r[len - 1] -> u; no route or off the route: untouched).
+ * tarl_fused_set_departure_router: the switch for the T-frame rollouts of the state-dependent heads. With on = 1 their shared
+ *   loop queues tarl_fused_pending_departures into pend (int32 [N][B], caller-owned) and the table lookup (WITHOUT choice8,
+ *   with routed: int32 [B], optional, caller-zeroed) in every frame, after the optional hold launch, with that frame's clock.
+ *   With on = 0 (every pointer NULL) the loop queues exactly what it queued before. The tables must outlive the switch.
+ * Host checks, all before any HIP call: null arguments, tarl_fused_select_next_hop_dest's on plan, handle, B and Nmax,
+ *   num_agents outside [1, 2^24], a non-finite t, num_dests < 1, 0 < nh_bstride < num_dests * N or r_bstride < num_agents *
+ *   max_hops (tables overlap), max_hops outside [1, 2^20], on outside {0, 1}, on without a table, a table without on. */
+#define TARL_DEPARTURE_ROUTER 2
+int tarl_fused_pending_departures(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                                  float t, int32_t* pend, tarl_stream stream);
+int tarl_fused_route_departures(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                                const int32_t* pend, const int32_t* dest_slot, const int32_t* next_hop, int64_t nh_bstride,
+                                int64_t num_dests, uint8_t* choice8, int32_t* routed, tarl_stream stream);
+int tarl_fused_route_departures_plan(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents,
+                                     const int32_t* pend, const int32_t* routes, const int32_t* route_len, int64_t r_bstride,
+                                     int64_t max_hops, uint8_t* choice8, int32_t* routed, tarl_stream stream);
+int tarl_fused_set_departure_router(tarl_fused* f, int on, const int32_t* dest_slot, const int32_t* next_hop,
+                                    int64_t nh_bstride, int64_t num_dests, int32_t* pend, int32_t* routed);
 
 /* ---- behaviour cloning of the shortest-path router ----------------------------------------------------------------
  * NOT in the reference: a warm start for the learned heads. TARL_ABI_VERSION is unchanged: nothing existing moved.

@@ -2,6 +2,8 @@
 // (tarl_fused_rollout) and T frames with a state-dependent policy head (tarl_rollout_head: the one loop under
 // tarl_fused_rollout_policy here, tarl_fused_rollout_prior[_dest] in prior.hip and tarl_fused_rollout_gt in gt_policy.hip),
 // written against the launch functions of the kernel files. (Design: fused_frame.h.)
+#include <cmath>
+
 #include "fused_frame.h"
 #include "rollout_heads.h"
 
@@ -170,7 +172,8 @@ extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, in
 // ---- T frames with a STATE-DEPENDENT policy head in one foreign call (rollout_heads.h) ----------------------------------------
 // Nothing of GraphDistribution can be hoisted: per frame the head's logits from the packed state (`frame`) -> action +
 // log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> [with tarl_fused_set_policy_hold: the hold rule on SELECTED_ROAD,
-// policy_hold.hip; the action buffer keeps the draw] -> Direction -> rows -> insert, queued back to back by one host loop
+// policy_hold.hip; the action buffer keeps the draw] -> [with tarl_fused_set_departure_router: the first hop of the agents
+// about to depart from an empty road, departures.hip] -> Direction -> rows -> insert, queued back to back by one host loop
 // in C (the same entry points a caller could queue himself, minus a foreign-call round trip per launch and the checks per
 // frame). The arguments are checked and the pointer table is uploaded once per call; the count bytes are the frame
 // kernels' own (FrameOut::counts8), the event byte is stored in the last frame only and the insert is packed
@@ -200,6 +203,13 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
   if (rc) return rc;
   const PlanOut P{plan->out_ptr, plan->out_dst};
   const int epw_packed = tarl_insert_envs_per_wave(f, a.A, B, T, a.times_host);
+  const bool route_departures = (f->policy_hold & TARL_DEPARTURE_ROUTER) != 0;   // tarl_fused_set_departure_router
+  DepartureRouter router{};
+  if (route_departures) {
+    rc = tarl_departure_router_of(plan, f, &router);
+    if (rc) return rc;
+    for (int64_t t = 0; t < T; ++t) TARL_REQUIRE(std::isfinite(a.times_host[t]), "non-finite time");
+  }
   for (int64_t t = 0; t < T; ++t) {
     const bool keep_t = a.keep_ptr_host && a.keep_ptr_host[t + 1] > a.keep_ptr_host[t];
     const int64_t lo = keep_t ? a.keep_ptr_host[t] : 0, n = keep_t ? a.keep_ptr_host[t + 1] - lo : 0;
@@ -210,11 +220,15 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
                                    a.choice8 ? a.choice8 + t * NB : nullptr, f->sel8, a.log_prob ? a.log_prob + t * B : nullptr,
                                    f->env_base, a.stream);
     if (rc) return rc;
-    if (f->policy_hold) {   // tarl_fused_set_policy_hold: the hold rule on f->sel8; a.choice8 keeps the draw (policy_hold.hip)
+    if (f->policy_hold & 1) {   // tarl_fused_set_policy_hold: the hold rule on f->sel8; a.choice8 keeps the draw (policy_hold.hip)
       rc = tarl_launch_policy_hold(s, plan, f, B, a.agent_features, a.A, a.a_bstride, nullptr, f->policy_held);
       if (rc) return rc;
     }
     const float time = a.times_host[t];
+    if (route_departures) {     // empty origin rows select for their departing agent (departures.hip); a.choice8 keeps the draw
+      rc = tarl_launch_departure_router(s, plan, f, B, a.A, time, router);
+      if (rc) return rc;
+    }
     const FrameOut out = rollout_frame_out(t, T, N, B, a.counts, a.metrics_envs, a.dtt_node, a.events, a.leg);
     rc = tarl_launch_direction(grid_d, threads, s, plan, f, a.edge_attr, a.log_edge_attr, (const uint8_t*)f->sel8, nullptr,
                                nullptr, a.log_eps, time, t > 0 ? a.times_host[t - 1] : a.prev_time, a.seed,

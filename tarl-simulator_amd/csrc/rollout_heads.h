@@ -43,13 +43,26 @@ struct HeadRollout {
 typedef int (*head_frame_fn)(const HeadRollout& a, void* ctx, int64_t t, const int32_t* env, const int32_t* slot, int64_t n);
 
 // Checks the common arguments once, then queues per frame: head -> tarl_graphdist_rollout_at (action bytes, log-prob,
-// SELECTED_ROAD) -> [the hold rule, where tarl_fused.policy_hold is set] -> Direction -> rows -> insert, the count bytes
-// written by the frame kernels.
+// SELECTED_ROAD) -> [the hold rule, where bit 0 of tarl_fused.policy_hold is set] -> [the pending table and the first-hop
+// route launch, where its bit TARL_DEPARTURE_ROUTER is set] -> Direction -> rows -> insert, the count bytes written by the
+// frame kernels.
 int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx);
 
 // policy_hold.hip: the launch of k_fused_hold_policy_actions alone (handle and agent table checked by the caller)
 int tarl_launch_policy_hold(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, const float* agent_features,
                             int64_t A, int64_t a_bstride, uint8_t* choice8, int32_t* held);
+
+// departures.hip: first-hop routing inside the loop (tarl_fused_set_departure_router; bit TARL_DEPARTURE_ROUTER of
+// tarl_fused.policy_hold). tarl_departure_router_of: what the setter registered for the handle, checked against the plan;
+// tarl_launch_departure_router: the pending table and the table-lookup route launch of one frame whose clock is t.
+struct DepartureRouter {
+  const int32_t *dest_slot, *next_hop;
+  int64_t nh_bstride, D;
+  int32_t *pend, *routed;
+};
+int tarl_departure_router_of(const tarl_plan* plan, const tarl_fused* f, DepartureRouter* r);
+int tarl_launch_departure_router(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t A, float t,
+                                 const DepartureRouter& r);
 
 // the kept rows straight from the packed state (a head whose logits do not leave fp32 observations behind)
 static inline int tarl_head_keep_rows(const HeadRollout& a, const int32_t* env, const int32_t* slot, int64_t n) {

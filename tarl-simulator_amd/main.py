@@ -113,7 +113,23 @@ OPTIONS = (
                                 "vectorised evaluation only (one more line in its block, `policy_hold` and `held` in "
                                 "eval_envs.json); train: acts on vectorised training and its eval_vec runs (train/held and "
                                 "eval_vec/held in train_log.jsonl), refused with --policy-head embedding, whose rollout "
-                                "kernels draw every frame's action ahead of the frames")),
+                                "kernels draw every frame's action ahead of the frames. An agent inserted directly onto "
+                                "its destination road: see --route-departures")),
+    ("--route-departures", dict(action="store_true",
+                                help="first-hop routing (an environment-side rule, DESIGN 4.23; not in the reference, off by "
+                                     "default): an EMPTY road with an agent ready to depart from it selects for that agent (the "
+                                     "smallest ready id of the origin) instead of for the dummy head agent 0, so the first hop "
+                                     "of a trip heads for the traveller's own destination; a non-empty origin road keeps its "
+                                     "head's choice. The routers look the hop up in their own tables, the replanning days in "
+                                     "the plan, a policy head in a free-flow table built once; a policy's draw, log-prob and "
+                                     "the PPO update are unchanged. eval: needs --eval-envs, --dijkstra-envs (routers hold / "
+                                     "free_flow) or --replan-days and acts on the policy's vectorised run, on the baselines "
+                                     "dijkstra_hold / free_flow and on the replanning days (one more line in each block, "
+                                     "`route_departures` and `departures_routed` in the JSON files); refused with "
+                                     "--eval-baseline dijkstra and --dijkstra-router reference (use dijkstra_hold / hold). "
+                                     "train: acts on vectorised training and its eval_vec runs (train/departures_routed and "
+                                     "eval_vec/departures_routed in train_log.jsonl), refused with --policy-head embedding. "
+                                     "--pretrain-bc runs its own engine without the rule")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "

@@ -98,9 +98,9 @@ def _eval_engine(eval_env, eval_envs, seed, agent_features=None):
                      device=g.x.device, timestep=sim.timestep, seed=seed + 104729, fused=True)
 
 
-def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_hold=False):
+def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_hold=False, route_departures=False):
     """The K-environment evaluator of ``ppo_train(eval_envs=K)``; ``policy_hold``: with the hold rule on the policy's action
-    (DESIGN 4.20)."""
+    (DESIGN 4.20); ``route_departures``: with the first-hop rule on empty origin roads."""
     from tarl_hip.evaluator import VecEvaluator
     engine = _eval_engine(eval_env, eval_envs, seed)
     dests = None
@@ -108,6 +108,8 @@ def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_ho
             policy_net.resolve_prior_method() != "all_pairs":
         dests = destination_set(engine.agents, engine.N)
     kw = {"policy_hold": True} if policy_hold else {}
+    if route_departures:
+        kw["route_departures"] = True
     return VecEvaluator.from_policy_net(engine, policy_net, prior_dests=dests, temperature=temperature, **kw)
 
 
@@ -147,7 +149,7 @@ def vec_eval_record(prefix, res):
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
-              eval_baseline="none", policy_hold=False, pretrain_bc=None):
+              eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False):
     """``pretrain_bc`` (not in the reference; None = off): a dict {iterations, expert, driver, envs, frames,
     samples, epochs, batch, lr} — that many behaviour-cloning iterations (tarl_hip.imitation.BCTrainer) run before the first
     PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``."""
@@ -201,7 +203,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             prior_weight=getattr(policy_net, "prior_weight", 1.0), **prior_kw,
                             gt_params=policy_net.transformer.kernel_tensors() if head == "graph_transformer" else None,
                             gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw,
-                            **({"policy_hold": True} if policy_hold else {}))
+                            **({"policy_hold": True} if policy_hold else {}),
+                            **({"route_departures": True} if route_departures else {}))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)
@@ -217,7 +220,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     if int(eval_envs) < 0:
         raise ValueError("eval_envs must be >= 0")
     # rank 0 alone evaluates (as it alone logs); the evaluator enters no collective
-    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature, policy_hold)
+    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature, policy_hold, route_departures)
                 if eval_envs and eval_env is not None and log is not None else None)
     ppo_train.last_vec_eval = vec_eval
     if eval_baseline not in EVAL_BASELINE_NAMES:
@@ -251,6 +254,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                    "iter_seconds": time.perf_counter() - t0}
             if policy_hold:               # rows the hold rule rewrote in this iteration's frames, per environment
                 rec["train/held"] = float(trainer.held.sum()) / engine.B
+            if route_departures:          # empty origin rows the first-hop rule wrote in this iteration's frames, per environment
+                rec["train/departures_routed"] = float(trainer.departures_routed.sum()) / engine.B
             if bool(done.any()):
                 rec["transport/avg_travel_time"] = float((ag0[done, 3] - ag0[done, 2]).mean())
         # periodic evaluation (src/rl/ppo_trainer.py:147-151): MODE rollout, optionally a sampled one, on eval_env
@@ -270,13 +275,16 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                     rec.update(vec_eval_record(prefix, res))
                     if policy_hold and res.held is not None:
                         rec[f"{prefix}/held"] = float(res.held.mean())
+                    if route_departures and res.departures_routed is not None:
+                        rec[f"{prefix}/departures_routed"] = float(res.departures_routed.mean())
                     ppo_train.last_eval[prefix] = res
                 if eval_baseline != "none":
                     from tarl_hip.evaluator import EVAL_BASELINES, VecEvaluator, paired_report, paired_scalars
                     if baseline_res is None:      # its engine and tables are released once the numbers are cached
                         b_head, b_kw = EVAL_BASELINES[eval_baseline]
                         baseline_res = VecEvaluator(_eval_engine(eval_env, eval_envs, seed, baseline_agents),
-                                                    b_head, **b_kw).run(n_eval)
+                                                    b_head, **b_kw,
+                                                    **({"route_departures": True} if route_departures else {})).run(n_eval)
                     rec.update(vec_eval_record("eval_vec_baseline", baseline_res))
                     rep = paired_report(ppo_train.last_eval["eval_vec"], baseline_res)
                     rec.update({f"eval_vec_paired/{k}": v for k, v in paired_scalars(rep).items()})

@@ -40,6 +40,8 @@ class RunnerArgs:
     #                                "dijkstra_hold": the router that holds one road short and delivers; "free_flow": that one on static tables
     policy_hold: bool = False      # mpnn / mpnn+ppo: the hold rule on the policy's action in the vectorised
     #                                evaluation (eval: needs eval_envs) and in vectorised training (not policy_head "embedding")
+    route_departures: bool = False # the first-hop rule on empty origin roads: eval with eval_envs, dijkstra_envs
+    #                                (routers hold / free_flow) or replan_days; train with the state-dependent heads
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
@@ -102,6 +104,23 @@ class RunnerArgs:
             raise ValueError(f"dijkstra_router must be one of {DIJKSTRA_ROUTER_NAMES}, got {self.dijkstra_router!r}")
         if self.dijkstra_router != "reference" and not self.dijkstra_envs:
             raise ValueError("dijkstra_router selects the router of the vectorised dijkstra evaluation: it needs dijkstra_envs > 0")
+        if self.route_departures:
+            if self.mode == "eval" and not (self.eval_envs or self.dijkstra_envs or self.replan_days):
+                raise ValueError("route_departures acts in the vectorised evaluation: in mode 'eval' it needs eval_envs > 0, "
+                                 "dijkstra_envs > 0 (dijkstra_router hold or free_flow) or replan_days > 0 (the "
+                                 "single-environment, reference-shaped pass is not changed)")
+            if self.eval_baseline == "dijkstra":
+                raise ValueError("route_departures leaves the reference-order router as the reference has it: use "
+                                 "eval_baseline dijkstra_hold or free_flow")
+            if self.dijkstra_envs and self.dijkstra_router == "reference":
+                raise ValueError("route_departures leaves the reference-order router as the reference has it: use "
+                                 "dijkstra_router hold or free_flow")
+            if self.mode == "train" and self.algo not in ("mpnn", "mpnn+ppo"):
+                raise ValueError("route_departures in mode 'train' acts on vectorised training: it needs algo mpnn or mpnn+ppo")
+            if self.mode == "train" and self.policy_head == "embedding":
+                raise ValueError("route_departures cannot train policy_head 'embedding': its rollout kernels draw the actions "
+                                 "of all frames ahead of the frames, so the rule has no frame state to read; use a "
+                                 "state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer, goal_mlp)")
         if self.eval_link_counts and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_link_counts counts per-road pops and withdrawals in the vectorised evaluation: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
@@ -374,7 +393,8 @@ class Runner:
                   checkpoint_path=(out / "policy.pt") if self.rank == 0 else None,
                   log_dir=str(out) if self.rank == 0 else None, eval_env=eval_env, eval_interval=1,
                   num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled,
-                  eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}), **bc_kw)
+                  eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}),
+                  **({"route_departures": True} if a.route_departures else {}), **bc_kw)
 
     def eval(self):
         a = self.args
@@ -537,7 +557,7 @@ class Runner:
                                                                     "link_bin_seconds")}
         engine = self._eval_engine(sim, self._replan_population, a.replan_envs)
         rp = Replanner(engine, days=a.replan_days, fraction=a.replan_fraction, max_hops=a.replan_max_hops,
-                       link_bin_seconds=a.eval_link_bin, seed=a.seed, **kw)
+                       link_bin_seconds=a.eval_link_bin, seed=a.seed, **self._departures_kw(engine), **kw)
         result = rp.run(frames)
         rep = replan_report(result)
         print(f"\n=== Replanning ({a.replan_days} days, {a.replan_envs} environments) ===")
@@ -555,6 +575,7 @@ class Runner:
         if last is not None:
             self._print_block(f"Vectorised evaluation ({last.envs} environments, routes, last day)", last)
             doc["routes"] = last.to_dict()
+            self._departures_output(doc["routes"], last)
             rows = [dict(kind="routes", **r) for r in last.rows()]
             self._reports_output(doc, last, None, out_dir, "replan")
             mode = (vectorised or {}).get("mode")
@@ -571,6 +592,29 @@ class Runner:
             w.writerows(rows)
         return out
 
+    def _departures_kw(self, engine):
+        """--route-departures for an evaluator on ``engine``: the keyword, after the one refusal that needs the graph."""
+        if not self.args.route_departures:
+            return {}
+        if engine.fs is None:
+            raise ValueError("route_departures rewrites the packed state's SELECTED_ROAD bytes: this graph cannot be held by "
+                             "the packed path (Nmax <= 127, out-degree <= 126, no parallel edges); run without the flag")
+        return {"route_departures": True}
+
+    def _departures_output(self, doc, res):
+        """One more line in the block just printed, and ``route_departures`` / ``departures_routed`` in its JSON entry."""
+        if not self.args.route_departures:
+            return
+        from tarl_hip.evaluator import aggregate
+        doc["route_departures"] = True
+        if res.departures_routed is None:       # (a domain exit: no statistics)
+            print(f"{'departures routed:':22} ran with the first-hop rule (DESIGN 4.23)")
+            return
+        g = aggregate([int(v) for v in res.departures_routed])
+        doc["departures_routed"] = [int(v) for v in res.departures_routed]
+        print(f"{'departures routed:':22} {g['mean']:.1f}" + (f" \u00b1 {g['se']:.1f} (se)" if g.get("se") is not None else "")
+              + " empty origin roads per environment selected for their departing agent (DESIGN 4.23)")
+
     def _vectorised_dijkstra(self, frames, out_dir):
         """--dijkstra-envs K: the shortest-path router on K environments of a fused engine (VecEvaluator, head "dijkstra", or
         "dijkstra_hold" with --dijkstra-router hold / free_flow:
@@ -583,10 +627,11 @@ class Runner:
         engine = self._eval_engine(self.simulator, self._dijkstra_population, self.args.dijkstra_envs)
         head, refresh = DIJKSTRA_ROUTERS[self.args.dijkstra_router]      # --dijkstra-router: reference / hold / free_flow
         res = VecEvaluator(engine, head, refresh_rate=self.agent.refresh_rate if refresh is None else refresh,
-                           **self._link_kw()).run(frames)
+                           **self._departures_kw(engine), **self._link_kw()).run(frames)
         self._print_block(f"Vectorised evaluation ({res.envs} environments, {router_label(res)})", res)
         out_dir.mkdir(parents=True, exist_ok=True)
         doc = {"mode": res.to_dict()}
+        self._departures_output(doc["mode"], res)
         self._reports_output(doc, res, None, out_dir, "dijkstra")
         with open(out_dir / "dijkstra_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
@@ -614,7 +659,7 @@ class Runner:
         if a.policy_head in ("embedding_dijkstra", "goal_mlp") and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
         ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw(),
-                                          **({"policy_hold": True} if a.policy_hold else {}))
+                                          **({"policy_hold": True} if a.policy_hold else {}), **self._departures_kw(engine))
         results = {"mode": ev.run(frames, deterministic=True), "sampled": None}
         pair = None
         if a.eval_trips and a.eval_baseline != "none" and not results["mode"].domain_exit:
@@ -638,6 +683,7 @@ class Runner:
                           f"environment {g['mean']:.1f}" + (f" \u00b1 {g['se']:.1f} (se)" if g.get("se") is not None else ""))
                 else:
                     print(f"{'policy hold:':22} ran with the hold rule on the policy's action (DESIGN 4.20)")
+            self._departures_output(doc[key], res)
             rows += [dict(kind=key, **r) for r in res.rows()]
         fields = ("kind", "env") + PER_ENV_KEYS
         if a.eval_baseline != "none":
@@ -645,7 +691,7 @@ class Runner:
             from tarl_hip.evaluator import EVAL_BASELINES, paired_lines, paired_report, router_label
             b_head, b_kw = EVAL_BASELINES[a.eval_baseline]      # dijkstra / dijkstra_hold / free_flow (hold, static tables)
             base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), b_head,
-                                **b_kw, **self._link_kw()).run(frames, trip_pair=pair)
+                                **b_kw, **self._departures_kw(engine), **self._link_kw()).run(frames, trip_pair=pair)
             rep = paired_report(results["mode"], base)
             self._print_block(f"Baseline ({router_label(base)})", base)
             print("\n=== Policy \u2212 baseline (paired) ===")
@@ -653,6 +699,7 @@ class Runner:
                 print(line)
             results["baseline"], results["paired"] = base, rep
             doc["baseline"], doc["paired"] = base.to_dict(), rep
+            self._departures_output(doc["baseline"], base)
             fields += tuple(f"baseline_{k}" for k in PER_ENV_KEYS)
             by_env = {r["env"]: r for r in base.rows()}
             for r in rows:

@@ -152,6 +152,9 @@ class EvalResult:
     turn_meta: dict | None = field(default=None, compare=False)             # first_bin, bin_seconds, edge_index, policy_prob
     # policy_hold=True (never after a domain exit): rows the hold rule rewrote, summed over the frames, DESIGN 4.20
     held: np.ndarray | None = field(default=None, compare=False)            # (K,) int64
+    # route_departures=True (never after a domain exit): empty origin rows the first-hop rule wrote, summed over the frames,
+    # DESIGN 4.23
+    departures_routed: np.ndarray | None = field(default=None, compare=False)       # (K,) int64
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -336,7 +339,7 @@ class VecEvaluator:
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
                  dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True, policy_hold=False,
-                 goal_mlp=None, goal_scale=None):
+                 goal_mlp=None, goal_scale=None, route_departures=False):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -390,7 +393,16 @@ class VecEvaluator:
         choice; ``EvalResult.held`` counts the held rows per environment. Unlike the routers' rule an empty row is never
         touched. The ``"embedding"`` head then takes the per-frame path of the state-dependent heads: its logits are computed
         once and broadcast, the action is drawn per frame (``ops.graphdist_mode_rollout`` / ``ops.graphdist_rollout``), then
-        the hold launch and ``frame_fused(skip_choice=True)``. Off, every head runs as it always did."""
+        the hold launch and ``frame_fused(skip_choice=True)``. Off, every head runs as it always did.
+        ``route_departures`` (an environment-side rule, NOT in the reference; every head but ``"dijkstra"``):
+        after the head (and the hold launch) has written a frame's action, every EMPTY road with an agent ready to depart
+        from it selects for that agent — the smallest ready id of the origin — instead of for the dummy head agent 0
+        (``ops.fused_pending_departures`` + ``ops.fused_route_departures``). ``"dijkstra_hold"`` looks the first hop up in
+        its own tables, ``"routes"`` in the plan (its fallback's byte stays where the plan has nothing), a policy head in
+        a free-flow per-destination table built once at frame 0 (``baseline_dests`` as for the routers). A non-empty
+        origin road keeps its head's choice. ``actions`` stays the head's own choice; ``EvalResult.departures_routed``
+        counts the rows written per environment. The ``"embedding"`` head takes its per-frame path, as under
+        ``policy_hold``."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -414,6 +426,9 @@ class VecEvaluator:
         if policy_hold and head in ROUTER_HEADS + PLAN_HEADS:
             raise ValueError(f"policy_hold is the hold rule for POLICY heads: head {head!r} has its own rule "
                              "('dijkstra_hold' and 'routes' hold one road short of the destination themselves)")
+        if route_departures and head == "dijkstra":
+            raise ValueError("route_departures is not for head 'dijkstra': the reference-order router stays the reference's "
+                             "(use 'dijkstra_hold', or its free-flow form with refresh_rate=0)")
         if int(poll_frames) < 1:
             raise ValueError("poll_frames must be >= 1")
         if int(refresh_rate) < (0 if head == "dijkstra_hold" else 1):
@@ -427,6 +442,8 @@ class VecEvaluator:
         self.bin_width, self.num_bins, self.poll_frames = float(bin_width), int(num_bins), int(poll_frames)
         self.keep_actions = bool(keep_actions)
         self.policy_hold = bool(policy_hold)
+        self.route_departures = bool(route_departures)
+        self._per_frame_draw = self.policy_hold or self.route_departures     # "embedding": drawn per frame, as the other heads
         self.refresh_rate = int(refresh_rate)
         K, N, E, dev = engine.B, engine.N, engine.E, engine.device
         plan = engine.plan
@@ -494,10 +511,16 @@ class VecEvaluator:
         self.reward = self.actions = self._flag_host = None
         if self.policy_hold:
             self.held = torch.zeros(K, dtype=torch.int32, device=dev)       # rows held, per environment, in this run
+        if self.route_departures:
+            self.pend = torch.empty((N, K), dtype=torch.int32, device=dev)  # smallest ready agent id per origin road, or -1
+            self.routed = torch.zeros(K, dtype=torch.int32, device=dev)     # rows routed, per environment, in this run
+            if head not in ROUTER_HEADS + PLAN_HEADS:   # a policy head: one free-flow table, built at frame 0 as 'free_flow' builds its own
+                self.dep_dests, self.dep_slot, self.dep_weights, self.dep_table, self.dep_scratch = \
+                    router_buffers(engine, baseline_dests, 1)
         if head == "embedding":
             self.mode8 = torch.zeros((1, N), dtype=torch.uint8, device=dev)
             self.mode_lp = torch.zeros(1, dtype=torch.float32, device=dev)
-            if self.policy_hold:        # the per-frame path: the logits of every environment, and the sampler's scratch
+            if self._per_frame_draw:    # the per-frame path: the logits of every environment, and the sampler's scratch
                 self.logits = torch.empty((K, E), dtype=torch.float32, device=dev)
                 need = int(_lib.load().tarl_graphdist_rollout_scratch_bytes(plan.handle, K))
                 self.dist_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
@@ -626,10 +649,12 @@ class VecEvaluator:
         from its own tables."""
         if self.policy_hold:
             self.held.zero_()
+        if self.route_departures:
+            self.routed.zero_()
         if self.head != "embedding":
             return      # (the baseline builds its tables at frame 0: 0 % refresh_rate == 0)
         eng = self.eng
-        if self.policy_hold:            # drawn per frame, so that the hold rule sees every frame's state: logits once, broadcast
+        if self._per_frame_draw:        # drawn per frame, so that the rules see every frame's state: logits once, broadcast
             logits = ops.policy_edge_logits(eng.plan, eng.static_node_features[0], self.emb).view(1, -1)
             self.logits.copy_(logits.expand_as(self.logits))
             return
@@ -664,6 +689,22 @@ class VecEvaluator:
             self.turn_sel[jt].copy_(eng.fs.sel8)        # the SELECTED_ROAD bytes this frame ran with
         return done
 
+    def _route_departures(self, t):
+        """The first-hop rule of DESIGN 4.23 on the bytes the head has just written: the pending table of this frame's clock,
+        then the route launch with the head's own lookup. ``rec`` keeps the head's choice."""
+        eng = self.eng
+        ops.fused_pending_departures(eng.plan, eng.fs, float(eng.time), out=self.pend)
+        if self.head in PLAN_HEADS:
+            ops.fused_route_departures_plan(eng.plan, eng.fs, self.pend, self.routes, self.route_len, routed=self.routed)
+        elif self.head in ROUTER_HEADS:
+            ops.fused_route_departures(eng.plan, eng.fs, self.pend, self.dest_slot, self.table, routed=self.routed)
+        else:
+            if t == 0:                  # after the reset every count is 0: free-flow times, the same in every environment
+                ops.fused_edge_travel_time(eng.plan, eng.fs, out=self.dep_weights)
+                ops.destination_trees_batched(eng.plan, self.dep_weights[:1], self.dep_dests, out=self.dep_table,
+                                              scratch=self.dep_scratch)
+            ops.fused_route_departures(eng.plan, eng.fs, self.pend, self.dep_slot, self.dep_table[0], routed=self.routed)
+
     def _frame_head(self, t, deterministic, rec, masks):
         eng = self.eng
         if self.head in ROUTER_HEADS:   # choice -> core -> withdraw / insert -> reward: the environment's step order
@@ -672,6 +713,8 @@ class VecEvaluator:
             refresh_router_tables(eng, t, self.refresh_rate, self.weights, self.dests, self.table, self.tree_scratch)
             ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table, choice8=rec,
                                            hold=self.head == "dijkstra_hold")
+            if self.route_departures:
+                self._route_departures(t)
             return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
         if self.head in PLAN_HEADS:     # the same order, the choice read from the plan
             if eng._packed_stale:
@@ -683,8 +726,10 @@ class VecEvaluator:
                                                   scratch=self.tree_scratch)
                 ops.fused_select_next_hop_dest(eng.plan, eng.fs, self.dest_slot, self.table[0], hold=True)
             ops.fused_select_route(eng.plan, eng.fs, self.routes, self.route_len, choice8=rec)
+            if self.route_departures:
+                self._route_departures(t)
             return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
-        if self.head == "embedding" and not self.policy_hold:
+        if self.head == "embedding" and not self._per_frame_draw:
             if rec is not None and deterministic:
                 rec.copy_(self.action8)
             return eng.frame_fused(skip_choice=deterministic, reward=self.reward[t], **masks)
@@ -698,6 +743,8 @@ class VecEvaluator:
                                   scratch=self.dist_scratch)
         if self.policy_hold:            # rec keeps the policy's own choice: the rule rewrites the packed state's bytes alone
             ops.fused_hold_policy_actions(eng.plan, eng.fs, eng.agents, held=self.held)
+        if self.route_departures:
+            self._route_departures(t)
         return eng.frame_fused(skip_choice=True, reward=self.reward[t], **masks)
 
     # -- the evaluation ----------------------------------------------------------------------------------------------------
@@ -794,6 +841,8 @@ class VecEvaluator:
                             agents_without_route=int((self.route_len[..., 1:] <= 0).sum()))
         if self.policy_hold:                  # (without the flag the settings stay as they were)
             settings["policy_hold"] = True
+        if self.route_departures:
+            settings["route_departures"] = True
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):
@@ -817,6 +866,8 @@ class VecEvaluator:
             setattr(res, k, v)
         if self.policy_hold:
             res.held = self.held.cpu().numpy().astype(np.int64)
+        if self.route_departures:
+            res.departures_routed = self.routed.cpu().numpy().astype(np.int64)
         if self.link_counts:
             st = ops.link_count_stats(self.link_acc)
             res.link_counts = self.link_acc.cpu().numpy()

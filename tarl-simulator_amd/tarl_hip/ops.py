@@ -7,6 +7,7 @@ strides), mutated in place like the reference does.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -1222,6 +1223,112 @@ def fused_set_policy_hold(fs, on, held=None):
             raise ValueError(f"held must be (B,) = ({fs.B},)")
     _lib.check(_lib.load().tarl_fused_set_policy_hold(fs.ref, 1 if on else 0, _lib.ptr(held)))
     fs.policy_held = held
+
+
+# ---- first-hop routing: empty origin roads select for their departing agent (NOT reference semantics) ----------
+def _departure_args(plan: Plan, fs, pend, choice8, routed):
+    N = plan.num_nodes
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    _contig(pend, torch.int32, "pend")
+    if tuple(pend.shape) != (N, fs.B):
+        raise ValueError(f"pend must be (N, B) = ({N}, {fs.B})")
+    if choice8 is not None:
+        _contig(choice8, torch.uint8, "choice8")
+        if tuple(choice8.shape) != (fs.B, N):
+            raise ValueError(f"choice8 must be (B, N) = ({fs.B}, {N})")
+    if routed is not None:
+        _contig(routed, torch.int32, "routed")
+        if tuple(routed.shape) != (fs.B,):
+            raise ValueError(f"routed must be (B,) = ({fs.B},)")
+
+
+def _departure_table(plan: Plan, fs, dest_slot, table):
+    N = plan.num_nodes
+    _contig(dest_slot, torch.int32, "dest_slot")
+    _contig(table, torch.int32, "table")
+    if dest_slot.dim() != 1 or dest_slot.numel() != N or table.dim() not in (2, 3) or table.size(-1) != N or \
+            (table.dim() == 3 and table.size(0) != fs.B):
+        raise ValueError(f"dest_slot must be ({N},) and table (D, {N}) or ({fs.B}, D, {N}), got "
+                         f"{tuple(dest_slot.shape)} and {tuple(table.shape)}")
+    D = table.size(-2)
+    return D * N if table.dim() == 3 else 0, D
+
+
+def fused_pending_departures(plan: Plan, fs, t, out=None):
+    """-> ``pend`` (N, B) int32: per road and environment the SMALLEST id among the agents that are ready to depart from it
+    in the frame whose clock is ``t`` (waiting, DEPARTURE_TIME <= t: the insert rule's test; agent 0 counts), -1 where there
+    is none (tarl_fused_pending_departures). With the departure window the scan starts at the insert cursor; neither the
+    cursor nor any other word of ``fs`` is written. ``out``: such a tensor to write into (every entry is written)."""
+    N = plan.num_nodes
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    t = float(t)
+    if not math.isfinite(t):
+        raise ValueError(f"t must be finite, got {t}")
+    if out is None:
+        out = torch.empty((N, fs.B), dtype=torch.int32, device=fs.hdp.device)
+    _contig(out, torch.int32, "out")
+    if tuple(out.shape) != (N, fs.B):
+        raise ValueError(f"out must be (N, B) = ({N}, {fs.B})")
+    _lib.check(_lib.load().tarl_fused_pending_departures(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, t, out.data_ptr(),
+                                                         _lib.current_stream()))
+    return out
+
+
+def fused_route_departures(plan: Plan, fs, pend, dest_slot, table, choice8=None, routed=None):
+    """First-hop routing by a next-hop table (tarl_fused_route_departures): every EMPTY road u of ``fs`` with
+    ``pend[u][b] >= 0`` (:func:`fused_pending_departures`) selects the next hop towards that agent's destination —
+    :func:`fused_select_next_hop_dest` with ``hold=True`` and the pending agent as the head, except that an unreachable
+    destination (-1) leaves the row as it was. A non-empty road keeps its head's choice; every other row keeps its bytes.
+    ``table`` int32 (D, N) or (B, D, N) with ``dest_slot`` (N,). ``choice8`` (B, N) uint8 (optional): the rows' bytes after
+    the call, env-major. ``routed`` (B,) int32 (optional): += the rows written."""
+    _departure_args(plan, fs, pend, choice8, routed)
+    stride, D = _departure_table(plan, fs, dest_slot, table)
+    _lib.check(_lib.load().tarl_fused_route_departures(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, pend.data_ptr(),
+                                                       dest_slot.data_ptr(), table.data_ptr(), stride, D, _lib.ptr(choice8),
+                                                       _lib.ptr(routed), _lib.current_stream()))
+    return choice8
+
+
+def fused_route_departures_plan(plan: Plan, fs, pend, routes, route_len, choice8=None, routed=None):
+    """First-hop routing by a per-agent plan (tarl_fused_route_departures_plan): as :func:`fused_route_departures`, the
+    lookup being :func:`fused_select_route`'s with the pending agent as the head. No route, or a road off the route: the
+    row keeps its byte."""
+    _departure_args(plan, fs, pend, choice8, routed)
+    _check_dev(routes, torch.int32, "routes")
+    _check_dev(route_len, torch.int32, "route_len")
+    _contig(routes, torch.int32, "routes")
+    _contig(route_len, torch.int32, "route_len")
+    if routes.dim() not in (2, 3) or tuple(route_len.shape) != tuple(routes.shape[:-1]) or routes.size(-2) != fs.A or \
+            routes.size(-1) < 1 or (routes.dim() == 3 and routes.size(0) != fs.B):
+        raise ValueError(f"routes must be ({fs.A}, L) or ({fs.B}, {fs.A}, L) int32 and route_len the same without L, got "
+                         f"{tuple(routes.shape)} and {tuple(route_len.shape)}")
+    L = routes.size(-1)
+    _lib.check(_lib.load().tarl_fused_route_departures_plan(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, pend.data_ptr(),
+                                                            routes.data_ptr(), route_len.data_ptr(),
+                                                            fs.A * L if routes.dim() == 3 else 0, L, _lib.ptr(choice8),
+                                                            _lib.ptr(routed), _lib.current_stream()))
+    return choice8
+
+
+def fused_set_departure_router(fs, on, dest_slot=None, table=None, pend=None, routed=None, plan=None):
+    """The switch of the state-dependent T-frame rollouts (tarl_fused_set_departure_router): with ``on`` their loop queues
+    :func:`fused_pending_departures` into ``pend`` and :func:`fused_route_departures` with ``dest_slot`` / ``table`` in every
+    frame, after the optional hold launch and before Direction. The rollout's ``choice8`` keeps the policy's draw.
+    ``routed`` (B,) int32 (optional): += the rows written, per environment. The tensors are kept alive on ``fs``. Off (the
+    default; no tensors) the loop queues exactly the launches it always queued."""
+    if not on:
+        if any(v is not None for v in (dest_slot, table, pend, routed)):
+            raise ValueError("a table or a routed counter without the switch")
+        _lib.check(_lib.load().tarl_fused_set_departure_router(fs.ref, 0, None, None, 0, 0, None, None))
+        fs.departure_router = None
+        return
+    if dest_slot is None or table is None or pend is None or plan is None:
+        raise ValueError("the switch needs plan, dest_slot, table and pend")
+    _departure_args(plan, fs, pend, None, routed)
+    stride, D = _departure_table(plan, fs, dest_slot, table)
+    _lib.check(_lib.load().tarl_fused_set_departure_router(fs.ref, 1, dest_slot.data_ptr(), table.data_ptr(), stride, D,
+                                                           pend.data_ptr(), _lib.ptr(routed)))
+    fs.departure_router = (dest_slot, table, pend, routed)
 
 
 BC_IGNORE = 0xFF        # TARL_BC_IGNORE: the label byte of a row the expert says nothing about

@@ -65,12 +65,15 @@ class ReplanResult:
 
 
 class Replanner:
-    def __init__(self, engine, *, days, fraction=0.1, max_hops=None, link_bin_seconds=3600, seed=0, per_env=True, keep=False, **eval_kw):
+    def __init__(self, engine, *, days, fraction=0.1, max_hops=None, link_bin_seconds=3600, seed=0, per_env=True, keep=False,
+                 route_departures=False, **eval_kw):
         """``engine``: a fused :class:`SimEngine` with K environments that share one population. ``days`` >= 1 simulated
         days; ``fraction``: the share that may switch per day, in (0, 1], or ``"msa"``; ``max_hops``: the longest route
         stored (default min(N, 256)); ``link_bin_seconds``: the bins of the road times; ``seed``: of the switch masks.
         ``keep``: also keep, per day, clones of the plan the day ran with, of the agent tables it left and of the switch mask
         drawn after it in ``history`` (tests). ``eval_kw``: further report flags of :class:`VecEvaluator` (link_counts, trips, turns, ...) for every day's run.
+        ``route_departures``: every day's ``routes`` evaluator runs with the first-hop rule, so that an agent
+        follows its own plan on its first road too.
         The routes take 4 K A max_hops bytes twice (current and new); with the search scratch that is refused beyond half
         the free device memory."""
         if int(days) < 1:
@@ -104,7 +107,8 @@ class Replanner:
                 raise ValueError(f"{k} is the replanner's own: every day runs with occupancy and the dynamic gap over all K "
                                  f"environments, in bins of link_bin_seconds")
         self.ev = VecEvaluator(engine, "routes", routes=self._plan_of(self.cur), occupancy=True, dynamic_gap=True,
-                               link_bin_seconds=self.link_bin_seconds, **eval_kw)
+                               link_bin_seconds=self.link_bin_seconds,
+                               **({"route_departures": True} if route_departures else {}), **eval_kw)
         st = engine.static_node_features[0]
         mx, ff = st[:, 0].contiguous(), st[:, 2].contiguous()
         cc = engine.cc if engine.cc is not None else ff * (mx + 10 - st[:, 4] * ff / 3600)      # as VecEvaluator._gap_reserve

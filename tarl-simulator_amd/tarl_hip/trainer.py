@@ -70,7 +70,8 @@ class VecPPOTrainer:
                  extra_params=(), seed=0, lazy_log_prob=False, rank_offset=True, rollout=None, metrics_envs=1,
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
-                 prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None):
+                 prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None,
+                 route_departures=False):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -85,7 +86,12 @@ class VecPPOTrainer:
         ``policy_hold`` (an action shield of the ENVIRONMENT, not in the reference): in every collected frame a
         row with a non-empty FIFO whose drawn road is its head agent's destination selects itself instead, between the draw
         and the frame (ops.fused_set_policy_hold). ``collect()`` stores the draw's bytes and log-prob, so the update is
-        unchanged; ``held`` (B,) int32 counts the held rows of the last ``collect()``. State-dependent heads only."""
+        unchanged; ``held`` (B,) int32 counts the held rows of the last ``collect()``. State-dependent heads only.
+        ``route_departures`` (an environment-side rule, not in the reference): in every collected frame an EMPTY
+        road with an agent ready to depart from it selects that agent's first hop, looked up in a free-flow per-destination
+        table built once after the first reset (ops.fused_set_departure_router), after the optional hold launch. The stored
+        action and log-prob are the draw's; ``departures_routed`` (B,) int32 counts the rows written by the last
+        ``collect()``. State-dependent heads only."""
         self.eng = engine
         # policy: "embedding" = the reference's live head (logit = embedding of the target road: state-independent, its
         # distribution is tabulated once per update); "edge_mlp" = the per-edge MLP head it carries as parameters
@@ -176,6 +182,22 @@ class VecPPOTrainer:
                              "between a frame's draw and its Direction launch where the rule could read that frame's state; "
                              "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
         self.held = torch.zeros(engine.B, dtype=torch.int32, device=engine.device) if self.policy_hold else None
+        self.route_departures = bool(route_departures)
+        if self.route_departures and not self.state_dep:
+            raise ValueError("route_departures is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
+                             "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
+                             "between a frame's draw and its Direction launch where the rule could read that frame's state; "
+                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+        self.departures_routed = self._departure_router = None
+        if self.route_departures:
+            if engine.fs is None:
+                raise ops._lib.TarlError("route_departures needs the fused engine (ops.fused_path_supported): the packed state "
+                                     "cannot represent this graph and there is no fall-back")
+            from .evaluator import router_buffers
+            self.departures_routed = torch.zeros(engine.B, dtype=torch.int32, device=engine.device)
+            self._departure_router = router_buffers(engine, None, 1) + (
+                torch.empty((engine.N, engine.B), dtype=torch.int32, device=engine.device),)
+            self._departure_table_built = False
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
@@ -352,6 +374,14 @@ class VecPPOTrainer:
             if self.policy_hold:        # the shared loop of the state-dependent rollouts consults the switch per frame
                 self.held.zero_()
                 ops.fused_set_policy_hold(eng.fs, True, self.held)
+            if self.route_departures:   # and this one, after the hold launch: the first hop of the agents about to depart
+                dests, slot, weights, table, scratch, pend = self._departure_router
+                if not self._departure_table_built:     # after the reset every count is 0: free-flow times, built once
+                    ops.fused_edge_travel_time(eng.plan, eng.fs, out=weights)
+                    ops.destination_trees_batched(eng.plan, weights[:1], dests, out=table, scratch=scratch)
+                    self._departure_table_built = True
+                self.departures_routed.zero_()
+                ops.fused_set_departure_router(eng.fs, True, slot, table[0], pend, self.departures_routed, plan=eng.plan)
             if self.state_dep:
                 self._draw_minibatch_frames()
             else:
@@ -366,6 +396,8 @@ class VecPPOTrainer:
             host_times.append(float(eng.time))
             if self.policy_hold:        # off again: whoever else runs this engine gets the loop as it always was
                 ops.fused_set_policy_hold(eng.fs, False)
+            if self.route_departures:
+                ops.fused_set_departure_router(eng.fs, False)
             if self.obs_all is not None:      # frame T: the final state (an episode end at T - 1 is not followed by a reset)
                 eng.obs16(out=self.obs_all[T])
             # the device status word travels to pinned host memory behind the rollout; it is looked at when it has
