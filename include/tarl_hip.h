@@ -415,7 +415,8 @@ typedef struct tarl_fused {
   /* the policy hold rule of the state-dependent rollouts (tarl_fused_set_policy_hold below; 0 = off, the default — the word
    * was reserved and zero until the rule existed, so a caller that never heard of it has it off). Bit 0 is that rule; bit 1
    * (TARL_DEPARTURE_ROUTER) is the first-hop routing of tarl_fused_set_departure_router, whose arguments the library keeps
-   * beside the handle: the struct itself does not grow. Each setter leaves the other's bit alone. */
+   * beside the handle: the struct itself does not grow. Bit 2 (TARL_TRIP_REWARD) is the trip reward of
+   * tarl_fused_set_trip_reward, kept the same way. Each setter leaves the others' bits alone. */
   int32_t policy_hold;
   /* device scratch of tarl_fused_bufs_bytes() bytes, 16-byte aligned (required by the frame / rollout entry points): the
    * library keeps a device-resident copy of this table of pointers there (written by a one-thread launch at the head of every
@@ -1157,6 +1158,38 @@ int tarl_fused_route_departures_plan(const tarl_plan* plan, const tarl_fused* f,
                                      int64_t max_hops, uint8_t* choice8, int32_t* routed, tarl_stream stream);
 int tarl_fused_set_departure_router(tarl_fused* f, int on, const int32_t* dest_slot, const int32_t* next_hop,
                                     int64_t nh_bstride, int64_t num_dests, int32_t* pend, int32_t* routed);
+
+/* ---- the trip reward: a lost agent is no longer free ------------------------------------------------------------------
+ * NOT reference semantics, off by default. The reward the insert launch writes is -sum_rows NUMBER_OF_AGENT, the vehicles
+ * standing in FIFOs after the frame: an agent lost to the U-turn double pop is queued nowhere and costs nothing
+ * from then on, and an agent that is due but kept out by a full origin road costs nothing either. The trip reward counts the
+ * travellers who should be under way and have not arrived. Per environment b, after the frame whose clock is t has run
+ * completely (Direction, rows, withdraw, insert):
+ *   on_way(b) = #{ a in [0, A) : a_status[b][a] == 1 }
+ *   ready(b)  = #{ a in [0, A) : a_status[b][a] == 0 && a_dep[b][a] <= t }       (the insert's own test, the same fp32 compare)
+ *   reward[b] = -(float)(on_way(b) + ready(b))                                    (exact: A <= 2^24)
+ * Every row of the agent table counts, agent 0 included. With queued = -(the queue reward of the same frame):
+ *   owed = queued + lost + ready,  lost = on_way - queued.
+ * tarl_fused_trip_reward: reward fp32 [B] and parts int32 [B][2] = {on_way, ready} (optional), every element overwritten.
+ *   on_way is one pass over the B * A status bytes by 16-byte loads (the unaligned head and tail bytes of every row one by
+ *   one; nothing outside [b * A, (b + 1) * A) is read); ready is the walk of tarl_fused_pending_departures with the departure
+ *   window (from cur_lo[b] while the sorted departure is <= t) and a test of a_dep beside the status byte without a_order.
+ *   Both give the same numbers. Integer arithmetic and integer atomics only: the result does not depend on scheduling. Reads
+ *   the agent arrays alone: neither the cursor nor a_ins nor any other word of the packed state is written. num_agents: the
+ *   A of the handle's agent arrays.
+ * tarl_fused_set_trip_reward: the switch for the T-frame rollouts of the state-dependent heads (bit TARL_TRIP_REWARD of
+ *   tarl_fused.policy_hold). With on = 1 their shared loop queues tarl_fused_trip_reward in every frame after the insert
+ *   launch, on the same stream, with that frame's clock, into reward + t * B (and parts + t * B * 2 where parts, int32
+ *   [T_max][B][2], caller-owned, is given): the reward buffer of the rollout then holds the trip reward instead of the queue
+ *   reward. A rollout without a reward buffer queues nothing. With on = 0 (parts NULL) the loop queues exactly what it queued
+ *   before. Action bytes, log-probs and count bytes are the same either way.
+ * Host checks, all before any HIP call (a refused call writes nothing): null plan, handle or reward,
+ *   tarl_fused_select_next_hop_dest's on B and Nmax, num_agents outside [1, 2^24], a non-finite t, missing agent buffers,
+ *   on outside {0, 1}, parts without on. */
+#define TARL_TRIP_REWARD 4
+int tarl_fused_trip_reward(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents, float t,
+                           float* reward, int32_t* parts, tarl_stream stream);
+int tarl_fused_set_trip_reward(tarl_fused* f, int on, int32_t* parts);
 
 /* ---- behaviour cloning of the shortest-path router ----------------------------------------------------------------
  * NOT in the reference: a warm start for the learned heads. TARL_ABI_VERSION is unchanged: nothing existing moved.

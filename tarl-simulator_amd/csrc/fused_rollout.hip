@@ -173,7 +173,8 @@ extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, in
 // Nothing of GraphDistribution can be hoisted: per frame the head's logits from the packed state (`frame`) -> action +
 // log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> [with tarl_fused_set_policy_hold: the hold rule on SELECTED_ROAD,
 // policy_hold.hip; the action buffer keeps the draw] -> [with tarl_fused_set_departure_router: the first hop of the agents
-// about to depart from an empty road, departures.hip] -> Direction -> rows -> insert, queued back to back by one host loop
+// about to depart from an empty road, departures.hip] -> Direction -> rows -> insert -> [with tarl_fused_set_trip_reward: the
+// trip reward over the insert's reward, trip_reward.hip], queued back to back by one host loop
 // in C (the same entry points a caller could queue himself, minus a foreign-call round trip per launch and the checks per
 // frame). The arguments are checked and the pointer table is uploaded once per call; the count bytes are the frame
 // kernels' own (FrameOut::counts8), the event byte is stored in the last frame only and the insert is packed
@@ -210,6 +211,14 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
     if (rc) return rc;
     for (int64_t t = 0; t < T; ++t) TARL_REQUIRE(std::isfinite(a.times_host[t]), "non-finite time");
   }
+  const bool trip_reward = (f->policy_hold & TARL_TRIP_REWARD) != 0 && a.reward;     // tarl_fused_set_trip_reward
+  int32_t* trip_parts = nullptr;
+  if (trip_reward) {
+    rc = tarl_check_trip_reward(f, B, a.A);
+    if (rc) return rc;
+    for (int64_t t = 0; t < T; ++t) TARL_REQUIRE(std::isfinite(a.times_host[t]), "non-finite time");
+    trip_parts = tarl_trip_reward_parts_of(f);
+  }
   for (int64_t t = 0; t < T; ++t) {
     const bool keep_t = a.keep_ptr_host && a.keep_ptr_host[t + 1] > a.keep_ptr_host[t];
     const int64_t lo = keep_t ? a.keep_ptr_host[t] : 0, n = keep_t ? a.keep_ptr_host[t + 1] - lo : 0;
@@ -240,6 +249,10 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
                             a.a_bstride, a.use_cong, time, a.ins_scratch, nullptr, a.reward ? a.reward + t * B : nullptr, out,
                             nullptr, nullptr);
     if (rc) return rc;
+    if (trip_reward) {          // the frame is complete: the travellers owed over the insert's queue reward (trip_reward.hip)
+      rc = tarl_launch_trip_reward(s, f, B, a.A, time, a.reward + t * B, trip_parts ? trip_parts + t * B * 2 : nullptr);
+      if (rc) return rc;
+    }
   }
   return TARL_OK;
 }

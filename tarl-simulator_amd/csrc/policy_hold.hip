@@ -89,7 +89,7 @@ extern "C" int tarl_fused_set_policy_hold(tarl_fused* f, int on, int32_t* held) 
   TARL_REQUIRE(f, "null argument");
   TARL_REQUIRE(on == 0 || on == 1, "on must be 0 or 1");
   TARL_REQUIRE(on || !held, "a held counter without the switch");
-  f->policy_hold = (f->policy_hold & ~1) | on;      // (bit TARL_DEPARTURE_ROUTER belongs to tarl_fused_set_departure_router)
+  f->policy_hold = (f->policy_hold & ~1) | on;      // (the other bits belong to their own setters)
   f->policy_held = held;
   return TARL_OK;
 }

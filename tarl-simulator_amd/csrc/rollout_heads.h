@@ -45,7 +45,7 @@ typedef int (*head_frame_fn)(const HeadRollout& a, void* ctx, int64_t t, const i
 // Checks the common arguments once, then queues per frame: head -> tarl_graphdist_rollout_at (action bytes, log-prob,
 // SELECTED_ROAD) -> [the hold rule, where bit 0 of tarl_fused.policy_hold is set] -> [the pending table and the first-hop
 // route launch, where its bit TARL_DEPARTURE_ROUTER is set] -> Direction -> rows -> insert, the count bytes written by the
-// frame kernels.
+// frame kernels -> [the trip reward over the insert's reward, where its bit TARL_TRIP_REWARD is set].
 int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx);
 
 // policy_hold.hip: the launch of k_fused_hold_policy_actions alone (handle and agent table checked by the caller)
@@ -63,6 +63,13 @@ struct DepartureRouter {
 int tarl_departure_router_of(const tarl_plan* plan, const tarl_fused* f, DepartureRouter* r);
 int tarl_launch_departure_router(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t A, float t,
                                  const DepartureRouter& r);
+
+// trip_reward.hip: the trip reward inside the loop (tarl_fused_set_trip_reward; bit TARL_TRIP_REWARD of
+// tarl_fused.policy_hold). tarl_check_trip_reward: the agent buffers and sizes; tarl_trip_reward_parts_of: the parts buffer the
+// setter registered for the handle, or NULL; tarl_launch_trip_reward: the launches of one frame whose clock is t.
+int tarl_check_trip_reward(const tarl_fused* f, int64_t B, int64_t A);
+int32_t* tarl_trip_reward_parts_of(const tarl_fused* f);
+int tarl_launch_trip_reward(hipStream_t s, const tarl_fused* f, int64_t B, int64_t A, float t, float* reward, int32_t* parts);
 
 // the kept rows straight from the packed state (a head whose logits do not leave fp32 observations behind)
 static inline int tarl_head_keep_rows(const HeadRollout& a, const int32_t* env, const int32_t* slot, int64_t n) {

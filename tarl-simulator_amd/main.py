@@ -130,6 +130,17 @@ OPTIONS = (
                                      "train: acts on vectorised training and its eval_vec runs (train/departures_routed and "
                                      "eval_vec/departures_routed in train_log.jsonl), refused with --policy-head embedding. "
                                      "--pretrain-bc runs its own engine without the rule")),
+    ("--reward", dict(choices=("queue", "trip"), default="queue",
+                      help="queue (default): the reference's reward, minus the vehicles standing in FIFOs after the frame. trip "
+                           "(an environment-side rule, DESIGN 4.24; not in the reference): minus the travellers who should be "
+                           "under way and have not arrived, the agents on the way plus the waiting agents that are due, so that "
+                           "an agent lost on the way or kept out by a full origin road keeps costing until the horizon. train: "
+                           "what PPO optimises (train/reward_kind in train_log.jsonl; the eval_vec runs log "
+                           "eval_vec/trip_return*), refused with --policy-head embedding. eval: needs --eval-envs, "
+                           "--dijkstra-envs or --replan-days; computed BESIDE the queue reward for the policy run, the "
+                           "baseline and the days (one more line per block, `trip_return` in the JSON files and the "
+                           "eval_envs.csv columns, a `trip_return` difference in the paired block); every other number stays "
+                           "as it is")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "

@@ -98,9 +98,11 @@ def _eval_engine(eval_env, eval_envs, seed, agent_features=None):
                      device=g.x.device, timestep=sim.timestep, seed=seed + 104729, fused=True)
 
 
-def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_hold=False, route_departures=False):
+def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_hold=False, route_departures=False,
+                   trip_reward=False):
     """The K-environment evaluator of ``ppo_train(eval_envs=K)``; ``policy_hold``: with the hold rule on the policy's action
-    (DESIGN 4.20); ``route_departures``: with the first-hop rule on empty origin roads."""
+    (DESIGN 4.20); ``route_departures``: with the first-hop rule on empty origin roads; ``trip_reward``: with the
+    trip reward beside the queue reward."""
     from tarl_hip.evaluator import VecEvaluator
     engine = _eval_engine(eval_env, eval_envs, seed)
     dests = None
@@ -110,6 +112,8 @@ def _vec_evaluator(eval_env, policy_net, eval_envs, seed, temperature, policy_ho
     kw = {"policy_hold": True} if policy_hold else {}
     if route_departures:
         kw["route_departures"] = True
+    if trip_reward:
+        kw["trip_reward"] = True
     return VecEvaluator.from_policy_net(engine, policy_net, prior_dests=dests, temperature=temperature, **kw)
 
 
@@ -149,10 +153,15 @@ def vec_eval_record(prefix, res):
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
-              eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False):
+              eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False, reward="queue"):
     """``pretrain_bc`` (not in the reference; None = off): a dict {iterations, expert, driver, envs, frames,
     samples, epochs, batch, lr} — that many behaviour-cloning iterations (tarl_hip.imitation.BCTrainer) run before the first
-    PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``."""
+    PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``.
+    ``reward``: ``"trip"`` trains on the trip reward (VecPPOTrainer(reward="trip")); the log records gain
+    ``train/reward_kind`` and the ``eval_vec*`` evaluations run with ``trip_reward=True`` and log ``eval_vec/trip_return*``."""
+    if reward not in ("queue", "trip"):
+        raise ValueError("reward must be 'queue' or 'trip'")
+    trip = reward == "trip"
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
     from tarl_hip.trainer import VecPPOTrainer
@@ -204,7 +213,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             gt_params=policy_net.transformer.kernel_tensors() if head == "graph_transformer" else None,
                             gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw,
                             **({"policy_hold": True} if policy_hold else {}),
-                            **({"route_departures": True} if route_departures else {}))
+                            **({"route_departures": True} if route_departures else {}),
+                            **({"reward": "trip"} if trip else {}))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)
@@ -220,7 +230,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     if int(eval_envs) < 0:
         raise ValueError("eval_envs must be >= 0")
     # rank 0 alone evaluates (as it alone logs); the evaluator enters no collective
-    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature, policy_hold, route_departures)
+    vec_eval = (_vec_evaluator(eval_env, policy_net, eval_envs, seed, trainer.temperature, policy_hold, route_departures, trip)
                 if eval_envs and eval_env is not None and log is not None else None)
     ppo_train.last_vec_eval = vec_eval
     if eval_baseline not in EVAL_BASELINE_NAMES:
@@ -256,6 +266,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                 rec["train/held"] = float(trainer.held.sum()) / engine.B
             if route_departures:          # empty origin rows the first-hop rule wrote in this iteration's frames, per environment
                 rec["train/departures_routed"] = float(trainer.departures_routed.sum()) / engine.B
+            if trip:                      # PPO/avg_episode_return above is the return of the trip reward
+                rec["train/reward_kind"] = "trip"
             if bool(done.any()):
                 rec["transport/avg_travel_time"] = float((ag0[done, 3] - ag0[done, 2]).mean())
         # periodic evaluation (src/rl/ppo_trainer.py:147-151): MODE rollout, optionally a sampled one, on eval_env
@@ -277,6 +289,9 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                         rec[f"{prefix}/held"] = float(res.held.mean())
                     if route_departures and res.departures_routed is not None:
                         rec[f"{prefix}/departures_routed"] = float(res.departures_routed.mean())
+                    if trip and res.trip_return is not None:
+                        g = res.aggregate["trip_return"]
+                        rec[f"{prefix}/trip_return"], rec[f"{prefix}/trip_return_se"] = g["mean"], g["se"]
                     ppo_train.last_eval[prefix] = res
                 if eval_baseline != "none":
                     from tarl_hip.evaluator import EVAL_BASELINES, VecEvaluator, paired_report, paired_scalars
@@ -284,7 +299,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                         b_head, b_kw = EVAL_BASELINES[eval_baseline]
                         baseline_res = VecEvaluator(_eval_engine(eval_env, eval_envs, seed, baseline_agents),
                                                     b_head, **b_kw,
-                                                    **({"route_departures": True} if route_departures else {})).run(n_eval)
+                                                    **({"route_departures": True} if route_departures else {}),
+                                                    **({"trip_reward": True} if trip else {})).run(n_eval)
                     rec.update(vec_eval_record("eval_vec_baseline", baseline_res))
                     rep = paired_report(ppo_train.last_eval["eval_vec"], baseline_res)
                     rec.update({f"eval_vec_paired/{k}": v for k, v in paired_scalars(rep).items()})
@@ -294,7 +310,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
             log.flush()
             if writer is not None:
                 for k, v in rec.items():
-                    if k in ("global_step", "iter_seconds") or v is None:
+                    if k in ("global_step", "iter_seconds") or v is None or isinstance(v, str):
                         continue
                     if isinstance(v, list):
                         if k.endswith("_vc"):

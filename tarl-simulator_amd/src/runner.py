@@ -42,6 +42,8 @@ class RunnerArgs:
     #                                evaluation (eval: needs eval_envs) and in vectorised training (not policy_head "embedding")
     route_departures: bool = False # the first-hop rule on empty origin roads: eval with eval_envs, dijkstra_envs
     #                                (routers hold / free_flow) or replan_days; train with the state-dependent heads
+    reward: str = "queue"          # "trip": the trip reward of DESIGN 4.24 — train: what PPO optimises (state-dependent heads);
+    #                                eval: computed beside the queue reward with eval_envs, dijkstra_envs or replan_days
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
@@ -121,6 +123,20 @@ class RunnerArgs:
                 raise ValueError("route_departures cannot train policy_head 'embedding': its rollout kernels draw the actions "
                                  "of all frames ahead of the frames, so the rule has no frame state to read; use a "
                                  "state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer, goal_mlp)")
+        if self.reward not in ("queue", "trip"):
+            raise ValueError(f"reward must be 'queue' or 'trip', got {self.reward!r}")
+        if self.reward == "trip":
+            if self.mode == "eval" and not (self.eval_envs or self.dijkstra_envs or self.replan_days):
+                raise ValueError("reward trip is computed by the vectorised evaluation: in mode 'eval' it needs eval_envs > 0, "
+                                 "dijkstra_envs > 0 or replan_days > 0 (the single-environment, reference-shaped pass is not "
+                                 "changed)")
+            if self.mode == "train" and self.algo not in ("mpnn", "mpnn+ppo"):
+                raise ValueError("reward trip in mode 'train' acts on vectorised training: it needs algo mpnn or mpnn+ppo")
+            if self.mode == "train" and self.policy_head == "embedding":
+                raise ValueError("reward trip cannot train policy_head 'embedding': its rollout kernels do not go through the "
+                                 "shared loop of the state-dependent heads, where the trip launch follows every frame's "
+                                 "insert; use a state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer, "
+                                 "goal_mlp)")
         if self.eval_link_counts and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_link_counts counts per-road pops and withdrawals in the vectorised evaluation: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
@@ -394,7 +410,8 @@ class Runner:
                   log_dir=str(out) if self.rank == 0 else None, eval_env=eval_env, eval_interval=1,
                   num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled,
                   eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}),
-                  **({"route_departures": True} if a.route_departures else {}), **bc_kw)
+                  **({"route_departures": True} if a.route_departures else {}),
+                  **({"reward": "trip"} if a.reward == "trip" else {}), **bc_kw)
 
     def eval(self):
         a = self.args
@@ -557,7 +574,7 @@ class Runner:
                                                                     "link_bin_seconds")}
         engine = self._eval_engine(sim, self._replan_population, a.replan_envs)
         rp = Replanner(engine, days=a.replan_days, fraction=a.replan_fraction, max_hops=a.replan_max_hops,
-                       link_bin_seconds=a.eval_link_bin, seed=a.seed, **self._departures_kw(engine), **kw)
+                       link_bin_seconds=a.eval_link_bin, seed=a.seed, **self._departures_kw(engine), **self._trip_kw(), **kw)
         result = rp.run(frames)
         rep = replan_report(result)
         print(f"\n=== Replanning ({a.replan_days} days, {a.replan_envs} environments) ===")
@@ -576,6 +593,7 @@ class Runner:
             self._print_block(f"Vectorised evaluation ({last.envs} environments, routes, last day)", last)
             doc["routes"] = last.to_dict()
             self._departures_output(doc["routes"], last)
+            self._trip_output(doc["routes"], last)
             rows = [dict(kind="routes", **r) for r in last.rows()]
             self._reports_output(doc, last, None, out_dir, "replan")
             mode = (vectorised or {}).get("mode")
@@ -587,7 +605,7 @@ class Runner:
         with open(out_dir / "replan_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "replan_envs.csv", "w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
+            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS + self._trip_fields())
             w.writeheader()
             w.writerows(rows)
         return out
@@ -600,6 +618,25 @@ class Runner:
             raise ValueError("route_departures rewrites the packed state's SELECTED_ROAD bytes: this graph cannot be held by "
                              "the packed path (Nmax <= 127, out-degree <= 126, no parallel edges); run without the flag")
         return {"route_departures": True}
+
+    def _trip_kw(self):
+        """--reward trip for an evaluator: the keyword."""
+        return {"trip_reward": True} if self.args.reward == "trip" else {}
+
+    def _trip_fields(self):
+        """... and the column it adds to the per-environment CSV files."""
+        return ("trip_return",) if self.args.reward == "trip" else ()
+
+    def _trip_output(self, doc, res):
+        """One more line in the block just printed, and ``trip_return`` (per environment) / ``trip_parts_last`` in its JSON
+        entry; the aggregate's ``trip_return`` is already in ``doc["aggregate"]``."""
+        if self.args.reward != "trip" or res.trip_return is None:      # (a domain exit: no statistics)
+            return
+        doc["trip_return"] = list(res.trip_return)
+        doc["trip_parts_last"] = [[int(v) for v in row] for row in res.trip_parts_last]
+        on_way, ready = res.trip_parts_last.mean(axis=0)
+        print(f"{'trip reward:':22} after the last frame {on_way:.1f} agents on the way and {ready:.1f} due and waiting per "
+              f"environment still owe their trip (DESIGN 4.24)")
 
     def _departures_output(self, doc, res):
         """One more line in the block just printed, and ``route_departures`` / ``departures_routed`` in its JSON entry."""
@@ -627,16 +664,17 @@ class Runner:
         engine = self._eval_engine(self.simulator, self._dijkstra_population, self.args.dijkstra_envs)
         head, refresh = DIJKSTRA_ROUTERS[self.args.dijkstra_router]      # --dijkstra-router: reference / hold / free_flow
         res = VecEvaluator(engine, head, refresh_rate=self.agent.refresh_rate if refresh is None else refresh,
-                           **self._departures_kw(engine), **self._link_kw()).run(frames)
+                           **self._departures_kw(engine), **self._trip_kw(), **self._link_kw()).run(frames)
         self._print_block(f"Vectorised evaluation ({res.envs} environments, {router_label(res)})", res)
         out_dir.mkdir(parents=True, exist_ok=True)
         doc = {"mode": res.to_dict()}
         self._departures_output(doc["mode"], res)
+        self._trip_output(doc["mode"], res)
         self._reports_output(doc, res, None, out_dir, "dijkstra")
         with open(out_dir / "dijkstra_envs.json", "w") as f:
             json.dump(doc, f, indent=1)
         with open(out_dir / "dijkstra_envs.csv", "w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS)
+            w = csv.DictWriter(f, fieldnames=("kind", "env") + PER_ENV_KEYS + self._trip_fields())
             w.writeheader()
             w.writerows(dict(kind="mode", **r) for r in res.rows())
         return {"mode": res}
@@ -659,7 +697,8 @@ class Runner:
         if a.policy_head in ("embedding_dijkstra", "goal_mlp") and self.policy_net.resolve_prior_method() != "all_pairs":
             dests = destination_set(engine.agents, engine.N)
         ev = VecEvaluator.from_policy_net(engine, self.policy_net, prior_dests=dests, **self._link_kw(),
-                                          **({"policy_hold": True} if a.policy_hold else {}), **self._departures_kw(engine))
+                                          **({"policy_hold": True} if a.policy_hold else {}), **self._departures_kw(engine),
+                                          **self._trip_kw())
         results = {"mode": ev.run(frames, deterministic=True), "sampled": None}
         pair = None
         if a.eval_trips and a.eval_baseline != "none" and not results["mode"].domain_exit:
@@ -684,14 +723,15 @@ class Runner:
                 else:
                     print(f"{'policy hold:':22} ran with the hold rule on the policy's action (DESIGN 4.20)")
             self._departures_output(doc[key], res)
+            self._trip_output(doc[key], res)
             rows += [dict(kind=key, **r) for r in res.rows()]
-        fields = ("kind", "env") + PER_ENV_KEYS
+        fields = ("kind", "env") + PER_ENV_KEYS + self._trip_fields()
         if a.eval_baseline != "none":
             # the router on a second engine with the same seed, K and population: the same noise streams as the policy run
             from tarl_hip.evaluator import EVAL_BASELINES, paired_lines, paired_report, router_label
             b_head, b_kw = EVAL_BASELINES[a.eval_baseline]      # dijkstra / dijkstra_hold / free_flow (hold, static tables)
             base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), b_head,
-                                **b_kw, **self._departures_kw(engine), **self._link_kw()).run(frames, trip_pair=pair)
+                                **b_kw, **self._departures_kw(engine), **self._trip_kw(), **self._link_kw()).run(frames, trip_pair=pair)
             rep = paired_report(results["mode"], base)
             self._print_block(f"Baseline ({router_label(base)})", base)
             print("\n=== Policy \u2212 baseline (paired) ===")
@@ -700,10 +740,12 @@ class Runner:
             results["baseline"], results["paired"] = base, rep
             doc["baseline"], doc["paired"] = base.to_dict(), rep
             self._departures_output(doc["baseline"], base)
-            fields += tuple(f"baseline_{k}" for k in PER_ENV_KEYS)
+            self._trip_output(doc["baseline"], base)
+            b_keys = PER_ENV_KEYS + self._trip_fields()
+            fields += tuple(f"baseline_{k}" for k in b_keys)
             by_env = {r["env"]: r for r in base.rows()}
             for r in rows:
-                r.update({f"baseline_{k}": by_env[r["env"]][k] for k in PER_ENV_KEYS} if r["env"] in by_env else {})
+                r.update({f"baseline_{k}": by_env[r["env"]][k] for k in b_keys} if r["env"] in by_env else {})
         out_dir.mkdir(parents=True, exist_ok=True)
         self._reports_output(doc, results["mode"], results.get("baseline"), out_dir, "eval")      # of the MODE run
         with open(out_dir / "eval_envs.json", "w") as f:

@@ -155,6 +155,10 @@ class EvalResult:
     # route_departures=True (never after a domain exit): empty origin rows the first-hop rule wrote, summed over the frames,
     # DESIGN 4.23
     departures_routed: np.ndarray | None = field(default=None, compare=False)       # (K,) int64
+    # trip_reward=True (never after a domain exit): the trip reward of DESIGN 4.24 beside the queue reward — per environment
+    # the sum over the frames of -(on_way + ready), and {on_way, ready} after the last frame
+    trip_return: list | None = None
+    trip_parts_last: np.ndarray | None = field(default=None, compare=False)         # (K, 2) int64
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -162,13 +166,16 @@ class EvalResult:
                                            "computation_time_ms")}
         if per_env:
             d["per_env"] = {k: getattr(self, k) for k in PER_ENV_KEYS}
+            if self.trip_return is not None:      # (without trip_reward the document stays as it was)
+                d["per_env"]["trip_return"] = self.trip_return
         return d
 
     def rows(self):
         """One dict per environment (the rows of eval_envs.csv)."""
         if self.domain_exit:
             return []
-        return [dict(env=b, **{k: getattr(self, k)[b] for k in PER_ENV_KEYS}) for b in range(self.envs)]
+        extra = () if self.trip_return is None else ("trip_return",)
+        return [dict(env=b, **{k: getattr(self, k)[b] for k in PER_ENV_KEYS + extra}) for b in range(self.envs)]
 
     def summary_lines(self):
         """The aggregate as printable lines."""
@@ -176,7 +183,7 @@ class EvalResult:
             a, b = self.domain_exit_frames
             return [f"domain exit: a FIFO count reached Nmax between frames {a} and {b}; no statistics"]
         out = []
-        for k in PER_ENV_KEYS:
+        for k in PER_ENV_KEYS + (() if self.trip_return is None else ("trip_return",)):
             g = self.aggregate[k]
             if g["mean"] is None:
                 out.append(f"{k + ':':22} no data ({g['missing']} environments without an arrival)")
@@ -240,7 +247,8 @@ def paired_report(a: EvalResult, b: EvalResult) -> dict:
         raise ValueError(f"paired_report needs the same frames: frames_run {a.frames_run} / {b.frames_run}")
     head["frames_run"] = a.frames_run
     metrics = {}
-    for name, key in PAIRED_METRICS:
+    both_trip = a.trip_return is not None and b.trip_return is not None      # (a row of its own where both runs have it)
+    for name, key in PAIRED_METRICS + ((("trip_return", "trip_return"),) if both_trip else ()):
         d = np.asarray([x - y for x, y in zip(getattr(a, key), getattr(b, key)) if x is not None and y is not None],
                        dtype=np.float64)
         metrics[name] = {"n": int(d.size), "dropped": int(a.envs - d.size), **_sample_moments(d), "ci95_kind": _CI95_KIND}
@@ -339,7 +347,7 @@ class VecEvaluator:
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
                  dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True, policy_hold=False,
-                 goal_mlp=None, goal_scale=None, route_departures=False):
+                 goal_mlp=None, goal_scale=None, route_departures=False, trip_reward=False):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -402,7 +410,13 @@ class VecEvaluator:
         a free-flow per-destination table built once at frame 0 (``baseline_dests`` as for the routers). A non-empty
         origin road keeps its head's choice. ``actions`` stays the head's own choice; ``EvalResult.departures_routed``
         counts the rows written per environment. The ``"embedding"`` head takes its per-frame path, as under
-        ``policy_hold``."""
+        ``policy_hold``.
+        ``trip_reward`` (NOT in the reference; every head, the routers and ``"routes"`` included): after every
+        frame one ``ops.fused_trip_reward`` call writes -(on_way + ready) of that frame's clock into a SECOND (T, K) buffer
+        and {on_way, ready} into a (T, K, 2) one. The queue ``reward`` buffer, ``episode_return`` and everything read from
+        them stay exactly as they are; ``EvalResult.trip_return`` is the sum over the frames per environment (float64 on the
+        host), ``trip_parts_last`` the two counts after the last frame, ``aggregate["trip_return"]`` its mean, standard
+        error and interval. The frames themselves do not change."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -443,6 +457,8 @@ class VecEvaluator:
         self.keep_actions = bool(keep_actions)
         self.policy_hold = bool(policy_hold)
         self.route_departures = bool(route_departures)
+        self.trip_reward = bool(trip_reward)
+        self.trip_rw = self.trip_parts = None       # (T, K) fp32 and (T, K, 2) int32, reserved with the reward buffer
         self._per_frame_draw = self.policy_hold or self.route_departures     # "embedding": drawn per frame, as the other heads
         self.refresh_rate = int(refresh_rate)
         K, N, E, dev = engine.B, engine.N, engine.E, engine.device
@@ -624,6 +640,9 @@ class VecEvaluator:
             self._flag_host = torch.zeros(T // self.poll_frames + 2, dtype=torch.int32).pin_memory()
             if self.keep_actions:
                 self.actions = torch.zeros((T, K, N), dtype=torch.uint8, device=dev)
+        if self.trip_reward and (self.trip_rw is None or self.trip_rw.size(0) < T):
+            self.trip_rw = torch.zeros((T, K), dtype=torch.float32, device=dev)
+            self.trip_parts = torch.zeros((T, K, 2), dtype=torch.int32, device=dev)
 
     # -- the action of one frame -----------------------------------------------------------------------------------------
     def _logits(self):
@@ -806,8 +825,11 @@ class VecEvaluator:
         seen = False
         done = 0
         for t in range(T):
+            clock = float(eng.time)     # this frame's clock: the frame advances it
             self._frame(t, bool(deterministic))
             done = t + 1
+            if self.trip_reward:        # the frame is complete: the travellers owed, beside the queue reward
+                ops.fused_trip_reward(eng.plan, fs, clock, out=self.trip_rw[t], parts=self.trip_parts[t])
             if self.link_counts and _due(done, self.link_block, T):         # one launch per block of the rings
                 ops.link_counts_accumulate(self.link_popped, self.link_withdrawn, self.link_acc,
                                            **sched.block(done, self.link_block))
@@ -843,6 +865,8 @@ class VecEvaluator:
             settings["policy_hold"] = True
         if self.route_departures:
             settings["route_departures"] = True
+        if self.trip_reward:
+            settings["trip_reward"] = True
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):
@@ -868,6 +892,10 @@ class VecEvaluator:
             res.held = self.held.cpu().numpy().astype(np.int64)
         if self.route_departures:
             res.departures_routed = self.routed.cpu().numpy().astype(np.int64)
+        if self.trip_reward:                  # integers below 2^24 per frame: the float64 sum is exact
+            res.trip_return = [float(v) for v in self.trip_rw[:done].double().sum(dim=0).cpu().numpy()]
+            res.trip_parts_last = self.trip_parts[done - 1].cpu().numpy().astype(np.int64)
+            res.aggregate["trip_return"] = aggregate(res.trip_return)
         if self.link_counts:
             st = ops.link_count_stats(self.link_acc)
             res.link_counts = self.link_acc.cpu().numpy()

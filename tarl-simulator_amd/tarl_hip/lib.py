@@ -157,6 +157,8 @@ SIGNATURES = {
     "tarl_fused_route_departures": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "tarl_fused_route_departures_plan": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "tarl_fused_set_departure_router": (C.c_int, [_p, C.c_int, _p, _p, _i64, _i64, _p, _p]),
+    "tarl_fused_trip_reward": (C.c_int, [_p, _p, _i64, _i32, _i64, C.c_float, _p, _p, _p]),
+    "tarl_fused_set_trip_reward": (C.c_int, [_p, C.c_int, _p]),
     "tarl_fused_expert_labels": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _p, _i64, _i64, _p, _p, _p]),
     "tarl_graphdist_bc_scratch_bytes": (_i64, [_p, _i64]),
     "tarl_graphdist_bc": (C.c_int, [_p, _p, _i64, _f32, _p, _f32, _p, _p, _p, _p, _p, _p]),

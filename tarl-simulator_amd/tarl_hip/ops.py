@@ -1331,6 +1331,47 @@ def fused_set_departure_router(fs, on, dest_slot=None, table=None, pend=None, ro
     fs.departure_router = (dest_slot, table, pend, routed)
 
 
+# ---- the trip reward: travellers who should be under way and have not arrived (NOT reference semantics) --------
+def fused_trip_reward(plan: Plan, fs, t, out=None, parts=None):
+    """-> ``reward`` (B,) fp32 = -(on_way + ready) per environment, after the frame whose clock is ``t`` has run completely
+    (tarl_fused_trip_reward): on_way = agents with status 1, ready = waiting agents with DEPARTURE_TIME <= t (the insert
+    rule's test; every row of the agent table counts, agent 0 too). With the departure window ``ready`` is the walk from
+    the insert cursor; neither the cursor nor any other word of ``fs`` is written. ``out``: such a tensor to write into;
+    ``parts`` (B, 2) int32 (optional): {on_way, ready}. Every element of both is overwritten."""
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    t = float(t)
+    if not math.isfinite(t):
+        raise ValueError(f"t must be finite, got {t}")
+    if out is None:
+        out = torch.empty((fs.B,), dtype=torch.float32, device=fs.hdp.device)
+    _contig(out, torch.float32, "out")
+    if tuple(out.shape) != (fs.B,):
+        raise ValueError(f"out must be (B,) = ({fs.B},)")
+    if parts is not None:
+        _contig(parts, torch.int32, "parts")
+        if tuple(parts.shape) != (fs.B, 2):
+            raise ValueError(f"parts must be (B, 2) = ({fs.B}, 2)")
+    _lib.check(_lib.load().tarl_fused_trip_reward(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, t, out.data_ptr(), _lib.ptr(parts),
+                                                  _lib.current_stream()))
+    return out
+
+
+def fused_set_trip_reward(fs, on, parts=None):
+    """The switch of the state-dependent T-frame rollouts (tarl_fused_set_trip_reward): with ``on`` their loop queues
+    :func:`fused_trip_reward` in every frame after the insert launch, into the rollout's ``reward[t]``: the reward buffer
+    then holds the trip reward instead of the queue reward. ``parts`` (T_max, B, 2) int32 (optional, kept alive on ``fs``):
+    {on_way, ready} of frame t at ``parts[t]``; the rollout must not run more than T_max frames. Action bytes, log-probs and
+    count bytes are the same either way. Off (the default) the loop queues exactly the launches it always queued."""
+    if parts is not None:
+        if not on:
+            raise ValueError("a parts buffer without the switch")
+        _contig(parts, torch.int32, "parts")
+        if parts.dim() != 3 or tuple(parts.shape[1:]) != (fs.B, 2):
+            raise ValueError(f"parts must be (T_max, B, 2) = (T_max, {fs.B}, 2)")
+    _lib.check(_lib.load().tarl_fused_set_trip_reward(fs.ref, 1 if on else 0, _lib.ptr(parts)))
+    fs.trip_parts = parts
+
+
 BC_IGNORE = 0xFF        # TARL_BC_IGNORE: the label byte of a row the expert says nothing about
 
 

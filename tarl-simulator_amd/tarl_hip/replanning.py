@@ -66,7 +66,7 @@ class ReplanResult:
 
 class Replanner:
     def __init__(self, engine, *, days, fraction=0.1, max_hops=None, link_bin_seconds=3600, seed=0, per_env=True, keep=False,
-                 route_departures=False, **eval_kw):
+                 route_departures=False, trip_reward=False, **eval_kw):
         """``engine``: a fused :class:`SimEngine` with K environments that share one population. ``days`` >= 1 simulated
         days; ``fraction``: the share that may switch per day, in (0, 1], or ``"msa"``; ``max_hops``: the longest route
         stored (default min(N, 256)); ``link_bin_seconds``: the bins of the road times; ``seed``: of the switch masks.
@@ -74,6 +74,8 @@ class Replanner:
         drawn after it in ``history`` (tests). ``eval_kw``: further report flags of :class:`VecEvaluator` (link_counts, trips, turns, ...) for every day's run.
         ``route_departures``: every day's ``routes`` evaluator runs with the first-hop rule, so that an agent
         follows its own plan on its first road too.
+        ``trip_reward``: every day's evaluator also computes the trip reward; the day records gain
+        ``trip_return`` (its moments over the environments), the report ``trip_return_mean`` / ``trip_return_se``.
         The routes take 4 K A max_hops bytes twice (current and new); with the search scratch that is refused beyond half
         the free device memory."""
         if int(days) < 1:
@@ -108,7 +110,8 @@ class Replanner:
                                  f"environments, in bins of link_bin_seconds")
         self.ev = VecEvaluator(engine, "routes", routes=self._plan_of(self.cur), occupancy=True, dynamic_gap=True,
                                link_bin_seconds=self.link_bin_seconds,
-                               **({"route_departures": True} if route_departures else {}), **eval_kw)
+                               **({"route_departures": True} if route_departures else {}),
+                               **({"trip_reward": True} if trip_reward else {}), **eval_kw)
         st = engine.static_node_features[0]
         mx, ff = st[:, 0].contiguous(), st[:, 2].contiguous()
         cc = engine.cc if engine.cc is not None else ff * (mx + 10 - st[:, 4] * ff / 3600)      # as VecEvaluator._gap_reserve
@@ -201,6 +204,10 @@ class Replanner:
             for key in DAY_KEYS:
                 v = np.asarray([x for x in rec["per_env"][key] if x is not None], dtype=np.float64)
                 rec[key] = dict(n=int(v.size), **_sample_moments(v))
+            if res.trip_return is not None:      # trip_reward=True: the frames owed by all travellers, DESIGN 4.24
+                rec["per_env"]["trip_return"] = list(res.trip_return)
+                v = np.asarray(res.trip_return, dtype=np.float64)
+                rec["trip_return"] = dict(n=int(v.size), **_sample_moments(v))
             records.append(rec)
         settings = dict(days=self.days, fraction=self.fraction, max_hops=self.max_hops, per_env=self.per_env, plans=P,
                         seed=self.seed, engine_seed=eng.seed, envs=K, frames=T, link_bin_seconds=bins, bins=int(H),
@@ -222,8 +229,10 @@ def replan_report(result: ReplanResult) -> dict:
     """The day table of a :class:`ReplanResult`: ``rows`` (one dict per day, ``columns`` their keys; a day that left the
     domain has no statistics), ``env_rows`` (one per day and environment), ``settings`` and the note on the shared noise."""
     rows, env_rows = [], []
+    trip = any("trip_return" in r for r in result.days)       # Replanner(trip_reward=True): two more columns
+    columns = list(REPLAN_COLUMNS) + (["trip_return_mean", "trip_return_se"] if trip else [])
     for r in result.days:
-        row = {c: None for c in REPLAN_COLUMNS}
+        row = {c: None for c in columns}
         row.update(day=r["day"], domain_exit=bool(r["domain_exit"]), sim_ms=r["sim_ms"])
         if not r["domain_exit"]:
             for key in DAY_KEYS:
@@ -231,10 +240,12 @@ def replan_report(result: ReplanResult) -> dict:
             row.update(switch_probability=r["switch_probability"], differs_share=r["differs"] / max(r["agents"], 1),
                        switched_share=None if r["switched"] is None else r["switched"] / max(r["agents"], 1),
                        without_route=r["without_route"], overflowing=r["overflowing"], plan_ms=r["plan_ms"])
+            if trip:
+                row["trip_return_mean"], row["trip_return_se"] = r["trip_return"]["mean"], r["trip_return"]["se"]
             for k in range(len(r["per_env"]["arrived"])):
                 env_rows.append(dict(day=r["day"], env=k, **{key: r["per_env"][key][k] for key in DAY_KEYS}))
         rows.append(row)
-    return dict(available=True, columns=list(REPLAN_COLUMNS), rows=rows, env_columns=["day", "env"] + list(DAY_KEYS),
+    return dict(available=True, columns=columns, rows=rows, env_columns=["day", "env"] + list(DAY_KEYS),
                 env_rows=env_rows, settings=dict(result.settings), domain_exit_day=result.domain_exit_day, note=REPLAN_NOTE)
 
 
@@ -260,5 +271,9 @@ def replan_lines(report: dict):
                    f"{_pm(r['avg_travel_time'], r['avg_travel_time_se'], '.2f'):>22} "
                    f"{_pm(r['relative_gap'], r['relative_gap_se'], '.4f'):>20} {r['differs_share']:>8.4f} {sw:>9} "
                    f"{r['without_route']:>9d} {r['overflowing']:>9d} {r['sim_ms']:>9.1f} {r['plan_ms']:>9.1f}")
+    if "trip_return_mean" in report["columns"]:
+        out.append("trip return per day: " + ", ".join(
+            "-" if r["domain_exit"] else _pm(r["trip_return_mean"], r["trip_return_se"], ".1f") for r in report["rows"])
+            + "  (-(on the way + due and waiting) summed over the frames, DESIGN 4.24)")
     out.append("note: " + report["note"])
     return out

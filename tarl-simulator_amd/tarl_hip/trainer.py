@@ -71,7 +71,7 @@ class VecPPOTrainer:
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
                  prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None,
-                 route_departures=False):
+                 route_departures=False, reward="queue"):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -91,7 +91,12 @@ class VecPPOTrainer:
         road with an agent ready to depart from it selects that agent's first hop, looked up in a free-flow per-destination
         table built once after the first reset (ops.fused_set_departure_router), after the optional hold launch. The stored
         action and log-prob are the draw's; ``departures_routed`` (B,) int32 counts the rows written by the last
-        ``collect()``. State-dependent heads only."""
+        ``collect()``. State-dependent heads only.
+        ``reward`` (DESIGN 4.24): ``"queue"`` (the default) is the reference's -sum of the FIFO counts after the frame;
+        ``"trip"`` (an environment-side rule, not in the reference) is -(agents on the way + waiting agents that are due),
+        so that a lost agent and a blocked departure keep costing until the horizon: ``collect()`` sets the switch of the
+        shared rollout loop (ops.fused_set_trip_reward) and ``self.reward`` then holds the trip reward; GAE, the critic and
+        the update read it as before. State-dependent heads on the fused path only."""
         self.eng = engine
         # policy: "embedding" = the reference's live head (logit = embedding of the target road: state-independent, its
         # distribution is tabulated once per update); "edge_mlp" = the per-edge MLP head it carries as parameters
@@ -198,6 +203,17 @@ class VecPPOTrainer:
             self._departure_router = router_buffers(engine, None, 1) + (
                 torch.empty((engine.N, engine.B), dtype=torch.int32, device=engine.device),)
             self._departure_table_built = False
+        if reward not in ("queue", "trip"):
+            raise ValueError("reward must be 'queue' or 'trip'")
+        self.reward_kind = reward
+        if reward == "trip" and not self.state_dep:
+            raise ValueError("reward='trip' is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
+                             "tarl_rollout_env) do not go through the shared loop of the state-dependent heads, where the "
+                             "trip launch follows every frame's insert; "
+                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+        if reward == "trip" and engine.fs is None:
+            raise ops._lib.TarlError("reward='trip' needs the fused engine (ops.fused_path_supported): the packed state "
+                                     "cannot represent this graph and there is no fall-back")
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
@@ -382,6 +398,8 @@ class VecPPOTrainer:
                     self._departure_table_built = True
                 self.departures_routed.zero_()
                 ops.fused_set_departure_router(eng.fs, True, slot, table[0], pend, self.departures_routed, plan=eng.plan)
+            if self.reward_kind == "trip":      # and after every frame's insert: the trip reward over the queue reward
+                ops.fused_set_trip_reward(eng.fs, True)
             if self.state_dep:
                 self._draw_minibatch_frames()
             else:
@@ -398,6 +416,8 @@ class VecPPOTrainer:
                 ops.fused_set_policy_hold(eng.fs, False)
             if self.route_departures:
                 ops.fused_set_departure_router(eng.fs, False)
+            if self.reward_kind == "trip":
+                ops.fused_set_trip_reward(eng.fs, False)
             if self.obs_all is not None:      # frame T: the final state (an episode end at T - 1 is not followed by a reset)
                 eng.obs16(out=self.obs_all[T])
             # the device status word travels to pinned host memory behind the rollout; it is looked at when it has
