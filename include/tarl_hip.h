@@ -1303,6 +1303,54 @@ int tarl_noise_export(const tarl_plan* plan, int kind, uint64_t seed, uint64_t c
 int tarl_prof_enable(int64_t max_frames);
 int tarl_prof_collect(int64_t first_late_frame, double* ms_all_host, double* ms_late_host, int64_t* frames_host);
 
+/* ---- per-agent path trace of the vectorised evaluation (--eval-paths; csrc/path_trace.hip) -----------------------
+ * NOT in the reference: which roads every (environment, agent) was seen on as a FIFO head, the free-flow cost of the hops
+ * between them and how much of it was detour. TARL_ABI_VERSION is unchanged: nothing existing moved, tarl_fused did not grow.
+ * State, caller-owned, per (environment b, agent a), row 0 the dummy and never touched by the pass:
+ *   last_road, roads, revisits, off_tree int32 [B][A]; path_cost, excess fp64 [B][A]; route int32 [B][A][L] (NULL iff L == 0);
+ *   bad int32 [B].
+ * tarl_path_trace_reset: last_road = -1, route = -1, everything else 0 (not all zero: a memset does not do).
+ * tarl_fused_path_trace: the SIGHTING PASS, one launch after a frame has run completely. READS the packed state (word 0 of
+ *   tarl_fused.hdp, and tarl_fused.a_dest when weights are given) and writes nothing of it. For every road u and environment b
+ *   whose count bits (hdp.x & 0x7F) are not 0, with a = hdp.x >> 8: a == 0 -> nothing; a >= num_agents -> bad[b] += 1;
+ *   p = last_road[b][a], p == u -> nothing; else, h = roads[b][a]:
+ *     p >= 0: e = the first entry of p's CSR out-list whose target is u; none -> bad[b] += 1, no cost. With weights:
+ *       w = (double) weights[original edge id of e]; path_cost += w; s = dest_slot[a_dest[b][a]]; destination outside [0, N),
+ *       s outside [0, num_dests) or dist[s][u] / dist[s][p] not finite -> off_tree += 1; else
+ *       excess += (w + dist[s][u]) - dist[s][p], fp64, in this order.
+ *     route[b][a][i] == u for some i < min(h, L) -> revisits += 1 (the kept prefix only); h < L -> route[b][a][h] = u;
+ *     roads = h + 1; last_road = u.
+ *   weights fp32 [E] (original edge order), dist fp64 [num_dests][N] and dest_slot int32 [N] (tarl_dest_trees) are optional
+ *   AS A GROUP; without them path_cost, excess and off_tree stay as they are. With dist the distances under the same weights
+ *   every term is a reduced cost: >= 0 up to rounding, exactly 0.0 on a hop of the tree the distances came from.
+ *   Every (b, a) element has one writer per launch (an agent heads at most one non-empty road): no atomics, but the integer
+ *   atomicAdd of bad[b], which must stay 0. A second launch on the same packed state changes nothing.
+ * tarl_path_agent_stats: after the episode, per agent over the K environments, agents fp32 [K][A][9] (environment k at
+ *   agents + k * a_bstride) for the DONE flag. out_i32 [8][A]: n_done, n_zero_excess (excess == 0 and off_tree == 0), n_loop
+ *   (revisits > 0), n_trunc (roads > L) over the environments in which the agent is DONE; n_seen (roads > 0), n_loop_all,
+ *   max roads over all; n_both. out_f64 [10][A]: sum and sum of squares of moves = max(roads - 1, 0), of path_cost and of
+ *   excess over the DONE environments; with roads_b, excess_b, agents_b (b_bstride) of a second run — all three or none — of
+ *   moves - moves_b and excess - excess_b over the environments DONE in both (rows 7 of out_i32 and 6..9 of out_f64, left alone
+ *   without them). One thread per agent adds k = 0, 1, ... in order from +0.0: bit-identical from run to run. Entry 0 is zero.
+ * Host checks, all before any HIP call (a refused call writes nothing): a null plan, handle, state pointer or output,
+ *   tarl_fused_select_next_hop_dest's rules on B and Nmax, num_agents outside [1, 2^24], L outside [0, TARL_PATH_MAX_HOPS],
+ *   route missing with L > 0, weights without dist or dest_slot and the reverse, sizes whose products overflow, agent tables
+ *   that overlap. What they cannot see: num_agents must be the A the handle's agent buffers were allocated for —
+ *   tarl_fused.a_dest is read as [b * num_agents + a], as tarl_fused_trip_reward reads the status bytes (ops.fused_path_trace
+ *   passes the handle's own A and refuses a state of another shape). */
+#define TARL_PATH_MAX_HOPS 4096
+int tarl_path_trace_reset(int64_t B, int64_t num_agents, int64_t L, int32_t* last_road, int32_t* roads, int32_t* revisits,
+                          int32_t* off_tree, double* path_cost, double* excess, int32_t* route, int32_t* bad,
+                          tarl_stream stream);
+int tarl_fused_path_trace(const tarl_plan* plan, const tarl_fused* f, int64_t B, int32_t Nmax, int64_t num_agents, int64_t L,
+                          int32_t* last_road, int32_t* roads, int32_t* revisits, int32_t* off_tree, double* path_cost,
+                          double* excess, int32_t* route, int32_t* bad, const float* weights, const double* dist,
+                          const int32_t* dest_slot, int64_t num_dests, tarl_stream stream);
+int tarl_path_agent_stats(const int32_t* roads, const int32_t* revisits, const int32_t* off_tree, const double* path_cost,
+                          const double* excess, const float* agents, int64_t a_bstride, const int32_t* roads_b,
+                          const double* excess_b, const float* agents_b, int64_t b_bstride, int64_t K, int64_t num_agents,
+                          int64_t L, int32_t* out_i32, double* out_f64, tarl_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

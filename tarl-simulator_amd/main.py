@@ -202,6 +202,21 @@ OPTIONS = (
                                "mean, standard error and interval per turn, its share of the movements out of its road, for "
                                "the embedding head the policy's probability and, with --eval-baseline, the paired "
                                "difference; eval_turns_lost.csv; `turns` in the JSON file")),
+    ("--eval-paths", dict(action="store_true",
+                          help="--eval-envs / --dijkstra-envs, eval: trace per (environment, traveller) the roads it was seen on "
+                               "as the head of a queue (DESIGN 4.25, not in the reference): how many, the free-flow cost of the "
+                               "hops, how much of it was detour against the free-flow shortest path to its own destination, and "
+                               "how often it came back to a road; a `Paths` block that splits the travel time of a completed trip "
+                               "into shortest free-flow cost + wandering + everything else (with --eval-trips), names the agents "
+                               "that loop and gives a table by departure time (bins of --eval-link-bin seconds); eval_paths.csv "
+                               "(dijkstra_paths.csv) with one row per agent and, with --eval-baseline, the paired differences; "
+                               "`paths` in the JSON file; also through --replan-days (replan_paths.csv)")),
+    ("--eval-paths-max-hops", dict(type=int, default=None, metavar="L",
+                                   help="--eval-paths: roads kept per trace (default 64, at most 4096; 0 keeps no routes: counts "
+                                        "and costs only, and no loop is recognised)")),
+    ("--eval-paths-routes", dict(type=int, default=0, metavar="J",
+                                 help="--eval-paths: also write the kept routes of the first J environments to "
+                                      "eval_paths_routes.csv (env, agent, roads, truncated, route as space-separated road ids)")),
     ("--iterations", dict(type=int, default=1,
                           help="train: collector batches (total frames per environment = iterations x rollout steps)")),
     ("--pretrain-bc", dict(type=int, default=0, metavar="I",

@@ -53,6 +53,9 @@ class RunnerArgs:
     eval_dynamic_gap: bool = False # eval_envs / dijkstra_envs, eval: the trips against the best path in hindsight (same bins)
     eval_dynamic_gap_envs: int = None   # ... over the first J of the K environments (default: all)
     eval_turns: bool = False       # eval_envs / dijkstra_envs: vehicles per route edge and the agents quirk Q24 loses (same bins)
+    eval_paths: bool = False       # eval_envs / dijkstra_envs, eval: the per-agent path trace of DESIGN 4.25 (same bins)
+    eval_paths_max_hops: int = None     # ... roads kept per trace (default 64; 0: none)
+    eval_paths_routes: int = 0     # ... the kept routes of the first J environments into <prefix>_paths_routes.csv
     replan_days: int = 0           # eval, any algo: J > 0 adds the day-to-day replanning loop (tarl_hip.replanning)
     replan_envs: int = 1           # ... on this many environments of an engine of its own
     replan_fraction: object = 0.1  # ... the share that may switch per day, in (0, 1], or "msa"
@@ -152,6 +155,21 @@ class RunnerArgs:
         if self.eval_dynamic_gap and not ((self.eval_envs or self.dijkstra_envs) and self.mode == "eval"):
             raise ValueError("eval_dynamic_gap measures the trips of the vectorised evaluation against the best path in "
                              "hindsight: it needs mode 'eval' and eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_paths and not ((self.eval_envs or self.dijkstra_envs) and self.mode == "eval"):
+            raise ValueError("eval_paths traces every traveller's roads in the vectorised evaluation: it needs mode 'eval' and "
+                             "eval_envs > 0 or dijkstra_envs > 0")
+        if self.eval_paths_max_hops is not None:
+            if not self.eval_paths:
+                raise ValueError("eval_paths_max_hops sizes the routes of eval_paths: it needs that flag")
+            if not 0 <= int(self.eval_paths_max_hops) <= 4096:
+                raise ValueError(f"eval_paths_max_hops must be in [0, 4096], got {self.eval_paths_max_hops!r}")
+        if self.eval_paths_routes is None or int(self.eval_paths_routes) < 0:
+            raise ValueError(f"eval_paths_routes must be >= 0, got {self.eval_paths_routes!r}")
+        if self.eval_paths_routes:
+            if not self.eval_paths:
+                raise ValueError("eval_paths_routes writes the routes of eval_paths: it needs that flag")
+            if self.eval_paths_max_hops is not None and int(self.eval_paths_max_hops) == 0:
+                raise ValueError("eval_paths_routes writes the kept routes: with eval_paths_max_hops 0 none is kept")
         if self.eval_dynamic_gap_envs is not None:
             if not self.eval_dynamic_gap:
                 raise ValueError("eval_dynamic_gap_envs limits the environments of eval_dynamic_gap: it needs that flag")
@@ -501,6 +519,11 @@ class Runner:
             kw.update(dynamic_gap=True, dynamic_gap_envs=a.eval_dynamic_gap_envs, link_bin_seconds=a.eval_link_bin)
         if a.eval_turns:
             kw.update(turns=True, link_bin_seconds=a.eval_link_bin)
+        if a.eval_paths:        # cost and detour under the free-flow weights of the per-trip report
+            sim = self.simulator if a.algo == "dijkstra" else self.env.simulator
+            g, h = sim.graph, sim.h
+            kw.update(paths=True, path_max_hops=a.eval_paths_max_hops, link_bin_seconds=a.eval_link_bin,
+                      path_weights=g.x[:, h.FREE_FLOW_TIME_TRAVEL][g.edge_index[1]])
         return kw
 
     @staticmethod
@@ -520,7 +543,7 @@ class Runner:
         return summary_fn(report)
 
     def _reports_output(self, doc, res, baseline, out_dir, prefix):
-        """--eval-link-counts, --eval-turns, --eval-occupancy, --eval-trips, --eval-dynamic-gap: each report of ``res`` (against ``baseline``, the evaluation of
+        """--eval-link-counts, --eval-turns, --eval-occupancy, --eval-trips, --eval-dynamic-gap, --eval-paths: each report of ``res`` (against ``baseline``, the evaluation of
         the same environments, where there is one) printed, written to ``<prefix>_<report>.csv`` (one row per road; the
         link counts with the expected flows that Runner.eval computed; the trips one row per agent, and per departure bin in
         ``<prefix>_trips_by_departure.csv``; the turns one row per route edge, and per road with a loss in
@@ -557,6 +580,21 @@ class Runner:
                 print("\n=== Dynamic gap: policy \u2212 baseline (paired) ===")
                 for line in E.dynamic_gap_paired_lines(rep):
                     print(line)
+        if a.eval_paths:
+            doc["paths"] = self._report_output(
+                "Paths", E.path_report(res, baseline=baseline), E.path_lines, E.path_summary,
+                [(out_dir / f"{prefix}_paths.csv", "columns", "rows"),
+                 (out_dir / f"{prefix}_paths_by_departure.csv", "by_departure_columns", "by_departure")])
+            if baseline is not None:      # the baseline's own block and file
+                doc["paths"]["baseline"] = self._report_output(
+                    f"Paths: baseline ({baseline.head})", E.path_report(baseline), E.path_lines, E.path_summary,
+                    [(out_dir / f"{prefix}_paths_baseline.csv", "columns", "rows")])
+            if a.eval_paths_routes and res.path_routes is not None:
+                import csv
+                with open(out_dir / f"{prefix}_paths_routes.csv", "w", newline="") as f:
+                    w = csv.DictWriter(f, fieldnames=("env", "agent", "roads", "truncated", "route"))
+                    w.writeheader()
+                    w.writerows(E.path_route_rows(res, a.eval_paths_routes))
 
     def _replanning(self, frames, out_dir, sim, vectorised):
         """--replan-days J: the day-to-day replanning loop (tarl_hip.replanning.Replanner; not in the reference) on
@@ -704,6 +742,9 @@ class Runner:
         if a.eval_trips and a.eval_baseline != "none" and not results["mode"].domain_exit:
             # the MODE run's agent tables, for the baseline's paired launch: a sampled run would overwrite them
             pair = engine.agents.clone() if a.eval_sampled else engine.agents
+        path_pair = None
+        if a.eval_paths and a.eval_baseline != "none" and not results["mode"].domain_exit:      # likewise, the MODE run's trace
+            path_pair = ((ev.path_state.clone(), engine.agents.clone()) if a.eval_sampled else (ev.path_state, engine.agents))
         if a.eval_sampled:
             results["sampled"] = ev.run(frames, deterministic=False)
         doc, rows = {}, []
@@ -731,7 +772,7 @@ class Runner:
             from tarl_hip.evaluator import EVAL_BASELINES, paired_lines, paired_report, router_label
             b_head, b_kw = EVAL_BASELINES[a.eval_baseline]      # dijkstra / dijkstra_hold / free_flow (hold, static tables)
             base = VecEvaluator(self._eval_engine(sim, self.policy_net.agent_features, a.eval_envs), b_head,
-                                **b_kw, **self._departures_kw(engine), **self._trip_kw(), **self._link_kw()).run(frames, trip_pair=pair)
+                                **b_kw, **self._departures_kw(engine), **self._trip_kw(), **self._link_kw()).run(frames, trip_pair=pair, path_pair=path_pair)
             rep = paired_report(results["mode"], base)
             self._print_block(f"Baseline ({router_label(base)})", base)
             print("\n=== Policy \u2212 baseline (paired) ===")

@@ -628,6 +628,197 @@ def trip_lines(report: dict):
 trip_summary = _summary
 
 
+# ---- per-agent path trace (VecEvaluator(paths=True)) ------------------------------------------------------------------
+PATH_NOTE = ("a road counts when the agent is seen as the head of its FIFO after a frame; moves = roads - 1; path cost = the "
+             "weights of the hops between them; excess = the reduced cost of every hop against the shortest-path distances to "
+             "the agent's own destination under the same weights (0 on a shortest path); a loop is a road met again among the "
+             "KEPT roads of the trace (the first max_hops), a truncated trace saw more roads than it keeps")
+
+
+def path_report(result: "EvalResult", baseline: "EvalResult | None" = None) -> dict:
+    """Per-agent rows, a by-departure table and a summary of the path trace of one evaluation (``VecEvaluator(paths=True)``),
+    formed in float64 on the host from the kernels' counts and sums.
+    Every row: ``agent``, ``origin``, ``destination``, ``departure``; ``envs_seen`` (roads > 0), ``arrival_share`` = n_done / K,
+    ``n_zero_excess``, ``n_loop``, ``n_trunc`` (over the environments in which the agent arrived), ``n_loop_all``,
+    ``roads_max``; ``moves_*``, ``cost_*`` and ``excess_*`` with ``mean``, ``sd`` (ddof 1), ``se``, ``ci95_lo`` / ``_hi``
+    (mean -+ 1.96 se, normal approximation) over the environments in which it arrived — ``None`` as in :func:`trip_report`,
+    cost and excess ``None`` throughout where the run had no weights or no distance table.
+    ``baseline``: the evaluation of another head on the same environments, run with ``run(..., path_pair=<this run's state
+    and agent tables>)``; the row gains ``paired_n`` and the paired difference result - baseline of moves and of excess with
+    se and interval. The summary splits a completed trip's travel time (where the run also reduced its trips) into path cost
+    and the rest. A run without a trace (a domain exit has none): ``{"available": False, "reason": ...}``."""
+    if (gone := _unavailable(result, result.path_stats, "the run did not trace its paths")) is not None:
+        return gone
+    ps, pa, meta = result.path_stats, result.paths, result.path_meta
+    K, A = pa["roads"].shape
+    has_w = bool(meta["weights"])
+    pair = None
+    if baseline is not None:
+        _check_pair("path_report", result, baseline)
+        if baseline.domain_exit or baseline.path_stats is None:
+            pair = {"available": False, "reason": "the baseline run has no path trace"}
+        elif baseline.frames_run != result.frames_run or baseline.paths["roads"].shape != (K, A) or not all(
+                np.array_equal(baseline.path_meta[k], meta[k]) for k in ("origin", "destination", "departure")):
+            raise ValueError("path_report needs the same frames and population in both runs")
+        elif not baseline.path_meta.get("paired") or "n_both" not in baseline.path_stats:
+            pair = {"available": False, "reason": "the baseline run was not paired with this one (run(path_pair=...))"}
+        else:
+            pair = {"available": True, "baseline_head": baseline.head}
+    paired = pair is not None and pair["available"]
+    n_done = ps["n_done"].astype(np.int64)
+    rows = []
+    for a in range(1, A):
+        n = int(n_done[a])
+        row = {"agent": a, "origin": int(meta["origin"][a]), "destination": int(meta["destination"][a]),
+               "departure": float(meta["departure"][a]), "envs_seen": int(ps["n_seen"][a]), "arrival_share": n / K,
+               "n_zero_excess": int(ps["n_zero_excess"][a]) if has_w else None, "n_loop": int(ps["n_loop"][a]),
+               "n_trunc": int(ps["n_trunc"][a]), "n_loop_all": int(ps["n_loop_all"][a]), "roads_max": int(ps["roads_max"][a])}
+        for name, key, on in (("moves", "moves", True), ("cost", "cost", has_w), ("excess", "excess", has_w)):
+            m = _trip_moments(n if on else 0, ps[key + "_sum"][a], ps[key + "_sumsq"][a])
+            row.update({f"{name}_mean": m["mean"], f"{name}_sd": m["sd"], f"{name}_se": m["se"],
+                        f"{name}_ci95_lo": m["ci95_lo"], f"{name}_ci95_hi": m["ci95_hi"]})
+        if paired:      # the baseline's launch holds d = baseline - result: the difference result - baseline is its negative
+            bs = baseline.path_stats
+            nb = int(bs["n_both"][a])
+            row["paired_n"] = nb
+            for name, key, on in (("moves", "dmoves", True), ("excess", "dexcess", has_w and bool(baseline.path_meta["weights"]))):
+                d = _trip_moments(nb if on else 0, -float(bs[key + "_sum"][a]), bs[key + "_sumsq"][a])
+                row.update({f"paired_{name}_diff_mean": d["mean"], f"paired_{name}_diff_se": d["se"],
+                            f"paired_{name}_diff_ci95_lo": d["ci95_lo"], f"paired_{name}_diff_ci95_hi": d["ci95_hi"]})
+        rows.append(row)
+    live, seen = n_done[1:], ps["n_seen"][1:].astype(np.int64)
+    trips = int(live.sum())
+    w = live.astype(np.float64)
+    spread = lambda v: float(np.std(v, ddof=1)) if v.size >= 2 else None      # noqa: E731
+    per = lambda key: ps[key][1:][live > 0].astype(np.float64) / w[live > 0]   # noqa: E731  (the agents' own means)
+    tot = lambda key: float(ps[key][1:].astype(np.float64).sum())             # noqa: E731
+    done = pa["done"].copy()
+    done[:, 0] = True       # the dummy is nobody's unfinished trip
+    open_ = ~done & (pa["roads"] > 0)
+    summary = {"envs": K, "agents": A - 1, "frames_run": result.frames_run, "max_hops": int(meta["max_hops"]), "note": PATH_NOTE,
+               "seen_in_every": int((seen == K).sum()), "seen_in_some": int(((seen > 0) & (seen < K)).sum()),
+               "seen_in_none": int((seen == 0).sum()), "trips": trips,
+               "mean_moves": tot("moves_sum") / trips if trips else None, "mean_moves_sd_over_agents": spread(per("moves_sum")),
+               "share_loop": int(ps["n_loop"][1:].sum()) / trips if trips else None,
+               "share_truncated": int(ps["n_trunc"][1:].sum()) / trips if trips else None,
+               "open": {"traces": int(open_.sum()), "with_loop": int((open_ & (pa["revisits"] > 0)).sum()),
+                        "truncated": int((open_ & (pa["roads"] > meta["max_hops"])).sum()),
+                        "mean_moves": float(np.maximum(pa["roads"][open_] - 1, 0).mean()) if open_.any() else None},
+               "weights": None, "excess_note": meta["note"], "top_excess": []}
+    if has_w:
+        cost, exc = tot("cost_sum"), tot("excess_sum")
+        wsum = {"mean_cost": cost / trips if trips else None, "mean_cost_sd_over_agents": spread(per("cost_sum")),
+                "mean_excess": exc / trips if trips else None, "mean_excess_sd_over_agents": spread(per("excess_sum")),
+                "excess_over_cost": exc / cost if cost > 0 else None,
+                "share_zero_excess": int(ps["n_zero_excess"][1:].sum()) / trips if trips else None,
+                "off_tree_hops": int(pa["off_tree"][:, 1:].sum()),
+                "open_zero_excess": int((open_ & (pa["excess"] == 0.0) & (pa["off_tree"] == 0)).sum()),
+                "excess_over_travel_time": None, "mean_travel_time": None, "mean_residual": None}
+        if result.trips is not None and trips and int(result.trips["n_done"][1:].sum()) == trips:
+            tt = float(result.trips["tt_sum"][1:].astype(np.float64).sum())
+            wsum.update(excess_over_travel_time=exc / tt if tt > 0 else None, mean_travel_time=tt / trips,
+                        mean_residual=(tt - cost) / trips)
+        summary["weights"] = wsum
+        top = sorted((r for r in rows if r["excess_mean"] is not None and r["excess_mean"] > 0), key=lambda r: (-r["excess_mean"], r["agent"]))[:10]
+        summary["top_excess"] = [{k: r[k] for k in ("agent", "origin", "destination", "departure", "moves_mean", "cost_mean",
+                                                    "excess_mean", "n_loop", "arrival_share")} for r in top]
+    H = int(meta["num_bins"])
+    names = trip_bin_names(meta["first_bin"], H, meta["bin_seconds"])
+    dep_bin = trip_host_bin(meta["departure"][1:], meta["bin_seconds"], meta["first_bin"], H)
+    by_rows = []
+    for h in range(H):
+        m = dep_bin == h
+        t = int(live[m].sum())
+        s = lambda key: float(ps[key][1:][m].astype(np.float64).sum())      # noqa: E731
+        by_rows.append({"bin": names[h], "scheduled": int(m.sum()), "trips": t, "moves_mean": s("moves_sum") / t if t else None,
+                        "cost_mean": s("cost_sum") / t if t and has_w else None,
+                        "excess_mean": s("excess_sum") / t if t and has_w else None,
+                        "share_loop": int(ps["n_loop"][1:][m].sum()) / t if t else None,
+                        "share_truncated": int(ps["n_trunc"][1:][m].sum()) / t if t else None})
+    if pair is not None:
+        if paired:
+            bs = baseline.path_stats
+            nb = int(bs["n_both"][1:].sum())
+            pair.update(pairs=nb, mean_moves_diff=-float(bs["dmoves_sum"][1:].sum()) / nb if nb else None,
+                        mean_excess_diff=(-float(bs["dexcess_sum"][1:].sum()) / nb
+                                          if nb and has_w and baseline.path_meta["weights"] else None))
+        summary["paired"] = pair
+    return {"available": True, "head": result.head, "bin_seconds": int(meta["bin_seconds"]), "first_bin": int(meta["first_bin"]),
+            "bins": names, "columns": list(rows[0]) if rows else [], "rows": rows, "by_departure_columns": list(by_rows[0]),
+            "by_departure": by_rows, "summary": summary}
+
+
+def path_route_rows(result: "EvalResult", envs: int):
+    """The kept routes of the first ``envs`` environments as rows of ``eval_paths_routes.csv``: env, agent, roads, truncated,
+    route (the kept road ids, space-separated). Agents never seen are left out."""
+    routes, length = result.path_routes
+    roads = result.paths["roads"]
+    rows = []
+    for k in range(min(int(envs), roads.shape[0])):
+        for a in range(1, roads.shape[1]):
+            if roads[k, a] > 0:
+                rows.append({"env": k, "agent": a, "roads": int(roads[k, a]), "truncated": int(roads[k, a] > length[k, a]),
+                             "route": " ".join(str(int(u)) for u in routes[k, a, :length[k, a]])})
+    return rows
+
+
+def path_lines(report: dict):
+    """:func:`path_report` as printable lines (the ``Paths`` block)."""
+    if not report["available"]:
+        return [f"not available: {report['reason']}"]
+    s = report["summary"]
+    pct = lambda v: "-" if v is None else f"{100.0 * v:.2f} %"      # noqa: E731
+    out = [f"definition:            {s['note']}",
+           f"{'agents:':22} {s['agents']:12d}   seen as a head in every environment {s['seen_in_every']}, in some "
+           f"{s['seen_in_some']}, in none {s['seen_in_none']} ({s['envs']} environments, {s['frames_run']} frames; "
+           f"{s['trips']} trips completed; {s['max_hops']} roads kept per trace)",
+           f"{'mean moves:':22} {_f(s['mean_moves'], '12.3f')}    (trip-weighted; sd over the agents "
+           f"{_f(s['mean_moves_sd_over_agents'], '.3f')})"]
+    w = s["weights"]
+    if w is None:
+        out.append(f"{'path cost, excess:':22} {s['excess_note'] or 'not available (no edge weights): roads and loops only'}")
+    else:
+        out.append(f"{'mean path cost:':22} {_f(w['mean_cost'], '12.3f')} s  (sd over the agents {_f(w['mean_cost_sd_over_agents'], '.3f')})")
+        out.append(f"{'mean excess:':22} {_f(w['mean_excess'], '12.3f')} s  (wandering: cost beyond the shortest path; sd over the "
+                   f"agents {_f(w['mean_excess_sd_over_agents'], '.3f')})")
+        out.append(f"{'excess / path cost:':22} {_f(w['excess_over_cost'], '12.4f')}    (sum excess / sum path cost)")
+        if w["mean_travel_time"] is not None:
+            out.append(f"{'excess / travel time:':22} {_f(w['excess_over_travel_time'], '12.4f')}    (sum excess / sum travel time)")
+            out.append(f"{'travel time:':22} {w['mean_travel_time']:12.3f} s = shortest free-flow cost "
+                       f"{w['mean_cost'] - w['mean_excess']:.3f} + wandering {w['mean_excess']:.3f} + everything else "
+                       f"{w['mean_residual']:.3f} (travel time - path cost: the first road, queues and the wait for the "
+                       f"withdraw rule)")
+        out.append(f"{'completed trips:':22} zero excess {pct(w['share_zero_excess'])}, with a loop {pct(s['share_loop'])}, "
+                   f"truncated {pct(s['share_truncated'])}; {w['off_tree_hops']} off-tree hops in all traces")
+    o = s["open"]
+    out.append(f"{'not arrived:':22} {o['traces']} traces of agents seen but not DONE at the end: with a loop {o['with_loop']}, "
+               f"truncated {o['truncated']}" + (f", zero excess {w['open_zero_excess']}" if w is not None else "") +
+               f", mean moves {_f(o['mean_moves'])}")
+    if w is None:
+        out.append(f"{'completed trips:':22} with a loop {pct(s['share_loop'])}, truncated {pct(s['share_truncated'])}")
+    if s["top_excess"]:
+        out.append("agents with the largest mean excess:")
+        for r in s["top_excess"]:
+            out.append(f"  agent {r['agent']:7d}  {r['origin']:6d} -> {r['destination']:6d}  departs {r['departure']:9.1f}  moves "
+                       f"{r['moves_mean']:7.2f}  cost {r['cost_mean']:9.2f}  excess {r['excess_mean']:9.2f}  loops in "
+                       f"{r['n_loop']} trips  arrived in {100.0 * r['arrival_share']:.0f} %")
+    out.append(f"By departure time (bins of {report['bin_seconds']} s; over the completed trips of the agents that depart in the bin):")
+    out.append(f"  {'bin':>8} {'scheduled':>9} {'trips':>8} {'moves':>9} {'cost':>10} {'excess':>10} {'loop':>9} {'truncated':>9}")
+    for r in report["by_departure"]:
+        out.append(f"  {r['bin']:>8} {r['scheduled']:9d} {r['trips']:8d} {_f(r['moves_mean']):>9} {_f(r['cost_mean']):>10} "
+                   f"{_f(r['excess_mean']):>10} {pct(r['share_loop']):>9} {pct(r['share_truncated']):>9}")
+    p = s.get("paired")
+    if p is not None and not p["available"]:
+        out.append(f"paired:                not available: {p['reason']}")
+    elif p is not None:
+        out.append(f"{'policy - ' + p['baseline_head'] + ':':22} moves {_f(p['mean_moves_diff'], '.3f')}, excess "
+                   f"{_f(p['mean_excess_diff'], '.3f')} s mean paired difference over {p['pairs']} trips completed in both runs")
+    return out
+
+
+path_summary = _summary
+
+
 # ---- dynamic relative gap (VecEvaluator(dynamic_gap=True)) ------------------------------------------------------------------------
 DYNAMIC_GAP_NOTE = ("g = travel time - hindsight time: the hindsight time is the quickest way from origin to destination (both "
                     "roads traversed) under the road times of the run's own mean occupancy per time bin, waiting allowed; "

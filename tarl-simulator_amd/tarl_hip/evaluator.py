@@ -66,6 +66,7 @@ from .eval_reports import (CONGESTION_FILE, DYNAMIC_GAP_NOTE, LINK_EXPECTED, LIN
                            aggregate, capacity_threshold, dynamic_gap_lines, dynamic_gap_paired_lines, dynamic_gap_report,
                            dynamic_gap_summary, geh, link_bin_names, link_count_lines, link_count_report, link_count_summary,
                            link_moments, occupancy_bin_names, occupancy_lines, occupancy_report, occupancy_summary,
+                           path_lines, path_report, path_route_rows, path_summary,
                            trip_bin_names, trip_free_flow_times, trip_host_bin, trip_lines, trip_report, trip_summary,
                            turn_bin_names, turn_lines, turn_report, turn_summary)
 
@@ -159,6 +160,13 @@ class EvalResult:
     # the sum over the frames of -(on_way + ready), and {on_way, ready} after the last frame
     trip_return: list | None = None
     trip_parts_last: np.ndarray | None = field(default=None, compare=False)         # (K, 2) int64
+    # paths=True (never after a domain exit): the per-agent path trace of DESIGN 4.25
+    paths: dict | None = field(default=None, compare=False)                 # last_road, roads, revisits, off_tree int32, path_cost,
+    #                                                                         excess fp64, done bool: numpy arrays (K, A)
+    path_routes: tuple | None = field(default=None, compare=False)          # (routes (K, A, L) int32, route_len (K, A) = min(roads, L))
+    path_stats: dict | None = field(default=None, compare=False)            # ops.path_agent_stats, numpy arrays (A,)
+    path_meta: dict | None = field(default=None, compare=False)             # max_hops, weights, note, bins, origin, destination,
+    #                                                                         departure (A,), paired
 
     def to_dict(self, per_env=False):
         d = {k: getattr(self, k) for k in ("envs", "head", "deterministic", "frames_run", "domain_exit",
@@ -347,7 +355,8 @@ class VecEvaluator:
                  keep_actions=False, refresh_rate=10, baseline_dests=None, link_counts=False, link_bin_seconds=3600,
                  link_block=None, occupancy=False, occupancy_block=None, trips=False, trip_free_flow=None, dynamic_gap=False,
                  dynamic_gap_envs=None, turns=False, turn_block=None, routes=None, route_fallback=True, policy_hold=False,
-                 goal_mlp=None, goal_scale=None, route_departures=False, trip_reward=False):
+                 goal_mlp=None, goal_scale=None, route_departures=False, trip_reward=False, paths=False, path_max_hops=None,
+                 path_weights=None):
         """``engine``: a fused :class:`SimEngine` with K environments. ``emb``: flat (num_embeddings,) fp32 embedding
         (MPNNPolicyNet.nodes_embedding.weight); ``edge_mlp``: ops.EdgeMlpWeights (edge_mlp* heads); ``prior_table`` (N, N),
         or (N, D) with ``dest_slot`` (embedding_dijkstra); ``gt_pe`` (N, 16) and ``gt_weights``: ops.GtWeights
@@ -416,7 +425,21 @@ class VecEvaluator:
         and {on_way, ready} into a (T, K, 2) one. The queue ``reward`` buffer, ``episode_return`` and everything read from
         them stay exactly as they are; ``EvalResult.trip_return`` is the sum over the frames per environment (float64 on the
         host), ``trip_parts_last`` the two counts after the last frame, ``aggregate["trip_return"]`` its mean, standard
-        error and interval. The frames themselves do not change."""
+        error and interval. The frames themselves do not change.
+        ``paths`` (NOT in the reference; every head, the routers and ``"routes"`` included): the per-agent path
+        trace. ``run()`` resets its state before the first frame and queues one ``ops.fused_path_trace`` after every frame,
+        after every other launch of that frame: which roads every (environment, agent) was seen on as a FIFO head, up to
+        ``path_max_hops`` kept per trace (default 64; 0 keeps no routes), how many, the free-flow cost of the hops and how
+        much of it was detour. ``path_weights`` fp32 (E,): the edge weights of cost and detour (default: ``trip_free_flow``
+        where that is given, else none — the trace then counts roads only); the fp64 distances come from one
+        ``ops.destination_trees(want_dist=True)`` pass here over the distinct destinations of the agent tables
+        (``baseline_dests`` as for the routers). A route array that exceeds half the free device memory is refused here, with
+        its size; a distance table that does (measured after the route array is allocated) is left out, and with it the
+        weights, which the launch takes only together with it: the trace then counts roads and loops only and the report
+        says "path cost and excess not available". After the episode
+        summary one ``ops.path_agent_stats`` call; ``run()`` raises when the trace met what must not happen (``bad``: a head id
+        beyond the agent table, two sightings no edge connects) and checks the population as for ``trips``. The frames
+        themselves do not change; without the flag nothing is allocated and nothing is queued."""
         if engine.fs is None:
             raise _lib.TarlError("VecEvaluator needs the fused engine (ops.fused_path_supported): the packed state cannot "
                                  "represent this graph and there is no fall-back")
@@ -475,7 +498,10 @@ class VecEvaluator:
         self.turns = bool(turns)
         if turn_block is not None and not self.turns:
             raise ValueError("turn_block sizes the rings of the turn counts: it needs turns=True")
-        if self.link_counts or self._occ_acc_on or self.trips or self.turns:      # one binning for every binned report
+        self.paths = bool(paths)
+        if not self.paths and (path_max_hops is not None or path_weights is not None):
+            raise ValueError("path_max_hops and path_weights configure the per-agent path trace: they need paths=True")
+        if self.link_counts or self._occ_acc_on or self.trips or self.turns or self.paths:      # one binning for every binned report
             self.link_bin_seconds = int(link_bin_seconds)
             if self.link_bin_seconds < 1:
                 raise ValueError("link_bin_seconds must be >= 1")
@@ -517,6 +543,8 @@ class VecEvaluator:
             self.trip_ff = None if trip_free_flow is None else trip_free_flow_times(engine, trip_free_flow)
         elif trip_free_flow is not None:
             raise ValueError("trip_free_flow is the reference of the per-trip report: it needs trips=True")
+        if self.paths:
+            self._init_paths(path_max_hops, trip_free_flow if path_weights is None else path_weights, baseline_dests)
         # scratch, allocated once
         self.log_prob = torch.zeros(K, dtype=torch.float32, device=dev)
         self.action8 = torch.zeros((K, N), dtype=torch.uint8, device=dev)          # the last frame's action bytes
@@ -558,6 +586,46 @@ class VecEvaluator:
             if head == "graph_transformer":
                 n = int(_lib.load().tarl_policy_gt_fwd_scratch_floats(plan.handle, K))
                 self.gt_scratch = torch.empty(n, dtype=torch.float32, device=dev)
+
+    def _init_paths(self, max_hops, weights, baseline_dests):
+        """The state of the path trace and, with ``weights``, the distance table of its detour measure: once per evaluator."""
+        eng = self.eng
+        K, A, N, dev = eng.B, eng.A, eng.N, eng.device
+        L = 64 if max_hops is None else int(max_hops)
+        if not 0 <= L <= ops.PATH_MAX_HOPS:
+            raise ValueError(f"path_max_hops must be in [0, {ops.PATH_MAX_HOPS}] (ops.PATH_MAX_HOPS), got {max_hops!r}")
+        free = int(torch.cuda.mem_get_info(dev)[0])
+        need = 4 * K * A * L
+        if need > free // 2:
+            raise _lib.TarlError(f"the path trace's route array ({need / 2**30:.2f} GiB for K = {K} environments x A = {A} agents "
+                                 f"x path_max_hops = {L}) exceeds half the free device memory ({free / 2**30:.2f} GiB free): "
+                                 f"evaluate fewer environments at a time or keep fewer roads per trace")
+        self.path_state = ops.path_trace_state(K, A, L, dev)
+        free = int(torch.cuda.mem_get_info(dev)[0])      # what is left beside the state
+        self.path_w = self.path_dist = self.path_slot = self.path_note = None
+        if weights is None:
+            return
+        w = weights.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        if w.numel() != eng.E:
+            raise ValueError(f"path_weights must hold one weight per edge ({eng.E}), got {w.numel()}")
+        if baseline_dests is None:      # src.agents.base.destination_set's rule, as router_buffers applies it
+            d = torch.unique(eng.agents[..., 1].reshape(-1).to(torch.int64))
+            d = d[(d >= 0) & (d < N)].contiguous()
+            slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
+            slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=dev)
+            baseline_dests = (d, slot)
+        dests, slot = baseline_dests
+        need = 8 * int(dests.numel()) * N
+        if need > free // 2:
+            self.path_note = (f"path cost and excess not available: the distance table ({need / 2**30:.2f} GiB for D = "
+                              f"{int(dests.numel())} destinations x N = {N} roads), without which the launch takes no weights, "
+                              f"exceeds half the free device memory ({free / 2**30:.2f} GiB free)")
+            return
+        if dests.numel() == 0:
+            self.path_note = "path cost and excess not available: no destination in range"
+            return
+        _, self.path_dist = ops.destination_trees(eng.plan, w, dests.contiguous(), want_next_hop=False, want_dist=True)
+        self.path_w, self.path_slot = w, slot.contiguous()
 
     def _ring_block(self, ring_bytes, frame_bytes, cap=None):
         """The default block of a ring of per-frame slices: the most frames that fit ``ring_bytes``, at most ``poll_frames``
@@ -768,12 +836,14 @@ class VecEvaluator:
 
     # -- the evaluation ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def run(self, frames=None, deterministic=True, trip_pair=None):
+    def run(self, frames=None, deterministic=True, trip_pair=None, path_pair=None):
         """Reset the engine, run ``frames`` frames (default: until the episode ends) and return an :class:`EvalResult`.
         ``trip_pair`` (``trips=True``): the agent tables (K, A, 9) that another run on the same environments left behind
         (its ``engine.agents``, still on the device); this run's per-agent launch then also pairs the two, trip by trip:
         ``trips`` gains n_both, d_sum, d_sumsq, n_faster, n_slower with d = this run - the other (``trip_report`` of the OTHER
-        run takes this one as its ``baseline``)."""
+        run takes this one as its ``baseline``). ``path_pair`` (``paths=True``): ``(state, agents)`` of another run on the same
+        environments — its ``ops.PathTraceState`` (a ``clone()`` where that evaluator runs again) and agent tables; this
+        run's ``path_stats`` then also hold the paired sums of moves and excess, this run - the other."""
         t_start = time.perf_counter()
         eng, fs = self.eng, self.eng.fs
         T = self.episode_frames if frames is None else int(frames)
@@ -785,21 +855,28 @@ class VecEvaluator:
             raise ValueError(f"head {self.head!r} has no sampled mode: a plan is followed, nothing is drawn")
         if trip_pair is not None and not self.trips:
             raise ValueError("trip_pair pairs the trips of two runs: it needs trips=True")
+        if path_pair is not None and not self.paths:
+            raise ValueError("path_pair pairs the path traces of two runs: it needs paths=True")
         self._reserve(T)
         self._flag_host.zero_()
         fs.check_flags()            # whatever an earlier user of this engine left unread is theirs: raised, not averaged
         eng.reset()
-        if self.trips or self.dynamic_gap:
+        if self.trips or self.dynamic_gap or self.paths:
             pop = eng.agents[:, :, :3]
             if not bool((pop == pop[:1]).all()):
-                raise ValueError(f"{'trips=True' if self.trips else 'dynamic_gap=True'} needs the same population in every "
+                raise ValueError(f"{'trips=True' if self.trips else ('dynamic_gap=True' if self.dynamic_gap else 'paths=True')} needs the same population in every "
                                  "environment: ORIGIN, DESTINATION or DEPARTURE_TIME differ between the agent tables")
             if trip_pair is not None and (tuple(trip_pair.shape) != tuple(eng.agents.shape) or
                                           not bool((trip_pair[:, :, :3] == pop).all())):
                 raise ValueError("trip_pair must hold the same population as this engine's agent tables")
+            if path_pair is not None and (tuple(path_pair[1].shape) != tuple(eng.agents.shape) or
+                                          not bool((path_pair[1][:, :, :3] == pop).all())):
+                raise ValueError("path_pair must hold the same population as this engine's agent tables")
+        if self.paths:
+            ops.path_trace_reset(self.path_state)
         self._start(bool(deterministic))
         sched = H = None
-        if self.link_counts or self._occ_acc_on or self.trips or self.turns:      # one binning for every binned report
+        if self.link_counts or self._occ_acc_on or self.trips or self.turns or self.paths:      # one binning for every binned report
             t0, step, bins = int(eng.time), int(eng.timestep), self.link_bin_seconds
             H = (t0 + (T - 1) * step) // bins - t0 // bins + 1
             sched = _BinSchedule(t0, step, bins, t0 // bins, H)
@@ -830,6 +907,8 @@ class VecEvaluator:
             done = t + 1
             if self.trip_reward:        # the frame is complete: the travellers owed, beside the queue reward
                 ops.fused_trip_reward(eng.plan, fs, clock, out=self.trip_rw[t], parts=self.trip_parts[t])
+            if self.paths:              # after every other launch of the frame: who heads which road now
+                ops.fused_path_trace(eng.plan, fs, self.path_state, self.path_w, self.path_dist, self.path_slot)
             if self.link_counts and _due(done, self.link_block, T):         # one launch per block of the rings
                 ops.link_counts_accumulate(self.link_popped, self.link_withdrawn, self.link_acc,
                                            **sched.block(done, self.link_block))
@@ -867,6 +946,8 @@ class VecEvaluator:
             settings["route_departures"] = True
         if self.trip_reward:
             settings["trip_reward"] = True
+        if self.paths:                        # (without the flag the settings stay as they were)
+            settings.update(paths=True, path_max_hops=self.path_state.L)
         res = EvalResult(envs=eng.B, head=self.head, deterministic=bool(deterministic), frames_run=done, settings=settings)
         first = 0
         for j, (upto, _) in enumerate(polls):
@@ -917,6 +998,8 @@ class VecEvaluator:
             self._trip_reduce(res, trip_pair, sched)
         if self.dynamic_gap:
             self._gap_reduce(res, sched, done)
+        if self.paths:
+            self._path_reduce(res, path_pair, sched)
         res.computation_time_ms = (time.perf_counter() - t_start) * 1000.0
         return res
 
@@ -984,6 +1067,25 @@ class VecEvaluator:
                              destination=pop[:, 1].astype(np.int64), departure=pop[:, 2].copy(),
                              free_flow=None if self.trip_ff is None else self.trip_ff.cpu().numpy(),
                              paired=trip_pair is not None)
+
+    # -- the per-agent path trace ---------------------------------------------------------------------------------
+    def _path_reduce(self, res, path_pair, sched):
+        """The trace of a finished run into ``res``: one reduction per agent over the environments, then the check that
+        nothing impossible was seen, then the arrays on the host."""
+        eng, st = self.eng, self.path_state
+        stats = ops.path_agent_stats(st, eng.agents, *(path_pair if path_pair is not None else (None, None)))
+        bad = st.bad.cpu().numpy()
+        if bad.any():
+            raise _lib.TarlError(f"path trace: {int(bad.sum())} sightings of a head id beyond the agent table or of two roads "
+                                 f"that no edge connects (per environment: {bad.tolist()}); such a run is not reported")
+        res.paths = {k: v.cpu().numpy() for k, v in st.tensors().items() if k not in ("route", "bad")}
+        res.paths["done"] = (eng.agents[:, :, 8] == 1.0).cpu().numpy()
+        res.path_routes = (st.route.cpu().numpy(), st.route_len.cpu().numpy())
+        res.path_stats = {k: v.cpu().numpy() for k, v in stats.items()}
+        pop = eng.agents[0, :, :3].cpu().numpy()
+        res.path_meta = dict(max_hops=st.L, weights=self.path_w is not None, note=self.path_note, first_bin=sched.first_bin,
+                             bin_seconds=sched.bin_seconds, num_bins=sched.H, origin=pop[:, 0].astype(np.int64),
+                             destination=pop[:, 1].astype(np.int64), departure=pop[:, 2].copy(), paired=path_pair is not None)
 
     # -- the dynamic relative gap (DESIGN 4.17) ---------------------------------------------------------------------------------
     def _gap_reserve(self, sched):

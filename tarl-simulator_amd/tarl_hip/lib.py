@@ -174,6 +174,10 @@ SIGNATURES = {
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),
+    # the per-agent path trace (csrc/path_trace.hip): B, A, L, the eight state arrays / the packed state in front of them
+    "tarl_path_trace_reset": (C.c_int, [_i64, _i64, _i64] + [_p] * 8 + [_p]),
+    "tarl_fused_path_trace": (C.c_int, [_p, _p, _i64, _i32, _i64, _i64] + [_p] * 8 + [_p, _p, _p, _i64, _p]),
+    "tarl_path_agent_stats": (C.c_int, [_p] * 6 + [_i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p]),
 }
 
 

@@ -1187,6 +1187,148 @@ def fused_select_route(plan: Plan, fs, routes, route_len, choice8=None):
     return choice8
 
 
+# ---- the per-agent path trace (csrc/path_trace.hip; NOT reference semantics) ----------------------------------
+PATH_MAX_HOPS = 4096      # = TARL_PATH_MAX_HOPS of include/tarl_hip.h
+PATH_MAX_AGENTS = 1 << 24
+_PATH_STATE_SPEC = (("last_road", torch.int32), ("roads", torch.int32), ("revisits", torch.int32), ("off_tree", torch.int32),
+                    ("path_cost", torch.float64), ("excess", torch.float64))
+_PATH_I32 = ("n_done", "n_zero_excess", "n_loop", "n_trunc", "n_seen", "n_loop_all", "roads_max", "n_both")
+_PATH_F64 = ("moves_sum", "moves_sumsq", "cost_sum", "cost_sumsq", "excess_sum", "excess_sumsq", "dmoves_sum", "dmoves_sumsq",
+             "dexcess_sum", "dexcess_sumsq")
+
+
+class PathTraceState:
+    """The state of the per-agent path trace for B environments of A agents (row 0 the dummy) and at most L kept roads:
+    ``last_road``, ``roads``, ``revisits``, ``off_tree`` int32 (B, A), ``path_cost``, ``excess`` fp64 (B, A), ``route`` int32
+    (B, A, L) and ``bad`` int32 (B,). Allocated uninitialised: :func:`path_trace_reset` sets the initial values."""
+
+    def __init__(self, B, A, L, device):
+        B, A, L = int(B), int(A), int(L)
+        if B < 1 or not 1 <= A <= PATH_MAX_AGENTS:
+            raise ValueError(f"B must be >= 1 and A in [1, {PATH_MAX_AGENTS}], got B = {B}, A = {A}")
+        if not 0 <= L <= PATH_MAX_HOPS:
+            raise ValueError(f"L must be in [0, {PATH_MAX_HOPS}] (ops.PATH_MAX_HOPS), got {L}")
+        self.B, self.A, self.L = B, A, L
+        for name, dt in _PATH_STATE_SPEC:
+            setattr(self, name, torch.empty((B, A), dtype=dt, device=device))
+        self.route = torch.empty((B, A, L), dtype=torch.int32, device=device)
+        self.bad = torch.empty(B, dtype=torch.int32, device=device)
+
+    def tensors(self):
+        """name -> tensor, in the order of the C ABI."""
+        return {**{n: getattr(self, n) for n, _ in _PATH_STATE_SPEC}, "route": self.route, "bad": self.bad}
+
+    def clone(self):
+        """A copy of the state as it stands (the other run of a paired report, where this one is reset and run again)."""
+        c = object.__new__(PathTraceState)
+        c.B, c.A, c.L = self.B, self.A, self.L
+        for name, t in self.tensors().items():
+            setattr(c, name, t.clone())
+        return c
+
+    @property
+    def route_len(self):
+        """(B, A) int32: the kept roads of every trace, min(roads, L) — with ``route`` the pair the ``"routes"`` head takes."""
+        return self.roads.clamp(max=self.L)
+
+    def _ptrs(self):
+        B, A, L = self.B, self.A, self.L
+        for name, dt in _PATH_STATE_SPEC:
+            t = getattr(self, name)
+            _meta(t, dt, (B, A), f"state.{name}")
+            _check_dev(t, dt, f"state.{name}")
+        _meta(self.route, torch.int32, (B, A, L), "state.route")
+        _check_dev(self.route, torch.int32, "state.route")
+        _meta(self.bad, torch.int32, (B,), "state.bad")
+        _check_dev(self.bad, torch.int32, "state.bad")
+        return [getattr(self, n).data_ptr() for n, _ in _PATH_STATE_SPEC] + [self.route.data_ptr() if L else None,
+                                                                             self.bad.data_ptr()]
+
+
+def path_trace_state(B, A, L, device):
+    """-> :class:`PathTraceState` for B environments, A agents (row 0 the dummy) and L kept roads per trace (0: none)."""
+    return PathTraceState(B, A, L, device)
+
+
+def path_trace_reset(state: PathTraceState):
+    """The initial values of the trace (tarl_path_trace_reset): ``last_road`` and ``route`` -1, everything else 0."""
+    _lib.check(_lib.load().tarl_path_trace_reset(state.B, state.A, state.L, *state._ptrs(), _lib.current_stream()))
+    return state
+
+
+def fused_path_trace(plan: Plan, fs, state: PathTraceState, weights=None, dist=None, dest_slot=None):
+    """The sighting pass of the per-agent path trace on the packed state AFTER a frame (tarl_fused_path_trace):
+    every agent that heads a non-empty road it was not seen on last gains that road — ``roads`` + 1, the road into ``route``
+    while fewer than L are kept, ``revisits`` + 1 where the kept prefix already holds it — and, with ``weights`` fp32 (E,) in
+    original edge order, ``dist`` fp64 (D, N) and ``dest_slot`` int32 (N,) of :func:`destination_trees` (all three or none),
+    the hop's weight into ``path_cost`` and its reduced cost ``(w + dist[s][u]) - dist[s][p]`` towards the agent's own
+    destination into ``excess`` (``off_tree`` + 1 where that is not finite). ``fs`` is read, never written. ``state.bad``
+    counts what must not happen: a head id beyond the agent table, two sightings no edge connects."""
+    N, E = plan.num_nodes, plan.num_edges
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    if (state.B, state.A) != (fs.B, fs.A):
+        raise ValueError(f"state is for (B, A) = ({state.B}, {state.A}), the packed state for ({fs.B}, {fs.A})")
+    given = [t is not None for t in (weights, dist, dest_slot)]
+    if any(given) and not all(given):
+        raise ValueError("weights, dist and dest_slot come together: all three or none")
+    D = 0
+    if weights is not None:
+        _meta(weights, torch.float32, (E,), "weights")
+        if dist.dim() != 2:
+            raise ValueError(f"dist must be (D, {N}), got {tuple(dist.shape)}")
+        D = dist.size(0)
+        _meta(dist, torch.float64, (D, N), "dist")
+        _meta(dest_slot, torch.int32, (N,), "dest_slot")
+        for t, dt, name in ((weights, torch.float32, "weights"), (dist, torch.float64, "dist"),
+                            (dest_slot, torch.int32, "dest_slot")):
+            _check_dev(t, dt, name)
+    _lib.check(_lib.load().tarl_fused_path_trace(plan.handle, fs.ref, fs.B, fs.Nmax, fs.A, state.L, *state._ptrs(),
+                                                 _lib.ptr(weights), _lib.ptr(dist), _lib.ptr(dest_slot), D,
+                                                 _lib.current_stream()))
+    return state
+
+
+def path_agent_stats(state: PathTraceState, agents, state_b=None, agents_b=None, out=None):
+    """The trace reduced per agent over the K environments after an episode (tarl_path_agent_stats); ``agents`` fp32
+    (K, A, 9), read for the DONE flag. Returns a dict of (A,) arrays, entry 0 (the dummy) zero. Over the environments in which
+    the agent ARRIVED: ``n_done``, ``n_zero_excess`` (excess == 0 and no off-tree hop), ``n_loop`` (revisits > 0), ``n_trunc``
+    (roads > L) int32 and the fp64 sums and sums of squares ``moves_sum``, ``moves_sumsq`` (moves = max(roads - 1, 0)),
+    ``cost_sum``, ``cost_sumsq``, ``excess_sum``, ``excess_sumsq``; over all environments ``n_seen`` (roads > 0),
+    ``n_loop_all`` and ``roads_max``. ``state_b`` with ``agents_b``: a second run on the same environments (the baseline); the
+    dict gains, over the environments in which the agent arrived in BOTH, ``n_both`` and the sums ``dmoves_sum``,
+    ``dmoves_sumsq``, ``dexcess_sum``, ``dexcess_sumsq`` of this run minus the other. Every sum adds the environments in
+    ascending order: bit-identical from run to run. ``out`` = (int32 (8, A), fp64 (10, A)) to write into."""
+    K, A, abs_ = _trip_tables(agents, "agents")
+    if (state.B, state.A) != (K, A):
+        raise ValueError(f"state is for (K, A) = ({state.B}, {state.A}), agents for ({K}, {A})")
+    if (state_b is None) != (agents_b is None):
+        raise ValueError("state_b and agents_b come together")
+    pair = state_b is not None
+    bbs = 0
+    if pair:
+        Kb, Ab, bbs = _trip_tables(agents_b, "agents_b")
+        if (Kb, Ab) != (K, A) or (state_b.B, state_b.A) != (K, A):
+            raise ValueError(f"state_b and agents_b must be for (K, A) = ({K}, {A}) like this run's")
+        _check_dev(agents_b, torch.float32, "agents_b")
+        state_b._ptrs()
+    _check_dev(agents, torch.float32, "agents")
+    ptrs = state._ptrs()
+    if out is None:
+        out = (torch.zeros((8, A), dtype=torch.int32, device=agents.device),
+               torch.zeros((10, A), dtype=torch.float64, device=agents.device))
+    oi, of = out
+    _meta(oi, torch.int32, (8, A), "out[0]")
+    _meta(of, torch.float64, (10, A), "out[1]")
+    _check_dev(oi, torch.int32, "out[0]")
+    _check_dev(of, torch.float64, "out[1]")
+    _lib.check(_lib.load().tarl_path_agent_stats(ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], agents.data_ptr(), abs_,
+                                                 state_b.roads.data_ptr() if pair else None,
+                                                 state_b.excess.data_ptr() if pair else None, _lib.ptr(agents_b), bbs, K, A,
+                                                 state.L, oi.data_ptr(), of.data_ptr(), _lib.current_stream()))
+    ni, nf = (8, 10) if pair else (7, 6)
+    return {**{n: oi[j] for j, n in enumerate(_PATH_I32[:ni])}, **{n: of[j] for j, n in enumerate(_PATH_F64[:nf])}}
+
+
 def fused_hold_policy_actions(plan: Plan, fs, agent_features, choice8=None, held=None):
     """The hold rule of DESIGN 4.13a as a post-pass over the SELECTED_ROAD bytes a POLICY head has just written into ``fs``
     (tarl_fused_hold_policy_actions; an action shield, not the reference's rule): a row with a non-empty FIFO
