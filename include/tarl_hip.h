@@ -416,7 +416,8 @@ typedef struct tarl_fused {
    * was reserved and zero until the rule existed, so a caller that never heard of it has it off). Bit 0 is that rule; bit 1
    * (TARL_DEPARTURE_ROUTER) is the first-hop routing of tarl_fused_set_departure_router, whose arguments the library keeps
    * beside the handle: the struct itself does not grow. Bit 2 (TARL_TRIP_REWARD) is the trip reward of
-   * tarl_fused_set_trip_reward, kept the same way. Each setter leaves the others' bits alone. */
+   * tarl_fused_set_trip_reward, kept the same way; bit 3 (TARL_HEAD_CAPTURE) the head capture of
+   * tarl_fused_set_head_capture, likewise. Each setter leaves the others' bits alone. */
   int32_t policy_hold;
   /* device scratch of tarl_fused_bufs_bytes() bytes, 16-byte aligned (required by the frame / rollout entry points): the
    * library keeps a device-resident copy of this table of pointers there (written by a one-thread launch at the head of every
@@ -1280,6 +1281,66 @@ int tarl_fused_rollout_goal(const tarl_plan* plan, const tarl_fused* f, int64_t 
                             const int64_t* keep_ptr_host, const int32_t* keep_env, const int32_t* keep_slot, float* obs_keep,
                             float* logits_scratch, void* dist_scratch, int32_t* ins_scratch, uint8_t* choice8, float* log_prob,
                             float* reward, uint8_t* counts, tarl_stream stream);
+
+/* ---- per-decision PPO credit (credit = "decision"; csrc/decision_credit.hip) -------------------------------------
+ * NOT in the reference, off by default. TARL_ABI_VERSION is unchanged: nothing existing moved and tarl_fused did not grow.
+ * Every road's categorical is credited with the delay of the traveller it decided for: the FIFO head of the packed state as
+ * the frame before left it. wave64, no floating-point atomics: two runs are bit-identical.
+ * tarl_fused_head_rows: head_keep[slot[j]][u] (int32, row length N) = the head id of road u in environment env[j]
+ *   (hdp.x >> 8) where the count bits of hdp.x are not 0, and 0 otherwise, for j in [0, n). Reads hdp alone and writes
+ *   nothing of the packed state; a pair whose environment is outside [0, B) gets a row of zeros. env / slot: int32 [n] on the
+ *   device; the slots are the caller's (rows of head_keep).
+ * tarl_fused_set_head_capture: the switch for the T-frame rollouts of the state-dependent heads (bit TARL_HEAD_CAPTURE of
+ *   tarl_fused.policy_hold; head_keep is kept beside the handle and must outlive the switch). With on = 1 their shared loop
+ *   queues tarl_fused_head_rows for the kept pairs of frame t in front of that frame's head call, on the same stream, with
+ *   the slots of the observation keep list. With on = 0 (head_keep NULL) the loop queues exactly what it queued before.
+ * tarl_decision_advantage: the raw advantage of `rows` kept rows of ONE episode segment, before the engine is reset (it reads
+ *   the live agent table). Row j is frame[j], environment env[j], row slot[j] of head_keep / adv_raw (int32 [rows] each, on
+ *   the device). A decision (row, road u) with a = head_keep[slot][u] is LIVE when a > 0, a < num_agents, u has an out-edge,
+ *   d = (long) DESTINATION of agent a lies in [0, N), s = dest_slot[d] lies in [0, num_dests) and dist[s][u] (fp64
+ *   [num_dests][N], tarl_dest_trees' distances) is finite. a >= num_agents adds 1 to bad[0]. For a live decision, in fp64:
+ *   n = the number of frames k in [t, t_end) with times[k] < ARRIVAL_TIME (a lower-bound search of the clocks, times fp32
+ *   [num_times] on the device) where DONE == 1, else n = t_end - t and truncated[0] += 1; S(n) = n for decision_gamma == 1
+ *   and (1 - gamma^n) / (1 - gamma) otherwise; adv_raw = S(dist[s][u] / timestep) - S(n), rounded to fp32. adv_raw [.][N] is
+ *   written for every road of every listed row (0 where the decision is not live) and head_keep is set to 0 where it is not
+ *   live: head_keep > 0 is the live mask from then on. truncated / bad: int32 [1], integer atomics.
+ * tarl_decision_stats: stats3 = {sum, sum of squares, count} of adv_raw over the `elems` elements with head_keep > 0: the
+ *   layout and the two-stage fp64 scheme of tarl_advantage_stats (partial: 768 doubles of scratch), in a fixed order.
+ * tarl_graphdist_node_logprob: lp_node[m][u] = log(p_choice + 1e-8) with p = softmax(logits / temperature) over u's
+ *   out-edges in k_softmax's fp32 expressions (max subtracted, the sum left to right in CSR order); 0 where choice[m][u]
+ *   (int32 [M][N], an edge id in original order or -1) names no out-edge of u. Every element is written.
+ * tarl_graphdist_decision_ppo: the clipped objective on the live decisions (head[m][u] > 0 and a valid choice), in fp32:
+ *   A = (adv_raw - mean) / max(std, 1e-6) from stats3 (tarl_advantage_normalize's rule, unbiased std), lp as above,
+ *   r = exp(lp - lp_old_node), s = min(r A, clamp(r, 1 - eps, 1 + eps) A). out4 fp64 [M][4] = per sample {sum of s, live
+ *   decisions, those with r outside [1 - eps, 1 + eps], sum of (lp_old - lp)}, a fixed tree per tile of 256 nodes and the
+ *   tiles in order. grad_logits (optional) fp32 [M][E]: += on the out-edges e_j of a live node where the unclipped term is
+ *   the minimum (a tie flows), -grad_scale / L * r A * (p_c / (p_c + 1e-8)) * ([j == c] - p_j) / temperature with L =
+ *   n_live[0] (int32 on the device; nothing is added while L <= 0); every other element is left as it was. Every edge has one
+ *   source node, so every element has one writer. scratch: tarl_graphdist_decision_ppo_scratch_bytes(plan, M) bytes, 8-byte
+ *   aligned, every byte written before it is read; -1 for a null plan, M < 1 or 2^24 or more (sample, tile) pairs.
+ * Refused on the host, before any HIP call (a refused call writes nothing): a null argument (grad_logits alone may be null;
+ *   env / slot / head_keep of tarl_fused_head_rows only matter for n > 0), sizes below 1 or beyond the launch limits, N * B of
+ *   2^31 or more, num_agents outside [1, 2^24], t_end outside [1, num_times], timestep <= 0, decision_gamma outside (0, 1],
+ *   temperature <= 0, clip_epsilon outside [0, 1), a misaligned scratch, on outside {0, 1}, on without a buffer or a buffer
+ *   without on. */
+#define TARL_HEAD_CAPTURE 8
+int tarl_fused_head_rows(const tarl_plan* plan, const tarl_fused* f, int64_t B, const int32_t* env, const int32_t* slot,
+                         int64_t n, int32_t* head_keep, tarl_stream stream);
+int tarl_fused_set_head_capture(tarl_fused* f, int on, int32_t* head_keep);
+int tarl_decision_advantage(const tarl_plan* plan, int32_t* head_keep, const int32_t* frame, const int32_t* env,
+                            const int32_t* slot, int64_t rows, int64_t B, const float* agent_features, int64_t num_agents,
+                            int64_t a_bstride, const float* times, int64_t num_times, int64_t t_end, const double* dist,
+                            const int32_t* dest_slot, int64_t num_dests, float timestep, double decision_gamma,
+                            float* adv_raw, int32_t* truncated, int32_t* bad, tarl_stream stream);
+int tarl_decision_stats(const float* adv_raw, const int32_t* head_keep, int64_t elems, double* partial, double* stats3,
+                        tarl_stream stream);
+int tarl_graphdist_node_logprob(const tarl_plan* plan, const float* logits, int64_t M, float temperature,
+                                const int32_t* choice, float* lp_node, tarl_stream stream);
+int64_t tarl_graphdist_decision_ppo_scratch_bytes(const tarl_plan* plan, int64_t M);
+int tarl_graphdist_decision_ppo(const tarl_plan* plan, const float* logits, int64_t M, float temperature,
+                                const int32_t* choice, const int32_t* head, const float* lp_old_node, const float* adv_raw,
+                                const double* stats3, const int32_t* n_live, float clip_epsilon, float grad_scale,
+                                double* out4, float* grad_logits, void* scratch, tarl_stream stream);
 
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the

@@ -42,7 +42,8 @@ struct HeadRollout {
 // -> obs_keep (n may be 0), the logits of all environments -> logits_scratch. State-independent work belongs to t == 0.
 typedef int (*head_frame_fn)(const HeadRollout& a, void* ctx, int64_t t, const int32_t* env, const int32_t* slot, int64_t n);
 
-// Checks the common arguments once, then queues per frame: head -> tarl_graphdist_rollout_at (action bytes, log-prob,
+// Checks the common arguments once, then queues per frame: [the head ids of the frame's kept pairs, where bit
+// TARL_HEAD_CAPTURE of tarl_fused.policy_hold is set] -> head -> tarl_graphdist_rollout_at (action bytes, log-prob,
 // SELECTED_ROAD) -> [the hold rule, where bit 0 of tarl_fused.policy_hold is set] -> [the pending table and the first-hop
 // route launch, where its bit TARL_DEPARTURE_ROUTER is set] -> Direction -> rows -> insert, the count bytes written by the
 // frame kernels -> [the trip reward over the insert's reward, where its bit TARL_TRIP_REWARD is set].
@@ -70,6 +71,14 @@ int tarl_launch_departure_router(hipStream_t s, const tarl_plan* plan, const tar
 int tarl_check_trip_reward(const tarl_fused* f, int64_t B, int64_t A);
 int32_t* tarl_trip_reward_parts_of(const tarl_fused* f);
 int tarl_launch_trip_reward(hipStream_t s, const tarl_fused* f, int64_t B, int64_t A, float t, float* reward, int32_t* parts);
+
+// decision_credit.hip: the head capture inside the loop (tarl_fused_set_head_capture; bit TARL_HEAD_CAPTURE of
+// tarl_fused.policy_hold). tarl_head_capture_of: the buffer the setter registered for the handle, or NULL;
+// tarl_check_head_rows: the sizes of one launch over n pairs; tarl_launch_head_rows: the launch alone (n >= 1).
+int32_t* tarl_head_capture_of(const tarl_fused* f);
+int tarl_check_head_rows(const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t n);
+int tarl_launch_head_rows(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, const int32_t* env,
+                          const int32_t* slot, int64_t n, int32_t* head_keep);
 
 // the kept rows straight from the packed state (a head whose logits do not leave fp32 observations behind)
 static inline int tarl_head_keep_rows(const HeadRollout& a, const int32_t* env, const int32_t* slot, int64_t n) {

@@ -141,6 +141,20 @@ OPTIONS = (
                            "baseline and the days (one more line per block, `trip_return` in the JSON files and the "
                            "eval_envs.csv columns, a `trip_return` difference in the paired block); every other number stays "
                            "as it is")),
+    ("--credit", dict(choices=("joint", "decision"), default="joint",
+                      help="train, mpnn / mpnn+ppo: how PPO assigns credit. joint (default): the reference's update, one "
+                           "probability ratio over all roads' draws and one advantage per frame and environment. decision "
+                           "(DESIGN 4.26; not in the reference): every road that had a traveller at the head of its queue is "
+                           "credited on its own, with that traveller's frames until it was withdrawn (until the horizon if it "
+                           "never was) against its free-flow frames to go, and the ratio and the clip act on that road's "
+                           "choice alone; critic and entropy terms are unchanged. train_log.jsonl gains train/credit, "
+                           "train/decisions, train/decision_delay_frames, train/decision_truncated, "
+                           "train/decision_clip_fraction and train/decision_kl. Refused in eval mode, with --policy-head "
+                           "embedding and with --value-head graph_transformer; combines with --reward, --policy-hold, "
+                           "--route-departures and --pretrain-bc")),
+    ("--credit-gamma", dict(type=float, default=None, metavar="G",
+                            help="--credit decision: the discount of a traveller's frames to go, in (0, 1] (default 1.0); "
+                                 "separate from GAE's gamma")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "

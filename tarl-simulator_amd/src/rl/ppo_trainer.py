@@ -153,14 +153,20 @@ def vec_eval_record(prefix, res):
 def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_batch=32, num_epochs=1,
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
-              eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False, reward="queue"):
+              eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False, reward="queue",
+              credit="joint", decision_gamma=1.0):
     """``pretrain_bc`` (not in the reference; None = off): a dict {iterations, expert, driver, envs, frames,
     samples, epochs, batch, lr} — that many behaviour-cloning iterations (tarl_hip.imitation.BCTrainer) run before the first
     PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``.
     ``reward``: ``"trip"`` trains on the trip reward (VecPPOTrainer(reward="trip")); the log records gain
-    ``train/reward_kind`` and the ``eval_vec*`` evaluations run with ``trip_reward=True`` and log ``eval_vec/trip_return*``."""
+    ``train/reward_kind`` and the ``eval_vec*`` evaluations run with ``trip_reward=True`` and log ``eval_vec/trip_return*``.
+    ``credit``: ``"decision"`` trains with per-decision credit (VecPPOTrainer(credit="decision",
+    decision_gamma=...)); the log records gain ``train/credit``, ``train/decisions``, ``train/decision_delay_frames``,
+    ``train/decision_truncated``, ``train/decision_clip_fraction`` and ``train/decision_kl``."""
     if reward not in ("queue", "trip"):
         raise ValueError("reward must be 'queue' or 'trip'")
+    if credit not in ("joint", "decision"):
+        raise ValueError("credit must be 'joint' or 'decision'")
     trip = reward == "trip"
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
@@ -214,7 +220,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             gt_pe=getattr(policy_net, "gt_pe", None), **critic_kw,
                             **({"policy_hold": True} if policy_hold else {}),
                             **({"route_departures": True} if route_departures else {}),
-                            **({"reward": "trip"} if trip else {}))
+                            **({"reward": "trip"} if trip else {}),
+                            **({"credit": "decision", "decision_gamma": decision_gamma} if credit == "decision" else {}))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)
@@ -268,6 +275,11 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                 rec["train/departures_routed"] = float(trainer.departures_routed.sum()) / engine.B
             if trip:                      # PPO/avg_episode_return above is the return of the trip reward
                 rec["train/reward_kind"] = "trip"
+            if credit == "decision":      # the per-decision term of the last minibatch; loss/objective above is the joint one's 0
+                dl = {k: float(v) for k, v in trainer.last["decision"].items()}
+                rec.update({"train/credit": "decision", "train/decisions": int(dl["decisions"]),
+                            "train/decision_delay_frames": dl["delay_frames"], "train/decision_truncated": dl["truncated"],
+                            "train/decision_clip_fraction": dl["clip_fraction"], "train/decision_kl": dl["kl"]})
             if bool(done.any()):
                 rec["transport/avg_travel_time"] = float((ag0[done, 3] - ag0[done, 2]).mean())
         # periodic evaluation (src/rl/ppo_trainer.py:147-151): MODE rollout, optionally a sampled one, on eval_env

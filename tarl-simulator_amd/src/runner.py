@@ -44,6 +44,8 @@ class RunnerArgs:
     #                                (routers hold / free_flow) or replan_days; train with the state-dependent heads
     reward: str = "queue"          # "trip": the trip reward of DESIGN 4.24 — train: what PPO optimises (state-dependent heads);
     #                                eval: computed beside the queue reward with eval_envs, dijkstra_envs or replan_days
+    credit: str = "joint"          # train: "decision" = per-decision PPO credit (state-dependent heads, default critic)
+    credit_gamma: float = None     # ... the discount of a traveller's frames to go, in (0, 1] (default 1.0)
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
@@ -140,6 +142,24 @@ class RunnerArgs:
                                  "shared loop of the state-dependent heads, where the trip launch follows every frame's "
                                  "insert; use a state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer, "
                                  "goal_mlp)")
+        if self.credit not in ("joint", "decision"):
+            raise ValueError(f"credit must be 'joint' or 'decision', got {self.credit!r}")
+        if self.credit_gamma is not None and self.credit != "decision":
+            raise ValueError("credit_gamma discounts the per-decision return: it needs credit decision")
+        if self.credit == "decision":
+            if self.mode != "train":
+                raise ValueError("credit decision changes the PPO update: it needs mode 'train' (an evaluation has no update)")
+            if self.algo not in ("mpnn", "mpnn+ppo"):
+                raise ValueError("credit decision acts on vectorised training: it needs algo mpnn or mpnn+ppo")
+            if self.policy_head == "embedding":
+                raise ValueError("credit decision cannot train policy_head 'embedding': its rollout kernels draw the actions of "
+                                 "all frames ahead of the frames, so there is no frame state whose heads could be captured; "
+                                 "use a state-dependent head (edge_mlp*, embedding_dijkstra, graph_transformer, goal_mlp)")
+            if self.value_head == "graph_transformer":
+                raise ValueError("credit decision is not available with value_head 'graph_transformer': its observation store "
+                                 "keeps every frame, and per-decision buffers for all of them are out of scope")
+            if self.credit_gamma is not None and not 0.0 < float(self.credit_gamma) <= 1.0:
+                raise ValueError(f"credit_gamma must be in (0, 1], got {self.credit_gamma!r}")
         if self.eval_link_counts and not (self.eval_envs or self.dijkstra_envs):
             raise ValueError("eval_link_counts counts per-road pops and withdrawals in the vectorised evaluation: it needs "
                              "eval_envs > 0 or dijkstra_envs > 0")
@@ -429,7 +449,9 @@ class Runner:
                   num_envs=a.num_envs, seed=a.seed, eval_envs=a.eval_envs, stochastic_eval=a.eval_sampled,
                   eval_baseline=a.eval_baseline, **({"policy_hold": True} if a.policy_hold else {}),
                   **({"route_departures": True} if a.route_departures else {}),
-                  **({"reward": "trip"} if a.reward == "trip" else {}), **bc_kw)
+                  **({"reward": "trip"} if a.reward == "trip" else {}),
+                  **({"credit": "decision", "decision_gamma": 1.0 if a.credit_gamma is None else float(a.credit_gamma)}
+                     if a.credit == "decision" else {}), **bc_kw)
 
     def eval(self):
         a = self.args

@@ -171,6 +171,15 @@ SIGNATURES = {
     "tarl_fused_rollout_goal": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _f32, _p, _i64, _i64, _p, _i64, _i64, _p, _p,
                                           _f32, C.c_int, _p, _i64, _p, _f32, _p, _f32, _u64, _u64, _u64, _u64] +
                                 [_p] * 11 + [_p]),
+    # per-decision PPO credit (csrc/decision_credit.hip)
+    "tarl_fused_head_rows": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p]),
+    "tarl_fused_set_head_capture": (C.c_int, [_p, C.c_int, _p]),
+    "tarl_decision_advantage": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _f32,
+                                          _f64, _p, _p, _p, _p]),
+    "tarl_decision_stats": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "tarl_graphdist_node_logprob": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p]),
+    "tarl_graphdist_decision_ppo_scratch_bytes": (_i64, [_p, _i64]),
+    "tarl_graphdist_decision_ppo": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p, _p, _p, _p, _f32, _f32, _p, _p, _p, _p]),
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),

@@ -1591,6 +1591,174 @@ def graphdist_bc(plan: Plan, logits, labels, temperature=1.0, grad_scale=None, w
     return nll, n_lab, n_hit, grad
 
 
+# ---- per-decision PPO credit (csrc/decision_credit.hip; NOT reference semantics) -----------------------------------
+HEAD_CAPTURE = 8        # TARL_HEAD_CAPTURE: bit 3 of tarl_fused.policy_hold
+
+
+def _rows_n(t, dtype, N, name, rows=None):
+    """A contiguous device (rows, N) tensor of ``dtype``."""
+    _contig(t, dtype, name)
+    if t.dim() != 2 or t.size(1) != N or (rows is not None and t.size(0) != rows):
+        raise ValueError(f"{name} must be ({'rows' if rows is None else rows}, {N}), got {tuple(t.shape)}")
+    return t
+
+
+def _row_list(t, n, name):
+    _contig(t, torch.int32, name)
+    if t.dim() != 1 or (n is not None and t.numel() != n):
+        raise ValueError(f"{name} must be a 1-D int32 tensor{'' if n is None else f' of {n} entries'}, got {tuple(t.shape)}")
+    return t.numel()
+
+
+def fused_head_rows(plan: Plan, fs, env, slot, head_keep):
+    """``head_keep[slot[j]][u]`` (int32 (rows, N)) = the head agent id of road u in environment ``env[j]`` of ``fs`` where the
+    road's FIFO is not empty, 0 otherwise (tarl_fused_head_rows): whom each road's decision of the next frame is taken for.
+    ``env`` / ``slot``: int32 (n,) device tensors; the slots must be rows of ``head_keep`` (the kernel trusts them, as
+    :func:`fused_obs16_rows` trusts its own). Reads ``fs.hdp`` alone."""
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    n = _row_list(env, None, "env")
+    _row_list(slot, n, "slot")
+    _rows_n(head_keep, torch.int32, plan.num_nodes, "head_keep")
+    _lib.check(_lib.load().tarl_fused_head_rows(plan.handle, fs.ref, fs.B, env.data_ptr(), slot.data_ptr(), n,
+                                                head_keep.data_ptr(), _lib.current_stream()))
+    return head_keep
+
+
+def fused_set_head_capture(fs, on, head_keep=None, plan=None):
+    """The switch of the state-dependent T-frame rollouts (tarl_fused_set_head_capture): with ``on`` their loop queues
+    :func:`fused_head_rows` for the kept (environment, slot) pairs of every frame in front of that frame's head call, into
+    ``head_keep`` (int32 (rows, N), kept alive on ``fs``; its rows are the rows of the rollout's ``obs_keep``). Off (the
+    default, ``head_keep`` None) the loop queues exactly the launches it always queued."""
+    if on:
+        if head_keep is None:
+            raise ValueError("the switch needs its head_keep buffer")
+        _contig(head_keep, torch.int32, "head_keep")
+        if head_keep.dim() != 2 or (plan is not None and head_keep.size(1) != plan.num_nodes):
+            raise ValueError(f"head_keep must be (rows, N), got {tuple(head_keep.shape)}")
+    elif head_keep is not None:
+        raise ValueError("a head_keep buffer without the switch")
+    _lib.check(_lib.load().tarl_fused_set_head_capture(fs.ref, 1 if on else 0, _lib.ptr(head_keep)))
+    fs.head_keep = head_keep
+
+
+def decision_advantage(plan: Plan, head_keep, frame, env, slot, agent_features, times, t_end, dist, dest_slot, *, B,
+                       timestep, decision_gamma=1.0, adv_raw, truncated, bad):
+    """The raw per-decision advantage of the kept rows of ONE episode segment (tarl_decision_advantage), to be called
+    before the engine is reset: row j is frame ``frame[j]``, environment ``env[j]``, row ``slot[j]`` of ``head_keep`` /
+    ``adv_raw`` ((rows, N) int32 / fp32). ``times`` (T + 1,) fp32 device clocks, ``t_end``: the segment ends after frame
+    t_end - 1; ``dist`` (D, N) float64 free-flow distances of :func:`destination_trees`, ``dest_slot`` (N,) int32.
+    Writes ``adv_raw`` of every road of the listed rows (0 where not live), clears ``head_keep`` where the decision is not
+    live, and adds to ``truncated`` / ``bad`` (int32 (1,))."""
+    N = plan.num_nodes
+    n = _row_list(frame, None, "frame")
+    _row_list(env, n, "env")
+    _row_list(slot, n, "slot")
+    _rows_n(head_keep, torch.int32, N, "head_keep")
+    _rows_n(adv_raw, torch.float32, N, "adv_raw", head_keep.size(0))
+    A, abs_ = _agents(agent_features, B)
+    _contig(times, torch.float32, "times")
+    _contig(dist, torch.float64, "dist")
+    _contig(dest_slot, torch.int32, "dest_slot")
+    if times.dim() != 1 or dist.dim() != 2 or dist.size(1) != N or tuple(dest_slot.shape) != (N,):
+        raise ValueError(f"times must be 1-D, dist (D, {N}) and dest_slot ({N},), got {tuple(times.shape)}, "
+                         f"{tuple(dist.shape)} and {tuple(dest_slot.shape)}")
+    for nm, t_ in (("truncated", truncated), ("bad", bad)):
+        _contig(t_, torch.int32, nm)
+        if t_.numel() != 1:
+            raise ValueError(f"{nm} must hold one int32")
+    if not 1 <= int(t_end) <= times.numel():
+        raise ValueError(f"t_end must be in [1, {times.numel()}], got {t_end}")
+    if not (float(timestep) > 0.0 and 0.0 < float(decision_gamma) <= 1.0):
+        raise ValueError("timestep must be positive and decision_gamma in (0, 1]")
+    _lib.check(_lib.load().tarl_decision_advantage(
+        plan.handle, head_keep.data_ptr(), frame.data_ptr(), env.data_ptr(), slot.data_ptr(), n, int(B),
+        agent_features.data_ptr(), A, abs_, times.data_ptr(), times.numel(), int(t_end), dist.data_ptr(), dest_slot.data_ptr(),
+        dist.size(0), float(timestep), float(decision_gamma), adv_raw.data_ptr(), truncated.data_ptr(), bad.data_ptr(),
+        _lib.current_stream()))
+    return adv_raw
+
+
+def decision_stats(adv_raw, head_keep):
+    """-> float64 (3,) = {sum, sum of squares, count} of ``adv_raw`` over the elements with ``head_keep > 0``
+    (tarl_decision_stats): :func:`advantage_stats` with a mask, the layout :func:`advantage_normalize_` reads."""
+    _contig(adv_raw, torch.float32, "adv_raw")
+    _contig(head_keep, torch.int32, "head_keep")
+    if adv_raw.shape != head_keep.shape or adv_raw.numel() < 1:
+        raise ValueError(f"adv_raw and head_keep must have one non-empty shape, got {tuple(adv_raw.shape)} and "
+                         f"{tuple(head_keep.shape)}")
+    partial = torch.empty(768, dtype=torch.float64, device=adv_raw.device)
+    stats = torch.empty(3, dtype=torch.float64, device=adv_raw.device)
+    _lib.check(_lib.load().tarl_decision_stats(adv_raw.data_ptr(), head_keep.data_ptr(), adv_raw.numel(), partial.data_ptr(),
+                                               stats.data_ptr(), _lib.current_stream()))
+    return stats
+
+
+def _decision_logits(plan: Plan, logits, temperature):
+    _contig(logits, torch.float32, "logits")
+    if logits.dim() != 2 or logits.size(1) != plan.num_edges or logits.size(0) < 1:
+        raise ValueError(f"logits must be (M, {plan.num_edges}) with M >= 1, got {tuple(logits.shape)}")
+    if not float(temperature) > 0.0:
+        raise ValueError("temperature must be positive")
+    return logits.size(0)
+
+
+def graphdist_node_logprob(plan: Plan, logits, choice, temperature=1.0, out=None):
+    """-> fp32 (M, N): log(p_choice + 1e-8) of every node's categorical over its out-edges, p = softmax(logits /
+    temperature) (tarl_graphdist_node_logprob); 0 where ``choice`` (int32 (M, N), the edge ids :func:`rollout_gather`
+    returns, -1: none) names no out-edge of the node. The sum over the nodes is GraphDistribution's joint log-prob."""
+    M = _decision_logits(plan, logits, temperature)
+    _rows_n(choice, torch.int32, plan.num_nodes, "choice", M)
+    if out is None:
+        out = torch.empty((M, plan.num_nodes), dtype=torch.float32, device=logits.device)
+    _rows_n(out, torch.float32, plan.num_nodes, "out", M)
+    _lib.check(_lib.load().tarl_graphdist_node_logprob(plan.handle, logits.data_ptr(), M, float(temperature),
+                                                       choice.data_ptr(), out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def graphdist_decision_ppo(plan: Plan, logits, choice, head, lp_old_node, adv_raw, stats3, n_live, *, clip_epsilon=0.2,
+                           temperature=1.0, grad_scale=1.0, grad_logits=None, scratch=None):
+    """The clipped PPO objective per live decision, forward and backward (tarl_graphdist_decision_ppo).
+    ``logits`` fp32 (M, E); ``choice`` / ``head`` int32 (M, N) (``head > 0``: live), ``lp_old_node`` / ``adv_raw`` fp32
+    (M, N); ``stats3`` float64 (3,) of :func:`decision_stats` (all-reduced where the statistic is global); ``n_live`` int32
+    (1,) on the device: the live decisions of this minibatch, the L of the mean. -> float64 (M, 4) = per sample {sum of the
+    clipped gains, live decisions, ratios outside the clip, sum of lp_old - lp}. ``grad_logits`` fp32 (M, E) (optional):
+    the gradient of -(1 / L) * sum of the gains times ``grad_scale`` is ADDED on the out-edges of the live nodes."""
+    L = _lib.load()
+    N = plan.num_nodes
+    M = _decision_logits(plan, logits, temperature)
+    need = int(L.tarl_graphdist_decision_ppo_scratch_bytes(plan.handle, M))
+    if need < 0:
+        raise _lib.TarlError("tarl_graphdist_decision_ppo_scratch_bytes refused the sizes")
+    if scratch is not None and scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch holds {scratch.numel() * scratch.element_size()} bytes, tarl_graphdist_decision_ppo needs "
+                         f"{need}")
+    _rows_n(choice, torch.int32, N, "choice", M)
+    _rows_n(head, torch.int32, N, "head", M)
+    _rows_n(lp_old_node, torch.float32, N, "lp_old_node", M)
+    _rows_n(adv_raw, torch.float32, N, "adv_raw", M)
+    _contig(stats3, torch.float64, "stats3")
+    _contig(n_live, torch.int32, "n_live")
+    if stats3.numel() != 3 or n_live.numel() != 1:
+        raise ValueError("stats3 must hold three float64 and n_live one int32")
+    if not 0.0 <= float(clip_epsilon) < 1.0:
+        raise ValueError("clip_epsilon must be in [0, 1)")
+    if grad_logits is not None:
+        _contig(grad_logits, torch.float32, "grad_logits")
+        if grad_logits.shape != logits.shape:
+            raise ValueError(f"grad_logits must be {tuple(logits.shape)}, got {tuple(grad_logits.shape)}")
+    if scratch is None:
+        scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=logits.device)
+    elif not scratch.is_cuda or not scratch.is_contiguous():
+        raise _lib.TarlError("scratch must be a contiguous tensor on the GPU")
+    out4 = torch.empty((M, 4), dtype=torch.float64, device=logits.device)
+    _lib.check(L.tarl_graphdist_decision_ppo(plan.handle, logits.data_ptr(), M, float(temperature), choice.data_ptr(),
+                                             head.data_ptr(), lp_old_node.data_ptr(), adv_raw.data_ptr(), stats3.data_ptr(),
+                                             n_live.data_ptr(), float(clip_epsilon), float(grad_scale), out4.data_ptr(),
+                                             _lib.ptr(grad_logits), scratch.data_ptr(), _lib.current_stream()))
+    return out4
+
+
 def graphdist_mode(plan: Plan, proba, *, want_choice=False):
     L = _lib.load()
     _contig(proba, torch.float32, "proba")

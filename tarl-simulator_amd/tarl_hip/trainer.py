@@ -71,7 +71,7 @@ class VecPPOTrainer:
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
                  prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None,
-                 route_departures=False, reward="queue"):
+                 route_departures=False, reward="queue", credit="joint", decision_gamma=1.0):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -96,7 +96,15 @@ class VecPPOTrainer:
         ``"trip"`` (an environment-side rule, not in the reference) is -(agents on the way + waiting agents that are due),
         so that a lost agent and a blocked departure keep costing until the horizon: ``collect()`` sets the switch of the
         shared rollout loop (ops.fused_set_trip_reward) and ``self.reward`` then holds the trip reward; GAE, the critic and
-        the update read it as before. State-dependent heads on the fused path only."""
+        the update read it as before. State-dependent heads on the fused path only.
+        ``credit``: ``"joint"`` (the default) is the reference's update, one ratio and one advantage per (frame,
+        environment); ``"decision"`` (not in the reference) credits every road's categorical with the delay of the traveller
+        at the head of its FIFO beyond free flow: ``collect()`` captures the heads of the kept rows (ops.fused_set_head_capture)
+        and takes their raw advantages per segment (ops.decision_advantage), ``minibatch_step`` replaces the joint policy term
+        by ops.graphdist_decision_ppo; critic and entropy terms are unchanged. ``decision_gamma``: the discount of a
+        traveller's frames to go, separate from GAE's ``gamma``. State-dependent heads on the fused path with the default
+        critic only. ``self.last["decision"]`` then carries the live decisions, their mean delay in frames, the truncated
+        share, the objective, the clip fraction and the approximate KL of the last minibatch (0-d device tensors)."""
         self.eng = engine
         # policy: "embedding" = the reference's live head (logit = embedding of the target road: state-independent, its
         # distribution is tabulated once per update); "edge_mlp" = the per-edge MLP head it carries as parameters
@@ -214,6 +222,12 @@ class VecPPOTrainer:
         if reward == "trip" and engine.fs is None:
             raise ops._lib.TarlError("reward='trip' needs the fused engine (ops.fused_path_supported): the packed state "
                                      "cannot represent this graph and there is no fall-back")
+        if credit not in ("joint", "decision"):
+            raise ValueError("credit must be 'joint' or 'decision'")
+        self.credit = credit
+        self.decision_gamma = float(decision_gamma)
+        if credit == "decision":
+            self._check_decision_credit(engine, value)
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
@@ -298,6 +312,49 @@ class VecPPOTrainer:
         self.done_mask = None
         self.obs_idx = None
         self.stage = NoStageTimer()          # bench.py swaps in a StageTimer for its update_path object
+
+    def _check_decision_credit(self, engine, value):
+        """Refusals of credit="decision", each naming its limit; its counters and the slot of the distance table."""
+        if not self.state_dep:
+            raise ValueError("credit='decision' is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
+                             "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
+                             "in front of a frame's draw where the heads of that frame's state could be captured; "
+                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+        if engine.fs is None:
+            raise ops._lib.TarlError("credit='decision' needs the fused engine (ops.fused_path_supported): the packed state "
+                                     "cannot represent this graph and there is no fall-back")
+        if value == "graph_transformer":
+            raise ValueError("credit='decision' is not available for value='graph_transformer': its observation store keeps "
+                             "every one of the T * B frames, and per-decision buffers for T * B rows are out of scope; use "
+                             "the default critic (value='simple')")
+        if not 0.0 < self.decision_gamma <= 1.0:
+            raise ValueError("decision_gamma must be in (0, 1]")
+        dev = engine.device
+        self.decision_truncated = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.decision_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._decision_dist = None          # (dist float64 (D, N), dest_slot int32 (N,)): built once, after the first reset
+        self.head_keep = self.adv_raw = self.lp_old_node = None
+
+    def _build_decision_dist(self):
+        """Free-flow shortest-path distances to every distinct destination (ops.destination_trees on the travel times of the
+        empty network, as the departure router and the path trace build theirs): the baseline of the per-decision return."""
+        eng = self.eng
+        N, dev = eng.N, eng.device
+        d = torch.unique(eng.agents[..., 1].reshape(-1).to(torch.int64))      # src.agents.base.destination_set's rule
+        d = d[(d >= 0) & (d < N)].contiguous()
+        if d.numel() == 0:
+            raise ValueError("credit='decision': no agent has a destination in range")
+        free = int(torch.cuda.mem_get_info(dev)[0])
+        if 8 * d.numel() * N > free // 2:
+            raise ValueError(f"credit='decision': the free-flow distance table ({8 * d.numel() * N / 2**30:.2f} GiB for D = "
+                             f"{d.numel()} destinations x N = {N} roads) exceeds half the free device memory "
+                             f"({free / 2**30:.2f} GiB free)")
+        slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        slot[d] = torch.arange(d.numel(), dtype=torch.int32, device=dev)
+        w = ops.fused_edge_travel_time(eng.plan, eng.fs)[0].contiguous()      # after the reset every count is 0: free flow
+        _, dist = ops.destination_trees(eng.plan, w, d, want_next_hop=False, want_dist=True)
+        self._decision_dist = (dist, slot)
 
     GTV_FWD_CHUNK_BYTES = 1 << 30      # scratch of one all-frames critic call: the store is evaluated in chunks of rows
 
@@ -402,6 +459,11 @@ class VecPPOTrainer:
                 ops.fused_set_trip_reward(eng.fs, True)
             if self.state_dep:
                 self._draw_minibatch_frames()
+                if self.credit == "decision":       # and in front of every frame's head: whom the kept rows decide for
+                    if self._decision_dist is None:
+                        self._build_decision_dist()
+                    self.decision_truncated.zero_()
+                    ops.fused_set_head_capture(eng.fs, True, self.head_keep, plan=eng.plan)
             else:
                 emb = self._emb()
                 eng.prepare_policy(emb, self.temperature)      # once per parameter update, not per frame
@@ -411,7 +473,12 @@ class VecPPOTrainer:
                 self.poll_flags()
             for sl in self._segments(done):
                 host_times += self._queue(sl)[:-1]
+                if self.credit == "decision":       # before _segments resets the engine: the agent table is this segment's
+                    self._decision_advantage(sl, host_times)
             host_times.append(float(eng.time))
+            if self.credit == "decision":
+                ops.fused_set_head_capture(eng.fs, False)
+                self._bad_host.copy_(self.decision_bad, non_blocking=True)
             if self.policy_hold:        # off again: whoever else runs this engine gets the loop as it always was
                 ops.fused_set_policy_hold(eng.fs, False)
             if self.route_departures:
@@ -468,6 +535,21 @@ class VecPPOTrainer:
                     eng.reset()
                     self.counts[t].zero_()
 
+    def _decision_advantage(self, sl, host_times):
+        """The raw per-decision advantages of the kept rows of segment ``sl`` (ops.decision_advantage), from the agent table
+        as the segment's last frame left it."""
+        eng = self.eng
+        t_sorted, keep_env, keep_slot = self._keep
+        lo, hi = bisect_left(t_sorted, sl.start), bisect_left(t_sorted, sl.stop)
+        if hi == lo:
+            return
+        self.times[sl.start:sl.stop].copy_(torch.tensor(host_times[sl.start:sl.stop], dtype=torch.float32))
+        dist, slot = self._decision_dist
+        ops.decision_advantage(eng.plan, self.head_keep, self._keep_frames[lo:hi], keep_env[lo:hi], keep_slot[lo:hi],
+                               eng.agents, self.times, sl.stop, dist, slot, B=eng.B, timestep=eng.timestep,
+                               decision_gamma=self.decision_gamma, adv_raw=self.adv_raw, truncated=self.decision_truncated,
+                               bad=self.decision_bad)
+
     def _draw_minibatch_frames(self):
         """State-dependent heads: the update only ever reads the observations of its minibatch frames, and those frames are
         a random draw that does not depend on the data. The draw is made up front and the rollout keeps only their
@@ -494,6 +576,12 @@ class VecPPOTrainer:
                       (flat[order] % B).to(torch.int32).pin_memory().to(eng.device, non_blocking=True),
                       order.to(torch.int32).pin_memory().to(eng.device, non_blocking=True))
         self.obs_mb = torch.empty((flat.numel(), N, 16), dtype=torch.float32, device=eng.device)
+        if self.credit == "decision":       # per kept row and road: the head, its raw advantage, the behaviour log-prob
+            self._keep_frames = torch.tensor(self._keep[0], dtype=torch.int32).pin_memory().to(eng.device, non_blocking=True)
+            if self.head_keep is None or self.head_keep.size(0) != flat.numel():
+                self.head_keep = torch.empty((flat.numel(), N), dtype=torch.int32, device=eng.device)
+                self.adv_raw = torch.empty((flat.numel(), N), dtype=torch.float32, device=eng.device)
+                self.lp_old_node = torch.empty((flat.numel(), N), dtype=torch.float32, device=eng.device)
 
     def _queue(self, sl):
         """Frames ``sl`` (one episode segment) in one foreign call; returns the clock values. The embedding head draws from
@@ -539,11 +627,19 @@ class VecPPOTrainer:
             self._flag_event = None
             if int(self._flag_host[0]) != 0:
                 self.eng.check_flags()
+            if self.credit == "decision" and int(self._bad_host[0]) != 0:
+                self._raise_bad_heads(int(self._bad_host[0]))
 
     def check_flags(self):
         """Blocking form of :meth:`poll_flags` (call at a synchronisation point, e.g. the end of training)."""
         self._flag_event = None
         self.eng.check_flags()
+        if self.credit == "decision" and int(self.decision_bad.item()) != 0:
+            self._raise_bad_heads(int(self.decision_bad.item()))
+
+    def _raise_bad_heads(self, n):
+        raise ops._lib.TarlError(f"credit='decision': {n} captured head ids lie at or beyond the agent table's {self.eng.A} "
+                                 "rows: the packed state and the agent table do not belong together")
 
     # -- HOT LOOP B -------------------------------------------------------------------------------------------------------
     def _actor_logits(self, obs):
@@ -681,6 +777,8 @@ class VecPPOTrainer:
                 # walking all N columns alone took 743 us, bench.py's update_path; spread over the columns: see DESIGN §4.7)
                 value, h1, h2 = ops.critic_forward(cw, counts_mb, time_mb, 1, keep_hidden=True, split_k=M <= 16384)
         scale = 1.0 / self.world
+        if self.credit == "decision":       # the policy term is the per-decision one below: no joint gradient (g_lp = 0)
+            adv_mb = torch.zeros_like(adv_mb)
         with st("ppo_loss"):
             out, g_lp, g_ent, g_val = ops.ppo_loss(lp_new, lp_old, adv_mb, value, tgt_mb, ent,
                                                    clip_epsilon=self.clip_epsilon, entropy_coef=self.entropy_coef,
@@ -690,6 +788,9 @@ class VecPPOTrainer:
         with st("graphdist_bwd"):
             g_logits = ops.graphdist_logprob_entropy_bwd(eng.plan, proba, self.temperature, choice=choice_mb,
                                                          grad_log_prob=g_lp, grad_entropy=g_ent, log_prob_fwd=lp_new)
+        if self.credit == "decision":
+            with st("decision_ppo"):
+                self._decision_step(logits, choice_mb, off, M, scale, g_logits)
         with st("actor_logits_bwd"):
             self._actor_logits_bwd(obs, g_logits)
         with st("critic_bwd"):
@@ -711,12 +812,57 @@ class VecPPOTrainer:
             self.flat.adam_step(lr=self.lr)
         return out
 
+    def _decision_prepare(self):
+        """credit="decision", after ``collect()`` and before the first optimiser step: the behaviour log-prob of every
+        (kept row, road) from the forward the update uses, on the kept observations with the parameters the rollout used, and
+        the statistics of the raw advantage over all live decisions of all kept rows (all ranks')."""
+        eng = self.eng
+        off = 0
+        for idx in self._mb_idx:
+            M = idx.numel()
+            choice_mb, _ = ops.rollout_gather(eng.plan, self.T, eng.B, False, idx, choice=self.choice)
+            ops.graphdist_node_logprob(eng.plan, self._actor_logits(self.obs_mb[off:off + M]), choice_mb, self.temperature,
+                                       out=self.lp_old_node[off:off + M])
+            off += M
+        self._decision_local = ops.decision_stats(self.adv_raw, self.head_keep)      # this rank's {sum, sum of squares, count}
+        self._decision_stats = self._decision_local.clone()
+        dist_utils.allreduce_sum_(self._decision_stats)
+        self._decision_last = None
+
+    def _decision_step(self, logits, choice_mb, off, M, scale, g_logits):
+        """The per-decision policy term of one minibatch (rows ``off .. off + M`` of the kept buffers): its gradient is
+        added into ``g_logits`` on the out-edges of the live roads."""
+        head = self.head_keep[off:off + M]
+        n_live = (head > 0).sum(dtype=torch.int32).reshape(1)
+        need = (ops._lib.load().tarl_graphdist_decision_ppo_scratch_bytes(self.eng.plan.handle, M) + 7) // 8
+        if getattr(self, "_decision_scratch", None) is None or self._decision_scratch.numel() < need:
+            self._decision_scratch = torch.empty(need, dtype=torch.float64, device=self.eng.device)      # once per trainer
+        out4 = ops.graphdist_decision_ppo(self.eng.plan, logits, choice_mb, head, self.lp_old_node[off:off + M],
+                                          self.adv_raw[off:off + M], self._decision_stats, n_live,
+                                          clip_epsilon=self.clip_epsilon, temperature=self.temperature, grad_scale=scale,
+                                          grad_logits=g_logits, scratch=self._decision_scratch)
+        self._decision_last = (out4.sum(0), n_live)
+
+    def _decision_report(self):
+        """``self.last["decision"]``: 0-d device tensors (no synchronisation here)."""
+        tot, _ = self._decision_last
+        live = tot[1].clamp(min=1.0)
+        st = self._decision_local
+        cnt = st[2].clamp(min=1.0)
+        return {"decisions": st[2], "delay_frames": -st[0] / cnt,
+                "truncated": self.decision_truncated[0].to(torch.float64) / cnt, "objective": -tot[0] / live,
+                "clip_fraction": tot[2] / live, "kl": tot[3] / live}
+
     def update(self):
         out = None
+        if self.credit == "decision":
+            self._decision_prepare()
         for _ in range(self.num_epochs):
             adv, target = self.advantages()
             out = self.minibatch_step(adv, target)
         self.last = {"losses": out}
+        if self.credit == "decision":
+            self.last["decision"] = self._decision_report()
         return out
 
     def train_iteration(self):

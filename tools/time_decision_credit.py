@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Developer tool for DESIGN 4.26: per-decision PPO credit (``--credit decision``). Everything printed also goes to --log
+(default profiles/decision_credit_time.log).
+
+  (a) cost, with HIP events, median of --reps with min - max: tarl_fused_head_rows for the kept pairs of one frame; one
+      ``collect()`` with and without the capture (variants alternating, per frame); and the stages of one minibatch step
+      (``decision_ppo`` beside ``graphdist_bwd`` and ``actor_logits_bwd`` at the same M), on the 8 x 8 torus and on the geometry
+      of BASELINE config 4 (25 x 25 torus, 2 500 roads, 16 384 agents), goal_mlp head, --envs environments.
+  (b) with --ppo: the experiment of DESIGN 4.24 part 3 again. 8 x 8 torus, 128 agents bound anywhere, the goal_mlp head, two
+      DAgger iterations (expert dijkstra, 16 environments, 512 samples, 4 epochs of minibatches of 64, lr 0.01), then
+      --ppo-iterations PPO iterations of 300 frames x --envs environments under policy_hold and route_departures, from the
+      same cloned weights, credit "joint" against "decision", per schedule of --schedules (epochs:minibatch:lr); MODE
+      evaluation under both rules over --envs environments before and after.
+
+    python tools/time_decision_credit.py [--envs 64] [--reps 5] [--ppo] [--ppo-iterations 10] [--schedules 1:32:1e-3,...]"""
+import argparse
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tarl-simulator_amd"), os.path.join(ROOT, "tests")]
+import torch  # noqa: E402
+
+from tarl_hip import ops, synth  # noqa: E402
+from tarl_hip.engine import EPISODE_START, SimEngine  # noqa: E402
+from tarl_hip.evaluator import VecEvaluator  # noqa: E402
+from tarl_hip.trainer import StageTimer, VecPPOTrainer  # noqa: E402
+
+LOG = None
+
+
+def say(text=""):
+    print(text, flush=True)
+    if LOG is not None:
+        LOG.write(text + "\n")
+        LOG.flush()
+
+
+def med(v, unit="us"):
+    return f"{statistics.median(v):10.2f} {unit} ({min(v):.2f} - {max(v):.2f})"
+
+
+def _mean_se(v):
+    v = [float(x) for x in v]
+    n = len(v)
+    m = sum(v) / n
+    return m, (math.sqrt(sum((x - m) ** 2 for x in v) / (n - 1) / n) if n > 1 else float("nan"))
+
+
+def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="trip", rules=True):
+    from src.agents.mpnn_agent import MPNNPolicyNet, MPNNValueNetSimple
+    N, Nmax = net.num_roads, net.Nmax
+    eng = SimEngine(net.x.cuda(), net.edge_index, net.edge_attr, Nmax, pop.cuda(), congestion_constant=net.congestion_constant,
+                    num_envs=B, seed=seed)
+    ff = net.x[:, 3 * Nmax + 2][net.edge_index[1]].cuda().contiguous()
+    torch.manual_seed(1)
+    pol = MPNNPolicyNet(net.edge_index, N, ff, device="cuda")
+    pol.prior_method = "all_pairs"
+    pol.use_goal_mlp(ops.goal_time_scale(net.x[:, 3 * Nmax:]))
+    val = MPNNValueNetSimple(net.edge_index, N, device="cuda")
+    l, gm = val.final_mlp, pol.goal_mlp
+    tr = VecPPOTrainer(eng, pol.nodes_embedding.weight, [l[0].weight, l[0].bias, l[2].weight, l[2].bias, l[4].weight, l[4].bias],
+                       rollout_steps=T, num_epochs=epochs, sub_batch_size=M, lr=lr,
+                       extra_params=[p for n, p in pol.named_parameters() if not n.startswith("nodes_embedding")],
+                       policy="goal_mlp", goal_mlp_params=[gm[0].weight, gm[0].bias, gm[2].weight, gm[2].bias],
+                       prior_table=pol.dist_matrix, policy_hold=rules, route_departures=rules, reward=reward, credit=credit)
+    return tr, pol
+
+
+def cost(label, net, pop, B, T, M, reps):
+    say(f"{label}: N = {net.num_roads}, B = {B}, T = {T} frames, minibatch M = {M}, goal_mlp head")
+    trs = {c: trainer(net, pop, B, T, credit=c, M=M, rules=False, reward="queue")[0] for c in ("joint", "decision")}
+    times = {c: [] for c in trs}
+    stages = {}
+    for rep in range(reps + 1):                 # one warm-up round, variants alternating
+        for c, tr in trs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            tr.collect()
+            b.record()
+            tr.stage = StageTimer()
+            tr.update()
+            ms = tr.stage.ms()
+            if rep:
+                times[c].append(a.elapsed_time(b) / T * 1e3)
+                for k, (v, n) in ms.items():
+                    stages.setdefault((c, k), []).append(v / n * 1e3)
+    for c in trs:
+        say(f"  collect, credit {c:9} {med(times[c])} per frame")
+    say(f"  capture = decision - joint: {statistics.median(times['decision']) - statistics.median(times['joint']):.2f} us per "
+        f"frame ({M} kept pairs over {T} frames: {M / T:.2f} head-row launches per frame)")
+    for k in ("graphdist_bwd", "actor_logits_bwd", "decision_ppo", "ppo_loss"):
+        for c in trs:
+            if (c, k) in stages:
+                say(f"  step stage {k:18} credit {c:9} {med(stages[(c, k)])}")
+    tr = trs["decision"]
+    eng = tr.eng
+    n = max(1, M // T)
+    env = torch.zeros(n, dtype=torch.int32, device="cuda")
+    slot = torch.arange(n, dtype=torch.int32, device="cuda")
+    v = []
+    for rep in range(reps + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(50):
+            ops.fused_head_rows(eng.plan, eng.fs, env, slot, tr.head_keep)
+        b.record()
+        torch.cuda.synchronize()
+        if rep:
+            v.append(a.elapsed_time(b) / 50 * 1e3)
+    say(f"  tarl_fused_head_rows, {n} pair(s): {med(v)} per launch (50 launches per sample)")
+    tr.check_flags()
+
+
+def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules):
+    from tarl_hip.imitation import BCTrainer
+    net = synth.torus_network(8, 8)
+    T = 300
+    pop = synth.population(128, net.num_roads, seed=7, t0=EPISODE_START, t1=EPISODE_START + 40)
+    engine = lambda B, seed: SimEngine(net.x.cuda(), net.edge_index, net.edge_attr, net.Nmax, pop.cuda(),        # noqa: E731
+                                       congestion_constant=net.congestion_constant, num_envs=B, seed=seed)
+    say(f"(b) PPO after cloning, 8 x 8 torus, 128 agents bound anywhere: goal_mlp head, {bc_iterations} DAgger iterations, then "
+        f"{ppo_iterations} PPO iterations of {T} frames x {K} environments under policy_hold and route_departures (reward trip); "
+        f"MODE evaluation under both rules, K = {K}, {T} frames, mean +- se")
+    for epochs, M, lr in schedules:
+        say(f"schedule: {epochs} epoch(s) of one minibatch of {M} frames per iteration, lr {lr:g}")
+        for credit in ("joint", "decision"):
+            tr, pol = trainer(net, pop, K, T, credit=credit, epochs=epochs, M=M, lr=lr)
+            bc = BCTrainer(tr, engine(16, 11), expert="dijkstra", driver="dagger", frames=T, samples=512, epochs=4, batch=64,
+                           lr=1e-2)
+            acc = [bc.iterate()["accuracy_after"] for _ in range(bc_iterations)]
+
+            def evaluate(tag):
+                eng = engine(K, 3)
+                res = VecEvaluator.from_policy_net(eng, pol, policy_hold=True, route_departures=True, trip_reward=True).run(T)
+                if res.domain_exit:
+                    say(f"  credit {credit:9} {tag:8} DOMAIN EXIT in frames {res.domain_exit_frames}")
+                    return
+                lost = (eng.agents[:, :, 7].sum(1) - eng.x[:, :, 3 * eng.Nmax + 1].sum(1)).tolist()
+                (am, ase), (lm, _), (tm, tse) = _mean_se(res.arrived), _mean_se(lost), _mean_se(res.trip_return)
+                say(f"  credit {credit:9} {tag:8} arrivals {am:7.2f} +- {ase:.2f}   agents lost {lm:5.2f}   trip return {tm:10.1f} +- "
+                    f"{tse:.1f}")
+            say(f"  credit {credit:9} cloned: accuracy on the store {' -> '.join(f'{a:.3f}' for a in acc)}")
+            evaluate("cloned")
+            for it in range(ppo_iterations):
+                tr.collect()
+                out = tr.update().tolist()
+                line = f"    [ppo {it}] collected reward per frame {float(tr.reward.mean()):9.3f}  joint kl {out[4]:.5f}"
+                if credit == "decision":
+                    d = {k: float(v) for k, v in tr.last["decision"].items()}
+                    line += (f"  decisions {int(d['decisions'])}  delay {d['delay_frames']:.2f} frames  truncated "
+                             f"{d['truncated']:.3f}  objective {d['objective']:.4f}  clip {d['clip_fraction']:.3f}  kl {d['kl']:.5f}")
+                say(line)
+            tr.check_flags()
+            evaluate("+ ppo")
+            del tr, bc, pol
+            torch.cuda.empty_cache()
+
+
+def main():
+    global LOG
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-cost", action="store_true")
+    ap.add_argument("--ppo", action="store_true")
+    ap.add_argument("--bc-iterations", type=int, default=2)
+    ap.add_argument("--ppo-iterations", type=int, default=10)
+    ap.add_argument("--schedules", default="1:32:1e-3,4:256:1e-3,8:512:3e-3")
+    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "decision_credit_time.log"))
+    a = ap.parse_args()
+    LOG = open(a.log, "a")
+    shown, skip = [], False       # the command line without where the log goes
+    for arg in sys.argv[1:]:
+        if skip or arg == "--log":
+            skip = not skip
+            continue
+        if not arg.startswith("--log="):
+            shown.append(arg)
+    say(f"# tools/time_decision_credit.py {' '.join(shown)}   (MI355X; DESIGN 4.26)")
+    if not a.no_cost:
+        say("(a) cost: HIP events, median (min - max) of the repetitions after one warm-up round")
+        net = synth.torus_network(8, 8)
+        pop = synth.population(128, net.num_roads, seed=7, t0=EPISODE_START, t1=EPISODE_START + 40)
+        cost("8 x 8 torus", net, pop, a.envs, 64, 32, a.reps)
+        cost("8 x 8 torus", net, pop, a.envs, 64, 512, a.reps)
+        net = synth.torus_network(25, 25)
+        pop = synth.population(16384, net.num_roads, seed=0)
+        cost("config-4 geometry (25 x 25 torus, 16 384 agents)", net, pop, a.envs, 32, 32, a.reps)
+    if a.ppo:
+        sched = [(int(e), int(m), float(lr)) for e, m, lr in (s.split(":") for s in a.schedules.split(","))]
+        ppo_after_cloning(a.envs, a.bc_iterations, a.ppo_iterations, sched)
+    LOG.close()
+
+
+if __name__ == "__main__":
+    main()
