@@ -1342,6 +1342,50 @@ int tarl_graphdist_decision_ppo(const tarl_plan* plan, const float* logits, int6
                                 const double* stats3, const int32_t* n_live, float clip_epsilon, float grad_scale,
                                 double* out4, float* grad_logits, void* scratch, tarl_stream stream);
 
+/* ---- the learned per-decision critic (credit_baseline = "learned"; csrc/decision_critic.hip) ---------------------
+ * NOT in the reference, off by default. TARL_ABI_VERSION is unchanged: nothing existing moved and tarl_fused did not grow.
+ * A baseline of the per-decision advantage that reads the state in front of the decision and never the action. The common
+ * inputs: obs16 fp32 [M][N][16] (the kept observations, 16-byte aligned), head int32 [M][N] (> 0: the decision is live, the
+ * mask tarl_decision_advantage leaves), frames_left int32 [M] (t_end - t of the row's segment), dist fp64 [num_dests][N] and
+ * dest_slot int32 [N] (the free-flow table of tarl_decision_advantage), timestep. For a live (m, u), with d = (long)
+ * DESTINATION of obs16[m][u], s = dest_slot[d], n_ff(x) = dist[s][x] / timestep in fp64 (+inf where d lies outside [0, N) or
+ * s outside [0, num_dests)), h = frames_left[m], fill(x) = NUMBER_OF_AGENT(x) / MAXN(x) (0 where MAXN <= 0) and v* the
+ * out-neighbour of u with the smallest finite dist[s][v] (CSR order, the first wins a tie), eight fp32 features:
+ *   f0 = (float)min(n_ff(u), 512) / 64, f1 = (float)min(h, 512) / 64, f2 = fill(u), f3 = fill(v*), f4 = the mean of fill(v)
+ *   over the reachable out-neighbours (the sum in CSR order, one divide), f5 = [v* == d], f6 = [n_ff(u) > h] (fp64),
+ *   f7 = min(FF(u) / timestep, 64) / 8; f3 = f4 = f5 = 0 where no neighbour is reachable.
+ * The network is 8 -> 16 (ReLU) -> 1 in tarl_policy_goal_mlp_fwd's flat layout of 161 floats (W1 at 0, b1 at 128, w2 at
+ * 144, b2 at 160), a multiply then an add, k and j ascending.
+ * tarl_decision_critic_features: feats fp32 [M][N][8] (16-byte aligned), every element written, zeros where not live.
+ * tarl_decision_critic_fwd: value[M][N] = the network's output, 0 where not live; adv_out (optional) = adv_raw +
+ *   delay_scale * value in fp32 (a multiply, then an add), 0 where not live. The M * N elements of value, adv_out and
+ *   adv_raw may not overlap (ranges are compared, not base pointers alone).
+ * tarl_decision_critic_loss: the smooth-L1 loss of the value against y = -adv_raw / delay_scale over the live decisions,
+ *   e = value - y, l = 0.5 e^2 for |e| < 1 and |e| - 0.5 otherwise. out5 fp64 [M][5] = per row {sum of l, live decisions,
+ *   sum of y, sum of y^2, sum of (y - value)^2}, a fixed tree per tile of 256 nodes and the tiles in order. grads
+ *   (optional) fp32 [161]: += the gradient of grad_scale * coef / L * sum of l with L = n_live[0] (int32 on the device;
+ *   zeros are added while L <= 0). No floating-point atomics: the (row, tile) pairs are split into at most 1024 runs by M
+ *   and N alone, the live decisions of a run are added in (row, node) order and the runs through a fixed tree (lane l of a
+ *   wave takes the runs l, l + 64, .. in order, then lanes l and l + 32, 16, .., 1): two runs are bit-identical.
+ *   scratch: tarl_decision_critic_loss_scratch_bytes(plan, M) bytes, 8-byte aligned, every byte written before it is read;
+ *   -1 for a null plan, M < 1 or 2^24 or more (row, tile) pairs.
+ * Refused on the host, before any HIP call (a refused call writes nothing): a null argument (adv_out and grads alone may be
+ *   null), M or num_dests below 1, 2^24 or more (row, tile) pairs, timestep <= 0, delay_scale not finite or <= 0, coef < 0
+ *   or not finite, a misaligned obs16 / feats / scratch, overlapping outputs. */
+int tarl_decision_critic_features(const tarl_plan* plan, const float* obs16, int64_t M, const int32_t* head,
+                                  const int32_t* frames_left, const double* dist, const int32_t* dest_slot,
+                                  int64_t num_dests, float timestep, float* feats, tarl_stream stream);
+int tarl_decision_critic_fwd(const tarl_plan* plan, const float* obs16, int64_t M, const int32_t* head,
+                             const int32_t* frames_left, const double* dist, const int32_t* dest_slot, int64_t num_dests,
+                             float timestep, const float* weights, float delay_scale, const float* adv_raw, float* value,
+                             float* adv_out, tarl_stream stream);
+int64_t tarl_decision_critic_loss_scratch_bytes(const tarl_plan* plan, int64_t M);
+int tarl_decision_critic_loss(const tarl_plan* plan, const float* obs16, int64_t M, const int32_t* head,
+                              const int32_t* frames_left, const double* dist, const int32_t* dest_slot, int64_t num_dests,
+                              float timestep, const float* weights, float delay_scale, const float* adv_raw,
+                              const int32_t* n_live, float coef, float grad_scale, double* out5, float* grads, void* scratch,
+                              tarl_stream stream);
+
 /* ---- the device noise, written out (test hook; nothing on the product path calls it) ---------------------------------------
  * The rollouts draw their own randomness: per frame one Gumbel value per in-edge for DirectionMPNN.aggregate's race (the
  * reference: torch.rand_like + -log(-log(u)), src/direction_mpnn.py:136-139) and one uniform per source node for

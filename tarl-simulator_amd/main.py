@@ -155,6 +155,17 @@ OPTIONS = (
     ("--credit-gamma", dict(type=float, default=None, metavar="G",
                             help="--credit decision: the discount of a traveller's frames to go, in (0, 1] (default 1.0); "
                                  "separate from GAE's gamma")),
+    ("--credit-baseline", dict(choices=("free_flow", "learned"), default=None,
+                               help="--credit decision: the baseline of the per-decision advantage (default free_flow, the "
+                                    "traveller's free-flow frames to go). learned (DESIGN 4.27; not in the reference) adds a "
+                                    "small critic on the state in front of the decision (the road, the destination, the load "
+                                    "around it, the frames left in the segment), trained beside the policy on the delay beyond "
+                                    "free flow; it never reads the action. It is not saved in policy.pt. train_log.jsonl gains "
+                                    "train/credit_baseline, train/decision_critic_loss, train/decision_explained_variance and "
+                                    "train/decision_value_mean")),
+    ("--credit-critic-coef", dict(type=float, default=None, metavar="C",
+                                  help="--credit decision --credit-baseline learned: the coefficient of the per-decision "
+                                       "critic's loss, >= 0 (default 1.0); refused without --credit-baseline learned")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "

@@ -154,7 +154,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
               eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False, reward="queue",
-              credit="joint", decision_gamma=1.0):
+              credit="joint", decision_gamma=1.0, credit_baseline="free_flow", decision_critic_coef=1.0):
     """``pretrain_bc`` (not in the reference; None = off): a dict {iterations, expert, driver, envs, frames,
     samples, epochs, batch, lr} — that many behaviour-cloning iterations (tarl_hip.imitation.BCTrainer) run before the first
     PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``.
@@ -162,11 +162,20 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     ``train/reward_kind`` and the ``eval_vec*`` evaluations run with ``trip_reward=True`` and log ``eval_vec/trip_return*``.
     ``credit``: ``"decision"`` trains with per-decision credit (VecPPOTrainer(credit="decision",
     decision_gamma=...)); the log records gain ``train/credit``, ``train/decisions``, ``train/decision_delay_frames``,
-    ``train/decision_truncated``, ``train/decision_clip_fraction`` and ``train/decision_kl``."""
+    ``train/decision_truncated``, ``train/decision_clip_fraction`` and ``train/decision_kl``.
+    ``credit_baseline``: ``"learned"`` adds the per-decision critic (VecPPOTrainer(credit_baseline="learned",
+    decision_critic_coef=...)); its 161 parameters are created here (ops.decision_critic_init), join the optimiser's buffer
+    and are not saved with the policy, as no critic is. The log records gain ``train/credit_baseline``,
+    ``train/decision_critic_loss``, ``train/decision_explained_variance`` and ``train/decision_value_mean``."""
     if reward not in ("queue", "trip"):
         raise ValueError("reward must be 'queue' or 'trip'")
     if credit not in ("joint", "decision"):
         raise ValueError("credit must be 'joint' or 'decision'")
+    if credit_baseline not in ("free_flow", "learned"):
+        raise ValueError("credit_baseline must be 'free_flow' or 'learned'")
+    if credit_baseline == "learned" and credit != "decision":
+        raise ValueError("credit_baseline learned is the baseline of the per-decision advantage: it needs credit decision")
+    learned = credit_baseline == "learned"
     trip = reward == "trip"
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
@@ -207,10 +216,11 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     if head == "goal_mlp":
         gm = policy_net.goal_mlp
         prior_kw["goal_mlp_params"] = [gm[0].weight, gm[0].bias, gm[2].weight, gm[2].bias]
+    dcritic = ops.decision_critic_init(engine.device, seed) if learned else []
     trainer = VecPPOTrainer(engine, policy_net.nodes_embedding.weight,
                             critic,
                             rollout_steps=frames_per_batch, num_epochs=num_epochs, sub_batch_size=sub_batch_size,
-                            extra_params=dormant, seed=seed,
+                            extra_params=dormant + dcritic, seed=seed,
                             policy=head if head in ("embedding", "embedding_dijkstra", "graph_transformer",
                                                     "goal_mlp") else "edge_mlp",
                             edge_mlp_params=[m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias],
@@ -221,7 +231,9 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             **({"policy_hold": True} if policy_hold else {}),
                             **({"route_departures": True} if route_departures else {}),
                             **({"reward": "trip"} if trip else {}),
-                            **({"credit": "decision", "decision_gamma": decision_gamma} if credit == "decision" else {}))
+                            **({"credit": "decision", "decision_gamma": decision_gamma} if credit == "decision" else {}),
+                            **({"credit_baseline": "learned", "decision_critic_params": dcritic,
+                                "decision_critic_coef": decision_critic_coef} if learned else {}))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)
@@ -280,6 +292,10 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                 rec.update({"train/credit": "decision", "train/decisions": int(dl["decisions"]),
                             "train/decision_delay_frames": dl["delay_frames"], "train/decision_truncated": dl["truncated"],
                             "train/decision_clip_fraction": dl["clip_fraction"], "train/decision_kl": dl["kl"]})
+                if learned:
+                    rec.update({"train/credit_baseline": "learned", "train/decision_critic_loss": dl["critic_loss"],
+                                "train/decision_explained_variance": dl["explained_variance"],
+                                "train/decision_value_mean": dl["value_mean"]})
             if bool(done.any()):
                 rec["transport/avg_travel_time"] = float((ag0[done, 3] - ag0[done, 2]).mean())
         # periodic evaluation (src/rl/ppo_trainer.py:147-151): MODE rollout, optionally a sampled one, on eval_env

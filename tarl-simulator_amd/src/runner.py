@@ -46,6 +46,8 @@ class RunnerArgs:
     #                                eval: computed beside the queue reward with eval_envs, dijkstra_envs or replan_days
     credit: str = "joint"          # train: "decision" = per-decision PPO credit (state-dependent heads, default critic)
     credit_gamma: float = None     # ... the discount of a traveller's frames to go, in (0, 1] (default 1.0)
+    credit_baseline: str = None    # ... "learned" = the per-decision critic of DESIGN 4.27 (default "free_flow")
+    credit_critic_coef: float = None   # ... the coefficient of that critic's loss (default 1.0)
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
@@ -146,7 +148,18 @@ class RunnerArgs:
             raise ValueError(f"credit must be 'joint' or 'decision', got {self.credit!r}")
         if self.credit_gamma is not None and self.credit != "decision":
             raise ValueError("credit_gamma discounts the per-decision return: it needs credit decision")
+        if self.credit_baseline not in (None, "free_flow", "learned"):
+            raise ValueError(f"credit_baseline must be 'free_flow' or 'learned', got {self.credit_baseline!r}")
+        if self.credit_baseline is not None and self.credit != "decision":
+            raise ValueError("credit_baseline names the baseline of the per-decision advantage: it needs credit decision")
+        if self.credit_critic_coef is not None and self.credit != "decision":
+            raise ValueError("credit_critic_coef weighs the per-decision critic's loss: it needs credit decision")
+        if self.credit_critic_coef is not None and self.credit_baseline != "learned":
+            raise ValueError("credit_critic_coef weighs the learned per-decision critic's loss: it needs credit_baseline "
+                             "learned (the free-flow baseline has nothing to train)")
         if self.credit == "decision":
+            if self.credit_critic_coef is not None and not 0.0 <= float(self.credit_critic_coef) < float("inf"):
+                raise ValueError(f"credit_critic_coef must be finite and >= 0, got {self.credit_critic_coef!r}")
             if self.mode != "train":
                 raise ValueError("credit decision changes the PPO update: it needs mode 'train' (an evaluation has no update)")
             if self.algo not in ("mpnn", "mpnn+ppo"):
@@ -451,7 +464,10 @@ class Runner:
                   **({"route_departures": True} if a.route_departures else {}),
                   **({"reward": "trip"} if a.reward == "trip" else {}),
                   **({"credit": "decision", "decision_gamma": 1.0 if a.credit_gamma is None else float(a.credit_gamma)}
-                     if a.credit == "decision" else {}), **bc_kw)
+                     if a.credit == "decision" else {}),
+                  **({"credit_baseline": "learned",
+                      "decision_critic_coef": 1.0 if a.credit_critic_coef is None else float(a.credit_critic_coef)}
+                     if a.credit_baseline == "learned" else {}), **bc_kw)
 
     def eval(self):
         a = self.args

@@ -180,6 +180,12 @@ SIGNATURES = {
     "tarl_graphdist_node_logprob": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p]),
     "tarl_graphdist_decision_ppo_scratch_bytes": (_i64, [_p, _i64]),
     "tarl_graphdist_decision_ppo": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p, _p, _p, _p, _f32, _f32, _p, _p, _p, _p]),
+    # the learned per-decision critic (csrc/decision_critic.hip)
+    "tarl_decision_critic_features": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _f32, _p, _p]),
+    "tarl_decision_critic_fwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _f32, _p, _f32, _p, _p, _p, _p]),
+    "tarl_decision_critic_loss_scratch_bytes": (_i64, [_p, _i64]),
+    "tarl_decision_critic_loss": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _f32, _p, _f32, _p, _p, _f32, _f32, _p, _p,
+                                            _p, _p]),
     "tarl_noise_export": (C.c_int, [_p, C.c_int, _u64, _u64, _p, _i64, _p, _p]),
     "tarl_prof_enable": (C.c_int, [_i64]),
     "tarl_prof_collect": (C.c_int, [_i64, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64)]),

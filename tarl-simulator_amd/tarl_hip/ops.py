@@ -2604,6 +2604,135 @@ class GoalMlpWeights:
         return self.flat[160:161]
 
 
+# ---- the learned per-decision critic (csrc/decision_critic.hip; NOT reference semantics) --------------------------
+DECISION_CRITIC_FEATURES, DECISION_CRITIC_PARAMS = 8, 161
+
+
+class DecisionCriticWeights(GoalMlpWeights):
+    """The 161 parameters of the per-decision critic (8 -> 16 -> 1) as ONE flat fp32 device tensor, the layout of
+    :class:`GoalMlpWeights`: built from the four tensors w1 (16, 8), b1 (16,), w2 (1, 16), b2 (1,), or with ``flat=``
+    around a (161,) view of a flat parameter buffer."""
+
+
+def decision_critic_init(device="cpu", seed=0):
+    """-> [w1 (16, 8), b1 (16,), w2 (1, 16), b2 (1,)] fp32: W1 uniform in (-0.1, 0.1), everything else 0. With the last
+    layer at zero the critic's value is 0, so the first update's advantages are those of the free-flow baseline."""
+    g = torch.Generator().manual_seed(int(seed))
+    w1 = (torch.rand((16, 8), generator=g, dtype=torch.float64) * 0.2 - 0.1).to(torch.float32)
+    return [t.to(device) for t in (w1, torch.zeros(16), torch.zeros(1, 16), torch.zeros(1))]
+
+
+def _critic_inputs(plan, obs16, head, frames_left, dist, dest_slot, timestep):
+    N = plan.num_nodes
+    _contig(obs16, torch.float32, "obs16")
+    if obs16.dim() != 3 or obs16.size(1) != N or obs16.size(2) != 16 or obs16.size(0) < 1:
+        raise ValueError(f"obs16 must be (M, {N}, 16) with M >= 1, got {tuple(obs16.shape)}")
+    M = obs16.size(0)
+    _rows_n(head, torch.int32, N, "head", M)
+    _row_list(frames_left, M, "frames_left")
+    _contig(dist, torch.float64, "dist")
+    _contig(dest_slot, torch.int32, "dest_slot")
+    if dist.dim() != 2 or dist.size(1) != N or dist.size(0) < 1 or tuple(dest_slot.shape) != (N,):
+        raise ValueError(f"dist must be (D, {N}) with D >= 1 and dest_slot ({N},), got {tuple(dist.shape)} and "
+                         f"{tuple(dest_slot.shape)}")
+    if not float(timestep) > 0.0:
+        raise ValueError("timestep must be positive")
+    return M, (plan.handle, obs16.data_ptr(), M, head.data_ptr(), frames_left.data_ptr(), dist.data_ptr(),
+               dest_slot.data_ptr(), dist.size(0), float(timestep))
+
+
+def _critic_net(weights, delay_scale, adv_raw, N, M):
+    if not isinstance(weights, GoalMlpWeights):
+        raise ValueError("weights must be ops.DecisionCriticWeights")
+    if not (math.isfinite(float(delay_scale)) and float(delay_scale) > 0.0):
+        raise ValueError("delay_scale must be positive and finite")
+    _rows_n(adv_raw, torch.float32, N, "adv_raw", M)
+
+
+def decision_critic_features(plan: Plan, obs16, head, frames_left, dist, dest_slot, *, timestep, out=None):
+    """-> fp32 (M, N, 8): the critic's features of every (kept row, road), zeros where ``head <= 0``
+    (tarl_decision_critic_features; the test hook the restatement is anchored to). ``obs16`` fp32 (M, N, 16), ``head`` int32
+    (M, N), ``frames_left`` int32 (M,), ``dist`` float64 (D, N) and ``dest_slot`` int32 (N,) of :func:`decision_advantage`."""
+    M, args = _critic_inputs(plan, obs16, head, frames_left, dist, dest_slot, timestep)
+    if out is None:
+        out = torch.empty((M, plan.num_nodes, DECISION_CRITIC_FEATURES), dtype=torch.float32, device=obs16.device)
+    _contig(out, torch.float32, "out")
+    if tuple(out.shape) != (M, plan.num_nodes, DECISION_CRITIC_FEATURES):
+        raise ValueError(f"out must be ({M}, {plan.num_nodes}, 8), got {tuple(out.shape)}")
+    _lib.check(_lib.load().tarl_decision_critic_features(*args, out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def decision_critic_forward(plan: Plan, obs16, head, frames_left, dist, dest_slot, weights, adv_raw, *, timestep,
+                            delay_scale=16.0, value=None, adv_out=None, want_adv=True):
+    """-> (value, adv_dec), fp32 (M, N) each (tarl_decision_critic_fwd): ``value`` the critic's estimate of the delay beyond
+    free flow in units of ``delay_scale`` frames, ``adv_dec = adv_raw + delay_scale * value``; zeros where ``head <= 0``.
+    ``want_adv=False`` -> (value, None)."""
+    M, args = _critic_inputs(plan, obs16, head, frames_left, dist, dest_slot, timestep)
+    N = plan.num_nodes
+    _critic_net(weights, delay_scale, adv_raw, N, M)
+    if value is None:
+        value = torch.empty((M, N), dtype=torch.float32, device=obs16.device)
+    _rows_n(value, torch.float32, N, "value", M)
+    if want_adv and adv_out is None:
+        adv_out = torch.empty((M, N), dtype=torch.float32, device=obs16.device)
+    if adv_out is not None:
+        _rows_n(adv_out, torch.float32, N, "adv_out", M)
+    ptrs = {adv_raw.data_ptr(), value.data_ptr()} | ({adv_out.data_ptr()} if adv_out is not None else set())
+    if len(ptrs) != (3 if adv_out is not None else 2):
+        raise ValueError("value and adv_out may alias neither adv_raw nor each other")
+    _lib.check(_lib.load().tarl_decision_critic_fwd(*args, weights.flat.data_ptr(), float(delay_scale), adv_raw.data_ptr(),
+                                                    value.data_ptr(), _lib.ptr(adv_out), _lib.current_stream()))
+    return value, adv_out
+
+
+def decision_critic_scratch_bytes(plan: Plan, M) -> int:
+    """Bytes of scratch of :func:`decision_critic_loss` for M rows: 40 per (row, tile of 256 roads) pair and 161 floats per
+    run of ceil(pairs / 1024) pairs — the rule of the library, which is asked and must agree."""
+    pairs = int(M) * max(1, -(-plan.num_nodes // 256))
+    per = -(-pairs // 1024)
+    want = pairs * 40 + (-(-pairs // per)) * DECISION_CRITIC_PARAMS * 4
+    need = int(_lib.load().tarl_decision_critic_loss_scratch_bytes(plan.handle, int(M)))
+    if need < 0:
+        raise _lib.TarlError("tarl_decision_critic_loss_scratch_bytes refused the sizes")
+    if need != want:
+        raise _lib.TarlError(f"the scratch of tarl_decision_critic_loss is {need} bytes, the shapes say {want}")
+    return need
+
+
+def decision_critic_loss(plan: Plan, obs16, head, frames_left, dist, dest_slot, weights, adv_raw, n_live, *, timestep,
+                         delay_scale=16.0, coef=1.0, grad_scale=1.0, grads=None, scratch=None):
+    """The critic's smooth-L1 loss over the live decisions of a minibatch, forward and backward (tarl_decision_critic_loss).
+    -> float64 (M, 5) = per row {sum of the losses, live decisions, sum of y, sum of y^2, sum of (y - value)^2} with the
+    target y = -adv_raw / delay_scale. ``grads`` fp32 (161,) (optional): the gradient of ``grad_scale * coef / L`` times the
+    summed loss is ADDED, L = ``n_live`` (int32 (1,) on the device). ``scratch``: at least
+    :func:`decision_critic_scratch_bytes` bytes; a shorter one is refused."""
+    M, args = _critic_inputs(plan, obs16, head, frames_left, dist, dest_slot, timestep)
+    _critic_net(weights, delay_scale, adv_raw, plan.num_nodes, M)
+    need = decision_critic_scratch_bytes(plan, M)
+    if scratch is not None and scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch holds {scratch.numel() * scratch.element_size()} bytes, tarl_decision_critic_loss needs "
+                         f"{need}")
+    _contig(n_live, torch.int32, "n_live")
+    if n_live.numel() != 1:
+        raise ValueError("n_live must hold one int32")
+    if not (math.isfinite(float(coef)) and float(coef) >= 0.0):
+        raise ValueError("coef must be finite and >= 0")
+    if grads is not None:
+        _contig(grads, torch.float32, "grads")
+        if tuple(grads.shape) != (DECISION_CRITIC_PARAMS,):
+            raise ValueError(f"grads must be ({DECISION_CRITIC_PARAMS},), got {tuple(grads.shape)}")
+    if scratch is None:
+        scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=obs16.device)
+    elif not scratch.is_cuda or not scratch.is_contiguous():
+        raise _lib.TarlError("scratch must be a contiguous tensor on the GPU")
+    out5 = torch.empty((M, 5), dtype=torch.float64, device=obs16.device)
+    _lib.check(_lib.load().tarl_decision_critic_loss(*args, weights.flat.data_ptr(), float(delay_scale), adv_raw.data_ptr(),
+                                                     n_live.data_ptr(), float(coef), float(grad_scale), out5.data_ptr(),
+                                                     _lib.ptr(grads), scratch.data_ptr(), _lib.current_stream()))
+    return out5
+
+
 def goal_time_scale(x_static) -> float:
     """``time_scale`` of the goal-conditioned head: the mean FREE_FLOW over the roads of ``x_static`` (the (N, 7) static
     columns, or any (..., N, >= 3) tensor whose column 2 is FREE_FLOW: the first environment speaks for all), computed in

@@ -13,6 +13,7 @@ Multi-GPU: one process per GPU, each with its own environments and minibatch; gr
 """
 from __future__ import annotations
 
+import math
 import os
 from bisect import bisect_left
 
@@ -71,7 +72,8 @@ class VecPPOTrainer:
                  policy="embedding", edge_mlp_params=None, policy_bf16=False, policy_precision=None, prior_table=None,
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
                  prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None,
-                 route_departures=False, reward="queue", credit="joint", decision_gamma=1.0):
+                 route_departures=False, reward="queue", credit="joint", decision_gamma=1.0, credit_baseline="free_flow",
+                 decision_critic_params=None, decision_critic_coef=1.0, decision_delay_scale=16.0):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -104,7 +106,15 @@ class VecPPOTrainer:
         by ops.graphdist_decision_ppo; critic and entropy terms are unchanged. ``decision_gamma``: the discount of a
         traveller's frames to go, separate from GAE's ``gamma``. State-dependent heads on the fused path with the default
         critic only. ``self.last["decision"]`` then carries the live decisions, their mean delay in frames, the truncated
-        share, the objective, the clip fraction and the approximate KL of the last minibatch (0-d device tensors)."""
+        share, the objective, the clip fraction and the approximate KL of the last minibatch (0-d device tensors).
+        ``credit_baseline`` (DESIGN 4.27; ``credit="decision"`` only): ``"free_flow"`` (the default) is the baseline above;
+        ``"learned"`` (not in the reference) adds a per-decision critic (csrc/decision_critic.hip) on the state in front of
+        the decision: ``decision_critic_params`` = [w1 (16, 8), b1 (16,), w2 (1, 16), b2 (1,)], consecutive in
+        ``extra_params`` like ``goal_mlp_params`` (ops.decision_critic_init makes them). Once per update it is evaluated on
+        all kept rows with the rollout's parameters and the policy term reads ``adv_raw + decision_delay_scale * value``;
+        every minibatch step adds the gradient of ``decision_critic_coef`` times its smooth-L1 loss against
+        ``-adv_raw / decision_delay_scale`` (stage ``decision_critic``). ``self.last["decision"]`` gains ``critic_loss``,
+        ``explained_variance`` and ``value_mean`` of the last epoch."""
         self.eng = engine
         # policy: "embedding" = the reference's live head (logit = embedding of the target road: state-independent, its
         # distribution is tabulated once per update); "edge_mlp" = the per-edge MLP head it carries as parameters
@@ -228,6 +238,14 @@ class VecPPOTrainer:
         self.decision_gamma = float(decision_gamma)
         if credit == "decision":
             self._check_decision_credit(engine, value)
+        if credit_baseline not in ("free_flow", "learned"):
+            raise ValueError("credit_baseline must be 'free_flow' or 'learned'")
+        self.credit_baseline = credit_baseline
+        self.decision_critic_coef = float(decision_critic_coef)
+        self.decision_delay_scale = float(decision_delay_scale)
+        self.decision_critic_params = None
+        if credit_baseline == "learned":
+            self.decision_critic_params = self._check_decision_critic(credit, decision_critic_params, extra_params)
         # lazy_log_prob: do not produce sample_log_prob for every collected frame (as the reference's collector does)
         # but only, exactly, for the frames a minibatch actually reads. Same training result; off by default so that a
         # frame does everything the reference's frame does.
@@ -250,6 +268,11 @@ class VecPPOTrainer:
             self._goal_off = self.flat.offsets[id(self.goal_mlp_params[0])][0]
             assert self.flat.offsets[id(self.goal_mlp_params[3])][0] == self._goal_off + ops.GOAL_MLP_PARAMS - 1
             self.goal_scale = ops.goal_time_scale(engine._x[0, :, 3 * engine.Nmax:])
+        if self.decision_critic_params is not None:      # one run of the flat buffer, as the goal head's
+            self._dcritic_off = self.flat.offsets[id(self.decision_critic_params[0])][0]
+            assert (self.flat.offsets[id(self.decision_critic_params[3])][0]
+                    == self._dcritic_off + ops.DECISION_CRITIC_PARAMS - 1)
+            self.frames_left = self.adv_dec = None
         B, N, dev = engine.B, engine.N, engine.device
         # which rollout kernel family: "env" = one workgroup per environment, records in LDS, one launch for all frames
         # (tarl_rollout_env; env-major buffers), "frames" = four env-minor launches per frame (tarl_fused_rollout).
@@ -335,6 +358,30 @@ class VecPPOTrainer:
         self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._decision_dist = None          # (dist float64 (D, N), dest_slot int32 (N,)): built once, after the first reset
         self.head_keep = self.adv_raw = self.lp_old_node = None
+
+    def _check_decision_critic(self, credit, params, extra_params):
+        """Refusals of credit_baseline="learned" -> the four parameter tensors."""
+        if credit != "decision":
+            raise ValueError("credit_baseline='learned' is the baseline of the per-decision advantage: it needs "
+                             "credit='decision'")
+        cp = list(params) if params is not None else []
+        if [tuple(p.shape) for p in cp] != [(16, 8), (16,), (1, 16), (1,)]:
+            raise ValueError("credit_baseline='learned' needs decision_critic_params = the four tensors w1 (16, 8), b1 (16,), "
+                             "w2 (1, 16), b2 (1,) (8 -> 16 -> 1)")
+        pos = {id(p): i for i, p in enumerate(extra_params)}
+        at = [pos.get(id(p), -9) for p in cp]
+        if at[0] < 0 or at != list(range(at[0], at[0] + 4)):
+            raise ValueError("decision_critic_params must be part of extra_params (the optimiser's flat buffer), in order and "
+                             "next to each other")
+        if not self.decision_critic_coef >= 0.0 or not math.isfinite(self.decision_critic_coef):
+            raise ValueError("decision_critic_coef must be finite and >= 0")
+        if not (math.isfinite(self.decision_delay_scale) and self.decision_delay_scale > 0.0):
+            raise ValueError("decision_delay_scale must be positive and finite")
+        return cp
+
+    def _dcritic(self):
+        return ops.DecisionCriticWeights(
+            flat=self.flat.flat[self._dcritic_off:self._dcritic_off + ops.DECISION_CRITIC_PARAMS])
 
     def _build_decision_dist(self):
         """Free-flow shortest-path distances to every distinct destination (ops.destination_trees on the travel times of the
@@ -543,6 +590,8 @@ class VecPPOTrainer:
         lo, hi = bisect_left(t_sorted, sl.start), bisect_left(t_sorted, sl.stop)
         if hi == lo:
             return
+        if self.decision_critic_params is not None:      # t_end - t of every kept row of this segment
+            self.frames_left.index_copy_(0, keep_slot[lo:hi].to(torch.int64), sl.stop - self._keep_frames[lo:hi])
         self.times[sl.start:sl.stop].copy_(torch.tensor(host_times[sl.start:sl.stop], dtype=torch.float32))
         dist, slot = self._decision_dist
         ops.decision_advantage(eng.plan, self.head_keep, self._keep_frames[lo:hi], keep_env[lo:hi], keep_slot[lo:hi],
@@ -582,6 +631,10 @@ class VecPPOTrainer:
                 self.head_keep = torch.empty((flat.numel(), N), dtype=torch.int32, device=eng.device)
                 self.adv_raw = torch.empty((flat.numel(), N), dtype=torch.float32, device=eng.device)
                 self.lp_old_node = torch.empty((flat.numel(), N), dtype=torch.float32, device=eng.device)
+            if self.decision_critic_params is not None and (self.adv_dec is None or self.adv_dec.size(0) != flat.numel()):
+                self.frames_left = torch.zeros(flat.numel(), dtype=torch.int32, device=eng.device)
+                self.adv_dec = torch.empty((flat.numel(), N), dtype=torch.float32, device=eng.device)
+                self.value_old = torch.empty((flat.numel(), N), dtype=torch.float32, device=eng.device)
 
     def _queue(self, sl):
         """Frames ``sl`` (one episode segment) in one foreign call; returns the clock values. The embedding head draws from
@@ -791,6 +844,9 @@ class VecPPOTrainer:
         if self.credit == "decision":
             with st("decision_ppo"):
                 self._decision_step(logits, choice_mb, off, M, scale, g_logits)
+            if self.decision_critic_params is not None:
+                with st("decision_critic"):
+                    self._decision_critic_step(obs, off, M, scale)
         with st("actor_logits_bwd"):
             self._actor_logits_bwd(obs, g_logits)
         with st("critic_bwd"):
@@ -825,7 +881,17 @@ class VecPPOTrainer:
                                        out=self.lp_old_node[off:off + M])
             off += M
         self._decision_local = ops.decision_stats(self.adv_raw, self.head_keep)      # this rank's {sum, sum of squares, count}
-        self._decision_stats = self._decision_local.clone()
+        self._decision_adv = self.adv_raw
+        if self.decision_critic_params is not None:      # the learned baseline, once, with the parameters the rollout had
+            dist, slot = self._decision_dist
+            ops.decision_critic_forward(eng.plan, self.obs_mb, self.head_keep, self.frames_left, dist, slot, self._dcritic(),
+                                        self.adv_raw, timestep=eng.timestep, delay_scale=self.decision_delay_scale,
+                                        value=self.value_old, adv_out=self.adv_dec)
+            self._decision_adv = self.adv_dec
+            self._decision_stats = ops.decision_stats(self.adv_dec, self.head_keep)
+            self._dcritic_last = None
+        else:
+            self._decision_stats = self._decision_local.clone()
         dist_utils.allreduce_sum_(self._decision_stats)
         self._decision_last = None
 
@@ -838,10 +904,25 @@ class VecPPOTrainer:
         if getattr(self, "_decision_scratch", None) is None or self._decision_scratch.numel() < need:
             self._decision_scratch = torch.empty(need, dtype=torch.float64, device=self.eng.device)      # once per trainer
         out4 = ops.graphdist_decision_ppo(self.eng.plan, logits, choice_mb, head, self.lp_old_node[off:off + M],
-                                          self.adv_raw[off:off + M], self._decision_stats, n_live,
+                                          self._decision_adv[off:off + M], self._decision_stats, n_live,
                                           clip_epsilon=self.clip_epsilon, temperature=self.temperature, grad_scale=scale,
                                           grad_logits=g_logits, scratch=self._decision_scratch)
         self._decision_last = (out4.sum(0), n_live)
+
+    def _decision_critic_step(self, obs, off, M, scale):
+        """The critic's loss on the live decisions of one minibatch, current parameters: its gradient is added into the
+        critic's run of the flat gradient buffer."""
+        need = (ops.decision_critic_scratch_bytes(self.eng.plan, M) + 7) // 8
+        if getattr(self, "_dcritic_scratch", None) is None or self._dcritic_scratch.numel() < need:
+            self._dcritic_scratch = torch.empty(need, dtype=torch.float64, device=self.eng.device)      # once per trainer
+        dist, slot = self._decision_dist
+        out5 = ops.decision_critic_loss(
+            self.eng.plan, obs, self.head_keep[off:off + M], self.frames_left[off:off + M], dist, slot, self._dcritic(),
+            self.adv_raw[off:off + M], self._decision_last[1], timestep=self.eng.timestep,
+            delay_scale=self.decision_delay_scale, coef=self.decision_critic_coef, grad_scale=scale,
+            grads=self.flat.grad[self._dcritic_off:self._dcritic_off + ops.DECISION_CRITIC_PARAMS],
+            scratch=self._dcritic_scratch)
+        self._dcritic_last = (out5, off, M)      # summed where the report is built: no further launch per step
 
     def _decision_report(self):
         """``self.last["decision"]``: 0-d device tensors (no synchronisation here)."""
@@ -849,9 +930,22 @@ class VecPPOTrainer:
         live = tot[1].clamp(min=1.0)
         st = self._decision_local
         cnt = st[2].clamp(min=1.0)
-        return {"decisions": st[2], "delay_frames": -st[0] / cnt,
-                "truncated": self.decision_truncated[0].to(torch.float64) / cnt, "objective": -tot[0] / live,
-                "clip_fraction": tot[2] / live, "kl": tot[3] / live}
+        rep = {"decisions": st[2], "delay_frames": -st[0] / cnt,
+               "truncated": self.decision_truncated[0].to(torch.float64) / cnt, "objective": -tot[0] / live,
+               "clip_fraction": tot[2] / live, "kl": tot[3] / live}
+        if self.decision_critic_params is not None:      # the last epoch's five sums, over all ranks
+            out5, off, M = self._dcritic_last
+            # ... and the sum of the values the advantages were formed with (0 where not live)
+            s5 = torch.cat([out5.sum(0), self.value_old[off:off + M].sum(dtype=torch.float64).reshape(1)])
+            if self.world > 1:
+                s5 = s5.clone()
+                dist_utils.allreduce_sum_(s5)
+            n = s5[1].clamp(min=1.0)
+            den = s5[3] - s5[2] * s5[2] / n
+            rep["critic_loss"] = self.decision_critic_coef * s5[0] / n
+            rep["explained_variance"] = torch.where(den > 0, 1.0 - s5[4] / den.clamp(min=1e-300), torch.zeros_like(den))
+            rep["value_mean"] = s5[5] / n
+        return rep
 
     def update(self):
         out = None

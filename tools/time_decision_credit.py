@@ -11,8 +11,13 @@
       --ppo-iterations PPO iterations of 300 frames x --envs environments under policy_hold and route_departures, from the
       same cloned weights, credit "joint" against "decision", per schedule of --schedules (epochs:minibatch:lr); MODE
       evaluation under both rules over --envs environments before and after.
+  --credit-baseline learned: the rows of the learned per-decision critic instead. (a) then times the stages of
+      a step of VecPPOTrainer(credit_baseline="learned") — ``decision_critic`` beside ``decision_ppo`` and
+      ``actor_logits_bwd`` — and the critic's forward over all kept rows, once per update; (b) runs the same experiment with
+      credit "decision" and the learned baseline (rows "learned", with the critic's explained variance per iteration).
 
-    python tools/time_decision_credit.py [--envs 64] [--reps 5] [--ppo] [--ppo-iterations 10] [--schedules 1:32:1e-3,...]"""
+    python tools/time_decision_credit.py [--envs 64] [--reps 5] [--ppo] [--ppo-iterations 10] [--schedules 1:32:1e-3,...]
+                                         [--credit-baseline {free_flow,learned}]"""
 import argparse
 import math
 import os
@@ -49,7 +54,8 @@ def _mean_se(v):
     return m, (math.sqrt(sum((x - m) ** 2 for x in v) / (n - 1) / n) if n > 1 else float("nan"))
 
 
-def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="trip", rules=True):
+def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="trip", rules=True, baseline="free_flow"):
+    """``baseline`` "learned" (with ``credit`` "decision"): the learned per-decision critic of DESIGN 4.27."""
     from src.agents.mpnn_agent import MPNNPolicyNet, MPNNValueNetSimple
     N, Nmax = net.num_roads, net.Nmax
     eng = SimEngine(net.x.cuda(), net.edge_index, net.edge_attr, Nmax, pop.cuda(), congestion_constant=net.congestion_constant,
@@ -61,12 +67,64 @@ def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="
     pol.use_goal_mlp(ops.goal_time_scale(net.x[:, 3 * Nmax:]))
     val = MPNNValueNetSimple(net.edge_index, N, device="cuda")
     l, gm = val.final_mlp, pol.goal_mlp
+    critic = ops.decision_critic_init("cuda", seed) if baseline == "learned" else []
+    kw = dict(credit_baseline="learned", decision_critic_params=critic) if critic else {}
     tr = VecPPOTrainer(eng, pol.nodes_embedding.weight, [l[0].weight, l[0].bias, l[2].weight, l[2].bias, l[4].weight, l[4].bias],
                        rollout_steps=T, num_epochs=epochs, sub_batch_size=M, lr=lr,
-                       extra_params=[p for n, p in pol.named_parameters() if not n.startswith("nodes_embedding")],
+                       extra_params=[p for n, p in pol.named_parameters() if not n.startswith("nodes_embedding")] + critic,
                        policy="goal_mlp", goal_mlp_params=[gm[0].weight, gm[0].bias, gm[2].weight, gm[2].bias],
-                       prior_table=pol.dist_matrix, policy_hold=rules, route_departures=rules, reward=reward, credit=credit)
+                       prior_table=pol.dist_matrix, policy_hold=rules, route_departures=rules, reward=reward,
+                       credit=credit, **kw)
     return tr, pol
+
+
+def critic_cost(label, net, pop, B, T, M, reps):
+    """The stages of a step under the learned baseline, and the critic's forward over all kept rows."""
+    say(f"{label}: N = {net.num_roads}, B = {B}, T = {T} frames, minibatch M = {M}, goal_mlp head, credit_baseline learned")
+    tr = trainer(net, pop, B, T, credit="decision", baseline="learned", M=M, rules=False, reward="queue")[0]
+    stages, fwd, live = {}, [], []
+    value = adv_dec = None
+    for rep in range(reps + 1):                 # one warm-up round
+        tr.collect()
+        tr.stage = StageTimer()
+        tr.update()
+        dist, slot = tr._decision_dist
+        if value is None:
+            value, adv_dec = torch.empty_like(tr.adv_raw), torch.empty_like(tr.adv_raw)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        ops.decision_critic_forward(tr.eng.plan, tr.obs_mb, tr.head_keep, tr.frames_left, dist, slot, tr._dcritic(),
+                                    tr.adv_raw, timestep=tr.eng.timestep, delay_scale=tr.decision_delay_scale,
+                                    value=value, adv_out=adv_dec)          # buffers of its own: the trainer's stay as they are
+        b.record()
+        torch.cuda.synchronize()
+        if rep:
+            fwd.append(a.elapsed_time(b) * 1e3)
+            live.append(int((tr.head_keep > 0).sum()))
+            for k, (v, n) in tr.stage.ms().items():
+                stages.setdefault(k, []).append(v / n * 1e3)
+    for k in ("actor_logits_bwd", "decision_ppo", "decision_critic"):
+        say(f"  step stage {k:18} {med(stages[k])}")
+    say(f"  critic forward over all {tr.head_keep.size(0)} kept rows (once per update) {med(fwd)}; live decisions "
+        f"{min(live)} - {max(live)} of {tr.head_keep.numel()}")
+    rows = min(M, tr.head_keep.size(0))         # the loss launch of one minibatch on its own, 50 launches per sample
+    head = tr.head_keep[:rows]
+    n_live = (head > 0).sum(dtype=torch.int32).reshape(1)
+    grads = torch.zeros(ops.DECISION_CRITIC_PARAMS, device="cuda")
+    scratch = torch.empty((ops.decision_critic_scratch_bytes(tr.eng.plan, rows) + 7) // 8, dtype=torch.float64, device="cuda")
+    v = []
+    for rep in range(reps + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(50):
+            ops.decision_critic_loss(tr.eng.plan, tr.obs_mb[:rows], head, tr.frames_left[:rows], dist, slot, tr._dcritic(),
+                                     tr.adv_raw[:rows], n_live, timestep=tr.eng.timestep, grads=grads, scratch=scratch)
+        b.record()
+        torch.cuda.synchronize()
+        if rep:
+            v.append(a.elapsed_time(b) / 50 * 1e3)
+    say(f"  tarl_decision_critic_loss, {rows} rows, {int(n_live)} live decisions: {med(v)} per call (50 calls per sample)")
+    tr.check_flags()
 
 
 def cost(label, net, pop, B, T, M, reps):
@@ -114,7 +172,7 @@ def cost(label, net, pop, B, T, M, reps):
     tr.check_flags()
 
 
-def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules):
+def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules, credits=("joint", "decision")):
     from tarl_hip.imitation import BCTrainer
     net = synth.torus_network(8, 8)
     T = 300
@@ -126,8 +184,9 @@ def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules):
         f"MODE evaluation under both rules, K = {K}, {T} frames, mean +- se")
     for epochs, M, lr in schedules:
         say(f"schedule: {epochs} epoch(s) of one minibatch of {M} frames per iteration, lr {lr:g}")
-        for credit in ("joint", "decision"):
-            tr, pol = trainer(net, pop, K, T, credit=credit, epochs=epochs, M=M, lr=lr)
+        for credit in credits:
+            tr, pol = trainer(net, pop, K, T, credit="decision" if credit == "learned" else credit, epochs=epochs, M=M, lr=lr,
+                              baseline="learned" if credit == "learned" else "free_flow")
             bc = BCTrainer(tr, engine(16, 11), expert="dijkstra", driver="dagger", frames=T, samples=512, epochs=4, batch=64,
                            lr=1e-2)
             acc = [bc.iterate()["accuracy_after"] for _ in range(bc_iterations)]
@@ -148,10 +207,13 @@ def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules):
                 tr.collect()
                 out = tr.update().tolist()
                 line = f"    [ppo {it}] collected reward per frame {float(tr.reward.mean()):9.3f}  joint kl {out[4]:.5f}"
-                if credit == "decision":
+                if credit != "joint":
                     d = {k: float(v) for k, v in tr.last["decision"].items()}
                     line += (f"  decisions {int(d['decisions'])}  delay {d['delay_frames']:.2f} frames  truncated "
                              f"{d['truncated']:.3f}  objective {d['objective']:.4f}  clip {d['clip_fraction']:.3f}  kl {d['kl']:.5f}")
+                if credit == "learned":
+                    line += (f"  critic loss {d['critic_loss']:.4f}  explained variance {d['explained_variance']:.3f}  value mean "
+                             f"{d['value_mean']:.3f}")
                 say(line)
             tr.check_flags()
             evaluate("+ ppo")
@@ -169,6 +231,7 @@ def main():
     ap.add_argument("--bc-iterations", type=int, default=2)
     ap.add_argument("--ppo-iterations", type=int, default=10)
     ap.add_argument("--schedules", default="1:32:1e-3,4:256:1e-3,8:512:3e-3")
+    ap.add_argument("--credit-baseline", choices=("free_flow", "learned"), default="free_flow")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "decision_credit_time.log"))
     a = ap.parse_args()
     LOG = open(a.log, "a")
@@ -179,19 +242,21 @@ def main():
             continue
         if not arg.startswith("--log="):
             shown.append(arg)
-    say(f"# tools/time_decision_credit.py {' '.join(shown)}   (MI355X; DESIGN 4.26)")
+    learned = a.credit_baseline == "learned"
+    say(f"# tools/time_decision_credit.py {' '.join(shown)}   (MI355X; DESIGN {'4.27' if learned else '4.26'})")
+    cost_fn = critic_cost if learned else cost
     if not a.no_cost:
         say("(a) cost: HIP events, median (min - max) of the repetitions after one warm-up round")
         net = synth.torus_network(8, 8)
         pop = synth.population(128, net.num_roads, seed=7, t0=EPISODE_START, t1=EPISODE_START + 40)
-        cost("8 x 8 torus", net, pop, a.envs, 64, 32, a.reps)
-        cost("8 x 8 torus", net, pop, a.envs, 64, 512, a.reps)
+        cost_fn("8 x 8 torus", net, pop, a.envs, 64, 32, a.reps)
+        cost_fn("8 x 8 torus", net, pop, a.envs, 64, 512, a.reps)
         net = synth.torus_network(25, 25)
         pop = synth.population(16384, net.num_roads, seed=0)
-        cost("config-4 geometry (25 x 25 torus, 16 384 agents)", net, pop, a.envs, 32, 32, a.reps)
+        cost_fn("config-4 geometry (25 x 25 torus, 16 384 agents)", net, pop, a.envs, 32, 32, a.reps)
     if a.ppo:
         sched = [(int(e), int(m), float(lr)) for e, m, lr in (s.split(":") for s in a.schedules.split(","))]
-        ppo_after_cloning(a.envs, a.bc_iterations, a.ppo_iterations, sched)
+        ppo_after_cloning(a.envs, a.bc_iterations, a.ppo_iterations, sched, ("learned",) if learned else ("joint", "decision"))
     LOG.close()
 
 
