@@ -1342,6 +1342,41 @@ int tarl_graphdist_decision_ppo(const tarl_plan* plan, const float* logits, int6
                                 const double* stats3, const int32_t* n_live, float clip_epsilon, float grad_scale,
                                 double* out4, float* grad_logits, void* scratch, tarl_stream stream);
 
+/* ---- credit scope "due" and the horizon bootstrap (csrc/decision_credit.hip) -------------------------------------
+ * NOT in the reference, off by default. TARL_ABI_VERSION is unchanged: nothing existing moved and tarl_fused did not grow.
+ * tarl_fused_head_rows_due: tarl_fused_head_rows on the whole 8-byte hdp word: head_keep[slot[j]][u] = the head id where the
+ *   count bits of hdp.x are not 0 AND the fp32 value of hdp.y (the head's departure) is <= t_clock, the clock the frame is
+ *   stepped with (Direction's own test); 0 elsewhere. The count is tested first: an empty road's hdp.y may be stale. A head
+ *   that is due but blocked by a full target is in scope. counts2 (int32 [2] on the device, or NULL) += {roads with a head,
+ *   roads with a due head} over the listed pairs, integer atomics. tarl_fused_head_rows' host checks, plus a finite t_clock.
+ * tarl_fused_set_head_capture_scope: scope 0 = headed (tarl_fused_head_rows, what the loop queued before), 1 = due: the
+ *   shared loop queues tarl_fused_head_rows_due with times_host[t] (all of them finite) and counts2 in its place. Refused
+ *   unless the capture is on for the handle; tarl_fused_set_head_capture(f, 1, ..) starts from scope 0 and (f, 0, NULL) clears
+ *   the scope. counts2 (nullable, scope 1 only) must outlive the switch.
+ * tarl_fused_agent_roads: agent_road (int32 [B][A]) = -1 everywhere (an asynchronous fill on the stream), then u for every id
+ *   in logical slots 0 .. count - 1 of road u's FIFO in environment b: count from hdp.x, the ring offset from tl, slot k at
+ *   its physical place in slots. The slot at the count (the pending garbage triple) is never read. Written by an integer
+ *   atomicMax: the result does not depend on scheduling. Ids outside [1, A), a ring offset >= Nmax and the part of a count
+ *   above Nmax add to bad[0] (int32 on the device) and are not followed. Writes nothing of the packed state. The host checks
+ *   of the frame entry points on (plan, f, B, Nmax), A in [1, 2^24], B * A < 2^31.
+ * tarl_decision_advantage_boot: tarl_decision_advantage plus the horizon rule. bootstrap == 0: the same kernel, the same
+ *   output bit for bit (agent_road / bootstrapped may be NULL). bootstrap == 1: a live decision whose traveller has DONE != 1
+ *   when the segment ends, with r = agent_road[b][a] in [0, N) and dist[s][r] finite, gets n = (t_end - t) + dist[s][r] /
+ *   timestep in fp64 (the free-flow time from the road it is queued on: an optimistic continuation) and adds to
+ *   bootstrapped[0], not to truncated[0]; every other such decision (queued nowhere: lost; unreachable) is charged t_end - t
+ *   and adds to truncated[0] as before. */
+int tarl_fused_head_rows_due(const tarl_plan* plan, const tarl_fused* f, int64_t B, float t_clock, const int32_t* env,
+                             const int32_t* slot, int64_t n, int32_t* head_keep, int32_t* counts2, tarl_stream stream);
+int tarl_fused_set_head_capture_scope(tarl_fused* f, int scope, int32_t* counts2);
+int tarl_fused_agent_roads(const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t A, int32_t Nmax,
+                           int32_t* agent_road, int32_t* bad, tarl_stream stream);
+int tarl_decision_advantage_boot(const tarl_plan* plan, int32_t* head_keep, const int32_t* frame, const int32_t* env,
+                                 const int32_t* slot, int64_t rows, int64_t B, const float* agent_features,
+                                 int64_t num_agents, int64_t a_bstride, const float* times, int64_t num_times, int64_t t_end,
+                                 const double* dist, const int32_t* dest_slot, int64_t num_dests, float timestep,
+                                 double decision_gamma, float* adv_raw, int32_t* truncated, int32_t* bad,
+                                 const int32_t* agent_road, int bootstrap, int32_t* bootstrapped, tarl_stream stream);
+
 /* ---- the learned per-decision critic (credit_baseline = "learned"; csrc/decision_critic.hip) ---------------------
  * NOT in the reference, off by default. TARL_ABI_VERSION is unchanged: nothing existing moved and tarl_fused did not grow.
  * A baseline of the per-decision advantage that reads the state in front of the decision and never the action. The common

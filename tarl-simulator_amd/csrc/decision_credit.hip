@@ -7,6 +7,10 @@
 //                            (or until the segment ends) against its free-flow frames to go, both through S(n) in fp64.
 //   k_decision_stats_*       {sum, sum of squares, count} of the raw advantage over the live decisions, tarl_advantage_stats'
 //                            two-stage fp64 scheme with a mask.
+//   k_fused_head_rows_due    the same word where the head is also DUE at the frame's clock (credit scope "due"):
+//                            the draw of a road whose head is still travelling reaches nobody.
+//   k_fused_agent_roads      the road every agent is queued on (-1: nowhere), from the packed FIFOs alone: where the horizon
+//                            bootstrap of k_decision_advantage continues from.
 //   k_graphdist_node_logprob log(p_choice + 1e-8) per node, k_softmax's expressions.
 //   k_graphdist_decision_ppo the clipped objective per live node, forward and backward, plus k_decision_ppo_reduce per sample.
 //
@@ -69,16 +73,82 @@ extern "C" int tarl_fused_head_rows(const tarl_plan* plan, const tarl_fused* f, 
   return tarl_launch_head_rows((hipStream_t)stream, plan, f, B, env, slot, n, head_keep);
 }
 
+// ---- (1b) credit scope "due"  ------------------------------------------------------------------------------------
+// k_fused_head_rows reading the whole 8-byte hdp word (the same lines: hd and dep are adjacent): the head id where the road
+// holds somebody AND its head's departure has come at the clock the frame is stepped with (Direction's fp32 test,
+// fused_direction.hip), 0 elsewhere. The count test comes first: an empty road's dep word may be stale (lazy rows,
+// fused_common.h). counts2 (optional) += {headed, due}, one integer atomic each per wave.
+__global__ __launch_bounds__(DC_TILE) void k_fused_head_rows_due(const uint2* __restrict__ hdp, int64_t N, uint32_t B,
+                                                                 uint32_t tiles, float t_clock,
+                                                                 const int32_t* __restrict__ env,
+                                                                 const int32_t* __restrict__ slot,
+                                                                 int32_t* __restrict__ head_keep,
+                                                                 int32_t* __restrict__ counts2) {
+  const uint32_t j = blockIdx.x / tiles, tile = blockIdx.x - j * tiles;
+  const int64_t u = (int64_t)tile * DC_TILE + threadIdx.x;
+  bool headed = false, due = false;
+  if (u < N) {
+    const int32_t b = env[j];
+    int32_t v = 0;
+    if (b >= 0 && (uint32_t)b < B) {
+      const uint2 w = hdp[u * B + b];                                 // N * B < 2^31 (checked by the caller)
+      headed = (w.x & HD_CNT) != 0u;
+      due = headed && __uint_as_float(w.y) <= t_clock;
+      if (due) v = (int32_t)(w.x >> 8);
+    }
+    head_keep[(int64_t)slot[j] * N + u] = v;
+  }
+  if (counts2) {
+    const int32_t c_headed = (int32_t)__popcll(__ballot(headed)), c_due = (int32_t)__popcll(__ballot(due));
+    if ((threadIdx.x & 63) == 0) {              // integer atomics: the result does not depend on scheduling
+      if (c_headed) atomicAdd(counts2, c_headed);
+      if (c_due) atomicAdd(counts2 + 1, c_due);
+    }
+  }
+}
+
+int tarl_launch_head_rows_due(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, float t_clock,
+                              const int32_t* env, const int32_t* slot, int64_t n, int32_t* head_keep, int32_t* counts2) {
+  const int64_t tiles = dc_tiles(plan);
+  hipLaunchKernelGGL(k_fused_head_rows_due, dim3((unsigned)(n * tiles)), dim3(DC_TILE), 0, s, (const uint2*)f->hdp, plan->N,
+                     (uint32_t)B, (uint32_t)tiles, t_clock, env, slot, head_keep, counts2);
+  TARL_LAUNCH_CHECK();
+  return TARL_OK;
+}
+
+extern "C" int tarl_fused_head_rows_due(const tarl_plan* plan, const tarl_fused* f, int64_t B, float t_clock,
+                                        const int32_t* env, const int32_t* slot, int64_t n, int32_t* head_keep,
+                                        int32_t* counts2, tarl_stream stream) {
+  const int rc = tarl_check_head_rows(plan, f, B, n);
+  if (rc != TARL_OK) return rc;
+  TARL_REQUIRE(std::isfinite(t_clock), "t_clock must be finite");
+  if (n == 0 || plan->N == 0) return TARL_OK;
+  TARL_REQUIRE(env && slot && head_keep, "null argument");
+  return tarl_launch_head_rows_due((hipStream_t)stream, plan, f, B, t_clock, env, slot, n, head_keep, counts2);
+}
+
 // ---- the switch of the one-call rollouts -------------------------------------------------------------------------------------
 // tarl_fused does not grow: the capture buffer lives beside the handle, keyed by its address, and bit TARL_HEAD_CAPTURE of
 // tarl_fused.policy_hold says that the loop queues the launch above (departures.hip has the scheme).
+struct HeadCapture {
+  int32_t* head_keep;
+  int scope;            // 0 = headed (k_fused_head_rows), 1 = due (k_fused_head_rows_due): tarl_fused_set_head_capture_scope
+  int32_t* counts2;     // scope 1: {headed, due} of the captured rows, or NULL
+};
 static std::mutex g_capture_mutex;
-static std::unordered_map<const tarl_fused*, int32_t*> g_capture;
+static std::unordered_map<const tarl_fused*, HeadCapture> g_capture;
 
 int32_t* tarl_head_capture_of(const tarl_fused* f) {
   std::lock_guard<std::mutex> lock(g_capture_mutex);
   const auto it = g_capture.find(f);
-  return it == g_capture.end() ? nullptr : it->second;
+  return it == g_capture.end() ? nullptr : it->second.head_keep;
+}
+
+int tarl_head_capture_scope_of(const tarl_fused* f, int32_t** counts2) {
+  std::lock_guard<std::mutex> lock(g_capture_mutex);
+  const auto it = g_capture.find(f);
+  *counts2 = it == g_capture.end() ? nullptr : it->second.counts2;
+  return it == g_capture.end() ? 0 : it->second.scope;
 }
 
 extern "C" int tarl_fused_set_head_capture(tarl_fused* f, int on, int32_t* head_keep) {
@@ -86,9 +156,73 @@ extern "C" int tarl_fused_set_head_capture(tarl_fused* f, int on, int32_t* head_
   TARL_REQUIRE(on == 0 || on == 1, "on must be 0 or 1");
   TARL_REQUIRE(on ? head_keep != nullptr : head_keep == nullptr, "the switch and its buffer go together");
   std::lock_guard<std::mutex> lock(g_capture_mutex);
-  if (on) g_capture[f] = head_keep;
+  if (on) g_capture[f] = HeadCapture{head_keep, 0, nullptr};      // (switching on starts from scope "headed")
   else g_capture.erase(f);
   f->policy_hold = on ? (f->policy_hold | TARL_HEAD_CAPTURE) : (f->policy_hold & ~TARL_HEAD_CAPTURE);
+  return TARL_OK;
+}
+
+extern "C" int tarl_fused_set_head_capture_scope(tarl_fused* f, int scope, int32_t* counts2) {
+  TARL_REQUIRE(f, "null argument");
+  TARL_REQUIRE(scope == 0 || scope == 1, "scope must be 0 (headed) or 1 (due)");
+  TARL_REQUIRE(scope == 1 || counts2 == nullptr, "counts2 belongs to scope 1 (due)");
+  std::lock_guard<std::mutex> lock(g_capture_mutex);
+  const auto it = g_capture.find(f);
+  TARL_REQUIRE(it != g_capture.end() && (f->policy_hold & TARL_HEAD_CAPTURE) != 0,
+               "the head capture is off for this handle (tarl_fused_set_head_capture)");
+  it->second.scope = scope;
+  it->second.counts2 = counts2;
+  return TARL_OK;
+}
+
+// ---- where every agent stands ----------------------------------------------------------------------------------
+// Lanes over (u, b) with b minor: the dense words hdp / tl coalesce; each lane walks logical slots 0 .. count - 1 of its own
+// FIFO (the slot AT the count holds the pending garbage triple and is never read). Must move per (road, environment): 8 + 4
+// bytes of dense words, and per queued agent one 4-byte id read and one 4-byte integer atomicMax (an agent is queued on one
+// road, so the max has one candidate and the result does not depend on scheduling). Writes nothing of the packed state.
+__global__ __launch_bounds__(DC_TILE) void k_fused_agent_roads(const uint2* __restrict__ hdp, const uint32_t* __restrict__ tl,
+                                                               const float* __restrict__ slots, int64_t lds, int64_t NB,
+                                                               uint32_t B, int32_t Nmax, int64_t A,
+                                                               int32_t* __restrict__ agent_road, int32_t* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * DC_TILE + threadIdx.x;      // = u * B + b
+  if (i >= NB) return;
+  int32_t cnt = (int32_t)(hdp[i].x & HD_CNT);
+  if (cnt == 0) return;
+  const int hoff = tl_hoff(tl[i]);
+  int32_t n_bad = 0;
+  if (hoff >= Nmax) {                           // no ring of this store starts there: nothing is read
+    n_bad = cnt;
+    cnt = 0;
+  } else if (cnt > Nmax) {
+    n_bad = cnt - Nmax;
+    cnt = Nmax;
+  }
+  const int32_t u = (int32_t)(i / B);
+  const int64_t b = i - (int64_t)u * B;
+  const float* row = slots + i * lds;
+  for (int32_t k = 0; k < cnt; ++k) {
+    const float idf = row[SLW * phys(hoff, k, Nmax)];
+    if (idf >= 1.0f && idf < (float)A) atomicMax(agent_road + b * A + (int64_t)idf, u);
+    else ++n_bad;
+  }
+  if (n_bad) atomicAdd(bad, n_bad);             // (off the defined domain only)
+}
+
+extern "C" int tarl_fused_agent_roads(const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t A, int32_t Nmax,
+                                      int32_t* agent_road, int32_t* bad, tarl_stream stream) {
+  TARL_REQUIRE(plan && f && agent_road && bad, "null argument");
+  const int rc = tarl_check_fused_core(plan, f, B, Nmax);
+  if (rc) return rc;
+  TARL_REQUIRE(A >= 1 && A <= ((int64_t)1 << 24) && B * A < ((int64_t)1 << 31), "bad agent table size");
+  TARL_REQUIRE(plan->N * B < ((int64_t)1 << 31), "bad sizes (N * B must stay below 2^31)");
+  hipStream_t s = (hipStream_t)stream;
+  TARL_CHECK_HIP(hipMemsetAsync(agent_road, 0xFF, (size_t)(B * A) * sizeof(int32_t), s));      // -1: queued nowhere
+  if (plan->N == 0) return TARL_OK;
+  const FusedBufs fb = tarl_to_bufs(f);
+  const int64_t NB = plan->N * B;
+  hipLaunchKernelGGL(k_fused_agent_roads, dim3((unsigned)ceil_div(NB, DC_TILE)), dim3(DC_TILE), 0, s, (const uint2*)fb.hdp,
+                     (const uint32_t*)fb.tl, (const float*)fb.slots, fb.lds, NB, (uint32_t)B, Nmax, A, agent_road, bad);
+  TARL_LAUNCH_CHECK();
   return TARL_OK;
 }
 
@@ -101,15 +235,20 @@ __device__ __forceinline__ double dc_owed(double n, double gamma) {
 // Must move per (row, road): 4 B of head_keep read (and 4 B written back where the decision is not live), 4 B of adv_raw
 // written; on a headed road four scattered gathers (destination, DONE, ARRIVAL_TIME, dist) and a binary search of the
 // segment's clocks (at most log2 T 4-byte loads of one short array every lane shares).
+// BOOT (horizon "bootstrap"): a traveller still under way when the segment ends continues, in free flow, from the
+// road r it is queued on (agent_road): n = (t_end - t) + dist[s][r] / timestep, counted in `bootstrapped`; one queued nowhere
+// (lost) or with no finite dist[s][r] keeps the charge and counts in `truncated`. Two more scattered gathers on such a lane.
+template <bool BOOT>
 __global__ __launch_bounds__(DC_TILE) void k_decision_advantage(
     const int32_t* __restrict__ out_ptr, int64_t N, uint32_t tiles, int32_t* __restrict__ head_keep,
     const int32_t* __restrict__ frame, const int32_t* __restrict__ env, const int32_t* __restrict__ slot, int64_t B,
     const float* __restrict__ ag, int64_t A, int64_t a_bstride, const float* __restrict__ times, int32_t t_end,
     const double* __restrict__ dist, const int32_t* __restrict__ dest_slot, int64_t D, double timestep, double gamma,
-    float* __restrict__ adv_raw, int32_t* __restrict__ truncated, int32_t* __restrict__ bad) {
+    float* __restrict__ adv_raw, int32_t* __restrict__ truncated, int32_t* __restrict__ bad,
+    const int32_t* __restrict__ agent_road, int32_t* __restrict__ bootstrapped) {
   const uint32_t j = blockIdx.x / tiles, tile = blockIdx.x - j * tiles;
   const int64_t u = (int64_t)tile * DC_TILE + threadIdx.x;
-  bool is_bad = false, is_trunc = false;
+  bool is_bad = false, is_trunc = false, is_boot = false;
   if (u < N) {
     const int64_t at = (int64_t)slot[j] * N + u;
     const int32_t a = head_keep[at], t = frame[j], b = env[j];
@@ -127,6 +266,7 @@ __global__ __launch_bounds__(DC_TILE) void k_decision_advantage(
             const double du = dist[(int64_t)s * N + u];
             if (isfinite(du)) {
               int32_t n = t_end - t;
+              double n_go = 0.0;                // BOOT: the free-flow frames still to go beyond the horizon
               if (row[AG_DONE] == 1.0f) {       // frames k in [t, t_end) with times[k] < ARRIVAL_TIME: a lower bound search
                 const float arr = row[AG_ARR];
                 int32_t lo = t, hi = t_end;
@@ -137,9 +277,20 @@ __global__ __launch_bounds__(DC_TILE) void k_decision_advantage(
                 }
                 n = lo - t;
               } else {
-                is_trunc = true;
+                if (BOOT) {
+                  const int32_t r = agent_road[(int64_t)b * A + a];
+                  if (r >= 0 && r < N) {
+                    const double dr = dist[(int64_t)s * N + r];
+                    if (isfinite(dr)) {
+                      n_go = dr / timestep;
+                      is_boot = true;
+                    }
+                  }
+                }
+                is_trunc = !is_boot;
               }
-              adv = dc_owed(du / timestep, gamma) - dc_owed((double)n, gamma);     // G - G_ff = -S(n) + S(n_ff)
+              adv = dc_owed(du / timestep, gamma) -                                // G - G_ff = -S(n) + S(n_ff)
+                    dc_owed(BOOT && is_boot ? (double)n + n_go : (double)n, gamma);
               live = true;
             }
           }
@@ -154,14 +305,20 @@ __global__ __launch_bounds__(DC_TILE) void k_decision_advantage(
     if (c_bad) atomicAdd(bad, c_bad);
     if (c_trunc) atomicAdd(truncated, c_trunc);
   }
+  if (BOOT) {
+    const int32_t c_boot = (int32_t)__popcll(__ballot(is_boot));
+    if ((threadIdx.x & 63) == 0 && c_boot) atomicAdd(bootstrapped, c_boot);
+  }
 }
 
-extern "C" int tarl_decision_advantage(const tarl_plan* plan, int32_t* head_keep, const int32_t* frame, const int32_t* env,
-                                       const int32_t* slot, int64_t rows, int64_t B, const float* agent_features,
-                                       int64_t num_agents, int64_t a_bstride, const float* times, int64_t num_times,
-                                       int64_t t_end, const double* dist, const int32_t* dest_slot, int64_t num_dests,
-                                       float timestep, double decision_gamma, float* adv_raw, int32_t* truncated,
-                                       int32_t* bad, tarl_stream stream) {
+static int decision_advantage_impl(const tarl_plan* plan, int32_t* head_keep, const int32_t* frame, const int32_t* env,
+                                   const int32_t* slot, int64_t rows, int64_t B, const float* agent_features,
+                                   int64_t num_agents, int64_t a_bstride, const float* times, int64_t num_times,
+                                   int64_t t_end, const double* dist, const int32_t* dest_slot, int64_t num_dests,
+                                   float timestep, double decision_gamma, float* adv_raw, int32_t* truncated, int32_t* bad,
+                                   const int32_t* agent_road, int bootstrap, int32_t* bootstrapped, tarl_stream stream) {
+  TARL_REQUIRE(bootstrap == 0 || bootstrap == 1, "bootstrap must be 0 or 1");
+  TARL_REQUIRE(!bootstrap || (agent_road && bootstrapped), "bootstrap needs agent_road and bootstrapped");
   TARL_REQUIRE(plan && head_keep && frame && env && slot && agent_features && times && dist && dest_slot && adv_raw &&
                    truncated && bad, "null argument");
   TARL_REQUIRE(rows >= 0 && B >= 1 && num_agents >= 1 && num_agents <= ((int64_t)1 << 24) && num_dests >= 1, "bad sizes");
@@ -172,12 +329,42 @@ extern "C" int tarl_decision_advantage(const tarl_plan* plan, int32_t* head_keep
   const int64_t tiles = dc_tiles(plan);
   TARL_REQUIRE(rows * tiles < DC_MAX_BLOCKS, "too many (row, tile) pairs for one launch");
   if (rows == 0 || plan->N == 0) return TARL_OK;
-  hipLaunchKernelGGL(k_decision_advantage, dim3((unsigned)(rows * tiles)), dim3(DC_TILE), 0, (hipStream_t)stream,
-                     plan->out_ptr, plan->N, (uint32_t)tiles, head_keep, frame, env, slot, B, agent_features, num_agents,
-                     a_bstride, times, (int32_t)t_end, dist, dest_slot, num_dests, (double)timestep, decision_gamma, adv_raw,
-                     truncated, bad);
+#define DC_LAUNCH(BOOT_)                                                                                                   \
+  hipLaunchKernelGGL(k_decision_advantage<BOOT_>, dim3((unsigned)(rows * tiles)), dim3(DC_TILE), 0, (hipStream_t)stream,   \
+                     plan->out_ptr, plan->N, (uint32_t)tiles, head_keep, frame, env, slot, B, agent_features, num_agents,  \
+                     a_bstride, times, (int32_t)t_end, dist, dest_slot, num_dests, (double)timestep, decision_gamma,       \
+                     adv_raw, truncated, bad, agent_road, bootstrapped)
+  if (bootstrap)
+    DC_LAUNCH(true);
+  else
+    DC_LAUNCH(false);
+#undef DC_LAUNCH
   TARL_LAUNCH_CHECK();
   return TARL_OK;
+}
+
+extern "C" int tarl_decision_advantage(const tarl_plan* plan, int32_t* head_keep, const int32_t* frame, const int32_t* env,
+                                       const int32_t* slot, int64_t rows, int64_t B, const float* agent_features,
+                                       int64_t num_agents, int64_t a_bstride, const float* times, int64_t num_times,
+                                       int64_t t_end, const double* dist, const int32_t* dest_slot, int64_t num_dests,
+                                       float timestep, double decision_gamma, float* adv_raw, int32_t* truncated,
+                                       int32_t* bad, tarl_stream stream) {
+  return decision_advantage_impl(plan, head_keep, frame, env, slot, rows, B, agent_features, num_agents, a_bstride, times,
+                                 num_times, t_end, dist, dest_slot, num_dests, timestep, decision_gamma, adv_raw, truncated,
+                                 bad, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int tarl_decision_advantage_boot(const tarl_plan* plan, int32_t* head_keep, const int32_t* frame,
+                                            const int32_t* env, const int32_t* slot, int64_t rows, int64_t B,
+                                            const float* agent_features, int64_t num_agents, int64_t a_bstride,
+                                            const float* times, int64_t num_times, int64_t t_end, const double* dist,
+                                            const int32_t* dest_slot, int64_t num_dests, float timestep,
+                                            double decision_gamma, float* adv_raw, int32_t* truncated, int32_t* bad,
+                                            const int32_t* agent_road, int bootstrap, int32_t* bootstrapped,
+                                            tarl_stream stream) {
+  return decision_advantage_impl(plan, head_keep, frame, env, slot, rows, B, agent_features, num_agents, a_bstride, times,
+                                 num_times, t_end, dist, dest_slot, num_dests, timestep, decision_gamma, adv_raw, truncated,
+                                 bad, agent_road, bootstrap, bootstrapped, stream);
 }
 
 // ---- (3) statistics over the live decisions ----------------------------------------------------------------------------------

@@ -171,7 +171,8 @@ extern "C" int tarl_fused_rollout(const tarl_plan* plan, const tarl_fused* f, in
 
 // ---- T frames with a STATE-DEPENDENT policy head in one foreign call (rollout_heads.h) ----------------------------------------
 // Nothing of GraphDistribution can be hoisted: per frame [with tarl_fused_set_head_capture: the head ids of the frame's kept
-// pairs, decision_credit.hip] -> the head's logits from the packed state (`frame`) -> action +
+// pairs, decision_credit.hip; the due heads alone under tarl_fused_set_head_capture_scope] -> the head's logits from the
+// packed state (`frame`) -> action +
 // log-prob + SELECTED_ROAD (tarl_graphdist_rollout) -> [with tarl_fused_set_policy_hold: the hold rule on SELECTED_ROAD,
 // policy_hold.hip; the action buffer keeps the draw] -> [with tarl_fused_set_departure_router: the first hop of the agents
 // about to depart from an empty road, departures.hip] -> Direction -> rows -> insert -> [with tarl_fused_set_trip_reward: the
@@ -221,6 +222,8 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
     trip_parts = tarl_trip_reward_parts_of(f);
   }
   int32_t* head_keep = nullptr;     // tarl_fused_set_head_capture: whom the kept pairs' roads decide for (decision_credit.hip)
+  int head_scope = 0;
+  int32_t* head_counts2 = nullptr;
   if ((f->policy_hold & TARL_HEAD_CAPTURE) != 0 && a.keep_ptr_host) {
     head_keep = tarl_head_capture_of(f);
     TARL_REQUIRE(head_keep, "head capture switched on without its buffer");
@@ -228,12 +231,17 @@ int tarl_rollout_head(const HeadRollout& a, head_frame_fn frame, void* ctx) {
       rc = tarl_check_head_rows(plan, f, B, a.keep_ptr_host[t + 1] - a.keep_ptr_host[t]);
       if (rc) return rc;
     }
+    head_scope = tarl_head_capture_scope_of(f, &head_counts2);      // tarl_fused_set_head_capture_scope: 1 = due heads only
+    if (head_scope == 1)
+      for (int64_t t = 0; t < T; ++t) TARL_REQUIRE(std::isfinite(a.times_host[t]), "non-finite time");
   }
   for (int64_t t = 0; t < T; ++t) {
     const bool keep_t = a.keep_ptr_host && a.keep_ptr_host[t + 1] > a.keep_ptr_host[t];
     const int64_t lo = keep_t ? a.keep_ptr_host[t] : 0, n = keep_t ? a.keep_ptr_host[t + 1] - lo : 0;
     if (head_keep && n) {
-      rc = tarl_launch_head_rows(s, plan, f, B, a.keep_env + lo, a.keep_slot + lo, n, head_keep);
+      rc = head_scope == 1 ? tarl_launch_head_rows_due(s, plan, f, B, a.times_host[t], a.keep_env + lo, a.keep_slot + lo, n,
+                                                       head_keep, head_counts2)
+                           : tarl_launch_head_rows(s, plan, f, B, a.keep_env + lo, a.keep_slot + lo, n, head_keep);
       if (rc) return rc;
     }
     rc = frame(a, ctx, t, a.keep_env + lo, a.keep_slot + lo, n);

@@ -79,6 +79,12 @@ int32_t* tarl_head_capture_of(const tarl_fused* f);
 int tarl_check_head_rows(const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t n);
 int tarl_launch_head_rows(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, const int32_t* env,
                           const int32_t* slot, int64_t n, int32_t* head_keep);
+// credit scope "due" (tarl_fused_set_head_capture_scope): tarl_head_capture_scope_of: 0 = headed (also when the setter was
+// never called), 1 = due, and the {headed, due} counters it registered, or NULL; tarl_launch_head_rows_due: the launch that
+// takes tarl_launch_head_rows' place under scope 1, with the clock the frame is stepped with.
+int tarl_head_capture_scope_of(const tarl_fused* f, int32_t** counts2);
+int tarl_launch_head_rows_due(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, float t_clock,
+                              const int32_t* env, const int32_t* slot, int64_t n, int32_t* head_keep, int32_t* counts2);
 
 // the kept rows straight from the packed state (a head whose logits do not leave fp32 observations behind)
 static inline int tarl_head_keep_rows(const HeadRollout& a, const int32_t* env, const int32_t* slot, int64_t n) {

@@ -166,6 +166,17 @@ OPTIONS = (
     ("--credit-critic-coef", dict(type=float, default=None, metavar="C",
                                   help="--credit decision --credit-baseline learned: the coefficient of the per-decision "
                                        "critic's loss, >= 0 (default 1.0); refused without --credit-baseline learned")),
+    ("--credit-scope", dict(choices=("headed", "due"), default=None,
+                            help="--credit decision: which roads are credited (default headed: every road with a traveller "
+                                 "at the head of its queue). due (DESIGN 4.28; not in the reference) credits only the roads "
+                                 "whose head is due at the frame's clock: the draw of a road whose head is still travelling "
+                                 "reaches nobody. train_log.jsonl gains train/credit_scope and train/decisions_headed")),
+    ("--credit-horizon", dict(choices=("charge", "bootstrap"), default=None,
+                              help="--credit decision: what a traveller still under way owes when a segment ends (default "
+                                   "charge: the frames to the horizon). bootstrap (DESIGN 4.28; not in the reference) adds "
+                                   "the free-flow time from the road it is queued on where the batch cut the segment (an "
+                                   "optimistic estimate); an episode that ended keeps the charge. train_log.jsonl gains "
+                                   "train/credit_horizon and train/decision_bootstrapped")),
     ("--dijkstra-envs", dict(type=int, default=0,
                              help="--algo dijkstra --mode eval: after the single-environment report, evaluate the router on K "
                                   "vectorised environments (each routing on its own congested travel times, in the "

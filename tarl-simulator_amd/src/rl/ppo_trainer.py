@@ -154,7 +154,8 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
               sub_batch_size=32, device=torch.device("cpu"), checkpoint_path=None, log_dir=None, eval_env=None,
               eval_interval=0, log_interval=1, stochastic_eval=False, num_envs=1, seed=0, eval_envs=0,
               eval_baseline="none", policy_hold=False, pretrain_bc=None, route_departures=False, reward="queue",
-              credit="joint", decision_gamma=1.0, credit_baseline="free_flow", decision_critic_coef=1.0):
+              credit="joint", decision_gamma=1.0, credit_baseline="free_flow", decision_critic_coef=1.0,
+              credit_scope="headed", credit_horizon="charge"):
     """``pretrain_bc`` (not in the reference; None = off): a dict {iterations, expert, driver, envs, frames,
     samples, epochs, batch, lr} — that many behaviour-cloning iterations (tarl_hip.imitation.BCTrainer) run before the first
     PPO iteration, on an engine of their own; one line each is printed and appended to ``bc_log.jsonl``.
@@ -166,7 +167,11 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     ``credit_baseline``: ``"learned"`` adds the per-decision critic (VecPPOTrainer(credit_baseline="learned",
     decision_critic_coef=...)); its 161 parameters are created here (ops.decision_critic_init), join the optimiser's buffer
     and are not saved with the policy, as no critic is. The log records gain ``train/credit_baseline``,
-    ``train/decision_critic_loss``, ``train/decision_explained_variance`` and ``train/decision_value_mean``."""
+    ``train/decision_critic_loss``, ``train/decision_explained_variance`` and ``train/decision_value_mean``.
+    ``credit_scope`` / ``credit_horizon``: ``"due"`` credits only the roads whose head is due, ``"bootstrap"``
+    continues a traveller cut off by the batch in free flow (VecPPOTrainer(credit_scope=..., credit_horizon=...)). The log
+    records gain ``train/credit_scope`` and ``train/decisions_headed``, ``train/credit_horizon`` and
+    ``train/decision_bootstrapped``, each pair only with its non-default value."""
     if reward not in ("queue", "trip"):
         raise ValueError("reward must be 'queue' or 'trip'")
     if credit not in ("joint", "decision"):
@@ -176,6 +181,14 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
     if credit_baseline == "learned" and credit != "decision":
         raise ValueError("credit_baseline learned is the baseline of the per-decision advantage: it needs credit decision")
     learned = credit_baseline == "learned"
+    if credit_scope not in ("headed", "due"):
+        raise ValueError("credit_scope must be 'headed' or 'due'")
+    if credit_horizon not in ("charge", "bootstrap"):
+        raise ValueError("credit_horizon must be 'charge' or 'bootstrap'")
+    if credit_scope != "headed" and credit != "decision":
+        raise ValueError("credit_scope narrows the per-decision credit: it needs credit decision")
+    if credit_horizon != "charge" and credit != "decision":
+        raise ValueError("credit_horizon closes the per-decision return: it needs credit decision")
     trip = reward == "trip"
     from tarl_hip import dist_utils, ops
     from tarl_hip.engine import SimEngine
@@ -233,7 +246,9 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                             **({"reward": "trip"} if trip else {}),
                             **({"credit": "decision", "decision_gamma": decision_gamma} if credit == "decision" else {}),
                             **({"credit_baseline": "learned", "decision_critic_params": dcritic,
-                                "decision_critic_coef": decision_critic_coef} if learned else {}))
+                                "decision_critic_coef": decision_critic_coef} if learned else {}),
+                            **({"credit_scope": "due"} if credit_scope == "due" else {}),
+                            **({"credit_horizon": "bootstrap"} if credit_horizon == "bootstrap" else {}))
     log = writer = None
     if log_dir is not None and rank == 0:      # rank 0 alone writes
         os.makedirs(log_dir, exist_ok=True)
@@ -288,7 +303,7 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
             if trip:                      # PPO/avg_episode_return above is the return of the trip reward
                 rec["train/reward_kind"] = "trip"
             if credit == "decision":      # the per-decision term of the last minibatch; loss/objective above is the joint one's 0
-                dl = {k: float(v) for k, v in trainer.last["decision"].items()}
+                dl = {k: float(v) for k, v in trainer.last["decision"].items() if not isinstance(v, str)}
                 rec.update({"train/credit": "decision", "train/decisions": int(dl["decisions"]),
                             "train/decision_delay_frames": dl["delay_frames"], "train/decision_truncated": dl["truncated"],
                             "train/decision_clip_fraction": dl["clip_fraction"], "train/decision_kl": dl["kl"]})
@@ -296,6 +311,10 @@ def ppo_train(env, policy_module, value_module, *, total_frames=128, frames_per_
                     rec.update({"train/credit_baseline": "learned", "train/decision_critic_loss": dl["critic_loss"],
                                 "train/decision_explained_variance": dl["explained_variance"],
                                 "train/decision_value_mean": dl["value_mean"]})
+                if credit_scope == "due":
+                    rec.update({"train/credit_scope": "due", "train/decisions_headed": int(dl["decisions_headed"])})
+                if credit_horizon == "bootstrap":
+                    rec.update({"train/credit_horizon": "bootstrap", "train/decision_bootstrapped": dl["bootstrapped"]})
             if bool(done.any()):
                 rec["transport/avg_travel_time"] = float((ag0[done, 3] - ag0[done, 2]).mean())
         # periodic evaluation (src/rl/ppo_trainer.py:147-151): MODE rollout, optionally a sampled one, on eval_env

@@ -48,6 +48,8 @@ class RunnerArgs:
     credit_gamma: float = None     # ... the discount of a traveller's frames to go, in (0, 1] (default 1.0)
     credit_baseline: str = None    # ... "learned" = the per-decision critic of DESIGN 4.27 (default "free_flow")
     credit_critic_coef: float = None   # ... the coefficient of that critic's loss (default 1.0)
+    credit_scope: str = None       # ... "due" = only roads whose head is due are credited (default "headed")
+    credit_horizon: str = None     # ... "bootstrap" = free-flow continuation past a segment cut by the batch (default "charge")
     dijkstra_envs: int = 0         # dijkstra, eval: K > 0 adds VecEvaluator(head="dijkstra") on K environments
     dijkstra_router: str = "reference"   # dijkstra_envs: "reference", "hold" (head "dijkstra_hold") or "free_flow" (hold, static tables)
     eval_link_counts: bool = False # eval_envs / dijkstra_envs: per-road link counts over the K environments (eval mode reports them)
@@ -154,6 +156,14 @@ class RunnerArgs:
             raise ValueError("credit_baseline names the baseline of the per-decision advantage: it needs credit decision")
         if self.credit_critic_coef is not None and self.credit != "decision":
             raise ValueError("credit_critic_coef weighs the per-decision critic's loss: it needs credit decision")
+        if self.credit_scope not in (None, "headed", "due"):
+            raise ValueError(f"credit_scope must be 'headed' or 'due', got {self.credit_scope!r}")
+        if self.credit_scope is not None and self.credit != "decision":
+            raise ValueError("credit_scope narrows the per-decision credit: it needs credit decision")
+        if self.credit_horizon not in (None, "charge", "bootstrap"):
+            raise ValueError(f"credit_horizon must be 'charge' or 'bootstrap', got {self.credit_horizon!r}")
+        if self.credit_horizon is not None and self.credit != "decision":
+            raise ValueError("credit_horizon closes the per-decision return: it needs credit decision")
         if self.credit_critic_coef is not None and self.credit_baseline != "learned":
             raise ValueError("credit_critic_coef weighs the learned per-decision critic's loss: it needs credit_baseline "
                              "learned (the free-flow baseline has nothing to train)")
@@ -467,7 +477,9 @@ class Runner:
                      if a.credit == "decision" else {}),
                   **({"credit_baseline": "learned",
                       "decision_critic_coef": 1.0 if a.credit_critic_coef is None else float(a.credit_critic_coef)}
-                     if a.credit_baseline == "learned" else {}), **bc_kw)
+                     if a.credit_baseline == "learned" else {}),
+                  **({"credit_scope": "due"} if a.credit_scope == "due" else {}),
+                  **({"credit_horizon": "bootstrap"} if a.credit_horizon == "bootstrap" else {}), **bc_kw)
 
     def eval(self):
         a = self.args

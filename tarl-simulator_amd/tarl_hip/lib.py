@@ -180,6 +180,12 @@ SIGNATURES = {
     "tarl_graphdist_node_logprob": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p]),
     "tarl_graphdist_decision_ppo_scratch_bytes": (_i64, [_p, _i64]),
     "tarl_graphdist_decision_ppo": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _p, _p, _p, _p, _f32, _f32, _p, _p, _p, _p]),
+    # credit scope "due" and the horizon bootstrap (csrc/decision_credit.hip)
+    "tarl_fused_head_rows_due": (C.c_int, [_p, _p, _i64, _f32, _p, _p, _i64, _p, _p, _p]),
+    "tarl_fused_set_head_capture_scope": (C.c_int, [_p, C.c_int, _p]),
+    "tarl_fused_agent_roads": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _p]),
+    "tarl_decision_advantage_boot": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64,
+                                               _f32, _f64, _p, _p, _p, _p, C.c_int, _p, _p]),
     # the learned per-decision critic (csrc/decision_critic.hip)
     "tarl_decision_critic_features": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _f32, _p, _p]),
     "tarl_decision_critic_fwd": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, _f32, _p, _f32, _p, _p, _p, _p]),

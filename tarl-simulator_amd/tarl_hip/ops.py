@@ -1610,25 +1610,54 @@ def _row_list(t, n, name):
     return t.numel()
 
 
-def fused_head_rows(plan: Plan, fs, env, slot, head_keep):
+def _counts2(counts):
+    """The {headed, due} counters of credit scope "due": int32 (2,) on the device, or None."""
+    if counts is not None:
+        _contig(counts, torch.int32, "counts")
+        if counts.numel() != 2:
+            raise ValueError(f"counts must hold two int32 {{headed, due}}, got {tuple(counts.shape)}")
+    return counts
+
+
+def fused_head_rows(plan: Plan, fs, env, slot, head_keep, t=None, counts=None):
     """``head_keep[slot[j]][u]`` (int32 (rows, N)) = the head agent id of road u in environment ``env[j]`` of ``fs`` where the
     road's FIFO is not empty, 0 otherwise (tarl_fused_head_rows): whom each road's decision of the next frame is taken for.
     ``env`` / ``slot``: int32 (n,) device tensors; the slots must be rows of ``head_keep`` (the kernel trusts them, as
-    :func:`fused_obs16_rows` trusts its own). Reads ``fs.hdp`` alone."""
+    :func:`fused_obs16_rows` trusts its own). Reads ``fs.hdp`` alone.
+    With ``t`` (credit scope "due"; tarl_fused_head_rows_due): the clock the next frame is stepped with; the id
+    only where the head's departure is ``<= t`` as well (Direction's fp32 test), and ``counts`` (int32 (2,), optional) +=
+    {roads with a head, roads with a due head}."""
     _check_dev(fs.hdp, torch.int32, "fs.hdp")
     n = _row_list(env, None, "env")
     _row_list(slot, n, "slot")
     _rows_n(head_keep, torch.int32, plan.num_nodes, "head_keep")
-    _lib.check(_lib.load().tarl_fused_head_rows(plan.handle, fs.ref, fs.B, env.data_ptr(), slot.data_ptr(), n,
-                                                head_keep.data_ptr(), _lib.current_stream()))
+    if t is None:
+        if counts is not None:
+            raise ValueError("counts belongs to the due scope: it needs the clock t")
+        _lib.check(_lib.load().tarl_fused_head_rows(plan.handle, fs.ref, fs.B, env.data_ptr(), slot.data_ptr(), n,
+                                                    head_keep.data_ptr(), _lib.current_stream()))
+        return head_keep
+    if not math.isfinite(float(t)):
+        raise ValueError(f"t must be a finite clock, got {t}")
+    _lib.check(_lib.load().tarl_fused_head_rows_due(plan.handle, fs.ref, fs.B, float(t), env.data_ptr(), slot.data_ptr(), n,
+                                                    head_keep.data_ptr(), _lib.ptr(_counts2(counts)), _lib.current_stream()))
     return head_keep
 
 
-def fused_set_head_capture(fs, on, head_keep=None, plan=None):
+def fused_set_head_capture(fs, on, head_keep=None, plan=None, scope="headed", counts=None):
     """The switch of the state-dependent T-frame rollouts (tarl_fused_set_head_capture): with ``on`` their loop queues
     :func:`fused_head_rows` for the kept (environment, slot) pairs of every frame in front of that frame's head call, into
     ``head_keep`` (int32 (rows, N), kept alive on ``fs``; its rows are the rows of the rollout's ``obs_keep``). Off (the
-    default, ``head_keep`` None) the loop queues exactly the launches it always queued."""
+    default, ``head_keep`` None) the loop queues exactly the launches it always queued.
+    ``scope="due"`` (tarl_fused_set_head_capture_scope): the loop queues the due form with every frame's clock
+    instead, ``counts`` (int32 (2,), optional, kept alive on ``fs``) += {headed, due}. ``"headed"`` makes no further call."""
+    if scope not in ("headed", "due"):
+        raise ValueError("scope must be 'headed' or 'due'")
+    if (scope == "due" or counts is not None) and not on:
+        raise ValueError("scope and counts belong to the switched-on capture")
+    if scope != "due" and counts is not None:
+        raise ValueError("counts belongs to scope 'due'")
+    _counts2(counts)
     if on:
         if head_keep is None:
             raise ValueError("the switch needs its head_keep buffer")
@@ -1639,17 +1668,50 @@ def fused_set_head_capture(fs, on, head_keep=None, plan=None):
         raise ValueError("a head_keep buffer without the switch")
     _lib.check(_lib.load().tarl_fused_set_head_capture(fs.ref, 1 if on else 0, _lib.ptr(head_keep)))
     fs.head_keep = head_keep
+    fs.head_counts = None
+    if scope == "due":
+        _lib.check(_lib.load().tarl_fused_set_head_capture_scope(fs.ref, 1, _lib.ptr(counts)))
+        fs.head_counts = counts
+
+
+def fused_agent_roads(plan: Plan, fs, Nmax, out=None, bad=None):
+    """-> int32 (B, A): the road every agent of ``fs`` is queued on, -1 where it is queued nowhere (waiting, arrived, or lost)
+    (tarl_fused_agent_roads). Reads the packed FIFOs alone (count, ring offset, the slots below the count) and
+    writes nothing of the state. ``bad`` (int32 (1,), optional) += the ids outside [1, A) it met, plus, off the defined domain,
+    the whole count of a row whose ring offset is >= Nmax (nothing of it is read) and the part of a count above Nmax."""
+    _check_dev(fs.hdp, torch.int32, "fs.hdp")
+    if out is None:
+        out = torch.empty((fs.B, fs.A), dtype=torch.int32, device=fs.hdp.device)
+    _contig(out, torch.int32, "out")
+    if tuple(out.shape) != (fs.B, fs.A):
+        raise ValueError(f"out must be ({fs.B}, {fs.A}), got {tuple(out.shape)}")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=out.device)
+    _contig(bad, torch.int32, "bad")
+    if bad.numel() != 1:
+        raise ValueError("bad must hold one int32")
+    _lib.check(_lib.load().tarl_fused_agent_roads(plan.handle, fs.ref, fs.B, fs.A, int(Nmax), out.data_ptr(), bad.data_ptr(),
+                                                  _lib.current_stream()))
+    return out
 
 
 def decision_advantage(plan: Plan, head_keep, frame, env, slot, agent_features, times, t_end, dist, dest_slot, *, B,
-                       timestep, decision_gamma=1.0, adv_raw, truncated, bad):
+                       timestep, decision_gamma=1.0, adv_raw, truncated, bad, agent_road=None, bootstrap=False,
+                       bootstrapped=None):
     """The raw per-decision advantage of the kept rows of ONE episode segment (tarl_decision_advantage), to be called
     before the engine is reset: row j is frame ``frame[j]``, environment ``env[j]``, row ``slot[j]`` of ``head_keep`` /
     ``adv_raw`` ((rows, N) int32 / fp32). ``times`` (T + 1,) fp32 device clocks, ``t_end``: the segment ends after frame
     t_end - 1; ``dist`` (D, N) float64 free-flow distances of :func:`destination_trees`, ``dest_slot`` (N,) int32.
     Writes ``adv_raw`` of every road of the listed rows (0 where not live), clears ``head_keep`` where the decision is not
-    live, and adds to ``truncated`` / ``bad`` (int32 (1,))."""
+    live, and adds to ``truncated`` / ``bad`` (int32 (1,)).
+    With ``agent_road`` (int32 (B, A) of :func:`fused_agent_roads`, taken when the segment ended) and ``bootstrapped``
+    (int32 (1,)) the call is tarl_decision_advantage_boot: ``bootstrap`` True continues a traveller still under
+    way at the horizon in free flow from the road it is queued on and counts it in ``bootstrapped`` instead of
+    ``truncated``; False gives the plain call's output bit for bit."""
     N = plan.num_nodes
+    boot_call = agent_road is not None or bootstrapped is not None
+    if bootstrap and not boot_call:
+        raise ValueError("bootstrap needs agent_road and bootstrapped")
     n = _row_list(frame, None, "frame")
     _row_list(env, n, "env")
     _row_list(slot, n, "slot")
@@ -1670,11 +1732,23 @@ def decision_advantage(plan: Plan, head_keep, frame, env, slot, agent_features, 
         raise ValueError(f"t_end must be in [1, {times.numel()}], got {t_end}")
     if not (float(timestep) > 0.0 and 0.0 < float(decision_gamma) <= 1.0):
         raise ValueError("timestep must be positive and decision_gamma in (0, 1]")
-    _lib.check(_lib.load().tarl_decision_advantage(
-        plan.handle, head_keep.data_ptr(), frame.data_ptr(), env.data_ptr(), slot.data_ptr(), n, int(B),
-        agent_features.data_ptr(), A, abs_, times.data_ptr(), times.numel(), int(t_end), dist.data_ptr(), dest_slot.data_ptr(),
-        dist.size(0), float(timestep), float(decision_gamma), adv_raw.data_ptr(), truncated.data_ptr(), bad.data_ptr(),
-        _lib.current_stream()))
+    args = (plan.handle, head_keep.data_ptr(), frame.data_ptr(), env.data_ptr(), slot.data_ptr(), n, int(B),
+            agent_features.data_ptr(), A, abs_, times.data_ptr(), times.numel(), int(t_end), dist.data_ptr(),
+            dest_slot.data_ptr(), dist.size(0), float(timestep), float(decision_gamma), adv_raw.data_ptr(),
+            truncated.data_ptr(), bad.data_ptr())
+    if not boot_call:
+        _lib.check(_lib.load().tarl_decision_advantage(*args, _lib.current_stream()))
+        return adv_raw
+    if agent_road is None or bootstrapped is None:
+        raise ValueError("agent_road and bootstrapped go together")
+    _contig(agent_road, torch.int32, "agent_road")
+    if tuple(agent_road.shape) != (int(B), A):
+        raise ValueError(f"agent_road must be ({int(B)}, {A}), got {tuple(agent_road.shape)}")
+    _contig(bootstrapped, torch.int32, "bootstrapped")
+    if bootstrapped.numel() != 1:
+        raise ValueError("bootstrapped must hold one int32")
+    _lib.check(_lib.load().tarl_decision_advantage_boot(*args, agent_road.data_ptr(), 1 if bootstrap else 0,
+                                                        bootstrapped.data_ptr(), _lib.current_stream()))
     return adv_raw
 
 

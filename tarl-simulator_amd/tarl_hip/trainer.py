@@ -73,7 +73,8 @@ class VecPPOTrainer:
                  prior_weight=1.0, gt_params=None, gt_pe=None, value="simple", gt_value_params=None, gt_value_pe=None,
                  prior_free_flow=None, prior_dests=None, policy_hold=False, goal_mlp_params=None,
                  route_departures=False, reward="queue", credit="joint", decision_gamma=1.0, credit_baseline="free_flow",
-                 decision_critic_params=None, decision_critic_coef=1.0, decision_delay_scale=16.0):
+                 decision_critic_params=None, decision_critic_coef=1.0, decision_delay_scale=16.0, credit_scope="headed",
+                 credit_horizon="charge"):
         """``emb_param``: nn.Parameter (num_nodes, 1) — MPNNPolicyNet.nodes_embedding.weight;
         ``critic_params``: [w1 (64,N+1), b1, w2 (64,64), b2, w3 (1,64), b3] — MPNNValueNetSimple.final_mlp.{0,2,4};
         ``extra_params``: further actor/critic parameters that never receive gradient on the live path (the dormant
@@ -107,6 +108,12 @@ class VecPPOTrainer:
         traveller's frames to go, separate from GAE's ``gamma``. State-dependent heads on the fused path with the default
         critic only. ``self.last["decision"]`` then carries the live decisions, their mean delay in frames, the truncated
         share, the objective, the clip fraction and the approximate KL of the last minibatch (0-d device tensors).
+        ``credit_scope`` / ``credit_horizon`` (``credit="decision"`` only, both combine with the learned baseline):
+        ``"due"`` credits only the roads whose head is due at the frame's clock (the draw of a road whose head is still
+        travelling reaches nobody; ops.fused_set_head_capture(scope="due")); ``"bootstrap"`` continues a traveller still under
+        way when a segment is cut by the batch in free flow from the road it is queued on (ops.fused_agent_roads, once per
+        segment) instead of charging it the frames to the horizon; a segment that ends with the episode keeps the charge.
+        ``self.last["decision"]`` then gains ``credit_scope`` / ``decisions_headed`` and ``credit_horizon`` / ``bootstrapped``.
         ``credit_baseline`` (DESIGN 4.27; ``credit="decision"`` only): ``"free_flow"`` (the default) is the baseline above;
         ``"learned"`` (not in the reference) adds a per-decision critic (csrc/decision_critic.hip) on the state in front of
         the decision: ``decision_critic_params`` = [w1 (16, 8), b1 (16,), w2 (1, 16), b2 (1,)], consecutive in
@@ -238,6 +245,13 @@ class VecPPOTrainer:
         self.decision_gamma = float(decision_gamma)
         if credit == "decision":
             self._check_decision_credit(engine, value)
+        self._check_credit_scope(credit, credit_scope, credit_horizon)
+        self.credit_scope, self.credit_horizon = credit_scope, credit_horizon
+        if credit_scope == "due":           # {headed, due} over the kept rows of one collect()
+            self.decision_counts = torch.zeros(2, dtype=torch.int32, device=engine.device)
+        if credit_horizon == "bootstrap":   # where every agent stands when a segment ends; the decisions continued from there
+            self.agent_road = torch.empty((engine.B, engine.A), dtype=torch.int32, device=engine.device)
+            self.decision_bootstrapped = torch.zeros(1, dtype=torch.int32, device=engine.device)
         if credit_baseline not in ("free_flow", "learned"):
             raise ValueError("credit_baseline must be 'free_flow' or 'learned'")
         self.credit_baseline = credit_baseline
@@ -358,6 +372,18 @@ class VecPPOTrainer:
         self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._decision_dist = None          # (dist float64 (D, N), dest_slot int32 (N,)): built once, after the first reset
         self.head_keep = self.adv_raw = self.lp_old_node = None
+
+    @staticmethod
+    def _check_credit_scope(credit, credit_scope, credit_horizon):
+        """Refusals of credit_scope / credit_horizon."""
+        if credit_scope not in ("headed", "due"):
+            raise ValueError("credit_scope must be 'headed' or 'due'")
+        if credit_horizon not in ("charge", "bootstrap"):
+            raise ValueError("credit_horizon must be 'charge' or 'bootstrap'")
+        if credit_scope != "headed" and credit != "decision":
+            raise ValueError("credit_scope narrows the per-decision credit: it needs credit decision")
+        if credit_horizon != "charge" and credit != "decision":
+            raise ValueError("credit_horizon closes the per-decision return: it needs credit decision")
 
     def _check_decision_critic(self, credit, params, extra_params):
         """Refusals of credit_baseline="learned" -> the four parameter tensors."""
@@ -510,7 +536,14 @@ class VecPPOTrainer:
                     if self._decision_dist is None:
                         self._build_decision_dist()
                     self.decision_truncated.zero_()
-                    ops.fused_set_head_capture(eng.fs, True, self.head_keep, plan=eng.plan)
+                    if self.credit_horizon == "bootstrap":
+                        self.decision_bootstrapped.zero_()
+                    if self.credit_scope == "due":
+                        self.decision_counts.zero_()
+                        ops.fused_set_head_capture(eng.fs, True, self.head_keep, plan=eng.plan, scope="due",
+                                                   counts=self.decision_counts)
+                    else:
+                        ops.fused_set_head_capture(eng.fs, True, self.head_keep, plan=eng.plan)
             else:
                 emb = self._emb()
                 eng.prepare_policy(emb, self.temperature)      # once per parameter update, not per frame
@@ -594,10 +627,15 @@ class VecPPOTrainer:
             self.frames_left.index_copy_(0, keep_slot[lo:hi].to(torch.int64), sl.stop - self._keep_frames[lo:hi])
         self.times[sl.start:sl.stop].copy_(torch.tensor(host_times[sl.start:sl.stop], dtype=torch.float32))
         dist, slot = self._decision_dist
+        boot = {}
+        if self.credit_horizon == "bootstrap":      # a segment cut by the batch is bootstrapped; an episode that ended is not
+            ops.fused_agent_roads(eng.plan, eng.fs, eng.Nmax, out=self.agent_road, bad=self.decision_bad)
+            boot = dict(agent_road=self.agent_road, bootstrap=bool(eng.time <= EPISODE_END),
+                        bootstrapped=self.decision_bootstrapped)
         ops.decision_advantage(eng.plan, self.head_keep, self._keep_frames[lo:hi], keep_env[lo:hi], keep_slot[lo:hi],
                                eng.agents, self.times, sl.stop, dist, slot, B=eng.B, timestep=eng.timestep,
                                decision_gamma=self.decision_gamma, adv_raw=self.adv_raw, truncated=self.decision_truncated,
-                               bad=self.decision_bad)
+                               bad=self.decision_bad, **boot)
 
     def _draw_minibatch_frames(self):
         """State-dependent heads: the update only ever reads the observations of its minibatch frames, and those frames are
@@ -933,6 +971,12 @@ class VecPPOTrainer:
         rep = {"decisions": st[2], "delay_frames": -st[0] / cnt,
                "truncated": self.decision_truncated[0].to(torch.float64) / cnt, "objective": -tot[0] / live,
                "clip_fraction": tot[2] / live, "kl": tot[3] / live}
+        if self.credit_scope == "due":          # the kept rows' roads with a head, of which ``decisions`` were due and live
+            rep["credit_scope"] = "due"
+            rep["decisions_headed"] = self.decision_counts[0].to(torch.float64)
+        if self.credit_horizon == "bootstrap":  # the share continued beyond the horizon (``truncated``: the share charged)
+            rep["credit_horizon"] = "bootstrap"
+            rep["bootstrapped"] = self.decision_bootstrapped[0].to(torch.float64) / cnt
         if self.decision_critic_params is not None:      # the last epoch's five sums, over all ranks
             out5, off, M = self._dcritic_last
             # ... and the sum of the values the advantages were formed with (0 where not live)

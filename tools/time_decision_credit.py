@@ -16,8 +16,15 @@
       ``actor_logits_bwd`` — and the critic's forward over all kept rows, once per update; (b) runs the same experiment with
       credit "decision" and the learned baseline (rows "learned", with the critic's explained variance per iteration).
 
+  --credit-scope due / --credit-horizon bootstrap: the rows of the narrowed credit instead. (a) then times
+      tarl_fused_head_rows_due beside tarl_fused_head_rows, tarl_fused_agent_roads (once per segment) and one ``collect()``
+      with the flags against one without; (b) runs the same experiment with credit "decision" and the flags given (rows "due",
+      "bootstrap", "due+boot"; with --credit-baseline learned "due+boot+L"), with the headed and bootstrapped counts per
+      iteration.
+
     python tools/time_decision_credit.py [--envs 64] [--reps 5] [--ppo] [--ppo-iterations 10] [--schedules 1:32:1e-3,...]
-                                         [--credit-baseline {free_flow,learned}]"""
+                                         [--credit-baseline {free_flow,learned}] [--credit-scope {headed,due}]
+                                         [--credit-horizon {charge,bootstrap}]"""
 import argparse
 import math
 import os
@@ -54,8 +61,10 @@ def _mean_se(v):
     return m, (math.sqrt(sum((x - m) ** 2 for x in v) / (n - 1) / n) if n > 1 else float("nan"))
 
 
-def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="trip", rules=True, baseline="free_flow"):
-    """``baseline`` "learned" (with ``credit`` "decision"): the learned per-decision critic of DESIGN 4.27."""
+def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="trip", rules=True, baseline="free_flow",
+            scope="headed", horizon="charge"):
+    """``baseline`` "learned" (with ``credit`` "decision"): the learned per-decision critic of DESIGN 4.27; ``scope`` "due" /
+    ``horizon`` "bootstrap": the narrowed credit of DESIGN 4.28."""
     from src.agents.mpnn_agent import MPNNPolicyNet, MPNNValueNetSimple
     N, Nmax = net.num_roads, net.Nmax
     eng = SimEngine(net.x.cuda(), net.edge_index, net.edge_attr, Nmax, pop.cuda(), congestion_constant=net.congestion_constant,
@@ -69,6 +78,10 @@ def trainer(net, pop, B, T, *, credit, epochs=1, M=32, lr=1e-3, seed=5, reward="
     l, gm = val.final_mlp, pol.goal_mlp
     critic = ops.decision_critic_init("cuda", seed) if baseline == "learned" else []
     kw = dict(credit_baseline="learned", decision_critic_params=critic) if critic else {}
+    if scope != "headed":
+        kw["credit_scope"] = scope
+    if horizon != "charge":
+        kw["credit_horizon"] = horizon
     tr = VecPPOTrainer(eng, pol.nodes_embedding.weight, [l[0].weight, l[0].bias, l[2].weight, l[2].bias, l[4].weight, l[4].bias],
                        rollout_steps=T, num_epochs=epochs, sub_batch_size=M, lr=lr,
                        extra_params=[p for n, p in pol.named_parameters() if not n.startswith("nodes_embedding")] + critic,
@@ -172,6 +185,65 @@ def cost(label, net, pop, B, T, M, reps):
     tr.check_flags()
 
 
+def _per_call(fn, reps, calls=50):
+    v = []
+    for r in range(reps + 1):                   # one warm-up round
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        if r:
+            v.append(a.elapsed_time(b) / calls * 1e3)
+    return v
+
+
+def scope_cost(label, net, pop, B, T, M, reps, scope, horizon):
+    """The launches of DESIGN 4.28 beside the one they replace, and a ``collect()`` frame with and without the flags."""
+    say(f"{label}: N = {net.num_roads}, B = {B}, T = {T} frames, minibatch M = {M}, goal_mlp head, credit_scope {scope}, "
+        f"credit_horizon {horizon}")
+    trs = {"decision": trainer(net, pop, B, T, credit="decision", M=M, rules=False, reward="queue")[0],
+           "narrowed": trainer(net, pop, B, T, credit="decision", M=M, rules=False, reward="queue", scope=scope,
+                               horizon=horizon)[0]}
+    times = {c: [] for c in trs}
+    for r in range(reps + 1):                   # one warm-up round, variants alternating
+        for c, tr in trs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            tr.collect()
+            b.record()
+            torch.cuda.synchronize()
+            if r:
+                times[c].append(a.elapsed_time(b) / T * 1e3)
+    for c in trs:
+        say(f"  collect, {c:9} {med(times[c])} per frame")
+    tr = trs["narrowed"]
+    eng = tr.eng
+    n = max(1, M // T)
+    env = torch.zeros(n, dtype=torch.int32, device="cuda")
+    slot = torch.arange(n, dtype=torch.int32, device="cuda")
+    hk = torch.empty_like(tr.head_keep)
+    counts = torch.zeros(2, dtype=torch.int32, device="cuda")
+    clock = float(eng.time)
+    v = _per_call(lambda: ops.fused_head_rows(eng.plan, eng.fs, env, slot, hk), reps)
+    say(f"  tarl_fused_head_rows,     {n} pair(s): {med(v)} per launch (50 launches per sample)")
+    v = _per_call(lambda: ops.fused_head_rows(eng.plan, eng.fs, env, slot, hk, t=clock, counts=counts), reps)
+    say(f"  tarl_fused_head_rows_due, {n} pair(s): {med(v)} per launch (50 launches per sample)")
+    road = torch.empty((eng.B, eng.A), dtype=torch.int32, device="cuda")
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    v = _per_call(lambda: ops.fused_agent_roads(eng.plan, eng.fs, eng.Nmax, out=road, bad=bad), reps)
+    say(f"  tarl_fused_agent_roads (fill + kernel, once per segment), {int((road >= 0).sum())} of {road.numel()} agents queued: "
+        f"{med(v)} per call (50 calls per sample)")
+    tr.check_flags()
+
+
+VARIANTS = {"joint": {}, "decision": {}, "learned": dict(baseline="learned"), "due": dict(scope="due"),
+            "bootstrap": dict(horizon="bootstrap"), "due+boot": dict(scope="due", horizon="bootstrap"),
+            "due+boot+L": dict(scope="due", horizon="bootstrap", baseline="learned"),
+            "due+L": dict(scope="due", baseline="learned"), "bootstrap+L": dict(horizon="bootstrap", baseline="learned")}
+
+
 def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules, credits=("joint", "decision")):
     from tarl_hip.imitation import BCTrainer
     net = synth.torus_network(8, 8)
@@ -185,8 +257,8 @@ def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules, credits=("joi
     for epochs, M, lr in schedules:
         say(f"schedule: {epochs} epoch(s) of one minibatch of {M} frames per iteration, lr {lr:g}")
         for credit in credits:
-            tr, pol = trainer(net, pop, K, T, credit="decision" if credit == "learned" else credit, epochs=epochs, M=M, lr=lr,
-                              baseline="learned" if credit == "learned" else "free_flow")
+            tr, pol = trainer(net, pop, K, T, credit="joint" if credit == "joint" else "decision", epochs=epochs, M=M, lr=lr,
+                              **VARIANTS[credit])
             bc = BCTrainer(tr, engine(16, 11), expert="dijkstra", driver="dagger", frames=T, samples=512, epochs=4, batch=64,
                            lr=1e-2)
             acc = [bc.iterate()["accuracy_after"] for _ in range(bc_iterations)]
@@ -205,13 +277,21 @@ def ppo_after_cloning(K, bc_iterations, ppo_iterations, schedules, credits=("joi
             evaluate("cloned")
             for it in range(ppo_iterations):
                 tr.collect()
+                on_way = float(tr.eng.agents[:, :, 7].sum()) / K
+                queued = float(tr.eng.x[:, :, 3 * net.Nmax + 1].sum()) / K
                 out = tr.update().tolist()
                 line = f"    [ppo {it}] collected reward per frame {float(tr.reward.mean()):9.3f}  joint kl {out[4]:.5f}"
+                d = {}                       # the joint row has no per-decision figures
                 if credit != "joint":
-                    d = {k: float(v) for k, v in tr.last["decision"].items()}
+                    d = {k: float(v) for k, v in tr.last["decision"].items() if not isinstance(v, str)}
                     line += (f"  decisions {int(d['decisions'])}  delay {d['delay_frames']:.2f} frames  truncated "
                              f"{d['truncated']:.3f}  objective {d['objective']:.4f}  clip {d['clip_fraction']:.3f}  kl {d['kl']:.5f}")
-                if credit == "learned":
+                if "decisions_headed" in d:
+                    line += f"  headed {int(d['decisions_headed'])}"
+                if "bootstrapped" in d:      # ... and who is left when the segment ends: ON_WAY agents against queued ones
+                    line += (f"  bootstrapped {d['bootstrapped']:.3f}  on the way {on_way:.1f} of which queued {queued:.2f} per "
+                             f"environment")
+                if "critic_loss" in d:
                     line += (f"  critic loss {d['critic_loss']:.4f}  explained variance {d['explained_variance']:.3f}  value mean "
                              f"{d['value_mean']:.3f}")
                 say(line)
@@ -232,6 +312,8 @@ def main():
     ap.add_argument("--ppo-iterations", type=int, default=10)
     ap.add_argument("--schedules", default="1:32:1e-3,4:256:1e-3,8:512:3e-3")
     ap.add_argument("--credit-baseline", choices=("free_flow", "learned"), default="free_flow")
+    ap.add_argument("--credit-scope", choices=("headed", "due"), default="headed")
+    ap.add_argument("--credit-horizon", choices=("charge", "bootstrap"), default="charge")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "decision_credit_time.log"))
     a = ap.parse_args()
     LOG = open(a.log, "a")
@@ -243,8 +325,12 @@ def main():
         if not arg.startswith("--log="):
             shown.append(arg)
     learned = a.credit_baseline == "learned"
-    say(f"# tools/time_decision_credit.py {' '.join(shown)}   (MI355X; DESIGN {'4.27' if learned else '4.26'})")
+    narrowed = a.credit_scope != "headed" or a.credit_horizon != "charge"
+    say(f"# tools/time_decision_credit.py {' '.join(shown)}   (MI355X; DESIGN "
+        f"{'4.28' if narrowed else '4.27' if learned else '4.26'})")
     cost_fn = critic_cost if learned else cost
+    if narrowed:
+        cost_fn = lambda *args: scope_cost(*args, a.credit_scope, a.credit_horizon)      # noqa: E731
     if not a.no_cost:
         say("(a) cost: HIP events, median (min - max) of the repetitions after one warm-up round")
         net = synth.torus_network(8, 8)
@@ -256,7 +342,10 @@ def main():
         cost_fn("config-4 geometry (25 x 25 torus, 16 384 agents)", net, pop, a.envs, 32, 32, a.reps)
     if a.ppo:
         sched = [(int(e), int(m), float(lr)) for e, m, lr in (s.split(":") for s in a.schedules.split(","))]
-        ppo_after_cloning(a.envs, a.bc_iterations, a.ppo_iterations, sched, ("learned",) if learned else ("joint", "decision"))
+        row = "+".join(n for n, on in (("due", a.credit_scope == "due"), ("boot", a.credit_horizon == "bootstrap")) if on)
+        row = {"due": "due", "boot": "bootstrap"}.get(row, row) + ("+L" if learned else "")
+        ppo_after_cloning(a.envs, a.bc_iterations, a.ppo_iterations, sched,
+                          (row,) if narrowed else ("learned",) if learned else ("joint", "decision"))
     LOG.close()
 
 
