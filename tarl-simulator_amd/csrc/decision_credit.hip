@@ -14,30 +14,26 @@
 //   k_graphdist_node_logprob log(p_choice + 1e-8) per node, k_softmax's expressions.
 //   k_graphdist_decision_ppo the clipped objective per live node, forward and backward, plus k_decision_ppo_reduce per sample.
 //
-// All per-node kernels: one lane per node, tiles of DC_TILE nodes, the (row, tile) pairs flattened into grid.x; on a
-// source-sorted edge list (CSR position == edge id) the edge-id indirection is skipped. No floating-point atomics: the
-// sums are fixed trees (lanes l and l + 32, 16, .., 1 of a wave, the tile's four waves in order, the tiles in order).
+// All per-node kernels have tile_sums.h's launch shape (one lane per node, the (row, tile) pairs flattened into grid.x); on
+// a source-sorted edge list (CSR position == edge id) the edge-id indirection is skipped. No floating-point atomics: the
+// sums are tile_sums.h's fixed trees.
 #include <mutex>
 #include <unordered_map>
 
 #include "rollout_heads.h"
+#include "tile_sums.h"
 
-#define DC_TILE 256
-#define DC_MAX_BLOCKS ((int64_t)1 << 24)   // (row, tile) pairs of one launch: grid.x * DC_TILE stays below 2^32 threads
 #define DC_STAT_BLOCKS 256
 #define DC_STD_FLOOR 1e-6f                 // = TARL_ADV_STD_FLOOR (ppo.hip): the rule of tarl_advantage_normalize
-
-static inline int64_t dc_tiles(const tarl_plan* plan) { return ceil_div(plan->N > 0 ? plan->N : 1, DC_TILE); }
 
 // ---- (1) the heads of the kept rows ---------------------------------------------------------------------------------------
 // Must move per (pair, road): the 4-byte hd word of hdp[u][env] (a stride of 8 B bytes between the lanes of a wave: the packed
 // state is env-minor and a kept pair is one environment, as for tarl_fused_obs16_rows) and one coalesced 4-byte store.
-__global__ __launch_bounds__(DC_TILE) void k_fused_head_rows(const uint32_t* __restrict__ hdp_words, int64_t N, uint32_t B,
+__global__ __launch_bounds__(TS_TILE) void k_fused_head_rows(const uint32_t* __restrict__ hdp_words, int64_t N, uint32_t B,
                                                              uint32_t tiles, const int32_t* __restrict__ env,
                                                              const int32_t* __restrict__ slot,
                                                              int32_t* __restrict__ head_keep) {
-  const uint32_t j = blockIdx.x / tiles, tile = blockIdx.x - j * tiles;
-  const int64_t u = (int64_t)tile * DC_TILE + threadIdx.x;
+  const auto [j, u] = ts_at(tiles);
   if (u >= N) return;
   const int32_t b = env[j];
   int32_t v = 0;
@@ -50,8 +46,8 @@ __global__ __launch_bounds__(DC_TILE) void k_fused_head_rows(const uint32_t* __r
 
 int tarl_launch_head_rows(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, const int32_t* env,
                           const int32_t* slot, int64_t n, int32_t* head_keep) {
-  const int64_t tiles = dc_tiles(plan);
-  hipLaunchKernelGGL(k_fused_head_rows, dim3((unsigned)(n * tiles)), dim3(DC_TILE), 0, s, (const uint32_t*)f->hdp, plan->N,
+  const int64_t tiles = ts_tiles(plan);
+  hipLaunchKernelGGL(k_fused_head_rows, dim3((unsigned)(n * tiles)), dim3(TS_TILE), 0, s, (const uint32_t*)f->hdp, plan->N,
                      (uint32_t)B, (uint32_t)tiles, env, slot, head_keep);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
@@ -60,7 +56,8 @@ int tarl_launch_head_rows(hipStream_t s, const tarl_plan* plan, const tarl_fused
 int tarl_check_head_rows(const tarl_plan* plan, const tarl_fused* f, int64_t B, int64_t n) {
   TARL_REQUIRE(plan && f && f->hdp, "null argument");
   TARL_REQUIRE(B >= 1 && plan->N * B < ((int64_t)1 << 31), "bad sizes (N * B must stay below 2^31)");
-  TARL_REQUIRE(n >= 0 && n * dc_tiles(plan) < DC_MAX_BLOCKS, "too many (pair, tile) pairs for one launch");
+  TARL_REQUIRE(n >= 0, "bad sizes");
+  TS_REQUIRE_PAIRS(n, ts_tiles(plan));
   return TARL_OK;
 }
 
@@ -78,14 +75,13 @@ extern "C" int tarl_fused_head_rows(const tarl_plan* plan, const tarl_fused* f, 
 // holds somebody AND its head's departure has come at the clock the frame is stepped with (Direction's fp32 test,
 // fused_direction.hip), 0 elsewhere. The count test comes first: an empty road's dep word may be stale (lazy rows,
 // fused_common.h). counts2 (optional) += {headed, due}, one integer atomic each per wave.
-__global__ __launch_bounds__(DC_TILE) void k_fused_head_rows_due(const uint2* __restrict__ hdp, int64_t N, uint32_t B,
+__global__ __launch_bounds__(TS_TILE) void k_fused_head_rows_due(const uint2* __restrict__ hdp, int64_t N, uint32_t B,
                                                                  uint32_t tiles, float t_clock,
                                                                  const int32_t* __restrict__ env,
                                                                  const int32_t* __restrict__ slot,
                                                                  int32_t* __restrict__ head_keep,
                                                                  int32_t* __restrict__ counts2) {
-  const uint32_t j = blockIdx.x / tiles, tile = blockIdx.x - j * tiles;
-  const int64_t u = (int64_t)tile * DC_TILE + threadIdx.x;
+  const auto [j, u] = ts_at(tiles);
   bool headed = false, due = false;
   if (u < N) {
     const int32_t b = env[j];
@@ -109,8 +105,8 @@ __global__ __launch_bounds__(DC_TILE) void k_fused_head_rows_due(const uint2* __
 
 int tarl_launch_head_rows_due(hipStream_t s, const tarl_plan* plan, const tarl_fused* f, int64_t B, float t_clock,
                               const int32_t* env, const int32_t* slot, int64_t n, int32_t* head_keep, int32_t* counts2) {
-  const int64_t tiles = dc_tiles(plan);
-  hipLaunchKernelGGL(k_fused_head_rows_due, dim3((unsigned)(n * tiles)), dim3(DC_TILE), 0, s, (const uint2*)f->hdp, plan->N,
+  const int64_t tiles = ts_tiles(plan);
+  hipLaunchKernelGGL(k_fused_head_rows_due, dim3((unsigned)(n * tiles)), dim3(TS_TILE), 0, s, (const uint2*)f->hdp, plan->N,
                      (uint32_t)B, (uint32_t)tiles, t_clock, env, slot, head_keep, counts2);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
@@ -180,11 +176,11 @@ extern "C" int tarl_fused_set_head_capture_scope(tarl_fused* f, int scope, int32
 // FIFO (the slot AT the count holds the pending garbage triple and is never read). Must move per (road, environment): 8 + 4
 // bytes of dense words, and per queued agent one 4-byte id read and one 4-byte integer atomicMax (an agent is queued on one
 // road, so the max has one candidate and the result does not depend on scheduling). Writes nothing of the packed state.
-__global__ __launch_bounds__(DC_TILE) void k_fused_agent_roads(const uint2* __restrict__ hdp, const uint32_t* __restrict__ tl,
+__global__ __launch_bounds__(TS_TILE) void k_fused_agent_roads(const uint2* __restrict__ hdp, const uint32_t* __restrict__ tl,
                                                                const float* __restrict__ slots, int64_t lds, int64_t NB,
                                                                uint32_t B, int32_t Nmax, int64_t A,
                                                                int32_t* __restrict__ agent_road, int32_t* __restrict__ bad) {
-  const int64_t i = (int64_t)blockIdx.x * DC_TILE + threadIdx.x;      // = u * B + b
+  const int64_t i = (int64_t)blockIdx.x * TS_TILE + threadIdx.x;      // = u * B + b
   if (i >= NB) return;
   int32_t cnt = (int32_t)(hdp[i].x & HD_CNT);
   if (cnt == 0) return;
@@ -220,7 +216,7 @@ extern "C" int tarl_fused_agent_roads(const tarl_plan* plan, const tarl_fused* f
   if (plan->N == 0) return TARL_OK;
   const FusedBufs fb = tarl_to_bufs(f);
   const int64_t NB = plan->N * B;
-  hipLaunchKernelGGL(k_fused_agent_roads, dim3((unsigned)ceil_div(NB, DC_TILE)), dim3(DC_TILE), 0, s, (const uint2*)fb.hdp,
+  hipLaunchKernelGGL(k_fused_agent_roads, dim3((unsigned)ceil_div(NB, TS_TILE)), dim3(TS_TILE), 0, s, (const uint2*)fb.hdp,
                      (const uint32_t*)fb.tl, (const float*)fb.slots, fb.lds, NB, (uint32_t)B, Nmax, A, agent_road, bad);
   TARL_LAUNCH_CHECK();
   return TARL_OK;
@@ -239,15 +235,14 @@ __device__ __forceinline__ double dc_owed(double n, double gamma) {
 // road r it is queued on (agent_road): n = (t_end - t) + dist[s][r] / timestep, counted in `bootstrapped`; one queued nowhere
 // (lost) or with no finite dist[s][r] keeps the charge and counts in `truncated`. Two more scattered gathers on such a lane.
 template <bool BOOT>
-__global__ __launch_bounds__(DC_TILE) void k_decision_advantage(
+__global__ __launch_bounds__(TS_TILE) void k_decision_advantage(
     const int32_t* __restrict__ out_ptr, int64_t N, uint32_t tiles, int32_t* __restrict__ head_keep,
     const int32_t* __restrict__ frame, const int32_t* __restrict__ env, const int32_t* __restrict__ slot, int64_t B,
     const float* __restrict__ ag, int64_t A, int64_t a_bstride, const float* __restrict__ times, int32_t t_end,
     const double* __restrict__ dist, const int32_t* __restrict__ dest_slot, int64_t D, double timestep, double gamma,
     float* __restrict__ adv_raw, int32_t* __restrict__ truncated, int32_t* __restrict__ bad,
     const int32_t* __restrict__ agent_road, int32_t* __restrict__ bootstrapped) {
-  const uint32_t j = blockIdx.x / tiles, tile = blockIdx.x - j * tiles;
-  const int64_t u = (int64_t)tile * DC_TILE + threadIdx.x;
+  const auto [j, u] = ts_at(tiles);
   bool is_bad = false, is_trunc = false, is_boot = false;
   if (u < N) {
     const int64_t at = (int64_t)slot[j] * N + u;
@@ -326,11 +321,11 @@ static int decision_advantage_impl(const tarl_plan* plan, int32_t* head_keep, co
   TARL_REQUIRE(t_end >= 1 && t_end <= num_times && num_times < ((int64_t)1 << 31), "t_end outside the clocks");
   TARL_REQUIRE(timestep > 0.0f && std::isfinite(timestep), "timestep must be positive and finite");
   TARL_REQUIRE(decision_gamma > 0.0 && decision_gamma <= 1.0, "decision_gamma must be in (0, 1]");
-  const int64_t tiles = dc_tiles(plan);
-  TARL_REQUIRE(rows * tiles < DC_MAX_BLOCKS, "too many (row, tile) pairs for one launch");
+  const int64_t tiles = ts_tiles(plan);
+  TS_REQUIRE_PAIRS(rows, tiles);
   if (rows == 0 || plan->N == 0) return TARL_OK;
 #define DC_LAUNCH(BOOT_)                                                                                                   \
-  hipLaunchKernelGGL(k_decision_advantage<BOOT_>, dim3((unsigned)(rows * tiles)), dim3(DC_TILE), 0, (hipStream_t)stream,   \
+  hipLaunchKernelGGL(k_decision_advantage<BOOT_>, dim3((unsigned)(rows * tiles)), dim3(TS_TILE), 0, (hipStream_t)stream,   \
                      plan->out_ptr, plan->N, (uint32_t)tiles, head_keep, frame, env, slot, B, agent_features, num_agents,  \
                      a_bstride, times, (int32_t)t_end, dist, dest_slot, num_dests, (double)timestep, decision_gamma,       \
                      adv_raw, truncated, bad, agent_road, bootstrapped)
@@ -368,63 +363,36 @@ extern "C" int tarl_decision_advantage_boot(const tarl_plan* plan, int32_t* head
 }
 
 // ---- (3) statistics over the live decisions ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(DC_TILE) void k_decision_stats_partial(const float* __restrict__ a,
+__global__ __launch_bounds__(TS_TILE) void k_decision_stats_partial(const float* __restrict__ a,
                                                                     const int32_t* __restrict__ head, int64_t n,
                                                                     double* __restrict__ partial) {
-  __shared__ double s_red[DC_TILE / 64][3];
-  double x1 = 0.0, x2 = 0.0, x3 = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * DC_TILE + threadIdx.x; i < n; i += (int64_t)gridDim.x * DC_TILE) {
+  __shared__ double s_red[TS_WAVES][3];
+  double x[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = (int64_t)blockIdx.x * TS_TILE + threadIdx.x; i < n; i += (int64_t)gridDim.x * TS_TILE) {
     if (head[i] > 0) {
       const double v = (double)a[i];
-      x1 += v;
-      x2 += v * v;
-      x3 += 1.0;
+      x[0] += v;
+      x[1] += v * v;
+      x[2] += 1.0;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    x1 += __shfl_down(x1, off);
-    x2 += __shfl_down(x2, off);
-    x3 += __shfl_down(x3, off);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) {
-    s_red[wid][0] = x1;
-    s_red[wid][1] = x2;
-    s_red[wid][2] = x3;
-  }
+  ts_wave_sum(x);
+  ts_wave_put(s_red, x);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double t1 = 0.0, t2 = 0.0, t3 = 0.0;
-    for (int w = 0; w < DC_TILE / 64; ++w) {
-      t1 += s_red[w][0];
-      t2 += s_red[w][1];
-      t3 += s_red[w][2];
-    }
-    partial[3 * blockIdx.x] = t1;
-    partial[3 * blockIdx.x + 1] = t2;
-    partial[3 * blockIdx.x + 2] = t3;
-  }
+  if (threadIdx.x == 0) ts_waves_in_order(s_red, partial + 3 * blockIdx.x);
 }
 
+// the workgroups' sums in order: one row of nblocks entries
 __global__ void k_decision_stats_final(const double* __restrict__ partial, int nblocks, double* __restrict__ stats) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double t1 = 0.0, t2 = 0.0, t3 = 0.0;
-  for (int i = 0; i < nblocks; ++i) {
-    t1 += partial[3 * i];
-    t2 += partial[3 * i + 1];
-    t3 += partial[3 * i + 2];
-  }
-  stats[0] = t1;
-  stats[1] = t2;
-  stats[2] = t3;
+  if (threadIdx.x == 0 && blockIdx.x == 0) ts_row_sum<3>(partial, 0, (uint32_t)nblocks, stats);
 }
 
 extern "C" int tarl_decision_stats(const float* adv_raw, const int32_t* head_keep, int64_t elems, double* partial,
                                    double* stats3, tarl_stream stream) {
   TARL_REQUIRE(adv_raw && head_keep && partial && stats3 && elems >= 1, "bad argument");
-  const int nb = (int)(ceil_div(elems, DC_TILE) < DC_STAT_BLOCKS ? ceil_div(elems, DC_TILE) : DC_STAT_BLOCKS);
+  const int nb = (int)(ceil_div(elems, TS_TILE) < DC_STAT_BLOCKS ? ceil_div(elems, TS_TILE) : DC_STAT_BLOCKS);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_decision_stats_partial, dim3(nb), dim3(DC_TILE), 0, s, adv_raw, head_keep, elems, partial);
+  hipLaunchKernelGGL(k_decision_stats_partial, dim3(nb), dim3(TS_TILE), 0, s, adv_raw, head_keep, elems, partial);
   TARL_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_decision_stats_final, dim3(1), dim3(64), 0, s, (const double*)partial, nb, stats3);
   TARL_LAUNCH_CHECK();
@@ -454,14 +422,13 @@ __device__ __forceinline__ int32_t dc_softmax_stats(const int32_t* __restrict__ 
 
 // ---- (4) log-prob per node -------------------------------------------------------------------------------------------------
 template <bool SORTED>
-__global__ __launch_bounds__(DC_TILE) void k_graphdist_node_logprob(const int32_t* __restrict__ out_ptr,
+__global__ __launch_bounds__(TS_TILE) void k_graphdist_node_logprob(const int32_t* __restrict__ out_ptr,
                                                                     const int32_t* __restrict__ out_eid,
                                                                     const float* __restrict__ logits, int64_t N, int64_t E,
                                                                     uint32_t tiles, float temperature,
                                                                     const int32_t* __restrict__ choice,
                                                                     float* __restrict__ lp_node) {
-  const uint32_t m = blockIdx.x / tiles, tile = blockIdx.x - m * tiles;
-  const int64_t n = (int64_t)tile * DC_TILE + threadIdx.x;
+  const auto [m, n] = ts_at(tiles);
   if (n >= N) return;
   const float* lb = logits + (int64_t)m * E;
   const int32_t k0 = out_ptr[n], k1 = out_ptr[n + 1];
@@ -480,11 +447,11 @@ extern "C" int tarl_graphdist_node_logprob(const tarl_plan* plan, const float* l
   TARL_REQUIRE(plan && logits && choice && lp_node, "null argument");
   TARL_REQUIRE(M >= 1, "M must be positive");
   TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
-  const int64_t tiles = dc_tiles(plan);
-  TARL_REQUIRE(M * tiles < DC_MAX_BLOCKS, "too many (sample, tile) pairs for one launch");
+  const int64_t tiles = ts_tiles(plan);
+  TS_REQUIRE_PAIRS(M, tiles);
   if (plan->N == 0) return TARL_OK;
 #define DC_LAUNCH(S_)                                                                                                      \
-  hipLaunchKernelGGL(k_graphdist_node_logprob<S_>, dim3((unsigned)(M * tiles)), dim3(DC_TILE), 0, (hipStream_t)stream,     \
+  hipLaunchKernelGGL(k_graphdist_node_logprob<S_>, dim3((unsigned)(M * tiles)), dim3(TS_TILE), 0, (hipStream_t)stream,     \
                      plan->out_ptr, plan->out_eid, logits, plan->N, plan->E, (uint32_t)tiles, temperature, choice, lp_node)
   if (plan->src_sorted)
     DC_LAUNCH(true);
@@ -496,27 +463,22 @@ extern "C" int tarl_graphdist_node_logprob(const tarl_plan* plan, const float* l
 }
 
 // ---- (5) the clipped objective per live decision, forward and backward -----------------------------------------------------------
-struct DcPartial {
-  double gain, live, clipped, kl;
-};
-static_assert(sizeof(DcPartial) == 32, "scratch layout of tarl_graphdist_decision_ppo");
+#define DC_SUMS 4      // per (sample, tile) pair and per sample: {clipped gain, live, ratios outside the clip, lp_old - lp} in fp64
 
 // Must move per (sample, road): head, choice, lp_old, adv_raw (16 B, coalesced); on a live road its out-edges' logits read
 // twice (max, sum) and once more in the backward, and their gradient entries read and written once (+=). Every edge has one
 // source node, so every element of grad has one writer.
 template <bool SORTED>
-__global__ __launch_bounds__(DC_TILE) void k_graphdist_decision_ppo(
+__global__ __launch_bounds__(TS_TILE) void k_graphdist_decision_ppo(
     const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_eid, const float* __restrict__ logits, int64_t N,
     int64_t E, uint32_t tiles, float temperature, const int32_t* __restrict__ choice, const int32_t* __restrict__ head,
     const float* __restrict__ lp_old, const float* __restrict__ adv_raw, const double* __restrict__ stats,
     const int32_t* __restrict__ n_live, float clip_eps, float grad_scale, float* __restrict__ grad,
-    DcPartial* __restrict__ part) {
-  __shared__ double s_red[DC_TILE / 64][4];
-  const uint32_t m = blockIdx.x / tiles, tile = blockIdx.x - m * tiles;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t n = (int64_t)tile * DC_TILE + threadIdx.x;
+    double* __restrict__ part) {
+  __shared__ double s_red[TS_WAVES][DC_SUMS];
+  const auto [m, n] = ts_at(tiles);
   const float* lb = logits + (int64_t)m * E;
-  double v_gain = 0.0, v_live = 0.0, v_clip = 0.0, v_kl = 0.0;
+  double v[DC_SUMS] = {0.0, 0.0, 0.0, 0.0};
   if (n < N && head[(int64_t)m * N + n] > 0) {
     const int32_t k0 = out_ptr[n], k1 = out_ptr[n + 1];
     const int32_t ce = choice[(int64_t)m * N + n];
@@ -537,10 +499,10 @@ __global__ __launch_bounds__(DC_TILE) void k_graphdist_decision_ppo(
       const float g1 = r * a;
       const float g2 = fminf(fmaxf(r, 1.0f - clip_eps), 1.0f + clip_eps) * a;
       const bool flows = g1 <= g2;                                // the unclipped term is the minimum; a tie flows
-      v_gain = (double)(flows ? g1 : g2);
-      v_live = 1.0;
-      v_clip = (r < 1.0f - clip_eps || r > 1.0f + clip_eps) ? 1.0 : 0.0;
-      v_kl = (double)(lo - lp);
+      v[0] = (double)(flows ? g1 : g2);
+      v[1] = 1.0;
+      v[2] = (r < 1.0f - clip_eps || r > 1.0f + clip_eps) ? 1.0 : 0.0;
+      v[3] = (double)(lo - lp);
       const int32_t L = n_live[0];
       if (grad && flows && L > 0) {
         float* gb = grad + (int64_t)m * E;
@@ -553,54 +515,23 @@ __global__ __launch_bounds__(DC_TILE) void k_graphdist_decision_ppo(
       }
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    v_gain += __shfl_down(v_gain, off);
-    v_live += __shfl_down(v_live, off);
-    v_clip += __shfl_down(v_clip, off);
-    v_kl += __shfl_down(v_kl, off);
-  }
-  if (lane == 0) {
-    s_red[wid][0] = v_gain;
-    s_red[wid][1] = v_live;
-    s_red[wid][2] = v_clip;
-    s_red[wid][3] = v_kl;
-  }
+  ts_wave_sum(v);
+  ts_wave_put(s_red, v);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    DcPartial p = {0.0, 0.0, 0.0, 0.0};
-    for (int w = 0; w < DC_TILE / 64; ++w) {
-      p.gain += s_red[w][0];
-      p.live += s_red[w][1];
-      p.clipped += s_red[w][2];
-      p.kl += s_red[w][3];
-    }
-    part[blockIdx.x] = p;
-  }
+  if (threadIdx.x == 0) ts_waves_in_order(s_red, part + (int64_t)blockIdx.x * DC_SUMS);
 }
 
-__global__ __launch_bounds__(64) void k_decision_ppo_reduce(const DcPartial* __restrict__ part, int64_t M, uint32_t tiles,
+__global__ __launch_bounds__(64) void k_decision_ppo_reduce(const double* __restrict__ part, int64_t M, uint32_t tiles,
                                                             double* __restrict__ out4) {
   const int64_t m = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (m >= M) return;
-  DcPartial s = {0.0, 0.0, 0.0, 0.0};
-  for (uint32_t t = 0; t < tiles; ++t) {
-    const DcPartial p = part[m * tiles + t];
-    s.gain += p.gain;
-    s.live += p.live;
-    s.clipped += p.clipped;
-    s.kl += p.kl;
-  }
-  out4[4 * m] = s.gain;
-  out4[4 * m + 1] = s.live;
-  out4[4 * m + 2] = s.clipped;
-  out4[4 * m + 3] = s.kl;
+  if (m < M) ts_row_sum<DC_SUMS>(part, m, tiles, out4);
 }
 
 extern "C" int64_t tarl_graphdist_decision_ppo_scratch_bytes(const tarl_plan* plan, int64_t M) {
   if (!plan || M < 1) return -1;
-  const int64_t tiles = dc_tiles(plan);
-  if (M * tiles >= DC_MAX_BLOCKS) return -1;
-  return M * tiles * (int64_t)sizeof(DcPartial);
+  const int64_t tiles = ts_tiles(plan);
+  if (!ts_pairs_fit(M, tiles)) return -1;
+  return M * tiles * DC_SUMS * (int64_t)sizeof(double);
 }
 
 extern "C" int tarl_graphdist_decision_ppo(const tarl_plan* plan, const float* logits, int64_t M, float temperature,
@@ -614,12 +545,12 @@ extern "C" int tarl_graphdist_decision_ppo(const tarl_plan* plan, const float* l
   TARL_REQUIRE(temperature > 0.0f, "temperature must be positive");
   TARL_REQUIRE(clip_epsilon >= 0.0f && clip_epsilon < 1.0f, "clip_epsilon must be in [0, 1)");
   TARL_REQUIRE(((uintptr_t)scratch) % 8 == 0, "scratch must be 8-byte aligned");
-  const int64_t tiles = dc_tiles(plan);
-  TARL_REQUIRE(M * tiles < DC_MAX_BLOCKS, "too many (sample, tile) pairs for one launch");
+  const int64_t tiles = ts_tiles(plan);
+  TS_REQUIRE_PAIRS(M, tiles);
   hipStream_t s = (hipStream_t)stream;
-  DcPartial* part = (DcPartial*)scratch;
+  double* part = (double*)scratch;
 #define DC_LAUNCH(S_)                                                                                                       \
-  hipLaunchKernelGGL(k_graphdist_decision_ppo<S_>, dim3((unsigned)(M * tiles)), dim3(DC_TILE), 0, s, plan->out_ptr,         \
+  hipLaunchKernelGGL(k_graphdist_decision_ppo<S_>, dim3((unsigned)(M * tiles)), dim3(TS_TILE), 0, s, plan->out_ptr,         \
                      plan->out_eid, logits, plan->N, plan->E, (uint32_t)tiles, temperature, choice, head, lp_old_node,     \
                      adv_raw, stats3, n_live, clip_epsilon, grad_scale, grad_logits, part)
   if (plan->src_sorted)
@@ -628,7 +559,7 @@ extern "C" int tarl_graphdist_decision_ppo(const tarl_plan* plan, const float* l
     DC_LAUNCH(false);
 #undef DC_LAUNCH
   TARL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_decision_ppo_reduce, dim3((unsigned)ceil_div(M, 64)), dim3(64), 0, s, (const DcPartial*)part, M,
+  hipLaunchKernelGGL(k_decision_ppo_reduce, dim3((unsigned)ceil_div(M, 64)), dim3(64), 0, s, (const double*)part, M,
                      (uint32_t)tiles, out4);
   TARL_LAUNCH_CHECK();
   return TARL_OK;

@@ -15,43 +15,36 @@
 //     g2 = min(tt / FF(v) - 1, 8), 0 unless FF(v) > 0                g6 = NUMBER_OF_AGENT(u) == 0 ? 1 : 0
 //     g3 = NUMBER_OF_AGENT(v) / MAXN(v), 0 where MAXN <= 0           g7 = min(FF(v) / S, 8)
 //
-//     pre_j = b1[j] + sum_{k = 0..7} W1[j][k] * g_k   (k ascending, a multiply then an add: -ffp-contract=off, no FMA)
-//     h_j   = pre_j > 0 ? pre_j : 0
-//     logit = b2 + sum_{j = 0..15} w2[j] * h_j        (j ascending)
+//     logit = the 8 -> 16 (ReLU) -> 1 network of mlp8.h on g (its operation order, its flat layout of MLP8_NW floats:
+//             goal_mlp.0.weight, .0.bias, .2.weight, .2.bias)
 //
 // so a numpy fp32 restatement reproduces features and logits bit for bit. An unreachable edge gets exactly PRIOR_UNREACHABLE
-// (-1e20), not mlp - 1e20, and takes no part in the backward; no inf or NaN is emitted. weights / grads: 161 floats,
-// W1 [16][8] at 0, b1 [16] at 128, w2 [16] at 144, b2 at 160 (goal_mlp.0.weight, .0.bias, .2.weight, .2.bias).
+// (-1e20), not mlp - 1e20, and takes no part in the backward; no inf or NaN is emitted.
 //
 // Producers:
 //   * from observations obs16 [M][N][16] (tarl_policy_goal_features, tarl_policy_goal_mlp_fwd, tarl_policy_goal_mlp_bwd): one
 //     thread per (sample, edge) in original edge order, which walks u's out-list for cmin (served by L1) and then evaluates
-//     its own edge. The backward recomputes the features; a workgroup owns a fixed run of (sample, edge) pairs, stages 256 of
-//     them at a time through LDS, and threads 0..160 each sum one gradient element over the pairs in pair order. Partials
-//     [partition][161] go to the caller's scratch, k_goal_bwd_sum adds them in partition order and ACCUMULATES (+=) into
+//     its own edge. The backward recomputes the features; a workgroup owns a fixed run of (sample, edge) pairs and puts them
+//     through mlp8.h's gradient scheme a tile at a time, every lane of the tile a staged row, in pair order. The partials
+//     [partition][MLP8_NW] go to the caller's scratch, k_goal_bwd_sum adds them in partition order and ACCUMULATES (+=) into
 //     grads, as tarl_policy_edge_mlp_bwd does. No float atomics: two runs are bit-identical.
 //   * tarl_fused_goal_mlp_logits: from the packed state, k_prior_fused's shape (a workgroup owns 64 environments x 64 CSR
 //     positions, lanes along the environments, u and v wave-uniform, the tile turned through LDS). Each wave takes 16
 //     CONSECUTIVE positions, so the out-list of a node falls to one wave where it can: on entering a node the wave walks the
 //     node's whole out-list once for cmin (wherever the list starts and ends: a list that straddles waves or tiles is walked
-//     by each of them), then evaluates its own positions, the second read of the same words served by L1/L2. The 161 weights
+//     by each of them), then evaluates its own positions, the second read of the same words served by L1/L2. The weights
 //     are wave-uniform reads of one const __restrict__ array (scalar loads).
 //   * tarl_fused_rollout_goal: the shared loop of the state-dependent heads (tarl_rollout_head) with this head's frame.
 #include <math.h>
 
+#include "mlp8.h"
 #include "prior_tables.h"
 #include "rollout_heads.h"
 
-#define GM_BLOCK 256
+#define GM_BLOCK MLP8_ROWS
 #define GM_TE 64            // environments per fused tile (one per lane)
 #define GM_TK 64            // CSR positions per fused tile
 #define GM_WK (GM_TK / (GM_BLOCK / 64))     // consecutive positions per wave
-#define GM_NF 8
-#define GM_NH 16
-#define GM_NW 161
-#define GM_B1 128
-#define GM_W2 144
-#define GM_B2 160
 #define GM_MAX_PARTS 1024   // partial-sum rows of the backward at most
 
 struct GoalCand {
@@ -61,7 +54,7 @@ struct GoalCand {
 __device__ __forceinline__ bool goal_finite(float c) { return fabsf(c) <= 3.4028234663852886e38f; }     // false for NaN
 
 __device__ __forceinline__ void goal_features(const GoalCand& q, float cmin, bool reach, bool v_is_d, float maxnu, float nau,
-                                              float S, float g[GM_NF]) {
+                                              float S, float g[MLP8_NF]) {
   g[0] = reach ? fminf(((q.D + q.tt) - cmin) / S, 8.0f) : 8.0f;
   g[1] = v_is_d ? 1.0f : 0.0f;
   g[2] = (q.ff > 0.0f) ? fminf(q.tt / q.ff - 1.0f, 8.0f) : 0.0f;
@@ -70,19 +63,6 @@ __device__ __forceinline__ void goal_features(const GoalCand& q, float cmin, boo
   g[5] = fminf(q.D / S, 64.0f) / 8.0f;
   g[6] = (nau == 0.0f) ? 1.0f : 0.0f;
   g[7] = fminf(q.ff / S, 8.0f);
-}
-
-__device__ __forceinline__ float goal_mlp_eval(const float* __restrict__ w, const float g[GM_NF]) {
-  float l = w[GM_B2];
-#pragma unroll
-  for (int j = 0; j < GM_NH; ++j) {
-    float pre = w[GM_B1 + j];
-#pragma unroll
-    for (int k = 0; k < GM_NF; ++k) pre = pre + w[j * GM_NF + k] * g[k];
-    const float h = pre > 0.0f ? pre : 0.0f;
-    l = l + w[GM_W2 + j] * h;
-  }
-  return l;
 }
 
 static __device__ __forceinline__ bool goal_v_is_d(int64_t v, float dest_f) { return (long long)dest_f == (long long)v; }
@@ -99,7 +79,7 @@ template <class Tab>
 __device__ __forceinline__ bool goal_edge_obs(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                               const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_dst,
                                               const float* __restrict__ om, int64_t e, const Tab& tab, float S,
-                                              float g[GM_NF]) {
+                                              float g[MLP8_NF]) {
   const int64_t u = src[e], v = dst[e];
   const float maxnu = om[u * 16 + 0], nau = om[u * 16 + 1], dest = om[u * 16 + 8];
   float cmin = INFINITY;
@@ -127,9 +107,9 @@ __global__ __launch_bounds__(GM_BLOCK) void k_goal_feats(GoalGraph G, const floa
   const int64_t gid = (int64_t)blockIdx.x * GM_BLOCK + threadIdx.x;
   if (gid >= M * G.E) return;
   const int64_t m = gid / G.E, e = gid - m * G.E;
-  float g[GM_NF];
+  float g[MLP8_NF];
   goal_edge_obs(G.src, G.dst, G.out_ptr, G.out_dst, obs + m * G.N * 16, e, tab, S, g);
-  float4* o = reinterpret_cast<float4*>(feats + gid * GM_NF);
+  float4* o = reinterpret_cast<float4*>(feats + gid * MLP8_NF);
   o[0] = make_float4(g[0], g[1], g[2], g[3]);
   o[1] = make_float4(g[4], g[5], g[6], g[7]);
 }
@@ -140,80 +120,65 @@ __global__ __launch_bounds__(GM_BLOCK) void k_goal_fwd(GoalGraph G, const float*
   const int64_t gid = (int64_t)blockIdx.x * GM_BLOCK + threadIdx.x;
   if (gid >= M * G.E) return;
   const int64_t m = gid / G.E, e = gid - m * G.E;
-  float g[GM_NF];
+  float g[MLP8_NF];
   const bool reach = goal_edge_obs(G.src, G.dst, G.out_ptr, G.out_dst, obs + m * G.N * 16, e, tab, S, g);
-  logits[gid] = reach ? goal_mlp_eval(w, g) : PRIOR_UNREACHABLE;
+  logits[gid] = reach ? mlp8_eval(w, g) : PRIOR_UNREACHABLE;
 }
 
 // Partition p owns the pairs [p * chunk, min((p + 1) * chunk, M * E)), chunk a multiple of GM_BLOCK: a function of the
-// shapes alone. Threads 0..160 own one gradient element each and add the staged pairs in pair order.
+// shapes alone. Every pair of a tile is a staged row, in pair order (mlp8.h); an unreachable pair is a row of exact zeros,
+// whatever its grad_logits.
 template <class Tab>
 __global__ __launch_bounds__(GM_BLOCK) void k_goal_bwd(GoalGraph G, const float* __restrict__ obs, int64_t M, Tab tab, float S,
                                                        const float* __restrict__ w, const float* __restrict__ gl,
                                                        int64_t chunk, float* __restrict__ partial) {
-  __shared__ float s_a[GM_BLOCK][GM_NH + 1];     // gl * w2[j] * [pre_j > 0]
-  __shared__ float s_h[GM_BLOCK][GM_NH + 1];     // gl * h_j
-  __shared__ float s_g[GM_BLOCK][GM_NF + 1];
-  __shared__ float s_gl[GM_BLOCK];
+  MLP8_STAGE_ARRAYS;
   const int t = threadIdx.x;
   const int64_t total = M * G.E;
   const int64_t p0 = (int64_t)blockIdx.x * chunk, p1 = (p0 + chunk < total) ? p0 + chunk : total;
   float acc = 0.0f;
   for (int64_t base = p0; base < p1; base += GM_BLOCK) {
     const int64_t gid = base + t;
-    float g[GM_NF], a[GM_NH], gh[GM_NH], r = 0.0f;
+    float g[MLP8_NF], a[MLP8_NH], gh[MLP8_NH], r = 0.0f;
 #pragma unroll
-    for (int k = 0; k < GM_NF; ++k) g[k] = 0.0f;
+    for (int k = 0; k < MLP8_NF; ++k) g[k] = 0.0f;
 #pragma unroll
-    for (int j = 0; j < GM_NH; ++j) a[j] = gh[j] = 0.0f;
+    for (int j = 0; j < MLP8_NH; ++j) a[j] = gh[j] = 0.0f;
     if (gid < p1) {
       const int64_t m = gid / G.E, e = gid - m * G.E;
       if (goal_edge_obs(G.src, G.dst, G.out_ptr, G.out_dst, obs + m * G.N * 16, e, tab, S, g)) {
         r = gl[gid];
 #pragma unroll
-        for (int j = 0; j < GM_NH; ++j) {
-          float pre = w[GM_B1 + j];
-#pragma unroll
-          for (int k = 0; k < GM_NF; ++k) pre = pre + w[j * GM_NF + k] * g[k];
-          a[j] = pre > 0.0f ? r * w[GM_W2 + j] : 0.0f;
-          gh[j] = pre > 0.0f ? r * pre : 0.0f;
-        }
+        for (int j = 0; j < MLP8_NH; ++j) mlp8_row_unit(w, g, r, j, &a[j], &gh[j]);
       } else {
 #pragma unroll
-        for (int k = 0; k < GM_NF; ++k) g[k] = 0.0f;     // an unreachable pair adds exact zeros, whatever its grad_logits
+        for (int k = 0; k < MLP8_NF; ++k) g[k] = 0.0f;     // an unreachable pair adds exact zeros, whatever its grad_logits
       }
     }
     __syncthreads();     // the previous tile has been summed
 #pragma unroll
-    for (int j = 0; j < GM_NH; ++j) {
+    for (int j = 0; j < MLP8_NH; ++j) {
       s_a[t][j] = a[j];
       s_h[t][j] = gh[j];
     }
 #pragma unroll
-    for (int k = 0; k < GM_NF; ++k) s_g[t][k] = g[k];
-    s_gl[t] = r;
+    for (int k = 0; k < MLP8_NF; ++k) s_f[t][k] = g[k];
+    s_r[t] = r;
     __syncthreads();
     const int n = (int)((p1 - base < GM_BLOCK) ? p1 - base : GM_BLOCK);
-    if (t < GM_B1) {
-      const int j = t >> 3, k = t & 7;
-      for (int p = 0; p < n; ++p) acc = acc + s_a[p][j] * s_g[p][k];
-    } else if (t < GM_W2) {
-      for (int p = 0; p < n; ++p) acc = acc + s_a[p][t - GM_B1];
-    } else if (t < GM_B2) {
-      for (int p = 0; p < n; ++p) acc = acc + s_h[p][t - GM_W2];
-    } else if (t == GM_B2) {
-      for (int p = 0; p < n; ++p) acc = acc + s_gl[p];
-    }
+    MLP8_ACCUMULATE(acc, t, n)
   }
-  if (t < GM_NW) partial[(int64_t)blockIdx.x * GM_NW + t] = acc;
+  mlp8_write_partial(partial, blockIdx.x, t, acc);
 }
 
+// One thread per element, the partitions in order. NOT k_dcr_sum's wave per element (decision_critic.hip): that one adds in
+// another order, so sharing either would change the other's gradient bits (mlp8.h).
 __global__ __launch_bounds__(GM_BLOCK) void k_goal_bwd_sum(const float* __restrict__ partial, int64_t parts,
                                                            float* __restrict__ grads) {
   const int t = threadIdx.x;
-  if (t >= GM_NW) return;
+  if (t >= MLP8_NW) return;
   float s = 0.0f;
-  for (int64_t p = 0; p < parts; ++p) s = s + partial[p * GM_NW + t];
+  for (int64_t p = 0; p < parts; ++p) s = s + partial[p * MLP8_NW + t];
   grads[t] = grads[t] + s;
 }
 
@@ -292,7 +257,7 @@ extern "C" int64_t tarl_policy_goal_mlp_bwd_scratch_floats(const tarl_plan* plan
   if (M > ((int64_t)1 << 40) / plan->E || ceil_div(M * plan->E, GM_BLOCK) >= 2147483647LL) return -1;
   int64_t chunk, parts;
   goal_partition(M * plan->E, &chunk, &parts);
-  return parts * GM_NW;
+  return parts * MLP8_NW;
 }
 
 extern "C" int tarl_policy_goal_mlp_bwd(const tarl_plan* plan, const float* obs16, int64_t M, const float* table,
@@ -370,9 +335,9 @@ __global__ __launch_bounds__(GM_BLOCK) void k_goal_fused(const int32_t* __restri
       }
       const GoalCand q = goal_cand_fused(s, B, b, v, dest, tab);
       const bool reach = goal_finite(q.D + q.tt);
-      float g[GM_NF];
+      float g[MLP8_NF];
       goal_features(q, cmin, reach, goal_v_is_d(v, dest), maxnu, nau, S, g);
-      l = reach ? goal_mlp_eval(w, g) : PRIOR_UNREACHABLE;
+      l = reach ? mlp8_eval(w, g) : PRIOR_UNREACHABLE;
     }
     u_prev = u;
     tile[lane][kk] = l;

@@ -65,6 +65,16 @@ class NoStageTimer:
         return False
 
 
+_NO_POINT_AFTER_THE_DRAW = ("draw the actions of all frames ahead of the frames, so there is no point between a frame's draw "
+                            "and its Direction launch where the rule could read that frame's state")
+
+
+def _not_for_embedding(what, why):
+    """The refusal of an option that needs the shared loop of the state-dependent heads."""
+    return (f"{what} is not available for policy='embedding': its rollouts (tarl_fused_rollout, tarl_rollout_env) {why}; "
+            "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+
+
 class VecPPOTrainer:
     def __init__(self, engine, emb_param, critic_params, *, rollout_steps, num_epochs=1, sub_batch_size=32, lr=1e-3,
                  gamma=0.99, lmbda=0.95, clip_epsilon=0.2, entropy_coef=0.01, critic_coef=1.0, temperature=1.0,
@@ -161,15 +171,11 @@ class VecPPOTrainer:
                 raise ValueError("edge_mlp_params must be part of extra_params (the optimiser's flat buffer)")
         elif policy in ("embedding_dijkstra", "goal_mlp"):
             if policy == "goal_mlp":
-                gp = list(goal_mlp_params) if goal_mlp_params is not None else []
-                if engine.fs is None or [tuple(p.shape) for p in gp] != [(16, 8), (16,), (1, 16), (1,)]:
-                    raise ValueError("policy='goal_mlp' needs the fused engine and goal_mlp_params = the four tensors "
-                                     "goal_mlp.{0,2}.{weight,bias} (8 -> 16 -> 1)")
-                pos = {id(p): i for i, p in enumerate(extra_params)}
-                at = [pos.get(id(p), -9) for p in gp]
-                if at[0] < 0 or at != list(range(at[0], at[0] + 4)):
-                    raise ValueError("goal_mlp_params must be part of extra_params (the optimiser's flat buffer), in order and "
-                                     "next to each other")
+                needs = ("policy='goal_mlp' needs the fused engine and goal_mlp_params = the four tensors "
+                         "goal_mlp.{0,2}.{weight,bias} (8 -> 16 -> 1)")
+                if engine.fs is None:
+                    raise ValueError(needs)
+                self._mlp8_params("goal_mlp_params", goal_mlp_params, extra_params, needs)
             if engine.fs is not None and prior_table is None and prior_free_flow is not None and prior_dests is not None:
                 self.prior_table, self.prior_dest_slot = self._build_prior_dest(engine, prior_free_flow, *prior_dests)
             elif engine.fs is None or prior_table is None:
@@ -207,17 +213,11 @@ class VecPPOTrainer:
         self.state_dep = policy != "embedding"
         self.policy_hold = bool(policy_hold)
         if self.policy_hold and not self.state_dep:
-            raise ValueError("policy_hold is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
-                             "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
-                             "between a frame's draw and its Direction launch where the rule could read that frame's state; "
-                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+            raise ValueError(_not_for_embedding("policy_hold", _NO_POINT_AFTER_THE_DRAW))
         self.held = torch.zeros(engine.B, dtype=torch.int32, device=engine.device) if self.policy_hold else None
         self.route_departures = bool(route_departures)
         if self.route_departures and not self.state_dep:
-            raise ValueError("route_departures is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
-                             "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
-                             "between a frame's draw and its Direction launch where the rule could read that frame's state; "
-                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+            raise ValueError(_not_for_embedding("route_departures", _NO_POINT_AFTER_THE_DRAW))
         self.departures_routed = self._departure_router = None
         if self.route_departures:
             if engine.fs is None:
@@ -232,10 +232,9 @@ class VecPPOTrainer:
             raise ValueError("reward must be 'queue' or 'trip'")
         self.reward_kind = reward
         if reward == "trip" and not self.state_dep:
-            raise ValueError("reward='trip' is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
-                             "tarl_rollout_env) do not go through the shared loop of the state-dependent heads, where the "
-                             "trip launch follows every frame's insert; "
-                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+            raise ValueError(_not_for_embedding(
+                "reward='trip'", "do not go through the shared loop of the state-dependent heads, where the trip launch "
+                                 "follows every frame's insert"))
         if reward == "trip" and engine.fs is None:
             raise ops._lib.TarlError("reward='trip' needs the fused engine (ops.fused_path_supported): the packed state "
                                      "cannot represent this graph and there is no fall-back")
@@ -279,13 +278,10 @@ class VecPPOTrainer:
         dist_utils.broadcast_(self.flat.flat, src=0)
         self.goal_mlp_params = list(goal_mlp_params) if policy == "goal_mlp" else None
         if policy == "goal_mlp":      # one run of the flat buffer, in the kernels' order; the time scale of the engine's roads
-            self._goal_off = self.flat.offsets[id(self.goal_mlp_params[0])][0]
-            assert self.flat.offsets[id(self.goal_mlp_params[3])][0] == self._goal_off + ops.GOAL_MLP_PARAMS - 1
+            self._goal_off = self._mlp8_offset(self.goal_mlp_params)
             self.goal_scale = ops.goal_time_scale(engine._x[0, :, 3 * engine.Nmax:])
         if self.decision_critic_params is not None:      # one run of the flat buffer, as the goal head's
-            self._dcritic_off = self.flat.offsets[id(self.decision_critic_params[0])][0]
-            assert (self.flat.offsets[id(self.decision_critic_params[3])][0]
-                    == self._dcritic_off + ops.DECISION_CRITIC_PARAMS - 1)
+            self._dcritic_off = self._mlp8_offset(self.decision_critic_params)
             self.frames_left = self.adv_dec = None
         B, N, dev = engine.B, engine.N, engine.device
         # which rollout kernel family: "env" = one workgroup per environment, records in LDS, one launch for all frames
@@ -353,10 +349,9 @@ class VecPPOTrainer:
     def _check_decision_credit(self, engine, value):
         """Refusals of credit="decision", each naming its limit; its counters and the slot of the distance table."""
         if not self.state_dep:
-            raise ValueError("credit='decision' is not available for policy='embedding': its rollouts (tarl_fused_rollout, "
-                             "tarl_rollout_env) draw the actions of all frames ahead of the frames, so there is no point "
-                             "in front of a frame's draw where the heads of that frame's state could be captured; "
-                             "use a state-dependent head (edge_mlp, embedding_dijkstra, graph_transformer, goal_mlp)")
+            raise ValueError(_not_for_embedding(
+                "credit='decision'", "draw the actions of all frames ahead of the frames, so there is no point in front of a "
+                                     "frame's draw where the heads of that frame's state could be captured"))
         if engine.fs is None:
             raise ops._lib.TarlError("credit='decision' needs the fused engine (ops.fused_path_supported): the packed state "
                                      "cannot represent this graph and there is no fall-back")
@@ -390,24 +385,44 @@ class VecPPOTrainer:
         if credit != "decision":
             raise ValueError("credit_baseline='learned' is the baseline of the per-decision advantage: it needs "
                              "credit='decision'")
-        cp = list(params) if params is not None else []
-        if [tuple(p.shape) for p in cp] != [(16, 8), (16,), (1, 16), (1,)]:
-            raise ValueError("credit_baseline='learned' needs decision_critic_params = the four tensors w1 (16, 8), b1 (16,), "
-                             "w2 (1, 16), b2 (1,) (8 -> 16 -> 1)")
-        pos = {id(p): i for i, p in enumerate(extra_params)}
-        at = [pos.get(id(p), -9) for p in cp]
-        if at[0] < 0 or at != list(range(at[0], at[0] + 4)):
-            raise ValueError("decision_critic_params must be part of extra_params (the optimiser's flat buffer), in order and "
-                             "next to each other")
+        cp = self._mlp8_params("decision_critic_params", params, extra_params,
+                               "credit_baseline='learned' needs decision_critic_params = the four tensors w1 (16, 8), b1 (16,), "
+                               "w2 (1, 16), b2 (1,) (8 -> 16 -> 1)")
         if not self.decision_critic_coef >= 0.0 or not math.isfinite(self.decision_critic_coef):
             raise ValueError("decision_critic_coef must be finite and >= 0")
         if not (math.isfinite(self.decision_delay_scale) and self.decision_delay_scale > 0.0):
             raise ValueError("decision_delay_scale must be positive and finite")
         return cp
 
+    @staticmethod
+    def _mlp8_params(name, params, extra_params, needs):
+        """The four tensors of an 8 -> 16 -> 1 network (the goal head, the decision critic) -> their list; refused (``needs``)
+        unless they are w1 (16, 8), b1 (16,), w2 (1, 16), b2 (1,) and one consecutive run of ``extra_params``, so that the
+        kernels read them as ONE run of the flat buffer."""
+        ps = list(params) if params is not None else []
+        if [tuple(p.shape) for p in ps] != [(16, 8), (16,), (1, 16), (1,)]:
+            raise ValueError(needs)
+        pos = {id(p): i for i, p in enumerate(extra_params)}
+        at = [pos.get(id(p), -9) for p in ps]
+        if at[0] < 0 or at != list(range(at[0], at[0] + 4)):
+            raise ValueError(f"{name} must be part of extra_params (the optimiser's flat buffer), in order and "
+                             "next to each other")
+        return ps
+
+    def _mlp8_offset(self, params):
+        """Where the run of :meth:`_mlp8_params` starts in the flat buffer."""
+        off = self.flat.offsets[id(params[0])][0]
+        assert self.flat.offsets[id(params[3])][0] == off + ops.GOAL_MLP_PARAMS - 1
+        return off
+
+    def _mlp8_view(self, buf, off):
+        """The network's 161 floats of ``buf`` (``flat.flat`` or ``flat.grad``) in the kernels' order: one layout for the
+        goal head and the decision critic (csrc/mlp8.h)."""
+        assert ops.GOAL_MLP_PARAMS == ops.DECISION_CRITIC_PARAMS
+        return buf[off:off + ops.GOAL_MLP_PARAMS]
+
     def _dcritic(self):
-        return ops.DecisionCriticWeights(
-            flat=self.flat.flat[self._dcritic_off:self._dcritic_off + ops.DECISION_CRITIC_PARAMS])
+        return ops.DecisionCriticWeights(flat=self._mlp8_view(self.flat.flat, self._dcritic_off))
 
     def _build_decision_dist(self):
         """Free-flow shortest-path distances to every distinct destination (ops.destination_trees on the travel times of the
@@ -498,7 +513,7 @@ class VecPPOTrainer:
         return ops.GtWeights(self.gt_params)
 
     def _goal(self):
-        return ops.GoalMlpWeights(flat=self.flat.flat[self._goal_off:self._goal_off + ops.GOAL_MLP_PARAMS])
+        return ops.GoalMlpWeights(flat=self._mlp8_view(self.flat.flat, self._goal_off))
 
     def _gt_value(self):
         return ops.GtValueWeights(self.gt_value_params)
@@ -767,7 +782,7 @@ class VecPPOTrainer:
             if getattr(self, "_goal_scratch", None) is None or self._goal_scratch.numel() < need:
                 self._goal_scratch = torch.empty(need, dtype=torch.float32, device=eng.device)     # once per trainer
             ops.policy_goal_mlp_bwd(eng.plan, obs, self._goal(), self.prior_table, self.goal_scale, g_logits,
-                                    self.flat.grad[self._goal_off:self._goal_off + ops.GOAL_MLP_PARAMS],
+                                    self._mlp8_view(self.flat.grad, self._goal_off),
                                     dest_slot=self.prior_dest_slot, scratch=self._goal_scratch)
         else:       # the prior has no parameters: the embedding receives the logits' gradient as is
             g_emb = ops.policy_edge_logits_bwd(eng.plan, obs, g_logits, self.emb_param.numel())
@@ -958,7 +973,7 @@ class VecPPOTrainer:
             self.eng.plan, obs, self.head_keep[off:off + M], self.frames_left[off:off + M], dist, slot, self._dcritic(),
             self.adv_raw[off:off + M], self._decision_last[1], timestep=self.eng.timestep,
             delay_scale=self.decision_delay_scale, coef=self.decision_critic_coef, grad_scale=scale,
-            grads=self.flat.grad[self._dcritic_off:self._dcritic_off + ops.DECISION_CRITIC_PARAMS],
+            grads=self._mlp8_view(self.flat.grad, self._dcritic_off),
             scratch=self._dcritic_scratch)
         self._dcritic_last = (out5, off, M)      # summed where the report is built: no further launch per step
 
